@@ -8,9 +8,13 @@ timed region contains the step kernels, the per-episode statistics kernel, the p
 N > 1 -- the RCCL all-gather of the episode statistics (the only collective on the path).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4] [--envs E_per_gpu]
-                  [--launch per_step|persistent] [--actor mlp]
+                  [--launch per_step|persistent] [--actor mlp] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` and `cpu_baseline`.
+A plain run sets up, runs W warm-up steps, times exactly K steps (one region, wall clock between device synchronisations),
+optionally writes the outputs of the last timed step (--dump-outputs) and prints ONE JSON line (rank 0) with the contract
+fields.  --full adds everything else the benchmark measures or checks: both launch modes timed with repetitions, the roofline
+passes, the whole-episode pass, the policy-in-the-loop / collector / device-refill / strided records, the other workloads,
+the RCCL self-checks and the CPU baseline (`roofline`, `cpu_baseline`, ... on the same line).
 """
 import argparse
 import json
@@ -469,6 +473,31 @@ def strided_record(eng, loop, E, P, D, T, dev, bytes_env_step, stride0_launch_us
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # under 64 MB by either reading of "MB"
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES, seed=2026):
+    """--dump-outputs: `arrays` (name -> device or host array, first axis = env rows) as DIR/<name>.npy; floating outputs in float64, the
+    integer ones (done, action mask) as float32.  When they exceed `budget` bytes together, a fixed, seeded sample of rows -- the same rows for
+    every array of the same length -- is written instead, and its row indices as DIR/sampled_rows_<length>.npy."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype.kind == "f" else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > budget:
+        keep = budget / total
+        rows = {}
+        for n in sorted({a.shape[0] for a in host.values()}):
+            rows[n] = np.sort(np.random.default_rng(seed).choice(n, size=max(1, int(n * keep) - 1), replace=False))
+            host[f"sampled_rows_{n}"] = rows[n].astype(np.float64)
+        host = {k: (v if k.startswith("sampled_rows_") else v[rows[v.shape[0]]]) for k, v in host.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(host)
+
+
 def self_launch(n_gpus, argv):
     """`python bench.py --gpus N` with no rendezvous in the environment: re-run this file as N ranks (one per GPU) under
     torch.distributed.run on this node -- the command the driver would type itself -- and pass rank 0's JSON line through."""
@@ -531,8 +560,8 @@ def main():
     ap.add_argument("--pool", type=int, default=0, help="scenario pool size as a multiple of --envs (default 8; cfg4: 2): every "
                     "episode steps a fresh window of the resident pool (the per-reset scenario draw of the reference)")
     ap.add_argument("--launch", default="auto", choices=["auto", "per_step", "persistent"])
-    ap.add_argument("--min-time", type=float, default=0.25, help="repeat the --steps-sized timed region until this many seconds "
-                    "have been measured per launch mode (median over the repetitions is reported)")
+    ap.add_argument("--min-time", type=float, default=0.25, help="with --full: repeat the --steps-sized timed region until this many "
+                    "seconds have been measured per launch mode (median over the repetitions is reported next to the headline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-soc-log", action="store_true", help="skip the SoC log that the battery-degradation statistics need")
     ap.add_argument("--actor-groups", type=int, default=1, help="with --actor mlp: split the envs of a GPU into this many independently "
@@ -546,9 +575,15 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-rollout-record", action="store_true", help="skip the short policy-in-the-loop pass (`rollout` in the line)")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the short cfg3 / cfg4 passes (`other_workloads` in the cfg2 line)")
-    ap.add_argument("--only-timed", action="store_true", help="profiling runs: nothing but the timed regions of the chosen launch mode "
-                    "(no whole-episode pass, no HIP-event roofline pass, no rollout record), so that a kernel trace of `--launch per_step` "
+    ap.add_argument("--only-timed", action="store_true", help="profiling runs with --full: nothing but the timed regions of the chosen launch "
+                    "mode (no whole-episode pass, no HIP-event roofline pass, no rollout record), so that a kernel trace of `--launch per_step` "
                     "holds single-step dispatches only")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: both launch modes timed with repetitions "
+                    "(--min-time), roofline and whole-episode passes, the rollout / collector / refill / strided records, the other "
+                    "workloads, the RCCL self-checks and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(observations, rewards, dones, action masks, the last episode statistics) as DIR/<name>.npy, float64 / float32, "
+                    "at most 64 MB in all (a fixed, seeded sample of env rows beyond that)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help=argparse.SUPPRESS)   # gloo: CPU launcher test only
     ap.add_argument("--engine", default="", help=argparse.SUPPRESS)   # module:Class of a stand-in engine (tests only)
     args = ap.parse_args()
@@ -616,11 +651,12 @@ def main():
         if args.actor == "none":
             acts = torch.empty((T, Eg, P), dtype=torch.float64, device=dev)
             eng.fill_uniform(acts, T * Eg * P, 999 + rank, wl["lo"], 1.0)
-        obs = torch.empty((Eg, D), dtype=torch.float64, device=dev)
-        rew = torch.empty((Eg,), dtype=torch.float64, device=dev)
-        done = torch.empty((Eg,), dtype=torch.uint8, device=dev)
-        mask = torch.empty((Eg, P), dtype=torch.uint8, device=dev)
-        stats = torch.empty((Eg, _abi.N_STATS), dtype=torch.float64, device=dev)
+        # (zeroed, not empty: --dump-outputs writes these buffers, also a statistics block no episode end has filled yet)
+        obs = torch.zeros((Eg, D), dtype=torch.float64, device=dev)
+        rew = torch.zeros((Eg,), dtype=torch.float64, device=dev)
+        done = torch.zeros((Eg,), dtype=torch.uint8, device=dev)
+        mask = torch.zeros((Eg, P), dtype=torch.uint8, device=dev)
+        stats = torch.zeros((Eg, _abi.N_STATS), dtype=torch.float64, device=dev)
         g_actor = None
         if args.actor != "none":
             from ev2gym_amd.actor import make_actor
@@ -639,8 +675,26 @@ def main():
             dist.barrier()
         devx.synchronize()
 
+    def timed_region(persistent):
+        """The headline: --warmup steps, then exactly --steps steps timed as ONE region bracketed by barrier + synchronize; episode ends
+        (statistics kernel, gather, reset onto fresh scenarios) fall where they fall inside it.  Returns (the slowest rank's seconds, this
+        rank's seconds)."""
+        loop.reset()
+        loop.run(args.warmup, persistent)
+        loop.reset()
+        barrier()
+        t0 = time.perf_counter()
+        loop.run(args.steps, persistent)
+        barrier()
+        mine = time.perf_counter() - t0
+        if not multi:
+            return mine, mine
+        tt = torch.tensor([mine], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        return float(tt.item()), mine
+
     def timed(persistent):
-        """Median over repetitions of the --steps-sized region.  One repetition = a chain of whole --steps regions long
+        """--full: median over repetitions of the --steps-sized region.  One repetition = a chain of whole --steps regions long
         enough to out-weigh the launch / synchronisation edges (>= 20 ms), bracketed by barrier + synchronize; episode ends
         (statistics kernel, gather, reset onto fresh scenarios) fall where they fall inside the chain."""
         loop.reset()
@@ -673,14 +727,26 @@ def main():
                 break
         return float(np.median(samples)), len(samples), inner, samples
 
-    modes = ["per_step", "persistent"] if args.launch == "auto" else [args.launch]
+    # the headline's launch mode: `auto` = one persistent launch per episode (a policy in the loop forces per_step above), the faster
+    # mode at every workload (--full times both and reports them side by side)
+    mode = "persistent" if args.launch == "auto" else args.launch
+    wall_s, my_wall_s = timed_region(mode == "persistent")
+    if args.dump_outputs and rank == 0:
+        cat = (lambda xs: xs[0]) if n_groups == 1 else torch.cat
+        arrays = {"obs": cat([l.obs for l in loops]), "reward": cat([l.rew for l in loops]), "done": cat([l.done for l in loops]),
+                  "action_mask": cat([l.mask for l in loops])}
+        last_stats = cat([l.stats for l in loops]) if gath is None else gath.finish()   # (the gathered rows at N > 1)
+        if last_stats is not None:
+            arrays["episode_stats"] = last_stats
+        dump_outputs(args.dump_outputs, arrays)
+
+    modes = (["per_step", "persistent"] if args.launch == "auto" else [args.launch]) if args.full else []
     res = {m: timed(m == "persistent") for m in modes}
     wall = {m: r[0] for m, r in res.items()}
-    best = min(wall, key=wall.get)
 
     # whole episodes, the RL-free upper bound of the path: one 112-step persistent launch + statistics + reset per episode
     full_ep = None
-    if actor is None and not args.only_timed:
+    if args.full and actor is None and not args.only_timed:
         def agree_max(n):
             if not multi:
                 return n
@@ -733,7 +799,7 @@ def main():
         loop.reset()
         return step_us, actor_us
 
-    if args.only_timed:
+    if not args.full or args.only_timed:
         roof = {m: None for m in modes}
     elif actor is None:
         roof = {m: roofline(m) for m in modes}
@@ -742,14 +808,14 @@ def main():
         step_frac = bytes_env_step * Eg / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBPS
         roof = {m: None for m in modes}
         actor_times = {"step_kernel_us": step_us, "actor_kernel_us": actor_us, "step_kernel": eng.kernel_name,
-                       "step_kernel_roofline_frac": step_frac, "ms_per_step_wall": wall[best] / args.steps * 1e3}
+                       "step_kernel_roofline_frac": step_frac, "ms_per_step_wall": wall_s / args.steps * 1e3}
     for e_ in engines:
         e_.check_faults()
 
     # the configs[4]-shaped number for the driver's default run: a short policy-in-the-loop pass (fused actor obs->400->300->P
     # between single-step launches) on a second handle over the same scenario pool, after the headline measurement
     rollout = None
-    if actor is None and not stub and not args.no_rollout_record and not args.only_timed and args.workload != "cfg4":
+    if args.full and actor is None and not stub and not args.no_rollout_record and not args.only_timed and args.workload != "cfg4":
         rollout = rollout_record(Engine, batch, rk, sk, local_rank, devx, E, wl["lo"], rank, args, T, bytes_env_step)
         try:
             rollout["collector"] = collector_record(Engine, batch, rk, sk, local_rank, devx, E, wl["lo"], rank, args, T)
@@ -766,7 +832,7 @@ def main():
     # outside the timed regions: the C-ABI's own RCCL gather (ev2g_comm_init / ev2g_gather_stats, the path of hosts without
     # torch.distributed) next to torch's, on the same statistics
     c_gather = None
-    if multi and hasattr(Engine, "comm_unique_id"):
+    if args.full and multi and hasattr(Engine, "comm_unique_id"):
         # every rank takes part in every collective below whatever fails locally (an exception on one rank only would leave the
         # others waiting): local failures are carried in `err` and agreed on before the next collective step
         from ev2gym_amd.dist import gather_stats_tensor
@@ -806,7 +872,7 @@ def main():
     # reports the communicator it is in -- the C-ABI communicator's rank count, a hash of the unique id it was handed -- and a block of GLOBAL
     # env ids travels through the same all-gather as the statistics: block r must hold rank r's ids, first to last
     self_check = None
-    if multi:
+    if args.full and multi:
         import hashlib
         env_ids = torch.arange(E, dtype=torch.int64, device=dev) + rank * E
         all_ids = torch.empty((world * E,), dtype=torch.int64, device=dev)
@@ -824,17 +890,17 @@ def main():
                       "every_rank_sees_world": all(p_["c_abi_comm_world_size"] in (None, world) for p_ in per)}
 
     refill = None
-    if actor is None and not stub and not args.no_rollout_record and not args.only_timed and args.workload != "cfg4":
+    if args.full and actor is None and not stub and not args.no_rollout_record and not args.only_timed and args.workload != "cfg4":
         refill = refill_record(Engine, wl, rk, sk, local_rank, devx, E, rank, args, T)
 
     # the persistent launch with every output KEPT ([T,E,*] blocks), and the other BASELINE single-GPU configs, on the same line
     strided, others = None, None
-    if actor is None and not stub and not args.only_timed and n_groups == 1 and "persistent" in modes:
+    if args.full and actor is None and not stub and not args.only_timed and n_groups == 1 and "persistent" in modes:
         try:
             strided = strided_record(eng, loop, E, P, D, T, dev, bytes_env_step, (roof.get("persistent") or {}).get("avg_launch_us"))
         except Exception as ex:   # (a record next to the headline: never lets the line fail)
             strided = {"error": f"{type(ex).__name__}: {ex}"}
-    if actor is None and not stub and not args.only_timed and not args.no_other_workloads and args.workload == "cfg2" and world == 1:   # (N = 1 records, like cpu_baseline)
+    if args.full and actor is None and not stub and not args.only_timed and not args.no_other_workloads and args.workload == "cfg2" and world == 1:   # (N = 1 records, like cpu_baseline)
         others = {}
         for name in ("cfg3", "cfg4"):
             Eo = max(64, WORKLOADS[name]["envs"] * E // wl["envs"])
@@ -844,10 +910,10 @@ def main():
                 others[name] = {"error": f"{type(ex).__name__}: {ex}"}
 
     env_steps_total = world * E * args.steps
-    value = env_steps_total / wall[best]
+    value = env_steps_total / wall_s
     per_rank, ranks_seen = None, None
     if multi:   # what every rank measured itself (the driver computes scaling efficiency from `value`)
-        mine = torch.tensor([E * args.steps / float(np.median(res[best][3]))], dtype=torch.float64, device=dev)
+        mine = torch.tensor([E * args.steps / my_wall_s], dtype=torch.float64, device=dev)
         allv = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allv, mine)
         per_rank = [float(v.item()) for v in allv]
@@ -861,28 +927,31 @@ def main():
     out = {
         "metric": "env-steps/sec (envs x chargers x steps); % HBM roofline",
         "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall[best] / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "reps": res[best][1], "regions_per_rep": res[best][2], "timing": "median over reps of (chain of `regions_per_rep` x `steps`-step regions) / regions_per_rep",
+        "ms_per_step": wall_s / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
+        "timing": "one region of `steps` steps after `warmup` warm-up steps, wall clock between device synchronisations (N > 1: the slowest rank's)",
         "config": {"workload": f"{args.workload}: {wl['desc']}", "envs_per_gpu": E, "scenario_pool_per_gpu": M, "scenario_pool_order": "generated" if args.keep_pool_order else "sorted by busy window inside every window of envs_per_gpu scenarios", "chargers": C_,
                    "transformers": R_, "steps_per_episode": T, "obs_dim": D, "occupancy_phi": round(phi, 4),
                    "algorithmic_bytes_per_env_step": bytes_env_step, "soc_log": not args.no_soc_log,
-                   "launch": best, "actor": args.actor if actor is None else actor.describe,
+                   "launch": mode, "actor": args.actor if actor is None else actor.describe,
                    "actor_env_groups": (n_groups if actor is not None else None),
                    "parallelism": f"env-sharded x{world}, RCCL all_gather of episode stats only (asynchronous; submitted behind the next episode's step kernel: dist.AsyncStatsGather)",
                    "stats_gather_mode": (getattr(gath, "mode", None) if gath is not None else None)},
         "port_steps_per_s": value * P,
-        "wall_s_by_launch_mode": {m: round(w, 6) for m, w in wall.items()},
-        "env_steps_per_s_by_launch_mode": {m: env_steps_total / w for m, w in wall.items()},
         "full_episode": full_ep,
-        "roofline": roof[best],
-        "roofline_by_launch_mode": roof,
+        "roofline": roof.get(mode),
+        "roofline_by_launch_mode": roof or None,
         "rccl_ranks_seen": ranks_seen, "per_rank_env_steps_per_s": per_rank,
         "rccl_collectives_issued": (gath.collectives if gath is not None else 0),
         "c_abi_rccl_gather": c_gather,
         "rccl_self_check": self_check,
     }
-    if actor is not None and not args.only_timed:
+    if args.full:   # the --steps-sized region again, repeated for --min-time per launch mode (the headline's timing up to round 6)
+        out["wall_s_by_launch_mode"] = {m: round(w, 6) for m, w in wall.items()}
+        out["env_steps_per_s_by_launch_mode"] = {m: env_steps_total / w for m, w in wall.items()}
+        out["repeated_timing"] = {m: {"reps": r[1], "regions_per_rep": r[2], "ms_per_step": r[0] / args.steps * 1e3} for m, r in res.items()}
+        out["repeated_timing"]["timing"] = "median over reps of (chain of `regions_per_rep` x `steps`-step regions) / regions_per_rep"
+    if args.full and actor is not None and not args.only_timed:
         out["actor_kernel_times"] = actor_times
     if rollout is not None:
         out["rollout"] = rollout
@@ -902,7 +971,7 @@ def main():
         dist.destroy_process_group()
     # after the process group is gone (no rank waits for this): the CPU baseline on rank 0's host cores.  At N > 1 the other
     # ranks' processes are winding down meanwhile, so the sample is shorter there and the N = 1 line is the one to quote.
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         budget = float(os.environ.get("EV2G_BENCH_CPU_BUDGET", "12.0" if world == 1 else "4.0"))
         out["cpu_baseline"] = cpu_baseline(batch.select(np.arange(min(E, 512))), rk, sk, wl["lo"], budget_s=budget)
     elif rank == 0:

@@ -6,5 +6,5 @@ timeout 900 python -m pytest tests -m gpu -q -x -k "collector or rollout or acto
 for nf in 0 1; do
   if [ $nf = 1 ]; then export EV2G_NO_FUSED=1; else unset EV2G_NO_FUSED; fi
   timeout 300 python tools/sb3_collect_bench.py cfg2 2>&1 | grep -v amdgpu.ids | tail -1 | tee $O/collector_cfg2_nofused$nf.json
-  timeout 300 python bench.py --actor mlp --no-cpu-baseline 2> $O/bench_actor_$nf.err | tee $O/bench_actor_nofused$nf.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('actor bench nofused=$nf', d['value'], d['ms_per_step'], d.get('actor_kernel_times'))"
+  timeout 300 python bench.py --full --actor mlp --no-cpu-baseline 2> $O/bench_actor_$nf.err | tee $O/bench_actor_nofused$nf.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('actor bench nofused=$nf', d['value'], d['ms_per_step'], d.get('actor_kernel_times'))"
 done

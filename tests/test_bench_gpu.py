@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -13,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("extra", [[], ["--workload", "cfg3"], ["--actor", "mlp"]], ids=["cfg2", "cfg3", "actor"])
 def test_bench_line_contract(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--envs", "512", "--steps", "20", "--warmup", "5", "--min-time", "0.02"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--envs", "512", "--steps", "20", "--warmup", "5", "--min-time", "0.02", "--full"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env={**os.environ, "EV2G_BENCH_CPU_BUDGET": "1.5"})
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
@@ -56,12 +57,37 @@ def test_bench_line_contract(extra):
         assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and "sample" in cb
 
 
+def test_plain_bench_line_times_the_steps_asked_for_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full): exactly --steps timed steps behind `ms_per_step`, no --full record on the line, and --dump-outputs writes the
+    last timed step's outputs -- the same bits from two runs with the same arguments (seeded scenarios and actions, deterministic kernels)."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs", "512", "--steps", "150", "--warmup", "10", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(line) == 1, p.stdout[-2000:]
+        out = json.loads(line[0])
+        assert out["steps"] == 150 and out["warmup"] == 10 and out["full"] is False and out["dtype"] == "f64" and out["higher_is_better"] is True
+        assert out["value"] > 1e6 and abs(out["value"] - 512 * 150 / (out["ms_per_step"] * 150 / 1e3)) <= 1e-6 * out["value"]
+        assert out["roofline"] is None and out["cpu_baseline"] is None and "rollout" not in out and "other_workloads" not in out
+        arrs = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sorted(arrs) == ["action_mask.npy", "done.npy", "episode_stats.npy", "obs.npy", "reward.npy"], sorted(arrs)
+        assert arrs["obs.npy"].shape == (512, out["config"]["obs_dim"]) and arrs["obs.npy"].dtype == np.float64
+        assert all(np.isfinite(a).all() for k, a in arrs.items() if k != "episode_stats.npy")
+        assert np.nansum(np.abs(arrs["episode_stats.npy"])) > 0      # 150 steps: one episode (112 steps) ended inside the run
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k
+
+
 def test_default_bench_line_holds_the_roofline_fractions():
     """Performance guard (round 6): the default `python bench.py` line -- BASELINE configs[1] at full size, with configs[2] / configs[3] riding on it --
     must keep the roofline fractions the kernels were tuned to.  The fast-path instantiations sit at the 128-register limit and depend on
     `-mllvm -disable-machine-licm` (ev2gym_amd/build.py); the big-env kernel on two workgroups per CU: a toolchain bump that breaks either shows
     up here as a red test instead of a silently slower library.  Floors are ~10 % under the round's measurements (boxes differ by ~3 %)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])

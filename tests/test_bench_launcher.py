@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +27,7 @@ def run_bench(*extra, env_extra=None):
 
 @pytest.mark.timeout(600)
 def test_bench_gpus_2_starts_its_own_ranks_and_reports_what_the_communicator_saw():
-    out = run_bench("--gpus", "2")
+    out = run_bench("--gpus", "2", "--full")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["steps"] == 40 and out["warmup"] == 5
     seen = out["rccl_ranks_seen"]
     assert seen["process_group_size"] == 2 and seen["all_gather_blocks"] == 2 and seen["backend"] == "gloo"
@@ -51,12 +52,35 @@ def test_bench_gpus_2_starts_its_own_ranks_and_reports_what_the_communicator_saw
 
 @pytest.mark.timeout(600)
 def test_bench_single_process_line_has_the_contract_fields():
-    out = run_bench("--gpus", "1", "--launch", "persistent")
+    out = run_bench("--gpus", "1", "--launch", "persistent", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in out
     assert out["n_gpus"] == 1 and out["rccl_ranks_seen"] is None and out["vs_baseline"] is None and out["dtype"] == "f64"
     assert out["config"]["launch"] == "persistent" and "workload" in out["config"]
+
+
+@pytest.mark.timeout(600)
+def test_plain_bench_times_exactly_the_steps_asked_for_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full): the contract fields only, exactly --steps timed steps, none of the --full records, and --dump-outputs writes
+    what the last timed step returned -- float32 / float64 arrays, the same ones for the same arguments."""
+    outs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = run_bench("--gpus", "1", "--dump-outputs", str(d))
+        assert out["steps"] == 40 and out["warmup"] == 5 and out["full"] is False and out["config"]["launch"] == "persistent"
+        assert out["value"] == pytest.approx(4 * 40 / (out["ms_per_step"] * 40 / 1e3), rel=1e-9)
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in out
+        assert out["roofline"] is None and out["full_episode"] is None and out["cpu_baseline"] is None
+        assert not {"rollout", "device_refill", "persistent_strided", "other_workloads", "repeated_timing"} & set(out)
+        files = sorted(os.listdir(d))
+        assert files == ["action_mask.npy", "done.npy", "episode_stats.npy", "obs.npy", "reward.npy"], files
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and a.shape[0] == 4 for a in arrs.values())
+        outs.append(arrs)
+    for f in outs[0]:
+        assert np.array_equal(outs[0][f], outs[1][f], equal_nan=True), f
 
 
 def test_world_size_mismatch_is_an_error():

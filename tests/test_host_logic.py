@@ -557,19 +557,34 @@ def test_demand_response_window_before_the_simulation_start_follows_python_slice
 
 def test_native_generator_survives_a_request_it_cannot_allocate():
     """ev2g_generate must hand an error code back (no exception crosses the C-ABI, worker threads included): a batch far beyond
-    the host's memory is refused, and the library keeps working afterwards."""
-    import ctypes as C
-    from ev2gym_amd.engine import load_library
-    L = load_library()
-    cfg = _abi.GenConfigC()
-    assert L.ev2g_gen_default_config(0, C.byref(cfg)) == 0
-    cfg.number_of_charging_stations = 1000
-    cfg.number_of_transformers = 50
-    out = C.c_void_p()
-    rc = L.ev2g_generate(C.byref(cfg), 2**31 - 1, 1, 8, C.byref(out))   # the first array alone (prices, [M, T] float64) would be 1.9 TB
-    assert rc != 0 and not out.value
-    assert L.ev2g_generate(C.byref(cfg), 2, 1, 2, C.byref(out)) == 0 and out.value
-    L.ev2g_gen_free(out)
+    the memory the process may use is refused, and the library keeps working afterwards.  Run in a child process whose address space
+    is capped 8 GB above what it maps once the library is loaded (RLIMIT_AS): whether the request fails must not depend on how much
+    RAM the host has or how it overcommits -- a host that grants it would fill the 1.9 TB batch instead."""
+    import subprocess
+    import sys
+    code = f"""if True:
+        import ctypes as C, resource, sys
+        sys.path.insert(0, {ROOT!r})
+        from ev2gym_amd import _abi
+        from ev2gym_amd.engine import load_library
+        L = load_library()
+        vm = int([l.split()[1] for l in open("/proc/self/status") if l.startswith("VmSize:")][0]) * 1024
+        hard = resource.getrlimit(resource.RLIMIT_AS)[1]
+        cap = vm + 8 * 2**30
+        resource.setrlimit(resource.RLIMIT_AS, (cap if hard == resource.RLIM_INFINITY else min(cap, hard), hard))
+        cfg = _abi.GenConfigC()
+        assert L.ev2g_gen_default_config(0, C.byref(cfg)) == 0
+        cfg.number_of_charging_stations = 1000
+        cfg.number_of_transformers = 50
+        out = C.c_void_p()
+        rc = L.ev2g_generate(C.byref(cfg), 2**31 - 1, 1, 8, C.byref(out))   # the first array alone (prices, [M, T] float64) would be 1.9 TB
+        assert rc != 0 and not out.value, rc
+        assert L.ev2g_generate(C.byref(cfg), 2, 1, 2, C.byref(out)) == 0 and out.value
+        L.ev2g_gen_free(out)
+        print("ok")
+    """
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-1000:], r.stderr[-2000:])
 
 
 def _write_data_dir(d, scenario_cols=("private", "public", "workplace")):

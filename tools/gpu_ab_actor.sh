@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/ab_actor; mkdir -p $O
 for rep in 1 2; do for lib in "$@"; do
   n=$(basename $lib .so)
-  EV2G_LIB=$PWD/$lib python bench.py --actor mlp --no-cpu-baseline > $O/actor_$n.json 2> $O/actor_$n.err
+  EV2G_LIB=$PWD/$lib python bench.py --full --actor mlp --no-cpu-baseline > $O/actor_$n.json 2> $O/actor_$n.err
   python - $O/actor_$n.json $n <<'P'
 import json,sys
 try:

@@ -10,7 +10,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 TAG=$1; shift
 OUT=gpurun_out/prof_$TAG; rm -rf $OUT; mkdir -p $OUT
-B="python bench.py --no-cpu-baseline --only-timed --min-time ${MIN_TIME:-0.1} --pool ${POOL:-2} $*"
+B="python bench.py --full --no-cpu-baseline --only-timed --min-time ${MIN_TIME:-0.1} --pool ${POOL:-2} $*"
 echo "## command: rocprofv3 <mode> -- $B"
 $B 2>$OUT/bench.err | tail -1 > $OUT/bench_line.json
 timeout ${PASS_TIMEOUT:-300} rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $B > $OUT/kt.log 2>&1

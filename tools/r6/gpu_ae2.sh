@@ -8,5 +8,5 @@ for v in "EV2G_FUSED_ONE_ENV=1" "EV2G_X=0" "EV2G_FUSED_ONE_ENV=1" "EV2G_X=0"; do
 done
 for v in "EV2G_FUSED_ONE_ENV=1" "EV2G_X=0"; do
   echo "## $v" | tee -a $O/rollout_cfg3.txt
-  env $v timeout 300 python bench.py --workload cfg3 --actor mlp --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], json.dumps(d.get('rollout'))[:300])" | tee -a $O/rollout_cfg3.txt
+  env $v timeout 300 python bench.py --full --workload cfg3 --actor mlp --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], json.dumps(d.get('rollout'))[:300])" | tee -a $O/rollout_cfg3.txt
 done

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r6_f32b; mkdir -p $O
 for L in build_variants/libev2g_w3off0.so build_variants/libev2g_w3off4.so build_variants/libev2g_w3off12.so build_variants/libev2g_w3off0.so build_variants/libev2g_w3off4.so build_variants/libev2g_w3off12.so; do
   echo "## $L" | tee -a $O/rollout_fp32.txt
-  EV2G_LIB=$L timeout 300 python bench.py --actor mlp_fp32 --steps 20 --warmup 5 --no-other-workloads 2>$O/err.txt | python -c "
+  EV2G_LIB=$L timeout 300 python bench.py --full --actor mlp_fp32 --steps 20 --warmup 5 --no-other-workloads 2>$O/err.txt | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['ms_per_step'])" | tee -a $O/rollout_fp32.txt
 done

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r6_f32d; mkdir -p $O
 timeout 900 python -m pytest tests/test_round6_gpu.py -x -q -m gpu -k "float32" 2>&1 | tail -5 | tee $O/pytest_new.txt
 timeout 900 python -m pytest tests/test_round5_gpu.py tests/test_actor_gpu.py -x -q -m gpu 2>&1 | tail -3 | tee $O/pytest_regress.txt
-timeout 600 python bench.py 2>$O/err.txt | tail -1 > $O/bench_default.json
+timeout 600 python bench.py --full 2>$O/err.txt | tail -1 > $O/bench_default.json
 python -c "
 import json
 d=json.loads(open('$O/bench_default.json').read())

@@ -6,7 +6,7 @@ EV2G_LIB=build_variants/libev2g_$L.so timeout 600 python -m pytest tests/test_ro
 done
 for L in xs0 xs1a1 xs1a0 xs1a0r6 xs0 xs1a1 xs1a0 xs1a0r6; do
   echo "## $L" | tee -a $O/rollout_fp32.txt
-  EV2G_LIB=build_variants/libev2g_$L.so timeout 300 python bench.py --actor mlp_fp32 --steps 20 --warmup 5 --no-other-workloads --no-cpu-baseline 2>$O/err.txt | python -c "
+  EV2G_LIB=build_variants/libev2g_$L.so timeout 300 python bench.py --full --actor mlp_fp32 --steps 20 --warmup 5 --no-other-workloads --no-cpu-baseline 2>$O/err.txt | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['ms_per_step'])" | tee -a $O/rollout_fp32.txt
 done

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r6_fork1; mkdir -p $O
 timeout 600 python -m pytest tests/test_round6_gpu.py -q -m gpu -k "stats_reset_refill" -p no:warnings 2>&1 | tail -15 | cut -c1-300 | tee $O/test.txt
 for v in "EV2G_X=0" "EV2G_NO_REFILL_OVERLAP=1" "EV2G_X=0" "EV2G_NO_REFILL_OVERLAP=1"; do
-  env $v timeout 600 python bench.py --no-cpu-baseline --no-other-workloads > $O/bench.json 2> $O/bench.err; echo "$v bench rc=$?"
+  env $v timeout 600 python bench.py --full --no-cpu-baseline --no-other-workloads > $O/bench.json 2> $O/bench.err; echo "$v bench rc=$?"
   python - "$v" <<'P' | tee -a $O/refill_overlap.txt
 import json, sys
 d = json.loads(open("gpurun_out/r6_fork1/bench.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # PMC passes over the fused actor + step launches (separate rocprofv3 runs, --pmc only): MFMA busy, instruction mix, waits, LDS conflicts, L2 hits -- bf16 and float32 policies
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=gpurun_out/r6_pmc_fused; mkdir -p $O; rm -rf $O/p*
 for A in mlp mlp_fp32; do
-CMD="python bench.py --no-cpu-baseline --only-timed --min-time 0.1 --pool 2 --workload cfg2 --actor $A"
+CMD="python bench.py --full --no-cpu-baseline --only-timed --min-time 0.1 --pool 2 --workload cfg2 --actor $A"
 i=0
 while read -r line; do
   [ -z "$line" ] && continue

@@ -5,7 +5,7 @@ for off in 0 31 32 33 34 35 36 37 38; do
   r=$(EV2G_FUZZ_OFFSET=$off timeout 600 python -m pytest tests/test_round6_gpu.py tests/test_round3_gpu.py -q -m gpu -k "refill or generated" -p no:warnings 2>&1 | grep -E "passed|failed" | tail -1)
   echo "EV2G_FUZZ_OFFSET=$off: $r" | tee -a $O/sweep.txt
 done
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 python - <<'P'
 import json
 d = json.loads(open("gpurun_out/r6_rf_sweep/bench_default.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ timeout 1200 python -m pytest tests/test_engine_gpu.py tests/test_round3_gpu.py 
 for L in build_variants/libev2g_soc0.so ev2gym_amd/libev2g_hip.so build_variants/libev2g_soc0.so ev2gym_amd/libev2g_hip.so; do
   echo "## $L" | tee -a $O/ab.txt
   EV2G_LIB=$L timeout 200 python tools/stats_time.py cfg2 2>&1 | grep -v amdgpu.ids | tail -1 | tee -a $O/ab.txt
-  EV2G_LIB=$L timeout 300 python bench.py --no-other-workloads --no-cpu-baseline --no-rollout-record 2>$O/err.txt | python -c "
+  EV2G_LIB=$L timeout 300 python bench.py --full --no-other-workloads --no-cpu-baseline --no-rollout-record 2>$O/err.txt | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print('value', d['value'], 'ms/step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'launch_us', d['roofline']['avg_launch_us'], 'episode', d['full_episode']['ms_per_episode'])" | tee -a $O/ab.txt
 done
