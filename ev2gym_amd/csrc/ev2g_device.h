@@ -1132,29 +1132,47 @@ template <int EPWS> __device__ __forceinline__ bool seg_all(bool p) {
     return (threadIdx.x < 32) ? ((unsigned)m == 0xffffffffu) : ((unsigned)(m >> 32) == 0xffffffffu);
 }
 
-// RESET: the episode-end sequence "statistics, then reset onto the next scenario window" (what an auto-resetting vectorised env does) in ONE
-// launch: the wavefront that computed an env's statistics re-arms that env's state right behind them (ev2g_reset_kernel's work for one env:
-// state lines from the new window's first-session tables, charger and env accumulators, history rows, reset observation) -- one kernel
-// launch and one cold start per episode less (ev2g_get_stats_reset, include/ev2g.h).
-template <int EPWS, bool RESET = false>
-__global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, int scn_off,
-                                                        const double *__restrict__ ss_afap, int cur_step,
-                                                        double *__restrict__ out, int reset_off = 0, double *__restrict__ r_obs = nullptr,
-                                                        float *__restrict__ r_obs32 = nullptr) {
-    // EPWS envs share a wavefront (W = 64 / EPWS lanes each): a wavefront's time is its chain of dependent memory round trips, not its lane
-    // count, so small envs (their sessions fit 32 lanes) are paired -- half the wavefronts for the same chain (ev2g_get_stats decides).
+// What get_statistics reads: the scenario's session tables and the state the finished (or running) episode left behind.  The stand-alone
+// statistics kernel fills it from its DevScn / DevState arguments, the step kernel's in-launch statistics phase (ev2g_step_wave.h) from its
+// parameter block -- both then run ev2g_env_stats below, the same operations in the same order, so their results are bit-identical.
+struct StatsView {
+    int T, C, R, P, dt;
+    const double *setpoint;
+    const int *scn_sess, *scn_sess_end, *ss_slot, *ss_tarr, *ss_tdep;
+    const double *ss_B, *ss_afap;
+    const int *cs_served;
+    const double *cs_sat_sum, *hist, *env_acc, *sess_final_cap, *sess_abs_e, *soc_log;
+    const PortLine *line;
+};
+__device__ __forceinline__ StatsView ev2g_stats_view(const DevScn &s, const DevState &st, const double *ss_afap) {
+    return StatsView{s.T, s.C, s.R, s.P, s.dt, s.setpoint, s.scn_sess, s.scn_sess_end, s.ss_slot, s.ss_tarr, s.ss_tdep, s.ss_B, ss_afap,
+                     st.cs_served, st.cs_sat_sum, st.hist, st.env_acc, st.sess_final_cap, st.sess_abs_e, st.soc_log, st.line};
+}
+
+#ifndef EV2G_STATS_NK
+#define EV2G_STATS_NK 40
+#endif
+#ifndef EV2G_STATS_TB
+#define EV2G_STATS_TB 8   // entries per batch of a session's tail (beyond the NK kept ones)
+#endif
+#ifndef EV2G_STATS_LK
+#define EV2G_STATS_LK 16  // entries behind the kept ones that the first pass parks in LDS for the second (8 KB per wavefront; 16 / 32 / 48: 37.2 / 37.3 / 41.8 us at cfg2 against 38.5 without)
+#endif
+
+// get_statistics (utils.py:12-123) of env e (scenario scn) at step cur_step into row e of `out` ([E, 17]; stored only when e_valid), by the
+// W = 64 / EPWS lanes of the env's segment (`lane` inside it).  NK entries of a session's SoC log are kept in registers for the second pass
+// and the LK entries behind them in LDS: l_keep[entry * 64 + lslot] (lslot: this lane's column, 0..63, of the wavefront's [LK][64] block).
+// The summation order does not depend on NK or LK.
+template <int EPWS, int NK, int LK>
+__device__ __forceinline__ void ev2g_env_stats(const StatsView &sv, int e, bool e_valid, int scn, int lane, int cur_step, double *__restrict__ out,
+                                               double *l_keep, int lslot) {
     constexpr int W = 64 / EPWS;
-    const int sub = threadIdx.x / W, lane = threadIdx.x - sub * W;   // `lane`: inside the env's segment
-    const int e_raw = blockIdx.x * EPWS + sub;
-    const bool e_valid = e_raw < s.E;
-    const int e = e_valid ? e_raw : s.E - 1;   // (an odd env count: the idle segment recomputes the last env and stores nothing)
-    const int scn = ev2g_scn(e, scn_off, s.M);
-    const int T = s.T, C = s.C, R = s.R, P = s.P;
+    const int T = sv.T, C = sv.C, R = sv.R, P = sv.P;
     double served = 0.0, sat = 0.0, nsat = 0.0;
     for (int c = lane; c < C; c += W) {
-        const int n = st.cs_served[(long long)e * C + c];
+        const int n = sv.cs_served[(long long)e * C + c];
         served += n;
-        if (n > 0) { sat += st.cs_sat_sum[(long long)e * C + c] / n; nsat += 1.0; }
+        if (n > 0) { sat += sv.cs_sat_sum[(long long)e * C + c] / n; nsat += 1.0; }
     }
     served = seg_sum<EPWS>(served); sat = seg_sum<EPWS>(sat); nsat = seg_sum<EPWS>(nsat);
     double over = 0.0, te = 0.0, ete = 0.0, ptv = 0.0;
@@ -1162,15 +1180,26 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
         // steps the running episode has not reached count as zeros (the reference's arrays are zero-initialised at reset); the
         // history slab may still hold the previous episode's values there after an in-kernel reset of a fused run
         const bool past = t < cur_step;
-        if (past) for (int r = 0; r < R; r++) over += st.hist[EV2G_HIST(e, t, T, R) + 2 + r];
-        const double sp = s.setpoint[(long long)scn * T + t], u = past ? st.hist[EV2G_HIST(e, t, T, R)] : 0.0;
+        if (past) for (int r = 0; r < R; r++) over += sv.hist[EV2G_HIST(e, t, T, R) + 2 + r];
+        const double sp = sv.setpoint[(long long)scn * T + t], u = past ? sv.hist[EV2G_HIST(e, t, T, R)] : 0.0;
         const double d = sp - u;
         te += d * d;
         ete += fabs(d);
         if (u > sp) ptv += u - sp;
     }
     over = seg_sum<EPWS>(over); te = seg_sum<EPWS>(te); ete = seg_sum<EPWS>(ete); ptv = seg_sum<EPWS>(ptv);
-    ete *= (double)s.dt / 60.0;
+    ete *= (double)sv.dt / 60.0;
+    // the columns that are final by now are stored now: kept until the end, these wave-uniform sums were 14 scalar registers held across the
+    // session pass (the in-launch phase has none to spare)
+    if (lane == 0 && e_valid) {
+        double *o = out + (long long)e * 17;
+        o[0] = served;
+        o[4] = (nsat > 0.0) ? sat / nsat : NAN;
+        o[5] = ptv;
+        o[6] = te;
+        o[7] = ete;
+        o[12] = over;
+    }
     // energy user satisfaction (utils.py:57-63) and battery degradation (ev.py:442-521) over every spawned session
     const double e0 = 7.543e6, e1 = 23.75e6, e2 = 6976, z0 = 7.348e-3, z1 = 3.667, z2 = 7.6e-4, z3 = 4.081e-3;
     const double b_cap_ah = 2.05, b_cap_kwh = 78, d_dist = 15000, b_age = 2 * 365, G_ = 0.186;
@@ -1178,7 +1207,7 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
     // per-session constants of get_battery_degradation, evaluated once (same operations, same values)
     const double k_arrh = exp(-e2 / theta), k_age = pow(b_age, 0.25);
     const double Q_acc = 2 * (b_age * (d_dist / 365) * G_ * b_cap_ah) / b_cap_kwh, k_qacc = pow(Q_acc, 0.5);
-    const bool log_soc = st.soc_log != nullptr;
+    const bool log_soc = sv.soc_log != nullptr;
     double sum = 0.0, mn = INFINITY, cnt = 0.0, deg_cal = 0.0, deg_cyc = 0.0;
     // One SESSION per lane (an env has ~0.7 sessions per port: 35 at cfg2): every lane's chain is the two or three memory round
     // trips of ONE session's SoC log.  With a lane per port the wavefront waited for its busiest port (up to six sessions in a row).
@@ -1190,17 +1219,17 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
     // sessions that would depart before they arrive): everything a lane needs of its session depends on the session index alone and is
     // requested in ONE round trip -- the port's state line (the attached EV's capacity) and the SoC log follow in a second one.  (Round 3
     // walked the port's chain first: first session, the line's current session, last session -- three dependent round trips more.)
-    const int d0 = s.scn_sess[scn], d1 = s.scn_sess_end[scn];
+    const int d0 = sv.scn_sess[scn], d1 = sv.scn_sess_end[scn];
     for (int k0 = d0; k0 < d1; k0 += W) {
         const int k = min(k0 + lane, d1 - 1);
         const bool has = k0 + lane < d1;
-        const int q = s.ss_slot[k], ta = s.ss_tarr[k], td = s.ss_tdep[k];
-        const double B = s.ss_B[k], afap = ss_afap[k], fin_cap = st.sess_final_cap[k];
-        const double fin_abs = log_soc ? st.sess_abs_e[k] : 0.0;
+        const int q = sv.ss_slot[k], ta = sv.ss_tarr[k], td = sv.ss_tdep[k];
+        const double B = sv.ss_B[k], afap = sv.ss_afap[k], fin_cap = sv.sess_final_cap[k];
+        const double fin_abs = log_soc ? sv.sess_abs_e[k] : 0.0;
         const long long g = (long long)e * P + q;
         const bool spawned = has && ta <= cur_step;   // spawned so far
         const bool live = td >= cur_step;             // still attached
-        const double l_cap = st.line[g].cap, l_abs = st.line[g].abse;
+        const double l_cap = sv.line[g].cap, l_abs = sv.line[g].abse;
         const double capk = live ? l_cap : fin_cap;
         if (spawned) {
             const double v = capk / afap * 100.0;
@@ -1212,7 +1241,7 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
         }
         if (spawned) {
             if (log_soc) {
-                const double *__restrict__ slog = st.soc_log + (long long)e * T * P + q;   // this port's column of the env's [T, P] block
+                const double *__restrict__ slog = sv.soc_log + (long long)e * T * P + q;   // this port's column of the env's [T, P] block
                 const int tend = min(td, cur_step - 1);
                 const double soc_f = capk / B;
                 // historic_soc entries are capacity / battery_capacity (ev.py:156): one reciprocal per session and a multiplication per
@@ -1226,18 +1255,6 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
                 // in batches of eight.  Accumulation order is the sequential one.  NK = 40 (80 registers, two wavefronts per SIMD) since the end of
                 // round 4: the kernel's time follows the number of dependent batches, not the occupancy -- NK 12 / 24 / 32 / 40 / 56: 43.5 / 41.6 /
                 // 39.9 / 38.6 / 55 us at cfg2, 52.0 -> 45.2 at cfg3, 482 -> 380 at cfg4 (profiles/r04_stats_log_pass_variants.txt).
-#ifndef EV2G_STATS_NK
-#define EV2G_STATS_NK 40
-#endif
-#ifndef EV2G_STATS_TB
-#define EV2G_STATS_TB 8   // entries per batch of a session's tail (beyond the NK kept ones)
-#endif
-#ifndef EV2G_STATS_LK
-#define EV2G_STATS_LK 16  // entries behind the kept ones that the first pass parks in LDS for the second (8 KB per wavefront; 16 / 32 / 48: 37.2 / 37.3 / 41.8 us at cfg2 against 38.5 without)
-#endif
-                constexpr int NK = EV2G_STATS_NK;
-                constexpr int LK = EV2G_STATS_LK;   // (a multiple of the tail batch)
-                extern __shared__ double l_keep[];  // [LK][64]
                 double xk[NK];
 #pragma unroll
                 for (int u = 0; u < NK; u++) xk[u] = slog[(long long)min(ta + u, tend) * P];
@@ -1255,7 +1272,7 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
                     for (int u = 0; u < EV2G_STATS_TB; u++) x[u] = slog[(long long)min(t + u, tend) * P];
                     if (LK > 0 && t - ta - NK < LK) {   // the next LK entries behind the kept ones are parked in LDS for the second pass ([entry][lane]: no bank conflicts)
 #pragma unroll
-                        for (int u = 0; u < EV2G_STATS_TB; u++) l_keep[(t - ta - NK + u) * 64 + (int)threadIdx.x] = x[u];
+                        for (int u = 0; u < EV2G_STATS_TB; u++) l_keep[(t - ta - NK + u) * 64 + lslot] = x[u];
                     }
 #pragma unroll
                     for (int u = 0; u < EV2G_STATS_TB; u++) {
@@ -1277,7 +1294,7 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
                     double x[EV2G_STATS_TB];
                     if (LK > 0 && t - ta - NK < LK) {
 #pragma unroll
-                        for (int u = 0; u < EV2G_STATS_TB; u++) x[u] = l_keep[(t - ta - NK + u) * 64 + (int)threadIdx.x];
+                        for (int u = 0; u < EV2G_STATS_TB; u++) x[u] = l_keep[(t - ta - NK + u) * 64 + lslot];
                     } else {
 #pragma unroll
                         for (int u = 0; u < EV2G_STATS_TB; u++) x[u] = slog[(long long)min(t + u, tend) * P];
@@ -1288,7 +1305,7 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
                 }
                 mad += fabs(avg_f - soc_f);
                 const double delta_DoD = 2 * (mad / nf);
-                const double T_sim = (td - ta + 1) * (double)s.dt / (60 * 24);
+                const double T_sim = (td - ta + 1) * (double)sv.dt / (60 * 24);
                 const double v_avg = v_min + kk * avg_soc;
                 const double alpha = (e0 * v_avg - e1) * k_arrh;
                 deg_cal += alpha * 0.75 * T_sim / k_age;
@@ -1302,6 +1319,18 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
     }
     sum = seg_sum<EPWS>(sum); cnt = seg_sum<EPWS>(cnt); mn = seg_min<EPWS>(mn);
     deg_cal = seg_sum<EPWS>(deg_cal); deg_cyc = seg_sum<EPWS>(deg_cyc);
+    if (lane == 0 && e_valid) {   // (likewise: only the satisfaction moments are left)
+        const double *acc = sv.env_acc + (long long)e * 8;
+        double *o = out + (long long)e * 17;
+        o[1] = acc[1];
+        o[2] = acc[2];
+        o[3] = acc[3];
+        o[11] = acc[4];
+        o[13] = log_soc ? deg_cal + deg_cyc : NAN;
+        o[14] = log_soc ? deg_cal : NAN;
+        o[15] = log_soc ? deg_cyc : NAN;
+        o[16] = acc[0];
+    }
     double mean = NAN, sd = NAN, mnv = NAN;
     if (cnt > 0.0) {
         mean = sum / cnt;
@@ -1311,10 +1340,10 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
             if (nkeep > 1) { const double v = vkeep[1] - mean; var += v * v; }
         } else {
             for (int k = d0 + lane; k < d1; k += W) {
-                const int ta = s.ss_tarr[k];
+                const int ta = sv.ss_tarr[k];
                 if (ta <= cur_step) {
-                    const double capk = (s.ss_tdep[k] >= cur_step) ? st.line[(long long)e * P + s.ss_slot[k]].cap : st.sess_final_cap[k];
-                    const double v = capk / ss_afap[k] * 100.0 - mean;
+                    const double capk = (sv.ss_tdep[k] >= cur_step) ? sv.line[(long long)e * P + sv.ss_slot[k]].cap : sv.sess_final_cap[k];
+                    const double v = capk / sv.ss_afap[k] * 100.0 - mean;
                     var += v * v;
                 }
             }
@@ -1324,65 +1353,91 @@ __global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, i
         mnv = mn;
     }
     if (lane == 0 && e_valid) {
-        const double *acc = st.env_acc + (long long)e * 8;
         double *o = out + (long long)e * 17;
-        o[0] = served;
-        o[1] = acc[1];
-        o[2] = acc[2];
-        o[3] = acc[3];
-        o[4] = (nsat > 0.0) ? sat / nsat : NAN;
-        o[5] = ptv;
-        o[6] = te;
-        o[7] = ete;
         o[8] = mean;
         o[9] = sd;
         o[10] = mnv;
-        o[11] = acc[4];
-        o[12] = over;
-        o[13] = log_soc ? deg_cal + deg_cyc : NAN;
-        o[14] = log_soc ? deg_cal : NAN;
-        o[15] = log_soc ? deg_cyc : NAN;
-        o[16] = acc[0];
     }
-    if (RESET && e_valid) {   // EV2Gym.reset()'s state-init part for this env, on scenario (e + reset_off) mod M (ev2g_reset_kernel, one env per segment)
-        const int scn_n = ev2g_scn(e, reset_off, s.M);
-        // the reset observation's head row (fast path: a copy of row 0 of the new scenario's head table) is requested before the state is
-        // re-armed, together with the ports' first-session tables: one round trip for the block's loads, then only stores
-        const bool hfast = s.head_tab != nullptr && s.state_kind != 1 && 2 + s.head_nh <= 2 * W && (r_obs || r_obs32);
-        double hrow0 = 0.0, hrow1 = 0.0;
-        if (hfast) {
-            const double *row = s.head_tab + (long long)scn_n * (T + 1) * s.head_nh;
-            hrow0 = row[min(max(lane - 2, 0), s.head_nh - 1)];
-            hrow1 = row[min(lane + W - 2, s.head_nh - 1)];
-        }
-        for (int q = lane; q < P; q += W) {
-            const long long g = (long long)e * P + q, gs = (long long)scn_n * P + q;
-            const int2 w = s.port_first_win[gs];
-            st.line[g].ta = w.x; st.line[g].td = w.y; st.line[g].ss = s.port_first[gs]; st.line[g].cyc_lut = 0;
-            st.line[g].cap = 0.0; st.line[g].tot = 0.0; st.line[g].prev = 0.0;
-            st.port_energy[g] = 0.0; st.port_current[g] = 0.0;
-            if (r_obs) { double *o = r_obs + (long long)e * s.D + s.slot_obs[q]; o[0] = 0.0; o[1] = 0.0; if (s.state_kind == 1) o[2] = 0.0; }
-            if (r_obs32) { float *o = r_obs32 + (long long)e * s.D + s.slot_obs[q]; o[0] = 0.f; o[1] = 0.f; if (s.state_kind == 1) o[2] = 0.f; }
-        }
-        for (int c = lane; c < C; c += W) {
-            const long long gc = (long long)e * C + c;
-            st.cs_sat_sum[gc] = 0.0; st.cs_served[gc] = 0;
-            if (st.cs_profits) { st.cs_profits[gc] = 0.0; st.cs_e_ch[gc] = 0.0; st.cs_e_dis[gc] = 0.0; st.cs_power_now[gc] = 0.0; st.cs_cur_now[gc] = 0.0; }
-        }
-        for (int i = lane; i < 8; i += W) st.env_acc[(long long)e * 8 + i] = 0.0;
-        // (history rows: only charge_power_potential[0], which the first step reads, is cleared -- rows the new episode has not reached are ignored by
-        // the statistics kernel and by ev2g_peek; clearing all T x (2 + R) values of every env was a quarter of this block's bytes)
-        if (lane == 0) st.hist[EV2G_HIST(e, 0, T, R) + 1] = 0.0;
-        for (int r = lane; r < R; r += W) st.tr_power_now[(long long)e * R + r] = 0.0;
-        if (lane == 0) st.env_fault[e] = 0;
-        if (hfast) {   // columns 0, 1: step counter 0 and no usage yet; 2 ..: the head row
-            const int c0 = lane, c1 = lane + W, nc = 2 + s.head_nh;
-            const double v0 = (c0 < 2) ? 0.0 : hrow0;
-            if (r_obs) { double *o = r_obs + (long long)e * s.D; if (c0 < nc) o[c0] = v0; if (c1 < nc) o[c1] = hrow1; }
-            if (r_obs32) { float *o = r_obs32 + (long long)e * s.D; if (c0 < nc) o[c0] = (float)v0; if (c1 < nc) o[c1] = (float)hrow1; }
-        } else {
-            if (r_obs) write_obs_env(s, r_obs + (long long)e * s.D, scn_n, 0, 0.0, lane, W);
-            if (r_obs32) write_obs_env(s, r_obs32 + (long long)e * s.D, scn_n, 0, 0.0, lane, W);
-        }
+}
+
+// EV2Gym.reset()'s state-init part for env e, on scenario (e + reset_off) mod M (ev2g_reset_kernel's work for one env), by the W lanes of the
+// env's segment: state lines from the new window's first-session tables, charger and env accumulators, history rows, reset observation
+template <int W>
+__device__ __forceinline__ void ev2g_env_reset(const DevScn &s, const DevState &st, int e, int lane, int reset_off, double *__restrict__ r_obs,
+                                               float *__restrict__ r_obs32) {
+    const int T = s.T, C = s.C, R = s.R, P = s.P;   // EV2Gym.reset()'s state-init part for this env, on scenario (e + reset_off) mod M (ev2g_reset_kernel, one env per segment)
+    const int scn_n = ev2g_scn(e, reset_off, s.M);
+    // the reset observation's head row (fast path: a copy of row 0 of the new scenario's head table) is requested before the state is
+    // re-armed, together with the ports' first-session tables: one round trip for the block's loads, then only stores
+    const bool hfast = s.head_tab != nullptr && s.state_kind != 1 && 2 + s.head_nh <= 2 * W && (r_obs || r_obs32);
+    double hrow0 = 0.0, hrow1 = 0.0;
+    if (hfast) {
+        const double *row = s.head_tab + (long long)scn_n * (T + 1) * s.head_nh;
+        hrow0 = row[min(max(lane - 2, 0), s.head_nh - 1)];
+        hrow1 = row[min(lane + W - 2, s.head_nh - 1)];
     }
+    for (int q = lane; q < P; q += W) {
+        const long long g = (long long)e * P + q, gs = (long long)scn_n * P + q;
+        const int2 w = s.port_first_win[gs];
+        st.line[g].ta = w.x; st.line[g].td = w.y; st.line[g].ss = s.port_first[gs]; st.line[g].cyc_lut = 0;
+        st.line[g].cap = 0.0; st.line[g].tot = 0.0; st.line[g].prev = 0.0;
+        st.port_energy[g] = 0.0; st.port_current[g] = 0.0;
+        if (r_obs) { double *o = r_obs + (long long)e * s.D + s.slot_obs[q]; o[0] = 0.0; o[1] = 0.0; if (s.state_kind == 1) o[2] = 0.0; }
+        if (r_obs32) { float *o = r_obs32 + (long long)e * s.D + s.slot_obs[q]; o[0] = 0.f; o[1] = 0.f; if (s.state_kind == 1) o[2] = 0.f; }
+    }
+    for (int c = lane; c < C; c += W) {
+        const long long gc = (long long)e * C + c;
+        st.cs_sat_sum[gc] = 0.0; st.cs_served[gc] = 0;
+        if (st.cs_profits) { st.cs_profits[gc] = 0.0; st.cs_e_ch[gc] = 0.0; st.cs_e_dis[gc] = 0.0; st.cs_power_now[gc] = 0.0; st.cs_cur_now[gc] = 0.0; }
+    }
+    for (int i = lane; i < 8; i += W) st.env_acc[(long long)e * 8 + i] = 0.0;
+    // (history rows: only charge_power_potential[0], which the first step reads, is cleared -- rows the new episode has not reached are ignored by
+    // the statistics kernel and by ev2g_peek; clearing all T x (2 + R) values of every env was a quarter of this block's bytes)
+    if (lane == 0) st.hist[EV2G_HIST(e, 0, T, R) + 1] = 0.0;
+    for (int r = lane; r < R; r += W) st.tr_power_now[(long long)e * R + r] = 0.0;
+    if (lane == 0) st.env_fault[e] = 0;
+    if (hfast) {   // columns 0, 1: step counter 0 and no usage yet; 2 ..: the head row
+        const int c0 = lane, c1 = lane + W, nc = 2 + s.head_nh;
+        const double v0 = (c0 < 2) ? 0.0 : hrow0;
+        if (r_obs) { double *o = r_obs + (long long)e * s.D; if (c0 < nc) o[c0] = v0; if (c1 < nc) o[c1] = hrow1; }
+        if (r_obs32) { float *o = r_obs32 + (long long)e * s.D; if (c0 < nc) o[c0] = (float)v0; if (c1 < nc) o[c1] = (float)hrow1; }
+    } else {
+        if (r_obs) write_obs_env(s, r_obs + (long long)e * s.D, scn_n, 0, 0.0, lane, W);
+        if (r_obs32) write_obs_env(s, r_obs32 + (long long)e * s.D, scn_n, 0, 0.0, lane, W);
+    }
+}
+
+// RESET: the episode-end sequence "statistics, then reset onto the next scenario window" (what an auto-resetting vectorised env does) in ONE
+// launch: the wavefront that computed an env's statistics re-arms that env's state right behind them (ev2g_reset_kernel's work for one env:
+// state lines from the new window's first-session tables, charger and env accumulators, history rows, reset observation) -- one kernel
+// launch and one cold start per episode less (ev2g_get_stats_reset, include/ev2g.h).
+template <int EPWS, bool RESET = false>
+__global__ void __launch_bounds__(64) ev2g_stats_kernel(DevScn s, DevState st, int scn_off,
+                                                        const double *__restrict__ ss_afap, int cur_step,
+                                                        double *__restrict__ out, int reset_off = 0, double *__restrict__ r_obs = nullptr,
+                                                        float *__restrict__ r_obs32 = nullptr) {
+    // EPWS envs share a wavefront (W = 64 / EPWS lanes each): a wavefront's time is its chain of dependent memory round trips, not its lane
+    // count, so small envs (their sessions fit 32 lanes) are paired -- half the wavefronts for the same chain (ev2g_get_stats decides).
+    constexpr int W = 64 / EPWS;
+    const int sub = threadIdx.x / W, lane = threadIdx.x - sub * W;   // `lane`: inside the env's segment
+    const int e_raw = blockIdx.x * EPWS + sub;
+    const bool e_valid = e_raw < s.E;
+    const int e = e_valid ? e_raw : s.E - 1;   // (an odd env count: the idle segment recomputes the last env and stores nothing)
+    const int scn = ev2g_scn(e, scn_off, s.M);
+    extern __shared__ double l_keep[];  // [EV2G_STATS_LK][64]
+    ev2g_env_stats<EPWS, EV2G_STATS_NK, EV2G_STATS_LK>(ev2g_stats_view(s, st, ss_afap), e, e_valid, scn, lane, cur_step, out, l_keep, (int)threadIdx.x);
+    if (RESET && e_valid) ev2g_env_reset<W>(s, st, e, lane, reset_off, r_obs, r_obs32);
+}
+
+// The reset-only episode end: the statistics were computed by the step launch that closed the episode (ev2g_step_wave's in-launch phase) into
+// `done_stats` ([E, 17]); this launch copies their rows into `out` and re-arms every env like ev2g_stats_kernel<EPWS, true> (same lanes per env).
+template <int EPWS>
+__global__ void __launch_bounds__(64) ev2g_copy_stats_reset_kernel(DevScn s, DevState st, const double *__restrict__ done_stats, double *__restrict__ out,
+                                                                   int reset_off, double *__restrict__ r_obs, float *__restrict__ r_obs32) {
+    constexpr int W = 64 / EPWS;
+    const int sub = threadIdx.x / W, lane = threadIdx.x - sub * W;
+    const int e = blockIdx.x * EPWS + sub;
+    if (e >= s.E) return;   // (no barrier in this kernel)
+    for (int j = lane; j < 17; j += W) out[(long long)e * 17 + j] = done_stats[(long long)e * 17 + j];
+    ev2g_env_reset<W>(s, st, e, lane, reset_off, r_obs, r_obs32);
 }

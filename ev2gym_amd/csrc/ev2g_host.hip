@@ -82,6 +82,15 @@ struct ev2g_handle {
     std::vector<int> cs_ph_host;
     int load_gen = 0;                           // counts ev2g_load_scenarios calls (part of the refill cache's key)
     int last_spec = -1;                         // ev2g_last_launch_specialisation
+    // in-launch episode statistics (ev2g_step_wave's INL phase): the last step launch closed the episode and wrote get_statistics of every env
+    // into d_stats_inl; ev2g_get_stats / ev2g_get_stats_reset copy those rows while nothing has changed the state since (every state-changing
+    // call clears the flag).  EV2G_NO_INLAUNCH_STATS=1 at load time: every episode end runs ev2g_stats_kernel (A/B, parity tests)
+    double *d_stats_inl = nullptr;              // [E, EV2G_N_STATS]: the loaded shape has the in-launch phase (V2P::stats_inl points here), else nullptr
+    const char *inl_shape_reason = "";          // ... why not
+    bool inl_stats = false, no_inl_stats = false;
+    int last_stats_route = -1;                  // ev2g_last_stats_route
+    const char *inl_reason = "";                // why the in-launch results are not available (the last step launch did not compute them, or they were discarded)
+    const char *stats_reason = "";              // ev2g_last_stats_reason: inl_reason at the last ev2g_get_stats / ev2g_get_stats_reset
     const char *general_reason = "";            // ev2g_last_launch_general_reason
     bool pow2_dt = false;                       // 60 / timescale is a power of two (15, 30, 60 minutes): compiled into ev2g_step_v2<.., 1>
     std::string kernel_name;                    // the step kernel ev2g_load_scenarios selected (ev2g_kernel_name)
@@ -241,6 +250,8 @@ const char *ev2g_kernel_name(const ev2g_handle *h) { return (h && h->loaded) ? h
 const char *ev2g_fallback_reason(const ev2g_handle *h) { return (h && h->loaded) ? h->fallback_reason.c_str() : ""; }
 const char *ev2g_big_kernel_reason(const ev2g_handle *h) { return (h && h->loaded) ? h->big_reason.c_str() : ""; }
 int ev2g_last_launch_specialisation(const ev2g_handle *h) { return (h && h->loaded) ? h->last_spec : -1; }
+int ev2g_last_stats_route(const ev2g_handle *h) { return (h && h->loaded) ? h->last_stats_route : -1; }
+const char *ev2g_last_stats_reason(const ev2g_handle *h) { return (h && h->loaded && h->last_stats_route == 0) ? h->stats_reason : ""; }
 const char *ev2g_last_launch_general_reason(const ev2g_handle *h) { return (h && h->loaded && h->last_spec == 0) ? h->general_reason : ""; }
 
 static const char *kStatNames[EV2G_N_STATS] = {
@@ -275,6 +286,15 @@ static double afap_energy(const ev2g_scenario_batch *b, long long s, double max_
 }
 
 int ev2g_reset_ex(ev2g_handle *h, double *obs, int64_t scenario_offset);
+
+// Envs per wavefront of ev2g_stats_kernel (the summation order of its reductions follows from it): two where an env's sessions fit 32 lanes with
+// room to spare (PublicPST: ~14 per env -- 74.6 -> 58.0 us at cfg3; at cfg2's ~35 per env half of the lanes would need a second pass: 47 -> 52 us,
+// so it keeps a wavefront per env).  Refillable pools: by the session slots per scenario, not by what the loaded batch happened to hold -- the
+// choice (and the summation order) stays put across refills.
+static bool stats_pair(const ev2g_handle *h) {
+    const long long per_scn = h->sess_cap > 0 ? (long long)h->sess_cap : (h->S + h->M - 1) / std::max(h->M, 1);
+    return (h->sess_cap > 0 ? per_scn <= 48 : h->S <= (long long)h->M * 24) && h->C <= 32 && !std::getenv("EV2G_STATS_ONE_ENV");
+}
 
 int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     if (!h || !b) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: null argument");
@@ -527,6 +547,7 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     h->wave_path = h->fallback_reason.empty();
     h->no_full = std::getenv("EV2G_NO_FULL") != nullptr; h->no_wide = std::getenv("EV2G_NO_WIDE") != nullptr; h->last_spec = -1;
     h->no_strided = std::getenv("EV2G_NO_STRIDED") != nullptr;
+    h->no_inl_stats = std::getenv("EV2G_NO_INLAUNCH_STATS") != nullptr; h->inl_stats = false; h->last_stats_route = -1; h->inl_reason = "no step launch since the scenarios were loaded";
     if (h->wave_path) {   // ev2g_step_wave addresses every array as base + 32-bit byte offset: all of them must stay below 4 GiB
         const unsigned long long lim = 1ull << 32;
         const unsigned long long biggest = std::max({(unsigned long long)E * P * 8, (unsigned long long)E * D * 8,
@@ -866,6 +887,7 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
         EV2G_SETP(v2p.lut, d_lut_eta);
         EV2G_SETP(v2p.head_tab, d_head_tab);
         EV2G_SETP(v2p.step_tab, d_step_tab);
+        EV2G_SETP(v2p.ss_afap, h->d_ss_afap);
         int ex = 0;   // 60/dt a power of two and dt/60 its exact reciprocal -> divisions by them are multiplications
         v2p.pow2_dt = (std::frexp(h->scn.sixty_over_dt, &ex) == 0.5 && h->scn.sixty_over_dt * h->scn.dt_over_60 == 1.0) ? 1 : 0;
         h->pow2_dt = v2p.pow2_dt != 0;
@@ -874,6 +896,20 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     HIPCHK(h, hipStreamSynchronize(h->stream));  // host staging vectors die here
 
     h->E = E; h->M = M; h->scn_off = 0; h->T = T; h->C = C; h->npc = npc; h->P = P; h->R = R; h->D = D; h->S = S;
+    {   // the in-launch statistics phase: a shape the statistics kernel runs with one env per wavefront (its summation order), like the phase
+        h->d_stats_inl = nullptr;
+        const char *why = "";
+        if (h->no_inl_stats) why = "EV2G_NO_INLAUNCH_STATS is set";
+        else if (!h->wave_path || !(h->cfg.flags & EV2G_FLAG_LOG_SOC)) why = "the step kernel is not ev2g_step_wave with the SoC log";
+        else if (h->wave_epw != 1 || stats_pair(h)) why = "several envs per wavefront (the in-launch phase computes one env per wavefront, like the statistics kernel at this shape)";
+        else if (h->lds_bytes < ev2g_inl_stats_lds_bytes()) why = "the step kernel's LDS is smaller than the phase's blocks";
+        h->inl_shape_reason = why;
+        if (!why[0]) {
+            if ((rc = dalloc(h, sp, (size_t)E * EV2G_N_STATS, &h->d_stats_inl))) return rc;
+            double *p = h->d_stats_inl;
+            HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, stats_inl), &p, sizeof p, hipMemcpyHostToDevice));
+        }
+    }
     h->slot_port = slot_port;
     h->port_slot = port_slot;
     h->env_sess_start.assign(b->env_session_start, b->env_session_start + M + 1);
@@ -904,6 +940,7 @@ int ev2g_reset_ex(ev2g_handle *h, double *obs, int64_t scenario_offset) {
     hipLaunchKernelGGL(ev2g_reset_kernel, dim3(s.n_groups), dim3(EV2G_BLOCK), 0, h->stream, s, h->st, obs, h->extras.obs_f32, (int)off);
     HIPCHK(h, hipGetLastError());
     h->current_step = 0;
+    h->inl_stats = false; h->inl_reason = "the episode was reset";
     return EV2G_OK;
 }
 
@@ -956,6 +993,7 @@ static StepIO make_io(const ev2g_handle *h, const double *actions, long long a_s
 
 static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int auto_reset) {
     const DevScn &s = h->scn;
+    h->inl_stats = false; h->inl_reason = "the step kernel is not ev2g_step_wave";
     if (h->wave_path) {
         // the fast path advances its output pointers by 32-bit byte strides
         const long long lim = 1ll << 32;
@@ -968,7 +1006,7 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
         const DevState &st = h->st;
         const FusedArgs fa0{};
         const WaveArgs wa{s.P, s.T, s.E, s.D, s.M, st.slab_port, st.slab_port_slice, st.hist,
-                          st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->wave_epw, h->wave_es};
+                    st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->wave_epw, h->wave_es};
         // every float64 output present, no extras, no charger histories: the specialisation without their checks (not for the run-time rewards)
         // ... in two flavours: float64 actions in / float64 observations out (a loop that consumes them, the benchmark), or the policy
         // network's hand-over, float32 actions in / float32 observations out and no float64 observation (ev2g_rollout)
@@ -997,6 +1035,16 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
                 else why = "the launch would run past the episode end";
             }
             h->general_reason = why;
+        }
+        {   // a launch of the float64 wide instantiation (2) that ends the episode computes its statistics in its tail (INL, ev2g_step_wave.h)
+            const char *why = "";
+            if (h->no_inl_stats) why = "EV2G_NO_INLAUNCH_STATS is set";
+            else if (t0 + k != s.T) why = "the last step launch did not end the episode";
+            else if (k < 2) why = "the episode ended in a single-step launch (per-step launches keep the statistics kernel)";
+            else if (!(wide && !str3 && f64io)) why = "the last step launch was not the float64 wide instantiation with step stride 0 (ev2g_last_launch_specialisation 2)";
+            else if (!h->d_stats_inl) why = h->inl_shape_reason;
+            h->inl_reason = why;
+            h->inl_stats = why[0] == 0;   // (the kernel applies the same rule: V2P::stats_inl set, k > 1, the launch ends at T -- ev2g_step_wave.h)
         }
 #define EV2G_WAVE_CASE(SK, RK)                                                                                              \
     case SK * 4 + RK:                                                                                                       \
@@ -1416,6 +1464,7 @@ static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, int k, const float *o
     const DevScn &s = h->scn;
     const DevState &st = h->st;
     const long long lim = 1ll << 32;
+    h->inl_stats = false; h->inl_reason = "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)";
     if (o_stride * 4 >= lim || a_stride * 4 >= lim || r_stride * 8 >= lim || d_stride >= lim || m_stride >= lim || o_stride < 0 || a_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0)
         return fail(h, EV2G_ERR_ARG, "ev2g_collect / ev2g_rollout: a step stride is negative or reaches 4 GiB");
     StepIO io = make_io(h, nullptr, a_stride, nullptr, o_stride, reward, r_stride, done, d_stride, mask, m_stride, 0, 0);
@@ -1634,12 +1683,23 @@ int ev2g_check_faults(ev2g_handle *h, int32_t *first_bad_env) {
 
 static int launch_stats(ev2g_handle *h, double *stats, bool reset, double *obs, long long off, float *obs32 = nullptr) {
     (void)hipSetDevice(h->device);
-    // two envs per wavefront where an env's sessions fit 32 lanes with room to spare (PublicPST: ~14 per env -- 74.6 -> 58.0 us at cfg3; at
-    // cfg2's ~35 per env half of the lanes would need a second pass: 47 -> 52 us, so it keeps a wavefront per env).  Refillable pools: by the
-    // session slots per scenario, not by what the loaded batch happened to hold -- the choice (and the summation order) stays put across refills.
-    const long long per_scn = h->sess_cap > 0 ? (long long)h->sess_cap : (h->S + h->M - 1) / std::max(h->M, 1);
-    const bool pair = (h->sess_cap > 0 ? per_scn <= 48 : h->S <= (long long)h->M * 24) && h->C <= 32 && !std::getenv("EV2G_STATS_ONE_ENV");
+    // the step launch that closed the episode computed the statistics (and nothing has changed the state since): copy them
+    const bool copy = h->inl_stats && h->current_step == h->T;
+    h->last_stats_route = copy ? 1 : 0;
+    h->stats_reason = copy ? "" : h->inl_reason;
+    if (copy && !reset) {
+        HIPCHK(h, hipMemcpyAsync(stats, h->d_stats_inl, sizeof(double) * (size_t)h->E * EV2G_N_STATS, hipMemcpyDeviceToDevice, h->stream));
+        return EV2G_OK;
+    }
+
+    const bool pair = stats_pair(h);
     const dim3 grid(pair ? (h->E + 1) / 2 : h->E);
+    if (copy) {   // reset-only: the rows are copied (the in-launch shapes are those with one env per wavefront)
+        hipLaunchKernelGGL((ev2g_copy_stats_reset_kernel<1>), dim3(h->E), dim3(64), 0, h->stream, h->scn, h->st, (const double *)h->d_stats_inl, stats, (int)off, obs,
+                           obs32 ? obs32 : (float *)h->extras.obs_f32);
+        HIPCHK(h, hipGetLastError());
+        return EV2G_OK;
+    }
 #define EV2G_STATS_LAUNCH(EPWS, RESET)                                                                                                    \
     hipLaunchKernelGGL((ev2g_stats_kernel<EPWS, RESET>), grid, dim3(64), (size_t)EV2G_STATS_LK * 64 * sizeof(double), h->stream, h->scn, h->st, (int)h->scn_off, (const double *)h->d_ss_afap, \
                        h->current_step, stats, (int)off, obs, RESET ? (obs32 ? obs32 : (float *)h->extras.obs_f32) : (float *)nullptr)
@@ -1669,6 +1729,7 @@ static int stats_reset_impl(ev2g_handle *h, double *stats, double *obs, float *o
     }
     h->scn_off = off;
     h->current_step = 0;
+    h->inl_stats = false; h->inl_reason = "the episode was reset";
     return EV2G_OK;
 }
 int ev2g_get_stats_reset(ev2g_handle *h, double *stats, double *obs, int64_t scenario_offset) { return stats_reset_impl(h, stats, obs, nullptr, scenario_offset); }
@@ -1949,6 +2010,7 @@ void ev2g_host_uniform(double *dst, int64_t n, uint64_t seed, double lo, double 
 // ---- scenario generator (host only) ----
 int ev2g_gen_default_config(int kind, ev2g_gen_config *cfg) { return ev2g_gen_default_config_impl(kind, cfg); }
 int ev2g_pool_refill(ev2g_handle *h, const ev2g_gen_config *cfg, uint64_t seed, int64_t first_index, int32_t first_slot, int32_t n) {
+    if (h) { h->inl_stats = false; h->inl_reason = "scenarios were refilled since the last step launch"; }
     try { return ev2g_pool_refill_impl(h, cfg, seed, first_index, first_slot, n); }
     catch (const std::exception &e) { return fail(h, EV2G_ERR_ARG, std::string("ev2g_pool_refill: ") + e.what()); }
 }

@@ -24,6 +24,15 @@ __host__ __device__ inline size_t ev2g_wave_lds_bytes(int envs_per_group, int bl
     const size_t NS = (size_t)block;
     return sizeof(double) * (EV2G_NQ * (NS + 8) + 7 * NS + 7 * (size_t)envs_per_group + 4 * 64) + sizeof(int) * (6 * NS + 8);
 }
+// the in-launch statistics phase (end of ev2g_step_wave): SoC-log entries per session kept in registers / parked in LDS (a multiple of
+// EV2G_STATS_TB; the whole workgroup's blocks, BLOCK / 64 x LK x 64 doubles, must fit the step's LDS -- checked by the host)
+#ifndef EV2G_INL_STATS_NK
+#define EV2G_INL_STATS_NK 12
+#endif
+#ifndef EV2G_INL_STATS_LK
+#define EV2G_INL_STATS_LK 16
+#endif
+__host__ __device__ inline size_t ev2g_inl_stats_lds_bytes(int block = EV2G_WAVE_BLOCK) { return (size_t)block * EV2G_INL_STATS_LK * sizeof(double); }
 // the fused actor + step instantiation (ACT, below): 16 envs and 16 wavefronts per workgroup, plus the policy's input rows (bf16) and its actions (float) in LDS
 #define EV2G_FUSED_BLOCK 1024
 #define EV2G_FUSED_SX 200     // MlpS16<6, ..>::SX: bf16 elements per observation row in LDS
@@ -176,6 +185,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
     constexpr bool STR_NT = FULLK >= 3;
 #endif   // the kept observation rows (0.6 GB per cfg2 launch) as streaming stores: they should not displace the state lines in L2 (-2 %, profiles/r05_ab_strided_nt.txt)
     constexpr bool F64 = FULL && !IO32, F32 = FULL && IO32;   // full with float64 actions in / observations out, or with the float32 hand-over
+    constexpr bool INL = FULLK == 2 && !IO32 && !ACT && BLOCK == EV2G_WAVE_BLOCK;   // the in-launch statistics phase is compiled in (end of the kernel)
 #if defined(EV2G_PHASE_TIMING) && defined(EV2G_PT_OUTER)
     const unsigned long long pt_k0 = __builtin_readcyclecounter();   // slot 7 := prologue, slot 6 := epilogue (tools/phase_timing.py --outer)
 #endif
@@ -1033,4 +1043,28 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
     PT_MARK(6)
 #endif
     PT_FLUSH
+    // ---- in-launch episode statistics (INL: the float64 wide instantiation) ----
+    // A launch of more than one step that ends the episode (t == T) computes get_statistics into V2P::stats_inl -- set by the loader only for a shape
+    // the statistics kernel runs one env per wavefront, like this phase (launch_steps in ev2g_host.hip applies the same rule) -- for
+    // for its own envs right here, while other workgroups are still stepping: everything the statistics read of env e -- its SoC log, history
+    // rows, charger counters, state lines, per-session results and episode accumulators -- was written by this workgroup, and the barrier
+    // below orders those stores (and the departures' atomics) before the loads.  Wavefront w computes env e0 + w with ev2g_env_stats, the
+    // statistics kernel's code (bit-identical results); the step's LDS is dead by now and holds each wavefront's [LK][64] block of parked
+    // SoC-log entries.  ev2g_get_stats / ev2g_get_stats_reset then copy the rows instead of recomputing them.
+    // (nothing of this phase is kept live across the step loop: the scalar registers of the full kernels are spoken for -- its pointers come from
+    // the parameter block, the env's scenario from this lane's step-table row)
+    double *stats_out = (INL && t == T && k_steps > 1) ? (double *)S->stats_inl : nullptr;
+    if (stats_out != nullptr) {   // (uniform)
+        __syncthreads();   // the epilogue's LDS reads are done; this workgroup's global stores and atomics are visible to all of its wavefronts
+        const int es = e0 + wv;
+        if (es < S->E) {   // (then lane 0 holds port 0 of env es: its step-table row is that of the env's scenario)
+            const int scn_s = (int)(__builtin_amdgcn_readfirstlane(hb_step) / (64u * (unsigned)T));
+            StatsView v{T, S->C, S->R, P, S->dt, (const double *)S->setpoint, (const int *)S->scn_sess, (const int *)S->scn_sess_end,
+                        (const int *)S->ss_slot, (const int *)S->ss_tarr, (const int *)S->ss_tdep, (const double *)S->ss_B, (const double *)S->ss_afap,
+                        (const int *)S->cs_served, (const double *)S->cs_sat_sum, (const double *)S->hist, (const double *)S->env_acc,
+                        (const double *)S->sess_final_cap, (const double *)S->sess_abs_e, (const double *)S->soc_log, (const PortLine *)S->line};
+            ev2g_env_stats<1, EV2G_INL_STATS_NK, EV2G_INL_STATS_LK>(v, es, true, scn_s, lane, T, stats_out,
+                                                                  lds + (size_t)wv * EV2G_INL_STATS_LK * 64, lane);
+        }
+    }
 }

@@ -60,6 +60,8 @@ def load_library(path: Optional[str] = None):
         "ev2g_kernel_name": (C.c_char_p, [vp]),
         "ev2g_last_launch_specialisation": (C.c_int, [vp]),
         "ev2g_last_launch_general_reason": (C.c_char_p, [vp]),
+        "ev2g_last_stats_route": (C.c_int, [vp]),
+        "ev2g_last_stats_reason": (C.c_char_p, [vp]),
         "ev2g_fallback_reason": (C.c_char_p, [vp]),
         "ev2g_big_kernel_reason": (C.c_char_p, [vp]),
         "ev2g_step": (C.c_int, [vp, vp, vp, vp, vp, vp]),
@@ -117,7 +119,7 @@ def load_library(path: Optional[str] = None):
 EXPORTED_SYMBOLS = [
     "ev2g_abi_version", "ev2g_create", "ev2g_destroy", "ev2g_last_error", "ev2g_load_scenarios", "ev2g_n_envs",
     "ev2g_n_scenarios", "ev2g_n_ports", "ev2g_obs_dim", "ev2g_n_steps", "ev2g_current_step", "ev2g_reset", "ev2g_reset_ex",
-    "ev2g_scenario_offset", "ev2g_set_step_extras", "ev2g_kernel_name", "ev2g_last_launch_specialisation", "ev2g_last_launch_general_reason", "ev2g_fallback_reason", "ev2g_big_kernel_reason", "ev2g_step", "ev2g_step_n",
+    "ev2g_scenario_offset", "ev2g_set_step_extras", "ev2g_kernel_name", "ev2g_last_launch_specialisation", "ev2g_last_launch_general_reason", "ev2g_last_stats_route", "ev2g_last_stats_reason", "ev2g_fallback_reason", "ev2g_big_kernel_reason", "ev2g_step", "ev2g_step_n",
     "ev2g_check_faults", "ev2g_get_stats", "ev2g_get_stats_reset", "ev2g_get_stats_reset_f32", "ev2g_reset_f32", "ev2g_collect", "ev2g_stat_name", "ev2g_peek", "ev2g_malloc", "ev2g_free",
     "ev2g_memcpy_h2d", "ev2g_memcpy_d2h", "ev2g_host_malloc", "ev2g_host_free", "ev2g_synchronize", "ev2g_fill_uniform", "ev2g_host_uniform",
     "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_rollout",
@@ -216,6 +218,16 @@ class Engine:
     def last_launch_specialisation(self) -> int:
         """0 general / 1 full / 2 full+wide instantiation of the fast-path kernel used by the last launch (-1: none, or another kernel)."""
         return int(self._lib.ev2g_last_launch_specialisation(self._h))
+
+    @property
+    def last_stats_route(self) -> int:
+        """1: the last stats() / stats_reset() copied the statistics the episode's closing step launch computed; 0: the statistics kernel
+        computed them (last_stats_reason says why); -1: no such call yet."""
+        return int(self._lib.ev2g_last_stats_route(self._h))
+
+    @property
+    def last_stats_reason(self) -> str:
+        return (self._lib.ev2g_last_stats_reason(self._h) or b"").decode()
 
     @property
     def fallback_reason(self) -> str:

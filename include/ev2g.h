@@ -274,6 +274,15 @@ int ev2g_last_launch_specialisation(const ev2g_handle *h);
 /* When the last fast-path launch got the general instantiation (0): what the caller passed or configured that ruled the full one out (the
  * first such thing), "" otherwise.  The Python Engine warns once with it: the general instantiation is ~20 % slower, silently. */
 const char *ev2g_last_launch_general_reason(const ev2g_handle *h);
+/* Where the last ev2g_get_stats / ev2g_get_stats_reset took the statistics from: 1 = computed inside the step launch that closed the episode
+ * (a launch of specialisation 2 ending at the last step, one env per wavefront: its workgroups compute their envs' statistics once they
+ * have stepped them) and copied -- ev2g_get_stats_reset is then a reset-only launch that also copies the rows; 0 = computed by the
+ * statistics kernel (a mid-episode call, per-step launches, the other instantiations and kernels, or EV2G_NO_INLAUNCH_STATS=1 at load time);
+ * -1 = no such call yet.  The values are bit-identical either way.  Any state-changing call (step, reset, refill, load) discards the in-launch
+ * results. */
+int ev2g_last_stats_route(const ev2g_handle *h);
+/* When ev2g_last_stats_route is 0: why the in-launch statistics were not available, "" otherwise. */
+const char *ev2g_last_stats_reason(const ev2g_handle *h);
 /* data-dependent faults recorded since the last reset (per-env flag word, device side):
  * returns 0 or EV2G_ERR_OVERCURRENT; synchronises the stream. */
 int ev2g_check_faults(ev2g_handle *h, int32_t *first_bad_env);
