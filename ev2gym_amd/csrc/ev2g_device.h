@@ -1149,15 +1149,9 @@ __device__ __forceinline__ StatsView ev2g_stats_view(const DevScn &s, const DevS
                      st.cs_served, st.cs_sat_sum, st.hist, st.env_acc, st.sess_final_cap, st.sess_abs_e, st.soc_log, st.line};
 }
 
-#ifndef EV2G_STATS_NK
 #define EV2G_STATS_NK 40
-#endif
-#ifndef EV2G_STATS_TB
 #define EV2G_STATS_TB 8   // entries per batch of a session's tail (beyond the NK kept ones)
-#endif
-#ifndef EV2G_STATS_LK
 #define EV2G_STATS_LK 16  // entries behind the kept ones that the first pass parks in LDS for the second (8 KB per wavefront; 16 / 32 / 48: 37.2 / 37.3 / 41.8 us at cfg2 against 38.5 without)
-#endif
 
 // get_statistics (utils.py:12-123) of env e (scenario scn) at step cur_step into row e of `out` ([E, 17]; stored only when e_valid), by the
 // W = 64 / EPWS lanes of the env's segment (`lane` inside it).  NK entries of a session's SoC log are kept in registers for the second pass

@@ -293,7 +293,7 @@ int ev2g_reset_ex(ev2g_handle *h, double *obs, int64_t scenario_offset);
 // choice (and the summation order) stays put across refills.
 static bool stats_pair(const ev2g_handle *h) {
     const long long per_scn = h->sess_cap > 0 ? (long long)h->sess_cap : (h->S + h->M - 1) / std::max(h->M, 1);
-    return (h->sess_cap > 0 ? per_scn <= 48 : h->S <= (long long)h->M * 24) && h->C <= 32 && !std::getenv("EV2G_STATS_ONE_ENV");
+    return (h->sess_cap > 0 ? per_scn <= 48 : h->S <= (long long)h->M * 24) && h->C <= 32;
 }
 
 int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
@@ -557,10 +557,8 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
                                                      (h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) ? (unsigned long long)T * E * C * 8 : 0ull});
         if (biggest >= lim) { h->wave_path = false; h->fallback_reason = "an array of the batch reaches 4 GiB (32-bit byte offsets)"; }
     }
-    if (h->wave_path) {   // wave-aligned: 64/P envs per wavefront, packed (EV2G_EPW_CAP / EV2G_EPW_ALIGN: A/B switches, read at load)
+    if (h->wave_path) {   // wave-aligned: 64/P envs per wavefront, packed
         h->wave_epw = 64 / P; h->wave_es = P;
-        if (const char *c = std::getenv("EV2G_EPW_CAP")) h->wave_epw = std::max(1, std::min(h->wave_epw, std::atoi(c)));
-        if (std::getenv("EV2G_EPW_ALIGN") && 64 / h->wave_epw >= P) h->wave_es = 64 / h->wave_epw;
         s.G = (EV2G_WAVE_BLOCK / 64) * h->wave_epw;
     }
     {   // EV2G_KERNEL=v2 forces the general kernel on the common shape (parity tests compare the two)
@@ -1072,15 +1070,7 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
         break;
         switch (s.state_kind * 4 + std::min(s.reward_kind, 3)) {   // rewards beyond the three compiled-in ones share instantiation 3
 #ifdef EV2G_ONLY_00   /* tuning builds (tools/): one specialisation, seconds to compile */
-            case 0:
-                if (str3) hipLaunchKernelGGL((ev2g_step_wave<0, 0, false, 3>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, h->stream, pp, io, t0, k, auto_reset, wa, fa0);
-                else if (wide && f32io) hipLaunchKernelGGL((ev2g_step_wave<0, 0, true, 2>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, h->stream, pp, io, t0, k, auto_reset, wa, fa0);
-                else if (full && f32io) hipLaunchKernelGGL((ev2g_step_wave<0, 0, true, 1>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, h->stream, pp, io, t0, k, auto_reset, wa, fa0);
-                else if (wide) hipLaunchKernelGGL((ev2g_step_wave<0, 0, false, 2>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, h->stream, pp, io, t0, k, auto_reset, wa, fa0);
-                else if (full) hipLaunchKernelGGL((ev2g_step_wave<0, 0, false, 1>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, h->stream, pp, io, t0, k, auto_reset, wa, fa0);
-                else if (!io.actions) hipLaunchKernelGGL((ev2g_step_wave<0, 0, true>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, h->stream, pp, io, t0, k, auto_reset, wa, fa0);
-                else hipLaunchKernelGGL((ev2g_step_wave<0, 0, false>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, h->stream, pp, io, t0, k, auto_reset, wa, fa0);
-                break;
+            EV2G_WAVE_CASE(0, 0)
             default: return fail(h, EV2G_ERR_ARG, "EV2G_ONLY_00 build: only the cfg2 specialisation exists");
 #else
             EV2G_WAVE_CASE(0, 0) EV2G_WAVE_CASE(0, 1) EV2G_WAVE_CASE(0, 2) EV2G_WAVE_CASE(0, 3)
@@ -1246,7 +1236,7 @@ static const void *mlp_kernel_for(const MlpDev &d) {
     return (const void *)ev2g_mlp3_any;
 }
 
-// the 16-row streaming kernel (ev2g_mlp3_s16) exists for the shipped shapes; EV2G_MLP_OLD=1 keeps round 3's 32-row kernel (A/B runs)
+// the 16-row streaming kernel (ev2g_mlp3_s16) exists for the shipped shapes
 struct MlpS16Pick { const void *fn; size_t lds; int ks1, nt1, nt2, nt3, nw, threads; };
 // nw: bf16 terms per weight -- 1: the bf16 network; 2 / 3: the float32 network as split bf16 operands (EV2G_MLP_F32 / EV2G_MLP_F32X3, ev2g_mlp.h)
 static MlpS16Pick mlp_s16_for(int d_in, int h1, int h2, int d_out, int nw) {
@@ -1258,15 +1248,11 @@ static MlpS16Pick mlp_s16_for(int d_in, int h1, int h2, int d_out, int nw) {
         if (ks1 <= 2 && nt3 <= 2) { ks1 = 2; nt1 = 25; nt2 = 19; nt3 = 2; }
         else if (ks1 <= 6 && nt3 <= 4) { ks1 = 6; nt1 = 25; nt2 = 19; nt3 = 4; }
     }
-    const char *old = std::getenv("EV2G_MLP_OLD");
-    if (old && old[0] == '1') return {nullptr, 0, 0, 0, 0, 0, 0, 0};
     // the bf16 network runs eight wavefronts per workgroup (two per SIMD: one's epilogue and LDS waits under the other's MFMAs -- 7.48 -> 7.39 us at
-    // 162 inputs, 6.35 -> 5.88 at 63); the float32 modes need the registers of four.  EV2G_MLP_WAVES=4 selects four for the bf16 network (A/B runs).
-    const char *w8 = std::getenv("EV2G_MLP_WAVES");
-    const int wv = (nw == 1 && !(w8 && w8[0] == '4')) ? 8 : 4;
+    // 162 inputs, 6.35 -> 5.88 at 63); the float32 modes need the registers of four.
+    const int wv = nw == 1 ? 8 : 4;
 #define EV2G_S16_CASE(K, A, B, Cc, N, W) \
     if (ks1 == K && nt1 == A && nt2 == B && nt3 == Cc && nw == N && wv == W) return {(const void *)ev2g_mlp3_s16<K, A, B, Cc, N, W>, MlpS16<K, A, B, Cc, N, W>::lds_bytes, ks1, nt1, nt2, nt3, nw, W * 64};
-    EV2G_S16_CASE(6, 25, 19, 4, 1, 4) EV2G_S16_CASE(2, 25, 19, 2, 1, 4)
     EV2G_S16_CASE(6, 25, 19, 4, 2, 4) EV2G_S16_CASE(2, 25, 19, 2, 2, 4)
     EV2G_S16_CASE(6, 25, 19, 4, 3, 4) EV2G_S16_CASE(2, 25, 19, 2, 3, 4)
     EV2G_S16_CASE(6, 25, 19, 4, 1, 8) EV2G_S16_CASE(2, 25, 19, 2, 1, 8)
@@ -1351,15 +1337,12 @@ int ev2g_mlp_create_ex(ev2g_handle *h, int d_in, int h1, int h2, int d_out, cons
 #ifdef EV2G_MLP_TIMING
     { unsigned long long *p; if (dalloc(h, m->allocs, 16, &p)) { delete m; return EV2G_ERR_HIP; } d.dbg = p; }
 #endif
-#ifdef EV2G_F32_STAMPS
-    { unsigned long long *p; if (dalloc(h, m->allocs, 8 * 16 * 8 + 8 * 16 * 16, &p)) { delete m; return EV2G_ERR_HIP; } d.dbg = p; }
-#endif
     if (precision != EV2G_MLP_BF16 && precision != EV2G_MLP_F32 && precision != EV2G_MLP_F32X3) { delete m; return fail(h, EV2G_ERR_ARG, "ev2g_mlp_create_ex: precision must be EV2G_MLP_BF16, EV2G_MLP_F32 or EV2G_MLP_F32X3"); }
     const bool f32 = precision != EV2G_MLP_BF16;
     const MlpS16Pick s16 = mlp_s16_for(d_in, h1, h2, d_out, precision == EV2G_MLP_BF16 ? 1 : (precision == EV2G_MLP_F32 ? 2 : 3));
     m->lds = s16.fn ? s16.lds : (f32 ? ev2g_mlp32_lds_bytes(d) : ev2g_mlp_lds_bytes(d));
     if (s16.fn) { m->rows = EV2G_MLPS_ROWS; m->threads = s16.threads; m->s16_ks1 = s16.ks1; m->s16_nt1 = s16.nt1; m->s16_nt2 = s16.nt2; m->s16_nt3 = s16.nt3; m->s16_nw = s16.nw; }
-    if (s16.fn && s16.nw == 1 && !std::getenv("EV2G_MLP_NO_BIG")) {
+    if (s16.fn && s16.nw == 1) {
         if (s16.ks1 == 6 && s16.nt3 == 4) { m->fn_big = (const void *)ev2g_mlp3_s16<6, 25, 19, 4, 1, 4, 2>; m->lds_big = MlpS16<6, 25, 19, 4, 1, 4, 2>::lds_bytes; }
         else if (s16.ks1 == 2 && s16.nt3 == 2) { m->fn_big = (const void *)ev2g_mlp3_s16<2, 25, 19, 2, 1, 4, 2>; m->lds_big = MlpS16<2, 25, 19, 2, 1, 4, 2>::lds_bytes; }
         if (m->fn_big) {
@@ -1427,13 +1410,6 @@ int ev2g_mlp_forward(ev2g_handle *h, const ev2g_mlp *m, const float *x, float *y
     return EV2G_OK;
 }
 
-#ifdef EV2G_F32_STAMPS
-extern "C" int ev2g_mlp_debug_f32_stamps(ev2g_handle *h, const ev2g_mlp *m, unsigned long long *out1024) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(out1024, m->dev.dbg, (8 * 16 * 8 + 8 * 16 * 16) * 8, hipMemcpyDeviceToHost));   // [workgroup 0..7][wavefront][stamp 0..7], then [workgroup][wavefront][16]: layer 3's k-steps
-    return 0;
-}
-#endif
 #ifdef EV2G_MLP_TIMING
 int ev2g_mlp_debug_stamps(ev2g_handle *h, const ev2g_mlp *m, unsigned long long *out8) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1469,8 +1445,8 @@ static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, int k, const float *o
         return fail(h, EV2G_ERR_ARG, "ev2g_collect / ev2g_rollout: a step stride is negative or reaches 4 GiB");
     StepIO io = make_io(h, nullptr, a_stride, nullptr, o_stride, reward, r_stride, done, d_stride, mask, m_stride, 0, 0);
     io.act32 = act; io.obs32 = obs;
-    // round 6: PublicPST envs of at most 32 ports go TWO to a wavefront (32 policy rows per workgroup; EV2G_FUSED_ONE_ENV=1: the one-env form, for A/B)
-    const int ae = (s.state_kind == EV2G_STATE_PUBLIC_PST && s.P <= 32 && m->s16_nw == 1 && !std::getenv("EV2G_FUSED_ONE_ENV")) ? 2 : 1;
+    // round 6: PublicPST envs of at most 32 ports go TWO to a wavefront (32 policy rows per workgroup)
+    const int ae = (s.state_kind == EV2G_STATE_PUBLIC_PST && s.P <= 32 && m->s16_nw == 1) ? 2 : 1;
     const WaveArgs wa{s.P, s.T, s.E, s.D, s.M, st.slab_port, st.slab_port_slice, st.hist, st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, ae, ae == 1 ? s.P : 32};
     FusedArgs fa{};
     fa.m = m->dev; fa.obs0 = obs0;

@@ -10,7 +10,8 @@
 //     every CU, v_mfma_f32_16x16x32_bf16 with the weights as the A operand, one static fragment sequence per wavefront through a register
 //     ring; also the FLOAT32 network as split bf16 operands (two / three terms per weight);
 //   * ev2g_mlp3_any / ev2g_mlp3_f32: any layer widths (bf16 operands / float32 operands on v_mfma_f32_32x32x2_f32), 32 rows per workgroup;
-//   * ev2g_mlp3_fixed (rounds 2-3; EV2G_MLP_OLD=1, kept for A/B runs): 32-row workgroups, v_mfma_f32_32x32x16_bf16, weights as the B operand.
+//   * ev2g_mlp3_fixed (rounds 2-3; shapes near the shipped ones that ev2g_mlp3_s16 does not cover): 32-row workgroups, v_mfma_f32_32x32x16_bf16,
+//     weights as the B operand.
 // Common to all: weights are packed ONCE on the host into the MFMA fragment order of the kernel that will read them (bf16, or float32 for
 // ev2g_mlp3_f32), so a lane's operand is one coalesced 16-byte load straight from L2; activations live in LDS; bias + activation are
 // applied to the accumulators in registers.  Precision: bf16 operands with fp32 accumulation unless a float32 mode is chosen
@@ -39,27 +40,6 @@ struct MlpDev {
 #else
 #define MLP_STAMP(i)
 #endif
-// the inline float32 policy's k-step (ev2g_mlp3_inline_f32): 0 = the compiler's interleaving of LDS reads, weight requests and MFMAs; 1 = the five MFMAs as one
-// back-to-back group behind one wait; 2 = 1 + the next k-step's operand terms read from LDS ahead of the group.  Measured at cfg2 (profiles/r06_fused_float32_policy.txt):
-// 2 with a ring of 4 fragments (no scratch) +2.5 % over 0 with a ring of 8; 1 and 2 with deeper rings spill 20..68 bytes per lane and lose 1..2.5 %.
-#ifndef EV2G_F32_GROUP
-#define EV2G_F32_GROUP 2
-#endif
-// the bf16 inline policy (ev2g_mlp3_inline), layers in which a wavefront may hold two tiles: bit 0 = layer 1, bit 1 = layer 2 walk k-step, tile slot (one operand read, two
-// independent MFMAs per k-step).  Measured at cfg2 (profiles/r06_fused_bf16_kstep_outer.txt): 0: 502 M, 1: 505 M, 2: 509 M, 3: 502 M env-steps/s -- the policy phase is bound
-// by the weight stream (437 KB per workgroup and forward at ~51 B/clk/CU): what one layer gains the other gives back (stamps); layer 2 alone keeps +1.3 %.
-#ifndef EV2G_BF16_KSOUTER
-#define EV2G_BF16_KSOUTER 2
-#endif
-// tuning builds (-DEV2G_F32_STAMPS, tools/r6/f32_stamps.py): every wavefront of the first 8 workgroups stamps the layers of the inline float32 policy (the last forward's stay)
-#ifdef EV2G_F32_STAMPS
-#define F32_STAMP(i) if (m.dbg && blockIdx.x < 8 && (threadIdx.x & 63) == 0) m.dbg[((blockIdx.x * 16 + (threadIdx.x >> 6)) * 8) + i] = __builtin_readcyclecounter();
-#define F32_STAMP2(i) if (m.dbg && blockIdx.x < 8 && (threadIdx.x & 63) == 0) m.dbg[1024 + ((blockIdx.x * 16 + (threadIdx.x >> 6)) * 16) + (i)] = __builtin_readcyclecounter();
-#else
-#define F32_STAMP(i)
-#define F32_STAMP2(i)
-#endif
-
 __host__ __device__ inline int ev2g_mlp_lds_stride(int k) { return k + 8; }   // bf16 elements per LDS row: +16 bytes against bank conflicts
 __host__ __device__ inline size_t ev2g_mlp_lds_bytes(const MlpDev &m) {
     const int a = ev2g_mlp_lds_stride(m.k1 > m.n2 ? m.k1 : m.n2), b = ev2g_mlp_lds_stride(m.n1);
@@ -92,38 +72,10 @@ __device__ __forceinline__ float ev2g_fast_tanh(float x) {
 // tanh of the float32 policies' output layer (EV2G_MLP_F32 / F32X3 in ev2g_mlp3_s16 and the fused launch's ev2g_mlp3_inline_f32: one function, so their actions stay
 // bit-identical): t = exp(-2|x|) on the hardware exp2 (1 ulp), then (1 - t) / (1 + t) by an IEEE division -- absolute error below 1.5e-7 everywhere (near 0 the
 // difference 1 - t carries t's rounding, 6e-8; beyond |x| = 9 the result is exactly 1).  The library tanhf it replaces cost the fused launch ~1.3 k cycles per
-// step on the critical path of layer 3's four wavefronts (profiles/r06_fused_float32_policy.txt); EV2G_F32_TANH=0 builds keep it.
-// the inline float32 policy's input rows: 1 = every wavefront splits ITS OWN row into the three bf16 terms at the policy's entry (22 VALU operations), into staging chunks
-// that are dead in layer 1; 0 = every wavefront splits the operand fragments it reads (6 x 44 operations per wavefront and forward: layer 1 was VALU-issue-bound, 9.5 k cycles)
-// The inline policies' weight requests through a SCALAR base: the wavefront's number read as a scalar (`tid >> 6` alone is a vector value to the compiler) makes the tile guards
-// scalar branches and a request `global_load_dwordx4 v, v_lane16, s[base]` behind scalar adds instead of three vector instructions and an address register pair.  Measured at
-// cfg2 (profiles/r06_fused_float32_policy.txt, r06_fused_bf16_kstep_outer.txt): float32 policy +1.4 % (324 -> 329 M: its layer 2 is MFMA / issue-bound), bf16 policy +0.2 %
-// (weight-stream-bound: off).
-#ifndef EV2G_S16_SADDR   // the same in the stand-alone streaming actor (ev2g_mlp3_s16)
-#define EV2G_S16_SADDR 1
-#endif
-#ifndef EV2G_BF16_SADDR
-#define EV2G_BF16_SADDR 0
-#endif
-#ifndef EV2G_F32_SADDR
-#define EV2G_F32_SADDR 1
-#endif
-#ifndef EV2G_F32_XSPLIT
-#define EV2G_F32_XSPLIT 1
-#endif
-#ifndef EV2G_F32_L1AHEAD   // layer 1 (two tiles' accumulators per wavefront): the next k-step's operand terms read ahead of the MFMA group (12 registers)
-#define EV2G_F32_L1AHEAD 0
-#endif
-#ifndef EV2G_F32_TANH
-#define EV2G_F32_TANH 1
-#endif
+// step on the critical path of layer 3's four wavefronts (profiles/r06_fused_float32_policy.txt).
 __device__ __forceinline__ float ev2g_tanh_f32(float x) {
-#if EV2G_F32_TANH
     const float t = __builtin_amdgcn_exp2f(fabsf(x) * -2.885390081777927f);   // exp(-2|x|)
     return copysignf((1.0f - t) / (1.0f + t), x);
-#else
-    return tanhf(x);
-#endif
 }
 
 // Epilogue of one 32 x 32 output tile held in MFMA accumulators: bias, activation, and either the next layer's A matrix
@@ -388,9 +340,6 @@ __global__ void __launch_bounds__(EV2G_MLP_BLOCK) ev2g_mlp3_fixed(MlpDev m, cons
 // Weights are packed per layer as [tile][k-step][lane] 16-byte fragments: lane l holds W[tile*16 + (l & 15)][ks*32 + 8*(l >> 4) + 0..7].
 #define EV2G_MLPS_ROWS 16
 #define EV2G_MLPS_RING 52
-#ifndef EV2G_MLPS_HEAD
-#define EV2G_MLPS_HEAD 28   // fragments requested before the input rows are converted
-#endif
 typedef float f32x4m __attribute__((ext_vector_type(4)));
 
 // NW > 1: the FLOAT32 network on the bf16 matrix cores (precision = EV2G_MLP_F32).  A float32 weight is stored as NW bf16 terms
@@ -432,11 +381,7 @@ __global__ void __launch_bounds__(WV * 64) ev2g_mlp3_s16(MlpDev m, const float *
     constexpr int BX = ROWS * C::SX, BH1 = ROWS * C::SH1, BH2 = ROWS * C::SH2;
     uint16_t *bufX = mlds, *bufH1 = bufX + NX * BX, *bufH2 = bufH1 + NX * BH1;
     float *lb = (float *)(bufH2 + NX * BH2);   // biases: layer 1 | layer 2 | layer 3
-#if EV2G_S16_SADDR
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane((tid >> 6) & (WV - 1));   // (uniform by construction: a scalar for the tile guards and the weight bases)
-#else
-    const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & (WV - 1);
-#endif
     const int row0 = blockIdx.x * ROWS;
     const int nr = min(ROWS, n_rows - row0);
     MLP_STAMP(0)
@@ -458,7 +403,6 @@ __global__ void __launch_bounds__(WV * 64) ev2g_mlp3_s16(MlpDev m, const float *
     float bv[(C::NB + NTH - 1) / NTH];   // the three bias vectors are ONE array on this path (ev2g_mlp_create_ex): b1 | b2 | b3, each padded to its tiles
 #pragma unroll
     for (int j = 0; j < (C::NB + NTH - 1) / NTH; j++) bv[j] = m.b1[min(tid + j * NTH, C::NB - 1)];
-#if EV2G_S16_SADDR
     const unsigned lane16 = (unsigned)lane * 16u;
     typedef const char __attribute__((address_space(1))) *wgptr;
     typedef unsigned u32x4g __attribute__((ext_vector_type(4)));
@@ -472,10 +416,6 @@ __global__ void __launch_bounds__(WV * 64) ev2g_mlp3_s16(MlpDev m, const float *
         __builtin_memcpy(&r, &v, 16);
         return r;
     };
-#else
-    const uint4 *w1 = (const uint4 *)m.w1 + lane, *w2 = (const uint4 *)m.w2 + lane, *w3 = (const uint4 *)m.w3 + lane;
-    auto frag = [&](const uint4 *w, int idx) __attribute__((always_inline)) -> uint4 { return w[(unsigned)(idx * 64)]; };
-#endif
     uint4 ring[RING];
     // fragment `seq` of this wavefront's sequence -> ring slot seq % RING (seq is a constant wherever this is called, after unrolling; the
     // tile guard is a compile-time `true` except in a layer's last tile slot).  Sequence order inside a layer: tile slot, k-step, weight term.
@@ -492,7 +432,7 @@ __global__ void __launch_bounds__(WV * 64) ev2g_mlp3_s16(MlpDev m, const float *
     // The CU's vector-memory port takes ~64 cycles per wavefront and fragment with four wavefronts asking (3.3 k cycles for the whole ring):
     // the input rows arrive while the first fragments are being requested.  HEAD of them go out first, then the rows are converted (the
     // port works the queue off meanwhile), the rest of the ring between the conversion steps; padding and biases come last.
-    constexpr int HEAD = (EV2G_MLPS_HEAD * 4 / WV) < RING ? (EV2G_MLPS_HEAD * 4 / WV) : RING;
+    constexpr int HEAD = (28 * 4 / WV) < RING ? (28 * 4 / WV) : RING;   // (28 fragments with four wavefronts)
     constexpr int PER = (RING - HEAD + NL2 - 1) / NL2;   // requests per conversion step
 #pragma unroll
     for (int sq = 0; sq < HEAD; sq++) request(sq);
@@ -672,26 +612,9 @@ __device__ __forceinline__ void ev2g_mlp3_inline(const MlpDev &m, const uint16_t
     constexpr int KS2 = C::KS2, KS3 = C::KS3;
     constexpr int MT1 = (NT1 + WVS - 1) / WVS, MT2 = (NT2 + WVS - 1) / WVS, MT3 = (NT3 + WVS - 1) / WVS;
     constexpr int S1 = MT1 * KS1, S2 = MT2 * KS2, S3 = MT3 * KS3, STOT = S1 + S2 + S3;
-#if EV2G_BF16_SADDR   // (as in ev2g_mlp3_inline_f32 below: the wavefront's number as a scalar, weight requests through a scalar base)
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned lane16 = (unsigned)lane * 16u;
-    typedef const char __attribute__((address_space(1))) *wgptr;
-    typedef unsigned u32x4g __attribute__((ext_vector_type(4)));
-    const wgptr w1 = (wgptr)(unsigned long long)m.w1, w2 = (wgptr)(unsigned long long)m.w2, w3 = (wgptr)(unsigned long long)m.w3;
-    auto frag = [&](wgptr w, int idx) __attribute__((always_inline)) -> uint4 {
-        wgptr fb = w + (unsigned long long)(unsigned)idx * 1024ull;
-        unsigned l16 = lane16;
-        asm volatile("" : "+s"(fb), "+v"(l16));
-        const u32x4g v = *(const u32x4g __attribute__((address_space(1))) *)(fb + l16);
-        uint4 r;
-        __builtin_memcpy(&r, &v, 16);
-        return r;
-    };
-#else
     const int lane = tid & 63, wave = tid >> 6;
     const uint4 *w1 = (const uint4 *)m.w1 + lane, *w2 = (const uint4 *)m.w2 + lane, *w3 = (const uint4 *)m.w3 + lane;
     auto frag = [&](const uint4 *w, int idx) __attribute__((always_inline)) -> uint4 { return w[(unsigned)(idx * 64)]; };
-#endif
     uint4 ring[RING];
     auto request = [&](int seq) __attribute__((always_inline)) {   // (seq is a constant wherever this is called, after unrolling)
         if (seq >= STOT) return;
@@ -699,21 +622,19 @@ __device__ __forceinline__ void ev2g_mlp3_inline(const MlpDev &m, const uint16_t
         const int r = seq - (L == 0 ? 0 : (L == 1 ? S1 : S1 + S2));
         const int KS = L == 0 ? KS1 : (L == 1 ? KS2 : KS3), NT = L == 0 ? NT1 : (L == 1 ? NT2 : NT3);
         const int MTL = L == 0 ? MT1 : (L == 1 ? MT2 : MT3);
-        const bool kso = RB == 1 && MTL == 2 && ((L == 0 && (EV2G_BF16_KSOUTER & 1)) || (L == 1 && (EV2G_BF16_KSOUTER & 2)));   // k-step, tile slot (below)
+        const bool kso = RB == 1 && MTL == 2 && L == 1;   // k-step, tile slot (below)
         const int i = kso ? r % MTL : r / KS, ks = kso ? r / MTL : r - i * KS;
         const auto w = L == 0 ? w1 : (L == 1 ? w2 : w3);
         if (WVS * i + WVS - 1 < NT || wave + WVS * i < NT) ring[seq % RING] = frag(w, (wave + WVS * i) * KS + ks);
     };
     // (requesting the head of the sequence a phase EARLIER in the step kernel -- behind phase E, D or C of the step before -- was tried: the whole ring
     // then lives across the step loop's back edge and the register allocator spills 40..119 registers; only layer 1's first tile (6 fragments)
-    // requested early fits -- and measured 1-2 % SLOWER than this, docs/history/experiments/round5/gpu_r5e.sh: the head's latency is not what the policy phase waits for)
-    F32_STAMP(0)
+    // requested early fits -- and measured 1-2 % SLOWER than this, docs/history/experiments/round5/README.md: the head's latency is not what the policy phase waits for)
 #pragma unroll
     for (int sq = 0; sq < RING; sq++) request(sq);
     // first barrier: every wavefront's observation columns of the step before (or the prologue's rows) are in bufX, and nobody still reads the
     // staging rows the hidden activations are about to use
     ev2g_mlp_lds_barrier();
-    F32_STAMP(1)
     if (tid < 256 * RB) {   // columns no tile writes (the next layer's k-steps read them): zeros
         const int pj = tid & 15, pr = tid >> 4;
         constexpr int P1 = KS2 * 32 - NT1 * 16, P2 = KS3 * 32 - NT2 * 16;
@@ -725,9 +646,10 @@ __device__ __forceinline__ void ev2g_mlp3_inline(const MlpDev &m, const uint16_t
         constexpr int L = decltype(Lc)::value;
         constexpr int KS = L == 0 ? KS1 : (L == 1 ? KS2 : KS3), NT = L == 0 ? NT1 : (L == 1 ? NT2 : NT3), MT = (NT + WVS - 1) / WVS;
         constexpr int base = L == 0 ? 0 : (L == 1 ? S1 : S1 + S2);
-        // EV2G_BF16_KSOUTER (bit 0: layer 1, bit 1: layer 2; one block of rows): a two-tile wavefront walks k-step, tile slot -- ONE operand read and two independent
-        // MFMAs per k-step -- instead of one tile after the other: its chain of (LDS read -> MFMA -> request) round trips halves (same chain per tile: bit-identical)
-        constexpr bool KSO = RB == 1 && MT == 2 && L < 2 && ((L == 0 && (EV2G_BF16_KSOUTER & 1)) || (L == 1 && (EV2G_BF16_KSOUTER & 2)));
+        // layer 2 with one block of rows: a two-tile wavefront walks k-step, tile slot -- ONE operand read and two independent MFMAs per k-step -- instead of one
+        // tile after the other: its chain of (LDS read -> MFMA -> request) round trips halves (same chain per tile: bit-identical).  Measured at cfg2
+        // (profiles/r06_fused_bf16_kstep_outer.txt): +1.3 % in layer 2; in layer 1 too it gives the gain back (the policy phase is bound by the weight stream)
+        constexpr bool KSO = RB == 1 && MT == 2 && L == 1;
         if (KSO) {
             f32x4m acc0[MT], acc1[MT];
 #pragma unroll
@@ -814,26 +736,21 @@ __device__ __forceinline__ void ev2g_mlp3_inline(const MlpDev &m, const uint16_t
         }
     };
     layer(std::integral_constant<int, 0>{}, bufX, C::SX, lb, bufH1, C::SH1);
-    F32_STAMP(2)
     ev2g_mlp_lds_barrier();
-    F32_STAMP(3)
     layer(std::integral_constant<int, 1>{}, bufH1, C::SH1, lb + NT1 * 16, bufH2, C::SH2);
-    F32_STAMP(4)
     ev2g_mlp_lds_barrier();
-    F32_STAMP(5)
     layer(std::integral_constant<int, 2>{}, bufH2, C::SH2, lb + (NT1 + NT2) * 16, nullptr, 0);
-    F32_STAMP(6)
     ev2g_mlp_lds_barrier();
-    F32_STAMP(7)
 }
 
 // ---- the FLOAT32 network (EV2G_MLP_F32: two bf16 terms per weight, three per activation, five MFMA products per k-step) as a device function of the
 // same 16-wavefront workgroup (ev2g_step_wave<.., ACT, 1, 2>).  Same tiles, same fragment packing, same per-tile MFMA chain -- terms, order, accumulator by
 // parity -- and the same epilogues as ev2g_mlp3_s16<.., NW = 2>: the actions are bit-identical to that kernel's.  What the 160 KB of LDS next to the step's
 // state dictate:
-//   * the input rows stay FLOAT32 in LDS (16 x (KS1*32 + 4) floats: two thirds of the three bf16 copies) and a wavefront splits its operand fragment into
-//     the three terms when it reads it -- ONCE per k-step for both of its layer-1 tiles (layer 1 walks k-step, tile, term; the other layers tile, k-step,
-//     term), so the split costs each wavefront 6 x 44 VALU operations per forward;
+//   * the input rows stay FLOAT32 in LDS (16 x (KS1*32 + 4) floats: two thirds of the three bf16 copies); at the policy's entry every wavefront splits ITS
+//     OWN row into the three terms (22 VALU operations) in staging chunks that are dead in layer 1 -- splitting the operand fragments as they are read
+//     cost each wavefront 6 x 44 operations per forward, and layer 1 was VALU-issue-bound (9.5 k cycles).  Layer 1 walks k-step, tile, term (one operand
+//     read for both of its tiles); the other layers tile, k-step, term;
 //   * the hidden activations are split where they are produced (three bf16 copies each, like the stand-alone kernel): H1's three copies and two of H2's
 //     in the step's staging rows (61.7 of 66 KB), H2's third copy over the input rows, which are dead after layer 1 -- the padding columns behind d_in
 //     are re-zeroed at the end (the step rewrites every real column before the next forward);
@@ -847,23 +764,13 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
     // Layer 3 (NT3 tiles: one wavefront each, the other wavefronts idle) through a ring of ITS OWN: with the shared ring's few slots a lone wavefront pays a
     // memory round trip per two k-steps (stamps: 330 cycles per k-step at RING = 4); the registers of layers 1 / 2 (a second tile's accumulators, the split
     // temporaries) are free there.  R3 fragments are requested when the wavefront leaves layer 2 -- they fly under the wait at that layer's closing barrier.
-#ifndef EV2G_F32_RING3
-#define EV2G_F32_RING3 8
-#endif
-    constexpr int R3 = (MT3 == 1) ? EV2G_F32_RING3 : 0, R3M = R3 > 0 ? R3 : 1;
+    constexpr int R3 = (MT3 == 1) ? 8 : 0, R3M = R3 > 0 ? R3 : 1;
     constexpr int S1 = MT1 * KS1 * NW, S2 = MT2 * KS2 * NW, S3 = R3 > 0 ? 0 : MT3 * KS3 * NW, STOT = S1 + S2 + S3;
     constexpr int BH1 = 16 * C::SH1, BH2 = 16 * C::SH2;
     static_assert(RING % NW == 0 && RING >= 2 * NW && R3 % NW == 0, "ring slots come in pairs of weight terms");
-    // (A/B switch: layer 3's few tiles on wavefronts W3OFF .. W3OFF + NT3 - 1.  Wavefronts 4..7 reach layer 2's closing barrier ~3 k cycles before the two-tile ones
-    // (0 .. 2), so their ring is full of layer-3 fragments by then -- and layer 3 takes the same 3.5 k cycles: it waits for its own LDS-read -> MFMA chain per k-step,
-    // not for weights; profiles/r06_fused_float32_policy.txt.  Default 0.)
-#ifndef EV2G_F32_W3OFF
-#define EV2G_F32_W3OFF 0
-#endif
-    constexpr int W3OFF = (MT3 == 1 && NT3 + EV2G_F32_W3OFF <= WVS) ? EV2G_F32_W3OFF : 0;
-#if EV2G_F32_SADDR
     // the wavefront's number as a SCALAR (it is uniform by construction; `tid >> 6` alone is a vector value to the compiler): the tile guards become scalar branches and a
-    // weight request is `global_load_dwordx4 v, v_lane16, s[base]` behind two scalar adds instead of three vector instructions and an address register pair per request
+    // weight request is `global_load_dwordx4 v, v_lane16, s[base]` behind two scalar adds instead of three vector instructions and an address register pair per request.
+    // Measured at cfg2 (profiles/r06_fused_float32_policy.txt): +1.4 % (layer 2 is MFMA / issue-bound); the bf16 policy, bound by the weight stream, keeps vector addresses
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lane16 = (unsigned)lane * 16u;
     typedef const char __attribute__((address_space(1))) *wgptr;
@@ -878,11 +785,6 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
         __builtin_memcpy(&r, &v, 16);
         return r;
     };
-#else
-    const int lane = tid & 63, wave = tid >> 6;
-    const uint4 *w1 = (const uint4 *)m.w1 + lane, *w2 = (const uint4 *)m.w2 + lane, *w3 = (const uint4 *)m.w3 + lane;
-    auto frag = [&](const uint4 *w, int idx) __attribute__((always_inline)) -> uint4 { return w[(unsigned)(idx * 64)]; };
-#endif
     const float *ball = m.b1;   // b1 | b2 | b3, each padded to its tiles
     uint4 ring[RING];
     auto request = [&](int seq) __attribute__((always_inline)) {   // (seq is a constant wherever this is called, after unrolling)
@@ -894,13 +796,12 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
         if (L == 0) { const int ks = r / (MT1 * NW), r2 = r - ks * (MT1 * NW); i = r2 / NW; rem = ks * NW + (r2 - i * NW); }
         else { i = r / (KS * NW); rem = r - i * (KS * NW); }
         const auto w = L == 0 ? w1 : (L == 1 ? w2 : w3);
-        if (L == 2) { if ((unsigned)(wave - W3OFF) < (unsigned)NT3) ring[seq % RING] = frag(w, (wave - W3OFF) * (KS * NW) + rem); }
+        if (L == 2) { if ((unsigned)wave < (unsigned)NT3) ring[seq % RING] = frag(w, wave * (KS * NW) + rem); }
         else
         if (WVS * i + WVS - 1 < NT || wave + WVS * i < NT) ring[seq % RING] = frag(w, (wave + WVS * i) * (KS * NW) + rem);
     };
-    F32_STAMP(0)
     uint4 ring3[R3M];
-    const int tile3 = wave - W3OFF;   // this wavefront's layer-3 tile, if 0 <= tile3 < NT3
+    const int tile3 = wave;   // this wavefront's layer-3 tile, if tile3 < NT3
     auto request3 = [&](int r) __attribute__((always_inline)) {   // fragment r = ks * NW + term of that tile (callers: wavefronts that own one)
         if (R3 > 0 && r < KS3 * NW) ring3[r % R3M] = frag(w3, tile3 * (KS3 * NW) + r);
     };
@@ -910,7 +811,6 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
     for (int i = 0; i < MT1; i++) bias1[i] = *(const f32x4m *)(ball + min(wave + WVS * i, NT1 - 1) * 16 + kq * 4);
 #pragma unroll
     for (int sq = 0; sq < RING; sq++) request(sq);
-#if EV2G_F32_XSPLIT
     // This wavefront's OWN input row (its env's observation: its own LDS writes, in program order) -> the three bf16 terms, into its own 512-byte chunks of three
     // staging rows (xs + c * xcs + wave * 256 elements; chunks no other wavefront touches outside the battery-maths phase, and dead in layer 1: H2's first two
     // copies land there in layer 2).  The 24 16-byte pieces of a row sit at piece (j ^ row): the rows are 512 bytes apart -- all on the same banks -- and a
@@ -929,9 +829,7 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
             }
         }
     }
-#endif
     ev2g_mlp_lds_barrier();   // the step's observation columns are in bufX; nobody reads the staging rows any more
-    F32_STAMP(1)
     if (tid < 256) {   // H1's columns no tile writes (layer 2's last k-step reads them): zeros, in every copy
         const int pj = tid & 15, pr = tid >> 4;
         constexpr int P1 = KS2 * 32 - NT1 * 16;
@@ -948,12 +846,11 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
         __builtin_memcpy(&av[1], &w_t1, 16);
 #pragma unroll
         for (int k = 0; k < NX; k++) __builtin_memcpy(&bv[k], &bt[k], 16);
-#if EV2G_F32_GROUP
         // every operand of the k-step collected BEFORE its first MFMA, then the five MFMAs back to back: a wait or a load between two MFMAs on the same accumulator
-        // costs ~40 cycles each (MI355X_MICROARCH.md, per-instruction constants)
+        // costs ~40 cycles each (MI355X_MICROARCH.md, per-instruction constants).  With the next k-step's operand terms read ahead (layers 2 and 3 below) and a
+        // ring of 4 fragments this measured +2.5 % at cfg2 over the compiler's own interleaving (profiles/r06_fused_float32_policy.txt)
         asm volatile("" : "+v"(av[0]), "+v"(av[1]), "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]));
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int p = NW - 1; p >= 0; p--) {
             bf16x8 a;
@@ -968,9 +865,7 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
                 }
             }
         }
-#if EV2G_F32_GROUP
         __builtin_amdgcn_sched_barrier(0);
-#endif
     };
     auto hidden_out = [&](const f32x4m &acc, uint16_t *o0, uint16_t *o1, uint16_t *o2, int so, int col) __attribute__((always_inline)) {
         uint32_t lo[NX], hi[NX];
@@ -980,7 +875,7 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
         *(uint2 *)(o1 + brow * so + col) = make_uint2(lo[1], hi[1]);
         *(uint2 *)(o2 + brow * so + col) = make_uint2(lo[2], hi[2]);
     };
-    // ---- layer 1: float32 rows -> three terms per operand fragment, once per k-step for both tile slots ----
+    // ---- layer 1: the input rows' three terms, one operand read per k-step for both tile slots ----
     f32x4m bias2[MT2];
 #pragma unroll
     for (int i = 0; i < MT2; i++) bias2[i] = *(const f32x4m *)(ball + NT1 * 16 + min(wave + WVS * i, NT2 - 1) * 16 + kq * 4);   // (a layer ahead)
@@ -988,31 +883,11 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
         f32x4m acc0[MT1], acc1[MT1];
 #pragma unroll
         for (int i = 0; i < MT1; i++) { acc0[i] = bias1[i]; acc1[i] = f32x4m{0.f, 0.f, 0.f, 0.f}; }
-#if EV2G_F32_XSPLIT && EV2G_F32_L1AHEAD
-        uint4 btn[NX];
-#pragma unroll
-        for (int k = 0; k < NX; k++) btn[k] = *(const uint4 *)(xs + k * xcs + brow * 256 + ((kq ^ brow) << 3));
-#endif
 #pragma unroll
         for (int ks = 0; ks < KS1; ks++) {
             uint4 bt[NX];
-#if EV2G_F32_XSPLIT && EV2G_F32_L1AHEAD
-#pragma unroll
-            for (int k = 0; k < NX; k++) bt[k] = btn[k];
-            if (ks + 1 < KS1) {
-#pragma unroll
-                for (int k = 0; k < NX; k++) btn[k] = *(const uint4 *)(xs + k * xcs + brow * 256 + ((((ks + 1) * 4 + kq) ^ brow) << 3));
-            }
-#elif EV2G_F32_XSPLIT
 #pragma unroll
             for (int k = 0; k < NX; k++) bt[k] = *(const uint4 *)(xs + k * xcs + brow * 256 + (((ks * 4 + kq) ^ brow) << 3));
-#else
-            const float4 xa = *(const float4 *)(bufX + brow * sxf + ks * 32 + kq * 8), xb = *(const float4 *)(bufX + brow * sxf + ks * 32 + kq * 8 + 4);
-            uint32_t t0[NX], t1[NX], t2[NX], t3[NX];
-            ev2g_split_bf16<NX>(xa.x, xa.y, t0); ev2g_split_bf16<NX>(xa.z, xa.w, t1); ev2g_split_bf16<NX>(xb.x, xb.y, t2); ev2g_split_bf16<NX>(xb.z, xb.w, t3);
-#pragma unroll
-            for (int k = 0; k < NX; k++) bt[k] = make_uint4(t0[k], t1[k], t2[k], t3[k]);
-#endif
 #pragma unroll
             for (int i = 0; i < MT1; i++) {
                 const int sq0 = (ks * MT1 + i) * NW;
@@ -1027,9 +902,7 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
             if (WVS * i + WVS - 1 < NT1 || tile < NT1) hidden_out(acc0[i] + acc1[i], h1, h1 + BH1, h1 + 2 * BH1, C::SH1, tile * 16 + kq * 4);
         }
     }
-    F32_STAMP(2)
     ev2g_mlp_lds_barrier();
-    F32_STAMP(3)
     if (tid < 256) {   // H2's tail columns (its third copy lies over the input rows: only now)
         const int pj = tid & 15, pr = tid >> 4;
         constexpr int P2 = KS3 * 32 - NT2 * 16;
@@ -1042,29 +915,21 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
         constexpr int base = L == 1 ? S1 : S1 + S2;
 #pragma unroll
         for (int i = 0; i < MT; i++) {
-            const int tile = L == 2 ? wave - W3OFF : wave + WVS * i;
+            const int tile = L == 2 ? wave : wave + WVS * i;
             if (L == 2 ? (unsigned)tile < (unsigned)NT : (WVS * i + WVS - 1 < NT || tile < NT)) {   // (uniform)
                 f32x4m acc0 = bias[i], acc1 = f32x4m{0.f, 0.f, 0.f, 0.f};
-#if EV2G_F32_GROUP >= 2   // the next k-step's operand terms are read from LDS before this one's MFMA group (12 registers more)
-                uint4 btn[NX];
+                uint4 btn[NX];   // the next k-step's operand terms are read from LDS before this one's MFMA group (12 registers more)
                 btn[0] = *(const uint4 *)(a0 + brow * sa + kq * 8); btn[1] = *(const uint4 *)(a1 + brow * sa + kq * 8); btn[2] = *(const uint4 *)(a2 + brow * sa + kq * 8);
-#endif
 #pragma unroll
                 for (int ks = 0; ks < KS; ks++) {
                     const int sq0 = base + (i * KS + ks) * NW;
                     uint4 bt[NX];
-#if EV2G_F32_GROUP >= 2
                     bt[0] = btn[0]; bt[1] = btn[1]; bt[2] = btn[2];
                     if (ks + 1 < KS) {
                         btn[0] = *(const uint4 *)(a0 + brow * sa + (ks + 1) * 32 + kq * 8);
                         btn[1] = *(const uint4 *)(a1 + brow * sa + (ks + 1) * 32 + kq * 8);
                         btn[2] = *(const uint4 *)(a2 + brow * sa + (ks + 1) * 32 + kq * 8);
                     }
-#else
-                    bt[0] = *(const uint4 *)(a0 + brow * sa + ks * 32 + kq * 8);
-                    bt[1] = *(const uint4 *)(a1 + brow * sa + ks * 32 + kq * 8);
-                    bt[2] = *(const uint4 *)(a2 + brow * sa + ks * 32 + kq * 8);
-#endif
                     if (L == 2 && R3 > 0) {
                         chain(ks, ring3[(ks * NW) % R3M], ring3[(ks * NW + 1) % R3M], bt, acc0, acc1);
 #pragma unroll
@@ -1074,9 +939,7 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
 #pragma unroll
                     for (int p = 0; p < NW; p++) request(sq0 + p + RING);
                     }
-                    if (L == 2) { F32_STAMP2(ks) }
                 }
-                if (L == 2) { F32_STAMP2(15) }
                 const f32x4m acc = acc0 + acc1;
                 const int col = tile * 16 + kq * 4;
                 if (L == 1) hidden_out(acc, h2ab, h2ab + BH2, h2c, C::SH2, col);
@@ -1105,19 +968,15 @@ __device__ __forceinline__ void ev2g_mlp3_inline_f32(const MlpDev &m, float *buf
     };
     f32x4m bias3[MT3];
 #pragma unroll
-    for (int i = 0; i < MT3; i++) bias3[i] = *(const f32x4m *)(ball + (NT1 + NT2) * 16 + min(max(wave - W3OFF, 0) + WVS * i, NT3 - 1) * 16 + kq * 4);
+    for (int i = 0; i < MT3; i++) bias3[i] = *(const f32x4m *)(ball + (NT1 + NT2) * 16 + min(max(wave, 0) + WVS * i, NT3 - 1) * 16 + kq * 4);
     layer(std::integral_constant<int, 1>{}, h1, h1 + BH1, h1 + 2 * BH1, C::SH1, bias2);
     if (R3 > 0 && (unsigned)tile3 < (unsigned)NT3) {   // (uniform)
 #pragma unroll
         for (int r = 0; r < R3; r++) request3(r);
     }
-    F32_STAMP(4)
     ev2g_mlp_lds_barrier();
-    F32_STAMP(5)
     layer(std::integral_constant<int, 2>{}, h2ab, h2ab + BH2, h2c, C::SH2, bias3);
-    F32_STAMP(6)
     ev2g_mlp_lds_barrier();
-    F32_STAMP(7)
     {   // the input rows' padding columns, which H2's third copy overwrote
         const int d_in = m.d_in, pr = tid >> 6;
         for (int cc = d_in + lane; cc < KS1 * 32; cc += 64) bufX[pr * sxf + cc] = 0.f;

@@ -43,7 +43,7 @@ struct RefillArgs {
     int *overflow;
     double *head_tab; int head_nh;   // fast path: observation head table [M, T+1, NH] (or null)
     double *step_tab;                // fast path: [M, T, 8] per-step scalars (or null)
-    unsigned long long *dbg;    // [16] cycle stamps of workgroup 0 (tools/refill_time.py --stamps), or null
+    unsigned long long *dbg;    // [16] cycle stamps of workgroups 0, n/2 and n-1 (EV2G_REFILL_STAMPS=1: the host prints them at the next refill), or null
     int multi;                  // chargers with several ports (or a topology file): an arriving EV takes the charger's first free port (ev_charger.py:266-286) --
                                 // the kernel replays that per charger before it places the sessions (needs T <= 256 and at most EV2G_RF_K sessions per port)
     const double *tr_cap;       // [R] transformer capacities of a topology file (device copy), or null: cfg.transformer_max_power
@@ -53,11 +53,6 @@ struct RefillArgs {
         if (blockIdx.x == gridDim.x - 1 && ((i) == 0 || (i) == 6)) a.dbg[8 + ((i) != 0)] = __builtin_readcyclecounter(); \
         if (blockIdx.x == gridDim.x / 2 && ((i) == 0 || (i) == 6)) a.dbg[10 + ((i) != 0)] = __builtin_readcyclecounter(); }
 
-#ifdef EV2G_RF_SUBSTAMPS   // development: cycles of workgroup 0 per part of the setpoint phase, accumulated in dbg[16 + i]
-#define RF_SUB(i) { const unsigned long long now_ = __builtin_readcyclecounter(); if (a.dbg && blockIdx.x == 0 && threadIdx.x == 0) a.dbg[16 + (i)] += now_ - sub_t; sub_t = now_; }
-#else
-#define RF_SUB(i)
-#endif
 __device__ __forceinline__ double rf_wave_max(double v) {
     for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
     return v;
@@ -157,7 +152,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
         const int q = q0 + lane;
         int n = 0, p = 0;
         if (q < P) p = s.slot_port[q];
-#ifndef EV2G_RF_SERIAL_PASS1
         const int t_end = g.T - g.min_stay_steps - 1;
         if (t_end <= 128) {
             // ev2g_gen_port_sessions' walk (ev2g_gen.h) in two parts.  The spawn trials do not depend on the port's history -- one hash round on the
@@ -195,12 +189,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
             n = ev2g_gen_port_sessions(g, rng, fleet, share_sum, p, tab, [&](int i, const Ev2gGenSession &e) { if (i < EV2G_RF_K) { l_spawn[p * EV2G_RF_K + i] = (unsigned char)(e.t_arr - 1); if (multi) l_dep[p * EV2G_RF_K + i] = (unsigned char)e.t_dep; } });
         }
         if (q < P && multi) { l_pslot[p] = q; l_rcnt[q] = 0; l_free[p] = 0; }
-#else
-        if (q < P) {
-            n = ev2g_gen_port_sessions(g, rng, fleet, share_sum, p, tab, [&](int i, const Ev2gGenSession &e) { if (i < EV2G_RF_K) { l_spawn[p * EV2G_RF_K + i] = (unsigned char)(e.t_arr - 1); if (multi) l_dep[p * EV2G_RF_K + i] = (unsigned char)e.t_dep; } });
-            if (multi) { l_pslot[p] = q; l_rcnt[q] = 0; l_free[p] = 0; }
-        }
-#endif
         if (multi && n > K) { n = K; if (a.overflow) atomicAdd(a.overflow, 1); }   // (a port with more sessions than the replay remembers: cut, and counted)
         const int incl = rf_wave_incl_scan(n, lane);
         const int base = carry + incl - n;
@@ -475,13 +463,7 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
                         if (lane < ncol) {   // (one exec mask around the whole loop, four rows' reads in flight: per row, the branch and the wait were the chain)
                             double *out = rows + lane;
                             int kk = j, step = 0;
-                            auto put = [&](double *o, double v) {
-#ifndef EV2G_RF_NO_NT_TABLES
-                                __builtin_nontemporal_store(v, o);
-#else
-                                *o = v;
-#endif
-                            };
+                            auto put = [&](double *o, double v) { __builtin_nontemporal_store(v, o); };
                             for (; step + 4 <= T - 1; step += 4, kk += 4, out += 4 * ncol) {
                                 double x[4];
 #pragma unroll
@@ -528,11 +510,8 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
                             }
                         }
                         const double v = (typ == 0) ? vp : ((typ == 1) ? vl : vm);
-#ifndef EV2G_RF_NO_NT_TABLES   // streaming stores: 54 KB per scenario written once and read by a later episode's step kernel (-3.5 % of the window, tools/r6/gpu_rf6.sh)
+                        // streaming stores: 54 KB per scenario written once and read by a later episode's step kernel (-3.5 % of the window)
                         if (lane < ncol) __builtin_nontemporal_store(v, &rows[(size_t)step * ncol + lane]);
-#else
-                        if (lane < ncol) rows[(size_t)step * ncol + lane] = v;
-#endif
                     }
                 }
             }
@@ -554,9 +533,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
     __syncthreads();
     RF_STAMP(5)
     double *sp_out = RW(double, setpoint) + (size_t)ms * T;
-#ifdef EV2G_RF_SUBSTAMPS
-    unsigned long long sub_t = __builtin_readcyclecounter();
-#endif
     const int n_sess = min(total, cap);
     if (!c.power_setpoint_enabled || n_sess == 0) {
         for (int t = lane; t < T; t += 64) { sp_out[t] = 0.0; if (a.step_tab) a.step_tab[((size_t)ms * T + t) * 8 + 5] = 0.0; }
@@ -570,7 +546,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
         double *sp = l_a;   // [T] accumulators (the transformer loop is done with l_a)
         double *prel = l_x; // [T] price relative to the day's maximum: once per step instead of once per session and step (the same quotient)
         for (int t = lane; t < T; t += 64) { sp[t] = 0.0; prel[t] = l_cp[t] / pmax; }
-#ifndef EV2G_RF_SERIAL_SETPOINTS
         // A session's weights are zero outside its stay (ev2g_gen_setpoint_weight) and a zero weight adds 0.0 to the accumulators, so only the
         // (session, step-of-its-stay) pairs need the normal draw and the division: ~30 of a session's 112 steps.  Consecutive sessions (in the
         // host's accumulation order) are PACKED into the wavefront, a lane per pair, as long as their stays fit 64 lanes together, and TWO such
@@ -605,7 +580,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
             }
             packed_ok = __ballot(!plain) == 0ull;
         }
-        RF_SUB(0)
         if (packed_ok) {
             double acc0 = 0.0, acc1 = 0.0;   // sp[lane], sp[lane + 64]
             int j = 0;
@@ -625,7 +599,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
                     }
                     bn[u] = nb;
                 }
-                RF_SUB(1)
                 // ---- one weight per lane and batch (inside the stay: ev2g_gen_setpoint_weight's `win`) ----
                 double w[2];
 #pragma unroll
@@ -635,7 +608,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
                     l_wb[u * 64 + lane] = w[u];
                 }
                 __syncthreads();
-                RF_SUB(2)
                 // ---- every member's weight sum on the host's tree: leaf v holds the weight of the member's step t with t mod 64 == v ----
                 double my_wsum[2] = {1.0, 1.0};
 #pragma unroll
@@ -652,7 +624,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
                         off += L;
                     }
                 }
-                RF_SUB(3)
                 // ---- one load per lane and batch ----
                 double val[2];
 #pragma unroll
@@ -665,7 +636,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
 #pragma unroll
                 for (int u = 0; u < 2; u++) l_wb[u * 64 + lane] = val[u];
                 __syncthreads();
-                RF_SUB(4)
                 // ---- the sessions add theirs to the accumulators one after the other ----
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
@@ -680,12 +650,10 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
                     }
                 }
                 __syncthreads();
-                RF_SUB(5)
             }
             if (lane < T) sp[lane] = acc0;
             if (lane + 64 < T) sp[lane + 64] = acc1;
         } else
-#endif
         for (int p = 0; p < P; p++) {   // port by port, a port's sessions in time order: the host's accumulation order
             const int base = l_pbase[p], cnt = max(0, min(l_pcnt[p], cap - base));
             for (int i = 0; i < cnt; i++) {
@@ -705,17 +673,14 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
             }
         }
         __syncthreads();
-        RF_SUB(6)
         const int kw = ev2g_gen_median_window(dt), left = kw / 2;
         for (int i = lane; i < T + kw - 1; i += 64) { const int t = i - left; l_pad[i] = sp[t < 0 ? 0 : (t >= T ? T - 1 : t)]; }
         __syncthreads();
         for (int t = lane; t < T; t += 64) { const double v = ev2g_gen_median(l_pad, t, kw); sp_out[t] = v; if (a.step_tab) a.step_tab[((size_t)ms * T + t) * 8 + 5] = v; }
     }
-    RF_SUB(7)
     // the fast path's occupancy / arrival masks of every step (step-table slots 6, 7; ev2g_build_occ_mask_kernel's values, ev2g_device.h)
     if (a.step_tab) {
         __syncthreads();
-        RF_SUB(8)
         if (T <= 128) {
             // A lane per port slot gathers its sessions' stays as a bit per step (occupied: t_arr .. t_dep; arriving at the end of step t: t_arr == t + 1),
             // then one ballot per step turns the rows into the per-step masks over the ports; lane (t mod 64) keeps step t's pair and stores it.
@@ -766,7 +731,6 @@ __global__ void __launch_bounds__(64) ev2g_refill_kernel(DevScn s, DevState st, 
             }
         }
     }
-    RF_SUB(9)
     RF_STAMP(6)
 #undef RW
 }

@@ -30,9 +30,6 @@
 #include "ev2g_step_v2.h"
 
 #define EV2G_BIG_BLOCK 512
-#ifndef EV2G_BIG_PRIO
-#define EV2G_BIG_PRIO 3
-#endif
 #define EV2G_BIG_NCC 16          // charger classes (distinct constant tuples) the LDS table holds
 #define EV2G_BIG_TMAX 32766      // windows are kept as 16-bit step numbers (0x7fff = none)
 
@@ -242,10 +239,6 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
                 const int q = tid_l + u * BLOCK, qc = (q < P) ? q : 0;
                 tatd[u] = s_tatd[qc]; cw[u] = s_cycd[qc]; capb[u] = s_cap[qc];
             }
-#ifdef EV2G_PT_ASPLIT
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            PT_MARK(7)
-#endif
 #pragma unroll
             for (int u = 0; u < 2; u++) {
                 const int q = tid_l + u * BLOCK;
@@ -269,9 +262,6 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
                 if (valid) { s_x[q] = amps[u]; s_y[q] = 0.0; }
             }
         }
-#ifdef EV2G_PT_ASPLIT
-        PT_MARK(6)
-#endif
         {   // compact the ports that have battery maths to do: charging items from the front of `items`, discharging ones from its back;
             // one LDS atomic per wavefront and list (ballot + lane prefix count)
             const unsigned long long mc0 = __ballot(amps[0] > 0.0), mc1 = __ballot(amps[1] > 0.0);
@@ -290,9 +280,6 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
             else if (amps[1] < 0.0) items[NP - 1 - (bdis + __popcll(md0) + EV2G_MBCNT(md1))] = (unsigned short)(tid_l + BLOCK);
 #undef EV2G_MBCNT
         }
-#ifdef EV2G_PT_ASPLIT
-        PT_MARK(0)
-#endif
         // ---- requests whose answers are consumed behind the battery maths: the next step's actions, this step's observation-head pairs ----
         {
             const bool more = (kk + 1 < k_steps);
@@ -305,11 +292,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
 #pragma unroll
         for (int u = 0; u < 2; u++) {   // ONE unconditional 16-byte load per slot from a selected, always valid address (a load in a branch that merges with a
                                         // default costs a vmcnt(0) drain, ev2g_step_v2.h); a price lane reads the pair that holds its column (clamped inside the row)
-#ifdef EV2G_BIG_ABL_HP0   /* ablation (wrong results): the head rows of step 0 every step -- cache-resident instead of streamed */
-            EV2G_GP(const double) pw = win_base + hp_src[u];
-#else
             EV2G_GP(const double) pw = win_base + (long long)sstep * 40 + hp_src[u];
-#endif
             EV2G_GP(const double) pp = b_prch + min(sstep + (-2 - hp_dst[u]), T - 2);
             hp[u] = __builtin_nontemporal_load((const d2a8_t __attribute__((address_space(1))) *)((hp_dst[u] < -1) ? pp : pw));
         }
@@ -333,18 +316,12 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
             }
             if (lane == 0) cntev[wv] = __popcll(me0) + __popcll(me1);
         }
-#ifdef EV2G_PT_ASPLIT
-        PT_MARK(4)
-#else
         PT_MARK(0)
-#endif
         lds_barrier();
         PT_MARK(1)
 
         // ---------------- B: worker lanes, battery maths on the compact list ----------------
-#ifndef EV2G_BIG_NOPRIO
-        __builtin_amdgcn_s_setprio(EV2G_BIG_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(3);   // the workers are the workgroup's critical path whenever they have items
         {
             const int nch = cnt[0], ndis = cnt[1];
             const int nchp = (nch + 63) & ~63;  // discharge items start on a wavefront boundary
@@ -441,11 +418,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
         // the observation head: |charge price| window and the transformers' load / PV / limit windows, copied from the scenario's tables
 #pragma unroll
         for (int u = 0; u < 2; u++) {
-#ifdef EV2G_BIG_ABL_NOHS  /* ablation (wrong results): no head stores */
-            if (hp_dst[u] >= 0) asm volatile("" :: "v"(hp[u]));
-#else
             if (hp_dst[u] >= 0) *(d2_t *)(obs_e + hp_dst[u]) = hp[u];
-#endif
             else if (hp_dst[u] < -1) {   // a price column: zero past the horizon
                 const int c = -2 - hp_dst[u], k = sstep + c;
                 obs_e[2 + c] = (k < T) ? fabs((k > T - 2) ? hp[u].y : hp[u].x) : 0.0;
@@ -598,9 +571,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
                 if (lane == 0) { wsum[3 * NW + wv] = w_ech; wsum[4 * NW + wv] = w_edis; emg[wv] = (double)n_em; }
             }
         }
-#ifndef EV2G_PT_ASPLIT
         PT_MARK(3)
-#endif
         // ---------------- D: power per transformer: 8 lanes per segment, DPP butterfly (the tree of ev2g_step_v2's one-env scheme) ----------------
         if (tid_l < R * 8) {
             const int r = tid_l >> 3, j = tid_l & 7;
@@ -612,11 +583,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
             acc += xor4_f64(acc);
             if (j == 0) tsum[r] = acc;
         }
-#ifdef EV2G_PT_ASPLIT
-        PT_MARK(3)
-#else
         PT_MARK(4)
-#endif
         lds_barrier();
         PT_MARK(1)
 

@@ -16,9 +16,7 @@
 #include "ev2g_step_v2.h"
 #include "ev2g_mlp.h"
 
-#ifndef EV2G_WAVE_BLOCK
 #define EV2G_WAVE_BLOCK 256
-#endif
 
 __host__ __device__ inline size_t ev2g_wave_lds_bytes(int envs_per_group, int block = EV2G_WAVE_BLOCK) {
     const size_t NS = (size_t)block;
@@ -26,27 +24,17 @@ __host__ __device__ inline size_t ev2g_wave_lds_bytes(int envs_per_group, int bl
 }
 // the in-launch statistics phase (end of ev2g_step_wave): SoC-log entries per session kept in registers / parked in LDS (a multiple of
 // EV2G_STATS_TB; the whole workgroup's blocks, BLOCK / 64 x LK x 64 doubles, must fit the step's LDS -- checked by the host)
-#ifndef EV2G_INL_STATS_NK
 #define EV2G_INL_STATS_NK 12
-#endif
-#ifndef EV2G_INL_STATS_LK
 #define EV2G_INL_STATS_LK 16
-#endif
 __host__ __device__ inline size_t ev2g_inl_stats_lds_bytes(int block = EV2G_WAVE_BLOCK) { return (size_t)block * EV2G_INL_STATS_LK * sizeof(double); }
 // the fused actor + step instantiation (ACT, below): 16 envs and 16 wavefronts per workgroup, plus the policy's input rows (bf16) and its actions (float) in LDS
 #define EV2G_FUSED_BLOCK 1024
 #define EV2G_FUSED_SX 200     // MlpS16<6, ..>::SX: bf16 elements per observation row in LDS
-#ifndef EV2G_FUSED_RING
 #define EV2G_FUSED_RING 10    // weight fragments a wavefront keeps in flight (ev2g_mlp3_inline)
-#endif
-#ifndef EV2G_FUSED_RING2
 #define EV2G_FUSED_RING2 7    // the same with two envs per wavefront (AE = 2): the second row block's accumulators and operand take 12 registers
-#endif
 
 #define EV2G_FUSED_SXF 196    // the float32 policy (NWF = 2): floats per observation row in LDS (6 k-steps of 32 + 16 bytes against bank conflicts)
-#ifndef EV2G_FUSED_RINGF
-#define EV2G_FUSED_RINGF 4    // ... and its weight fragments in flight per wavefront (two terms per k-step; 6 / 8 measure the same as 4 and leave no registers for EV2G_F32_GROUP = 2)
-#endif
+#define EV2G_FUSED_RINGF 4    // ... and its weight fragments in flight per wavefront (two terms per k-step; 6 / 8 measure the same as 4 and leave no registers for reading the next k-step's operands ahead)
 __host__ __device__ inline size_t ev2g_fused_lds_bytes(int envs_per_wave = 1, int weight_terms = 1) {
     if (weight_terms > 1)   // float32 input rows (H2's third copy lies over them between layers 1 and 3), biases from global memory: 163 488 of the 163 840 bytes
         return ev2g_wave_lds_bytes(EV2G_FUSED_BLOCK / 64 * envs_per_wave, EV2G_FUSED_BLOCK) + (size_t)16 * EV2G_FUSED_SXF * 4;
@@ -179,11 +167,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
     static_assert(AE == 1 || (ACT && SK == 1 && AE == 2), "two envs per wavefront in the fused instantiation: PublicPST only");
     static_assert(NWF == 1 || (ACT && AE == 1 && NWF == 2), "the float32 policy inside the launch: one env per wavefront (16 policy rows per workgroup)");
     constexpr bool FULL = FULLK >= 1, WIDE = FULLK >= 2, STR = FULLK >= 3 || ACT;
-#ifdef EV2G_STR_NT_OFF   // (A/B: the kept rows as ordinary stores)
-    constexpr bool STR_NT = false;
-#else
-    constexpr bool STR_NT = FULLK >= 3;
-#endif   // the kept observation rows (0.6 GB per cfg2 launch) as streaming stores: they should not displace the state lines in L2 (-2 %, profiles/r05_ab_strided_nt.txt)
+    constexpr bool STR_NT = FULLK >= 3;   // the kept observation rows (0.6 GB per cfg2 launch) as streaming stores: they should not displace the state lines in L2 (-2 %, profiles/r05_ab_strided_nt.txt)
     constexpr bool F64 = FULL && !IO32, F32 = FULL && IO32;   // full with float64 actions in / observations out, or with the float32 hand-over
     constexpr bool INL = FULLK == 2 && !IO32 && !ACT && BLOCK == EV2G_WAVE_BLOCK;   // the in-launch statistics phase is compiled in (end of the kernel)
 #if defined(EV2G_PHASE_TIMING) && defined(EV2G_PT_OUTER)
@@ -495,13 +479,9 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         // A wavefront none of whose ports holds an EV in this step or receives one at its end (workplace nights, early mornings: a third of the
         // wavefront-steps at cfg2) has nothing to decide in phases A and C: every action is masked, every per-port observation column and mask entry
         // is zero, nothing is staged (phase D skips such a wavefront already).  The full kernels know it from the windows in their registers.
-#ifdef EV2G_NO_EMPTY_WAVE_PATH
-        const bool wave_live = true;
-#else
         // (one env per wavefront only: with two or three a wavefront is rarely empty and the test costs more than it saves -- cfg3 +0.8 %, cfg2 -3 %,
         // profiles/r05_ab_empty_wavefront_path.txt)
         const bool wave_live = !FULL || EPW != 1 || __ballot(valid && ((r_ta <= t && t <= r_td) || r_ta == sstep)) != 0ull;   // (uniform)
-#endif
         if (valid && wave_live) {
             // every LDS operand of the phase in one batch (one wait) instead of one round trip per branch
             int ta = FULL ? r_ta : s_ta[tid_l], td = FULL ? r_td : s_td[tid_l];
@@ -831,7 +811,6 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                               // an unclamped index past the env reads a neighbour's slot (or, behind the last row, the array that
                               // follows `stage` in LDS) and is masked
                 const bool upper = P > 16;   // (uniform)
-#ifndef EV2G_NO_DPAR
                 // two or three envs per wavefront (the PublicPST benchmark shape: 3 x 20 ports): their reductions are independent -- all LDS
                 // reads first, then the three add / butterfly chains side by side -- instead of one env after the other, each behind its own
                 // LDS round trip (1.9 k of a workgroup-step's 10.8 k ticks at cfg3)
@@ -866,7 +845,6 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                 if (EPW == 3) envs_at_once(std::integral_constant<int, 3>{});
                 else if (EPW == 2) envs_at_once(std::integral_constant<int, 2>{});
                 else
-#endif
 #pragma unroll 1
                 for (int w = 0; w < EPW; w++) {
                     const int a = wbase + w * ES, b = a + P;

@@ -134,9 +134,10 @@ int main() {
     assert subprocess.call([str(tmp_path / "gen_host")]) == 0
 
 
-def test_fast_path_kernels_keep_four_wavefronts_per_simd_and_do_not_spill():
+def test_kernels_keep_their_register_budgets_and_do_not_spill():
     """Every instantiation of the fast-path kernel must fit 128 VGPRs (4 wavefronts per SIMD: 4096 envs x 50 chargers are then resident at
     once) without spilling to scratch -- the specialisations sit right at that limit, and a spill is silent at run time (only slower).
+    The streaming actor, the big-env kernel and the statistics kernel are held to their own budgets below.
     hipcc cross-compiles gfx950 here; the figures are the compiler's own (-Rpass-analysis=kernel-resource-usage)."""
     import subprocess
     from ev2gym_amd import build
@@ -175,10 +176,10 @@ def test_fast_path_kernels_keep_four_wavefronts_per_simd_and_do_not_spill():
         if act:          # (the policy's pointers and the running output pointers; the weight ring must stay in registers: no scratch, above)
             # (the fused PublicPST launch with the float32 policy -- scalar weight bases on top of PublicPST's three columns per port -- parks up to 51 scalars in lanes)
             assert block == 1024 and v["SGPRs Spill"] <= (56 if sk == 1 else 32), (k, v)
-    # the streaming actor (ev2g_mlp.h): ten instantiations (two shapes x {bf16 with eight wavefronts, float32 as two / three bf16 terms, bf16 with 32 rows per
+    # the streaming actor (ev2g_mlp.h): eight instantiations (two shapes x {bf16 with eight wavefronts, float32 as two / three bf16 terms, bf16 with 32 rows per
     # workgroup}); a register ring that the compiler could not keep in registers would land in scratch and cost the forward its weight stream
     actor = {k: v for k, v in res.items() if "ev2g_mlp3_s16" in k}
-    assert len(actor) == 10, sorted(actor)
+    assert len(actor) == 8, sorted(actor)
     for k, v in actor.items():
         assert v["VGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (k, v)
     # the statistics kernel keeps 40 entries of a session in registers: at most 256 VGPRs (two wavefronts per SIMD), no scratch -- one wavefront per SIMD
