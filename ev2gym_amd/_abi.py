@@ -40,6 +40,11 @@ COST_KINDS = {
     "transformer_overload_usrpenalty_cost": 1,         # rl_agent/cost.py:8-18
     "ProfitMax_TrPenalty_UserIncentives_safety": 2,    # rl_agent/cost.py:22-27
 }
+HEURISTIC_KINDS = {   # the env-reading heuristic agents run on the device (ev2g_heuristic_create)
+    "ChargeAsLateAsPossible": 0,                    # baselines/heuristics.py:98-149
+    "ChargeAsFastAsPossibleToDesiredCapacity": 1,   # baselines/heuristics.py:230-267
+    "RoundRobin": 2,                                # baselines/heuristics.py:7-96
+}
 AUTO_RESET_SAME = 1
 AUTO_RESET_NEXT = 2
 

@@ -1,7 +1,7 @@
 """Rule-based agents with the reference's `get_action(env)` surface (ev2gym/baselines/heuristics.py).
 
-ChargeAsFastAsPossible / RandomAgent / DoNothing work on the single-env facade (returning `np.ndarray[number_of_ports]` like the reference) and on
-`EV2GymVec` (returning a `[num_envs, number_of_ports]` array / device tensor).
+Every agent here works on the single-env facade (returning `np.ndarray[number_of_ports]` like the reference) and on `EV2GymVec` (returning
+a `[num_envs, number_of_ports]` array / device tensor; the env-reading agents' actions are computed on the device).
 """
 import math
 
@@ -52,6 +52,15 @@ class DoNothing:
 
 
 # ---- agents that READ the env (single-env facade `ev2gym_amd.env.EV2Gym`, or the reference's own env: the same object graph) ----
+# On `EV2GymVec` they do not walk an object graph: a device kernel computes their actions from the engine's state (ev2g_heuristic_actions)
+# into the vec env's action buffer, the same actions bit for bit.
+def _device_actions(agent, env, name):
+    dev = getattr(agent, "_dev", None)
+    if dev is None or dev[0] is not env:
+        dev = agent._dev = (env, env.heuristic_create(name))
+    return env.heuristic_actions(dev[1])
+
+
 def _ports(env):
     """(port number, charger, attached EV or None) in the reference's port order (charger by charger, port by port)."""
     n = 0
@@ -70,6 +79,8 @@ class RoundRobin:
 
     def __init__(self, env, verbose=False, **kwargs):
         self.verbose, self.env = verbose, env
+        if hasattr(env, "num_envs"):   # EV2GymVec: the queues live on the device
+            return
         total = 0
         for cs in env.charging_stations:
             total += cs.max_charge_current * cs.voltage * math.sqrt(cs.phases) / cs.n_ports
@@ -89,6 +100,8 @@ class RoundRobin:
                 self.ev_buffer.remove(n)
 
     def get_action(self, env):
+        if hasattr(env, "num_envs"):
+            return _device_actions(self, env, "RoundRobin")
         want = env.power_setpoints[env.current_step] * 1000 / self.average_power   # EVs' worth of power, in W / W
         self.update_ev_buffer(env)
         n = min(int(np.ceil(want)), len(self.ev_buffer))
@@ -110,6 +123,8 @@ class ChargeAsLateAsPossible:
         self.verbose = verbose
 
     def get_action(self, env):
+        if hasattr(env, "num_envs"):
+            return _device_actions(self, env, "ChargeAsLateAsPossible")
         act = np.zeros(env.number_of_ports)
         for n, cs, ev in _ports(env):
             if ev is None:
@@ -130,6 +145,8 @@ class ChargeAsFastAsPossibleToDesiredCapacity:
         self.verbose = verbose
 
     def get_action(self, env):
+        if hasattr(env, "num_envs"):
+            return _device_actions(self, env, "ChargeAsFastAsPossibleToDesiredCapacity")
         act = np.zeros(env.number_of_ports)
         for n, cs, ev in _ports(env):
             if ev is None:

@@ -23,10 +23,19 @@
 #include "ev2g_mlp.h"
 #include "ev2g_comm.h"
 #include "ev2g_refill.h"
+#include "ev2g_heuristic.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
 #include "ev2g_gen_host.h"
+
+// an env-reading heuristic agent on the device (ev2g_heuristic_create): its kind, the shape it was made for, RoundRobin's queues
+// and the action block ev2g_heuristic_run writes when the caller passes none
+struct ev2g_heuristic {
+    int kind = 0, E = 0, P = 0;
+    int *queue = nullptr, *qlen = nullptr;   // [E, P], [E]
+    double *act = nullptr;                   // [E, P]
+};
 
 #define EV2G_EV_RING 32
 struct ev2g_handle {
@@ -115,6 +124,12 @@ struct ev2g_handle {
     };
     std::vector<RolloutGraph> rollout_graphs;
     long long graph_launches = 0;
+    // the env-reading heuristic agents (ev2g_heuristic.h): port -> slot table and the charger constants in the reference's operation
+    // order (rebuilt by every load), and the agents created on this handle (freed with it)
+    int *d_port_slot = nullptr;
+    double *d_heur_cs_kw = nullptr;
+    double heur_avg_power = 0.0;
+    std::vector<ev2g_heuristic *> heuristics;
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -234,6 +249,11 @@ void ev2g_destroy(ev2g_handle *h) {
     if (h->peek_stage) (void)hipHostFree(h->peek_stage);
     free_pool(h->refill_cache.allocs);
     if (h->d_refill_overflow) (void)hipFree(h->d_refill_overflow);
+    for (ev2g_heuristic *a : h->heuristics) {
+        (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->act);
+        delete a;
+    }
+    h->heuristics.clear();
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
     for (int i = 0; i < EV2G_EV_RING; i++) { if (h->ev0s[i]) (void)hipEventDestroy(h->ev0s[i]); if (h->ev1s[i]) (void)hipEventDestroy(h->ev1s[i]); }
@@ -680,6 +700,19 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     UP(dp, cs_maxp) s.cs_maxp = dp;
     UP(dp, cs_minp) s.cs_minp = dp;
     UP(dp, cs_vk) s.cs_vk = dp;
+    {   // the heuristic agents' charger constants, evaluated like the reference: EV_Charger.get_max_power (ev_charger.py:251-252) and
+        // RoundRobin.average_power (heuristics.py:19-24) -- not cs_maxp, whose operation order rounds differently
+        std::vector<double> cs_kw(C);
+        double total = 0.0;
+        for (int c = 0; c < C; c++) {
+            const double I = b->cs_max_charge_current[c], V = b->cs_voltage[c], sq = std::sqrt((double)b->cs_phases[c]);
+            cs_kw[c] = I * V * sq / 1000;
+            total += I * V * sq / (double)np_of[c];
+        }
+        h->heur_avg_power = total / (double)C;
+        UP(dp, cs_kw) h->d_heur_cs_kw = dp;
+        UP(ip, port_slot) h->d_port_slot = ip;
+    }
     {   // the six per-charger operands of the fast path side by side: (imax, |dmax|), (imin, dmin), (max power, min power)
         std::vector<double> cs_pack((size_t)C * 6);
         for (int c = 0; c < C; c++) {
@@ -1622,6 +1655,112 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
             HIPCHK(h, hipMemcpyAsync(act_i, x.actions_f32, EP * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
             HIPCHK(h, hipMemcpyAsync(obs_n, x.obs_f32, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         }
+        h->current_step += 1;
+    }
+    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
+    h->timed = true;
+    return EV2G_OK;
+}
+
+// ---- env-reading heuristic agents (ev2g_heuristic.h) ----
+int ev2g_heuristic_create(ev2g_handle *h, int kind, ev2g_heuristic **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_create: null argument");
+    *out = nullptr;
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_heuristic_create: no scenarios loaded");
+    if (kind < EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE || kind > EV2G_HEURISTIC_ROUND_ROBIN)
+        return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_create: unknown heuristic kind");
+    (void)hipSetDevice(h->device);
+    ev2g_heuristic *a = new ev2g_heuristic();
+    a->kind = kind; a->E = h->E; a->P = h->P;
+    const size_t EP = (size_t)h->E * h->P;
+    bool ok = hipMalloc(&a->act, EP * sizeof(double)) == hipSuccess;
+    if (ok && kind == EV2G_HEURISTIC_ROUND_ROBIN) {
+        ok = hipMalloc(&a->queue, EP * sizeof(int)) == hipSuccess && hipMalloc(&a->qlen, (size_t)h->E * sizeof(int)) == hipSuccess &&
+             hipMemsetAsync(a->qlen, 0, (size_t)h->E * sizeof(int), h->stream) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->act);
+        delete a;
+        return fail(h, EV2G_ERR_HIP, "ev2g_heuristic_create: device allocation failed");
+    }
+    h->heuristics.push_back(a);
+    *out = a;
+    return EV2G_OK;
+}
+
+void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a) {
+    if (!h || !a) return;
+    auto it = std::find(h->heuristics.begin(), h->heuristics.end(), a);
+    if (it == h->heuristics.end()) return;
+    h->heuristics.erase(it);
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->act);
+    delete a;
+}
+
+static int heuristic_check(ev2g_handle *h, ev2g_heuristic *a, const char *who) {
+    if (!h || !a) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (std::find(h->heuristics.begin(), h->heuristics.end(), a) == h->heuristics.end())
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the heuristic was not created on this handle");
+    if (a->E != h->E || a->P != h->P)
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports differ from those the heuristic was created for");
+    return EV2G_OK;
+}
+
+// the agent's actions for the current step into actions [E, P] (device); RoundRobin's queue advances
+static int heuristic_launch(ev2g_handle *h, ev2g_heuristic *a, double *actions) {
+    const DevScn &s = h->scn;
+    const HeurArgs ha{h->d_port_slot, h->d_heur_cs_kw, h->heur_avg_power, a->queue, a->qlen, (int)h->scn_off};
+    const int t = h->current_step;
+    if (a->kind == EV2G_HEURISTIC_ROUND_ROBIN) {
+        // one wavefront per env, up to four per workgroup while their LDS stages fit 64 KiB
+        const size_t wb = ev2g_heur_rr_wave_bytes(s.P);
+        if (wb > 65536) return fail(h, EV2G_ERR_ARG, "ev2g_heuristic: RoundRobin supports up to 13000 ports per env");
+        const int epb = (int)std::min<size_t>(EV2G_HEUR_BLOCK / 64, 65536 / wb);
+        hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_RR>, dim3((s.E + epb - 1) / epb), dim3(64 * epb), epb * wb, h->stream, s, h->st, ha,
+                           t, actions);
+    } else {
+        const long long n = (long long)s.E * s.P;
+        const dim3 grid((unsigned)((n + EV2G_HEUR_BLOCK - 1) / EV2G_HEUR_BLOCK));
+        if (a->kind == EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE)
+            hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_CALP>, grid, dim3(EV2G_HEUR_BLOCK), 0, h->stream, s, h->st, ha, t, actions);
+        else
+            hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_CAFTDC>, grid, dim3(EV2G_HEUR_BLOCK), 0, h->stream, s, h->st, ha, t, actions);
+    }
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_heuristic_actions(ev2g_handle *h, ev2g_heuristic *a, double *actions) {
+    int rc = heuristic_check(h, a, "ev2g_heuristic_actions");
+    if (rc) return rc;
+    if (!actions) return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_actions: actions is null");
+    if (h->current_step >= h->T) return fail(h, EV2G_ERR_DONE, "ev2g_heuristic_actions: episode is done, reset the environment");
+    (void)hipSetDevice(h->device);
+    return heuristic_launch(h, a, actions);
+}
+
+int ev2g_heuristic_run(ev2g_handle *h, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
+                       double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride) {
+    int rc = heuristic_check(h, a, "ev2g_heuristic_run");
+    if (rc) return rc;
+    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0)
+        return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_run: negative step count or stride");
+    // the engine resets lazily inside the step launch after an episode end, so the agent's launch for the new episode's first step
+    // would read the finished episode's ports: segments stay inside one episode, the caller resets in between
+    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_heuristic_run: the segment would run past the episode end");
+    if (!actions) { actions = a->act; a_stride = 0; }
+    (void)hipSetDevice(h->device);
+    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
+    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    for (int i = 0; i < k_steps; i++) {
+        double *act_i = actions + (long long)i * a_stride;
+        if ((rc = heuristic_launch(h, a, act_i))) return rc;
+        const StepIO io = make_io(h, act_i, 0, obs ? obs + (long long)i * o_stride : nullptr, 0, reward ? reward + (long long)i * r_stride : nullptr, 0,
+                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
+        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
         h->current_step += 1;
     }
     HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;

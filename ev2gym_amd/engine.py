@@ -72,6 +72,10 @@ def load_library(path: Optional[str] = None):
         "ev2g_get_stats_reset_f32": (C.c_int, [vp, vp, vp, C.c_int64]),
         "ev2g_reset_f32": (C.c_int, [vp, vp, C.c_int64]),
         "ev2g_collect": (C.c_int, [vp, vp, C.c_int, vp]),
+        "ev2g_heuristic_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+        "ev2g_heuristic_destroy": (None, [vp, vp]),
+        "ev2g_heuristic_actions": (C.c_int, [vp, vp, vp]),
+        "ev2g_heuristic_run": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -124,7 +128,8 @@ EXPORTED_SYMBOLS = [
     "ev2g_memcpy_h2d", "ev2g_memcpy_d2h", "ev2g_host_malloc", "ev2g_host_free", "ev2g_synchronize", "ev2g_fill_uniform", "ev2g_host_uniform",
     "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_rollout",
     "ev2g_rollout_graph_launches", "ev2g_comm_get_unique_id", "ev2g_comm_init", "ev2g_comm_destroy", "ev2g_comm_world_size", "ev2g_comm_gathers", "ev2g_gather_stats",
-    "ev2g_pool_refill", "ev2g_pool_refill_overflows", "ev2g_pool_session_capacity", "ev2g_gen_default_config", "ev2g_generate", "ev2g_gen_batch", "ev2g_gen_free", "ev2g_gen_table"]
+    "ev2g_pool_refill", "ev2g_pool_refill_overflows", "ev2g_pool_session_capacity", "ev2g_gen_default_config", "ev2g_generate", "ev2g_gen_batch", "ev2g_gen_free", "ev2g_gen_table",
+    "ev2g_heuristic_create", "ev2g_heuristic_destroy", "ev2g_heuristic_actions", "ev2g_heuristic_run"]
 
 
 def _ptr(x):
@@ -368,6 +373,29 @@ class Engine:
 
     def fill_uniform(self, dst, n, seed, lo, hi):
         self._check(self._lib.ev2g_fill_uniform(self._h, _ptr(dst), int(n), int(seed), float(lo), float(hi)))
+
+    # ---- the env-reading heuristic agents on the device (include/ev2g.h: ev2g_heuristic_*) ----------------------------------------
+    def heuristic_create(self, name):
+        """A device-resident agent of the reference's heuristic `name` (a key of _abi.HEURISTIC_KINDS, or the kind number), bound to this
+        engine's envs and ports; freed by heuristic_destroy or with the engine."""
+        kind = _abi.HEURISTIC_KINDS[name] if isinstance(name, str) else int(name)
+        a = C.c_void_p()
+        self._check(self._lib.ev2g_heuristic_create(self._h, kind, C.byref(a)))
+        return a
+
+    def heuristic_destroy(self, a):
+        if self._h and a:
+            self._lib.ev2g_heuristic_destroy(self._h, a)
+
+    def heuristic_actions(self, a, out):
+        """The agent's float64 actions [E, P] for the current step into the device array `out` (DeviceBuffer or torch tensor); no step."""
+        self._check(self._lib.ev2g_heuristic_actions(self._h, a, _ptr(out)))
+
+    def heuristic_run(self, a, k, actions=None, a_stride=0, obs=None, o_stride=0, reward=None, r_stride=0, done=None, d_stride=0,
+                      mask=None, m_stride=0):
+        """k x (agent -> one step) inside one episode, outputs as in step_n; timed like step_n (last_step_n_kernel_ms)."""
+        self._check(self._lib.ev2g_heuristic_run(self._h, a, int(k), _ptr(actions), int(a_stride), _ptr(obs), int(o_stride), _ptr(reward),
+                                                 int(r_stride), _ptr(done), int(d_stride), _ptr(mask), int(m_stride)))
 
     # ---- statistics / inspection ---------------------------------------------------------------
     def stats(self, out=None) -> np.ndarray:

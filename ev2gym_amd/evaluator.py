@@ -9,7 +9,10 @@ Algorithms with a closed-form action source (the reference's rule-based agents t
   ChargeAsFastAsPossible (heuristics.py:152-166)  every port at 1
   DoNothing (heuristics.py:533-544)               every port at 0
   RandomAgent (heuristics.py:546-558)             uniform samples of the action box, counter-based generator (seed, index)
-Agents that read the env (round robin, charge-as-late-as-possible, MPC, RL policies) go through `EV2GymVec` / the facade step by step.
+and the rule-based agents that READ the env (`DEVICE_HEURISTICS`, not in the default list): a device kernel computes their actions
+from the engine's state before every step (ev2g_heuristic_run: agent launch + one-step launch, T times, one C call per algorithm)
+  ChargeAsLateAsPossible (heuristics.py:98-149), ChargeAsFastAsPossibleToDesiredCapacity (:230-267), RoundRobin (:7-96).
+Other agents that read the env (MPC, RL policies) go through `EV2GymVec` / the facade step by step.
 """
 from __future__ import annotations
 
@@ -22,6 +25,8 @@ from . import _abi
 from .scenario import ScenarioBatch
 
 ALGORITHMS = ("ChargeAsFastAsPossible", "DoNothing", "RandomAgent")
+# env-reading agents an engine with `heuristic_run` evaluates on the device (named explicitly: the default list stays the three above)
+DEVICE_HEURISTICS = tuple(_abi.HEURISTIC_KINDS)
 # the statistics columns of the reference's results table (evaluator.py:262-283), in its order
 RESULT_STATS = ["total_ev_served", "total_profits", "total_energy_charged", "total_energy_discharged", "average_user_satisfaction",
                 "power_tracker_violation", "tracking_error", "energy_tracking_error", "energy_user_satisfaction", "total_transformer_overload",
@@ -46,19 +51,28 @@ def evaluate(scenarios: ScenarioBatch, algorithms: Iterable[str] = ALGORITHMS, s
     lo = -1.0 if scenarios.v2g_enabled else 0.0
     rows = []
     for name in algorithms:
-        if name not in ALGORITHMS:
-            raise NotImplementedError(f"evaluate(): '{name}' reads the env; closed-form action sources are {ALGORITHMS}")
+        if name not in ALGORITHMS and name not in DEVICE_HEURISTICS:
+            raise NotImplementedError(f"evaluate(): '{name}' reads the env; closed-form action sources are {ALGORITHMS}, "
+                                      f"device-evaluated heuristics {DEVICE_HEURISTICS}")
         eng = engine_factory(scenarios, rk, sk)
         try:
-            if name == "RandomAgent":
-                acts, stride = eng.empty((T, E, P)), E * P
-                eng.fill_uniform(acts, T * E * P, seed, lo, 1.0)
+            if name in DEVICE_HEURISTICS:
+                if not hasattr(eng, "heuristic_run"):
+                    raise NotImplementedError(f"evaluate(): '{name}' reads the env and this engine cannot run it on the device")
+                agent = eng.heuristic_create(name)
+                eng.reset()
+                t0 = time.perf_counter()
+                eng.heuristic_run(agent, T)   # T x (agent launch -> one-step launch), one C call
             else:
-                acts, stride = eng.empty((E, P)), 0      # one [E,P] block reused every step
-                acts.upload(np.full((E, P), 1.0 if name == "ChargeAsFastAsPossible" else 0.0))
-            eng.reset()
-            t0 = time.perf_counter()
-            eng.step_n(T, acts, stride, auto_reset=0, persistent=True)
+                if name == "RandomAgent":
+                    acts, stride = eng.empty((T, E, P)), E * P
+                    eng.fill_uniform(acts, T * E * P, seed, lo, 1.0)
+                else:
+                    acts, stride = eng.empty((E, P)), 0      # one [E,P] block reused every step
+                    acts.upload(np.full((E, P), 1.0 if name == "ChargeAsFastAsPossible" else 0.0))
+                eng.reset()
+                t0 = time.perf_counter()
+                eng.step_n(T, acts, stride, auto_reset=0, persistent=True)
             st = eng.stats()
             wall = time.perf_counter() - t0
             eng.check_faults()

@@ -217,6 +217,15 @@ class EV2GymVec:
         self.engine.fill_uniform(self._act, self.num_envs * self.number_of_ports, seed, low, high)
         return self._act
 
+    def heuristic_create(self, name: str):
+        """A device-resident agent of the reference's env-reading heuristic `name` (_abi.HEURISTIC_KINDS) for these envs."""
+        return self.engine.heuristic_create(name)
+
+    def heuristic_actions(self, agent):
+        """That agent's actions for the current step, computed on the device into the env's action buffer (returned)."""
+        self.engine.heuristic_actions(agent, self._act)
+        return self._act
+
     # ---- gym surface -------------------------------------------------------------------------------
     @property
     def current_step(self) -> int:

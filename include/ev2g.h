@@ -405,6 +405,29 @@ typedef struct {
 } ev2g_transitions;
 int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_transitions *tr);
 
+/* ---- the reference's env-reading heuristic agents ON THE DEVICE (baselines/heuristics.py) ----------------------------------------------
+ * The agent reads the engine's state before each step -- which ports hold an EV, its capacity, departure, desired capacity, the step's power
+ * setpoint -- and writes float64 actions [E,P] in the reference's port order, bit for bit what the reference's agent chooses on that env
+ * (same operation order).  RoundRobin keeps its queue of ports per env on the device; it is emptied at step 0 of every episode, like the
+ * fresh agent the reference's evaluator builds for every run (evaluator.py:237). */
+#define EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE 0         /* heuristics.py:98-149  */
+#define EV2G_HEURISTIC_CHARGE_AS_FAST_TO_DESIRED_CAPACITY 1 /* heuristics.py:230-267 */
+#define EV2G_HEURISTIC_ROUND_ROBIN 2                        /* heuristics.py:7-96    */
+typedef struct ev2g_heuristic ev2g_heuristic;
+/* needs loaded scenarios; the agent is bound to the handle's env and port counts (a reload that changes them makes its calls fail) and is
+ * freed with the handle if not before */
+int ev2g_heuristic_create(ev2g_handle *h, int kind, ev2g_heuristic **out);
+void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a);
+/* the agent's actions for the current step into actions [E,P] (DEVICE); no step is taken.  RoundRobin's queue advances as in get_action(). */
+int ev2g_heuristic_actions(ev2g_handle *h, ev2g_heuristic *a, double *actions);
+/* k_steps x (agent -> one step) inside ONE episode, enqueued without host round trips: the agent's launch, then a one-step launch of the step
+ * kernel the handle selected.  actions [k,E,P] written at base + k*a_stride (NULL: a buffer of the agent, stride 0); obs / reward / done /
+ * mask as in ev2g_step_n (DEVICE, each may be NULL).  A segment that would run past the episode end returns EV2G_ERR_DONE: reset in between
+ * (with auto-reset the engine re-arms an env inside the next step launch, after the agent would have read it).  Timed like ev2g_step_n
+ * (ev2g_last_step_n_kernel_ms). */
+int ev2g_heuristic_run(ev2g_handle *h, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
+                       double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride);
+
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
 void ev2g_free(ev2g_handle *h, void *p);
