@@ -198,11 +198,12 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
             if ((te) + 1 < T) b_hist[((te) + 1) * (2 + R) + 1] = potn_;                                                                       \
             const double reward_ = costs_ - q_over_ - q_sat_;   /* ProfitMax_TrPenalty_UserIncentives (reward.py:34-44) */                    \
             const double a0_ = eacc[0] + reward_, a1_ = eacc[1] + costs_;                                                                     \
-            io.reward[e] = reward_;                                                                                                           \
-            io.done[e] = ((te) + 1 >= T) ? 1 : 0;                                                                                             \
-            obs_e[0] = (double)((te) + 1);                                                                                                    \
-            obs_e[1] = usage_;                                                                                                                \
-            if (last_) {  /* flush the accumulators (get_statistics reads them): a launch of this kernel ends inside the episode */            \
+            if (last_) {  /* the outputs (step stride 0: only the launch's last step's can ever be seen), then the accumulators' flush       \
+                             (get_statistics reads them): a launch of this kernel ends inside the episode */                                  \
+                io.reward[e] = reward_;                                                                                                       \
+                io.done[e] = ((te) + 1 >= T) ? 1 : 0;                                                                                         \
+                obs_e[0] = (double)((te) + 1);                                                                                                \
+                obs_e[1] = usage_;                                                                                                            \
                 double *ga_ = (double *)S->env_acc + e * 8;                                                                                   \
                 ga_[0] += a0_; ga_[1] += a1_; ga_[2] += q_ech_; ga_[3] += q_edis_; ga_[4] += q_emerg_;                                        \
                 eacc[0] = 0.0; eacc[1] = 0.0;                                                                                                 \
@@ -287,8 +288,11 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
 #pragma unroll
             for (int u = 0; u < 2; u++) a_next[u] = __builtin_nontemporal_load(an + (pk[u] & 0xffff));
         }
-        d2_t hp[2];
+        // (the outputs have step stride 0 -- a row written before the launch's last step is overwritten unseen -- so only the last step requests the
+        // observation head: a UNIFORM branch, the other path leaves the registers at zero)
+        d2_t hp[2] = {{0.0, 0.0}, {0.0, 0.0}};
         typedef double d2a8_t __attribute__((ext_vector_type(2), aligned(8)));
+        if (last_step)
 #pragma unroll
         for (int u = 0; u < 2; u++) {   // ONE unconditional 16-byte load per slot from a selected, always valid address (a load in a branch that merges with a
                                         // default costs a vmcnt(0) drain, ev2g_step_v2.h); a price lane reads the pair that holds its column (clamped inside the row)
@@ -416,6 +420,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
         asm volatile("" : "+v"(a_next[0]), "+v"(a_next[1]), "+v"(hp[0]), "+v"(hp[1]));
         asm volatile("" : "+v"(pf_ra), "+v"(pf_rb), "+v"(pf_rc), "+v"(pf_lut), "+v"(pf_pk));
         // the observation head: |charge price| window and the transformers' load / PV / limit windows, copied from the scenario's tables
+        if (last_step)
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             if (hp_dst[u] >= 0) *(d2_t *)(obs_e + hp_dst[u]) = hp[u];
@@ -432,7 +437,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
         // action mask, its two observation columns, its charge-power-potential term.  `cwq`: the port's word (charger class, potential-term index)
 #define EV2G_BIG_PORT_OUT(q_, pk_, occ_after_, cap_, bcap_, td_, cwq_)                                                                        \
         {                                                                                                                                    \
-            mask_e[(pk_) & 0xffff] = (occ_after_) ? 1 : 0;                                                                                   \
+            if (last_step) mask_e[(pk_) & 0xffff] = (occ_after_) ? 1 : 0;   /* (stride-0 outputs: the launch's last step's only) */          \
             d2_t ov_ = {0.0, 0.0};                                                                                                           \
             double pot_ = 0.0;                                                                                                               \
             if (occ_after_) {                                                                                                                \
@@ -450,7 +455,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_big(const V2P *__restrict_
                 const double mx_ = ct_[4], mn_ = ct_[5];                                                                                     \
                 pot_ = (pot_ > mx_) ? mx_ : ((pot_ < mn_) ? 0.0 : pot_);                                                                     \
             }                                                                                                                                \
-            *(d2_t *)(obs_e + ((unsigned)(pk_) >> 16)) = ov_;                                                                                \
+            if (last_step) *(d2_t *)(obs_e + ((unsigned)(pk_) >> 16)) = ov_;                                                                 \
             v_pot += pot_;                                                                                                                   \
         }
         {

@@ -139,8 +139,9 @@ struct WaveArgs {
 // V2P::reward_kind (ev2g_reward / ev2g_departure_term in ev2g_device.h).
 // FULL (with IO32: the same for the policy network's hand-over -- float32 actions in, the float32 observation out INSTEAD of the float64
 // one; what ev2g_rollout launches between two actor forwards):
-// the launch writes all four float64 outputs (observation, reward, done, mask) with step stride 0 (each step overwrites the last:
-// what a loop that consumes them step by step, or a benchmark, passes), takes float64 actions, uses no extras (fused cost, float32
+// the launch writes all four float64 outputs (observation, reward, done, mask) with step stride 0 (one buffer that holds the launch's
+// last step: what a loop that consumes them step by step, or a benchmark, passes -- only the LAST step of a longer launch writes them,
+// LSO below: the earlier rows could never be seen), takes float64 actions, uses no extras (fused cost, float32
 // observations, charger histories) and contains no in-launch reset.  The null checks, the extras' parameter fetches, the outputs'
 // per-step pointer arithmetic and the reset branch -- dozens of scalar instructions a step, issued by every wavefront -- are compiled
 // out: measured 4.53 -> 4.28 us/step at cfg2, 5.40 -> 5.08 at cfg3 (the kernel's time is its instruction count, SURVEY par.8d / DESIGN par.3).
@@ -169,6 +170,9 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
     constexpr bool FULL = FULLK >= 1, WIDE = FULLK >= 2, STR = FULLK >= 3 || ACT;
     constexpr bool STR_NT = FULLK >= 3;   // the kept observation rows (0.6 GB per cfg2 launch) as streaming stores: they should not displace the state lines in L2 (-2 %, profiles/r05_ab_strided_nt.txt)
     constexpr bool F64 = FULL && !IO32, F32 = FULL && IO32;   // full with float64 actions in / observations out, or with the float32 hand-over
+    // LSO: the full instantiations whose outputs have step stride 0 write them in the launch's LAST step only -- every earlier row would be overwritten
+    // before anyone could read it (include/ev2g.h: the buffer holds the launch's last step; its contents while the launch runs are unspecified)
+    constexpr bool LSO = FULL && !STR;
     constexpr bool INL = FULLK == 2 && !IO32 && !ACT && BLOCK == EV2G_WAVE_BLOCK;   // the in-launch statistics phase is compiled in (end of the kernel)
 #if defined(EV2G_PHASE_TIMING) && defined(EV2G_PT_OUTER)
     const unsigned long long pt_k0 = __builtin_readcyclecounter();   // slot 7 := prologue, slot 6 := epilogue (tools/phase_timing.py --outer)
@@ -411,6 +415,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         uint8_t *mask = FULL ? mask_run : (io.mask ? io.mask + (long long)kk * io.m_stride : nullptr);
         const int sstep = t + 1;
         const bool last_step = (kk == k_steps - 1) || (!FULL && sstep >= T && !auto_reset);
+        const bool out = !LSO || last_step;   // (uniform) this step's observation / reward / done / mask rows are written
         int *cntk = cnt + 2 * (kk & 1);
         // next step's counters, cleared BEFORE this step's first barrier: they were last read in the battery-maths phase of the step
         // before, which a busy step closes with a barrier and a quiet step leaves at zero
@@ -463,7 +468,10 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         d2v pf_h0 = {0.0, 0.0}, pf_h1 = {0.0, 0.0};
         constexpr int NHEAD = (SK == 1) ? 0 : (SK == 0 ? 60 : 20);   // 20 prices (+ 40 window columns)
         constexpr int NPAIR = NHEAD / 2;
-        if (SK == 1) {
+        // (LSO: a step that writes no observation requests none of this -- a UNIFORM branch around the loads, whose registers the other path leaves
+        // at their zeros: no divergent merge, and phase C's collection point pins both paths alike)
+        if (!out) {
+        } else if (SK == 1) {
             pf_ob0 = ldg32_nt<double>(S->step_tab, eT64 + (unsigned)min(sstep, T - 1) * 64u + 40u);   // next setpoint; head lane only, masked by sstep < T
         } else {
             // observation head table [E, T+1, NHEAD]: |charge price| window (zero-padded) + load/PV/limit window, exactly
@@ -610,7 +618,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         asm volatile("" : "+v"(a_next), "+v"(pf_pch), "+v"(pf_pdis), "+v"(pf_tr), "+v"(pf_ob0), "+v"(pf_h0), "+v"(pf_h1));
         asm volatile("" : "+v"(pf_c2), "+v"(pf_c7), "+v"(pf_tl), "+v"(pf_d0), "+v"(pf_d1));
         bool occ_any = false;   // an EV on this port before or after the step
-        if (FULL && valid && !wave_live) {   // the empty wavefront's outputs: zeros
+        if (FULL && valid && !wave_live && out) {   // the empty wavefront's outputs: zeros
             stg32<uint8_t>(mask, (unsigned)g_l, (uint8_t)0);
             const unsigned ocol_l = (unsigned)((SK == 1) ? 3 + 3 * q_l : (SK == 0 ? 62 + 2 * q_l : 22 + 2 * q_l));
             if (F64) {
@@ -710,7 +718,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                                               ldg32<double>(S->rec, r8 + (unsigned)offsetof(SessRec, pacmax)), sixty_over_dt, td, sstep);
             }
             occ_any = occ || occ_after;
-            if (FULL || mask) stg32<uint8_t>(mask, (unsigned)g_l, occ_after ? 1 : 0);
+            if (FULL ? out : mask != nullptr) stg32<uint8_t>(mask, (unsigned)g_l, occ_after ? 1 : 0);
             double o0 = 0.0, o1 = 0.0, o2 = 0.0;
             if (occ_after) {
                 const double soc = FULL ? ev2g_fdiv2(cap, b_bcap, r_rb) : cap / b_bcap;   // bit-identical (ev2g_device.h)
@@ -721,7 +729,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
             pot = (pot > c_maxp) ? c_maxp : ((pot < c_minp) ? 0.0 : pot);   // per-charger clamp (utils.py:779-789)
             // (the narrow full kernels sit at the register limit: they re-derive the port's column from the env's base)
             const unsigned ocol_l = (unsigned)((SK == 1) ? 3 + 3 * q_l : (SK == 0 ? 62 + 2 * q_l : 22 + 2 * q_l));
-            if (F64 || (!FULL && obs)) {
+            if ((F64 && out) || (!FULL && obs)) {
                 const unsigned o8 = WIDE ? hb_obs_port : (FULL ? hb_obs_env + ocol_l * 8u : (unsigned)(e_l * D + ocol) * 8u);
                 if (STR_NT) { stg32_nt<d2v>(obs, o8, (d2v){o0, o1}); if (SK == 1) stg32_nt<double>(obs, o8 + 16u, o2); }
                 else {
@@ -729,7 +737,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                 if (SK == 1) stg32<double>(obs, o8 + 16u, o2);
                 }
             }
-            if (F32 || (!FULL && obs32)) {
+            if ((F32 && out) || (!FULL && obs32)) {
                 const unsigned o4 = WIDE ? hb_obs_port : (FULL ? hb_obs_env + ocol_l * 4u : (unsigned)(e_l * D + ocol) * 4u);
                 if (SK == 1) { stg32<float>(obs32, o4, (float)o0); stg32<float>(obs32, o4 + 4u, (float)o1); stg32<float>(obs32, o4 + 8u, (float)o2); }
                 else stg32<f2v>(obs32, o4, (f2v){(float)o0, (float)o1});
@@ -929,7 +937,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
             const double n0 = ea0 + reward, n1 = ea1 + costs, n2 = ea2 + esum[4], n3 = ea3 + esum[5], n4 = ea4 + esum[6];
             ea[0] = n0; ea[1] = n1; ea[2] = n2; ea[3] = n3; ea[4] = n4; ea[5] = potn;
             if (RK == 3) ea[6] = ea5;
-            if (FULL) { stg32<double>(rew_run, e8, reward); stg32<uint8_t>(done_run, (unsigned)e_l, (sstep >= T) ? 1 : 0); }
+            if (FULL && out) { stg32<double>(rew_run, e8, reward); stg32<uint8_t>(done_run, (unsigned)e_l, (sstep >= T) ? 1 : 0); }
             if (!FULL && io.reward) stg32<double>(io.reward + (long long)kk * io.r_stride, e8, reward);
             if (!FULL && io.done) stg32<uint8_t>(io.done + (long long)kk * io.d_stride, (unsigned)e_l, (sstep >= T) ? 1 : 0);
             if (!FULL && S->x_cost)   // cost_function (rl_agent/cost.py:8-27); the overload weight is applied here when the reward does not carry it
@@ -941,7 +949,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                 stg32<double>(env_acc, a8 + 32u, n4);
             }
         }
-        if ((valid || hcopy) && (F32 || (!FULL && obs32))) {
+        if ((valid || hcopy) && ((F32 && out) || (!FULL && obs32))) {
             const unsigned o4 = FULL ? hb_obs_env : (unsigned)(e_l * D) * 4u;
             if (SK == 1) {
                 if (q_l == 0) {
@@ -973,7 +981,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                 }
             }
         }
-        if (valid && (F64 || (!FULL && obs))) {
+        if (valid && ((F64 && out) || (!FULL && obs))) {
             const unsigned o8 = FULL ? hb_obs_env : (unsigned)(e_l * D) * 8u;
             if (SK == 1) {  // PublicPST state.py:6-35
                 if (q_l == 0) {

@@ -208,7 +208,10 @@ int ev2g_step(ev2g_handle *h, const double *actions, double *obs, double *reward
 
 /* K consecutive steps from a device-resident action source, enqueued without host round trips.
  * actions: [K,E,P] (action_step_stride = E*P) or one [E,P] block reused (stride 0).
- * Output k is written at base + k*<stride> elements (stride 0 = overwrite one buffer).
+ * Output k is written at base + k*<stride> elements.  Stride 0 = one buffer: after the call it holds the outputs of the
+ * call's LAST step, every element of it written; what it holds while the steps run is unspecified (a persistent launch of
+ * the specialised kernels -- ev2g_last_launch_specialisation 1, 2, 5 -- writes it in its last step only, the other paths
+ * overwrite it step by step).  Pass step strides to keep the rows of every step.
  *   mode 0  one kernel launch per step, enqueued back to back from C;
  *   mode 1  ONE persistent launch: every workgroup loops over the K steps of its own envs (envs are
  *           independent, so no grid-wide synchronisation is needed).
