@@ -45,6 +45,12 @@ HEURISTIC_KINDS = {   # the env-reading heuristic agents run on the device (ev2g
     "ChargeAsFastAsPossibleToDesiredCapacity": 1,   # baselines/heuristics.py:230-267
     "RoundRobin": 2,                                # baselines/heuristics.py:7-96
 }
+AGENT_KINDS = {   # every agent ev2g_heuristic_create knows: the three above and the header's EV2G_AGENT_* kinds, same number space
+    **HEURISTIC_KINDS,
+    "ChargeAsLateAsPossibleToDesiredCapacity": 3,   # baselines/heuristics.py:561-622
+    "RoundRobin_GF": 4,                             # baselines/heuristics.py:270-399  (one port per charger)
+    "RoundRobin_GF_off_allowed": 5,                 # baselines/heuristics.py:402-530  (one port per charger)
+}
 AUTO_RESET_SAME = 1
 AUTO_RESET_NEXT = 2
 

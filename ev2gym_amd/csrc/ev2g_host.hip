@@ -29,13 +29,20 @@
 static thread_local std::string g_create_error;
 #include "ev2g_gen_host.h"
 
-// an env-reading heuristic agent on the device (ev2g_heuristic_create): its kind, the shape it was made for, RoundRobin's queues
-// and the action block ev2g_heuristic_run writes when the caller passes none
+// an env-reading heuristic agent on the device (ev2g_heuristic_create): its kind, the shape it was made for, the RoundRobin agents' queues
+// (RoundRobin_GF*: with every entry's min_power / max_power) and the action block ev2g_heuristic_run writes when the caller passes none
 struct ev2g_heuristic {
     int kind = 0, E = 0, P = 0;
     int *queue = nullptr, *qlen = nullptr;   // [E, P], [E]
+    double *qmin = nullptr, *qmax = nullptr; // [E, P] each
     double *act = nullptr;                   // [E, P]
 };
+
+// releases an agent's device memory and the agent (wherever one ends: ev2g_heuristic_destroy, ev2g_destroy, a failed create)
+static void heuristic_free(ev2g_heuristic *a) {
+    (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->qmin); (void)hipFree(a->qmax); (void)hipFree(a->act);
+    delete a;
+}
 
 #define EV2G_EV_RING 32
 struct ev2g_handle {
@@ -127,8 +134,8 @@ struct ev2g_handle {
     // the env-reading heuristic agents (ev2g_heuristic.h): port -> slot table and the charger constants in the reference's operation
     // order (rebuilt by every load), and the agents created on this handle (freed with it)
     int *d_port_slot = nullptr;
-    double *d_heur_cs_kw = nullptr;
-    double heur_avg_power = 0.0;
+    double *d_heur_cs_kw = nullptr, *d_heur_cs_min_kw = nullptr;
+    double heur_avg_power = 0.0, heur_min_action = 0.0;
     std::vector<ev2g_heuristic *> heuristics;
 };
 
@@ -249,10 +256,7 @@ void ev2g_destroy(ev2g_handle *h) {
     if (h->peek_stage) (void)hipHostFree(h->peek_stage);
     free_pool(h->refill_cache.allocs);
     if (h->d_refill_overflow) (void)hipFree(h->d_refill_overflow);
-    for (ev2g_heuristic *a : h->heuristics) {
-        (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->act);
-        delete a;
-    }
+    for (ev2g_heuristic *a : h->heuristics) heuristic_free(a);
     h->heuristics.clear();
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
@@ -700,17 +704,21 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     UP(dp, cs_maxp) s.cs_maxp = dp;
     UP(dp, cs_minp) s.cs_minp = dp;
     UP(dp, cs_vk) s.cs_vk = dp;
-    {   // the heuristic agents' charger constants, evaluated like the reference: EV_Charger.get_max_power (ev_charger.py:251-252) and
-        // RoundRobin.average_power (heuristics.py:19-24) -- not cs_maxp, whose operation order rounds differently
-        std::vector<double> cs_kw(C);
+    {   // the heuristic agents' charger constants, evaluated like the reference: EV_Charger.get_max_power / get_min_charge_power
+        // (ev_charger.py:251-255), RoundRobin.average_power (heuristics.py:19-24) and RoundRobin_GF.min_action (heuristics.py:285-286:
+        // the loop leaves the LAST charger's) -- not cs_maxp / cs_minp, whose operation order rounds differently
+        std::vector<double> cs_kw(C), cs_min_kw(C);
         double total = 0.0;
         for (int c = 0; c < C; c++) {
             const double I = b->cs_max_charge_current[c], V = b->cs_voltage[c], sq = std::sqrt((double)b->cs_phases[c]);
             cs_kw[c] = I * V * sq / 1000;
+            cs_min_kw[c] = b->cs_min_charge_current[c] * V * sq / 1000;
             total += I * V * sq / (double)np_of[c];
         }
         h->heur_avg_power = total / (double)C;
+        h->heur_min_action = b->cs_min_charge_current[C - 1] / b->cs_max_charge_current[C - 1] + 1e-4;
         UP(dp, cs_kw) h->d_heur_cs_kw = dp;
+        UP(dp, cs_min_kw) h->d_heur_cs_min_kw = dp;
         UP(ip, port_slot) h->d_port_slot = ip;
     }
     {   // the six per-charger operands of the fast path side by side: (imax, |dmax|), (imin, dmin), (max power, min power)
@@ -1663,24 +1671,43 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
 }
 
 // ---- env-reading heuristic agents (ev2g_heuristic.h) ----
+// what an agent kind needs of the loaded scenarios beyond their envs and ports; asked at create and again before every launch, because
+// ev2g_load_scenarios may replace the scenarios under a live agent (same E and P, other chargers)
+static int heuristic_shape_check(ev2g_handle *h, int kind, const std::string &who) {
+    const bool gf = kind == EV2G_AGENT_ROUND_ROBIN_GF || kind == EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED;
+    // the reference indexes its per-charger max_cs_power with a port id (heuristics.py:392): it is defined for one-port chargers only
+    // (and the kernel reads the charger table with that port id)
+    if (gf && h->P != h->C)
+        return fail(h, EV2G_ERR_ARG, who + ": RoundRobin_GF / RoundRobin_GF_off_allowed need one port per charger "
+                                           "(the reference indexes its per-charger power table with a port id)");
+    // one env's queue stage has to fit the 64 KiB of LDS
+    if (gf && ev2g_heur_gf_wave_bytes(h->P) > 65536)
+        return fail(h, EV2G_ERR_ARG, who + ": RoundRobin_GF / RoundRobin_GF_off_allowed support up to 3100 ports per env");
+    if (kind == EV2G_HEURISTIC_ROUND_ROBIN && ev2g_heur_rr_wave_bytes(h->P) > 65536)
+        return fail(h, EV2G_ERR_ARG, who + ": RoundRobin supports up to 13000 ports per env");
+    return EV2G_OK;
+}
+
 int ev2g_heuristic_create(ev2g_handle *h, int kind, ev2g_heuristic **out) {
     if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_create: null argument");
     *out = nullptr;
     if (!h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_heuristic_create: no scenarios loaded");
-    if (kind < EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE || kind > EV2G_HEURISTIC_ROUND_ROBIN)
+    if (kind < EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE || kind > EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED)
         return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_create: unknown heuristic kind");
+    const bool gf = kind == EV2G_AGENT_ROUND_ROBIN_GF || kind == EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED;
+    if (int rc = heuristic_shape_check(h, kind, "ev2g_heuristic_create")) return rc;
     (void)hipSetDevice(h->device);
     ev2g_heuristic *a = new ev2g_heuristic();
     a->kind = kind; a->E = h->E; a->P = h->P;
     const size_t EP = (size_t)h->E * h->P;
     bool ok = hipMalloc(&a->act, EP * sizeof(double)) == hipSuccess;
-    if (ok && kind == EV2G_HEURISTIC_ROUND_ROBIN) {
+    if (ok && (kind == EV2G_HEURISTIC_ROUND_ROBIN || gf)) {
         ok = hipMalloc(&a->queue, EP * sizeof(int)) == hipSuccess && hipMalloc(&a->qlen, (size_t)h->E * sizeof(int)) == hipSuccess &&
              hipMemsetAsync(a->qlen, 0, (size_t)h->E * sizeof(int), h->stream) == hipSuccess;
     }
+    if (ok && gf) ok = hipMalloc(&a->qmin, EP * sizeof(double)) == hipSuccess && hipMalloc(&a->qmax, EP * sizeof(double)) == hipSuccess;
     if (!ok) {
-        (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->act);
-        delete a;
+        heuristic_free(a);
         return fail(h, EV2G_ERR_HIP, "ev2g_heuristic_create: device allocation failed");
     }
     h->heuristics.push_back(a);
@@ -1695,8 +1722,7 @@ void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a) {
     h->heuristics.erase(it);
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->act);
-    delete a;
+    heuristic_free(a);
 }
 
 static int heuristic_check(ev2g_handle *h, ev2g_heuristic *a, const char *who) {
@@ -1706,18 +1732,27 @@ static int heuristic_check(ev2g_handle *h, ev2g_heuristic *a, const char *who) {
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the heuristic was not created on this handle");
     if (a->E != h->E || a->P != h->P)
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports differ from those the heuristic was created for");
-    return EV2G_OK;
+    return heuristic_shape_check(h, a->kind, who);
 }
 
-// the agent's actions for the current step into actions [E, P] (device); RoundRobin's queue advances
+// the agent's actions for the current step into actions [E, P] (device); the RoundRobin agents' queues advance
 static int heuristic_launch(ev2g_handle *h, ev2g_heuristic *a, double *actions) {
     const DevScn &s = h->scn;
-    const HeurArgs ha{h->d_port_slot, h->d_heur_cs_kw, h->heur_avg_power, a->queue, a->qlen, (int)h->scn_off};
+    const HeurArgs ha{h->d_port_slot, h->d_heur_cs_kw, h->heur_avg_power, a->queue, a->qlen, (int)h->scn_off,
+                      h->d_heur_cs_min_kw, h->heur_min_action, a->qmin, a->qmax};
     const int t = h->current_step;
-    if (a->kind == EV2G_HEURISTIC_ROUND_ROBIN) {
+    if (a->kind == EV2G_AGENT_ROUND_ROBIN_GF || a->kind == EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED) {
+        // as RoundRobin below, with the two power lists in the stage
+        const size_t wb = ev2g_heur_gf_wave_bytes(s.P);   // (<= 64 KiB: heuristic_shape_check)
+        const int epb = (int)std::min<size_t>(EV2G_HEUR_BLOCK / 64, 65536 / wb);
+        const dim3 grid((s.E + epb - 1) / epb), block(64 * epb);
+        if (a->kind == EV2G_AGENT_ROUND_ROBIN_GF)
+            hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_RRGF>, grid, block, epb * wb, h->stream, s, h->st, ha, t, actions);
+        else
+            hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_RRGF_OFF>, grid, block, epb * wb, h->stream, s, h->st, ha, t, actions);
+    } else if (a->kind == EV2G_HEURISTIC_ROUND_ROBIN) {
         // one wavefront per env, up to four per workgroup while their LDS stages fit 64 KiB
-        const size_t wb = ev2g_heur_rr_wave_bytes(s.P);
-        if (wb > 65536) return fail(h, EV2G_ERR_ARG, "ev2g_heuristic: RoundRobin supports up to 13000 ports per env");
+        const size_t wb = ev2g_heur_rr_wave_bytes(s.P);   // (<= 64 KiB: heuristic_shape_check)
         const int epb = (int)std::min<size_t>(EV2G_HEUR_BLOCK / 64, 65536 / wb);
         hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_RR>, dim3((s.E + epb - 1) / epb), dim3(64 * epb), epb * wb, h->stream, s, h->st, ha,
                            t, actions);
@@ -1726,6 +1761,8 @@ static int heuristic_launch(ev2g_handle *h, ev2g_heuristic *a, double *actions) 
         const dim3 grid((unsigned)((n + EV2G_HEUR_BLOCK - 1) / EV2G_HEUR_BLOCK));
         if (a->kind == EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE)
             hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_CALP>, grid, dim3(EV2G_HEUR_BLOCK), 0, h->stream, s, h->st, ha, t, actions);
+        else if (a->kind == EV2G_AGENT_CHARGE_AS_LATE_TO_DESIRED_CAPACITY)
+            hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_CALPDC>, grid, dim3(EV2G_HEUR_BLOCK), 0, h->stream, s, h->st, ha, t, actions);
         else
             hipLaunchKernelGGL(ev2g_heuristic_kernel<EV2G_HEUR_CAFTDC>, grid, dim3(EV2G_HEUR_BLOCK), 0, h->stream, s, h->st, ha, t, actions);
     }

@@ -376,9 +376,9 @@ class Engine:
 
     # ---- the env-reading heuristic agents on the device (include/ev2g.h: ev2g_heuristic_*) ----------------------------------------
     def heuristic_create(self, name):
-        """A device-resident agent of the reference's heuristic `name` (a key of _abi.HEURISTIC_KINDS, or the kind number), bound to this
-        engine's envs and ports; freed by heuristic_destroy or with the engine."""
-        kind = _abi.HEURISTIC_KINDS[name] if isinstance(name, str) else int(name)
+        """A device-resident agent of the reference's heuristic `name` (a key of _abi.AGENT_KINDS, or the kind number), bound to this
+        engine's envs and ports; freed by heuristic_destroy or with the engine.  The two RoundRobin_GF agents need one port per charger."""
+        kind = _abi.AGENT_KINDS[name] if isinstance(name, str) else int(name)
         a = C.c_void_p()
         self._check(self._lib.ev2g_heuristic_create(self._h, kind, C.byref(a)))
         return a

@@ -9,9 +9,11 @@ Algorithms with a closed-form action source (the reference's rule-based agents t
   ChargeAsFastAsPossible (heuristics.py:152-166)  every port at 1
   DoNothing (heuristics.py:533-544)               every port at 0
   RandomAgent (heuristics.py:546-558)             uniform samples of the action box, counter-based generator (seed, index)
-and the rule-based agents that READ the env (`DEVICE_HEURISTICS`, not in the default list): a device kernel computes their actions
+and the rule-based agents that READ the env (`DEVICE_AGENTS`, not in the default list): a device kernel computes their actions
 from the engine's state before every step (ev2g_heuristic_run: agent launch + one-step launch, T times, one C call per algorithm)
-  ChargeAsLateAsPossible (heuristics.py:98-149), ChargeAsFastAsPossibleToDesiredCapacity (:230-267), RoundRobin (:7-96).
+  ChargeAsLateAsPossible (heuristics.py:98-149), ChargeAsFastAsPossibleToDesiredCapacity (:230-267), RoundRobin (:7-96)
+  (these three are `DEVICE_HEURISTICS`), ChargeAsLateAsPossibleToDesiredCapacity (:561-622), and the two setpoint trackers of the PublicPST
+  problem, RoundRobin_GF (:270-399) and RoundRobin_GF_off_allowed (:402-530), which need one port per charger.
 Other agents that read the env (MPC, RL policies) go through `EV2GymVec` / the facade step by step.
 """
 from __future__ import annotations
@@ -27,6 +29,7 @@ from .scenario import ScenarioBatch
 ALGORITHMS = ("ChargeAsFastAsPossible", "DoNothing", "RandomAgent")
 # env-reading agents an engine with `heuristic_run` evaluates on the device (named explicitly: the default list stays the three above)
 DEVICE_HEURISTICS = tuple(_abi.HEURISTIC_KINDS)
+DEVICE_AGENTS = tuple(_abi.AGENT_KINDS)   # those three and the three kinds added after them
 # the statistics columns of the reference's results table (evaluator.py:262-283), in its order
 RESULT_STATS = ["total_ev_served", "total_profits", "total_energy_charged", "total_energy_discharged", "average_user_satisfaction",
                 "power_tracker_violation", "tracking_error", "energy_tracking_error", "energy_user_satisfaction", "total_transformer_overload",
@@ -51,12 +54,12 @@ def evaluate(scenarios: ScenarioBatch, algorithms: Iterable[str] = ALGORITHMS, s
     lo = -1.0 if scenarios.v2g_enabled else 0.0
     rows = []
     for name in algorithms:
-        if name not in ALGORITHMS and name not in DEVICE_HEURISTICS:
-            raise NotImplementedError(f"evaluate(): '{name}' reads the env; closed-form action sources are {ALGORITHMS}, "
-                                      f"device-evaluated heuristics {DEVICE_HEURISTICS}")
+        if name not in ALGORITHMS and name not in DEVICE_AGENTS:
+            raise NotImplementedError(f"evaluate(): '{name}' is not evaluated on the device; closed-form action sources are {ALGORITHMS}, "
+                                      f"device-evaluated env-reading agents {DEVICE_AGENTS}")
         eng = engine_factory(scenarios, rk, sk)
         try:
-            if name in DEVICE_HEURISTICS:
+            if name in DEVICE_AGENTS:
                 if not hasattr(eng, "heuristic_run"):
                     raise NotImplementedError(f"evaluate(): '{name}' reads the env and this engine cannot run it on the device")
                 agent = eng.heuristic_create(name)

@@ -218,7 +218,7 @@ class EV2GymVec:
         return self._act
 
     def heuristic_create(self, name: str):
-        """A device-resident agent of the reference's env-reading heuristic `name` (_abi.HEURISTIC_KINDS) for these envs."""
+        """A device-resident agent of the reference's env-reading heuristic `name` (_abi.AGENT_KINDS) for these envs."""
         return self.engine.heuristic_create(name)
 
     def heuristic_actions(self, agent):

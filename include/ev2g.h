@@ -411,17 +411,30 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
 /* ---- the reference's env-reading heuristic agents ON THE DEVICE (baselines/heuristics.py) ----------------------------------------------
  * The agent reads the engine's state before each step -- which ports hold an EV, its capacity, departure, desired capacity, the step's power
  * setpoint -- and writes float64 actions [E,P] in the reference's port order, bit for bit what the reference's agent chooses on that env
- * (same operation order).  RoundRobin keeps its queue of ports per env on the device; it is emptied at step 0 of every episode, like the
+ * (same operation order).  The RoundRobin agents keep their queue of ports per env on the device; it is emptied at step 0 of every episode, like the
  * fresh agent the reference's evaluator builds for every run (evaluator.py:237). */
 #define EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE 0         /* heuristics.py:98-149  */
 #define EV2G_HEURISTIC_CHARGE_AS_FAST_TO_DESIRED_CAPACITY 1 /* heuristics.py:230-267 */
 #define EV2G_HEURISTIC_ROUND_ROBIN 2                        /* heuristics.py:7-96    */
+/* Three more kinds in the SAME number space (ev2g_heuristic_create's `kind`).  They carry another prefix because the EV2G_HEURISTIC_* list
+ * is a frozen set that existing callers and checks enumerate; the union of both lists is what _abi.AGENT_KINDS mirrors.
+ *  - the two RoundRobin_GF agents keep, next to their queue of ports, the min_power / max_power every queue entry was INSERTED with, as the
+ *    reference does: a port whose next EV arrives the step after the last one left stays queued with the old EV's powers;
+ *  - they exist for one-port chargers only: the reference indexes its per-charger power table with a port id and divides by zero otherwise, so
+ *    ev2g_heuristic_create returns EV2G_ERR_ARG for them when any charger of the loaded scenarios has more than one port, and so do
+ *    ev2g_heuristic_actions / _run for a live agent after a reload brought such chargers;
+ *  - their selection is a sequential float64 sum in queue order: a plain left-to-right sum from 0, which is what the reference's sum()
+ *    computes under CPython before 3.12 (from 3.12 on sum() compensates float sums and the reference itself gives other bits);
+ *  - at most 3100 ports per env (RoundRobin: 13000), refused at create. */
+#define EV2G_AGENT_CHARGE_AS_LATE_TO_DESIRED_CAPACITY 3     /* heuristics.py:561-622 */
+#define EV2G_AGENT_ROUND_ROBIN_GF 4                         /* heuristics.py:270-399 */
+#define EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED 5             /* heuristics.py:402-530 */
 typedef struct ev2g_heuristic ev2g_heuristic;
 /* needs loaded scenarios; the agent is bound to the handle's env and port counts (a reload that changes them makes its calls fail) and is
  * freed with the handle if not before */
 int ev2g_heuristic_create(ev2g_handle *h, int kind, ev2g_heuristic **out);
 void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a);
-/* the agent's actions for the current step into actions [E,P] (DEVICE); no step is taken.  RoundRobin's queue advances as in get_action(). */
+/* the agent's actions for the current step into actions [E,P] (DEVICE); no step is taken.  A RoundRobin agent's queue advances as in get_action(). */
 int ev2g_heuristic_actions(ev2g_handle *h, ev2g_heuristic *a, double *actions);
 /* k_steps x (agent -> one step) inside ONE episode, enqueued without host round trips: the agent's launch, then a one-step launch of the step
  * kernel the handle selected.  actions [k,E,P] written at base + k*a_stride (NULL: a buffer of the agent, stride 0); obs / reward / done /

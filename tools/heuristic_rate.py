@@ -8,7 +8,8 @@ launch of the step kernel, T times per episode), one JSON line per (workload, ag
       the agent kernel's share of each (agent + step) pair, from the dispatches of every kernel_trace.csv under OUT
 
 The workloads are bench.py's shapes; cfg2 and cfg4 are drawn with power setpoints (their configs have none, and RoundRobin charges
-ceil(setpoint / average charger power) EVs per step: without setpoints it never charges and its queue never rotates).
+ceil(setpoint / average charger power) EVs per step: without setpoints it never charges and its queue never rotates; the same holds
+for the two RoundRobin_GF agents).
 """
 import argparse
 import csv
@@ -34,7 +35,7 @@ WORKLOADS = {
     "cfg3": (8192, lambda E, s: GenConfig.public_pst(E, 20, seed=s), PST),
     "cfg4": (2048, lambda E, s: GenConfig.v2g_profit_plus_loads(E, 1000, 50, seed=s, power_setpoint_enabled=True), DEFAULT),
 }
-AGENTS = {k: n for n, k in _abi.HEURISTIC_KINDS.items()}
+AGENTS = {k: n for n, k in _abi.AGENT_KINDS.items()}
 
 
 def rates(workload, episodes):
@@ -59,7 +60,7 @@ def rates(workload, episodes):
         return statistics.median(ms), ms
 
     step_ms, _ = timed(lambda: eng.step_n(T, acts, 0, obs, 0, rew, 0, done, 0, mask, 0, auto_reset=0, persistent=False))
-    for name in _abi.HEURISTIC_KINDS:
+    for name in _abi.AGENT_KINDS:   # (every workload here has one-port chargers: the RoundRobin_GF agents run on all three)
         a = eng.heuristic_create(name)
         med, ms = timed(lambda: eng.heuristic_run(a, T, None, 0, obs, 0, rew, 0, done, 0, mask, 0))
         print(json.dumps(dict(workload=workload, agent=name, envs=E, ports=P, steps=T, step_kernel=eng.kernel_name,
