@@ -24,6 +24,7 @@
 #include "ev2g_comm.h"
 #include "ev2g_refill.h"
 #include "ev2g_heuristic.h"
+#include "ev2g_link.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -42,6 +43,27 @@ struct ev2g_heuristic {
 static void heuristic_free(ev2g_heuristic *a) {
     (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->qmin); (void)hipFree(a->qmax); (void)hipFree(a->act);
     delete a;
+}
+
+// a communication-fault link (ev2g_link_create, ev2g_link.h): the two probabilities, the uniforms of each half (a [T, E, P] device matrix, or
+// the seed of the generated ones), the shape it was made for, the held commands (FailedActionCommunication.previous_actions_list) and the two
+// remembered energy columns (DelayedObservation.previous_obs_list / actual_previous_obs_list, column 4 + 3 i), and the blocks ev2g_link_run /
+// ev2g_link_rollout work on when the caller passes none (allocated on first use)
+struct ev2g_link {
+    int E = 0, P = 0, T = 0;
+    double p_fail = 0.0, p_delay = 0.0;
+    unsigned long long seed_act = 0, seed_obs = 0;
+    double *rand_act = nullptr, *rand_obs = nullptr;   // [T, E, P] each, or nullptr
+    double *held = nullptr, *prev = nullptr, *actual = nullptr;   // [E, P] each
+    double *raw = nullptr, *obs = nullptr;             // [E, P] the agent's raw actions, [E, D] the observation row
+    float *obs32 = nullptr, *act32 = nullptr;          // [E, D], [E, P]: the policy's input and output rows
+};
+
+static void link_free(ev2g_link *l) {
+    for (void *p : {(void *)l->rand_act, (void *)l->rand_obs, (void *)l->held, (void *)l->prev, (void *)l->actual, (void *)l->raw, (void *)l->obs,
+                    (void *)l->obs32, (void *)l->act32})
+        (void)hipFree(p);
+    delete l;
 }
 
 #define EV2G_EV_RING 32
@@ -137,6 +159,7 @@ struct ev2g_handle {
     double *d_heur_cs_kw = nullptr, *d_heur_cs_min_kw = nullptr;
     double heur_avg_power = 0.0, heur_min_action = 0.0;
     std::vector<ev2g_heuristic *> heuristics;
+    std::vector<ev2g_link *> links;             // the communication-fault links created on this handle (freed with it)
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -258,6 +281,8 @@ void ev2g_destroy(ev2g_handle *h) {
     if (h->d_refill_overflow) (void)hipFree(h->d_refill_overflow);
     for (ev2g_heuristic *a : h->heuristics) heuristic_free(a);
     h->heuristics.clear();
+    for (ev2g_link *l : h->links) link_free(l);
+    h->links.clear();
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
     for (int i = 0; i < EV2G_EV_RING; i++) { if (h->ev0s[i]) (void)hipEventDestroy(h->ev0s[i]); if (h->ev1s[i]) (void)hipEventDestroy(h->ev1s[i]); }
@@ -1799,6 +1824,190 @@ int ev2g_heuristic_run(ev2g_handle *h, ev2g_heuristic *a, int k_steps, double *a
                                   done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
         if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
         h->current_step += 1;
+    }
+    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
+    h->timed = true;
+    return EV2G_OK;
+}
+
+// ---- communication-fault links (ev2g_link.h) ----
+// a host matrix in the reference's layout [E, P, T] as a device matrix [T, E, P]
+static int link_upload(ev2g_handle *h, const double *src, int E, int P, int T, double **dst) {
+    std::vector<double> tr((size_t)E * P * T);
+    for (int e = 0; e < E; e++)
+        for (int p = 0; p < P; p++)
+            for (int t = 0; t < T; t++) tr[((size_t)t * E + e) * P + p] = src[((size_t)e * P + p) * T + t];
+    HIPCHK(h, hipMalloc((void **)dst, tr.size() * sizeof(double)));
+    HIPCHK(h, hipMemcpy(*dst, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
+    return EV2G_OK;
+}
+
+int ev2g_link_reset_state(ev2g_handle *h, ev2g_link *l);
+
+int ev2g_link_create(ev2g_handle *h, double p_fail, double p_delay, uint64_t seed_act, uint64_t seed_obs, const double *rand_act,
+                     const double *rand_obs, ev2g_link **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_link_create: null argument");
+    *out = nullptr;
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_link_create: no scenarios loaded");
+    if (!(p_fail >= 0.0 && p_fail <= 1.0) || !(p_delay >= 0.0 && p_delay <= 1.0))
+        return fail(h, EV2G_ERR_ARG, "ev2g_link_create: p_fail and p_delay must be between 0 and 1 (noise_wrappers.py:24,76)");
+    if (p_delay > 0.0 && (h->cfg.state_kind != EV2G_STATE_PUBLIC_PST || h->D != 3 + 3 * h->P))
+        return fail(h, EV2G_ERR_ARG, "ev2g_link_create: delayed observations need the PublicPST state function (noise_wrappers.py:79-80)");
+    (void)hipSetDevice(h->device);
+    ev2g_link *l = new ev2g_link();
+    l->E = h->E; l->P = h->P; l->T = h->T;
+    l->p_fail = p_fail; l->p_delay = p_delay; l->seed_act = seed_act; l->seed_obs = seed_obs;
+    const size_t EP = (size_t)h->E * h->P * sizeof(double);
+    int rc = EV2G_OK;
+    if (hipMalloc((void **)&l->held, EP) != hipSuccess || hipMalloc((void **)&l->prev, EP) != hipSuccess || hipMalloc((void **)&l->actual, EP) != hipSuccess)
+        rc = fail(h, EV2G_ERR_HIP, "ev2g_link_create: device allocation failed");
+    if (!rc && rand_act && p_fail > 0.0) rc = link_upload(h, rand_act, l->E, l->P, l->T, &l->rand_act);
+    if (!rc && rand_obs && p_delay > 0.0) rc = link_upload(h, rand_obs, l->E, l->P, l->T, &l->rand_obs);
+    if (!rc) { h->links.push_back(l); rc = ev2g_link_reset_state(h, l); if (rc) h->links.pop_back(); }
+    if (rc) { link_free(l); return rc; }
+    *out = l;
+    return EV2G_OK;
+}
+
+void ev2g_link_destroy(ev2g_handle *h, ev2g_link *l) {
+    if (!h || !l) return;
+    auto it = std::find(h->links.begin(), h->links.end(), l);
+    if (it == h->links.end()) return;
+    h->links.erase(it);
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    link_free(l);
+}
+
+static int link_check(ev2g_handle *h, ev2g_link *l, const char *who) {
+    if (!h || !l) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (std::find(h->links.begin(), h->links.end(), l) == h->links.end())
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the link was not created on this handle");
+    if (l->E != h->E || l->P != h->P || l->T != h->T)
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports / steps differ from those the link was created for");
+    (void)hipSetDevice(h->device);
+    return EV2G_OK;
+}
+
+int ev2g_link_reset_state(ev2g_handle *h, ev2g_link *l) {
+    if (int rc = link_check(h, l, "ev2g_link_reset_state")) return rc;
+    const size_t EP = (size_t)l->E * l->P * sizeof(double);
+    HIPCHK(h, hipMemsetAsync(l->held, 0, EP, h->stream));
+    HIPCHK(h, hipMemsetAsync(l->prev, 0, EP, h->stream));
+    HIPCHK(h, hipMemsetAsync(l->actual, 0, EP, h->stream));
+    return EV2G_OK;
+}
+
+// one of the link's own blocks, allocated on first use
+static int link_buffer(ev2g_handle *h, void **p, size_t bytes) {
+    if (!*p) HIPCHK(h, hipMalloc(p, std::max<size_t>(bytes, 1)));
+    return EV2G_OK;
+}
+
+// the fail kernel for step t: in [E, P] (float64, or float32 with in32) -> the link's held block, and `out` when given
+static int link_launch_act(ev2g_handle *h, ev2g_link *l, int t, const void *in, bool in32, double *out) {
+    const LinkRand r{l->rand_act, l->seed_act, l->E, l->P, l->T};
+    const long long n = (long long)l->E * l->P;
+    const dim3 grid((unsigned)std::min<long long>((n + EV2G_LINK_BLOCK - 1) / EV2G_LINK_BLOCK, 1 << 20));
+    if (in32) hipLaunchKernelGGL(ev2g_link_act_kernel<true>, grid, dim3(EV2G_LINK_BLOCK), 0, h->stream, in, r, l->p_fail, t, l->held, out);
+    else hipLaunchKernelGGL(ev2g_link_act_kernel<false>, grid, dim3(EV2G_LINK_BLOCK), 0, h->stream, in, r, l->p_fail, t, l->held, out);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+// the delay kernel on the observation of env step t (0 = the reset observation ... T = the terminal one)
+static int link_launch_obs(ev2g_handle *h, ev2g_link *l, int t, double *obs, float *obs32) {
+    const LinkRand r{l->rand_obs, l->seed_obs, l->E, l->P, l->T};
+    const int epb = EV2G_LINK_BLOCK / 64;
+    hipLaunchKernelGGL(ev2g_link_obs_kernel, dim3((l->E + epb - 1) / epb), dim3(EV2G_LINK_BLOCK), 0, h->stream, obs, obs32, r, l->p_delay, h->D, t,
+                       (double)h->scn.dt, l->prev, l->actual);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_link_actions(ev2g_handle *h, ev2g_link *l, int t, const void *in, int in_is_f32, double *out) {
+    if (int rc = link_check(h, l, "ev2g_link_actions")) return rc;
+    if (!in) return fail(h, EV2G_ERR_ARG, "ev2g_link_actions: the action block is null");
+    if (t < 0) t = h->current_step;
+    if (t >= l->T) return fail(h, EV2G_ERR_DONE, "ev2g_link_actions: step " + std::to_string(t) + " is past the episode's last step");
+    return link_launch_act(h, l, t, in, in_is_f32 != 0, out);
+}
+
+int ev2g_link_observe(ev2g_handle *h, ev2g_link *l, int t, double *obs, float *obs32) {
+    if (int rc = link_check(h, l, "ev2g_link_observe")) return rc;
+    if (!obs) return fail(h, EV2G_ERR_ARG, "ev2g_link_observe: the observation block is null");
+    if (h->cfg.state_kind != EV2G_STATE_PUBLIC_PST || h->D != 3 + 3 * l->P)
+        return fail(h, EV2G_ERR_ARG, "ev2g_link_observe: delayed observations need the PublicPST state function (noise_wrappers.py:79-80)");
+    if (t < 0) t = h->current_step;
+    if (t > l->T) return fail(h, EV2G_ERR_ARG, "ev2g_link_observe: step " + std::to_string(t) + " is past the terminal observation");
+    return link_launch_obs(h, l, t, obs, obs32);
+}
+
+float *ev2g_link_obs_f32(ev2g_handle *h, ev2g_link *l) {
+    if (link_check(h, l, "ev2g_link_obs_f32")) return nullptr;
+    if (link_buffer(h, (void **)&l->obs32, (size_t)l->E * h->D * sizeof(float))) return nullptr;
+    return l->obs32;
+}
+
+int ev2g_link_run(ev2g_handle *h, ev2g_link *l, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
+                  double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride) {
+    int rc = link_check(h, l, "ev2g_link_run");
+    if (rc) return rc;
+    if (a && (rc = heuristic_check(h, a, "ev2g_link_run"))) return rc;
+    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0)
+        return fail(h, EV2G_ERR_ARG, "ev2g_link_run: negative step count or stride");
+    if (!a && !actions) return fail(h, EV2G_ERR_ARG, "ev2g_link_run: without an agent the raw actions are read from `actions`");
+    // (as ev2g_heuristic_run: the agent's launch for a new episode's first step would read the finished episode's ports)
+    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_link_run: the segment would run past the episode end");
+    const bool f_on = l->p_fail > 0.0, d_on = l->p_delay > 0.0;
+    if (a && !actions) { if ((rc = link_buffer(h, (void **)&l->raw, (size_t)l->E * l->P * sizeof(double)))) return rc; actions = l->raw; a_stride = 0; }
+    if (d_on && !obs) { if ((rc = link_buffer(h, (void **)&l->obs, (size_t)l->E * h->D * sizeof(double)))) return rc; obs = l->obs; o_stride = 0; }
+    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
+    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    for (int i = 0; i < k_steps; i++) {
+        double *raw_i = actions + (long long)i * a_stride, *obs_i = obs ? obs + (long long)i * o_stride : nullptr;
+        if (a && (rc = heuristic_launch(h, a, raw_i))) return rc;
+        if (f_on && (rc = link_launch_act(h, l, h->current_step, raw_i, false, nullptr))) return rc;
+        const StepIO io = make_io(h, f_on ? l->held : raw_i, 0, obs_i, 0, reward ? reward + (long long)i * r_stride : nullptr, 0,
+                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
+        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
+        h->current_step += 1;
+        if (d_on && (rc = link_launch_obs(h, l, h->current_step, obs_i, nullptr))) return rc;
+    }
+    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
+    h->timed = true;
+    return EV2G_OK;
+}
+
+int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
+                      int64_t d_stride, uint8_t *mask, int64_t m_stride) {
+    int rc = link_check(h, l, "ev2g_link_rollout");
+    if (rc) return rc;
+    if (!m || k_steps < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0) return fail(h, EV2G_ERR_ARG, "ev2g_link_rollout: bad arguments");
+    if (m->dev.d_in != h->D || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_link_rollout: actor shape != (obs dim, ports)");
+    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_link_rollout: the segment would run past the episode end");
+    const size_t ED = (size_t)l->E * h->D, EP = (size_t)l->E * l->P;
+    if ((rc = link_buffer(h, (void **)&l->obs, ED * sizeof(double))) || (rc = link_buffer(h, (void **)&l->obs32, ED * sizeof(float))) ||
+        (rc = link_buffer(h, (void **)&l->act32, EP * sizeof(float)))) return rc;
+    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
+    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    for (int i = 0; i < k_steps; i++) {
+        if ((rc = ev2g_mlp_forward(h, m, l->obs32, l->act32, l->E))) return rc;
+        // (the fail kernel also widens the policy's float32 row into the float64 block the step reads: it runs for p_fail = 0 too, where it
+        // holds nothing and draws no uniform)
+        if ((rc = link_launch_act(h, l, h->current_step, l->act32, true, nullptr))) return rc;
+        const StepIO io = make_io(h, l->held, 0, l->obs, 0, reward ? reward + (long long)i * r_stride : nullptr, 0,
+                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
+        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
+        h->current_step += 1;
+        if (l->p_delay > 0.0) {
+            if ((rc = link_launch_obs(h, l, h->current_step, l->obs, l->obs32))) return rc;
+        } else {
+            const dim3 grid((unsigned)std::min<size_t>((ED + EV2G_LINK_BLOCK - 1) / EV2G_LINK_BLOCK, 1 << 20));
+            hipLaunchKernelGGL(ev2g_link_f32_kernel, grid, dim3(EV2G_LINK_BLOCK), 0, h->stream, (const double *)l->obs, l->obs32, (long long)ED);
+            HIPCHK(h, hipGetLastError());
+        }
     }
     HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
     h->timed = true;

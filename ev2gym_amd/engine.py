@@ -76,6 +76,14 @@ def load_library(path: Optional[str] = None):
         "ev2g_heuristic_destroy": (None, [vp, vp]),
         "ev2g_heuristic_actions": (C.c_int, [vp, vp, vp]),
         "ev2g_heuristic_run": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]),
+        "ev2g_link_create": (C.c_int, [vp, dbl, dbl, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(vp)]),
+        "ev2g_link_destroy": (None, [vp, vp]),
+        "ev2g_link_reset_state": (C.c_int, [vp, vp]),
+        "ev2g_link_actions": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp]),
+        "ev2g_link_observe": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+        "ev2g_link_obs_f32": (vp, [vp, vp]),
+        "ev2g_link_run": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]),
+        "ev2g_link_rollout": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -129,7 +137,9 @@ EXPORTED_SYMBOLS = [
     "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_rollout",
     "ev2g_rollout_graph_launches", "ev2g_comm_get_unique_id", "ev2g_comm_init", "ev2g_comm_destroy", "ev2g_comm_world_size", "ev2g_comm_gathers", "ev2g_gather_stats",
     "ev2g_pool_refill", "ev2g_pool_refill_overflows", "ev2g_pool_session_capacity", "ev2g_gen_default_config", "ev2g_generate", "ev2g_gen_batch", "ev2g_gen_free", "ev2g_gen_table",
-    "ev2g_heuristic_create", "ev2g_heuristic_destroy", "ev2g_heuristic_actions", "ev2g_heuristic_run"]
+    "ev2g_heuristic_create", "ev2g_heuristic_destroy", "ev2g_heuristic_actions", "ev2g_heuristic_run",
+    "ev2g_link_create", "ev2g_link_destroy", "ev2g_link_reset_state", "ev2g_link_actions", "ev2g_link_observe", "ev2g_link_obs_f32",
+    "ev2g_link_run", "ev2g_link_rollout"]
 
 
 def _ptr(x):
@@ -396,6 +406,59 @@ class Engine:
         """k x (agent -> one step) inside one episode, outputs as in step_n; timed like step_n (last_step_n_kernel_ms)."""
         self._check(self._lib.ev2g_heuristic_run(self._h, a, int(k), _ptr(actions), int(a_stride), _ptr(obs), int(o_stride), _ptr(reward),
                                                  int(r_stride), _ptr(done), int(d_stride), _ptr(mask), int(m_stride)))
+
+    # ---- the reference's communication-fault models on the device (include/ev2g.h: ev2g_link_*) -----------------------------------
+    def link_create(self, p_fail=0.0, p_delay=0.0, seed_act=0, seed_obs=0, rand_act=None, rand_obs=None):
+        """A link of FailedActionCommunication (p_fail) and DelayedObservation (p_delay; PublicPST only) for this engine's envs
+        (rl_agent/noise_wrappers.py), freed by link_destroy or with the engine.  rand_act / rand_obs: host matrices [E, P, T] (env e's [P, T]
+        block is the reference wrapper's `random`), or None: generated from the seed, the bits of host_uniform(E * P * T, seed, 0, 1)."""
+        keep = []
+        for r in (rand_act, rand_obs):
+            if r is not None:
+                r = np.ascontiguousarray(r, np.float64)
+                if r.shape != (self.E, self.P, self.T):
+                    raise ValueError(f"link_create: a uniform matrix has shape {r.shape}, expected {(self.E, self.P, self.T)}")
+            keep.append(r)
+        l = C.c_void_p()
+        self._check(self._lib.ev2g_link_create(self._h, float(p_fail), float(p_delay), int(seed_act) & (2 ** 64 - 1), int(seed_obs) & (2 ** 64 - 1),
+                                               *[None if r is None else r.ctypes.data for r in keep], C.byref(l)))
+        return l
+
+    def link_destroy(self, l):
+        if self._h and l:
+            self._lib.ev2g_link_destroy(self._h, l)
+
+    def link_reset_state(self, l):
+        """Zero the held commands and the remembered observation columns (a freshly constructed pair of wrappers)."""
+        self._check(self._lib.ev2g_link_reset_state(self._h, l))
+
+    def link_actions(self, l, actions, out=None, t=-1, f32=False):
+        """The delivered commands of step t (default: the current step) for the raw device actions [E, P] (float64, or float32 with f32=True)
+        into the link and into the float64 device array `out`; no step."""
+        self._check(self._lib.ev2g_link_actions(self._h, l, int(t), _ptr(actions), int(bool(f32)), _ptr(out)))
+
+    def link_observe(self, l, obs, obs32=None, t=-1):
+        """Rewrite the device observation [E, D] of step t (default: the current step; 0 = the reset observation) as DelayedObservation delivers
+        it; obs32 receives the float32 copy."""
+        self._check(self._lib.ev2g_link_observe(self._h, l, int(t), _ptr(obs), _ptr(obs32)))
+
+    def link_obs_f32(self, l) -> int:
+        """Device address of the link's float32 delivered row [E, D], the policy input of link_rollout."""
+        p = self._lib.ev2g_link_obs_f32(self._h, l)
+        if not p:
+            raise EngineError(-1, self.last_error())
+        return int(p)
+
+    def link_run(self, l, k, agent=None, actions=None, a_stride=0, obs=None, o_stride=0, reward=None, r_stride=0, done=None, d_stride=0,
+                 mask=None, m_stride=0):
+        """k x ([agent ->] held commands -> one step -> delayed observation) inside one episode; outputs as in step_n, timed like it."""
+        self._check(self._lib.ev2g_link_run(self._h, l, agent, int(k), _ptr(actions), int(a_stride), _ptr(obs), int(o_stride), _ptr(reward),
+                                            int(r_stride), _ptr(done), int(d_stride), _ptr(mask), int(m_stride)))
+
+    def link_rollout(self, l, m, k, reward=None, r_stride=0, done=None, d_stride=0, mask=None, m_stride=0):
+        """k x (actor on the link's float32 delivered row -> held commands -> one step -> delayed observation), unfused, inside one episode."""
+        self._check(self._lib.ev2g_link_rollout(self._h, l, m, int(k), _ptr(reward), int(r_stride), _ptr(done), int(d_stride), _ptr(mask),
+                                                int(m_stride)))
 
     # ---- statistics / inspection ---------------------------------------------------------------
     def stats(self, out=None) -> np.ndarray:

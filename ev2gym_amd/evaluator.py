@@ -15,6 +15,11 @@ from the engine's state before every step (ev2g_heuristic_run: agent launch + on
   (these three are `DEVICE_HEURISTICS`), ChargeAsLateAsPossibleToDesiredCapacity (:561-622), and the two setpoint trackers of the PublicPST
   problem, RoundRobin_GF (:270-399) and RoundRobin_GF_off_allowed (:402-530), which need one port per charger.
 Other agents that read the env (MPC, RL policies) go through `EV2GymVec` / the facade step by step.
+
+`p_fail > 0` evaluates every algorithm under the reference's FailedActionCommunication model (rl_agent/noise_wrappers.py:12-60): a charger
+that misses a command keeps executing the one it was sent last.  Every algorithm, the closed-form sources included, then runs through
+`ev2g_link_run` (fail kernel + one-step launch, T times, one C call) with a fresh link per algorithm, its uniforms generated on the device
+from `fail_seed`.
 """
 from __future__ import annotations
 
@@ -43,11 +48,13 @@ def _default_engine(batch, rk, sk):
 
 def evaluate(scenarios: ScenarioBatch, algorithms: Iterable[str] = ALGORITHMS, state_function="V2G_profit_max_loads",
              reward_function="ProfitMax_TrPenalty_UserIncentives", seed: int = 0, discharge_price_factor: Optional[float] = None,
-             engine_factory=_default_engine):
+             engine_factory=_default_engine, p_fail: float = 0.0, fail_seed: int = 0):
     """Runs every scenario of `scenarios` (e.g. `load_replay` files concatenated, or a generated batch) under every algorithm and
     returns a pandas DataFrame with the reference's columns: run, Algorithm, control_horizon, discharge_price_factor, the thirteen
     statistics of its table, total_reward, time (seconds of GPU kernel time for the algorithm's whole batch, shared by its rows)."""
     import pandas as pd
+    if not 0.0 <= p_fail <= 1.0:
+        raise ValueError(f"evaluate(): p_fail = {p_fail} is not a probability")
     sk = _abi.STATE_KINDS[state_function if isinstance(state_function, str) else state_function.__name__]
     rk = _abi.REWARD_KINDS[reward_function if isinstance(reward_function, str) else reward_function.__name__]
     E, T, P = scenarios.n_envs, scenarios.n_steps, scenarios.n_ports
@@ -59,7 +66,23 @@ def evaluate(scenarios: ScenarioBatch, algorithms: Iterable[str] = ALGORITHMS, s
                                       f"device-evaluated env-reading agents {DEVICE_AGENTS}")
         eng = engine_factory(scenarios, rk, sk)
         try:
-            if name in DEVICE_AGENTS:
+            if p_fail > 0:
+                if not hasattr(eng, "link_run") or (name in DEVICE_AGENTS and not hasattr(eng, "heuristic_create")):
+                    raise NotImplementedError(f"evaluate(): p_fail needs an engine with link_run ('{name}' cannot be run under it on this one)")
+                link = eng.link_create(p_fail=p_fail, seed_act=fail_seed)   # a fresh pair of wrappers per run (evaluator.py:237 style)
+                agent, acts, stride = None, None, 0
+                if name in DEVICE_AGENTS:
+                    agent = eng.heuristic_create(name)
+                elif name == "RandomAgent":
+                    acts, stride = eng.empty((T, E, P)), E * P
+                    eng.fill_uniform(acts, T * E * P, seed, lo, 1.0)
+                else:
+                    acts = eng.empty((E, P))
+                    acts.upload(np.full((E, P), 1.0 if name == "ChargeAsFastAsPossible" else 0.0))
+                eng.reset()
+                t0 = time.perf_counter()
+                eng.link_run(link, T, agent, acts, stride)   # T x ([agent ->] fail kernel -> one-step launch), one C call
+            elif name in DEVICE_AGENTS:
                 if not hasattr(eng, "heuristic_run"):
                     raise NotImplementedError(f"evaluate(): '{name}' reads the env and this engine cannot run it on the device")
                 agent = eng.heuristic_create(name)

@@ -444,6 +444,59 @@ int ev2g_heuristic_actions(ev2g_handle *h, ev2g_heuristic *a, double *actions);
 int ev2g_heuristic_run(ev2g_handle *h, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
                        double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride);
 
+/* ---- the reference's communication-fault models ON THE DEVICE (rl_agent/noise_wrappers.py) ------------------------------------------------
+ * A link holds both of the reference's robustness wrappers for the E envs of a handle:
+ *   FailedActionCommunication (noise_wrappers.py:12-60): a charger whose uniform of the step is below p_fail keeps executing the command it
+ *     was sent last (zeros before the first); what is held is what was SENT, not what the env left of it after zeroing empty ports;
+ *   DelayedObservation (noise_wrappers.py:62-198, the PublicPST branch): an occupied slot whose uniform of the step is below p_delay shows the
+ *     energy column delivered one step earlier, and the power reading obs[2] is lowered by the energy that was not communicated,
+ *     (nc * 60) / timescale, nc summed over the delayed slots in slot order (a plain left-to-right float64 sum), and clamped at 0 last.
+ * Both are bit for bit the reference's arithmetic.  Like the reference's objects a link keeps its uniforms and its held commands / remembered
+ * rows ACROSS episodes (ev2g_link_reset_state zeroes the latter: the fresh wrapper a caller builds per run, evaluator.py:237 style).
+ * Uniforms of each half: a HOST matrix in the reference's layout [E,P,T] (env e's [P,T] matrix is the wrapper's `random`; row i pairs with
+ * port / observation slot i), uploaded once -- or NULL: the counter-based generator of ev2g_fill_uniform evaluated on the fly at index
+ * (e*P + i)*T + t under the half's seed, i.e. the matrix ev2g_host_uniform(., E*P*T, seed, 0, 1) fills, without allocating it.
+ * Two stated differences to the reference:
+ *  - at the terminal observation (current_step == T) the reference indexes random[:, T] and raises as soon as one port is occupied; here that
+ *    observation passes through with no slot delayed (nc = 0, remembered rows updated, clamp applied);
+ *  - the reference's `assert obs[2] >= -5` (noise_wrappers.py:193) is not reproduced, only the clamp.
+ * Out of scope: the wrapper's graph-state branch (noise_wrappers.py:134-161) and the action wrappers (rl_agent/action_wrappers.py). */
+typedef struct ev2g_link ev2g_link;
+/* Needs loaded scenarios; bound to the handle's envs, ports and steps like an agent (a reload that changes them makes its calls fail) and freed
+ * with the handle if not before.  EV2G_ERR_ARG: a probability outside [0,1]; p_delay > 0 on a handle whose state is not EV2G_STATE_PUBLIC_PST
+ * (noise_wrappers.py:79-80).  A probability of exactly 0 disables that half: ev2g_link_run launches nothing for it (its matrix is not uploaded). */
+int ev2g_link_create(ev2g_handle *h, double p_fail, double p_delay, uint64_t seed_act, uint64_t seed_obs, const double *rand_act,
+                     const double *rand_obs, ev2g_link **out);
+void ev2g_link_destroy(ev2g_handle *h, ev2g_link *l);
+/* zeroes the held commands and the remembered rows (noise_wrappers.py:32,105-106: a freshly constructed pair of wrappers) */
+int ev2g_link_reset_state(ev2g_handle *h, ev2g_link *l);
+/* FailedActionCommunication.action (noise_wrappers.py:37-60) for step t (t < 0: the handle's current step): `in` [E,P] DEVICE, float64 or --
+ * in_is_f32 != 0 -- float32, widened as the engine widens float32 actions; the delivered commands go to the link (they are the next call's
+ * previous ones) and to out [E,P] float64 (DEVICE, may be NULL).  No step is taken.  EV2G_ERR_DONE for t >= T. */
+int ev2g_link_actions(ev2g_handle *h, ev2g_link *l, int t, const void *in, int in_is_f32, double *out);
+/* DelayedObservation.observation (noise_wrappers.py:113-198) on the observation of step t (t < 0: the handle's current step; 0 = the reset
+ * observation, T = the terminal one, which passes through): obs [E,D] DEVICE is rewritten in place; obs32 [E,D] (DEVICE, may be NULL) receives
+ * the delivered row rounded to float32.  PublicPST handles only. */
+int ev2g_link_observe(ev2g_handle *h, ev2g_link *l, int t, double *obs, float *obs32);
+/* k_steps x ([agent ->] fail kernel -> one-step launch of the step kernel the handle selected -> delay kernel on the observation row it wrote)
+ * inside ONE episode, enqueued without host round trips.  agent == NULL: the raw actions are read from actions [k,E,P] (a_stride 0: one block
+ * reused); with an agent (ev2g_heuristic_create) its raw actions are written there when it is not NULL.  obs / reward / done / mask as in
+ * ev2g_step_n (DEVICE, each may be NULL; the delayed half then works on a row of the link).  obs holds the DELIVERED observations.  A segment
+ * that would run past the episode end returns EV2G_ERR_DONE, as ev2g_heuristic_run does.  Timed like ev2g_step_n (ev2g_last_step_n_kernel_ms).
+ * A link that delays (p_delay > 0) must be shown every episode's RESET observation first, as the reference's wrapper is (noise_wrappers.py:113
+ * on reset): ev2g_reset into a block, then ev2g_link_observe(h, l, 0, that block, NULL), before the first segment.  Without it the remembered
+ * rows still hold the previous episode's terminal observation (zeros on a fresh link) when step 1's observation is delayed. */
+int ev2g_link_run(ev2g_handle *h, ev2g_link *l, ev2g_heuristic *agent, int k_steps, double *actions, int64_t a_stride, double *obs,
+                  int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride);
+/* The policy loop under the link: k_steps x (ev2g_mlp_forward on the link's float32 delivered row -> fail kernel on the policy's float32
+ * actions -> one-step launch -> delay kernel writing the float64 row and its float32 copy), inside one episode.  The rows live in the link;
+ * ev2g_link_obs_f32 returns the float32 one [E,D] (DEVICE): fill it before the first segment of an episode, with ev2g_link_observe(h, l, 0,
+ * reset observation, that pointer) -- or ev2g_reset_f32 into it for a link that delays nothing.  The unfused chain only: there is NO
+ * fused-launch variant (ev2g_rollout's single launch per segment has no place for the two kernels between policy and step). */
+float *ev2g_link_obs_f32(ev2g_handle *h, ev2g_link *l);
+int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
+                      int64_t d_stride, uint8_t *mask, int64_t m_stride);
+
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
 void ev2g_free(ev2g_handle *h, void *p);

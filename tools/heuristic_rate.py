@@ -4,6 +4,9 @@ launch of the step kernel, T times per episode), one JSON line per (workload, ag
   python tools/heuristic_rate.py [--workloads cfg2,cfg3,cfg4] [--episodes 3]
       env-steps/s from HIP-event kernel time (last_step_n_kernel_ms), next to the same per-step launches with fixed actions (`step_only`)
   rocprofv3 --kernel-trace --stats -d OUT/cfg2 -- python tools/heuristic_rate.py --workloads cfg2 --episodes 1
+  python tools/heuristic_rate.py --workloads cfg3 --link 0.1,0.1
+      ev2g_link_run (the reference's failed-command / delayed-observation models, csrc/ev2g_link.h) next to the plain per-step launches,
+      episodes alternating between the two: fixed actions, and one RoundRobin run (p_delay needs a PublicPST workload: cfg3)
   python tools/heuristic_rate.py --shares OUT
       the agent kernel's share of each (agent + step) pair, from the dispatches of every kernel_trace.csv under OUT
 
@@ -36,6 +39,42 @@ WORKLOADS = {
     "cfg4": (2048, lambda E, s: GenConfig.v2g_profit_plus_loads(E, 1000, 50, seed=s, power_setpoint_enabled=True), DEFAULT),
 }
 AGENTS = {k: n for n, k in _abi.AGENT_KINDS.items()}
+
+
+def link_rates(workload, episodes, p_fail, p_delay):
+    """Plain per-step launches and the same launches under a link, alternating episode by episode: env-steps/s of HIP-event kernel time."""
+    from ev2gym_amd.engine import Engine
+    from ev2gym_amd.scenario_gen import generate_native
+    E, gen, kinds = WORKLOADS[workload]
+    eng = Engine(generate_native(gen(E, 1234)), _abi.REWARD_KINDS[kinds[0]], _abi.STATE_KINDS[kinds[1]], flags=_abi.FLAG_LOG_SOC)
+    E, P, D, T = eng.E, eng.P, eng.D, eng.T
+    obs, rew = eng.empty((E, D)), eng.empty((E,))
+    done, mask = eng.empty((E,), np.uint8), eng.empty((E, P), np.uint8)
+    acts = eng.empty((E, P)).upload(np.ones((E, P)))
+    link, rr = eng.link_create(p_fail, p_delay, seed_act=1, seed_obs=2), eng.heuristic_create("RoundRobin")
+    out = (None, 0, obs, 0, rew, 0, done, 0, mask, 0)
+    pairs = {"fixed actions": (lambda: eng.step_n(T, acts, 0, *out[2:], auto_reset=0, persistent=False),
+                               lambda: eng.link_run(link, T, None, acts, 0, *out[2:])),
+             "RoundRobin": (lambda: eng.heuristic_run(rr, T, *out), lambda: eng.link_run(link, T, rr, *out))}
+    for name, runs in pairs.items():
+        ms = ([], [])
+        for i in range(episodes + 1):   # the first episode of each warms up
+            for which, run in enumerate(runs):
+                eng.reset(obs)
+                if which and p_delay > 0:
+                    eng.link_observe(link, obs)
+                run()
+                if i:
+                    ms[which].append(eng.last_step_n_kernel_ms())
+        eng.check_faults()
+        rate = lambda m: round(E * T / (m / 1e3))   # noqa: E731
+        plain, linked = statistics.median(ms[0]), statistics.median(ms[1])
+        print(json.dumps(dict(workload=workload, source=name, link=[p_fail, p_delay], envs=E, ports=P, steps=T, step_kernel=eng.kernel_name,
+                              plain_env_steps_per_s=rate(plain), plain_range=[rate(max(ms[0])), rate(min(ms[0]))],
+                              link_env_steps_per_s=rate(linked), link_range=[rate(max(ms[1])), rate(min(ms[1]))],
+                              plain_us_per_step=round(plain * 1e3 / T, 3), link_us_per_step=round(linked * 1e3 / T, 3),
+                              link_over_plain=round(linked / plain, 4))), flush=True)
+    eng.close()
 
 
 def rates(workload, episodes):
@@ -113,10 +152,14 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--workloads", default="cfg2,cfg3,cfg4")
     ap.add_argument("--episodes", type=int, default=3)
+    ap.add_argument("--link", metavar="P_FAIL,P_DELAY", help="time ev2g_link_run under these probabilities next to the plain per-step launches")
     ap.add_argument("--shares", metavar="DIR", help="read rocprofv3 kernel traces under DIR instead of running")
     args = ap.parse_args()
     if args.shares:
         shares(args.shares)
     else:
         for w in args.workloads.split(","):
-            rates(w, args.episodes)
+            if args.link:
+                link_rates(w, args.episodes, *[float(x) for x in args.link.split(",")])
+            else:
+                rates(w, args.episodes)
