@@ -25,6 +25,7 @@
 #include "ev2g_refill.h"
 #include "ev2g_heuristic.h"
 #include "ev2g_link.h"
+#include "ev2g_grid.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -64,6 +65,22 @@ static void link_free(ev2g_link *l) {
                     (void *)l->obs32, (void *)l->act32})
         (void)hipFree(p);
     delete l;
+}
+
+// a distribution grid (ev2g_grid_create, ev2g_grid.h): the network's K (transposed) and L, the solver's settings, the base profiles of every
+// resident scenario when the grid was made for ev2g_grid_run, the shape it was made for, and the per-env rows ev2g_grid_run works on when the
+// caller passes none
+struct ev2g_grid {
+    int E = 0, T = 0, M = 0, n = 0, max_iter = 0;
+    double s_base = 0.0, tolerance = 0.0;
+    double2 *Kt = nullptr, *L = nullptr;            // [n, n], [n]
+    double *p_base = nullptr, *q_base = nullptr;    // [M, T + 1, n] each, or nullptr: a solver only
+    double *vm = nullptr, *rew = nullptr;           // [E, n + 1], [E]
+};
+
+static void grid_free(ev2g_grid *g) {
+    for (void *p : {(void *)g->Kt, (void *)g->L, (void *)g->p_base, (void *)g->q_base, (void *)g->vm, (void *)g->rew}) (void)hipFree(p);
+    delete g;
 }
 
 #define EV2G_EV_RING 32
@@ -160,6 +177,7 @@ struct ev2g_handle {
     double heur_avg_power = 0.0, heur_min_action = 0.0;
     std::vector<ev2g_heuristic *> heuristics;
     std::vector<ev2g_link *> links;             // the communication-fault links created on this handle (freed with it)
+    std::vector<ev2g_grid *> grids;             // the distribution grids created on this handle (freed with it)
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -283,6 +301,8 @@ void ev2g_destroy(ev2g_handle *h) {
     h->heuristics.clear();
     for (ev2g_link *l : h->links) link_free(l);
     h->links.clear();
+    for (ev2g_grid *g : h->grids) grid_free(g);
+    h->grids.clear();
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
     for (int i = 0; i < EV2G_EV_RING; i++) { if (h->ev0s[i]) (void)hipEventDestroy(h->ev0s[i]); if (h->ev1s[i]) (void)hipEventDestroy(h->ev1s[i]); }
@@ -2008,6 +2028,130 @@ int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_ste
             hipLaunchKernelGGL(ev2g_link_f32_kernel, grid, dim3(EV2G_LINK_BLOCK), 0, h->stream, (const double *)l->obs, l->obs32, (long long)ED);
             HIPCHK(h, hipGetLastError());
         }
+    }
+    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
+    h->timed = true;
+    return EV2G_OK;
+}
+
+// ---- distribution grid: the Laurent power flow after each step (ev2g_grid.h) ----
+static int grid_upload(ev2g_handle *h, const void *src, size_t bytes, void **dst) {
+    HIPCHK(h, hipMalloc(dst, std::max<size_t>(bytes, 1)));
+    HIPCHK(h, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return EV2G_OK;
+}
+
+int ev2g_grid_create(ev2g_handle *h, int n_bus, const double *K, const double *L, double s_base, double tolerance, int max_iter,
+                     const double *p_base, const double *q_base, ev2g_grid **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_grid_create: null argument");
+    *out = nullptr;
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_grid_create: no scenarios loaded");
+    if (!K || !L) return fail(h, EV2G_ERR_ARG, "ev2g_grid_create: K or L is null");
+    if (n_bus < 2 || max_iter < 0 || !(s_base > 0.0)) return fail(h, EV2G_ERR_ARG, "ev2g_grid_create: n_bus < 2, max_iter < 0 or s_base <= 0");
+    const int n = n_bus - 1;
+    if (ev2g_grid_wave_bytes(n) > EV2G_GRID_LDS_MAX) return fail(h, EV2G_ERR_ARG, "ev2g_grid_create: up to 1025 buses (one row's stage has to fit 48 KiB of LDS)");
+    if ((p_base == nullptr) != (q_base == nullptr)) return fail(h, EV2G_ERR_ARG, "ev2g_grid_create: p_base and q_base come together");
+    // the reference builds one transformer per non-slack bus (loaders.py:481-485) and writes node i + 1 from transformer i (ev2gym_env.py:388-390)
+    if (p_base && h->R != n)
+        return fail(h, EV2G_ERR_ARG, "ev2g_grid_create: the loaded scenarios have " + std::to_string(h->R) + " transformers, the grid needs n_bus - 1 = " +
+                                     std::to_string(n) + " (one per non-slack bus, loaders.py:481-485)");
+    (void)hipSetDevice(h->device);
+    ev2g_grid *g = new ev2g_grid();
+    g->E = h->E; g->T = h->T; g->M = h->M; g->n = n; g->max_iter = max_iter; g->s_base = s_base; g->tolerance = tolerance;
+    std::vector<double> kt((size_t)n * n * 2);
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) {
+            kt[((size_t)j * n + i) * 2] = K[((size_t)i * n + j) * 2];
+            kt[((size_t)j * n + i) * 2 + 1] = K[((size_t)i * n + j) * 2 + 1];
+        }
+    int rc = grid_upload(h, kt.data(), kt.size() * sizeof(double), (void **)&g->Kt);
+    if (!rc) rc = grid_upload(h, L, (size_t)n * 2 * sizeof(double), (void **)&g->L);
+    const size_t prof = (size_t)h->M * (h->T + 1) * n * sizeof(double);
+    if (!rc && p_base) rc = grid_upload(h, p_base, prof, (void **)&g->p_base);
+    if (!rc && q_base) rc = grid_upload(h, q_base, prof, (void **)&g->q_base);
+    if (!rc && (hipMalloc((void **)&g->vm, (size_t)h->E * n_bus * sizeof(double)) != hipSuccess || hipMalloc((void **)&g->rew, (size_t)h->E * sizeof(double)) != hipSuccess))
+        rc = fail(h, EV2G_ERR_HIP, "ev2g_grid_create: device allocation failed");
+    if (rc) { grid_free(g); return rc; }
+    h->grids.push_back(g);
+    *out = g;
+    return EV2G_OK;
+}
+
+void ev2g_grid_destroy(ev2g_handle *h, ev2g_grid *g) {
+    if (!h || !g) return;
+    auto it = std::find(h->grids.begin(), h->grids.end(), g);
+    if (it == h->grids.end()) return;
+    h->grids.erase(it);
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    grid_free(g);
+}
+
+static int grid_check(ev2g_handle *h, ev2g_grid *g, bool run, const char *who) {
+    if (!h || !g) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (std::find(h->grids.begin(), h->grids.end(), g) == h->grids.end())
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the grid was not created on this handle");
+    if (run) {
+        if (!g->p_base) return fail(h, EV2G_ERR_ARG, std::string(who) + ": the grid was created without base profiles (a solver only)");
+        if (g->E != h->E || g->T != h->T || g->M != h->M || g->n != h->R)
+            return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / steps / pool / transformers differ from those the grid was created for");
+    }
+    (void)hipSetDevice(h->device);
+    return EV2G_OK;
+}
+
+// one wavefront per row, up to EV2G_GRID_WAVES per workgroup while their LDS stages fit the 48 KiB a launch gets without a function attribute
+static int grid_launch(ev2g_handle *h, const ev2g_grid *g, GridArgs ga, bool compose) {
+    if (ga.n_rows <= 0) return EV2G_OK;
+    ga.Kt = g->Kt; ga.L = g->L; ga.n = g->n; ga.max_iter = g->max_iter; ga.s_base = g->s_base; ga.tolerance = g->tolerance;
+    const size_t wb = ev2g_grid_wave_bytes(g->n);   // (<= EV2G_GRID_LDS_MAX: ev2g_grid_create)
+    const int epb = (int)std::min<size_t>(EV2G_GRID_WAVES, EV2G_GRID_LDS_MAX / wb);
+    const dim3 grid((ga.n_rows + epb - 1) / epb), block(64 * epb);
+    if (compose) hipLaunchKernelGGL(ev2g_grid_kernel<true>, grid, block, epb * wb, h->stream, ga);
+    else hipLaunchKernelGGL(ev2g_grid_kernel<false>, grid, block, epb * wb, h->stream, ga);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_grid_solve(ev2g_handle *h, ev2g_grid *g, const double *p_kw, const double *q_kw, int n_rows, double *vm, double *v_complex,
+                    int32_t *iters, double *loss_v) {
+    if (int rc = grid_check(h, g, false, "ev2g_grid_solve")) return rc;
+    if (!p_kw || !q_kw || n_rows < 0) return fail(h, EV2G_ERR_ARG, "ev2g_grid_solve: p_kw or q_kw is null, or n_rows < 0");
+    GridArgs ga{};
+    ga.p = p_kw; ga.q = q_kw; ga.n_rows = n_rows; ga.vm = vm; ga.vc = v_complex; ga.iters = iters; ga.loss = loss_v;
+    return grid_launch(h, g, ga, false);
+}
+
+int ev2g_grid_run(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
+                  double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm, int64_t v_stride,
+                  double base_weight, double voltage_weight) {
+    int rc = grid_check(h, g, true, "ev2g_grid_run");
+    if (rc) return rc;
+    if (a && (rc = heuristic_check(h, a, "ev2g_grid_run"))) return rc;
+    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0 || v_stride < 0)
+        return fail(h, EV2G_ERR_ARG, "ev2g_grid_run: negative step count or stride");
+    if (!a && !actions) return fail(h, EV2G_ERR_ARG, "ev2g_grid_run: without an agent the actions are read from `actions`");
+    // (as ev2g_heuristic_run: segments stay inside one episode)
+    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_grid_run: the segment would run past the episode end");
+    if (a && !actions) { actions = a->act; a_stride = 0; }
+    if (!reward) { reward = g->rew; r_stride = 0; }
+    if (!vm) { vm = g->vm; v_stride = 0; }
+    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
+    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    for (int i = 0; i < k_steps; i++) {
+        double *act_i = actions + (long long)i * a_stride, *rew_i = reward + (long long)i * r_stride;
+        if (a && (rc = heuristic_launch(h, a, act_i))) return rc;
+        const StepIO io = make_io(h, act_i, 0, obs ? obs + (long long)i * o_stride : nullptr, 0, rew_i, 0,
+                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
+        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
+        // a one-step launch leaves Transformer.current_power of its step in tr_power_now (every step kernel writes it in a launch's last step)
+        GridArgs ga{};
+        ga.p = g->p_base; ga.q = g->q_base; ga.tr_power = h->st.tr_power_now; ga.M = h->M; ga.T1 = h->T + 1; ga.t = h->current_step;
+        ga.scn_off = (int)h->scn_off; ga.n_rows = h->E; ga.vm = vm + (long long)i * v_stride; ga.reward = rew_i;
+        ga.base_weight = base_weight; ga.voltage_weight = voltage_weight;
+        if ((rc = grid_launch(h, g, ga, true))) return rc;
+        h->current_step += 1;
     }
     HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
     h->timed = true;

@@ -84,6 +84,10 @@ def load_library(path: Optional[str] = None):
         "ev2g_link_obs_f32": (vp, [vp, vp]),
         "ev2g_link_run": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]),
         "ev2g_link_rollout": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64]),
+        "ev2g_grid_create": (C.c_int, [vp, C.c_int, vp, vp, dbl, dbl, C.c_int, vp, vp, C.POINTER(vp)]),
+        "ev2g_grid_destroy": (None, [vp, vp]),
+        "ev2g_grid_solve": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
+        "ev2g_grid_run": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, dbl, dbl]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -139,7 +143,8 @@ EXPORTED_SYMBOLS = [
     "ev2g_pool_refill", "ev2g_pool_refill_overflows", "ev2g_pool_session_capacity", "ev2g_gen_default_config", "ev2g_generate", "ev2g_gen_batch", "ev2g_gen_free", "ev2g_gen_table",
     "ev2g_heuristic_create", "ev2g_heuristic_destroy", "ev2g_heuristic_actions", "ev2g_heuristic_run",
     "ev2g_link_create", "ev2g_link_destroy", "ev2g_link_reset_state", "ev2g_link_actions", "ev2g_link_observe", "ev2g_link_obs_f32",
-    "ev2g_link_run", "ev2g_link_rollout"]
+    "ev2g_link_run", "ev2g_link_rollout",
+    "ev2g_grid_create", "ev2g_grid_destroy", "ev2g_grid_solve", "ev2g_grid_run"]
 
 
 def _ptr(x):
@@ -459,6 +464,45 @@ class Engine:
         """k x (actor on the link's float32 delivered row -> held commands -> one step -> delayed observation), unfused, inside one episode."""
         self._check(self._lib.ev2g_link_rollout(self._h, l, m, int(k), _ptr(reward), int(r_stride), _ptr(done), int(d_stride), _ptr(mask),
                                                 int(m_stride)))
+
+    # ---- the distribution grid's power flow on the device (include/ev2g.h: ev2g_grid_*) ------------------------------------------
+    def grid_create(self, network, profiles=None, tolerance=1e-6, max_iter=100):
+        """A device-resident Laurent power flow of `network` (ev2gym_amd.grid.GridNetwork, or anything with n_bus, K, L, s_base), freed by
+        grid_destroy or with the engine.  profiles = (p_base, q_base), host arrays [M, T + 1, n_bus - 1] in kW (GridNetwork.base_profiles), make
+        it usable by grid_run: the scenarios then need one transformer per non-slack bus.  None: the solver only (grid_solve)."""
+        n = int(network.n_bus) - 1
+        K = np.ascontiguousarray(network.K, np.complex128)
+        L = np.ascontiguousarray(np.asarray(network.L).reshape(-1), np.complex128)
+        if K.shape != (n, n) or L.shape != (n,):
+            raise ValueError(f"grid_create: K {K.shape} / L {L.shape} do not fit {n + 1} buses")
+        pq = [None, None]
+        if profiles is not None:
+            pq = [np.ascontiguousarray(x, np.float64) for x in profiles]
+            want = (self.M, self.T + 1, n)
+            for x in pq:
+                if x.shape != want:
+                    raise ValueError(f"grid_create: a base profile has shape {x.shape}, expected {want} (scenarios of the pool, steps + 1, non-slack buses)")
+        g = C.c_void_p()
+        self._check(self._lib.ev2g_grid_create(self._h, n + 1, K.ctypes.data, L.ctypes.data, float(network.s_base), float(tolerance), int(max_iter),
+                                               *[None if x is None else x.ctypes.data for x in pq], C.byref(g)))
+        return g
+
+    def grid_destroy(self, g):
+        if self._h and g:
+            self._lib.ev2g_grid_destroy(self._h, g)
+
+    def grid_solve(self, g, p_kw, q_kw, n_rows, vm=None, v_complex=None, iters=None, loss_v=None):
+        """The bare batched solver on device arrays: p_kw / q_kw [n_rows, n] in kW -> vm [n_rows, n_bus], v_complex [n_rows, n, 2],
+        iters [n_rows] int32, loss_v [n_rows] (each optional)."""
+        self._check(self._lib.ev2g_grid_solve(self._h, g, _ptr(p_kw), _ptr(q_kw), int(n_rows), _ptr(vm), _ptr(v_complex), _ptr(iters), _ptr(loss_v)))
+
+    def grid_run(self, g, k, agent=None, actions=None, a_stride=0, obs=None, o_stride=0, reward=None, r_stride=0, done=None, d_stride=0,
+                 mask=None, m_stride=0, vm=None, v_stride=0, base_weight=0.0, voltage_weight=1000.0):
+        """k x ([agent ->] one step -> power flow on that step's transformer powers) inside one episode; outputs as in step_n plus the bus
+        voltages vm [k, E, n_bus]; reward = base_weight * the step's reward + voltage_weight * loss_v.  Timed like step_n."""
+        self._check(self._lib.ev2g_grid_run(self._h, g, agent, int(k), _ptr(actions), int(a_stride), _ptr(obs), int(o_stride), _ptr(reward),
+                                            int(r_stride), _ptr(done), int(d_stride), _ptr(mask), int(m_stride), _ptr(vm), int(v_stride),
+                                            float(base_weight), float(voltage_weight)))
 
     # ---- statistics / inspection ---------------------------------------------------------------
     def stats(self, out=None) -> np.ndarray:

@@ -17,6 +17,8 @@ episodes.
 
 Arrays are torch CUDA tensors when torch sees the GPU (zero-copy: the engine writes through `data_ptr()` on
 torch's current stream -- the SB3 path), otherwise engine-owned device buffers mirrored to numpy.
+`grid=` (ev2gym_amd.grid.GridNetwork) with `grid_profiles=(load, pv)` is the reference's `simulate_grid: True` with the Laurent solver: the power
+flow runs on the device after every step (csrc/ev2g_grid.h), `node_voltage` holds the bus voltages, `grid_reward` adds the voltage term.
 Only the fused built-in state / reward functions run here; arbitrary Python callables need the single-env
 facade (`ev2gym_amd.env.EV2Gym`), which says so instead of silently falling back.
 """
@@ -53,12 +55,43 @@ def _kind(fn, table, what):
     return None
 
 
+def grid_setup(grid, grid_profiles, grid_reward, reward_kind, E, M, T, R):
+    """EV2GymVec's grid arguments, checked and turned into what Engine.grid_create / grid_run take: (p_base, q_base) [M, T + 1, n_bus - 1] and
+    the reward's (base_weight, voltage_weight).  grid_profiles = (load, pv), each [T + 1, n_bus] (every scenario of the pool sees the same day)
+    or [M, T + 1, n_bus] in kW, column 0 the slack bus; grid_reward: a key of grid.GRID_REWARDS or a (base_weight, voltage_weight) pair."""
+    from .grid import GRID_REWARDS
+    n = int(grid.n_bus) - 1
+    if R != n:
+        raise ValueError(f"grid: the scenarios have {R} transformers, a {grid.n_bus}-bus network needs n_bus - 1 = {n} "
+                         "(the reference builds one transformer per non-slack bus, loaders.py:481-485)")
+    if isinstance(grid_reward, str):
+        if grid_reward not in GRID_REWARDS:
+            raise ValueError(f"unknown grid_reward '{grid_reward}' (known: {sorted(GRID_REWARDS)}, or a (base_weight, voltage_weight) pair; "
+                             "V2G_grid_full_reward needs a reward specialisation of the step kernels that does not exist)")
+        base, bw, vw = GRID_REWARDS[grid_reward]
+        if base is not None and reward_kind != _abi.REWARD_KINDS[base]:
+            raise ValueError(f"grid_reward '{grid_reward}' is {base} plus the voltage term: construct the env with reward_function='{base}'")
+    else:
+        bw, vw = (float(x) for x in grid_reward)
+    want = f"grid_profiles: (load, pv), each [{T + 1}, {grid.n_bus}] or [{M}, {T + 1}, {grid.n_bus}] (steps + 1 rows, all buses)"
+    if grid_profiles is None or len(grid_profiles) != 2:
+        raise ValueError(want + "; the load-profile generator of the reference is not part of this package")
+    load, pv = (np.asarray(x, np.float64) for x in grid_profiles)
+    if load.shape != pv.shape or load.shape not in ((T + 1, grid.n_bus), (M, T + 1, grid.n_bus)):
+        raise ValueError(want + f", got {load.shape} and {pv.shape}")
+    p, q = grid.base_profiles(load, pv)
+    if p.ndim == 2:
+        p, q = np.broadcast_to(p, (M,) + p.shape), np.broadcast_to(q, (M,) + q.shape)
+    return np.ascontiguousarray(p), np.ascontiguousarray(q), bw, vw
+
+
 class EV2GymVec:
     def __init__(self, config_file=None, num_envs: int = 1, device: int = 0, state_function="PublicPST",
                  reward_function="SquaredTrackingErrorReward", cost_function=None, seed: Optional[int] = None,
                  scenarios: Optional[ScenarioBatch] = None, auto_reset: bool = False, log_cs_history: bool = False, log_soc: bool = True,
                  use_torch: Optional[bool] = None, rank: int = 0, world_size: int = 1, verbose: bool = False,
-                 load_from_replay_path=None, pool_factor: int = 8, resample_every: Optional[int] = None, generator: str = "native", data_dir=None, device_refill: bool = False, sorted_pool: bool = True, **unused):
+                 load_from_replay_path=None, pool_factor: int = 8, resample_every: Optional[int] = None, generator: str = "native", data_dir=None, device_refill: bool = False, sorted_pool: bool = True,
+                 grid=None, grid_profiles=None, grid_reward="V2G_grid_simple_reward", **unused):
         self.state_kind = _kind(state_function, _abi.STATE_KINDS, "state_function")
         self.reward_kind = _kind(reward_function, _abi.REWARD_KINDS, "reward_function")
         if self.state_kind is None or self.reward_kind is None:
@@ -154,6 +187,18 @@ class EV2GymVec:
         if self.cost_kind:
             self._cost = self._alloc((e.E,))
             e.set_extras(cost=self._cost)
+        # grid= (ev2gym_amd.grid.GridNetwork): the reference's simulate_grid with the Laurent solver.  step() then runs the power flow on the
+        # device after the step kernel (Engine.grid_run) and `node_voltage` holds the last step's bus voltages [E, n_bus]
+        self._grid = None
+        self.node_voltage = None
+        if grid is not None:
+            if self.device_refill or self.resample_every:
+                raise ValueError("grid: the base profiles are attached to the pool's scenarios; device_refill / resample_every re-draw those")
+            p_base, q_base, self._grid_bw, self._grid_vw = grid_setup(grid, grid_profiles, grid_reward, self.reward_kind, e.E, e.M, e.T, e.R)
+            self._grid = e.grid_create(grid, (p_base, q_base))
+            self._vm = self._alloc((e.E, grid.n_bus))
+        elif grid_profiles is not None:
+            raise ValueError("grid_profiles without grid=")
         self.stats = None
         self._refill_next = e.M * max(1, world_size)   # next unused scenario index of this env's stream (every rank continues after the whole first pool)
         self._refill_stride = max(1, world_size)
@@ -309,7 +354,12 @@ class EV2GymVec:
         if self.engine.current_step >= self.simulation_length:
             raise AssertionError("Episode is done, please reset the environment")   # ev2gym_env.py:343
         a = self._as_device_actions(actions)
-        self.engine.step(a, self._obs, self._rew, self._done, self._mask)
+        if self._grid is not None:
+            self.engine.grid_run(self._grid, 1, None, a, 0, self._obs, 0, self._rew, 0, self._done, 0, self._mask, 0, self._vm, 0,
+                                 self._grid_bw, self._grid_vw)
+            self.node_voltage = self._out(self._vm)
+        else:
+            self.engine.step(a, self._obs, self._rew, self._done, self._mask)
         info = {"action_mask": self._out(self._mask), "cost": self._out(self._cost) if self._cost is not None else None}
         finished = self.engine.current_step >= self.simulation_length
         if finished:

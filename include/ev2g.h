@@ -497,6 +497,49 @@ float *ev2g_link_obs_f32(ev2g_handle *h, ev2g_link *l);
 int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
                       int64_t d_stride, uint8_t *mask, int64_t m_stride);
 
+/* ---- the distribution grid's power flow ON THE DEVICE (simulate_grid: models/grid.py, models/grid_utility/grid_tensor.py) ----------------
+ * A grid holds the reference's Laurent power flow (pf_solver "Laurent", constant-power loads) for the E envs of a handle.  After every step
+ * the reference injects each transformer's current_power at its bus (ev2gym_env.py:387-393: node i + 1 <- transformer i), adds the step's base
+ * load minus PV (grid.py:110-139), and iterates from a flat start v = 1 + 0j
+ *     lambda = conj(S * (1 / v));  v' = K lambda + L;  tol = max_i | |v'_i| - |v_i| |;  v = v'       (S = (P + jQ) / s_base, grid.py:151-199)
+ * while iterations < max_iter and tol >= tolerance; |v| with the slack's 1.0 in front is env.node_voltage of that step, and the voltage
+ * rewards add  loss_v = sum_i min(0, 0.05 - |1 - |v_i||)  over all n_bus entries (rl_agent/reward.py:117-119, 269-279).
+ * K [n,n] and L [n] (n = n_bus - 1; complex128, re / im interleaved, HOST) are the network's -inv(Ydd) and K Yds (grid_tensor.py:110-118),
+ * uploaded once.  The stopping rule is per env: an env that has converged keeps its v and its iteration count while others go on, and the loop
+ * is bounded by max_iter whatever the data does (a NaN residual ends it, as numpy's comparison does).
+ * Stated differences to the reference:
+ *  - the product K lambda is summed over j = 0 .. n-1 in that order with fused multiply-adds; numpy's goes through BLAS in no defined order, so
+ *    voltages agree to rounding (1e-9 relative is the bar the tests hold), not bit for bit; iteration counts agree wherever the residual is
+ *    not within rounding of the tolerance;
+ *  - the base profiles are the CALLER's arrays: the reference samples loads from a fitted generator (data/augmentor.pkl) that is not part of it;
+ *  - the episode statistics (ev2g_get_stats' total_reward included) keep the step kernel's own reward; the composed reward is what
+ *    ev2g_grid_run writes to `reward`;
+ *  - ev2g_pool_refill does not re-draw a grid's profiles: they stay attached to the pool slots they were uploaded for.
+ * Out of scope: the load-profile generator, the PandaPower solver, V2G_grid_state and V2G_grid_full_reward. */
+typedef struct ev2g_grid ev2g_grid;
+/* Needs loaded scenarios; freed with the handle if not before.  p_base / q_base: HOST arrays [M, T+1, n] in kW, block m for scenario m of the
+ * resident pool (env e runs scenario (e + offset) mod M), row t read after step t (the reference also reads row T, after the last step) -- or
+ * both NULL: a solver only (ev2g_grid_solve), ev2g_grid_run then fails.  EV2G_ERR_ARG: n_bus < 2 or > 1025, max_iter < 0, s_base <= 0, and --
+ * with profiles -- a scenario batch whose transformer count is not n_bus - 1 (the reference builds one transformer per non-slack bus,
+ * loaders.py:481-485).  The reference's settings are s_base 1000, tolerance 1e-6, max_iter 100 (grid_tensor.py:50,564-565). */
+int ev2g_grid_create(ev2g_handle *h, int n_bus, const double *K, const double *L, double s_base, double tolerance, int max_iter,
+                     const double *p_base, const double *q_base, ev2g_grid **out);
+void ev2g_grid_destroy(ev2g_handle *h, ev2g_grid *g);
+/* The bare batched solver, no engine state involved: p_kw / q_kw [n_rows, n] DEVICE in kW -> vm [n_rows, n_bus], v_complex [n_rows, n, 2],
+ * iters [n_rows] int32, loss_v [n_rows] (DEVICE, each may be NULL).  Asynchronous on the handle's stream. */
+int ev2g_grid_solve(ev2g_handle *h, ev2g_grid *g, const double *p_kw, const double *q_kw, int n_rows, double *vm, double *v_complex,
+                    int32_t *iters, double *loss_v);
+/* k_steps x ([agent ->] one-step launch of the step kernel the handle selected -> grid kernel) inside ONE episode, enqueued without host round
+ * trips.  Arguments and error returns as ev2g_link_run (agent == NULL: actions [k,E,P] are read; EV2G_ERR_DONE for a segment past the episode
+ * end).  After step t the grid kernel solves P_i = p_base[scenario, t, i] + transformer i's power, Q_i = q_base[scenario, t, i], writes |v| to
+ * vm [k,E,n_bus] at base + k*v_stride (v_stride 0: one block; NULL: a block of the grid) and rewrites
+ *     reward[e] = base_weight * reward[e] + voltage_weight * loss_v[e]          (base_weight == 0: voltage_weight * loss_v, nothing read)
+ * V2G_grid_simple_reward is (0, 1000); Grid_V2G_profitmaxV2 is (1, 50000) on a handle whose reward is EV2G_REWARD_V2G_PROFITMAX_V2.
+ * Timed like ev2g_step_n (ev2g_last_step_n_kernel_ms). */
+int ev2g_grid_run(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *agent, int k_steps, double *actions, int64_t a_stride, double *obs,
+                  int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride,
+                  double *vm, int64_t v_stride, double base_weight, double voltage_weight);
+
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
 void ev2g_free(ev2g_handle *h, void *p);
