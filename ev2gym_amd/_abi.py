@@ -32,7 +32,8 @@ STAT_NAMES = [  # get_statistics(), utilities/utils.py:84-101
     'total_transformer_overload', 'battery_degradation', 'battery_degradation_calendar',
     'battery_degradation_cycling', 'total_reward']
 
-# grid-simulation keys of the same dict (utils.py:103-112): constant 0 (the power flow runs on the device, ev2g_grid_*, but keeps no episode history)
+# grid-simulation keys of the same dict (utils.py:103-112): constant 0 unless EV2GymVec(grid_statistics=True) fills the three voltage keys from the
+# grid kernel's accumulators (ev2g_grid_get_stats); saved_grid_energy is 0 in the reference too
 GRID_STAT_ZEROS = ('saved_grid_energy', 'voltage_violation', 'voltage_violation_counter',
                    'voltage_violation_counter_per_step')
 
@@ -54,6 +55,8 @@ AGENT_KINDS = {   # every agent ev2g_heuristic_create knows: the three above and
 AUTO_RESET_SAME = 1
 AUTO_RESET_NEXT = 2
 
+ERR_ARG = -1
+ERR_STATE = -3
 ERR_DONE = -4
 ERR_OVERCURRENT = -5
 FLAG_LOG_CS_HISTORY = 1

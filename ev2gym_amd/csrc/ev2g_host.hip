@@ -76,10 +76,24 @@ struct ev2g_grid {
     double2 *Kt = nullptr, *L = nullptr;            // [n, n], [n]
     double *p_base = nullptr, *q_base = nullptr;    // [M, T + 1, n] each, or nullptr: a solver only
     double *vm = nullptr, *rew = nullptr;           // [E, n + 1], [E]
+    // the episode's voltage statistics (ev2g_grid_kernel<true>'s accumulators), with profiles only: [E] each
+    double *vv_sum = nullptr, *rew_sum = nullptr;
+    int *vv_count = nullptr, *vv_steps = nullptr;
+    // V2G_grid_state (ev2g_grid_state_attach): the time-feature table [M or 1, T + 1, 3], the row width 6 + 2 n + 3 P, the grid's own rows
+    // [E, Dg] and the blocks ev2g_grid_rollout works on ([E, P] each); obs32 holds the state of step counter obs32_step as long as nothing
+    // has changed the engine's state since (obs32_epoch == the handle's state_epoch), -1: nothing
+    double *tf = nullptr;
+    int tf_per_scn = 0, Dg = 0;
+    double *obs = nullptr, *act = nullptr;
+    float *obs32 = nullptr, *act32 = nullptr;
+    int obs32_step = -1;
+    long long obs32_epoch = -1;
 };
 
 static void grid_free(ev2g_grid *g) {
-    for (void *p : {(void *)g->Kt, (void *)g->L, (void *)g->p_base, (void *)g->q_base, (void *)g->vm, (void *)g->rew}) (void)hipFree(p);
+    for (void *p : {(void *)g->Kt, (void *)g->L, (void *)g->p_base, (void *)g->q_base, (void *)g->vm, (void *)g->rew, (void *)g->vv_sum, (void *)g->rew_sum,
+                    (void *)g->vv_count, (void *)g->vv_steps, (void *)g->tf, (void *)g->obs, (void *)g->act, (void *)g->obs32, (void *)g->act32})
+        (void)hipFree(p);
     delete g;
 }
 
@@ -151,6 +165,7 @@ struct ev2g_handle {
     std::string kernel_name;                    // the step kernel ev2g_load_scenarios selected (ev2g_kernel_name)
     std::string fallback_reason;                // why the common-shape fast path was NOT taken ("" when it was / does not apply)
     int current_step = 0;
+    long long state_epoch = 0;                  // counts the calls that change the envs' state (load, reset, step launches, refill): what a grid's obs32 row is valid for
     size_t lds_bytes = 0;
     // HIP-event pairs of the last EV2G_EV_RING timed calls (ev2g_step_n / ev2g_rollout / ev2g_collect): a caller that queues several launches and
     // reads their durations afterwards (bench.py's roofline pass) does not have to drain the stream after each one
@@ -617,6 +632,7 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     h->no_full = std::getenv("EV2G_NO_FULL") != nullptr; h->no_wide = std::getenv("EV2G_NO_WIDE") != nullptr; h->last_spec = -1;
     h->no_strided = std::getenv("EV2G_NO_STRIDED") != nullptr;
     h->no_inl_stats = std::getenv("EV2G_NO_INLAUNCH_STATS") != nullptr; h->inl_stats = false; h->last_stats_route = -1; h->inl_reason = "no step launch since the scenarios were loaded";
+    h->state_epoch += 1;
     if (h->wave_path) {   // ev2g_step_wave addresses every array as base + 32-bit byte offset: all of them must stay below 4 GiB
         const unsigned long long lim = 1ull << 32;
         const unsigned long long biggest = std::max({(unsigned long long)E * P * 8, (unsigned long long)E * D * 8,
@@ -1024,7 +1040,7 @@ int ev2g_reset_ex(ev2g_handle *h, double *obs, int64_t scenario_offset) {
     hipLaunchKernelGGL(ev2g_reset_kernel, dim3(s.n_groups), dim3(EV2G_BLOCK), 0, h->stream, s, h->st, obs, h->extras.obs_f32, (int)off);
     HIPCHK(h, hipGetLastError());
     h->current_step = 0;
-    h->inl_stats = false; h->inl_reason = "the episode was reset";
+    h->inl_stats = false; h->inl_reason = "the episode was reset"; h->state_epoch += 1;
     return EV2G_OK;
 }
 
@@ -1077,7 +1093,7 @@ static StepIO make_io(const ev2g_handle *h, const double *actions, long long a_s
 
 static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int auto_reset) {
     const DevScn &s = h->scn;
-    h->inl_stats = false; h->inl_reason = "the step kernel is not ev2g_step_wave";
+    h->inl_stats = false; h->inl_reason = "the step kernel is not ev2g_step_wave"; h->state_epoch += 1;
     if (h->wave_path) {
         // the fast path advances its output pointers by 32-bit byte strides
         const long long lim = 1ll << 32;
@@ -1526,7 +1542,7 @@ static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, int k, const float *o
     const DevScn &s = h->scn;
     const DevState &st = h->st;
     const long long lim = 1ll << 32;
-    h->inl_stats = false; h->inl_reason = "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)";
+    h->inl_stats = false; h->inl_reason = "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)"; h->state_epoch += 1;
     if (o_stride * 4 >= lim || a_stride * 4 >= lim || r_stride * 8 >= lim || d_stride >= lim || m_stride >= lim || o_stride < 0 || a_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0)
         return fail(h, EV2G_ERR_ARG, "ev2g_collect / ev2g_rollout: a step stride is negative or reaches 4 GiB");
     StepIO io = make_io(h, nullptr, a_stride, nullptr, o_stride, reward, r_stride, done, d_stride, mask, m_stride, 0, 0);
@@ -2071,6 +2087,14 @@ int ev2g_grid_create(ev2g_handle *h, int n_bus, const double *K, const double *L
     if (!rc && q_base) rc = grid_upload(h, q_base, prof, (void **)&g->q_base);
     if (!rc && (hipMalloc((void **)&g->vm, (size_t)h->E * n_bus * sizeof(double)) != hipSuccess || hipMalloc((void **)&g->rew, (size_t)h->E * sizeof(double)) != hipSuccess))
         rc = fail(h, EV2G_ERR_HIP, "ev2g_grid_create: device allocation failed");
+    if (!rc && p_base) {   // the episode's voltage statistics: zero until the first step of an episode overwrites them
+        const size_t Ed = (size_t)h->E * sizeof(double), Ei = (size_t)h->E * sizeof(int);
+        if (hipMalloc((void **)&g->vv_sum, Ed) != hipSuccess || hipMalloc((void **)&g->rew_sum, Ed) != hipSuccess ||
+            hipMalloc((void **)&g->vv_count, Ei) != hipSuccess || hipMalloc((void **)&g->vv_steps, Ei) != hipSuccess ||
+            hipMemset(g->vv_sum, 0, Ed) != hipSuccess || hipMemset(g->rew_sum, 0, Ed) != hipSuccess ||
+            hipMemset(g->vv_count, 0, Ei) != hipSuccess || hipMemset(g->vv_steps, 0, Ei) != hipSuccess)
+            rc = fail(h, EV2G_ERR_HIP, "ev2g_grid_create: device allocation failed");
+    }
     if (rc) { grid_free(g); return rc; }
     h->grids.push_back(g);
     *out = g;
@@ -2123,20 +2147,55 @@ int ev2g_grid_solve(ev2g_handle *h, ev2g_grid *g, const double *p_kw, const doub
     return grid_launch(h, g, ga, false);
 }
 
-int ev2g_grid_run(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
-                  double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm, int64_t v_stride,
-                  double base_weight, double voltage_weight) {
-    int rc = grid_check(h, g, true, "ev2g_grid_run");
+// the grid kernel after the one-step launch of step h->current_step: a one-step launch leaves Transformer.current_power of its step in
+// tr_power_now (every step kernel writes it in a launch's last step)
+static int grid_launch_step(ev2g_handle *h, const ev2g_grid *g, double *vm, double *reward, double base_weight, double voltage_weight) {
+    GridArgs ga{};
+    ga.p = g->p_base; ga.q = g->q_base; ga.tr_power = h->st.tr_power_now; ga.M = h->M; ga.T1 = h->T + 1; ga.t = h->current_step;
+    ga.scn_off = (int)h->scn_off; ga.n_rows = h->E; ga.vm = vm; ga.reward = reward;
+    ga.base_weight = base_weight; ga.voltage_weight = voltage_weight;
+    ga.vv_sum = g->vv_sum; ga.rew_sum = g->rew_sum; ga.vv_count = g->vv_count; ga.vv_steps = g->vv_steps;
+    return grid_launch(h, g, ga, true);
+}
+
+// the state kernel for the handle's current step counter; a row written into the grid's own obs32 is remembered as valid for that counter
+static int grid_launch_state(ev2g_handle *h, ev2g_grid *g, double *obs, float *obs32) {
+    if (!obs && !obs32) return EV2G_OK;
+    HeurArgs ha{};
+    ha.port_slot = h->d_port_slot; ha.scn_off = (int)h->scn_off;
+    const GridStateArgs sa{g->tf, g->tf_per_scn, g->p_base, g->q_base, g->n, h->current_step, g->Dg, obs, obs32};
+    const long long total = (long long)h->E * g->Dg;
+    const dim3 grid((unsigned)std::min<long long>((total + EV2G_GRID_STATE_BLOCK - 1) / EV2G_GRID_STATE_BLOCK, 1 << 20));
+    hipLaunchKernelGGL(ev2g_grid_state_kernel, grid, dim3(EV2G_GRID_STATE_BLOCK), 0, h->stream, h->scn, h->st, ha, sa);
+    HIPCHK(h, hipGetLastError());
+    if (obs32 == g->obs32) { g->obs32_step = h->current_step; g->obs32_epoch = h->state_epoch; }
+    return EV2G_OK;
+}
+
+static int grid_state_check(ev2g_handle *h, ev2g_grid *g, const char *who) {
+    if (int rc = grid_check(h, g, true, who)) return rc;
+    if (!g->tf) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no state attached to the grid (ev2g_grid_state_attach)");
+    if (g->Dg != 6 + 2 * g->n + 3 * h->P) return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' ports differ from those the state was attached for");
+    return EV2G_OK;
+}
+
+// ev2g_grid_run and ev2g_grid_run_observed: k_steps x ([agent ->] one-step launch -> grid kernel [-> state kernel of the next counter])
+static int grid_run_loop(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
+                         double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm,
+                         int64_t v_stride, double base_weight, double voltage_weight, bool observed, double *gobs, int64_t go_stride, float *gobs32,
+                         int64_t go32_stride, const char *who) {
+    int rc = observed ? grid_state_check(h, g, who) : grid_check(h, g, true, who);
     if (rc) return rc;
-    if (a && (rc = heuristic_check(h, a, "ev2g_grid_run"))) return rc;
-    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0 || v_stride < 0)
-        return fail(h, EV2G_ERR_ARG, "ev2g_grid_run: negative step count or stride");
-    if (!a && !actions) return fail(h, EV2G_ERR_ARG, "ev2g_grid_run: without an agent the actions are read from `actions`");
+    if (a && (rc = heuristic_check(h, a, who))) return rc;
+    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0 || v_stride < 0 || go_stride < 0 || go32_stride < 0)
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": negative step count or stride");
+    if (!a && !actions) return fail(h, EV2G_ERR_ARG, std::string(who) + ": without an agent the actions are read from `actions`");
     // (as ev2g_heuristic_run: segments stay inside one episode)
-    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_grid_run: the segment would run past the episode end");
+    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, std::string(who) + ": the segment would run past the episode end");
     if (a && !actions) { actions = a->act; a_stride = 0; }
     if (!reward) { reward = g->rew; r_stride = 0; }
     if (!vm) { vm = g->vm; v_stride = 0; }
+    if (observed && !gobs32) { gobs32 = g->obs32; go32_stride = 0; }   // the grid's own row stays the current counter's: ev2g_grid_rollout can go on from it
     h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
     HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
     for (int i = 0; i < k_steps; i++) {
@@ -2145,16 +2204,104 @@ int ev2g_grid_run(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, 
         const StepIO io = make_io(h, act_i, 0, obs ? obs + (long long)i * o_stride : nullptr, 0, rew_i, 0,
                                   done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
         if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-        // a one-step launch leaves Transformer.current_power of its step in tr_power_now (every step kernel writes it in a launch's last step)
-        GridArgs ga{};
-        ga.p = g->p_base; ga.q = g->q_base; ga.tr_power = h->st.tr_power_now; ga.M = h->M; ga.T1 = h->T + 1; ga.t = h->current_step;
-        ga.scn_off = (int)h->scn_off; ga.n_rows = h->E; ga.vm = vm + (long long)i * v_stride; ga.reward = rew_i;
-        ga.base_weight = base_weight; ga.voltage_weight = voltage_weight;
-        if ((rc = grid_launch(h, g, ga, true))) return rc;
+        if ((rc = grid_launch_step(h, g, vm + (long long)i * v_stride, rew_i, base_weight, voltage_weight))) return rc;
         h->current_step += 1;
+        if (observed && (rc = grid_launch_state(h, g, gobs ? gobs + (long long)i * go_stride : nullptr, gobs32 + (long long)i * go32_stride))) return rc;
     }
     HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
     h->timed = true;
+    return EV2G_OK;
+}
+
+int ev2g_grid_run(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
+                  double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm, int64_t v_stride,
+                  double base_weight, double voltage_weight) {
+    return grid_run_loop(h, g, a, k_steps, actions, a_stride, obs, o_stride, reward, r_stride, done, d_stride, mask, m_stride, vm, v_stride, base_weight,
+                         voltage_weight, false, nullptr, 0, nullptr, 0, "ev2g_grid_run");
+}
+
+int ev2g_grid_run_observed(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs,
+                           int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride,
+                           double *vm, int64_t v_stride, double base_weight, double voltage_weight, double *gobs, int64_t go_stride, float *gobs32,
+                           int64_t go32_stride) {
+    return grid_run_loop(h, g, a, k_steps, actions, a_stride, obs, o_stride, reward, r_stride, done, d_stride, mask, m_stride, vm, v_stride, base_weight,
+                         voltage_weight, true, gobs, go_stride, gobs32, go32_stride, "ev2g_grid_run_observed");
+}
+
+int ev2g_grid_state_attach(ev2g_handle *h, ev2g_grid *g, const double *time_features, int per_scenario) {
+    if (int rc = grid_check(h, g, true, "ev2g_grid_state_attach")) return rc;
+    if (!time_features) return fail(h, EV2G_ERR_ARG, "ev2g_grid_state_attach: time_features is null");
+    const int Dg = 6 + 2 * g->n + 3 * h->P;
+    const size_t ED = (size_t)h->E * Dg, EP = (size_t)h->E * h->P, tfb = (size_t)(per_scenario ? h->M : 1) * (h->T + 1) * 3 * sizeof(double);
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (a second attach replaces blocks that queued kernels may still read)
+    for (void **p : {(void **)&g->tf, (void **)&g->obs, (void **)&g->act, (void **)&g->obs32, (void **)&g->act32}) { (void)hipFree(*p); *p = nullptr; }
+    g->Dg = 0; g->obs32_step = -1; g->obs32_epoch = -1;
+    int rc = grid_upload(h, time_features, tfb, (void **)&g->tf);
+    if (!rc && (hipMalloc((void **)&g->obs, ED * sizeof(double)) != hipSuccess || hipMalloc((void **)&g->obs32, ED * sizeof(float)) != hipSuccess ||
+                hipMalloc((void **)&g->act, EP * sizeof(double)) != hipSuccess || hipMalloc((void **)&g->act32, EP * sizeof(float)) != hipSuccess))
+        rc = fail(h, EV2G_ERR_HIP, "ev2g_grid_state_attach: device allocation failed");
+    if (rc) {
+        for (void **p : {(void **)&g->tf, (void **)&g->obs, (void **)&g->act, (void **)&g->obs32, (void **)&g->act32}) { (void)hipFree(*p); *p = nullptr; }
+        return rc;
+    }
+    g->tf_per_scn = per_scenario ? 1 : 0;
+    g->Dg = Dg;
+    return EV2G_OK;
+}
+
+int ev2g_grid_state_dim(ev2g_handle *h, ev2g_grid *g) {
+    if (!h || !g || std::find(h->grids.begin(), h->grids.end(), g) == h->grids.end() || !g->tf) return -1;
+    return g->Dg;
+}
+
+int ev2g_grid_observe(ev2g_handle *h, ev2g_grid *g, double *obs, float *obs32) {
+    if (int rc = grid_state_check(h, g, "ev2g_grid_observe")) return rc;
+    // the caller's blocks, and the grid's own rows (what ev2g_grid_rollout's first forward pass reads)
+    if (int rc = grid_launch_state(h, g, obs, obs32)) return rc;
+    return grid_launch_state(h, g, g->obs, g->obs32);
+}
+
+int ev2g_grid_rollout(ev2g_handle *h, ev2g_grid *g, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
+                      int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm, int64_t v_stride, double base_weight, double voltage_weight) {
+    int rc = grid_state_check(h, g, "ev2g_grid_rollout");
+    if (rc) return rc;
+    if (!m || k_steps < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0 || v_stride < 0) return fail(h, EV2G_ERR_ARG, "ev2g_grid_rollout: bad arguments");
+    if (m->dev.d_in != g->Dg || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_grid_rollout: actor shape != (grid state dim, ports)");
+    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_grid_rollout: the segment would run past the episode end");
+    if (g->obs32_step != h->current_step || g->obs32_epoch != h->state_epoch)
+        return fail(h, EV2G_ERR_STATE, "ev2g_grid_rollout: the grid's float32 row does not hold the state of step counter " + std::to_string(h->current_step) +
+                                       " (ev2g_grid_observe first; a reset or a step outside the grid's calls invalidates it)");
+    if (!reward) { reward = g->rew; r_stride = 0; }
+    if (!vm) { vm = g->vm; v_stride = 0; }
+    const long long EP = (long long)h->E * h->P;
+    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
+    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    for (int i = 0; i < k_steps; i++) {
+        if ((rc = ev2g_mlp_forward(h, m, g->obs32, g->act32, h->E))) return rc;
+        const dim3 grid((unsigned)std::min<long long>((EP + EV2G_GRID_STATE_BLOCK - 1) / EV2G_GRID_STATE_BLOCK, 1 << 20));
+        hipLaunchKernelGGL(ev2g_grid_widen_kernel, grid, dim3(EV2G_GRID_STATE_BLOCK), 0, h->stream, (const float *)g->act32, g->act, EP);
+        HIPCHK(h, hipGetLastError());
+        double *rew_i = reward + (long long)i * r_stride;
+        const StepIO io = make_io(h, g->act, 0, nullptr, 0, rew_i, 0, done ? done + (long long)i * d_stride : nullptr, 0,
+                                  mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
+        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
+        if ((rc = grid_launch_step(h, g, vm + (long long)i * v_stride, rew_i, base_weight, voltage_weight))) return rc;
+        h->current_step += 1;
+        if ((rc = grid_launch_state(h, g, nullptr, g->obs32))) return rc;
+    }
+    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
+    h->timed = true;
+    return EV2G_OK;
+}
+
+int ev2g_grid_get_stats(ev2g_handle *h, ev2g_grid *g, double *vv_sum, int32_t *vv_count, int32_t *vv_steps, double *rew_sum) {
+    if (int rc = grid_check(h, g, true, "ev2g_grid_get_stats")) return rc;
+    const size_t Ed = (size_t)h->E * sizeof(double), Ei = (size_t)h->E * sizeof(int32_t);
+    if (vv_sum) HIPCHK(h, hipMemcpyAsync(vv_sum, g->vv_sum, Ed, hipMemcpyDeviceToHost, h->stream));
+    if (vv_count) HIPCHK(h, hipMemcpyAsync(vv_count, g->vv_count, Ei, hipMemcpyDeviceToHost, h->stream));
+    if (vv_steps) HIPCHK(h, hipMemcpyAsync(vv_steps, g->vv_steps, Ei, hipMemcpyDeviceToHost, h->stream));
+    if (rew_sum) HIPCHK(h, hipMemcpyAsync(rew_sum, g->rew_sum, Ed, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return EV2G_OK;
 }
 
@@ -2234,7 +2381,7 @@ static int stats_reset_impl(ev2g_handle *h, double *stats, double *obs, float *o
     }
     h->scn_off = off;
     h->current_step = 0;
-    h->inl_stats = false; h->inl_reason = "the episode was reset";
+    h->inl_stats = false; h->inl_reason = "the episode was reset"; h->state_epoch += 1;
     return EV2G_OK;
 }
 int ev2g_get_stats_reset(ev2g_handle *h, double *stats, double *obs, int64_t scenario_offset) { return stats_reset_impl(h, stats, obs, nullptr, scenario_offset); }
@@ -2515,7 +2662,7 @@ void ev2g_host_uniform(double *dst, int64_t n, uint64_t seed, double lo, double 
 // ---- scenario generator (host only) ----
 int ev2g_gen_default_config(int kind, ev2g_gen_config *cfg) { return ev2g_gen_default_config_impl(kind, cfg); }
 int ev2g_pool_refill(ev2g_handle *h, const ev2g_gen_config *cfg, uint64_t seed, int64_t first_index, int32_t first_slot, int32_t n) {
-    if (h) { h->inl_stats = false; h->inl_reason = "scenarios were refilled since the last step launch"; }
+    if (h) { h->inl_stats = false; h->inl_reason = "scenarios were refilled since the last step launch"; h->state_epoch += 1; }
     try { return ev2g_pool_refill_impl(h, cfg, seed, first_index, first_slot, n); }
     catch (const std::exception &e) { return fail(h, EV2G_ERR_ARG, std::string("ev2g_pool_refill: ") + e.what()); }
 }

@@ -88,6 +88,12 @@ def load_library(path: Optional[str] = None):
         "ev2g_grid_destroy": (None, [vp, vp]),
         "ev2g_grid_solve": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
         "ev2g_grid_run": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, dbl, dbl]),
+        "ev2g_grid_get_stats": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "ev2g_grid_state_attach": (C.c_int, [vp, vp, vp, C.c_int]),
+        "ev2g_grid_state_dim": (C.c_int, [vp, vp]),
+        "ev2g_grid_observe": (C.c_int, [vp, vp, vp, vp]),
+        "ev2g_grid_run_observed": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, dbl, dbl, vp, i64, vp, i64]),
+        "ev2g_grid_rollout": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, dbl, dbl]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -144,7 +150,8 @@ EXPORTED_SYMBOLS = [
     "ev2g_heuristic_create", "ev2g_heuristic_destroy", "ev2g_heuristic_actions", "ev2g_heuristic_run",
     "ev2g_link_create", "ev2g_link_destroy", "ev2g_link_reset_state", "ev2g_link_actions", "ev2g_link_observe", "ev2g_link_obs_f32",
     "ev2g_link_run", "ev2g_link_rollout",
-    "ev2g_grid_create", "ev2g_grid_destroy", "ev2g_grid_solve", "ev2g_grid_run"]
+    "ev2g_grid_create", "ev2g_grid_destroy", "ev2g_grid_solve", "ev2g_grid_run",
+    "ev2g_grid_state_attach", "ev2g_grid_state_dim", "ev2g_grid_observe", "ev2g_grid_run_observed", "ev2g_grid_rollout", "ev2g_grid_get_stats"]
 
 
 def _ptr(x):
@@ -503,6 +510,49 @@ class Engine:
         self._check(self._lib.ev2g_grid_run(self._h, g, agent, int(k), _ptr(actions), int(a_stride), _ptr(obs), int(o_stride), _ptr(reward),
                                             int(r_stride), _ptr(done), int(d_stride), _ptr(mask), int(m_stride), _ptr(vm), int(v_stride),
                                             float(base_weight), float(voltage_weight)))
+
+    def grid_state_attach(self, g, time_features):
+        """Attach V2G_grid_state (rl_agent/state.py:216-278) to a grid made with profiles: time_features [T + 1, 3] (ev2gym_amd.grid.time_features;
+        every scenario of the pool starts at the same date) or [M, T + 1, 3].  Returns the row width Dg."""
+        tf = np.ascontiguousarray(time_features, np.float64)
+        if tf.shape not in ((self.T + 1, 3), (self.M, self.T + 1, 3)):
+            raise ValueError(f"grid_state_attach: time_features has shape {tf.shape}, expected {(self.T + 1, 3)} or {(self.M, self.T + 1, 3)} "
+                             "(steps + 1 rows of weekday / 7, sin, cos)")
+        self._check(self._lib.ev2g_grid_state_attach(self._h, g, tf.ctypes.data, int(tf.ndim == 3)))
+        return self.grid_state_dim(g)
+
+    def grid_state_dim(self, g) -> int:
+        """6 + 2 (n_bus - 1) + 3 P, or -1 when no state is attached to the grid."""
+        return int(self._lib.ev2g_grid_state_dim(self._h, g))
+
+    def grid_observe(self, g, obs=None, obs32=None):
+        """The V2G_grid_state rows [E, Dg] of the current step counter into the device arrays obs (float64) / obs32 (float32), and into the
+        grid's own rows (what grid_rollout starts from)."""
+        self._check(self._lib.ev2g_grid_observe(self._h, g, _ptr(obs), _ptr(obs32)))
+
+    def grid_run_observed(self, g, k, agent=None, actions=None, a_stride=0, obs=None, o_stride=0, reward=None, r_stride=0, done=None, d_stride=0,
+                          mask=None, m_stride=0, vm=None, v_stride=0, base_weight=0.0, voltage_weight=1000.0, gobs=None, go_stride=0,
+                          gobs32=None, go32_stride=0):
+        """grid_run, and after each step's power flow the V2G_grid_state rows of the next step counter into gobs [k, E, Dg] / gobs32."""
+        self._check(self._lib.ev2g_grid_run_observed(self._h, g, agent, int(k), _ptr(actions), int(a_stride), _ptr(obs), int(o_stride),
+                                                     _ptr(reward), int(r_stride), _ptr(done), int(d_stride), _ptr(mask), int(m_stride), _ptr(vm),
+                                                     int(v_stride), float(base_weight), float(voltage_weight), _ptr(gobs), int(go_stride),
+                                                     _ptr(gobs32), int(go32_stride)))
+
+    def grid_rollout(self, g, m, k, reward=None, r_stride=0, done=None, d_stride=0, mask=None, m_stride=0, vm=None, v_stride=0,
+                     base_weight=0.0, voltage_weight=1000.0):
+        """k x (actor on the grid's float32 state row -> one step -> power flow -> next state row), unfused, inside one episode; grid_observe
+        first.  The actor maps Dg -> P."""
+        self._check(self._lib.ev2g_grid_rollout(self._h, g, m, int(k), _ptr(reward), int(r_stride), _ptr(done), int(d_stride), _ptr(mask),
+                                                int(m_stride), _ptr(vm), int(v_stride), float(base_weight), float(voltage_weight)))
+
+    def grid_get_stats(self, g) -> dict:
+        """The episode's voltage statistics kept by the grid kernel, [E] host arrays: voltage_violation, voltage_violation_counter,
+        voltage_violation_counter_per_step (utilities/utils.py:69-78) and total_reward, the sum of the composed rewards."""
+        vv, rs = np.empty(self.E, np.float64), np.empty(self.E, np.float64)
+        cnt, steps = np.empty(self.E, np.int32), np.empty(self.E, np.int32)
+        self._check(self._lib.ev2g_grid_get_stats(self._h, g, vv.ctypes.data, cnt.ctypes.data, steps.ctypes.data, rs.ctypes.data))
+        return dict(voltage_violation=vv, voltage_violation_counter=cnt, voltage_violation_counter_per_step=steps, total_reward=rs)
 
     # ---- statistics / inspection ---------------------------------------------------------------
     def stats(self, out=None) -> np.ndarray:

@@ -2,7 +2,10 @@
 matrices of the Laurent power flow, the base load profiles, and a plain numpy restatement of the iteration.
 
 The device runs the iteration (csrc/ev2g_grid.h, `Engine.grid_create / grid_solve / grid_run`, `EV2GymVec(grid=...)`); everything here is host
-preparation, done once per network, and `solve_numpy`, the CPU check of the kernel.  numpy only.
+preparation, done once per network, and `solve_numpy`, the CPU check of the kernel.  numpy only.  For the grid scenario's observation and
+statistics (`EV2GymVec(state_function="V2G_grid_state", grid_start=, grid_statistics=True)`, `Engine.grid_state_attach / grid_observe /
+grid_run_observed / grid_rollout / grid_get_stats`) it holds `time_features`, `grid_state_dim`, and the numpy restatements `grid_state_numpy`
+and `voltage_statistics`.
 
     net = GridNetwork.from_files("Nodes_34.csv", "Lines_34.csv")
     p_base, q_base = net.base_profiles(load, pv)        # load / pv: [T + 1, n_bus] in kW, column 0 the slack bus
@@ -12,6 +15,9 @@ The reference samples `load` from a fitted generator (data/augmentor.pkl) that i
 arrays (PowerGrid.reset's `load_data` / `pv_data` arguments, grid.py:79-91).
 """
 from __future__ import annotations
+
+import datetime
+import math
 
 import numpy as np
 
@@ -26,6 +32,53 @@ def voltage_loss(vm):
     """sum_i min(0, 0.05 - |1 - vm_i|) over the last axis (rl_agent/reward.py:117-119)."""
     vm = np.asarray(vm, np.float64)
     return np.minimum(np.zeros_like(vm), 0.05 - np.abs(1 - vm)).sum(axis=-1)
+
+
+def time_features(start, timescale_min, T):
+    """[T + 1, 3]: weekday / 7, sin(hour / 24 * 2 pi), cos(hour / 24 * 2 pi) of sim_date at every step counter 0 .. T, the first three
+    columns of V2G_grid_state (rl_agent/state.py:222-224).  sim_date starts at `start` and advances by `timescale_min` minutes per step
+    (ev2gym_env.py:560); weekday and hour roll over at midnight."""
+    out = np.empty((int(T) + 1, 3), np.float64)
+    date = start
+    for c in range(int(T) + 1):
+        out[c] = (date.weekday() / 7, math.sin(date.hour / 24 * 2 * math.pi), math.cos(date.hour / 24 * 2 * math.pi))
+        date = date + datetime.timedelta(minutes=timescale_min)
+    return out
+
+
+def grid_state_dim(n_bus, P):
+    """Width of a V2G_grid_state row: 6 + 2 (n_bus - 1) + 3 P."""
+    return 6 + 2 * (int(n_bus) - 1) + 3 * int(P)
+
+
+def grid_state_numpy(c, T, time_row, charge_prices, power_setpoints, power_usage, p_base, q_base, port_capacity, port_departure, port_bus):
+    """One V2G_grid_state row (rl_agent/state.py:216-278) from plain arrays, for step counter c of a T-step episode: time_row [3] (a row of
+    time_features), charge_prices / power_setpoints [T], power_usage [T] (current_power_usage; read at c - 1, and as 0 at c == 0, where the
+    reference reads the last entry of a freshly zeroed array), p_base / q_base [T + 1, n] (row c is what node_active_power /
+    node_reactive_power [1:, max(c - 1, 0)] hold), and per port in reference port order the EV's current_capacity, its time_of_departure
+    and the charger's bus -- a NaN capacity marks an empty port (three zeros).  Copies and integer differences only."""
+    P = len(port_capacity)
+    n = np.asarray(p_base).shape[1]
+    row = np.zeros(6 + 2 * n + 3 * P, np.float64)
+    row[0:3] = time_row
+    row[3] = charge_prices[c] if c < T else 0.0
+    row[4] = power_setpoints[c] if c < T else 0.0
+    row[5] = power_usage[c - 1] if c > 0 else 0.0
+    row[6:6 + n] = p_base[c]
+    row[6 + n:6 + 2 * n] = q_base[c]
+    for i in range(P):
+        if not np.isnan(port_capacity[i]):
+            row[6 + 2 * n + 3 * i:9 + 2 * n + 3 * i] = (port_capacity[i], int(port_departure[i]) - c + 1, port_bus[i])
+    return row
+
+
+def voltage_statistics(vm):
+    """(voltage_violation, voltage_violation_counter, voltage_violation_counter_per_step) of get_statistics (utilities/utils.py:69-78) for
+    the node voltages vm [T, n_bus] of one episode (the reference holds them as [n_bus, T]; sums and counts do not care): the sum of
+    min(0, 0.05 - |1 - v|) over every entry, the number of entries below 0.95 or above 1.05, the number of steps with at least one."""
+    vm = np.asarray(vm, np.float64)
+    out = (vm < 0.95) | (vm > 1.05)
+    return float(np.minimum(np.zeros_like(vm), 0.05 - np.abs(1 - vm)).sum()), int(np.sum(vm < 0.95) + np.sum(vm > 1.05)), int(np.sum(np.any(out, axis=-1)))
 
 
 def _read_csv(path):

@@ -19,6 +19,8 @@ Arrays are torch CUDA tensors when torch sees the GPU (zero-copy: the engine wri
 torch's current stream -- the SB3 path), otherwise engine-owned device buffers mirrored to numpy.
 `grid=` (ev2gym_amd.grid.GridNetwork) with `grid_profiles=(load, pv)` is the reference's `simulate_grid: True` with the Laurent solver: the power
 flow runs on the device after every step (csrc/ev2g_grid.h), `node_voltage` holds the bus voltages, `grid_reward` adds the voltage term.
+With it, `state_function="V2G_grid_state"` (and `grid_start=`, the episode's starting date) makes `reset()` / `step()` return the reference's grid
+observation, built on the device by the grid, and `grid_statistics=True` fills the episode's voltage keys and `total_reward` from the device.
 Only the fused built-in state / reward functions run here; arbitrary Python callables need the single-env
 facade (`ev2gym_amd.env.EV2Gym`), which says so instead of silently falling back.
 """
@@ -53,6 +55,28 @@ def _kind(fn, table, what):
     if name in table and getattr(fn, "__module__", "").startswith("ev2gym"):
         return table[name]   # the reference's own built-in of that name
     return None
+
+
+def grid_state_setup(state_function, grid, grid_start, M, T, timescale):
+    """EV2GymVec's `state_function="V2G_grid_state"` (the string, or a function of that name such as rl_agent.state.V2G_grid_state): None when
+    another state function was asked for, else the time-feature table Engine.grid_state_attach takes -- [T + 1, 3] for one starting datetime,
+    [M, T + 1, 3] for a list of M (one per scenario of the pool).  Raises before any device is touched."""
+    name = state_function if isinstance(state_function, str) else getattr(state_function, "__name__", None)
+    if name != "V2G_grid_state":
+        if grid_start is not None:
+            raise ValueError("grid_start is the starting date of state_function='V2G_grid_state'")
+        return None
+    if grid is None:
+        raise ValueError("state_function 'V2G_grid_state' reads the grid's node powers: it is accepted only together with grid= (and grid_profiles=)")
+    import datetime
+    from .grid import time_features
+    if isinstance(grid_start, datetime.datetime):
+        return time_features(grid_start, timescale, T)
+    starts = list(grid_start) if grid_start is not None else []
+    if len(starts) != M or not all(isinstance(d, datetime.datetime) for d in starts):
+        raise ValueError(f"grid_start: a datetime, or a list of {M} datetimes (one per scenario of the pool), got "
+                         f"{'None' if grid_start is None else len(starts)}")
+    return np.stack([time_features(d, timescale, T) for d in starts])
 
 
 def grid_setup(grid, grid_profiles, grid_reward, reward_kind, E, M, T, R):
@@ -91,8 +115,13 @@ class EV2GymVec:
                  scenarios: Optional[ScenarioBatch] = None, auto_reset: bool = False, log_cs_history: bool = False, log_soc: bool = True,
                  use_torch: Optional[bool] = None, rank: int = 0, world_size: int = 1, verbose: bool = False,
                  load_from_replay_path=None, pool_factor: int = 8, resample_every: Optional[int] = None, generator: str = "native", data_dir=None, device_refill: bool = False, sorted_pool: bool = True,
-                 grid=None, grid_profiles=None, grid_reward="V2G_grid_simple_reward", **unused):
-        self.state_kind = _kind(state_function, _abi.STATE_KINDS, "state_function")
+                 grid=None, grid_profiles=None, grid_reward="V2G_grid_simple_reward", grid_start=None, grid_statistics: bool = False, **unused):
+        # V2G_grid_state is a property of the grid, not a step-kernel specialisation: the handle gets a built-in state kind whose row the
+        # step launch is never asked for, and the grid builds the observation
+        self._grid_state = (state_function if isinstance(state_function, str) else getattr(state_function, "__name__", None)) == "V2G_grid_state"
+        if self._grid_state and grid is None:
+            grid_state_setup(state_function, grid, grid_start, 0, 0, 0)   # raises
+        self.state_kind = _abi.STATE_KINDS["V2G_profit_max"] if self._grid_state else _kind(state_function, _abi.STATE_KINDS, "state_function")
         self.reward_kind = _kind(reward_function, _abi.REWARD_KINDS, "reward_function")
         if self.state_kind is None or self.reward_kind is None:
             raise NotImplementedError(
@@ -147,6 +176,7 @@ class EV2GymVec:
             n_active = min(int(num_envs), scenarios.n_envs) if num_envs and int(num_envs) > 1 else scenarios.n_envs
         self.scenarios = scenarios
         self.rank, self.world_size = rank, world_size
+        time_tab = grid_state_setup(state_function, grid, grid_start, scenarios.n_envs, scenarios.n_steps, scenarios.timescale)
         if use_torch is None:
             try:
                 import torch
@@ -177,8 +207,11 @@ class EV2GymVec:
         self.device = device
         low = -1.0 if self.v2g_enabled else 0.0
         self.action_space = Box(low, 1.0, (self.number_of_ports,))           # ev2gym_env.py:226-231
+        if self._grid_state:
+            from .grid import grid_state_dim
+            self.obs_dim = grid_state_dim(grid.n_bus, e.P)
         self.observation_space = Box(-np.inf, np.inf, (self.obs_dim,))       # ev2gym_env.py:234-238
-        self._obs = self._alloc((e.E, e.D))
+        self._obs = self._alloc((e.E, self.obs_dim))
         self._rew = self._alloc((e.E,))
         self._done = self._alloc((e.E,), np.uint8)
         self._mask = self._alloc((e.E, e.P), np.uint8)
@@ -197,8 +230,13 @@ class EV2GymVec:
             p_base, q_base, self._grid_bw, self._grid_vw = grid_setup(grid, grid_profiles, grid_reward, self.reward_kind, e.E, e.M, e.T, e.R)
             self._grid = e.grid_create(grid, (p_base, q_base))
             self._vm = self._alloc((e.E, grid.n_bus))
+            if self._grid_state:
+                assert e.grid_state_attach(self._grid, time_tab) == self.obs_dim
         elif grid_profiles is not None:
             raise ValueError("grid_profiles without grid=")
+        self.grid_statistics = bool(grid_statistics)
+        if self.grid_statistics and self._grid is None:
+            raise ValueError("grid_statistics without grid=")
         self.stats = None
         self._refill_next = e.M * max(1, world_size)   # next unused scenario index of this env's stream (every rank continues after the whole first pool)
         self._refill_stride = max(1, world_size)
@@ -297,7 +335,11 @@ class EV2GymVec:
         if self.device_refill and self._episodes > 0:
             self._refill_used_window()
         self._last_offset = offset
-        self.engine.reset(self._obs, offset=offset)
+        if self._grid_state:
+            self.engine.reset(None, offset=offset)
+            self.engine.grid_observe(self._grid, self._obs)
+        else:
+            self.engine.reset(self._obs, offset=offset)
         self._episodes += 1
         if not kwargs.get("_keep_stats"):
             self.stats = None
@@ -354,7 +396,11 @@ class EV2GymVec:
         if self.engine.current_step >= self.simulation_length:
             raise AssertionError("Episode is done, please reset the environment")   # ev2gym_env.py:343
         a = self._as_device_actions(actions)
-        if self._grid is not None:
+        if self._grid_state:
+            self.engine.grid_run_observed(self._grid, 1, None, a, 0, None, 0, self._rew, 0, self._done, 0, self._mask, 0, self._vm, 0,
+                                          self._grid_bw, self._grid_vw, self._obs, 0)
+            self.node_voltage = self._out(self._vm)
+        elif self._grid is not None:
             self.engine.grid_run(self._grid, 1, None, a, 0, self._obs, 0, self._rew, 0, self._done, 0, self._mask, 0, self._vm, 0,
                                  self._grid_bw, self._grid_vw)
             self.node_voltage = self._out(self._vm)
@@ -394,6 +440,10 @@ class EV2GymVec:
         out = {k: st[:, i] for i, k in enumerate(_abi.STAT_NAMES)}
         zero = st[:, 0] * 0
         out.update({k: zero for k in _abi.GRID_STAT_ZEROS})
+        if self.grid_statistics:
+            # the grid kernel's accumulators: the three voltage keys and the sum of the composed rewards; saved_grid_energy stays 0 (the
+            # reference allocates that array and never writes it)
+            out.update(self.engine.grid_get_stats(self._grid))
         return out
 
     def get_statistics_all_ranks(self):

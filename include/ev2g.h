@@ -513,9 +513,10 @@ int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_ste
  *    not within rounding of the tolerance;
  *  - the base profiles are the CALLER's arrays: the reference samples loads from a fitted generator (data/augmentor.pkl) that is not part of it;
  *  - the episode statistics (ev2g_get_stats' total_reward included) keep the step kernel's own reward; the composed reward is what
- *    ev2g_grid_run writes to `reward`;
+ *    ev2g_grid_run writes to `reward`, and its sum over the episode is ev2g_grid_get_stats' rew_sum;
  *  - ev2g_pool_refill does not re-draw a grid's profiles: they stay attached to the pool slots they were uploaded for.
- * Out of scope: the load-profile generator, the PandaPower solver, V2G_grid_state and V2G_grid_full_reward. */
+ * Out of scope: the load-profile generator, the PandaPower solver, V2G_grid_full_reward (it needs a per-departure term of the step kernels),
+ * saved_grid_energy (the reference never writes that array: 0) and fusing the grid or state kernels into a persistent step launch. */
 typedef struct ev2g_grid ev2g_grid;
 /* Needs loaded scenarios; freed with the handle if not before.  p_base / q_base: HOST arrays [M, T+1, n] in kW, block m for scenario m of the
  * resident pool (env e runs scenario (e + offset) mod M), row t read after step t (the reference also reads row T, after the last step) -- or
@@ -539,6 +540,40 @@ int ev2g_grid_solve(ev2g_handle *h, ev2g_grid *g, const double *p_kw, const doub
 int ev2g_grid_run(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *agent, int k_steps, double *actions, int64_t a_stride, double *obs,
                   int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride,
                   double *vm, int64_t v_stride, double base_weight, double voltage_weight);
+/* The episode's voltage statistics (get_statistics, utilities/utils.py:65-112), kept by the grid kernel of ev2g_grid_run / _run_observed /
+ * _rollout: per env the sum of loss_v over the steps run (voltage_violation), the number of (step, non-slack bus) pairs with |v| < 0.95 or
+ * |v| > 1.05 (voltage_violation_counter), the number of steps with at least one (voltage_violation_counter_per_step) and the sum of the
+ * composed rewards written to `reward` (total_reward).  The step of counter 0 overwrites them: an episode restarts them itself, and a
+ * segmented run reports what an unsplit one does.  HOST arrays [E], each may be NULL; synchronises the stream. */
+int ev2g_grid_get_stats(ev2g_handle *h, ev2g_grid *g, double *vv_sum, int32_t *vv_count, int32_t *vv_steps, double *rew_sum);
+/* ---- V2G_grid_state (rl_agent/state.py:216-278): the observation of the grid scenario, a property of a grid -- not an EV2G_STATE_* kind ----
+ * Row of env e at step counter c (0 = after reset ... T = after the last step), Dg = 6 + 2n + 3P columns, n = n_bus - 1:
+ *   0..2  weekday/7, sin(hour/24 2 pi), cos(hour/24 2 pi) of sim_date at c: time_features, a HOST table [M, T+1, 3] -- or [1, T+1, 3] with
+ *         per_scenario == 0 -- copied as it is (the engine keeps no calendar);   3  charge_prices[0, c], signed, 0 at c == T;
+ *   4  power_setpoints[c], 0 at c == T;   5  current_power_usage[c-1], 0 at c == 0;   6..6+n  p_base[scenario, c, :];   6+n..6+2n  q_base
+ *   likewise (what node_active_power / node_reactive_power [1:, max(c-1, 0)] hold: PowerGrid.step returns the NEXT row's base, grid.py:131-141);
+ *   then per port in reference port order (EV.current_capacity, time_of_departure - c + 1, the charger's transformer index) or three zeros.
+ * Copies, integer differences and constants only: bit for bit the reference's row; float32 rows are the plain conversion of the float64 ones.
+ * ev2g_grid_state_attach uploads the table and allocates the grid's own rows (EV2G_ERR_ARG for a solver-only grid); ev2g_grid_state_dim
+ * returns Dg, or -1 without an attached state. */
+int ev2g_grid_state_attach(ev2g_handle *h, ev2g_grid *g, const double *time_features, int per_scenario);
+int ev2g_grid_state_dim(ev2g_handle *h, ev2g_grid *g);
+/* The state of the handle's current step counter into obs [E,Dg] float64 and obs32 [E,Dg] float32 (DEVICE, each may be NULL) and into the
+ * grid's own rows, which ev2g_grid_rollout starts from.  Asynchronous on the handle's stream. */
+int ev2g_grid_observe(ev2g_handle *h, ev2g_grid *g, double *obs, float *obs32);
+/* ev2g_grid_run, plus after each step's power flow the state of the NEXT counter into gobs [k,E,Dg] at base + k*go_stride and gobs32
+ * likewise (DEVICE, stride 0: one block; gobs NULL: not written; gobs32 NULL: the grid's own float32 row, so that ev2g_grid_rollout can go on). */
+int ev2g_grid_run_observed(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *agent, int k_steps, double *actions, int64_t a_stride, double *obs,
+                           int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride,
+                           double *vm, int64_t v_stride, double base_weight, double voltage_weight, double *gobs, int64_t go_stride,
+                           float *gobs32, int64_t go32_stride);
+/* The policy loop on the grid scenario: k_steps x (ev2g_mlp_forward on the grid's float32 state row -> the float32 actions widened into a
+ * float64 block -> one-step launch (no step-kernel observation) -> grid kernel -> state kernel into the float32 row), inside one episode,
+ * enqueued without host round trips; reward / done / mask / vm as in ev2g_grid_run.  EV2G_ERR_ARG unless the actor maps Dg -> P;
+ * EV2G_ERR_STATE unless the grid's row holds the state of the current counter: ev2g_grid_observe (or a previous ev2g_grid_rollout / an
+ * ev2g_grid_run_observed with gobs32 NULL) wrote it and no reset or step outside these calls came after.  Timed like ev2g_step_n. */
+int ev2g_grid_rollout(ev2g_handle *h, ev2g_grid *g, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
+                      int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm, int64_t v_stride, double base_weight, double voltage_weight);
 
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);

@@ -1,8 +1,11 @@
 """Rates of the distribution grid's power flow on the device (ev2g_grid_run: a one-step launch of the step kernel, then the grid kernel, T
 times per episode) next to the same one-launch-per-step run without the grid, episodes alternating between the two, one JSON line per workload.
 
-  python tools/grid_rate.py [--workloads bus34,bus123] [--episodes 3]
+  python tools/grid_rate.py [--workloads bus34,bus123] [--episodes 3] [--state] [--rollout]
       env-steps/s from HIP-event kernel time (last_step_n_kernel_ms), and solve_numpy's env-steps/s on one CPU core for the same node powers
+      --state adds ev2g_grid_run_observed (the V2G_grid_state rows, float64 and float32, after every step) to the alternation, --rollout
+      ev2g_grid_rollout under a seeded Dg -> 64 -> 64 -> P bf16 actor (whose actions differ from the all-ones block of the other runs: its
+      figure is the chain's cost, not a like-for-like rate)
   rocprofv3 --kernel-trace --stats -d OUT/bus34 -- python tools/grid_rate.py --workloads bus34 --episodes 1 --no-cpu
       the grid kernel's share of a step's kernel time is rocprofv3's own statistics table
 
@@ -30,7 +33,7 @@ KINDS = ("V2G_profitmaxV2", "V2G_profit_max")
 WORKLOADS = {"bus34": (34, 4096), "bus123": (123, 1024)}
 
 
-def rates(workload, episodes, net_dir, cpu):
+def rates(workload, episodes, net_dir, cpu, state=False, rollout=False):
     from ev2gym_amd.engine import Engine
     from ev2gym_amd.scenario_gen import generate_native
     n_bus, E = WORKLOADS[workload]
@@ -48,7 +51,25 @@ def rates(workload, episodes, net_dir, cpu):
     acts, vm = eng.empty((E, P)).upload(np.ones((E, P))), eng.empty((E, n_bus))
     runs = (lambda: eng.step_n(T, acts, 0, obs, 0, rew, 0, done, 0, mask, 0, auto_reset=0, persistent=False),
             lambda: eng.grid_run(g, T, None, acts, 0, obs, 0, rew, 0, done, 0, mask, 0, vm, 0, 1.0, 50000.0))
-    ms = ([], [])
+    names = ["plain", "grid"]
+    if state or rollout:
+        import datetime
+        from ev2gym_amd.grid import time_features
+        Dg = eng.grid_state_attach(g, time_features(datetime.datetime(2022, 1, 17, 5, 0), eng.batch.timescale, T))
+    if state:
+        gobs, gobs32 = eng.empty((E, Dg)), eng.empty((E, Dg), np.float32)
+        runs += (lambda: eng.grid_run_observed(g, T, None, acts, 0, obs, 0, rew, 0, done, 0, mask, 0, vm, 0, 1.0, 50000.0, gobs, 0, gobs32, 0),)
+        names.append("observed")
+    if rollout:
+        from ev2gym_amd.actor import init_mlp_weights
+        mlp = eng.mlp_create(*init_mlp_weights(Dg, P, seed=9, h1=64, h2=64), out_lo=-1.0, precision="bf16")
+
+        def policy_loop():
+            eng.grid_observe(g)
+            eng.grid_rollout(g, mlp, T, rew, 0, done, 0, mask, 0, vm, 0, 1.0, 50000.0)
+        runs += (policy_loop,)
+        names.append("rollout")
+    ms = tuple([] for _ in runs)
     for i in range(episodes + 1):   # the first episode of each warms up
         for which, run in enumerate(runs):
             eng.reset()
@@ -79,7 +100,12 @@ def rates(workload, episodes, net_dir, cpu):
                           grid_env_steps_per_s=rate(grid), grid_range=[rate(max(ms[1])), rate(min(ms[1]))],
                           plain_us_per_step=round(plain * 1e3 / T, 3), grid_us_per_step=round(grid * 1e3 / T, 3),
                           grid_over_plain=round(grid / plain, 4), iterations_mean=round(float(iters.mean()), 2),
-                          iterations_range=[int(iters.min()), int(iters.max())], solve_numpy_env_steps_per_s_one_core=cpu_rate)), flush=True)
+                          iterations_range=[int(iters.min()), int(iters.max())], solve_numpy_env_steps_per_s_one_core=cpu_rate,
+                          **{f"{nm}_{k}": v for nm, m in zip(names[2:], ms[2:]) for k, v in
+                             (("env_steps_per_s", rate(statistics.median(m))), ("range", [rate(max(m)), rate(min(m))]),
+                              ("us_per_step", round(statistics.median(m) * 1e3 / T, 3)), ("over_grid", round(statistics.median(m) / grid, 4)))},
+                          grid_stats_violating_steps_mean=round(float(eng.grid_get_stats(g)["voltage_violation_counter_per_step"].mean()), 2))),
+          flush=True)
     eng.close()
 
 
@@ -89,6 +115,8 @@ if __name__ == "__main__":
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--network-dir", default=os.path.join(ROOT, "tests", "golden", "grid"))
     ap.add_argument("--no-cpu", action="store_true", help="skip solve_numpy's timing")
+    ap.add_argument("--state", action="store_true", help="also time ev2g_grid_run_observed")
+    ap.add_argument("--rollout", action="store_true", help="also time ev2g_grid_rollout")
     args = ap.parse_args()
     for w in args.workloads.split(","):
-        rates(w, args.episodes, args.network_dir, not args.no_cpu)
+        rates(w, args.episodes, args.network_dir, not args.no_cpu, args.state, args.rollout)
