@@ -167,8 +167,9 @@ struct ev2g_handle {
     int current_step = 0;
     long long state_epoch = 0;                  // counts the calls that change the envs' state (load, reset, step launches, refill): what a grid's obs32 row is valid for
     size_t lds_bytes = 0;
-    // HIP-event pairs of the last EV2G_EV_RING timed calls (ev2g_step_n / ev2g_rollout / ev2g_collect): a caller that queues several launches and
-    // reads their durations afterwards (bench.py's roofline pass) does not have to drain the stream after each one
+    // HIP-event pairs of the last EV2G_EV_RING timed calls (timed_open / timed_close: ev2g_step_n, ev2g_rollout, ev2g_collect and run_chain's
+    // callers -- ev2g_heuristic_run, ev2g_link_run / _rollout, ev2g_grid_run / _run_observed / _rollout; not ev2g_step): a caller that queues
+    // several launches and reads their durations afterwards (bench.py's roofline pass) does not have to drain the stream after each one
     hipEvent_t ev0s[EV2G_EV_RING] = {}, ev1s[EV2G_EV_RING] = {};
     int ev_slot = 0;
     bool ev_valid[EV2G_EV_RING] = {};          // the slot's closing event was recorded (a call that failed half-way leaves it false: its duration reads -1)
@@ -233,6 +234,48 @@ static int dalloc(ev2g_handle *h, std::vector<void *> &pool, size_t n, T **dst) 
 static void free_pool(std::vector<void *> &pool) {
     for (void *p : pool) (void)hipFree(p);
     pool.clear();
+}
+
+// The bracket of a timed call: timed_open takes the next slot of the event ring once the arguments are accepted, timed_close records the end
+// on the success path only -- a call that returns an error in between leaves the slot invalid (its duration reads -1) and `timed` as it was.
+static int timed_open(ev2g_handle *h) {
+    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
+    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    return EV2G_OK;
+}
+static int timed_close(ev2g_handle *h) {
+    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
+    h->timed = true;
+    return EV2G_OK;
+}
+
+// a block of per-step rows: row i starts `stride` elements after row i - 1 (0: one row, overwritten); a null block has no rows
+template <typename T>
+struct Rows {
+    T *p = nullptr;
+    long long stride = 0;
+    T *at(long long i) const { return p ? p + i * stride : nullptr; }
+};
+
+// The objects a handle owns (`list`: its heuristics, links or grids).  owned_check: the front of every *_check; owned_destroy: nothing for
+// an object the handle does not own, else out of the list, the stream drained, freed.
+template <typename T>
+static int owned_check(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T *x, const char *thing, const char *who) {
+    if (!h || !x) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (std::find((h->*list).begin(), (h->*list).end(), x) == (h->*list).end())
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the " + thing + " was not created on this handle");
+    return EV2G_OK;
+}
+template <typename T>
+static void owned_destroy(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T *x, void (*release)(T *)) {
+    if (!h || !x) return;
+    auto it = std::find((h->*list).begin(), (h->*list).end(), x);
+    if (it == (h->*list).end()) return;
+    (h->*list).erase(it);
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    release(x);
 }
 
 // dictionary entry of a ClsRec (by value, bit for bit); -1 when the dictionary is full
@@ -1072,21 +1115,29 @@ int ev2g_set_step_extras(ev2g_handle *h, const ev2g_step_extras *x) {
     return EV2G_OK;
 }
 
-// StepIO of one call: the caller's buffers plus the scenario-pool window; step0 offsets the sticky extras' step strides
-static StepIO make_io(const ev2g_handle *h, const double *actions, long long a_stride, double *obs, long long o_stride,
-                      double *reward, long long r_stride, uint8_t *done, long long d_stride, uint8_t *mask, long long m_stride,
-                      long long step0, int auto_reset) {
+// the float64 blocks of one launch: the rows of its first step, and the strides the kernel advances them by from step to step
+struct StepRows {
+    Rows<const double> actions;
+    Rows<double> obs, reward;
+    Rows<uint8_t> done, mask;
+    StepRows from(long long i) const {   // the same blocks, from row i on
+        return {{actions.at(i), actions.stride}, {obs.at(i), obs.stride}, {reward.at(i), reward.stride}, {done.at(i), done.stride}, {mask.at(i), mask.stride}};
+    }
+};
+
+// StepIO of one launch: the caller's buffers plus the scenario-pool window; step0 offsets the sticky extras' step strides
+static StepIO make_io(const ev2g_handle *h, const StepRows &r, long long step0, int auto_reset) {
     StepIO io{};
-    io.actions = actions; io.a_stride = a_stride;
-    io.obs = obs; io.o_stride = o_stride;
-    io.reward = reward; io.r_stride = r_stride;
-    io.done = done; io.d_stride = d_stride;
-    io.mask = mask; io.m_stride = m_stride;
+    io.actions = r.actions.p; io.a_stride = r.actions.stride;
+    io.obs = r.obs.p; io.o_stride = r.obs.stride;
+    io.reward = r.reward.p; io.r_stride = r.reward.stride;
+    io.done = r.done.p; io.d_stride = r.done.stride;
+    io.mask = r.mask.p; io.m_stride = r.mask.stride;
     io.scn_off = (int)h->scn_off;
     io.scn_stride = (auto_reset == EV2G_AUTO_RESET_NEXT) ? h->E % h->M : 0;
     io.step0 = (int)step0;
     io.log_soc = (h->cfg.flags & EV2G_FLAG_LOG_SOC) ? 1 : 0;
-    io.act32 = actions ? nullptr : h->extras.actions_f32;
+    io.act32 = r.actions.p ? nullptr : h->extras.actions_f32;
     io.obs32 = (h->extras.obs_f32 && h->extras.obs_f32_step_stride == 0) ? h->extras.obs_f32 : nullptr;
     return io;
 }
@@ -1223,13 +1274,42 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
     return EV2G_OK;
 }
 
+// ---- one-step launch chains ----
+// What an entry that runs k x (stages around a one-step launch) asks for, in launch order: chain_steps enqueues it, run_chain is the whole timed
+// call of a segment inside one episode (both stand below the stages they launch, behind grid_state_check).
+struct StepChain {
+    const char *who = "";   // the entry's name, for messages
+    // the step's actions: the caller's rows; an agent that writes them (no rows: into its own block); or an actor's forward pass between the
+    // float32 rows of the link or of the grid, whose fail / widen kernel makes the float64 block the step reads -- without either, between the
+    // registered hand-over pair (ev2g_set_step_extras), which the step kernel reads itself
+    Rows<double> actions;
+    ev2g_heuristic *agent = nullptr;
+    const ev2g_mlp *actor = nullptr;
+    // a link: ahead of the step the fail kernel (p_fail > 0, and always under an actor), behind it the delay kernel (p_delay > 0) or, under an
+    // actor, the plain float32 copy of the observation
+    ev2g_link *link = nullptr;
+    // a grid: behind the step the compose kernel, then (observed) the state kernel of the next step counter
+    ev2g_grid *grid = nullptr;
+    double base_weight = 0.0, voltage_weight = 0.0;
+    bool observed = false;
+    Rows<double> vm, gobs;
+    Rows<float> gobs32;
+    Rows<double> obs, reward;   // every step's outputs
+    Rows<uint8_t> done, mask;
+    int auto_reset = 0;                // an episode end inside the segment (chain_steps; run_chain refuses it up front): 0 ends the call with EV2G_ERR_DONE
+    bool a_stride_to_kernel = false;   // ev2g_step_n: StepIO::a_stride = actions.stride (the float32 action hand-over applies step0 * a_stride in the kernel)
+    bool count_steps = true;           // StepIO::step0 = the step's index in the segment, else 0
+};
+static int chain_steps(ev2g_handle *h, const StepChain &c, int k);
+static int run_chain(ev2g_handle *h, StepChain c, int k);
+
 int ev2g_step(ev2g_handle *h, const double *actions, double *obs, double *reward, uint8_t *done, uint8_t *action_mask) {
     if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_step: no scenarios loaded");
     if (!actions && !h->extras.actions_f32) return fail(h, EV2G_ERR_ARG, "ev2g_step: actions is null (and no float32 actions are set)");
     if (h->current_step >= h->T)
         return fail(h, EV2G_ERR_DONE, "ev2g_step: episode is done, reset the environment (ev2gym_env.py:343)");
     (void)hipSetDevice(h->device);
-    const StepIO io = make_io(h, actions, 0, obs, 0, reward, 0, done, 0, action_mask, 0, 0, 0);
+    const StepIO io = make_io(h, StepRows{{actions}, {obs}, {reward}, {done}, {action_mask}}, 0, 0);
     int rc = launch_steps(h, io, h->current_step, 1, 0);
     if (rc) return rc;
     h->current_step += 1;
@@ -1245,8 +1325,8 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
     (void)hipSetDevice(h->device);
     int rc = EV2G_OK;
     const long long adv = (auto_reset == EV2G_AUTO_RESET_NEXT) ? h->E % h->M : 0;   // pool offset advance per in-run reset
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    const StepRows rows{{actions, a_stride}, {obs, o_stride}, {reward, r_stride}, {done, d_stride}, {mask, m_stride}};
+    if ((rc = timed_open(h))) return rc;
     if (mode == EV2G_STEPN_PERSISTENT) {
         int k = k_steps;
         if (!auto_reset) k = std::min(k, h->T - h->current_step);
@@ -1263,22 +1343,14 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
                     if (r2) return r2;
                 }
                 const int kc = std::min(k - i0, h->T - h->current_step);
-                const StepIO io = make_io(h, actions ? actions + (long long)i0 * a_stride : nullptr, a_stride,
-                                          obs ? obs + (long long)i0 * o_stride : nullptr, o_stride,
-                                          reward ? reward + (long long)i0 * r_stride : nullptr, r_stride,
-                                          done ? done + (long long)i0 * d_stride : nullptr, d_stride,
-                                          mask ? mask + (long long)i0 * m_stride : nullptr, m_stride, i0, 0);
-                int r2 = launch_steps(h, io, h->current_step, kc, 0);
+                int r2 = launch_steps(h, make_io(h, rows.from(i0), i0, 0), h->current_step, kc, 0);
                 if (r2) return r2;
                 h->current_step += kc;
                 i0 += kc;
             }
-            HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-            h->timed = true;
-            return rc;
+            return timed_close(h);
         }
-        const StepIO io = make_io(h, actions, a_stride, obs, o_stride, reward, r_stride, done, d_stride, mask, m_stride, 0, auto_reset);
-        if (k > 0) rc = launch_steps(h, io, h->current_step, k, auto_reset);
+        if (k > 0) rc = launch_steps(h, make_io(h, rows, 0, auto_reset), h->current_step, k, auto_reset);
         if (rc) return rc;
         if (auto_reset) {
             // replay the step counter on the host: reset happens lazily before the step that follows a terminal one
@@ -1290,25 +1362,15 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
         }
         if (k < k_steps) rc = fail(h, EV2G_ERR_DONE, "ev2g_step_n: episode finished before k_steps (auto_reset off)");
     } else {
-        for (int i = 0; i < k_steps; i++) {
-            if (h->current_step >= h->T) {
-                if (!auto_reset) { rc = fail(h, EV2G_ERR_DONE, "ev2g_step_n: episode finished before k_steps (auto_reset off)"); break; }
-                int r2 = ev2g_reset_ex(h, nullptr, h->scn_off + adv);
-                if (r2) return r2;
-            }
-            const StepIO io = make_io(h, actions ? actions + (long long)i * a_stride : nullptr, a_stride,   // (float32 actions: the kernel applies step0 * a_stride)
-                                      obs ? obs + (long long)i * o_stride : nullptr, 0,
-                                      reward ? reward + (long long)i * r_stride : nullptr, 0,
-                                      done ? done + (long long)i * d_stride : nullptr, 0,
-                                      mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
-            int r2 = launch_steps(h, io, h->current_step, 1, 0);
-            if (r2) return r2;
-            h->current_step += 1;
-        }
+        StepChain c{"ev2g_step_n"};
+        c.actions = {const_cast<double *>(actions), a_stride}; c.a_stride_to_kernel = true;   // (no agent: the rows are only read)
+        c.obs = rows.obs; c.reward = rows.reward; c.done = rows.done; c.mask = rows.mask;
+        c.auto_reset = auto_reset;
+        rc = chain_steps(h, c, k_steps);
+        if (rc && rc != EV2G_ERR_DONE) return rc;   // (an episode end with auto_reset off: the steps before it are a timed call)
     }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
-    return rc;
+    const int rc2 = timed_close(h);
+    return rc2 ? rc2 : rc;
 }
 
 // ---- policy in the loop -------------------------------------------------------------------------------------------
@@ -1536,17 +1598,18 @@ static bool fused_eligible(const ev2g_handle *h, const ev2g_mlp *m) {
            !std::getenv("EV2G_NO_FUSED");
 }
 // k steps from the current one; obs0: the [E, D] float32 rows the first forward reads; obs / act / reward / done / mask: the rows of the segment's first
-// step with their step strides (elements; 0 = one row, overwritten)
-static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, int k, const float *obs0, float *obs, long long o_stride, float *act, long long a_stride,
-                        double *reward, long long r_stride, uint8_t *done, long long d_stride, uint8_t *mask, long long m_stride) {
+// step with their step strides
+static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, int k, const float *obs0, Rows<float> obs, Rows<float> act, Rows<double> reward,
+                        Rows<uint8_t> done, Rows<uint8_t> mask) {
     const DevScn &s = h->scn;
     const DevState &st = h->st;
     const long long lim = 1ll << 32;
     h->inl_stats = false; h->inl_reason = "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)"; h->state_epoch += 1;
-    if (o_stride * 4 >= lim || a_stride * 4 >= lim || r_stride * 8 >= lim || d_stride >= lim || m_stride >= lim || o_stride < 0 || a_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0)
+    if (obs.stride * 4 >= lim || act.stride * 4 >= lim || reward.stride * 8 >= lim || done.stride >= lim || mask.stride >= lim || obs.stride < 0 ||
+        act.stride < 0 || reward.stride < 0 || done.stride < 0 || mask.stride < 0)
         return fail(h, EV2G_ERR_ARG, "ev2g_collect / ev2g_rollout: a step stride is negative or reaches 4 GiB");
-    StepIO io = make_io(h, nullptr, a_stride, nullptr, o_stride, reward, r_stride, done, d_stride, mask, m_stride, 0, 0);
-    io.act32 = act; io.obs32 = obs;
+    StepIO io = make_io(h, StepRows{{nullptr, act.stride}, {nullptr, obs.stride}, reward, done, mask}, 0, 0);
+    io.act32 = act.p; io.obs32 = obs.p;
     // round 6: PublicPST envs of at most 32 ports go TWO to a wavefront (32 policy rows per workgroup)
     const int ae = (s.state_kind == EV2G_STATE_PUBLIC_PST && s.P <= 32 && m->s16_nw == 1) ? 2 : 1;
     const WaveArgs wa{s.P, s.T, s.E, s.D, s.M, st.slab_port, st.slab_port_slice, st.hist, st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, ae, ae == 1 ? s.P : 32};
@@ -1614,33 +1677,18 @@ int ev2g_rollout(ev2g_handle *h, const ev2g_mlp *m, int k_steps, double *reward,
         return fail(h, EV2G_ERR_ARG, "ev2g_rollout: register float32 observation (step stride 0) and action buffers with ev2g_set_step_extras first");
     if (m->dev.d_in != h->D || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_rollout: actor shape != (obs dim, ports)");
     (void)hipSetDevice(h->device);
-    const long long adv = (auto_reset == EV2G_AUTO_RESET_NEXT) ? h->E % h->M : 0;
-    // the k x (actor forward, env step) launches; `capturing`: no host-side reset inside (the caller made sure none is needed)
-    auto enqueue = [&](int k) -> int {
-        for (int i = 0; i < k; i++) {
-            if (h->current_step >= h->T) {
-                if (!auto_reset) return fail(h, EV2G_ERR_DONE, "ev2g_rollout: episode finished before k_steps (auto_reset off)");
-                int r2 = ev2g_reset_ex(h, nullptr, h->scn_off + adv);
-                if (r2) return r2;
-            }
-            int r2 = ev2g_mlp_forward(h, m, x.obs_f32, (float *)x.actions_f32, h->E);
-            if (r2) return r2;
-            StepIO io = make_io(h, nullptr, 0, nullptr, 0, reward ? reward + (long long)i * r_stride : nullptr, 0,
-                                done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, 0, 0);
-            if (x.cost) io.step0 = i;   // (a cost buffer may record every step; the float32 buffers do not advance)
-            r2 = launch_steps(h, io, h->current_step, 1, 0);
-            if (r2) return r2;
-            h->current_step += 1;
-        }
-        return EV2G_OK;
-    };
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    // the k x (actor forward, env step) launches: the forward pass works on the registered float32 pair, which the step reads and writes itself
+    StepChain c{"ev2g_rollout"};
+    c.actor = m;
+    c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    c.auto_reset = auto_reset;
+    c.count_steps = x.cost != nullptr;   // (a cost buffer may record every step; the float32 buffers do not advance)
+    if (int rc = timed_open(h)) return rc;
     int rc = EV2G_OK;
     static const bool use_graphs = [] { const char *e = std::getenv("EV2G_ROLLOUT_GRAPHS"); return !(e && e[0] == '0'); }();
     const bool whole = h->current_step + k_steps <= h->T;   // no episode end inside the segment: nothing but kernel launches
     if (whole && k_steps >= 1 && reward && done && mask && fused_eligible(h, m)) {   // ONE launch: the policy between the steps, inside it
-        rc = launch_fused(h, m, k_steps, x.obs_f32, x.obs_f32, 0, (float *)x.actions_f32, 0, reward, r_stride, done, d_stride, mask, m_stride);
+        rc = launch_fused(h, m, k_steps, x.obs_f32, {x.obs_f32}, {(float *)x.actions_f32}, c.reward, c.done, c.mask);
         if (rc) return rc;
         h->current_step += k_steps;
     } else
@@ -1653,7 +1701,7 @@ int ev2g_rollout(ev2g_handle *h, const ev2g_mlp *m, int k_steps, double *reward,
             const int t_before = h->current_step;
             hipGraph_t graph = nullptr;
             HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            rc = enqueue(k_steps);
+            rc = chain_steps(h, c, k_steps);   // (no episode end inside: nothing but kernel launches)
             const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
             h->current_step = t_before;
             if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -1673,11 +1721,10 @@ int ev2g_rollout(ev2g_handle *h, const ev2g_mlp *m, int k_steps, double *reward,
         h->current_step += k_steps;
         h->graph_launches++;
     } else {
-        rc = enqueue(k_steps);
+        rc = chain_steps(h, c, k_steps);
     }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
-    return rc;
+    const int rc2 = timed_close(h);   // (also behind a segment that ended early or failed in chain_steps: its launches are on the stream)
+    return rc2 ? rc2 : rc;
 }
 
 long long ev2g_rollout_graph_launches(const ev2g_handle *h) { return h ? h->graph_launches : 0; }
@@ -1699,36 +1746,35 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
     if (!direct && !(x.obs_f32 && x.actions_f32 && x.obs_f32_step_stride == 0))
         return fail(h, EV2G_ERR_ARG, "ev2g_collect: this configuration steps through the registered float32 hand-over buffers: register them with "
                                      "ev2g_set_step_extras (observation step stride 0) first");
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+    const Rows<float> obs{tr->obs, (long long)ED}, act{tr->actions, (long long)EP};
+    const Rows<double> reward{tr->reward, h->E};
+    const Rows<uint8_t> done{tr->done, h->E}, mask{tr->mask, (long long)EP};
+    if (int rc = timed_open(h)) return rc;
     if (direct && k_steps >= 1 && fused_eligible(h, m)) {   // ONE launch for the segment: rows read and written in place, the policy inside the launch
-        const int rc = launch_fused(h, m, k_steps, tr->obs, tr->obs + ED, (long long)ED, tr->actions, (long long)EP, tr->reward, h->E, tr->done, h->E, tr->mask, (long long)EP);
+        const int rc = launch_fused(h, m, k_steps, tr->obs, {obs.at(1), obs.stride}, act, reward, done, mask);
         if (rc) return rc;
         h->current_step += k_steps;
         k_steps = 0;
     }
     for (int i = 0; i < k_steps; i++) {
-        float *obs_i = tr->obs + (size_t)i * ED, *obs_n = obs_i + ED, *act_i = tr->actions + (size_t)i * EP;
+        float *obs_i = obs.at(i), *obs_n = obs.at(i + 1), *act_i = act.at(i);
+        StepIO io = make_io(h, StepRows{{}, {}, {reward.at(i)}, {done.at(i)}, {mask.at(i)}}, 0, 0);
         int rc;
         if (direct) {
             if ((rc = ev2g_mlp_forward(h, m, obs_i, act_i, h->E))) return rc;
-            StepIO io = make_io(h, nullptr, 0, nullptr, 0, tr->reward + (size_t)i * h->E, 0, tr->done + (size_t)i * h->E, 0, tr->mask + (size_t)i * EP, 0, 0, 0);
             io.act32 = act_i; io.obs32 = obs_n;
             if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
             if (h->last_spec <= 0) return fail(h, EV2G_ERR_STATE, "ev2g_collect: internal: the direct path needs the full instantiation");
         } else {
             if (i == 0) HIPCHK(h, hipMemcpyAsync(x.obs_f32, obs_i, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
             if ((rc = ev2g_mlp_forward(h, m, x.obs_f32, (float *)x.actions_f32, h->E))) return rc;
-            StepIO io = make_io(h, nullptr, 0, nullptr, 0, tr->reward + (size_t)i * h->E, 0, tr->done + (size_t)i * h->E, 0, tr->mask + (size_t)i * EP, 0, 0, 0);
             if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
             HIPCHK(h, hipMemcpyAsync(act_i, x.actions_f32, EP * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
             HIPCHK(h, hipMemcpyAsync(obs_n, x.obs_f32, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         }
         h->current_step += 1;
     }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
-    return EV2G_OK;
+    return timed_close(h);
 }
 
 // ---- env-reading heuristic agents (ev2g_heuristic.h) ----
@@ -1776,21 +1822,10 @@ int ev2g_heuristic_create(ev2g_handle *h, int kind, ev2g_heuristic **out) {
     return EV2G_OK;
 }
 
-void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a) {
-    if (!h || !a) return;
-    auto it = std::find(h->heuristics.begin(), h->heuristics.end(), a);
-    if (it == h->heuristics.end()) return;
-    h->heuristics.erase(it);
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    heuristic_free(a);
-}
+void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a) { owned_destroy(h, &ev2g_handle::heuristics, a, heuristic_free); }
 
 static int heuristic_check(ev2g_handle *h, ev2g_heuristic *a, const char *who) {
-    if (!h || !a) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
-    if (std::find(h->heuristics.begin(), h->heuristics.end(), a) == h->heuristics.end())
-        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the heuristic was not created on this handle");
+    if (int rc = owned_check(h, &ev2g_handle::heuristics, a, "heuristic", who)) return rc;
     if (a->E != h->E || a->P != h->P)
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports differ from those the heuristic was created for");
     return heuristic_shape_check(h, a->kind, who);
@@ -1842,28 +1877,11 @@ int ev2g_heuristic_actions(ev2g_handle *h, ev2g_heuristic *a, double *actions) {
 
 int ev2g_heuristic_run(ev2g_handle *h, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
                        double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride) {
-    int rc = heuristic_check(h, a, "ev2g_heuristic_run");
-    if (rc) return rc;
-    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0)
-        return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_run: negative step count or stride");
-    // the engine resets lazily inside the step launch after an episode end, so the agent's launch for the new episode's first step
-    // would read the finished episode's ports: segments stay inside one episode, the caller resets in between
-    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_heuristic_run: the segment would run past the episode end");
-    if (!actions) { actions = a->act; a_stride = 0; }
-    (void)hipSetDevice(h->device);
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
-    for (int i = 0; i < k_steps; i++) {
-        double *act_i = actions + (long long)i * a_stride;
-        if ((rc = heuristic_launch(h, a, act_i))) return rc;
-        const StepIO io = make_io(h, act_i, 0, obs ? obs + (long long)i * o_stride : nullptr, 0, reward ? reward + (long long)i * r_stride : nullptr, 0,
-                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
-        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-        h->current_step += 1;
-    }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
-    return EV2G_OK;
+    if (int rc = heuristic_check(h, a, "ev2g_heuristic_run")) return rc;
+    StepChain c{"ev2g_heuristic_run"};
+    c.agent = a; c.actions = {actions, a_stride};
+    c.obs = {obs, o_stride}; c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    return run_chain(h, c, k_steps);
 }
 
 // ---- communication-fault links (ev2g_link.h) ----
@@ -1905,21 +1923,10 @@ int ev2g_link_create(ev2g_handle *h, double p_fail, double p_delay, uint64_t see
     return EV2G_OK;
 }
 
-void ev2g_link_destroy(ev2g_handle *h, ev2g_link *l) {
-    if (!h || !l) return;
-    auto it = std::find(h->links.begin(), h->links.end(), l);
-    if (it == h->links.end()) return;
-    h->links.erase(it);
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    link_free(l);
-}
+void ev2g_link_destroy(ev2g_handle *h, ev2g_link *l) { owned_destroy(h, &ev2g_handle::links, l, link_free); }
 
 static int link_check(ev2g_handle *h, ev2g_link *l, const char *who) {
-    if (!h || !l) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
-    if (std::find(h->links.begin(), h->links.end(), l) == h->links.end())
-        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the link was not created on this handle");
+    if (int rc = owned_check(h, &ev2g_handle::links, l, "link", who)) return rc;
     if (l->E != h->E || l->P != h->P || l->T != h->T)
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports / steps differ from those the link was created for");
     (void)hipSetDevice(h->device);
@@ -1991,29 +1998,11 @@ int ev2g_link_run(ev2g_handle *h, ev2g_link *l, ev2g_heuristic *a, int k_steps, 
     int rc = link_check(h, l, "ev2g_link_run");
     if (rc) return rc;
     if (a && (rc = heuristic_check(h, a, "ev2g_link_run"))) return rc;
-    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0)
-        return fail(h, EV2G_ERR_ARG, "ev2g_link_run: negative step count or stride");
-    if (!a && !actions) return fail(h, EV2G_ERR_ARG, "ev2g_link_run: without an agent the raw actions are read from `actions`");
-    // (as ev2g_heuristic_run: the agent's launch for a new episode's first step would read the finished episode's ports)
-    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_link_run: the segment would run past the episode end");
-    const bool f_on = l->p_fail > 0.0, d_on = l->p_delay > 0.0;
-    if (a && !actions) { if ((rc = link_buffer(h, (void **)&l->raw, (size_t)l->E * l->P * sizeof(double)))) return rc; actions = l->raw; a_stride = 0; }
-    if (d_on && !obs) { if ((rc = link_buffer(h, (void **)&l->obs, (size_t)l->E * h->D * sizeof(double)))) return rc; obs = l->obs; o_stride = 0; }
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
-    for (int i = 0; i < k_steps; i++) {
-        double *raw_i = actions + (long long)i * a_stride, *obs_i = obs ? obs + (long long)i * o_stride : nullptr;
-        if (a && (rc = heuristic_launch(h, a, raw_i))) return rc;
-        if (f_on && (rc = link_launch_act(h, l, h->current_step, raw_i, false, nullptr))) return rc;
-        const StepIO io = make_io(h, f_on ? l->held : raw_i, 0, obs_i, 0, reward ? reward + (long long)i * r_stride : nullptr, 0,
-                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
-        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-        h->current_step += 1;
-        if (d_on && (rc = link_launch_obs(h, l, h->current_step, obs_i, nullptr))) return rc;
-    }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
-    return EV2G_OK;
+    StepChain c{"ev2g_link_run"};
+    c.agent = a; c.actions = {actions, a_stride};
+    c.link = l;
+    c.obs = {obs, o_stride}; c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    return run_chain(h, c, k_steps);
 }
 
 int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
@@ -2022,32 +2011,11 @@ int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_ste
     if (rc) return rc;
     if (!m || k_steps < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0) return fail(h, EV2G_ERR_ARG, "ev2g_link_rollout: bad arguments");
     if (m->dev.d_in != h->D || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_link_rollout: actor shape != (obs dim, ports)");
-    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_link_rollout: the segment would run past the episode end");
-    const size_t ED = (size_t)l->E * h->D, EP = (size_t)l->E * l->P;
-    if ((rc = link_buffer(h, (void **)&l->obs, ED * sizeof(double))) || (rc = link_buffer(h, (void **)&l->obs32, ED * sizeof(float))) ||
-        (rc = link_buffer(h, (void **)&l->act32, EP * sizeof(float)))) return rc;
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
-    for (int i = 0; i < k_steps; i++) {
-        if ((rc = ev2g_mlp_forward(h, m, l->obs32, l->act32, l->E))) return rc;
-        // (the fail kernel also widens the policy's float32 row into the float64 block the step reads: it runs for p_fail = 0 too, where it
-        // holds nothing and draws no uniform)
-        if ((rc = link_launch_act(h, l, h->current_step, l->act32, true, nullptr))) return rc;
-        const StepIO io = make_io(h, l->held, 0, l->obs, 0, reward ? reward + (long long)i * r_stride : nullptr, 0,
-                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
-        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-        h->current_step += 1;
-        if (l->p_delay > 0.0) {
-            if ((rc = link_launch_obs(h, l, h->current_step, l->obs, l->obs32))) return rc;
-        } else {
-            const dim3 grid((unsigned)std::min<size_t>((ED + EV2G_LINK_BLOCK - 1) / EV2G_LINK_BLOCK, 1 << 20));
-            hipLaunchKernelGGL(ev2g_link_f32_kernel, grid, dim3(EV2G_LINK_BLOCK), 0, h->stream, (const double *)l->obs, l->obs32, (long long)ED);
-            HIPCHK(h, hipGetLastError());
-        }
-    }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
-    return EV2G_OK;
+    StepChain c{"ev2g_link_rollout"};
+    c.actor = m;
+    c.link = l;
+    c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    return run_chain(h, c, k_steps);
 }
 
 // ---- distribution grid: the Laurent power flow after each step (ev2g_grid.h) ----
@@ -2101,21 +2069,10 @@ int ev2g_grid_create(ev2g_handle *h, int n_bus, const double *K, const double *L
     return EV2G_OK;
 }
 
-void ev2g_grid_destroy(ev2g_handle *h, ev2g_grid *g) {
-    if (!h || !g) return;
-    auto it = std::find(h->grids.begin(), h->grids.end(), g);
-    if (it == h->grids.end()) return;
-    h->grids.erase(it);
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    grid_free(g);
-}
+void ev2g_grid_destroy(ev2g_handle *h, ev2g_grid *g) { owned_destroy(h, &ev2g_handle::grids, g, grid_free); }
 
 static int grid_check(ev2g_handle *h, ev2g_grid *g, bool run, const char *who) {
-    if (!h || !g) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
-    if (std::find(h->grids.begin(), h->grids.end(), g) == h->grids.end())
-        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the grid was not created on this handle");
+    if (int rc = owned_check(h, &ev2g_handle::grids, g, "grid", who)) return rc;
     if (run) {
         if (!g->p_base) return fail(h, EV2G_ERR_ARG, std::string(who) + ": the grid was created without base profiles (a solver only)");
         if (g->E != h->E || g->T != h->T || g->M != h->M || g->n != h->R)
@@ -2179,53 +2136,114 @@ static int grid_state_check(ev2g_handle *h, ev2g_grid *g, const char *who) {
     return EV2G_OK;
 }
 
-// ev2g_grid_run and ev2g_grid_run_observed: k_steps x ([agent ->] one-step launch -> grid kernel [-> state kernel of the next counter])
-static int grid_run_loop(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
-                         double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm,
-                         int64_t v_stride, double base_weight, double voltage_weight, bool observed, double *gobs, int64_t go_stride, float *gobs32,
-                         int64_t go32_stride, const char *who) {
-    int rc = observed ? grid_state_check(h, g, who) : grid_check(h, g, true, who);
-    if (rc) return rc;
-    if (a && (rc = heuristic_check(h, a, who))) return rc;
-    if (k_steps < 0 || a_stride < 0 || o_stride < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0 || v_stride < 0 || go_stride < 0 || go32_stride < 0)
-        return fail(h, EV2G_ERR_ARG, std::string(who) + ": negative step count or stride");
-    if (!a && !actions) return fail(h, EV2G_ERR_ARG, std::string(who) + ": without an agent the actions are read from `actions`");
-    // (as ev2g_heuristic_run: segments stay inside one episode)
-    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, std::string(who) + ": the segment would run past the episode end");
-    if (a && !actions) { actions = a->act; a_stride = 0; }
-    if (!reward) { reward = g->rew; r_stride = 0; }
-    if (!vm) { vm = g->vm; v_stride = 0; }
-    if (observed && !gobs32) { gobs32 = g->obs32; go32_stride = 0; }   // the grid's own row stays the current counter's: ev2g_grid_rollout can go on from it
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
-    for (int i = 0; i < k_steps; i++) {
-        double *act_i = actions + (long long)i * a_stride, *rew_i = reward + (long long)i * r_stride;
-        if (a && (rc = heuristic_launch(h, a, act_i))) return rc;
-        const StepIO io = make_io(h, act_i, 0, obs ? obs + (long long)i * o_stride : nullptr, 0, rew_i, 0,
-                                  done ? done + (long long)i * d_stride : nullptr, 0, mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
+// ---- the runner of one-step launch chains (StepChain) ----
+// k x ([agent | actor [-> widen]] [-> fail kernel] -> one-step launch [-> grid kernel] -> the step counter advances [-> delay kernel | float32
+// copy] [-> state kernel of the next counter]).  Nothing but launches while no episode ends inside: ev2g_rollout captures it into a graph.
+static int chain_steps(ev2g_handle *h, const StepChain &c, int k) {
+    ev2g_link *l = c.link; ev2g_grid *g = c.grid;
+    const long long adv = (c.auto_reset == EV2G_AUTO_RESET_NEXT) ? h->E % h->M : 0;   // pool offset advance per in-run reset
+    const long long ED = (long long)h->E * h->D, EP = (long long)h->E * h->P;
+    int rc;
+    for (int i = 0; i < k; i++) {
+        if (h->current_step >= h->T) {
+            if (!c.auto_reset) return fail(h, EV2G_ERR_DONE, std::string(c.who) + ": episode finished before k_steps (auto_reset off)");
+            if ((rc = ev2g_reset_ex(h, nullptr, h->scn_off + adv))) return rc;
+        }
+        const double *act_i = c.actions.at(i);   // what the step reads; null: the registered float32 actions
+        if (c.agent && (rc = heuristic_launch(h, c.agent, c.actions.at(i)))) return rc;
+        if (c.actor) {   // (it reads the object's OWN float32 row: an entry under an actor leaves obs / gobs32 to run_chain's defaults, which write it)
+            const float *in32 = l ? l->obs32 : g ? g->obs32 : h->extras.obs_f32;
+            float *out32 = l ? l->act32 : g ? g->act32 : (float *)h->extras.actions_f32;
+            if ((rc = ev2g_mlp_forward(h, c.actor, in32, out32, h->E))) return rc;
+            if (g) {
+                const dim3 grid((unsigned)std::min<long long>((EP + EV2G_GRID_STATE_BLOCK - 1) / EV2G_GRID_STATE_BLOCK, 1 << 20));
+                hipLaunchKernelGGL(ev2g_grid_widen_kernel, grid, dim3(EV2G_GRID_STATE_BLOCK), 0, h->stream, (const float *)g->act32, g->act, EP);
+                HIPCHK(h, hipGetLastError());
+                act_i = g->act;
+            }
+        }
+        if (l && (c.actor || l->p_fail > 0.0)) {
+            // (under an actor the fail kernel also widens the policy's float32 row into the float64 block the step reads: it runs for
+            // p_fail = 0 too, where it holds nothing and draws no uniform)
+            if ((rc = link_launch_act(h, l, h->current_step, c.actor ? (const void *)l->act32 : (const void *)act_i, c.actor != nullptr, nullptr))) return rc;
+            act_i = l->held;
+        }
+        const StepIO io = make_io(h, StepRows{{act_i, c.a_stride_to_kernel ? c.actions.stride : 0}, {c.obs.at(i)}, {c.reward.at(i)}, {c.done.at(i)}, {c.mask.at(i)}},
+                                  c.count_steps ? i : 0, 0);
         if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-        if ((rc = grid_launch_step(h, g, vm + (long long)i * v_stride, rew_i, base_weight, voltage_weight))) return rc;
+        if (g && (rc = grid_launch_step(h, g, c.vm.at(i), c.reward.at(i), c.base_weight, c.voltage_weight))) return rc;
         h->current_step += 1;
-        if (observed && (rc = grid_launch_state(h, g, gobs ? gobs + (long long)i * go_stride : nullptr, gobs32 + (long long)i * go32_stride))) return rc;
+        if (l && l->p_delay > 0.0) {
+            if ((rc = link_launch_obs(h, l, h->current_step, c.obs.at(i), c.actor ? l->obs32 : nullptr))) return rc;
+        } else if (l && c.actor) {
+            const dim3 grid((unsigned)std::min<long long>((ED + EV2G_LINK_BLOCK - 1) / EV2G_LINK_BLOCK, 1 << 20));
+            hipLaunchKernelGGL(ev2g_link_f32_kernel, grid, dim3(EV2G_LINK_BLOCK), 0, h->stream, (const double *)c.obs.at(i), l->obs32, ED);
+            HIPCHK(h, hipGetLastError());
+        }
+        if (g && c.observed && (rc = grid_launch_state(h, g, c.gobs.at(i), c.gobs32.at(i)))) return rc;
     }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
     return EV2G_OK;
+}
+
+// The timed call of a segment inside one episode: the checks every such entry makes (behind its own), the agent's, the link's and the grid's
+// own blocks where the caller passes none, the bracket, the steps.
+static int run_chain(ev2g_handle *h, StepChain c, int k) {
+    const std::string who = c.who;
+    ev2g_link *l = c.link; ev2g_grid *g = c.grid;
+    if (k < 0 || c.actions.stride < 0 || c.obs.stride < 0 || c.reward.stride < 0 || c.done.stride < 0 || c.mask.stride < 0 || c.vm.stride < 0 ||
+        c.gobs.stride < 0 || c.gobs32.stride < 0)
+        return fail(h, EV2G_ERR_ARG, who + ": negative step count or stride");
+    if (!c.agent && !c.actor && !c.actions.p) return fail(h, EV2G_ERR_ARG, who + ": without an agent the " + (l ? "raw " : "") + "actions are read from `actions`");
+    // the engine resets lazily inside the step launch after an episode end, so an agent's launch for the new episode's first step would
+    // read the finished episode's ports: segments stay inside one episode, the caller resets in between
+    if (h->current_step + k > h->T) return fail(h, EV2G_ERR_DONE, who + ": the segment would run past the episode end");
+    if (c.actor && g && !l && (g->obs32_step != h->current_step || g->obs32_epoch != h->state_epoch))
+        return fail(h, EV2G_ERR_STATE, who + ": the grid's float32 row does not hold the state of step counter " + std::to_string(h->current_step) +
+                                       " (ev2g_grid_observe first; a reset or a step outside the grid's calls invalidates it)");
+    int rc;
+    if (l) {   // (the link's blocks are allocated on first use)
+        const size_t ED = (size_t)l->E * h->D, EP = (size_t)l->E * l->P;
+        if (c.agent && !c.actions.p) { if ((rc = link_buffer(h, (void **)&l->raw, EP * sizeof(double)))) return rc; c.actions = {l->raw}; }
+        if ((c.actor || l->p_delay > 0.0) && !c.obs.p) { if ((rc = link_buffer(h, (void **)&l->obs, ED * sizeof(double)))) return rc; c.obs = {l->obs}; }
+        if (c.actor && ((rc = link_buffer(h, (void **)&l->obs32, ED * sizeof(float))) || (rc = link_buffer(h, (void **)&l->act32, EP * sizeof(float))))) return rc;
+    }
+    if (c.agent && !c.actions.p) c.actions = {c.agent->act};
+    if (g) {
+        if (!c.reward.p) c.reward = {g->rew};
+        if (!c.vm.p) c.vm = {g->vm};
+        if (c.observed && !c.gobs32.p) c.gobs32 = {g->obs32};   // the grid's own row stays the current counter's: ev2g_grid_rollout can go on from it
+    }
+    (void)hipSetDevice(h->device);
+    if ((rc = timed_open(h)) || (rc = chain_steps(h, c, k))) return rc;
+    return timed_close(h);
 }
 
 int ev2g_grid_run(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs, int64_t o_stride,
                   double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm, int64_t v_stride,
                   double base_weight, double voltage_weight) {
-    return grid_run_loop(h, g, a, k_steps, actions, a_stride, obs, o_stride, reward, r_stride, done, d_stride, mask, m_stride, vm, v_stride, base_weight,
-                         voltage_weight, false, nullptr, 0, nullptr, 0, "ev2g_grid_run");
+    int rc = grid_check(h, g, true, "ev2g_grid_run");
+    if (rc) return rc;
+    if (a && (rc = heuristic_check(h, a, "ev2g_grid_run"))) return rc;
+    StepChain c{"ev2g_grid_run"};
+    c.agent = a; c.actions = {actions, a_stride};
+    c.grid = g; c.base_weight = base_weight; c.voltage_weight = voltage_weight; c.vm = {vm, v_stride};
+    c.obs = {obs, o_stride}; c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    return run_chain(h, c, k_steps);
 }
 
 int ev2g_grid_run_observed(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *a, int k_steps, double *actions, int64_t a_stride, double *obs,
                            int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride,
                            double *vm, int64_t v_stride, double base_weight, double voltage_weight, double *gobs, int64_t go_stride, float *gobs32,
                            int64_t go32_stride) {
-    return grid_run_loop(h, g, a, k_steps, actions, a_stride, obs, o_stride, reward, r_stride, done, d_stride, mask, m_stride, vm, v_stride, base_weight,
-                         voltage_weight, true, gobs, go_stride, gobs32, go32_stride, "ev2g_grid_run_observed");
+    int rc = grid_state_check(h, g, "ev2g_grid_run_observed");
+    if (rc) return rc;
+    if (a && (rc = heuristic_check(h, a, "ev2g_grid_run_observed"))) return rc;
+    StepChain c{"ev2g_grid_run_observed"};
+    c.agent = a; c.actions = {actions, a_stride};
+    c.grid = g; c.base_weight = base_weight; c.voltage_weight = voltage_weight; c.vm = {vm, v_stride};
+    c.observed = true; c.gobs = {gobs, go_stride}; c.gobs32 = {gobs32, go32_stride};
+    c.obs = {obs, o_stride}; c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    return run_chain(h, c, k_steps);
 }
 
 int ev2g_grid_state_attach(ev2g_handle *h, ev2g_grid *g, const double *time_features, int per_scenario) {
@@ -2267,31 +2285,12 @@ int ev2g_grid_rollout(ev2g_handle *h, ev2g_grid *g, const ev2g_mlp *m, int k_ste
     if (rc) return rc;
     if (!m || k_steps < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0 || v_stride < 0) return fail(h, EV2G_ERR_ARG, "ev2g_grid_rollout: bad arguments");
     if (m->dev.d_in != g->Dg || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_grid_rollout: actor shape != (grid state dim, ports)");
-    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_grid_rollout: the segment would run past the episode end");
-    if (g->obs32_step != h->current_step || g->obs32_epoch != h->state_epoch)
-        return fail(h, EV2G_ERR_STATE, "ev2g_grid_rollout: the grid's float32 row does not hold the state of step counter " + std::to_string(h->current_step) +
-                                       " (ev2g_grid_observe first; a reset or a step outside the grid's calls invalidates it)");
-    if (!reward) { reward = g->rew; r_stride = 0; }
-    if (!vm) { vm = g->vm; v_stride = 0; }
-    const long long EP = (long long)h->E * h->P;
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
-    for (int i = 0; i < k_steps; i++) {
-        if ((rc = ev2g_mlp_forward(h, m, g->obs32, g->act32, h->E))) return rc;
-        const dim3 grid((unsigned)std::min<long long>((EP + EV2G_GRID_STATE_BLOCK - 1) / EV2G_GRID_STATE_BLOCK, 1 << 20));
-        hipLaunchKernelGGL(ev2g_grid_widen_kernel, grid, dim3(EV2G_GRID_STATE_BLOCK), 0, h->stream, (const float *)g->act32, g->act, EP);
-        HIPCHK(h, hipGetLastError());
-        double *rew_i = reward + (long long)i * r_stride;
-        const StepIO io = make_io(h, g->act, 0, nullptr, 0, rew_i, 0, done ? done + (long long)i * d_stride : nullptr, 0,
-                                  mask ? mask + (long long)i * m_stride : nullptr, 0, i, 0);
-        if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-        if ((rc = grid_launch_step(h, g, vm + (long long)i * v_stride, rew_i, base_weight, voltage_weight))) return rc;
-        h->current_step += 1;
-        if ((rc = grid_launch_state(h, g, nullptr, g->obs32))) return rc;
-    }
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
-    return EV2G_OK;
+    StepChain c{"ev2g_grid_rollout"};
+    c.actor = m;
+    c.grid = g; c.base_weight = base_weight; c.voltage_weight = voltage_weight; c.vm = {vm, v_stride};
+    c.observed = true;   // (into the grid's own float32 row: the next forward pass reads it)
+    c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    return run_chain(h, c, k_steps);
 }
 
 int ev2g_grid_get_stats(ev2g_handle *h, ev2g_grid *g, double *vv_sum, int32_t *vv_count, int32_t *vv_steps, double *rew_sum) {
