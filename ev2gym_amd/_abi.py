@@ -52,6 +52,12 @@ AGENT_KINDS = {   # every agent ev2g_heuristic_create knows: the three above and
     "RoundRobin_GF": 4,                             # baselines/heuristics.py:270-399  (one port per charger)
     "RoundRobin_GF_off_allowed": 5,                 # baselines/heuristics.py:402-530  (one port per charger)
 }
+WRAP_KINDS = {   # the reference's action wrappers run on the device (ev2g_wrap_create), by class name
+    "BinaryAction": 0,                              # rl_agent/action_wrappers.py:8-47
+    "ThreeStep_Action": 1,                          # rl_agent/action_wrappers.py:50-90
+    "ThreeStep_Action_DiscreteActionSpace": 1,      # rl_agent/action_wrappers.py:93-138  (the same action())
+    "Rescale_RepairLayer": 2,                       # rl_agent/action_wrappers.py:159-451  (one port per charger)
+}
 AUTO_RESET_SAME = 1
 AUTO_RESET_NEXT = 2
 

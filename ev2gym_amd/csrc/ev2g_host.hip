@@ -26,6 +26,7 @@
 #include "ev2g_heuristic.h"
 #include "ev2g_link.h"
 #include "ev2g_grid.h"
+#include "ev2g_wrap.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -95,6 +96,20 @@ static void grid_free(ev2g_grid *g) {
                     (void *)g->vv_count, (void *)g->vv_steps, (void *)g->tf, (void *)g->obs, (void *)g->act, (void *)g->obs32, (void *)g->act32})
         (void)hipFree(p);
     delete g;
+}
+
+// an action wrapper (ev2g_wrap_create, ev2g_wrap.h): its kind, the shape it was made for, Rescale_RepairLayer's queue of every env with each
+// entry's min_power / max_power, and the float64 block the step reads when the caller passes no `wrapped` rows
+struct ev2g_wrap {
+    int kind = 0, E = 0, P = 0;
+    int *queue = nullptr, *qlen = nullptr;   // [E, P], [E]
+    double *qmin = nullptr, *qmax = nullptr; // [E, P] each
+    double *act = nullptr;                   // [E, P]
+};
+
+static void wrap_free(ev2g_wrap *w) {
+    (void)hipFree(w->queue); (void)hipFree(w->qlen); (void)hipFree(w->qmin); (void)hipFree(w->qmax); (void)hipFree(w->act);
+    delete w;
 }
 
 #define EV2G_EV_RING 32
@@ -194,6 +209,7 @@ struct ev2g_handle {
     std::vector<ev2g_heuristic *> heuristics;
     std::vector<ev2g_link *> links;             // the communication-fault links created on this handle (freed with it)
     std::vector<ev2g_grid *> grids;             // the distribution grids created on this handle (freed with it)
+    std::vector<ev2g_wrap *> wraps;             // the action wrappers created on this handle (freed with it)
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -361,6 +377,8 @@ void ev2g_destroy(ev2g_handle *h) {
     h->links.clear();
     for (ev2g_grid *g : h->grids) grid_free(g);
     h->grids.clear();
+    for (ev2g_wrap *w : h->wraps) wrap_free(w);
+    h->wraps.clear();
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
     for (int i = 0; i < EV2G_EV_RING; i++) { if (h->ev0s[i]) (void)hipEventDestroy(h->ev0s[i]); if (h->ev1s[i]) (void)hipEventDestroy(h->ev1s[i]); }
@@ -1294,6 +1312,10 @@ struct StepChain {
     bool observed = false;
     Rows<double> vm, gobs;
     Rows<float> gobs32;
+    // an action wrapper (not with a link or a grid): between the action source and the step, from the caller's row -- under an actor from the
+    // registered float32 action row -- into the wrapper's own float64 block or the caller's `wrapped` row, which the step then reads
+    ev2g_wrap *wrap = nullptr;
+    Rows<double> wrapped;
     Rows<double> obs, reward;   // every step's outputs
     Rows<uint8_t> done, mask;
     int auto_reset = 0;                // an episode end inside the segment (chain_steps; run_chain refuses it up front): 0 ends the call with EV2G_ERR_DONE
@@ -1302,6 +1324,7 @@ struct StepChain {
 };
 static int chain_steps(ev2g_handle *h, const StepChain &c, int k);
 static int run_chain(ev2g_handle *h, StepChain c, int k);
+static int wrap_launch(ev2g_handle *h, ev2g_wrap *w, const void *in, bool in32, double *out);
 
 int ev2g_step(ev2g_handle *h, const double *actions, double *obs, double *reward, uint8_t *done, uint8_t *action_mask) {
     if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_step: no scenarios loaded");
@@ -2137,7 +2160,7 @@ static int grid_state_check(ev2g_handle *h, ev2g_grid *g, const char *who) {
 }
 
 // ---- the runner of one-step launch chains (StepChain) ----
-// k x ([agent | actor [-> widen]] [-> fail kernel] -> one-step launch [-> grid kernel] -> the step counter advances [-> delay kernel | float32
+// k x ([agent | actor [-> widen]] [-> fail kernel | action wrapper] -> one-step launch [-> grid kernel] -> the step counter advances [-> delay kernel | float32
 // copy] [-> state kernel of the next counter]).  Nothing but launches while no episode ends inside: ev2g_rollout captures it into a graph.
 static int chain_steps(ev2g_handle *h, const StepChain &c, int k) {
     ev2g_link *l = c.link; ev2g_grid *g = c.grid;
@@ -2168,6 +2191,11 @@ static int chain_steps(ev2g_handle *h, const StepChain &c, int k) {
             if ((rc = link_launch_act(h, l, h->current_step, c.actor ? (const void *)l->act32 : (const void *)act_i, c.actor != nullptr, nullptr))) return rc;
             act_i = l->held;
         }
+        if (c.wrap) {
+            double *out = c.wrapped.p ? c.wrapped.at(i) : c.wrap->act;
+            if ((rc = wrap_launch(h, c.wrap, c.actor ? h->extras.actions_f32 : (const void *)act_i, c.actor != nullptr, out))) return rc;
+            act_i = out;
+        }
         const StepIO io = make_io(h, StepRows{{act_i, c.a_stride_to_kernel ? c.actions.stride : 0}, {c.obs.at(i)}, {c.reward.at(i)}, {c.done.at(i)}, {c.mask.at(i)}},
                                   c.count_steps ? i : 0, 0);
         if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
@@ -2191,7 +2219,7 @@ static int run_chain(ev2g_handle *h, StepChain c, int k) {
     const std::string who = c.who;
     ev2g_link *l = c.link; ev2g_grid *g = c.grid;
     if (k < 0 || c.actions.stride < 0 || c.obs.stride < 0 || c.reward.stride < 0 || c.done.stride < 0 || c.mask.stride < 0 || c.vm.stride < 0 ||
-        c.gobs.stride < 0 || c.gobs32.stride < 0)
+        c.gobs.stride < 0 || c.gobs32.stride < 0 || c.wrapped.stride < 0)
         return fail(h, EV2G_ERR_ARG, who + ": negative step count or stride");
     if (!c.agent && !c.actor && !c.actions.p) return fail(h, EV2G_ERR_ARG, who + ": without an agent the " + (l ? "raw " : "") + "actions are read from `actions`");
     // the engine resets lazily inside the step launch after an episode end, so an agent's launch for the new episode's first step would
@@ -2316,6 +2344,120 @@ double ev2g_step_n_kernel_ms_back(ev2g_handle *h, int back) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, h->ev0s[slot], h->ev1s[slot]) != hipSuccess) return -1.0;
     return (double)ms;
+}
+
+// ---- action wrappers (ev2g_wrap.h) ----
+// what a wrapper kind needs of the loaded scenarios beyond their envs and ports; asked at create and again before every launch, as for the agents
+static int wrap_shape_check(ev2g_handle *h, int kind, const std::string &who) {
+    if (kind != EV2G_WRAP_RESCALE_REPAIR) return EV2G_OK;
+    // the reference asserts it (action_wrappers.py:186) and indexes its per-charger tables with port ids and queue positions
+    if (h->P != h->C)
+        return fail(h, EV2G_ERR_ARG, who + ": Rescale_RepairLayer needs one port per charger (action_wrappers.py:186)");
+    // one env's queue stage has to fit the 64 KiB of LDS
+    if (h->P > EV2G_WRAP_MAX_PORTS || ev2g_wrap_wave_bytes(h->P) > 65536)
+        return fail(h, EV2G_ERR_ARG, who + ": Rescale_RepairLayer supports up to " + std::to_string(EV2G_WRAP_MAX_PORTS) + " ports per env");
+    return EV2G_OK;
+}
+
+int ev2g_wrap_create(ev2g_handle *h, int kind, ev2g_wrap **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_wrap_create: null argument");
+    *out = nullptr;
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_wrap_create: no scenarios loaded");
+    if (kind < EV2G_WRAP_BINARY || kind > EV2G_WRAP_RESCALE_REPAIR) return fail(h, EV2G_ERR_ARG, "ev2g_wrap_create: unknown wrapper kind");
+    if (int rc = wrap_shape_check(h, kind, "ev2g_wrap_create")) return rc;
+    (void)hipSetDevice(h->device);
+    ev2g_wrap *w = new ev2g_wrap();
+    w->kind = kind; w->E = h->E; w->P = h->P;
+    const size_t EP = (size_t)h->E * h->P;
+    bool ok = hipMalloc((void **)&w->act, EP * sizeof(double)) == hipSuccess;
+    if (ok && kind == EV2G_WRAP_RESCALE_REPAIR)
+        ok = hipMalloc((void **)&w->queue, EP * sizeof(int)) == hipSuccess && hipMalloc((void **)&w->qlen, (size_t)h->E * sizeof(int)) == hipSuccess &&
+             hipMalloc((void **)&w->qmin, EP * sizeof(double)) == hipSuccess && hipMalloc((void **)&w->qmax, EP * sizeof(double)) == hipSuccess &&
+             hipMemsetAsync(w->qlen, 0, (size_t)h->E * sizeof(int), h->stream) == hipSuccess;
+    if (!ok) {
+        wrap_free(w);
+        return fail(h, EV2G_ERR_HIP, "ev2g_wrap_create: device allocation failed");
+    }
+    h->wraps.push_back(w);
+    *out = w;
+    return EV2G_OK;
+}
+
+void ev2g_wrap_destroy(ev2g_handle *h, ev2g_wrap *w) { owned_destroy(h, &ev2g_handle::wraps, w, wrap_free); }
+
+static int wrap_check(ev2g_handle *h, ev2g_wrap *w, const char *who) {
+    if (int rc = owned_check(h, &ev2g_handle::wraps, w, "wrapper", who)) return rc;
+    if (w->E != h->E || w->P != h->P)
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports differ from those the wrapper was created for");
+    if (int rc = wrap_shape_check(h, w->kind, who)) return rc;
+    (void)hipSetDevice(h->device);
+    return EV2G_OK;
+}
+
+int ev2g_wrap_reset_state(ev2g_handle *h, ev2g_wrap *w) {
+    if (int rc = wrap_check(h, w, "ev2g_wrap_reset_state")) return rc;
+    if (w->qlen) HIPCHK(h, hipMemsetAsync(w->qlen, 0, (size_t)w->E * sizeof(int), h->stream));
+    return EV2G_OK;
+}
+
+// the wrapper's actions for the current step: in [E, P] (float64, or float32 with in32) -> out [E, P] float64 (may be a float64 `in`); the
+// repair layer's queue advances
+static int wrap_launch(ev2g_handle *h, ev2g_wrap *w, const void *in, bool in32, double *out) {
+    const DevScn &s = h->scn;
+    if (w->kind == EV2G_WRAP_RESCALE_REPAIR) {
+        // one wavefront per env, up to four per workgroup while their LDS stages fit 64 KiB
+        const WrapArgs wa{h->d_port_slot, h->d_heur_cs_kw, h->d_heur_cs_min_kw, w->queue, w->qlen, w->qmin, w->qmax, (int)h->scn_off};
+        const size_t wb = ev2g_wrap_wave_bytes(s.P);   // (<= 64 KiB: wrap_shape_check)
+        const int epb = (int)std::min<size_t>(EV2G_WRAP_BLOCK / 64, 65536 / wb);
+        const dim3 grid((s.E + epb - 1) / epb), block(64 * epb);
+        const int t = h->current_step;
+        if (in32) hipLaunchKernelGGL(ev2g_wrap_repair_kernel<true>, grid, block, epb * wb, h->stream, s, h->st, wa, t, in, out);
+        else hipLaunchKernelGGL(ev2g_wrap_repair_kernel<false>, grid, block, epb * wb, h->stream, s, h->st, wa, t, in, out);
+    } else {
+        const long long n = (long long)s.E * s.P;
+        const dim3 grid((unsigned)std::min<long long>((n + EV2G_WRAP_BLOCK - 1) / EV2G_WRAP_BLOCK, 1 << 20));
+        const int kind = w->kind == EV2G_WRAP_BINARY ? EV2G_WRAP_KIND_BINARY : EV2G_WRAP_KIND_THREE_STEP;
+        if (in32) hipLaunchKernelGGL(ev2g_wrap_discrete_kernel<true>, grid, dim3(EV2G_WRAP_BLOCK), 0, h->stream, s, (const int *)h->d_port_slot, kind, in, out);
+        else hipLaunchKernelGGL(ev2g_wrap_discrete_kernel<false>, grid, dim3(EV2G_WRAP_BLOCK), 0, h->stream, s, (const int *)h->d_port_slot, kind, in, out);
+    }
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_wrap_actions(ev2g_handle *h, ev2g_wrap *w, const void *in, int in_is_f32, double *out) {
+    if (int rc = wrap_check(h, w, "ev2g_wrap_actions")) return rc;
+    if (!in || !out) return fail(h, EV2G_ERR_ARG, "ev2g_wrap_actions: the action block is null");
+    if (h->current_step >= h->T) return fail(h, EV2G_ERR_DONE, "ev2g_wrap_actions: episode is done, reset the environment");
+    return wrap_launch(h, w, in, in_is_f32 != 0, out);
+}
+
+int ev2g_wrap_run(ev2g_handle *h, ev2g_wrap *w, int k_steps, double *actions, int64_t a_stride, double *wrapped, int64_t w_stride, double *obs,
+                  int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride) {
+    if (int rc = wrap_check(h, w, "ev2g_wrap_run")) return rc;
+    StepChain c{"ev2g_wrap_run"};
+    c.actions = {actions, a_stride};
+    c.wrap = w; c.wrapped = {wrapped, w_stride};
+    c.obs = {obs, o_stride}; c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    return run_chain(h, c, k_steps);
+}
+
+int ev2g_wrap_rollout(ev2g_handle *h, ev2g_wrap *w, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
+                      int64_t d_stride, uint8_t *mask, int64_t m_stride) {
+    if (int rc = wrap_check(h, w, "ev2g_wrap_rollout")) return rc;
+    if (!m || k_steps < 0 || r_stride < 0 || d_stride < 0 || m_stride < 0) return fail(h, EV2G_ERR_ARG, "ev2g_wrap_rollout: bad arguments");
+    if (w->kind == EV2G_WRAP_THREE_STEP)
+        return fail(h, EV2G_ERR_ARG, "ev2g_wrap_rollout: ThreeStep_Action takes the discrete actions 0 / 1 / 2, which an actor's tanh output never equals");
+    const ev2g_step_extras &x = h->extras;
+    if (!x.obs_f32 || !x.actions_f32 || x.obs_f32_step_stride != 0)
+        return fail(h, EV2G_ERR_ARG, "ev2g_wrap_rollout: register float32 observation (step stride 0) and action buffers with ev2g_set_step_extras first");
+    if (m->dev.d_in != h->D || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_wrap_rollout: actor shape != (obs dim, ports)");
+    // the unfused policy loop between the registered float32 pair, the wrapper between actor and step: no fused variant, no graph capture
+    StepChain c{"ev2g_wrap_rollout"};
+    c.actor = m;
+    c.wrap = w;
+    c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
+    c.count_steps = x.cost != nullptr;   // (as ev2g_rollout: a cost buffer may record every step; the float32 buffers do not advance)
+    return run_chain(h, c, k_steps);
 }
 
 int ev2g_check_faults(ev2g_handle *h, int32_t *first_bad_env) {

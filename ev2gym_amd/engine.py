@@ -84,6 +84,12 @@ def load_library(path: Optional[str] = None):
         "ev2g_link_obs_f32": (vp, [vp, vp]),
         "ev2g_link_run": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]),
         "ev2g_link_rollout": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64]),
+        "ev2g_wrap_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+        "ev2g_wrap_destroy": (None, [vp, vp]),
+        "ev2g_wrap_reset_state": (C.c_int, [vp, vp]),
+        "ev2g_wrap_actions": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+        "ev2g_wrap_run": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]),
+        "ev2g_wrap_rollout": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64]),
         "ev2g_grid_create": (C.c_int, [vp, C.c_int, vp, vp, dbl, dbl, C.c_int, vp, vp, C.POINTER(vp)]),
         "ev2g_grid_destroy": (None, [vp, vp]),
         "ev2g_grid_solve": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
@@ -151,7 +157,8 @@ EXPORTED_SYMBOLS = [
     "ev2g_link_create", "ev2g_link_destroy", "ev2g_link_reset_state", "ev2g_link_actions", "ev2g_link_observe", "ev2g_link_obs_f32",
     "ev2g_link_run", "ev2g_link_rollout",
     "ev2g_grid_create", "ev2g_grid_destroy", "ev2g_grid_solve", "ev2g_grid_run",
-    "ev2g_grid_state_attach", "ev2g_grid_state_dim", "ev2g_grid_observe", "ev2g_grid_run_observed", "ev2g_grid_rollout", "ev2g_grid_get_stats"]
+    "ev2g_grid_state_attach", "ev2g_grid_state_dim", "ev2g_grid_observe", "ev2g_grid_run_observed", "ev2g_grid_rollout", "ev2g_grid_get_stats",
+    "ev2g_wrap_create", "ev2g_wrap_destroy", "ev2g_wrap_reset_state", "ev2g_wrap_actions", "ev2g_wrap_run", "ev2g_wrap_rollout"]
 
 
 def _ptr(x):
@@ -470,6 +477,40 @@ class Engine:
     def link_rollout(self, l, m, k, reward=None, r_stride=0, done=None, d_stride=0, mask=None, m_stride=0):
         """k x (actor on the link's float32 delivered row -> held commands -> one step -> delayed observation), unfused, inside one episode."""
         self._check(self._lib.ev2g_link_rollout(self._h, l, m, int(k), _ptr(reward), int(r_stride), _ptr(done), int(d_stride), _ptr(mask),
+                                                int(m_stride)))
+
+    # ---- the reference's action wrappers on the device (include/ev2g.h: ev2g_wrap_*) ----------------------------------------------
+    def wrap_create(self, name):
+        """A device-resident action wrapper of the reference's class `name` (a key of _abi.WRAP_KINDS, or the kind number), bound to this
+        engine's envs and ports; freed by wrap_destroy or with the engine.  Rescale_RepairLayer needs one port per charger."""
+        kind = _abi.WRAP_KINDS[name] if isinstance(name, str) else int(name)
+        w = C.c_void_p()
+        self._check(self._lib.ev2g_wrap_create(self._h, kind, C.byref(w)))
+        return w
+
+    def wrap_destroy(self, w):
+        if self._h and w:
+            self._lib.ev2g_wrap_destroy(self._h, w)
+
+    def wrap_reset_state(self, w):
+        """Empty the repair layer's queue (a freshly constructed wrapper); nothing to do for the discretisers."""
+        self._check(self._lib.ev2g_wrap_reset_state(self._h, w))
+
+    def wrap_actions(self, w, actions, out, f32=False):
+        """The wrapper's action() at the current step for the raw device actions [E, P] (float64, or float32 with f32=True) into the float64
+        device array `out`, which may be a float64 `actions`; no step."""
+        self._check(self._lib.ev2g_wrap_actions(self._h, w, _ptr(actions), int(bool(f32)), _ptr(out)))
+
+    def wrap_run(self, w, k, actions, a_stride=0, wrapped=None, w_stride=0, obs=None, o_stride=0, reward=None, r_stride=0, done=None,
+                 d_stride=0, mask=None, m_stride=0):
+        """k x (wrapper -> one step) inside one episode on the raw actions [k, E, P]; the wrapped actions go to `wrapped`; outputs as in
+        step_n, timed like it."""
+        self._check(self._lib.ev2g_wrap_run(self._h, w, int(k), _ptr(actions), int(a_stride), _ptr(wrapped), int(w_stride), _ptr(obs),
+                                            int(o_stride), _ptr(reward), int(r_stride), _ptr(done), int(d_stride), _ptr(mask), int(m_stride)))
+
+    def wrap_rollout(self, w, m, k, reward=None, r_stride=0, done=None, d_stride=0, mask=None, m_stride=0):
+        """k x (actor between the registered float32 buffers -> wrapper -> one step), unfused, inside one episode."""
+        self._check(self._lib.ev2g_wrap_rollout(self._h, w, m, int(k), _ptr(reward), int(r_stride), _ptr(done), int(d_stride), _ptr(mask),
                                                 int(m_stride)))
 
     # ---- the distribution grid's power flow on the device (include/ev2g.h: ev2g_grid_*) ------------------------------------------

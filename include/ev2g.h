@@ -460,7 +460,7 @@ int ev2g_heuristic_run(ev2g_handle *h, ev2g_heuristic *a, int k_steps, double *a
  *  - at the terminal observation (current_step == T) the reference indexes random[:, T] and raises as soon as one port is occupied; here that
  *    observation passes through with no slot delayed (nc = 0, remembered rows updated, clamp applied);
  *  - the reference's `assert obs[2] >= -5` (noise_wrappers.py:193) is not reproduced, only the clamp.
- * Out of scope: the wrapper's graph-state branch (noise_wrappers.py:134-161) and the action wrappers (rl_agent/action_wrappers.py). */
+ * Out of scope: the wrapper's graph-state branch (noise_wrappers.py:134-161); the action wrappers (rl_agent/action_wrappers.py) are ev2g_wrap_* below. */
 typedef struct ev2g_link ev2g_link;
 /* Needs loaded scenarios; bound to the handle's envs, ports and steps like an agent (a reload that changes them makes its calls fail) and freed
  * with the handle if not before.  EV2G_ERR_ARG: a probability outside [0,1]; p_delay > 0 on a handle whose state is not EV2G_STATE_PUBLIC_PST
@@ -495,6 +495,53 @@ int ev2g_link_run(ev2g_handle *h, ev2g_link *l, ev2g_heuristic *agent, int k_ste
  * fused-launch variant (ev2g_rollout's single launch per segment has no place for the two kernels between policy and step). */
 float *ev2g_link_obs_f32(ev2g_handle *h, ev2g_link *l);
 int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
+                      int64_t d_stride, uint8_t *mask, int64_t m_stride);
+
+/* ---- the reference's action wrappers ON THE DEVICE (rl_agent/action_wrappers.py) -------------------------------------------------------------
+ * A wrapper rewrites the raw actions [E,P] of the current step into the actions the step reads, for the E envs of a handle, in float64 and in
+ * the reference's operation order (bit for bit its arithmetic).  min_action[p] = cs_min_charge_current / cs_max_charge_current + 1e-4 of
+ * port p's charger.
+ *   EV2G_WRAP_BINARY          BinaryAction (action_wrappers.py:47): in > 0.5 ? 1 : min_action[p];
+ *   EV2G_WRAP_THREE_STEP      ThreeStep_Action and ThreeStep_Action_DiscreteActionSpace (:90, :138): in == 0 ? 0 : (in == 1 ? min_action[p] : 1);
+ *   EV2G_WRAP_RESCALE_REPAIR  Rescale_RepairLayer (:277-451): a = in * (1 - min_action) + min_action; the wrapper's queue of ports whose EV is
+ *     below full charge is updated (update_ev_buffer, :205-243); the queued EVs' clamped powers are raised proportionally towards the step's
+ *     power setpoint, or reduced proportionally and then topped up greedily in queue order, or left alone when they meet it exactly; the
+ *     result is a[p] * occupied_ports[p].  Every sum is the plain left-to-right float64 sum in queue order (Python's sum() before CPython
+ *     3.12).  One port per charger only (:186).  The queue lives in the wrapper ACROSS episodes, as the reference's object does
+ *     (ev2g_wrap_reset_state empties it: a freshly built wrapper).  Two quirks of the reference are reproduced:
+ *      - a queue entry keeps the min_power / max_power it was inserted with: a port whose next EV arrives the step after the last one left
+ *        stays queued with the old EV's powers;
+ *      - new_action[i] = proposed_power[i] / max_cs_power[i] divides by the charger at the QUEUE POSITION i, not by the entry's own port
+ *        (:356, :429); with chargers of unequal power the two differ.
+ * The discretisers work for any number of ports per charger.  MinMax_RepairLayer raises in the reference's constructor and has no kind; mask_fn
+ * is left out.  A step chain holds a wrapper OR a link / grid, not both; stacked wrappers are not supported. */
+#define EV2G_WRAP_BINARY 0
+#define EV2G_WRAP_THREE_STEP 1
+#define EV2G_WRAP_RESCALE_REPAIR 2
+typedef struct ev2g_wrap ev2g_wrap;
+/* Needs loaded scenarios; bound to the handle's envs and ports like an agent (a reload that changes them makes its calls fail) and freed with
+ * the handle if not before.  EV2G_ERR_ARG: an unknown kind; EV2G_WRAP_RESCALE_REPAIR on chargers with several ports, or above 2259 ports per
+ * env (one env's queue stage has to fit the 64 KiB of LDS). */
+int ev2g_wrap_create(ev2g_handle *h, int kind, ev2g_wrap **out);
+void ev2g_wrap_destroy(ev2g_handle *h, ev2g_wrap *w);
+/* empties the repair layer's queue of every env (a freshly constructed wrapper); nothing to do for the discretisers */
+int ev2g_wrap_reset_state(ev2g_handle *h, ev2g_wrap *w);
+/* The wrapper's action() for the handle's current step: `in` [E,P] DEVICE, float64 or -- in_is_f32 != 0 -- float32, widened as the engine widens
+ * float32 actions; out [E,P] float64 DEVICE, which may be a float64 `in` (rewritten in place).  No step is taken; the repair layer's queue
+ * advances as the reference's does on every action() call.  EV2G_ERR_DONE past the episode's last step. */
+int ev2g_wrap_actions(ev2g_handle *h, ev2g_wrap *w, const void *in, int in_is_f32, double *out);
+/* k_steps x (wrapper kernel -> one-step launch of the step kernel the handle selected) inside ONE episode, enqueued without host round trips.
+ * The raw actions are read from actions [k,E,P] at base + k*a_stride (a_stride 0: one block reused); the wrapped actions are written to
+ * wrapped [k,E,P] at base + k*w_stride (NULL: a block of the wrapper, stride 0), which the step reads.  obs / reward / done / mask as in
+ * ev2g_step_n (DEVICE, each may be NULL).  A segment that would run past the episode end returns EV2G_ERR_DONE, as ev2g_heuristic_run does.
+ * Timed like ev2g_step_n (ev2g_last_step_n_kernel_ms). */
+int ev2g_wrap_run(ev2g_handle *h, ev2g_wrap *w, int k_steps, double *actions, int64_t a_stride, double *wrapped, int64_t w_stride, double *obs,
+                  int64_t o_stride, double *reward, int64_t r_stride, uint8_t *done, int64_t d_stride, uint8_t *mask, int64_t m_stride);
+/* The policy loop under a wrapper: k_steps x (ev2g_mlp_forward between the float32 buffers registered with ev2g_set_step_extras -> wrapper
+ * kernel on the policy's float32 actions -> one-step launch reading the wrapper's float64 block and writing the float32 observation), inside
+ * one episode: ev2g_rollout's two-launch chain plus one launch, unfused and not captured into a graph.  EV2G_ERR_ARG for EV2G_WRAP_THREE_STEP
+ * (a tanh output never equals 0 or 1), without the registered pair, or unless the actor maps D -> P. */
+int ev2g_wrap_rollout(ev2g_handle *h, ev2g_wrap *w, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
                       int64_t d_stride, uint8_t *mask, int64_t m_stride);
 
 /* ---- the distribution grid's power flow ON THE DEVICE (simulate_grid: models/grid.py, models/grid_utility/grid_tensor.py) ----------------
