@@ -23,62 +23,8 @@
 #define EV2G_BLOCK 256
 #define EV2G_NQ 8  // staged quantities per port
 
-// One EV session, 128 bytes = one cache line: what the per-step battery maths and an arrival need (ev.py:68-113), laid out by CONSUMER so that
-// each of them fetches a contiguous run of 16-byte chunks: a charging step reads chunks 0..4 (80 bytes), a discharging step chunks 3..6
-// (64 bytes), an arrival chunks 2 and 7.  `rB` / `rv` are the correctly rounded reciprocals of `B` / `v` (computed once per session, by the
-// loader or the device generator, with an IEEE division): the battery maths divides by B and v through them (ev2g_fdiv2, below) instead of
-// through ~11-instruction hardware division sequences.
-struct __attribute__((aligned(128))) SessRec {
-    double pacmax, ts;        // chunk 0  (charge)
-    double tsm, eta_ch;       // chunk 1  (charge)
-    double gate_ch;           // chunk 2  (charge)  min_ac_charge_power*1000/(voltage*sqrt(charger phases))   (ev.py:151)
-    double B;                 //          (charge, arrival)
-    double rB;                // chunk 3  (charge)  RN(1 / B)
-    double v;                 //          (charge, discharge)  voltage*sqrt(min(charger phases, ev_phases))   (ev.py:169,279,365)
-    double rv;                // chunk 4  (charge, discharge)  RN(1 / v)
-    double gate_dis;          //          (discharge)  min_discharge_power*1000/(voltage*sqrt(charger phases))   (ev.py:153)
-    double minB, emerg;       // chunk 5  (discharge)
-    double pdismax, eta_dis;  // chunk 6  (discharge)
-    double cap0;              // chunk 7  (arrival)  battery_capacity_at_arrival
-    double potc;              //          (arrival)  this EV's term of calculate_charge_power_potential before the charger clamp:
-                              //          v * min(pacmax*1000/v, charger max current) / 1000   (utils.py:773-777), evaluated once per session
-};
-// What a departure reads (and the rewards that look at every connected EV's desired capacity), 16 bytes per session next to the records
-struct SessTail {
-    double des;          // desired_capacity
-    int nt_arr, nt_dep;  // window of the next session on the same port (EV2G_INT_MAX = none)
-};
-
-// Round 5: the battery maths' operands that are the SAME for every session of one car model on one kind of charger (ev.py:68-113: the model's
-// powers, battery size, gates; the charger's voltage and phases) live in a small dictionary instead of in every session's record: a few
-// dozen 128-byte entries that stay in the vector L1, so the fetch in the middle of the battery-maths phase is an L1 hit instead of an L2
-// round trip to the session's own line (the one lever that reached 0.60 of the roofline in round 4's ablation).  What really differs per
-// session -- transition_soc and, without an efficiency table, the two efficiencies (utils.py:293-296,309-310) -- is SessDyn: it travels with the
-// arrival's other operands into the port's LDS state (ev2g_step_wave.h) and, across launches, into the port's PortDyn entry.
-// Laid out by consumer: a charging step reads chunks 0..3 (one 64-byte sector), a discharging step chunks 4..6.
-struct __attribute__((aligned(128))) ClsRec {
-    double pacmax, tsm;       // chunk 0  (charge)
-    double gate_ch, B;        // chunk 1  (charge)
-    double rB, v;             // chunk 2  (charge)
-    double rv, pad0;          // chunk 3  (charge)
-    double v_d, rv_d;         // chunk 4  (discharge: copies of v, rv)
-    double gate_dis, minB;    // chunk 5  (discharge)
-    double emerg, pdismax;    // chunk 6  (discharge)
-    double pad1[2];
-};
-#define EV2G_CLS_CAP 4096     // dictionary entries (12 bits of the port's LDS word); a batch with more distinct tuples keeps one ClsRec per SESSION instead
-struct __attribute__((aligned(32))) SessDyn {
-    double ts, eta_ch;        // EV.transition_soc, EV.charge_efficiency (a number: sessions without an efficiency table)
-    double eta_dis;           // EV.discharge_efficiency
-    int lut, cls;             // efficiency-table id (-1: none), dictionary entry (the session's own index when the batch has no dictionary)
-};
+#include "ev2g_records.h"   // SessRec, SessTail, ClsRec, SessDyn, ev2g_cls_of, EV2G_CLS_CAP, EV2G_INT_MAX (plain C++: the host-only loader plan shares them)
 typedef SessDyn PortDyn;      // the same four words for the EV attached to a port, written at its arrival: what a later launch's prologue reads
-__host__ __device__ inline ClsRec ev2g_cls_of(const SessRec &r) {
-    ClsRec c;
-    c.pacmax = r.pacmax; c.tsm = r.tsm; c.gate_ch = r.gate_ch; c.B = r.B; c.rB = r.rB; c.v = r.v; c.rv = r.rv; c.pad0 = 0.0;
-    c.v_d = r.v; c.rv_d = r.rv; c.gate_dis = r.gate_dis; c.minB = r.minB; c.emerg = r.emerg; c.pdismax = r.pdismax; c.pad1[0] = 0.0; c.pad1[1] = 0.0;
-    return c;
-}
 
 struct DevScn {  // read-only scenario + layout, device pointers
     int E;        // envs stepped concurrently (state arrays are [E, ...])
@@ -213,8 +159,6 @@ __host__ __device__ __forceinline__ int ev2g_scn(int e, int off, int M) { const 
 __device__ __forceinline__ double ev2g_action(const StepIO &io, const float *act32, long long step_off, long long i) {
     return io.actions ? io.actions[step_off + i] : (double)act32[step_off + i];
 }
-
-#define EV2G_INT_MAX 0x7fffffff
 
 __device__ __forceinline__ double ceil2(double a) { return ceil(a * 100.0) / 100.0; }       // ev.py:188-189
 __device__ __forceinline__ double rnd5(double x) { return rint(x * 100000.0) / 100000.0; }  // ev_charger.py:157

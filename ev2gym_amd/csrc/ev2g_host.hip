@@ -1,9 +1,9 @@
 // ev2g_host.hip -- host side of libev2g_hip.so: the C-ABI of include/ev2g.h over HIP.
 //
-// Scenario packing (the host half of ev2g_load_scenarios) turns the reference-shaped batch
-// (chargers, transformers, EVs_profiles-ordered sessions) into the device layout documented in
-// ev2g_device.h / DESIGN.md:  transformer-major port slots, sessions sorted by (env, slot, arrival)
-// with the next session's window chained in, per-port first-session tables, max_energy_AFAP.
+// Scenario packing turns the reference-shaped batch (chargers, transformers, EVs_profiles-ordered sessions) into the device
+// layout documented in ev2g_device.h / DESIGN.md.  Its host half -- transformer-major port slots, sessions sorted by
+// (env, slot, arrival) with the next session's window chained in, per-port first-session tables, max_energy_AFAP -- is
+// ev2g_load_host.h's LoadPlan; ev2g_load_scenarios below routes, uploads and allocates (its load_* functions).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 
 #include "../../include/ev2g.h"
 #include "ev2g_device.h"
+#include "ev2g_load_host.h"
 #include "ev2g_step_v2.h"
 #include "ev2g_step_wave.h"
 #include "ev2g_step_big.h"
@@ -159,11 +160,12 @@ struct ev2g_handle {
     bool no_strided = false;                    // EV2G_NO_STRIDED at load time: strided outputs run the general instantiation (round 4's routing; parity tests)
     // battery-maths dictionary (ClsRec, ev2g_device.h): host mirror of the entries in use, so that ev2g_pool_refill can append the
     // classes its fleet may draw; d_cls_rec has room for EV2G_CLS_CAP entries when DevScn::dict is set
-    typedef std::array<uint64_t, 11> ClsKey;
     std::map<ClsKey, int> cls_map;
     ClsRec *d_cls_rec = nullptr;
     std::vector<double> cs_vk_host;             // [C,4] voltage*sqrt(k) and [C] phases of the loaded chargers (the refill's dictionary entries)
     std::vector<int> cs_ph_host;
+    std::vector<double> cs_imax_host;           // [C] max_charge_current of the loaded chargers: only so that the refill can call ev2g_sess_consts, the one
+                                                // place the record constants are formed (the potc it yields is not part of a dictionary entry: ev2g_cls_of)
     int load_gen = 0;                           // counts ev2g_load_scenarios calls (part of the refill cache's key)
     int last_spec = -1;                         // ev2g_last_launch_specialisation
     // in-launch episode statistics (ev2g_step_wave's INL phase): the last step launch closed the episode and wrote get_statistics of every env
@@ -294,21 +296,6 @@ static void owned_destroy(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T
     release(x);
 }
 
-// dictionary entry of a ClsRec (by value, bit for bit); -1 when the dictionary is full
-static int cls_find_or_add(std::map<ev2g_handle::ClsKey, int> &map, std::vector<ClsRec> &tab, const ClsRec &c) {
-    ev2g_handle::ClsKey k;
-    const double f[11] = {c.pacmax, c.tsm, c.gate_ch, c.B, c.rB, c.v, c.rv, c.gate_dis, c.minB, c.emerg, c.pdismax};
-    std::memcpy(k.data(), f, sizeof f);
-    auto it = map.find(k);
-    if (it != map.end()) return it->second;
-    if (map.size() >= EV2G_CLS_CAP) return -1;
-    const int id = (int)map.size();
-    map.emplace(k, id);
-    if ((size_t)id >= tab.size()) tab.resize((size_t)id + 1);
-    tab[(size_t)id] = c;
-    return id;
-}
-
 #include "ev2g_refill_host.h"
 
 extern "C" {
@@ -407,29 +394,6 @@ static const char *kStatNames[EV2G_N_STATS] = {
     "battery_degradation", "battery_degradation_calendar", "battery_degradation_cycling", "total_reward"};
 const char *ev2g_stat_name(int i) { return (i >= 0 && i < EV2G_N_STATS) ? kStatNames[i] : ""; }
 
-// EV.calculate_max_energy_with_AFAP (ev.py:407-440)
-static double afap_energy(const ev2g_scenario_batch *b, long long s, double max_cs_power) {
-    const double pac = b->ev_pac_max[s];
-    const double max_power = (std::fabs(max_cs_power) > std::fabs(pac)) ? pac : max_cs_power;
-    double eff;
-    if (b->ev_lut[s] >= 0) {
-        double m = 0;
-        for (int k = 0; k < EV2G_LUT_LEN; k++) m = std::max(m, b->lut[(size_t)b->ev_lut[s] * EV2G_LUT_LEN + k]);
-        eff = m / 100.0;
-    } else
-        eff = b->ev_eta_ch[s];
-    double x = b->ev_cap0[s];
-    for (int k = b->ev_t_arr[s]; k < b->ev_t_dep[s] + 1; k++) {
-        x += max_power * eff * b->timescale / 60.0;
-        x = std::ceil(x * 100.0) / 100.0;
-        if (x > b->ev_B[s]) {
-            x = b->ev_B[s];
-            break;
-        }
-    }
-    return x;
-}
-
 int ev2g_reset_ex(ev2g_handle *h, double *obs, int64_t scenario_offset);
 
 // Envs per wavefront of ev2g_stats_kernel (the summation order of its reductions follows from it): two where an env's sessions fit 32 lanes with
@@ -441,263 +405,38 @@ static bool stats_pair(const ev2g_handle *h) {
     return (h->sess_cap > 0 ? per_scn <= 48 : h->S <= (long long)h->M * 24) && h->C <= 32;
 }
 
-int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
-    if (!h || !b) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: null argument");
-    (void)hipSetDevice(h->device);
-    const int M = b->n_envs, T = b->n_steps, C = b->n_chargers, npc = b->ports_per_charger, R = b->n_transformers;
-    const int ND = std::max(b->n_dr_max, 0);
-    const int E = h->cfg.n_active_envs > 0 ? h->cfg.n_active_envs : M;   // envs stepped concurrently
-    if (E > M) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: n_active_envs exceeds the number of scenarios in the batch");
-    if (M <= 0 || T <= 0 || C <= 0 || npc <= 0 || R <= 0 || b->timescale <= 0)
-        return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: non-positive size");
-    if (b->horizon != 20) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: horizon must be 20 (state.py:119,129-132)");
-    if (npc > 32) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: more than 32 ports per charger unsupported");
-    // ports of each charger: uniform, or per charger from a topology file (loaders.py:312-340); numbered cumulatively in charger
-    // order like the reference's port_counter (ev2gym_env.py:364-385)
-    std::vector<int> np_of(C, npc), pbase(C + 1, 0);
-    bool het = false;
-    if (b->cs_n_ports) {
-        int mx = 0;
-        for (int c = 0; c < C; c++) {
-            np_of[c] = b->cs_n_ports[c];
-            if (np_of[c] < 1) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: cs_n_ports must be >= 1");
-            mx = std::max(mx, np_of[c]);
-            het = het || np_of[c] != npc;
-        }
-        if (mx != npc) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: ports_per_charger must be the maximum of cs_n_ports");
-    }
-    for (int c = 0; c < C; c++) pbase[c + 1] = pbase[c] + np_of[c];
-    const int P = pbase[C];
-    if (het)   // the reference's action mask is indexed i*cs.n_ports + j (ev2gym_env.py:452-457): past the array it raises IndexError
-        for (int c = 0; c < C; c++)
-            if (c * np_of[c] + np_of[c] > P)
-                return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: this charger order makes the reference's action mask index "
-                                             "i*n_ports+j leave the mask array (ev2gym_env.py:457 raises IndexError); order the chargers by falling port count");
-    const long long S = b->env_session_start[M];
-    if (S != b->n_sessions || b->env_session_start[0] != 0)
-        return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: env_session_start inconsistent with n_sessions");
-    if (S > 0x7ffffff0LL) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: too many sessions for 32-bit indices");
-    {   // the kernels index with 32-bit ints: every element offset they form must stay below 2^31
-        const long long lim = 0x7fffffffLL, Pq = P;
-        const long long Dq = 3 + 3 * Pq > 22 + 40LL * R + 2 * Pq ? 3 + 3 * Pq : 22 + 40LL * R + 2 * Pq;
-        const bool log_cs = (h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) != 0;
-        if ((long long)M * Pq > lim || (long long)M * Dq > lim || (long long)M * R * (T + 1) * 40 > lim ||
-            (log_cs && (long long)T * M * std::max<long long>(C, Pq) > lim) || (long long)M * T * 8 > lim)
-            return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: batch too large for 32-bit element offsets "
-                                         "(need M*P, M*D, M*R*(T+1)*40, T*M*C < 2^31): split it over more handles / GPUs");
-    }
-    if (T > 65535 || b->n_lut > 65534)
-        return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: simulation_length and the number of efficiency tables must stay below 65536 (a port's state line "
-                                     "packs charging_cycles and the table id into 16 bits each)");
-    for (int c = 0; c < C; c++) {
-        if (b->cs_transformer[c] < 0 || b->cs_transformer[c] >= R)
-            return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: cs_transformer out of range");
-        if (b->cs_phases[c] < 1 || b->cs_phases[c] > 3)
-            return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: cs_phases must be 1..3");
-    }
-    (void)hipStreamSynchronize(h->stream);
-    drop_rollout_graphs(h);
-    free_pool(h->scn_allocs);
-    free_pool(h->st_allocs);
-    h->loaded = false;
+// ---- ev2g_load_scenarios: the device stage ----
+// ev2g_load_host.h plans on the host (layout, session order, constants, records, dictionary); the load_* functions below route the plan to
+// a kernel, upload it, build the device tables and allocate the state, in the order ev2g_load_scenarios calls them.
 
-    // ---- slot order: transformer-major, chargers in id order inside a transformer, ports adjacent ----
-    std::vector<int> slot_port(P), slot_cs(P), slot_tr(P), slot_obs(P), slot_mask(P), port_slot(P), tr_seg(R + 1, 0), tr_obs(R);
-    {
-        int q = 0;
-        for (int r = 0; r < R; r++) {
-            tr_seg[r] = q;
-            for (int c = 0; c < C; c++)
-                if (b->cs_transformer[c] == r)
-                    for (int j = 0; j < np_of[c]; j++) {
-                        slot_port[q] = pbase[c] + j;
-                        slot_mask[q] = c * np_of[c] + j;   // where the reference sets this port's action-mask entry (ev2gym_env.py:457)
-                        slot_cs[q] = c;
-                        slot_tr[q] = r;
-                        port_slot[pbase[c] + j] = q;
-                        q++;
-                    }
-        }
-        tr_seg[R] = q;
-    }
-    const int sk = h->cfg.state_kind;
-    int D;
-    if (sk == EV2G_STATE_PUBLIC_PST) {
-        D = 3 + 3 * P;
-        for (int q = 0; q < P; q++) slot_obs[q] = 3 + 3 * q;
-        for (int r = 0; r < R; r++) tr_obs[r] = 0;
-    } else if (sk == EV2G_STATE_V2G_PROFIT_MAX) {
-        D = 22 + 2 * P;
-        for (int q = 0; q < P; q++) slot_obs[q] = 22 + 2 * q;
-        for (int r = 0; r < R; r++) tr_obs[r] = 0;
-    } else {
-        D = 22 + 40 * R + 2 * P;
-        for (int r = 0; r < R; r++) tr_obs[r] = 22 + 40 * r + 2 * tr_seg[r];
-        for (int q = 0; q < P; q++) slot_obs[q] = 22 + 40 * (slot_tr[q] + 1) + 2 * q;
-    }
-    int max_seg = 1;
-    for (int r = 0; r < R; r++) max_seg = std::max(max_seg, tr_seg[r + 1] - tr_seg[r]);
-
-    // ---- resolve ports (first-free replay, ev_charger.py:266-286) and order sessions by (env, slot, arrival) ----
-    // Device session storage.  Packed (default): scenario m owns the device sessions [env_session_start[m], env_session_start[m+1]).
-    // EV2G_FLAG_REFILLABLE: every scenario owns a fixed-size block of `cap` session slots (the largest count of the batch + 25 % + 8,
-    // or EV2G_POOL_SESSION_CAP), so that ev2g_pool_refill can regenerate a scenario in place on the device; SD counts slots, holes included.
-    const bool refillable = (h->cfg.flags & EV2G_FLAG_REFILLABLE) != 0;
-    long long cap = 0;
-    if (refillable) {
-        for (int m = 0; m < M; m++) cap = std::max<long long>(cap, b->env_session_start[m + 1] - b->env_session_start[m]);
-        cap = ((cap + cap / 4 + 8) + 7) / 8 * 8;
-        if (const char *e = std::getenv("EV2G_POOL_SESSION_CAP")) cap = std::max<long long>(cap, std::atoll(e));
-        if (cap * M > 0x7ffffff0LL) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: too many session slots for 32-bit indices (refillable pool)");
-    }
-    const long long SD = refillable ? cap * M : S;
-    h->sess_cap = (int)cap;
-    std::vector<int> sess_port((size_t)S), host_to_dev((size_t)S), ss_slot((size_t)std::max<long long>(SD, 1));   // ss_slot: port slot of a session, device order
-    std::vector<int> scn_sess((size_t)M + 1), scn_sess_end((size_t)M);   // device sessions of scenario m: [scn_sess[m], scn_sess_end[m]) (device order is scenario-major)
-    for (int m = 0; m <= M; m++) scn_sess[(size_t)m] = refillable ? (int)(cap * m) : (int)b->env_session_start[m];
-    for (int m = 0; m < M; m++) scn_sess_end[(size_t)m] = scn_sess[(size_t)m] + (int)(b->env_session_start[m + 1] - b->env_session_start[m]);
-    std::vector<long long> dev_to_host((size_t)SD, -1);
-    std::vector<int> port_first((size_t)M * P, -1);
-    std::vector<int> port_end((size_t)M * P, -1);   // one past the port's last session (device order: a port's sessions are consecutive)
-    std::vector<int2> port_first_win((size_t)M * P, make_int2(EV2G_INT_MAX, EV2G_INT_MAX));
-    {
-        std::vector<int> free_at((size_t)C * npc);
-        std::vector<std::pair<long long, long long>> keyed;  // (slot, host idx)
-        long long d = 0;
-        for (int e = 0; e < M; e++) {
-            d = scn_sess[(size_t)e];
-            std::fill(free_at.begin(), free_at.end(), 0);
-            const long long s0 = b->env_session_start[e], s1 = b->env_session_start[e + 1];
-            if (s1 < s0) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: env_session_start not monotone");
-            keyed.clear();
-            int prev_arr = 0;
-            for (long long s = s0; s < s1; s++) {
-                const int cs = b->ev_cs[s], ta = b->ev_t_arr[s], td = b->ev_t_dep[s];
-                if (cs < 0 || cs >= C) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: ev_cs out of range");
-                if (ta < 1 || td < ta) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: need 1 <= t_arr <= t_dep");
-                if (ta < prev_arr) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: sessions must be sorted by arrival");
-                if (b->ev_phases[s] < 1 || b->ev_phases[s] > 3)
-                    return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: ev_phases must be 1..3");
-                if (b->ev_lut[s] >= b->n_lut) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: ev_lut out of range");
-                prev_arr = ta;
-                int slot = -1;
-                for (int j = 0; j < np_of[cs]; j++)
-                    if (free_at[(size_t)cs * npc + j] <= ta - 1) {  // attached at the end of step ta-1
-                        slot = j;
-                        break;
-                    }
-                if (slot < 0)
-                    return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: no free port for a session (assert n_evs_connected < n_ports, ev_charger.py:271)");
-                free_at[(size_t)cs * npc + slot] = td;  // freed inside step td, before that step's spawns
-                sess_port[s] = pbase[cs] + slot;
-                keyed.emplace_back((long long)port_slot[pbase[cs] + slot], s);
-            }
-            std::stable_sort(keyed.begin(), keyed.end(),
-                             [](const auto &x, const auto &y) { return x.first < y.first; });
-            for (auto &kv : keyed) {
-                host_to_dev[kv.second] = (int)d;
-                dev_to_host[d] = kv.second;
-                ss_slot[(size_t)d] = (int)kv.first;
-                const size_t g = (size_t)e * P + kv.first;
-                if (port_first[g] < 0) {
-                    port_first[g] = (int)d;
-                    port_first_win[g] = make_int2(b->ev_t_arr[kv.second], b->ev_t_dep[kv.second]);
-                }
-                port_end[g] = (int)d + 1;
-                d++;
-            }
-        }
-    }
-    // ---- gather session fields into device order, chain the next window ----
-#define GATHER(type, name, src)                                 \
-    std::vector<type> name((size_t)SD);                         \
-    for (long long d = 0; d < SD; d++) if (dev_to_host[d] >= 0) name[d] = b->src[dev_to_host[d]];
-    GATHER(int, ss_tarr, ev_t_arr)
-    GATHER(int, ss_tdep, ev_t_dep)
-    GATHER(int, ss_phases, ev_phases)
-    GATHER(int, ss_lut, ev_lut)
-    GATHER(double, ss_cap0, ev_cap0)
-    GATHER(double, ss_B, ev_B)
-    GATHER(double, ss_des, ev_desired)
-    GATHER(double, ss_minB, ev_minB)
-    GATHER(double, ss_emerg, ev_min_emerg)
-    GATHER(double, ss_pacmax, ev_pac_max)
-    GATHER(double, ss_pacmin, ev_pac_min)
-    GATHER(double, ss_pdismax, ev_pdis_max)
-    GATHER(double, ss_pdismin, ev_pdis_min)
-    GATHER(double, ss_ts, ev_ts)
-    GATHER(double, ss_tsm, ev_tsm)
-    GATHER(double, ss_etach, ev_eta_ch)
-    GATHER(double, ss_etadis, ev_eta_dis)
-#undef GATHER
-    std::vector<int> ss_ntarr((size_t)SD, EV2G_INT_MAX), ss_ntdep((size_t)SD, EV2G_INT_MAX);
-    std::vector<double> ss_afap((size_t)SD), sess_afap_host((size_t)S);
-    for (long long d = 0; d + 1 < SD; d++) {
-        const long long a = dev_to_host[d], c = dev_to_host[d + 1];
-        if (a < 0 || c < 0) continue;   // (an unused slot of a refillable pool)
-        // same env and same port => the next device session is this port's next session
-        bool same_env = false;
-        {
-            // env of a host session: binary search in env_session_start
-            const int64_t *st = b->env_session_start;
-            const int64_t *ua = std::upper_bound(st, st + M + 1, (int64_t)a);
-            const int64_t *uc = std::upper_bound(st, st + M + 1, (int64_t)c);
-            same_env = (ua == uc);
-        }
-        if (same_env && sess_port[a] == sess_port[c]) {
-            ss_ntarr[d] = ss_tarr[d + 1];
-            ss_ntdep[d] = ss_tdep[d + 1];
-        }
-    }
-    std::vector<double> cs_maxp(C), cs_minp(C), cs_vk((size_t)C * 4), cs_dmax_abs(C);
-    for (int c = 0; c < C; c++) {
-        const double V = b->cs_voltage[c];
-        for (int k = 0; k < 4; k++) cs_vk[(size_t)c * 4 + k] = V * std::sqrt((double)k);
-        const double sq = std::sqrt((double)b->cs_phases[c]);
-        cs_maxp[c] = sq * V * b->cs_max_charge_current[c] / 1000;  // utils.py:779-782
-        cs_minp[c] = sq * V * b->cs_min_charge_current[c] / 1000;
-        cs_dmax_abs[c] = std::fabs(b->cs_max_discharge_current[c]);
-    }
-    for (long long s = 0; s < S; s++) {
-        const int cs = b->ev_cs[s];
-        // EV_Charger.get_max_power (ev_charger.py:251-252)
-        const double mp = b->cs_max_charge_current[cs] * b->cs_voltage[cs] * std::sqrt((double)b->cs_phases[cs]) / 1000;
-        sess_afap_host[s] = afap_energy(b, s, mp);
-        ss_afap[host_to_dev[s]] = sess_afap_host[s];
-    }
-    std::vector<double> tr_peak((size_t)M * R);
-    for (size_t er = 0; er < (size_t)M * R; er++) {
-        double m = b->tr_max_power[er * T];
-        for (int t = 1; t < T; t++) m = std::max(m, b->tr_max_power[er * T + t]);
-        tr_peak[er] = m;
-    }
-
-    // ---- launch geometry ----
+// Kernel routing and launch geometry.  Fast path (ev2g_step_wave): the common shape.  Anything else runs the general kernels; which one was
+// chosen, and why the fast path was not, is reported by ev2g_kernel_name() / ev2g_fallback_reason() -- routing is never silent.
+static int load_route(ev2g_handle *h, const LoadPlan &p, const LoadSwitches &sw) {
+    const int E = p.E, M = p.M, T = p.T, C = p.C, npc = p.npc, P = p.P, R = p.R, D = p.D, sk = h->cfg.state_kind;
     DevScn &s = h->scn;
     s = DevScn{};
-    s.E = E; s.M = M; s.T = T; s.C = C; s.npc = npc; s.P = P; s.R = R; s.D = D; s.ND = std::max(ND, 1); s.dt = b->timescale;
-    s.reward_kind = h->cfg.reward_kind; s.state_kind = sk; s.flags = h->cfg.flags; s.cost_kind = h->cfg.cost_kind; s.n_lut = b->n_lut;
+    s.E = E; s.M = M; s.T = T; s.C = C; s.npc = npc; s.P = P; s.R = R; s.D = D; s.ND = std::max(p.ND, 1); s.dt = p.dt;
+    s.reward_kind = h->cfg.reward_kind; s.state_kind = sk; s.flags = h->cfg.flags; s.cost_kind = h->cfg.cost_kind; s.n_lut = p.n_lut;
+    s.het = p.het ? 1 : 0;
     // v2 kernel: one home lane per port, BLOCK >= P; the generic kernel handles larger envs
-    h->block = het ? 0 : (P <= 256) ? 256 : (P <= 512) ? 512 : (P <= 1024) ? 1024 : 0;   // different port counts per charger: generic kernel
+    h->block = p.het ? 0 : (P <= 256) ? 256 : (P <= 512) ? 512 : (P <= 1024) ? 1024 : 0;   // different port counts per charger: generic kernel
     const int blk = h->block ? h->block : EV2G_BLOCK;
     s.G = std::max(1, blk / P);
     s.G = std::min(s.G, E);
-    // fast path (ev2g_step_wave): the common shape.  Anything else runs the general kernels; which one was chosen, and why the
-    // fast path was not, is reported by ev2g_kernel_name() / ev2g_fallback_reason() -- routing is never silent.
     h->fallback_reason.clear();
     if (P < 2 || P > 64) h->fallback_reason = "ports per env outside 2..64";
     else if (R != 1) h->fallback_reason = "more than one transformer";
     else if (npc != 1) h->fallback_reason = "multi-port chargers";
-    if (het) h->fallback_reason = "chargers with different port counts (topology file)";
+    if (p.het) h->fallback_reason = "chargers with different port counts (topology file)";
     h->wave_path = h->fallback_reason.empty();
-    h->no_full = std::getenv("EV2G_NO_FULL") != nullptr; h->no_wide = std::getenv("EV2G_NO_WIDE") != nullptr; h->last_spec = -1;
-    h->no_strided = std::getenv("EV2G_NO_STRIDED") != nullptr;
-    h->no_inl_stats = std::getenv("EV2G_NO_INLAUNCH_STATS") != nullptr; h->inl_stats = false; h->last_stats_route = -1; h->inl_reason = "no step launch since the scenarios were loaded";
+    h->no_full = sw.no_full; h->no_wide = sw.no_wide; h->last_spec = -1;
+    h->no_strided = sw.no_strided;
+    h->no_inl_stats = sw.no_inl_stats; h->inl_stats = false; h->last_stats_route = -1; h->inl_reason = "no step launch since the scenarios were loaded";
     h->state_epoch += 1;
     if (h->wave_path) {   // ev2g_step_wave addresses every array as base + 32-bit byte offset: all of them must stay below 4 GiB
         const unsigned long long lim = 1ull << 32;
         const unsigned long long biggest = std::max({(unsigned long long)E * P * 8, (unsigned long long)E * D * 8,
-                                                     (unsigned long long)M * (T + 1) * 60 * 8, (unsigned long long)SD * sizeof(SessRec),
+                                                     (unsigned long long)M * (T + 1) * 60 * 8, (unsigned long long)p.SD * sizeof(SessRec),
                                                      (unsigned long long)M * T * 64, (unsigned long long)E * T * 8 * 3, (unsigned long long)M * P * 8, (unsigned long long)E * P * sizeof(PortLine),
                                                      (h->cfg.flags & EV2G_FLAG_LOG_SOC) ? (unsigned long long)E * T * P * 8 : 0ull,
                                                      (h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) ? (unsigned long long)T * E * C * 8 : 0ull});
@@ -707,12 +446,10 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
         h->wave_epw = 64 / P; h->wave_es = P;
         s.G = (EV2G_WAVE_BLOCK / 64) * h->wave_epw;
     }
-    {   // EV2G_KERNEL=v2 forces the general kernel on the common shape (parity tests compare the two)
-        const char *kn = std::getenv("EV2G_KERNEL");
-        if (h->wave_path && kn && std::string(kn) == "v2") {
-            h->wave_path = false; h->fallback_reason = "EV2G_KERNEL=v2"; s.G = std::min(std::max(1, blk / P), E);
-        }
+    if (h->wave_path && sw.kernel_v2) {   // EV2G_KERNEL=v2 forces the general kernel on the common shape (parity tests compare the two)
+        h->wave_path = false; h->fallback_reason = "EV2G_KERNEL=v2"; s.G = std::min(std::max(1, blk / P), E);
     }
+    if (h->wave_path && p.n_lut > 4094) h->no_full = true;   // the full kernels keep table id + 1 in 12 bits of a port's LDS word
     {
         char nm[64];
         if (h->wave_path) std::snprintf(nm, sizeof nm, "ev2g_step_wave<%d,%d>", sk, std::min(h->cfg.reward_kind, 3));
@@ -722,12 +459,12 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     }
     {
         int gs = 4;
-        while (gs < 64 && gs < max_seg) gs <<= 1;
+        while (gs < 64 && gs < p.max_seg) gs <<= 1;
         s.gs = gs;
     }
     s.n_groups = (E + s.G - 1) / s.G;
-    s.sixty_over_dt = 60.0 / (double)b->timescale;
-    s.dt_over_60 = (double)b->timescale / 60.0;
+    s.sixty_over_dt = 60.0 / (double)p.dt;
+    s.dt_over_60 = (double)p.dt / 60.0;
     if (h->wave_path)
         h->lds_bytes = ev2g_wave_lds_bytes(s.G);
     else if (h->block)
@@ -736,174 +473,83 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
         h->lds_bytes = ev2g_generic_lds_bytes(s.G, P, R, npc);
     if (h->lds_bytes > 160 * 1024)
         return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: ports per env exceed the LDS staging capacity (P <= ~2400)");
-    {
-        const void *fn = h->block == 256 ? (const void *)ev2g_step_v2<256>
-                         : h->block == 512 ? (const void *)ev2g_step_v2<512>
-                         : h->block == 1024 ? (const void *)ev2g_step_v2<1024> : (const void *)ev2g_step_kernel;
-        if (h->lds_bytes > 48 * 1024)
-            HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        const void *fs = h->block == 256 ? (const void *)ev2g_step_v2<256, 1>
-                         : h->block == 512 ? (const void *)ev2g_step_v2<512, 1>
-                         : h->block == 1024 ? (const void *)ev2g_step_v2<1024, 1> : nullptr;
-        if (fs && h->lds_bytes > 48 * 1024)
-            HIPCHK(h, hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    }
-    // AoS session records (one cache line each) for the v2 kernel
-    std::vector<SessRec> recs((size_t)std::max<long long>(SD, 1));
-    std::vector<SessTail> tails((size_t)std::max<long long>(SD, 1));
-    std::memset(recs.data(), 0, recs.size() * sizeof(SessRec));
-    std::memset(tails.data(), 0, tails.size() * sizeof(SessTail));
-    for (long long d = 0; d < SD; d++) {
-        const long long hs = dev_to_host[d];
-        if (hs < 0) continue;
-        const int cs = b->ev_cs[hs];
-        SessRec &r = recs[d];
-        r.B = ss_B[d]; r.cap0 = ss_cap0[d]; r.minB = ss_minB[d]; r.emerg = ss_emerg[d];
-        r.pacmax = ss_pacmax[d]; r.pdismax = ss_pdismax[d]; r.ts = ss_ts[d]; r.tsm = ss_tsm[d];
-        r.eta_ch = ss_etach[d]; r.eta_dis = ss_etadis[d];
-        const double v_gate = cs_vk[(size_t)cs * 4 + b->cs_phases[cs]];
-        r.gate_ch = ss_pacmin[d] * 1000.0 / v_gate;
-        r.gate_dis = ss_pdismin[d] * 1000.0 / v_gate;
-        r.v = cs_vk[(size_t)cs * 4 + std::min(b->cs_phases[cs], ss_phases[d])];
-        r.rB = 1.0 / r.B; r.rv = 1.0 / r.v;   // correctly rounded reciprocals (IEEE division): what ev2g_fdiv2 divides through
-        {   // this EV's charge-power-potential term before the charger clamp (utils.py:773-777), the reference's operations in its order
-            const double evc = r.pacmax * 1000.0 / r.v, imax = b->cs_max_charge_current[cs];
-            r.potc = r.v * ((evc < imax) ? evc : imax) / 1000.0;
-        }
-        tails[d].des = ss_des[d]; tails[d].nt_arr = ss_ntarr[d]; tails[d].nt_dep = ss_ntdep[d];
-    }
-    // Battery-maths dictionary (fast path): the distinct (car model x charger kind) operand tuples of the batch, and per session what is left
-    // (SessDyn).  More than EV2G_CLS_CAP tuples (arbitrary ev_* arrays through the ABI), or EV2G_NO_DICT: one ClsRec per session, entry = session.
-    std::vector<SessDyn> dyns((size_t)std::max<long long>(SD, 1));
-    std::memset(dyns.data(), 0, dyns.size() * sizeof(SessDyn));
-    std::vector<ClsRec> cls_tab;
-    h->cls_map.clear();
-    bool dict = h->wave_path && std::getenv("EV2G_NO_DICT") == nullptr;
-    if (h->wave_path) {
-        for (long long d = 0; d < SD && dict; d++) {
-            if (dev_to_host[d] < 0) continue;
-            const int k = cls_find_or_add(h->cls_map, cls_tab, ev2g_cls_of(recs[d]));
-            if (k < 0) { dict = false; break; }
-            dyns[d].cls = k;
-        }
-        if (!dict) {
-            h->cls_map.clear();
-            cls_tab.assign((size_t)std::max<long long>(SD, 1), ClsRec{});
-            for (long long d = 0; d < SD; d++) if (dev_to_host[d] >= 0) { cls_tab[d] = ev2g_cls_of(recs[d]); dyns[d].cls = (int)d; }
-        } else
-            cls_tab.resize(EV2G_CLS_CAP, ClsRec{});   // room for the classes a device refill may add
-        for (long long d = 0; d < SD; d++) {
-            if (dev_to_host[d] < 0) continue;
-            dyns[d].ts = ss_ts[d]; dyns[d].eta_ch = ss_etach[d]; dyns[d].eta_dis = ss_etadis[d]; dyns[d].lut = ss_lut[d];
-        }
-        if (b->n_lut > 4094) h->no_full = true;   // the full kernels keep table id + 1 in 12 bits of a port's LDS word
-    }
+    const void *fn = h->block == 256 ? (const void *)ev2g_step_v2<256>
+                     : h->block == 512 ? (const void *)ev2g_step_v2<512>
+                     : h->block == 1024 ? (const void *)ev2g_step_v2<1024> : (const void *)ev2g_step_kernel;
+    if (h->lds_bytes > 48 * 1024)
+        HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    const void *fs = h->block == 256 ? (const void *)ev2g_step_v2<256, 1>
+                     : h->block == 512 ? (const void *)ev2g_step_v2<512, 1>
+                     : h->block == 1024 ? (const void *)ev2g_step_v2<1024, 1> : nullptr;
+    if (fs && h->lds_bytes > 48 * 1024)
+        HIPCHK(h, hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    return EV2G_OK;
+}
 
-    // ---- upload ----
+// ev2g_step_big (ev2g_step_big.h): big single-env workgroups with two ports per home lane.  What it needs beyond the launch-time conditions
+// of the specialised instantiation: single-port chargers, at most 50 transformers, at most EV2G_BIG_NCC distinct charger tuples, windows that fit
+// 16-bit step numbers.  EV2G_NO_BIG keeps ev2g_step_v2<1024> (A/B runs, parity tests).
+static int load_route_big(ev2g_handle *h, LoadPlan &p, const ev2g_scenario_batch *b, const LoadSwitches &sw) {
+    h->big_path = false; h->big_reason.clear(); h->big_args = BigArgs{};
+    if (h->block != 1024 || h->wave_path) return EV2G_OK;
+    load_plan_big(p, b, EV2G_BIG_NCC);
+    const size_t lb = ev2g_big_lds_bytes(p.P, p.R);
+    if (sw.no_big) h->big_reason = "EV2G_NO_BIG is set";
+    else if (p.npc != 1) h->big_reason = "multi-port chargers";
+    else if (h->cfg.state_kind != EV2G_STATE_V2G_PROFIT_MAX_LOADS) h->big_reason = "the state function is not V2G_profit_max_loads";
+    else if (20 * p.R + 20 > 2 * EV2G_BIG_BLOCK) h->big_reason = "more than 50 transformers (their 20 R window-column pairs + 20 price columns ride in 1024 pair slots)";
+    else if (p.many) h->big_reason = "more than 16 distinct charger constant tuples";
+    else if (p.tmax > EV2G_BIG_TMAX / 2 || p.tmin < -1) h->big_reason = "a session window or the episode length exceeds 16383 steps";
+    else if (!p.even || p.D >= 65536) h->big_reason = "observation columns are not 16-byte aligned pairs";
+    else if (lb > 80 * 1024) h->big_reason = "the port state exceeds half of a CU's LDS";
+    else if (p.E < 1) h->big_reason = "no envs";
+    else {
+        h->big_args.ncc = (int)(p.ctab.size() / 6);
+        h->lds_big = lb; h->big_path = true;
+        HIPCHK(h, hipFuncSetAttribute((const void *)ev2g_step_big<EV2G_BIG_BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
+    }
+    return EV2G_OK;
+}
+
+// Copies the plan and the batch's own arrays to the device (asynchronously: the plan outlives the stream synchronisation that ends the load).
+// *d_lut_eta: the efficiency tables as efficiencies, what V2P::lut points at.
+static int load_upload(ev2g_handle *h, const LoadPlan &p, const ev2g_scenario_batch *b, double **d_lut_eta) {
+    DevScn &s = h->scn;
     auto &pool = h->scn_allocs;
+    const int M = p.M, T = p.T, C = p.C, R = p.R;
     int rc = 0;
 #define UP(dst, vec) if ((rc = upload(h, pool, (vec).data(), (vec).size(), &(dst)))) return rc;
 #define UPP(dst, ptr, n) if ((rc = upload(h, pool, (ptr), (size_t)(n), &(dst)))) return rc;
-    int *ip; double *dp; int2 *i2p;
-    UP(ip, slot_port) s.slot_port = ip;
-    UP(ip, slot_cs) s.slot_cs = ip;
-    UP(ip, slot_obs) s.slot_obs = ip;
-    UP(ip, slot_tr) s.slot_tr = ip;
-    UP(ip, slot_mask) s.slot_mask = ip;
-    UP(ip, np_of) s.cs_np = ip;
-    UP(ip, pbase) s.cs_pbase = ip;
-    {
-        std::vector<int> cs_slot0(C);
-        for (int c = 0; c < C; c++) cs_slot0[c] = port_slot[pbase[c]];
-        UP(ip, cs_slot0) s.cs_slot0 = ip;
-    }
-    s.het = het ? 1 : 0;
+    int *ip; double *dp;
+    UP(ip, p.slot_port) s.slot_port = ip;
+    UP(ip, p.slot_cs) s.slot_cs = ip;
+    UP(ip, p.slot_obs) s.slot_obs = ip;
+    UP(ip, p.slot_tr) s.slot_tr = ip;
+    UP(ip, p.slot_mask) s.slot_mask = ip;
+    UP(ip, p.np_of) s.cs_np = ip;
+    UP(ip, p.pbase) s.cs_pbase = ip;
+    UP(ip, p.cs_slot0) s.cs_slot0 = ip;
     UPP(dp, b->cs_min_charge_current, C) s.cs_imin = dp;
     UPP(dp, b->cs_max_charge_current, C) s.cs_imax = dp;
     UPP(dp, b->cs_min_discharge_current, C) s.cs_dmin = dp;
-    UP(dp, cs_dmax_abs) s.cs_dmax_abs = dp;
+    UP(dp, p.cs_dmax_abs) s.cs_dmax_abs = dp;
     UPP(dp, b->cs_voltage, C) s.cs_volt = dp;
-    UP(dp, cs_maxp) s.cs_maxp = dp;
-    UP(dp, cs_minp) s.cs_minp = dp;
-    UP(dp, cs_vk) s.cs_vk = dp;
-    {   // the heuristic agents' charger constants, evaluated like the reference: EV_Charger.get_max_power / get_min_charge_power
-        // (ev_charger.py:251-255), RoundRobin.average_power (heuristics.py:19-24) and RoundRobin_GF.min_action (heuristics.py:285-286:
-        // the loop leaves the LAST charger's) -- not cs_maxp / cs_minp, whose operation order rounds differently
-        std::vector<double> cs_kw(C), cs_min_kw(C);
-        double total = 0.0;
-        for (int c = 0; c < C; c++) {
-            const double I = b->cs_max_charge_current[c], V = b->cs_voltage[c], sq = std::sqrt((double)b->cs_phases[c]);
-            cs_kw[c] = I * V * sq / 1000;
-            cs_min_kw[c] = b->cs_min_charge_current[c] * V * sq / 1000;
-            total += I * V * sq / (double)np_of[c];
-        }
-        h->heur_avg_power = total / (double)C;
-        h->heur_min_action = b->cs_min_charge_current[C - 1] / b->cs_max_charge_current[C - 1] + 1e-4;
-        UP(dp, cs_kw) h->d_heur_cs_kw = dp;
-        UP(dp, cs_min_kw) h->d_heur_cs_min_kw = dp;
-        UP(ip, port_slot) h->d_port_slot = ip;
-    }
-    {   // the six per-charger operands of the fast path side by side: (imax, |dmax|), (imin, dmin), (max power, min power)
-        std::vector<double> cs_pack((size_t)C * 6);
-        for (int c = 0; c < C; c++) {
-            double *r = &cs_pack[(size_t)c * 6];
-            r[0] = b->cs_max_charge_current[c]; r[1] = cs_dmax_abs[c]; r[2] = b->cs_min_charge_current[c];
-            r[3] = b->cs_min_discharge_current[c]; r[4] = cs_maxp[c]; r[5] = cs_minp[c];
-        }
-        UP(dp, cs_pack) s.cs_pack = dp;
-    }
-    {   // ev2g_step_big (ev2g_step_big.h): big single-env workgroups with two ports per home lane.  What it needs beyond the launch-time conditions
-        // of the specialised instantiation: single-port chargers, at most 64 transformers, at most EV2G_BIG_NCC distinct charger tuples, windows that fit
-        // 16-bit step numbers.  EV2G_NO_BIG keeps ev2g_step_v2<1024> (A/B runs, parity tests).
-        h->big_path = false; h->big_reason.clear(); h->big_args = BigArgs{};
-        if (h->block == 1024 && !h->wave_path) {
-            std::vector<unsigned char> ccls(P);
-            std::vector<double> ctab;
-            bool many = false;
-            for (int q = 0; q < P && !many; q++) {
-                const int c = slot_cs[q];
-                const double r[6] = {b->cs_max_charge_current[c], b->cs_min_charge_current[c], b->cs_min_discharge_current[c], cs_dmax_abs[c], cs_maxp[c], cs_minp[c]};
-                int k = 0;
-                const int n = (int)(ctab.size() / 6);
-                while (k < n && std::memcmp(&ctab[(size_t)k * 6], r, sizeof r) != 0) k++;
-                if (k == n) { if (n == EV2G_BIG_NCC) { many = true; break; } ctab.insert(ctab.end(), r, r + 6); }
-                ccls[q] = (unsigned char)k;
-            }
-            int tmax = T, tmin = 0;
-            for (long long d = 0; d < SD; d++) if (dev_to_host[d] >= 0) { tmax = std::max({tmax, ss_tarr[d], ss_tdep[d]}); tmin = std::min({tmin, ss_tarr[d], ss_tdep[d]}); }
-            bool even = D % 2 == 0;
-            for (int q = 0; q < P; q++) even = even && slot_obs[q] % 2 == 0;
-            const size_t lb = ev2g_big_lds_bytes(P, R);
-            if (std::getenv("EV2G_NO_BIG")) h->big_reason = "EV2G_NO_BIG is set";
-            else if (npc != 1) h->big_reason = "multi-port chargers";
-            else if (sk != EV2G_STATE_V2G_PROFIT_MAX_LOADS) h->big_reason = "the state function is not V2G_profit_max_loads";
-            else if (20 * R + 20 > 2 * EV2G_BIG_BLOCK) h->big_reason = "more than 50 transformers (their 20 R window-column pairs + 20 price columns ride in 1024 pair slots)";
-            else if (many) h->big_reason = "more than 16 distinct charger constant tuples";
-            else if (tmax > EV2G_BIG_TMAX / 2 || tmin < -1) h->big_reason = "a session window or the episode length exceeds 16383 steps";
-            else if (!even || D >= 65536) h->big_reason = "observation columns are not 16-byte aligned pairs";
-            else if (lb > 80 * 1024) h->big_reason = "the port state exceeds half of a CU's LDS";
-            else if (E < 1) h->big_reason = "no envs";
-            else {
-                unsigned char *cp; UP(cp, ccls) h->big_args.slot_ccls = cp;
-                UP(dp, ctab) h->big_args.ccls_tab = dp;
-                std::vector<double> ptab(15, std::nan(""));   // the distinct potential terms of the loaded sessions (the first 15: any other value is fetched from the state line)
-                int npot = 0;
-                for (long long d = 0; d < SD && npot < 15; d++) {
-                    if (dev_to_host[d] < 0) continue;
-                    int k = 0;
-                    while (k < npot && ptab[(size_t)k] != recs[d].potc) k++;
-                    if (k == npot) ptab[(size_t)npot++] = recs[d].potc;
-                }
-                UP(dp, ptab) h->big_args.potc_tab = dp;
-                h->big_args.ncc = (int)(ctab.size() / 6);
-                h->lds_big = lb; h->big_path = true;
-                HIPCHK(h, hipFuncSetAttribute((const void *)ev2g_step_big<EV2G_BIG_BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-            }
-        }
+    UP(dp, p.cs_maxp) s.cs_maxp = dp;
+    UP(dp, p.cs_minp) s.cs_minp = dp;
+    UP(dp, p.cs_vk) s.cs_vk = dp;
+    h->heur_avg_power = p.avg_power; h->heur_min_action = p.min_action;
+    UP(dp, p.cs_kw) h->d_heur_cs_kw = dp;
+    UP(dp, p.cs_min_kw) h->d_heur_cs_min_kw = dp;
+    UP(ip, p.port_slot) h->d_port_slot = ip;
+    UP(dp, p.cs_pack) s.cs_pack = dp;
+    if (h->big_path) {
+        unsigned char *cp; UP(cp, p.ccls) h->big_args.slot_ccls = cp;
+        UP(dp, p.ctab) h->big_args.ccls_tab = dp;
+        UP(dp, p.ptab) h->big_args.potc_tab = dp;
     }
     UPP(ip, b->cs_phases, C) s.cs_ph = ip;
-    UP(ip, tr_seg) s.tr_seg = ip;
-    UP(ip, tr_obs) s.tr_obs = ip;
+    UP(ip, p.tr_seg) s.tr_seg = ip;
+    UP(ip, p.tr_obs) s.tr_obs = ip;
     UPP(dp, b->charge_price, (size_t)M * T) s.price_ch = dp;
     UPP(dp, b->discharge_price, (size_t)M * T) s.price_dis = dp;
     UPP(dp, b->power_setpoints, (size_t)M * T) s.setpoint = dp;
@@ -913,64 +559,60 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     UPP(dp, b->tr_solar_power, (size_t)M * R * T) s.tr_solar = dp;
     UPP(dp, b->tr_load_forecast, (size_t)M * R * T) s.tr_lf = dp;
     UPP(dp, b->tr_pv_forecast, (size_t)M * R * T) s.tr_pvf = dp;
-    UP(dp, tr_peak) s.tr_peak = dp;
-    {
-        std::vector<double> tr_base((size_t)M * R * T);
-        for (size_t i = 0; i < tr_base.size(); i++) tr_base[i] = b->tr_inflexible_load[i] + b->tr_solar_power[i];
-        UP(dp, tr_base) s.tr_base = dp;
-    }
-    UPP(dp, b->tr_dr, (size_t)M * R * ND * 3) s.tr_dr = dp;
+    UP(dp, p.tr_peak) s.tr_peak = dp;
+    UP(dp, p.tr_base) s.tr_base = dp;
+    UPP(dp, b->tr_dr, (size_t)M * R * p.ND * 3) s.tr_dr = dp;
     UPP(ip, b->tr_n_dr, (size_t)M * R) s.tr_ndr = ip;
     UPP(ip, b->tr_steps_ahead, (size_t)M * R) s.tr_ahead = ip;
-    UP(ip, ss_tarr) s.ss_tarr = ip;
-    UP(ip, ss_tdep) s.ss_tdep = ip;
-    UP(ip, ss_ntarr) s.ss_ntarr = ip;
-    UP(ip, ss_ntdep) s.ss_ntdep = ip;
-    UP(ip, ss_phases) s.ss_phases = ip;
-    UP(ip, ss_lut) s.ss_lut = ip;
-    UP(dp, ss_cap0) s.ss_cap0 = dp;
-    UP(dp, ss_B) s.ss_B = dp;
-    UP(dp, ss_des) s.ss_des = dp;
-    UP(dp, ss_minB) s.ss_minB = dp;
-    UP(dp, ss_emerg) s.ss_emerg = dp;
-    UP(dp, ss_pacmax) s.ss_pacmax = dp;
-    UP(dp, ss_pacmin) s.ss_pacmin = dp;
-    UP(dp, ss_pdismax) s.ss_pdismax = dp;
-    UP(dp, ss_pdismin) s.ss_pdismin = dp;
-    UP(dp, ss_ts) s.ss_ts = dp;
-    UP(dp, ss_tsm) s.ss_tsm = dp;
-    UP(dp, ss_etach) s.ss_etach = dp;
-    UP(dp, ss_etadis) s.ss_etadis = dp;
-    UPP(dp, b->lut, (size_t)b->n_lut * EV2G_LUT_LEN) s.lut = dp;
-    // the same tables as efficiencies (percent / 100, the division of ev.py:290,379 done once): what V2P::lut points at
-    std::vector<double> lut_eta((size_t)b->n_lut * EV2G_LUT_LEN);
-    for (size_t i = 0; i < lut_eta.size(); i++) lut_eta[i] = b->lut[i] / 100.0;
-    double *d_lut_eta = nullptr;
-    UP(d_lut_eta, lut_eta)
-    {   // the largest entry of every efficiency table (percent): what EV.calculate_max_energy_with_AFAP uses (ev.py:418-421); device-side refills need it
-        std::vector<double> rowmax((size_t)std::max(b->n_lut, 1), 0.0);
-        for (int l = 0; l < b->n_lut; l++)
-            for (int k = 0; k < EV2G_LUT_LEN; k++) rowmax[l] = std::max(rowmax[l], b->lut[(size_t)l * EV2G_LUT_LEN + k]);
-        UP(dp, rowmax) h->d_lut_rowmax = dp;
-    }
-    h->refilled = false;
-    UP(ip, port_first) s.port_first = ip;
-    UP(ip, port_end) s.port_end = ip;
-    UP(ip, ss_slot) s.ss_slot = ip;
-    UP(ip, scn_sess) s.scn_sess = ip;
-    UP(ip, scn_sess_end) s.scn_sess_end = ip;
-    UP(i2p, port_first_win) s.port_first_win = i2p;
-    UP(dp, ss_afap) h->d_ss_afap = dp;
-    { SessRec *rp; UP(rp, recs) s.rec = rp; }
-    { SessTail *tp; UP(tp, tails) s.tail = tp; }
+    UP(ip, p.ss_tarr) s.ss_tarr = ip;
+    UP(ip, p.ss_tdep) s.ss_tdep = ip;
+    UP(ip, p.ss_ntarr) s.ss_ntarr = ip;
+    UP(ip, p.ss_ntdep) s.ss_ntdep = ip;
+    UP(ip, p.ss_phases) s.ss_phases = ip;
+    UP(ip, p.ss_lut) s.ss_lut = ip;
+    UP(dp, p.ss_cap0) s.ss_cap0 = dp;
+    UP(dp, p.ss_B) s.ss_B = dp;
+    UP(dp, p.ss_des) s.ss_des = dp;
+    UP(dp, p.ss_minB) s.ss_minB = dp;
+    UP(dp, p.ss_emerg) s.ss_emerg = dp;
+    UP(dp, p.ss_pacmax) s.ss_pacmax = dp;
+    UP(dp, p.ss_pacmin) s.ss_pacmin = dp;
+    UP(dp, p.ss_pdismax) s.ss_pdismax = dp;
+    UP(dp, p.ss_pdismin) s.ss_pdismin = dp;
+    UP(dp, p.ss_ts) s.ss_ts = dp;
+    UP(dp, p.ss_tsm) s.ss_tsm = dp;
+    UP(dp, p.ss_etach) s.ss_etach = dp;
+    UP(dp, p.ss_etadis) s.ss_etadis = dp;
+    UPP(dp, b->lut, (size_t)p.n_lut * EV2G_LUT_LEN) s.lut = dp;
+    UP(*d_lut_eta, p.lut_eta)
+    UP(dp, p.rowmax) h->d_lut_rowmax = dp;
+    UP(ip, p.port_first) s.port_first = ip;
+    UP(ip, p.port_end) s.port_end = ip;
+    UP(ip, p.ss_slot) s.ss_slot = ip;
+    UP(ip, p.scn_sess) s.scn_sess = ip;
+    UP(ip, p.scn_sess_end) s.scn_sess_end = ip;
+    static_assert(sizeof(IntPair) == sizeof(int2), "port_first_win is uploaded as int2");
+    { int2 *i2p; UPP(i2p, (const int2 *)p.port_first_win.data(), p.port_first_win.size()) s.port_first_win = i2p; }
+    UP(dp, p.ss_afap) h->d_ss_afap = dp;
+    { SessRec *rp; UP(rp, p.recs) s.rec = rp; }
+    { SessTail *tp; UP(tp, p.tails) s.tail = tp; }
     s.sess_dyn = nullptr; s.cls_rec = nullptr; s.dict = 0; s.n_cls = 0; h->d_cls_rec = nullptr;
     if (h->wave_path) {
-        SessDyn *dp2; UP(dp2, dyns) s.sess_dyn = dp2;
-        ClsRec *cp; UP(cp, cls_tab) s.cls_rec = cp; h->d_cls_rec = cp;
-        s.dict = dict ? 1 : 0; s.n_cls = dict ? (int)h->cls_map.size() : 0;
+        SessDyn *dp2; UP(dp2, p.dyns) s.sess_dyn = dp2;
+        ClsRec *cp; UP(cp, p.cls_tab) s.cls_rec = cp; h->d_cls_rec = cp;
+        s.dict = p.dict ? 1 : 0; s.n_cls = p.dict ? (int)p.cls_map.size() : 0;
     }
 #undef UP
 #undef UPP
+    return EV2G_OK;
+}
+
+// The tables the device builds from the uploaded scenarios: the forecast / limit windows of the V2G_profit_max_loads state, and the
+// fast path's step table (with its occupancy masks) and observation head table.
+static int load_build_tables(ev2g_handle *h) {
+    DevScn &s = h->scn;
+    auto &pool = h->scn_allocs;
+    const int M = s.M, T = s.T, R = s.R, sk = s.state_kind;
     s.win_tab = nullptr;
     if (sk == EV2G_STATE_V2G_PROFIT_MAX_LOADS && h->block) {
         double *tab = nullptr;
@@ -982,9 +624,9 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
         HIPCHK(h, hipGetLastError());
         s.win_tab = tab;
     }
-    double *d_step_tab = nullptr;
     h->d_step_tab = nullptr;
     if (h->wave_path) {   // R == 1: [M,T] series interleaved per (env, step)
+        double *d_step_tab = nullptr;
         const size_t n = (size_t)M * T * 8;
         HIPCHK(h, hipMalloc((void **)&d_step_tab, n * sizeof(double)));
         pool.push_back(d_step_tab);
@@ -995,10 +637,10 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
         HIPCHK(h, hipGetLastError());
         h->d_step_tab = d_step_tab;
     }
-    double *d_head_tab = nullptr;
     h->d_head_tab = nullptr; h->head_nh = 0;
     s.head_tab = nullptr; s.head_nh = 0;
     if (h->wave_path && sk != EV2G_STATE_PUBLIC_PST) {
+        double *d_head_tab = nullptr;
         const int NH = (sk == EV2G_STATE_V2G_PROFIT_MAX_LOADS) ? 60 : 20;
         const size_t n = (size_t)M * (T + 1) * NH;
         HIPCHK(h, hipMalloc((void **)&d_head_tab, n * sizeof(double)));
@@ -1009,11 +651,18 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
         h->d_head_tab = d_head_tab; h->head_nh = NH;
         s.head_tab = d_head_tab; s.head_nh = NH;   // (the reset observation copies its head from row 0, write_obs_env)
     }
-    // ---- state ----
+    return EV2G_OK;
+}
+
+// The envs' state (zeroed), for `SD` device session slots
+static int load_alloc_state(ev2g_handle *h, long long SD) {
+    const DevScn &s = h->scn;
     DevState &st = h->st;
     st = DevState{};
     auto &sp = h->st_allocs;
-    const size_t EP = (size_t)E * P, EC = (size_t)E * C;
+    const int E = s.E, T = s.T, R = s.R;
+    const size_t EP = (size_t)E * s.P, EC = (size_t)E * s.C;
+    int rc = 0;
 #define AL(field, n) if ((rc = dalloc(h, sp, (size_t)(n), &st.field))) return rc;
     {   // per-port state: one 64-byte line per port + one slab of EV2G_PS_* slices for what is not on the step's path
         AL(line, EP)
@@ -1042,42 +691,88 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     AL(dbg, (size_t)s.n_groups * 18)
 #endif
 #undef AL
-    {
-        V2P v2p;
-        ev2g_v2_fill_params(v2p, h->scn, h->st);
-        EV2G_SETP(v2p.lut, d_lut_eta);
-        EV2G_SETP(v2p.head_tab, d_head_tab);
-        EV2G_SETP(v2p.step_tab, d_step_tab);
-        EV2G_SETP(v2p.ss_afap, h->d_ss_afap);
-        int ex = 0;   // 60/dt a power of two and dt/60 its exact reciprocal -> divisions by them are multiplications
-        v2p.pow2_dt = (std::frexp(h->scn.sixty_over_dt, &ex) == 0.5 && h->scn.sixty_over_dt * h->scn.dt_over_60 == 1.0) ? 1 : 0;
-        h->pow2_dt = v2p.pow2_dt != 0;
-        if ((rc = upload(h, sp, &v2p, 1, &h->d_v2p))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // host staging vectors die here
+    return EV2G_OK;
+}
 
-    h->E = E; h->M = M; h->scn_off = 0; h->T = T; h->C = C; h->npc = npc; h->P = P; h->R = R; h->D = D; h->S = S;
-    {   // the in-launch statistics phase: a shape the statistics kernel runs with one env per wavefront (its summation order), like the phase
-        h->d_stats_inl = nullptr;
-        const char *why = "";
-        if (h->no_inl_stats) why = "EV2G_NO_INLAUNCH_STATS is set";
-        else if (!h->wave_path || !(h->cfg.flags & EV2G_FLAG_LOG_SOC)) why = "the step kernel is not ev2g_step_wave with the SoC log";
-        else if (h->wave_epw != 1 || stats_pair(h)) why = "several envs per wavefront (the in-launch phase computes one env per wavefront, like the statistics kernel at this shape)";
-        else if (h->lds_bytes < ev2g_inl_stats_lds_bytes()) why = "the step kernel's LDS is smaller than the phase's blocks";
-        h->inl_shape_reason = why;
-        if (!why[0]) {
-            if ((rc = dalloc(h, sp, (size_t)E * EV2G_N_STATS, &h->d_stats_inl))) return rc;
-            double *p = h->d_stats_inl;
-            HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, stats_inl), &p, sizeof p, hipMemcpyHostToDevice));
-        }
+// The device copy of the v2 kernels' parameter block.  `v2p` is the caller's: the copy is asynchronous, so the block lives where the
+// stream synchronisation that ends the load is.
+static int load_params(ev2g_handle *h, double *d_lut_eta, V2P &v2p) {
+    ev2g_v2_fill_params(v2p, h->scn, h->st);
+    EV2G_SETP(v2p.lut, d_lut_eta);
+    EV2G_SETP(v2p.head_tab, h->d_head_tab);
+    EV2G_SETP(v2p.step_tab, h->d_step_tab);
+    EV2G_SETP(v2p.ss_afap, h->d_ss_afap);
+    int ex = 0;   // 60/dt a power of two and dt/60 its exact reciprocal -> divisions by them are multiplications
+    v2p.pow2_dt = (std::frexp(h->scn.sixty_over_dt, &ex) == 0.5 && h->scn.sixty_over_dt * h->scn.dt_over_60 == 1.0) ? 1 : 0;
+    h->pow2_dt = v2p.pow2_dt != 0;
+    return upload(h, h->st_allocs, &v2p, 1, &h->d_v2p);
+}
+
+// The in-launch statistics phase: a shape the statistics kernel runs with one env per wavefront (its summation order), like the phase
+static int load_decide_inl_stats(ev2g_handle *h) {
+    h->d_stats_inl = nullptr;
+    const char *why = "";
+    if (h->no_inl_stats) why = "EV2G_NO_INLAUNCH_STATS is set";
+    else if (!h->wave_path || !(h->cfg.flags & EV2G_FLAG_LOG_SOC)) why = "the step kernel is not ev2g_step_wave with the SoC log";
+    else if (h->wave_epw != 1 || stats_pair(h)) why = "several envs per wavefront (the in-launch phase computes one env per wavefront, like the statistics kernel at this shape)";
+    else if (h->lds_bytes < ev2g_inl_stats_lds_bytes()) why = "the step kernel's LDS is smaller than the phase's blocks";
+    h->inl_shape_reason = why;
+    if (!why[0]) {
+        int rc = 0;
+        if ((rc = dalloc(h, h->st_allocs, (size_t)h->E * EV2G_N_STATS, &h->d_stats_inl))) return rc;
+        double *p = h->d_stats_inl;
+        HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, stats_inl), &p, sizeof p, hipMemcpyHostToDevice));
     }
-    h->slot_port = slot_port;
-    h->port_slot = port_slot;
-    h->env_sess_start.assign(b->env_session_start, b->env_session_start + M + 1);
-    h->host_to_dev = host_to_dev;
-    h->cs_vk_host = cs_vk; h->cs_ph_host.assign(b->cs_phases, b->cs_phases + C); h->load_gen += 1;
-    h->sess_port = sess_port;
-    h->sess_afap = sess_afap_host;
+    return EV2G_OK;
+}
+
+int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
+    if (!h || !b) return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: null argument");
+    (void)hipSetDevice(h->device);
+    const LoadSwitches sw = load_switches_from_env();
+    LoadPlan plan;   // the uploads copy out of its vectors, and out of v2p, asynchronously: every return below load_upload synchronises the stream first
+    V2P v2p;
+    std::string msg;
+    int rc = load_plan_check(plan, b, h->cfg, msg);
+    if (rc) return fail(h, rc, msg);   // (a pool loaded earlier stays loaded and usable; from here on a refusal leaves the handle unloaded)
+    (void)hipStreamSynchronize(h->stream);
+    drop_rollout_graphs(h);
+    free_pool(h->scn_allocs);
+    free_pool(h->st_allocs);
+    h->loaded = false;
+    h->cls_map.clear();
+
+    if ((rc = load_plan_layout(plan, b, h->cfg, sw, msg))) return fail(h, rc, msg);
+    h->sess_cap = (int)plan.cap;
+    if ((rc = load_plan_order(plan, b, msg))) return fail(h, rc, msg);
+    load_plan_constants(plan, b);
+    load_plan_records(plan, b);
+    if ((rc = load_route(h, plan, sw))) return rc;
+    load_plan_dictionary(plan, h->wave_path, sw);
+    if ((rc = load_route_big(h, plan, b, sw))) return rc;
+
+    double *d_lut_eta = nullptr;
+    rc = load_upload(h, plan, b, &d_lut_eta);
+    if (!rc) rc = load_build_tables(h);
+    if (!rc) rc = load_alloc_state(h, plan.SD);
+    if (!rc) rc = load_params(h, d_lut_eta, v2p);
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the plan's vectors and v2p are free to die from here
+
+    h->E = plan.E; h->M = plan.M; h->scn_off = 0; h->T = plan.T; h->C = plan.C; h->npc = plan.npc; h->P = plan.P; h->R = plan.R; h->D = plan.D; h->S = plan.S;
+    if ((rc = load_decide_inl_stats(h))) return rc;
+    // host mirrors for peek / stats / refill
+    h->slot_port = std::move(plan.slot_port);
+    h->port_slot = std::move(plan.port_slot);
+    h->env_sess_start.assign(b->env_session_start, b->env_session_start + plan.M + 1);
+    h->host_to_dev = std::move(plan.host_to_dev);
+    h->sess_port = std::move(plan.sess_port);
+    h->sess_afap = std::move(plan.sess_afap_host);
+    h->cls_map = std::move(plan.cls_map);
+    h->cs_vk_host = std::move(plan.cs_vk);
+    h->cs_ph_host.assign(b->cs_phases, b->cs_phases + plan.C);
+    h->cs_imax_host.assign(b->cs_max_charge_current, b->cs_max_charge_current + plan.C);
+    h->refilled = false; h->load_gen += 1;
     h->loaded = true;
     if (h->extras.cost || h->extras.obs_f32 || h->extras.actions_f32) {
         const ev2g_step_extras keep = h->extras;

@@ -106,14 +106,9 @@ static int ev2g_pool_refill_impl(ev2g_handle *h, const ev2g_gen_config *cfg, uin
                                  c.heterogeneous_ev_specs ? fleet.pac(m) : c.ev_max_ac_charge_power, 1.0};
                 const Ev2gSessFields f = ev2g_gen_session_fields(g, rng0, e, spec_row.empty() ? nullptr : spec_row.data());
                 for (int cs = 0; cs < s.C; cs++) {
-                    const int ph = h->cs_ph_host[(size_t)cs];
-                    const double v_gate = h->cs_vk_host[(size_t)cs * 4 + ph];
                     SessRec r{};
                     r.B = e.B; r.minB = f.minB; r.emerg = f.min_emerg; r.pacmax = e.pac; r.pdismax = f.pdis_max; r.tsm = f.tsm;
-                    r.gate_ch = f.pac_min * 1000.0 / v_gate;
-                    r.gate_dis = f.pdis_min * 1000.0 / v_gate;
-                    r.v = h->cs_vk_host[(size_t)cs * 4 + std::min(ph, f.phases)];
-                    r.rB = 1.0 / r.B; r.rv = 1.0 / r.v;
+                    ev2g_sess_consts(r, &h->cs_vk_host[(size_t)cs * 4], h->cs_ph_host[(size_t)cs], f.phases, f.pac_min, f.pdis_min, h->cs_imax_host[(size_t)cs]);
                     const int k = cls_find_or_add(h->cls_map, tab, ev2g_cls_of(r));
                     if (k < 0) {   // the entries this call added never reach the device: take them out of the host mirror again
                         for (auto it = h->cls_map.begin(); it != h->cls_map.end();) it = ((size_t)it->second >= n_before) ? h->cls_map.erase(it) : std::next(it);
