@@ -111,6 +111,15 @@ class StepExtrasC(C.Structure):
                 ("obs_f32_step_stride", C.c_int64), ("actions_f32", C.c_void_p)]
 
 
+class OnPolicyRowsC(C.Structure):   # ev2g_onpolicy_rows: the device arrays of an ev2g_ac_collect segment, in header order
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("values", C.c_void_p), ("log_probs", C.c_void_p),
+                ("reward", C.c_void_p), ("done", C.c_void_p), ("mask", C.c_void_p)]
+
+
+AC_ACTIVATIONS = {"tanh": 0, "relu": 1}   # EV2G_AC_TANH (SB3's default activation_fn) / EV2G_AC_RELU
+AC_MAX_IN, AC_MAX_HIDDEN, AC_MAX_OUT = 192, 256, 64   # the limits of ev2g_ac_create
+
+
 class EnvViewC(C.Structure):
     _fields_ = [
         ("current_step", C.c_int32), ("n_ports", C.c_int32), ("n_chargers", C.c_int32),

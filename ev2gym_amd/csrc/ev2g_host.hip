@@ -28,6 +28,7 @@
 #include "ev2g_link.h"
 #include "ev2g_grid.h"
 #include "ev2g_wrap.h"
+#include "ev2g_ac.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -111,6 +112,24 @@ struct ev2g_wrap {
 static void wrap_free(ev2g_wrap *w) {
     (void)hipFree(w->queue); (void)hipFree(w->qlen); (void)hipFree(w->qmin); (void)hipFree(w->qmax); (void)hipFree(w->act);
     delete w;
+}
+
+// a Gaussian actor-critic (ev2g_ac_create, ev2g_ac.h): the packed network, the noise stream's seed and launch counter, and the clipped action
+// block [E, P] the step of ev2g_ac_collect reads (allocated on first use)
+struct ev2g_acpolicy {
+    AcDev dev{};
+    std::vector<void *> allocs;
+    size_t lds = 0;
+    int relu = 0;
+    unsigned long long seed = 0, n = 0;
+    float *clipped = nullptr;
+    size_t clipped_elems = 0;
+};
+
+static void ac_free(ev2g_acpolicy *ac) {
+    for (void *p : ac->allocs) (void)hipFree(p);
+    (void)hipFree(ac->clipped);
+    delete ac;
 }
 
 #define EV2G_EV_RING 32
@@ -212,6 +231,8 @@ struct ev2g_handle {
     std::vector<ev2g_link *> links;             // the communication-fault links created on this handle (freed with it)
     std::vector<ev2g_grid *> grids;             // the distribution grids created on this handle (freed with it)
     std::vector<ev2g_wrap *> wraps;             // the action wrappers created on this handle (freed with it)
+    std::vector<ev2g_acpolicy *> acs;           // the Gaussian actor-critics created on this handle (freed with it)
+    unsigned ac_attr_mask = 0;                  // ev2g_ac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -366,6 +387,8 @@ void ev2g_destroy(ev2g_handle *h) {
     h->grids.clear();
     for (ev2g_wrap *w : h->wraps) wrap_free(w);
     h->wraps.clear();
+    for (ev2g_acpolicy *ac : h->acs) ac_free(ac);
+    h->acs.clear();
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
     for (int i = 0; i < EV2G_EV_RING; i++) { if (h->ev0s[i]) (void)hipEventDestroy(h->ev0s[i]); if (h->ev1s[i]) (void)hipEventDestroy(h->ev1s[i]); }
@@ -1011,6 +1034,12 @@ struct StepChain {
     // registered float32 action row -- into the wrapper's own float64 block or the caller's `wrapped` row, which the step then reads
     ev2g_wrap *wrap = nullptr;
     Rows<double> wrapped;
+    // a Gaussian actor-critic (not with a link, a grid or a wrapper): its sampling launch reads float32 observation row i of ac_obs and writes the
+    // sample, value and log-probability rows; the step reads the object's clipped block and writes observation row i + 1 -- per launch on the fast
+    // path (ac_direct), through the registered hand-over pair with device-to-device copies elsewhere (ev2g_collect's two routes)
+    ev2g_acpolicy *ac = nullptr;
+    bool ac_deterministic = false, ac_direct = false;
+    Rows<float> ac_obs, ac_actions, ac_values, ac_log_probs;
     Rows<double> obs, reward;   // every step's outputs
     Rows<uint8_t> done, mask;
     int auto_reset = 0;                // an episode end inside the segment (chain_steps; run_chain refuses it up front): 0 ends the call with EV2G_ERR_DONE
@@ -1020,6 +1049,8 @@ struct StepChain {
 static int chain_steps(ev2g_handle *h, const StepChain &c, int k);
 static int run_chain(ev2g_handle *h, StepChain c, int k);
 static int wrap_launch(ev2g_handle *h, ev2g_wrap *w, const void *in, bool in32, double *out);
+static int ac_launch(ev2g_handle *h, ev2g_acpolicy *ac, const float *x, int n_rows, bool sample, float *mean, float *actions, float *clipped,
+                     float *value, float *log_prob);
 
 int ev2g_step(ev2g_handle *h, const double *actions, double *obs, double *reward, uint8_t *done, uint8_t *action_mask) {
     if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_step: no scenarios loaded");
@@ -1447,6 +1478,15 @@ int ev2g_rollout(ev2g_handle *h, const ev2g_mlp *m, int k_steps, double *reward,
 
 long long ev2g_rollout_graph_launches(const ev2g_handle *h) { return h ? h->graph_launches : 0; }
 
+// The collectors' route (ev2g_collect's unfused loop, ev2g_ac_collect): true where a one-step launch can take float32 action and observation
+// rows of its own (StepIO::act32 / obs32) and gets the full instantiation for them -- the fast path with nothing registered, no charger
+// histories, a compiled-in reward; elsewhere the step works on the registered hand-over pair and the rows are copied around it.
+static bool collect_direct(const ev2g_handle *h) {
+    const ev2g_step_extras &x = h->extras;
+    return h->wave_path && !x.cost && !x.obs_f32 && !x.actions_f32 && !(h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) &&
+           std::min(h->scn.reward_kind, 3) != 3 && !h->no_full;
+}
+
 int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_transitions *tr) {
     if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_collect: no scenarios loaded");
     if (!m || !tr || k_steps < 0 || !tr->obs || !tr->actions || !tr->reward || !tr->done || !tr->mask)
@@ -1459,8 +1499,7 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
     // reads and writes the caller's rows directly.  Elsewhere (general kernels; run-time rewards; a registered cost buffer) the step
     // works on the registered hand-over buffers of ev2g_set_step_extras and the rows are copied device-to-device around it.
     const ev2g_step_extras &x = h->extras;
-    const bool direct = h->wave_path && !x.cost && !x.obs_f32 && !x.actions_f32 && !(h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) &&
-                        std::min(h->scn.reward_kind, 3) != 3 && !h->no_full;
+    const bool direct = collect_direct(h);
     if (!direct && !(x.obs_f32 && x.actions_f32 && x.obs_f32_step_stride == 0))
         return fail(h, EV2G_ERR_ARG, "ev2g_collect: this configuration steps through the registered float32 hand-over buffers: register them with "
                                      "ev2g_set_step_extras (observation step stride 0) first");
@@ -1855,7 +1894,7 @@ static int grid_state_check(ev2g_handle *h, ev2g_grid *g, const char *who) {
 }
 
 // ---- the runner of one-step launch chains (StepChain) ----
-// k x ([agent | actor [-> widen]] [-> fail kernel | action wrapper] -> one-step launch [-> grid kernel] -> the step counter advances [-> delay kernel | float32
+// k x ([agent | actor [-> widen] | actor-critic sample] [-> fail kernel | action wrapper] -> one-step launch [-> grid kernel] -> the step counter advances [-> delay kernel | float32
 // copy] [-> state kernel of the next counter]).  Nothing but launches while no episode ends inside: ev2g_rollout captures it into a graph.
 static int chain_steps(ev2g_handle *h, const StepChain &c, int k) {
     ev2g_link *l = c.link; ev2g_grid *g = c.grid;
@@ -1891,11 +1930,22 @@ static int chain_steps(ev2g_handle *h, const StepChain &c, int k) {
             if ((rc = wrap_launch(h, c.wrap, c.actor ? h->extras.actions_f32 : (const void *)act_i, c.actor != nullptr, out))) return rc;
             act_i = out;
         }
-        const StepIO io = make_io(h, StepRows{{act_i, c.a_stride_to_kernel ? c.actions.stride : 0}, {c.obs.at(i)}, {c.reward.at(i)}, {c.done.at(i)}, {c.mask.at(i)}},
-                                  c.count_steps ? i : 0, 0);
+        if (c.ac) {
+            if ((rc = ac_launch(h, c.ac, c.ac_obs.at(i), h->E, !c.ac_deterministic, nullptr, c.ac_actions.at(i), c.ac->clipped, c.ac_values.at(i),
+                                c.ac_log_probs.at(i)))) return rc;
+            if (!c.ac_direct)
+                HIPCHK(h, hipMemcpyAsync((void *)h->extras.actions_f32, c.ac->clipped, EP * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        }
+        StepIO io = make_io(h, StepRows{{act_i, c.a_stride_to_kernel ? c.actions.stride : 0}, {c.obs.at(i)}, {c.reward.at(i)}, {c.done.at(i)}, {c.mask.at(i)}},
+                            c.count_steps ? i : 0, 0);
+        if (c.ac && c.ac_direct) { io.act32 = c.ac->clipped; io.obs32 = c.ac_obs.at(i + 1); }
         if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
+        if (c.ac && !c.ac_direct)
+            HIPCHK(h, hipMemcpyAsync(c.ac_obs.at(i + 1), h->extras.obs_f32, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         if (g && (rc = grid_launch_step(h, g, c.vm.at(i), c.reward.at(i), c.base_weight, c.voltage_weight))) return rc;
         h->current_step += 1;
+        // (collect_direct promises the full instantiation; were it ever wrong the step has run and is counted, the rows of this step are not to be trusted)
+        if (c.ac && c.ac_direct && h->last_spec <= 0) return fail(h, EV2G_ERR_STATE, std::string(c.who) + ": internal: the direct path needs the full instantiation");
         if (l && l->p_delay > 0.0) {
             if ((rc = link_launch_obs(h, l, h->current_step, c.obs.at(i), c.actor ? l->obs32 : nullptr))) return rc;
         } else if (l && c.actor) {
@@ -1916,7 +1966,9 @@ static int run_chain(ev2g_handle *h, StepChain c, int k) {
     if (k < 0 || c.actions.stride < 0 || c.obs.stride < 0 || c.reward.stride < 0 || c.done.stride < 0 || c.mask.stride < 0 || c.vm.stride < 0 ||
         c.gobs.stride < 0 || c.gobs32.stride < 0 || c.wrapped.stride < 0)
         return fail(h, EV2G_ERR_ARG, who + ": negative step count or stride");
-    if (!c.agent && !c.actor && !c.actions.p) return fail(h, EV2G_ERR_ARG, who + ": without an agent the " + (l ? "raw " : "") + "actions are read from `actions`");
+    if (c.ac && (l || g || c.wrap))
+        return fail(h, EV2G_ERR_ARG, who + ": a Gaussian actor-critic does not stack with a link, a grid or an action wrapper");
+    if (!c.agent && !c.actor && !c.ac && !c.actions.p) return fail(h, EV2G_ERR_ARG, who + ": without an agent the " + (l ? "raw " : "") + "actions are read from `actions`");
     // the engine resets lazily inside the step launch after an episode end, so an agent's launch for the new episode's first step would
     // read the finished episode's ports: segments stay inside one episode, the caller resets in between
     if (h->current_step + k > h->T) return fail(h, EV2G_ERR_DONE, who + ": the segment would run past the episode end");
@@ -2153,6 +2205,224 @@ int ev2g_wrap_rollout(ev2g_handle *h, ev2g_wrap *w, const ev2g_mlp *m, int k_ste
     c.reward = {reward, r_stride}; c.done = {done, d_stride}; c.mask = {mask, m_stride};
     c.count_steps = x.cost != nullptr;   // (as ev2g_rollout: a cost buffer may record every step; the float32 buffers do not advance)
     return run_chain(h, c, k_steps);
+}
+
+// ---- the Gaussian actor-critic and GAE (ev2g_ac.h) ----
+struct AcWeights { const float *pW1, *pb1, *pW2, *pb2, *vW1, *vb1, *vW2, *vb2, *aW, *ab, *cW, *cb; };
+
+static int ac_check(ev2g_handle *h, ev2g_acpolicy *ac, const char *who) {
+    if (!h || !ac) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (std::find(h->acs.begin(), h->acs.end(), ac) == h->acs.end())
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the actor-critic was not created on this handle");
+    (void)hipSetDevice(h->device);
+    return EV2G_OK;
+}
+
+// packs the twelve host arrays into the object's device arrays (allocated at create) and drains the stream: the staging vectors are temporaries
+static int ac_upload_weights(ev2g_handle *h, ev2g_acpolicy *ac, const AcWeights &w) {
+    const AcDev &d = ac->dev;
+    std::vector<std::vector<float>> stage;
+    auto put = [&](const float *dst, std::vector<float> v) -> hipError_t {
+        stage.push_back(std::move(v));
+        return hipMemcpyAsync((void *)dst, stage.back().data(), stage.back().size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    };
+    auto padded = [](const float *b, int n, int N) { std::vector<float> v((size_t)N, 0.f); std::copy(b, b + n, v.begin()); return v; };
+    stage.reserve(12);
+    HIPCHK(h, put(d.w1, pack_linear_f32(w.pW1, d.h1, d.d_in, d.n1, d.k1))); HIPCHK(h, put(d.b1, padded(w.pb1, d.h1, d.n1)));
+    HIPCHK(h, put(d.w2, pack_linear_f32(w.pW2, d.h2, d.h1, d.n2, d.n1))); HIPCHK(h, put(d.b2, padded(w.pb2, d.h2, d.n2)));
+    HIPCHK(h, put(d.w3, pack_linear_f32(w.aW, d.d_out, d.h2, d.n3, d.n2))); HIPCHK(h, put(d.b3, padded(w.ab, d.d_out, d.n3)));
+    HIPCHK(h, put(d.u1, pack_linear_f32(w.vW1, d.v1, d.d_in, d.m1, d.k1))); HIPCHK(h, put(d.c1, padded(w.vb1, d.v1, d.m1)));
+    HIPCHK(h, put(d.u2, pack_linear_f32(w.vW2, d.v2, d.v1, d.m2, d.m1))); HIPCHK(h, put(d.c2, padded(w.vb2, d.v2, d.m2)));
+    HIPCHK(h, put(d.u3, padded(w.cW, d.v2, d.m2))); HIPCHK(h, put(d.c3, padded(w.cb, 1, 1)));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+static int ac_upload_log_std(ev2g_handle *h, ev2g_acpolicy *ac, const float *log_std, const char *who) {
+    const int P = ac->dev.d_out;
+    std::vector<float> sigma((size_t)P);
+    std::vector<double> a((size_t)P), c((size_t)P);
+    for (int p = 0; p < P; p++) {
+        if (!std::isfinite(log_std[p])) return fail(h, EV2G_ERR_ARG, std::string(who) + ": log_std[" + std::to_string(p) + "] is not finite");
+        const double s = std::exp((double)log_std[p]);
+        sigma[p] = (float)s;
+        const double sf = (double)sigma[p];   // (the float32 sigma the sample is scaled by)
+        a[p] = 1.0 / (2.0 * sf * sf);
+        c[p] = -(double)log_std[p] - 0.9189385332046727;   // log(2 pi) / 2
+    }
+    HIPCHK(h, hipMemcpyAsync((void *)ac->dev.sigma, sigma.data(), P * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync((void *)ac->dev.lp_a, a.data(), P * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync((void *)ac->dev.lp_c, c.data(), P * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+static bool ac_weights_null(const AcWeights &w) {
+    return !w.pW1 || !w.pb1 || !w.pW2 || !w.pb2 || !w.vW1 || !w.vb1 || !w.vW2 || !w.vb2 || !w.aW || !w.ab || !w.cW || !w.cb;
+}
+
+int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int d_out, int activation, const float *pi_W1, const float *pi_b1,
+                   const float *pi_W2, const float *pi_b2, const float *vf_W1, const float *vf_b1, const float *vf_W2, const float *vf_b2,
+                   const float *action_W, const float *action_b, const float *value_W, const float *value_b, const float *log_std, float lo,
+                   uint64_t seed, ev2g_acpolicy **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: null argument");
+    *out = nullptr;
+    const AcWeights w{pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b};
+    if (ac_weights_null(w) || !log_std) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: a weight, bias or log_std pointer is null");
+    if (d_in < 1 || d_in > EV2G_AC_MAX_IN) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: d_in must be 1 .. " + std::to_string(EV2G_AC_MAX_IN));
+    const int hid[4] = {h1, h2, v1, v2};
+    const char *hid_name[4] = {"h1", "h2", "v1", "v2"};
+    for (int i = 0; i < 4; i++)
+        if (hid[i] < 1 || hid[i] > EV2G_AC_MAX_HIDDEN)
+            return fail(h, EV2G_ERR_ARG, std::string("ev2g_ac_create: ") + hid_name[i] + " must be 1 .. " + std::to_string(EV2G_AC_MAX_HIDDEN));
+    if (d_out < 1 || d_out > EV2G_AC_MAX_OUT) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: d_out must be 1 .. " + std::to_string(EV2G_AC_MAX_OUT));
+    if (activation != EV2G_AC_TANH && activation != EV2G_AC_RELU) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: activation must be EV2G_AC_TANH or EV2G_AC_RELU");
+    if (lo != -1.0f && lo != 0.0f) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: lo must be -1 or 0");
+    for (int p = 0; p < d_out; p++)
+        if (!std::isfinite(log_std[p])) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: log_std[" + std::to_string(p) + "] is not finite");
+    (void)hipSetDevice(h->device);
+    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
+    ev2g_acpolicy *ac = new ev2g_acpolicy();
+    AcDev &d = ac->dev;
+    d.d_in = d_in; d.h1 = h1; d.h2 = h2; d.v1 = v1; d.v2 = v2; d.d_out = d_out;
+    d.k1 = up(d_in, 8); d.n1 = up(h1, 32); d.n2 = up(h2, 32); d.m1 = up(v1, 32); d.m2 = up(v2, 32); d.n3 = up(d_out, 32);
+    d.lo = lo;
+    ac->relu = activation == EV2G_AC_RELU;
+    ac->seed = seed; ac->n = 0;
+    ac->lds = ev2g_ac_lds(d).bytes;
+    int rc = 0;
+    float *f = nullptr;
+    double *g = nullptr;
+    auto fa = [&](size_t n, const float **dst) { rc = dalloc(h, ac->allocs, n, &f); *dst = f; return rc; };
+    auto da = [&](size_t n, const double **dst) { rc = dalloc(h, ac->allocs, n, &g); *dst = g; return rc; };
+    if (fa((size_t)d.n1 * d.k1, &d.w1) || fa(d.n1, &d.b1) || fa((size_t)d.n2 * d.n1, &d.w2) || fa(d.n2, &d.b2) || fa((size_t)d.n3 * d.n2, &d.w3) ||
+        fa(d.n3, &d.b3) || fa((size_t)d.m1 * d.k1, &d.u1) || fa(d.m1, &d.c1) || fa((size_t)d.m2 * d.m1, &d.u2) || fa(d.m2, &d.c2) || fa(d.m2, &d.u3) ||
+        fa(1, &d.c3) || fa(d_out, &d.sigma) || da(d_out, &d.lp_a) || da(d_out, &d.lp_c) || (rc = ac_upload_weights(h, ac, w)) ||
+        (rc = ac_upload_log_std(h, ac, log_std, "ev2g_ac_create"))) {
+        ac_free(ac);
+        return rc;
+    }
+    if (ac->lds > 48 * 1024 && !(h->ac_attr_mask & (1u << ac->relu))) {   // (function attributes are per device: once per handle)
+        const void *fn = ac->relu ? (const void *)ev2g_ac_act_kernel<EV2G_AC_RELU> : (const void *)ev2g_ac_act_kernel<EV2G_AC_TANH>;
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev2g_ac_lds_max());
+        if (e != hipSuccess) { ac_free(ac); return fail(h, EV2G_ERR_HIP, std::string("ev2g_ac_create: hipFuncSetAttribute: ") + hipGetErrorString(e)); }
+        h->ac_attr_mask |= 1u << ac->relu;
+    }
+    h->acs.push_back(ac);
+    *out = ac;
+    return EV2G_OK;
+}
+
+void ev2g_ac_destroy(ev2g_handle *h, ev2g_acpolicy *ac) { owned_destroy(h, &ev2g_handle::acs, ac, ac_free); }
+
+int ev2g_ac_seed(ev2g_handle *h, ev2g_acpolicy *ac, uint64_t seed, uint64_t first_draw) {
+    if (int rc = ac_check(h, ac, "ev2g_ac_seed")) return rc;
+    ac->seed = seed; ac->n = first_draw;
+    return EV2G_OK;
+}
+
+int ev2g_ac_set_log_std(ev2g_handle *h, ev2g_acpolicy *ac, const float *log_std) {
+    if (int rc = ac_check(h, ac, "ev2g_ac_set_log_std")) return rc;
+    if (!log_std) return fail(h, EV2G_ERR_ARG, "ev2g_ac_set_log_std: log_std is null");
+    for (int p = 0; p < ac->dev.d_out; p++)   // (checked before anything is enqueued: a refused call leaves the object as it was)
+        if (!std::isfinite(log_std[p])) return fail(h, EV2G_ERR_ARG, "ev2g_ac_set_log_std: log_std[" + std::to_string(p) + "] is not finite");
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // launches still reading the old values
+    return ac_upload_log_std(h, ac, log_std, "ev2g_ac_set_log_std");
+}
+
+int ev2g_ac_set_weights(ev2g_handle *h, ev2g_acpolicy *ac, const float *pi_W1, const float *pi_b1, const float *pi_W2, const float *pi_b2,
+                        const float *vf_W1, const float *vf_b1, const float *vf_W2, const float *vf_b2, const float *action_W,
+                        const float *action_b, const float *value_W, const float *value_b) {
+    if (int rc = ac_check(h, ac, "ev2g_ac_set_weights")) return rc;
+    const AcWeights w{pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b};
+    if (ac_weights_null(w)) return fail(h, EV2G_ERR_ARG, "ev2g_ac_set_weights: a weight or bias pointer is null");
+    return ac_upload_weights(h, ac, w);   // (stream-ordered behind the launches that read the old weights)
+}
+
+// one launch of ev2g_ac_act_kernel over n_rows rows; a sampling launch takes the object's counter and advances it
+static int ac_launch(ev2g_handle *h, ev2g_acpolicy *ac, const float *x, int n_rows, bool sample, float *mean, float *actions, float *clipped,
+                     float *value, float *log_prob) {
+    const dim3 grid((unsigned)((n_rows + EV2G_AC_ROWS - 1) / EV2G_AC_ROWS)), block(EV2G_AC_BLOCK);
+    const uint64_t draw0 = (uint64_t)ac->n * (uint64_t)n_rows;
+    if (ac->relu)
+        hipLaunchKernelGGL(ev2g_ac_act_kernel<EV2G_AC_RELU>, grid, block, ac->lds, h->stream, ac->dev, x, n_rows, sample ? 1 : 0, (uint64_t)ac->seed, draw0,
+                           mean, actions, clipped, value, log_prob);
+    else
+        hipLaunchKernelGGL(ev2g_ac_act_kernel<EV2G_AC_TANH>, grid, block, ac->lds, h->stream, ac->dev, x, n_rows, sample ? 1 : 0, (uint64_t)ac->seed, draw0,
+                           mean, actions, clipped, value, log_prob);
+    HIPCHK(h, hipGetLastError());
+    if (sample) ac->n += 1;
+    return EV2G_OK;
+}
+
+int ev2g_ac_forward(ev2g_handle *h, ev2g_acpolicy *ac, const float *obs32, int n_rows, float *mean, float *value) {
+    if (int rc = ac_check(h, ac, "ev2g_ac_forward")) return rc;
+    if (!obs32 || n_rows <= 0) return fail(h, EV2G_ERR_ARG, "ev2g_ac_forward: obs32 is null or n_rows is not positive");
+    return ac_launch(h, ac, obs32, n_rows, false, mean, nullptr, nullptr, value, nullptr);
+}
+
+int ev2g_ac_act(ev2g_handle *h, ev2g_acpolicy *ac, const float *obs32, int n_rows, int deterministic, float *actions, float *clipped, float *value,
+                float *log_prob) {
+    if (int rc = ac_check(h, ac, "ev2g_ac_act")) return rc;
+    if (!obs32 || n_rows <= 0) return fail(h, EV2G_ERR_ARG, "ev2g_ac_act: obs32 is null or n_rows is not positive");
+    return ac_launch(h, ac, obs32, n_rows, !deterministic, nullptr, actions, clipped, value, log_prob);
+}
+
+int ev2g_ac_collect(ev2g_handle *h, ev2g_acpolicy *ac, int k_steps, int deterministic, const ev2g_onpolicy_rows *r) {
+    if (int rc = ac_check(h, ac, "ev2g_ac_collect")) return rc;
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_ac_collect: no scenarios loaded");
+    if (!r || k_steps < 0 || !r->obs || !r->actions || !r->values || !r->log_probs || !r->reward || !r->done || !r->mask)
+        return fail(h, EV2G_ERR_ARG, "ev2g_ac_collect: null argument (every row array is required)");
+    if (ac->dev.d_in != h->D) return fail(h, EV2G_ERR_ARG, "ev2g_ac_collect: d_in " + std::to_string(ac->dev.d_in) + " != the observation width " + std::to_string(h->D));
+    if (ac->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_ac_collect: d_out " + std::to_string(ac->dev.d_out) + " != the ports " + std::to_string(h->P));
+    const size_t ED = (size_t)h->E * h->D, EP = (size_t)h->E * h->P;
+    const ev2g_step_extras &x = h->extras;
+    const bool direct = collect_direct(h);   // the two routes of ev2g_collect's unfused loop
+    if (!direct && !(x.obs_f32 && x.actions_f32 && x.obs_f32_step_stride == 0))
+        return fail(h, EV2G_ERR_ARG, "ev2g_ac_collect: this configuration steps through the registered float32 hand-over buffers: register them with "
+                                     "ev2g_set_step_extras (observation step stride 0) first");
+    if (ac->clipped_elems < EP) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(ac->clipped); ac->clipped = nullptr; ac->clipped_elems = 0;
+        HIPCHK(h, hipMalloc((void **)&ac->clipped, EP * sizeof(float)));
+        ac->clipped_elems = EP;
+    }
+    StepChain c{"ev2g_ac_collect"};
+    c.ac = ac; c.ac_deterministic = deterministic != 0; c.ac_direct = direct;
+    c.ac_obs = {r->obs, (long long)ED}; c.ac_actions = {r->actions, (long long)EP}; c.ac_values = {r->values, h->E}; c.ac_log_probs = {r->log_probs, h->E};
+    c.reward = {r->reward, h->E}; c.done = {r->done, h->E}; c.mask = {r->mask, (long long)EP};
+    c.count_steps = false;   // (as ev2g_collect: the registered buffers do not advance)
+    return run_chain(h, c, k_steps);
+}
+
+void ev2g_ac_host_normal(float *dst, int64_t n_values, uint64_t seed, uint64_t first_index) {
+    for (int64_t i = 0; i < n_values; i++) dst[i] = ev2g_ac_normal(seed, first_index + (uint64_t)i);
+}
+
+static int gae_args(ev2g_handle *h, const char *who, const void *a, const void *b, const void *c, const void *d, const void *e, const void *f,
+                    const void *g, int k, int n_envs) {
+    if (!a || !b || !c || !d || !e || !f || !g) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (k < 1 || n_envs < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": k and n_envs must be positive");
+    return EV2G_OK;
+}
+
+int ev2g_gae(ev2g_handle *h, const double *reward, const float *values, const uint8_t *episode_starts, const float *last_values,
+             const uint8_t *last_dones, int k, int n_envs, double gamma, double lambda, float *advantages, float *returns) {
+    if (!h) return fail(h, EV2G_ERR_ARG, "ev2g_gae: null handle");
+    if (int rc = gae_args(h, "ev2g_gae", reward, values, episode_starts, last_values, last_dones, advantages, returns, k, n_envs)) return rc;
+    (void)hipSetDevice(h->device);
+    hipLaunchKernelGGL(ev2g_gae_kernel, dim3((n_envs + 255) / 256), dim3(256), 0, h->stream, reward, values, episode_starts, last_values, last_dones, k,
+                       n_envs, (float)gamma, (float)(gamma * lambda), advantages, returns);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_host_gae(const double *reward, const float *values, const uint8_t *episode_starts, const float *last_values, const uint8_t *last_dones,
+                  int k, int n_envs, double gamma, double lambda, float *advantages, float *returns) {
+    if (int rc = gae_args(nullptr, "ev2g_host_gae", reward, values, episode_starts, last_values, last_dones, advantages, returns, k, n_envs)) return rc;
+    const float g = (float)gamma, c = (float)(gamma * lambda);
+    for (int e = 0; e < n_envs; e++) ev2g_gae_env(reward, values, episode_starts, last_values, last_dones, k, n_envs, e, g, c, advantages, returns);
+    return EV2G_OK;
 }
 
 int ev2g_check_faults(ev2g_handle *h, int32_t *first_bad_env) {

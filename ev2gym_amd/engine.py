@@ -100,6 +100,17 @@ def load_library(path: Optional[str] = None):
         "ev2g_grid_observe": (C.c_int, [vp, vp, vp, vp]),
         "ev2g_grid_run_observed": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, dbl, dbl, vp, i64, vp, i64]),
         "ev2g_grid_rollout": (C.c_int, [vp, vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, dbl, dbl]),
+        "ev2g_ac_create": (C.c_int, [vp] + [C.c_int] * 7 + [vp] * 13 + [C.c_float, C.c_uint64, C.POINTER(vp)]),
+        "ev2g_ac_destroy": (None, [vp, vp]),
+        "ev2g_ac_seed": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ev2g_ac_set_log_std": (C.c_int, [vp, vp, vp]),
+        "ev2g_ac_set_weights": (C.c_int, [vp, vp] + [vp] * 12),
+        "ev2g_ac_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp]),
+        "ev2g_ac_act": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "ev2g_ac_collect": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(_abi.OnPolicyRowsC)]),
+        "ev2g_ac_host_normal": (None, [vp, i64, C.c_uint64, C.c_uint64]),
+        "ev2g_gae": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, dbl, dbl, vp, vp]),
+        "ev2g_host_gae": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, dbl, dbl, vp, vp]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -158,7 +169,9 @@ EXPORTED_SYMBOLS = [
     "ev2g_link_run", "ev2g_link_rollout",
     "ev2g_grid_create", "ev2g_grid_destroy", "ev2g_grid_solve", "ev2g_grid_run",
     "ev2g_grid_state_attach", "ev2g_grid_state_dim", "ev2g_grid_observe", "ev2g_grid_run_observed", "ev2g_grid_rollout", "ev2g_grid_get_stats",
-    "ev2g_wrap_create", "ev2g_wrap_destroy", "ev2g_wrap_reset_state", "ev2g_wrap_actions", "ev2g_wrap_run", "ev2g_wrap_rollout"]
+    "ev2g_wrap_create", "ev2g_wrap_destroy", "ev2g_wrap_reset_state", "ev2g_wrap_actions", "ev2g_wrap_run", "ev2g_wrap_rollout",
+    "ev2g_ac_create", "ev2g_ac_destroy", "ev2g_ac_seed", "ev2g_ac_set_log_std", "ev2g_ac_set_weights", "ev2g_ac_forward", "ev2g_ac_act",
+    "ev2g_ac_collect", "ev2g_ac_host_normal", "ev2g_gae", "ev2g_host_gae"]
 
 
 def _ptr(x):
@@ -595,6 +608,60 @@ class Engine:
         self._check(self._lib.ev2g_grid_get_stats(self._h, g, vv.ctypes.data, cnt.ctypes.data, steps.ctypes.data, rs.ctypes.data))
         return dict(voltage_violation=vv, voltage_violation_counter=cnt, voltage_violation_counter_per_step=steps, total_reward=rs)
 
+    # ---- on-policy rollouts on the device (include/ev2g.h: ev2g_ac_*, ev2g_gae) ----------------------------------------------------
+    def ac_create(self, weights, log_std, activation="tanh", lo=-1.0, seed=0):
+        """A device-resident Gaussian actor-critic (SB3's default ActorCriticPolicy for a Box action space), freed by ac_destroy or with the
+        engine.  weights: the twelve host arrays in the order of ev2g_ac_create -- policy trunk (W1, b1, W2, b2), value trunk (W1, b1, W2,
+        b2), action head (W, b), value head (W, b) -- in torch.nn.Linear layout; ev2gym_amd.onpolicy.GaussianActorCritic checks the shapes."""
+        arrs = [np.ascontiguousarray(a, np.float32) for a in weights]
+        assert len(arrs) == 12
+        ls = np.ascontiguousarray(log_std, np.float32)
+        (h1, d_in), h2, (v1, _), v2, d_out = arrs[0].shape, arrs[2].shape[0], arrs[4].shape, arrs[6].shape[0], arrs[8].shape[0]
+        act = _abi.AC_ACTIVATIONS[activation] if isinstance(activation, str) else int(activation)
+        ac = C.c_void_p()
+        self._check(self._lib.ev2g_ac_create(self._h, d_in, h1, h2, v1, v2, d_out, act, *[a.ctypes.data for a in arrs], ls.ctypes.data,
+                                             float(lo), int(seed) & (2 ** 64 - 1), C.byref(ac)))
+        return ac
+
+    def ac_destroy(self, ac):
+        if self._h and ac:
+            self._lib.ev2g_ac_destroy(self._h, ac)
+
+    def ac_seed(self, ac, seed, first_draw=0):
+        """The noise stream's seed and the launch counter the next sampling launch uses."""
+        self._check(self._lib.ev2g_ac_seed(self._h, ac, int(seed) & (2 ** 64 - 1), int(first_draw)))
+
+    def ac_set_log_std(self, ac, log_std):
+        ls = np.ascontiguousarray(log_std, np.float32)
+        self._check(self._lib.ev2g_ac_set_log_std(self._h, ac, ls.ctypes.data))
+
+    def ac_set_weights(self, ac, weights):
+        arrs = [np.ascontiguousarray(a, np.float32) for a in weights]
+        assert len(arrs) == 12
+        self._check(self._lib.ev2g_ac_set_weights(self._h, ac, *[a.ctypes.data for a in arrs]))
+
+    def ac_forward(self, ac, obs32, n_rows, mean=None, value=None):
+        """mean [n_rows, P] / value [n_rows] of the float32 device rows obs32 [n_rows, D]; nothing sampled, no counter advanced."""
+        self._check(self._lib.ev2g_ac_forward(self._h, ac, _ptr(obs32), int(n_rows), _ptr(mean), _ptr(value)))
+
+    def ac_act(self, ac, obs32, n_rows, actions=None, clipped=None, value=None, log_prob=None, deterministic=False):
+        """One sampling launch on device rows, no step: the unclipped sample, clip(sample, lo, 1), the value and the log-probability."""
+        self._check(self._lib.ev2g_ac_act(self._h, ac, _ptr(obs32), int(n_rows), int(bool(deterministic)), _ptr(actions), _ptr(clipped),
+                                          _ptr(value), _ptr(log_prob)))
+
+    def ac_collect(self, ac, k, obs, actions, values, log_probs, reward, done, mask, deterministic=False):
+        """k x (sampling launch -> env step) inside one episode, the rows written straight into the caller's DEVICE arrays (ev2g_ac_collect):
+        obs float32 [k + 1, E, D] (row 0 is the input observation), actions float32 [k, E, P] (unclipped), values / log_probs float32 [k, E],
+        reward float64 [k, E], done / mask uint8."""
+        rows = _abi.OnPolicyRowsC(_ptr(obs), _ptr(actions), _ptr(values), _ptr(log_probs), _ptr(reward), _ptr(done), _ptr(mask))
+        self._check(self._lib.ev2g_ac_collect(self._h, ac, int(k), int(bool(deterministic)), C.byref(rows)))
+
+    def gae(self, reward, values, episode_starts, last_values, last_dones, k, n_envs, gamma, gae_lambda, advantages, returns):
+        """RolloutBuffer.compute_returns_and_advantage on device arrays (ev2g_gae): reward float64 [k, n_envs], values float32, episode_starts
+        uint8, last_values float32 [n_envs], last_dones uint8 [n_envs] -> advantages / returns float32 [k, n_envs]."""
+        self._check(self._lib.ev2g_gae(self._h, _ptr(reward), _ptr(values), _ptr(episode_starts), _ptr(last_values), _ptr(last_dones), int(k),
+                                       int(n_envs), float(gamma), float(gae_lambda), _ptr(advantages), _ptr(returns)))
+
     # ---- statistics / inspection ---------------------------------------------------------------
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
@@ -726,3 +793,26 @@ def host_uniform(n, seed, lo, hi) -> np.ndarray:
     out = np.empty(int(n))
     load_library().ev2g_host_uniform(out.ctypes.data, int(n), int(seed), float(lo), float(hi))
     return out
+
+
+def host_normal(n, seed, first_index=0) -> np.ndarray:
+    """Host twin of the actor-critic's noise (ev2g_ac_host_normal): the float32 standard normals of draw indices first_index .. + n - 1."""
+    out = np.empty(int(n), np.float32)
+    load_library().ev2g_ac_host_normal(out.ctypes.data, int(n), int(seed) & (2 ** 64 - 1), int(first_index))
+    return out
+
+
+def host_gae(reward, values, episode_starts, last_values, last_dones, gamma, gae_lambda):
+    """Host twin of Engine.gae (ev2g_host_gae, the same source): [k, n_envs] host arrays -> (advantages, returns) float32."""
+    reward = np.ascontiguousarray(reward, np.float64)
+    values = np.ascontiguousarray(values, np.float32)
+    starts = np.ascontiguousarray(episode_starts, np.uint8)
+    lv, ld = np.ascontiguousarray(last_values, np.float32), np.ascontiguousarray(last_dones, np.uint8)
+    k, n = reward.shape
+    assert values.shape == (k, n) and starts.shape == (k, n) and lv.shape == (n,) and ld.shape == (n,)
+    adv, ret = np.empty((k, n), np.float32), np.empty((k, n), np.float32)
+    rc = load_library().ev2g_host_gae(reward.ctypes.data, values.ctypes.data, starts.ctypes.data, lv.ctypes.data, ld.ctypes.data, k, n,
+                                      float(gamma), float(gae_lambda), adv.ctypes.data, ret.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, (load_library().ev2g_last_error(None) or b"").decode())
+    return adv, ret

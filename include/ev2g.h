@@ -622,6 +622,81 @@ int ev2g_grid_run_observed(ev2g_handle *h, ev2g_grid *g, ev2g_heuristic *agent, 
 int ev2g_grid_rollout(ev2g_handle *h, ev2g_grid *g, const ev2g_mlp *m, int k_steps, double *reward, int64_t r_stride, uint8_t *done,
                       int64_t d_stride, uint8_t *mask, int64_t m_stride, double *vm, int64_t v_stride, double base_weight, double voltage_weight);
 
+/* ---- on-policy rollouts ON THE DEVICE: a Gaussian actor-critic and GAE (train_stable_baselines.py:24,62-130: PPO by default, A2C, TRPO) --------
+ * SB3's default ActorCriticPolicy for a Box action space: a policy trunk d_in -> h1 -> h2 with a linear action head h2 -> d_out (the mean), a
+ * separate value trunk d_in -> v1 -> v2 with a linear head v2 -> 1, one hidden activation for both trunks and a state-independent log_std[d_out].
+ * Weights are HOST float32 arrays in torch.nn.Linear layout (W[out,in] row-major, b[out]), copied once.  Float32 operands on the exact-f32 matrix
+ * instruction, float32 accumulation (csrc/ev2g_ac.h); no bf16 split.
+ * LIMITS: d_in <= 192, every hidden width <= 256, d_out <= 64 -- the shipped V2G_profit_max_loads (162 -> 50) and PublicPST (63 -> 20) shapes fit;
+ * anything else is EV2G_ERR_ARG at create, there is no generic fallback.
+ * One launch per batch of observation rows computes both trunks and both heads and, when sampling,
+ *     a = mean + exp(log_std) * eps,   log_prob = sum_p [ -(a - mean)^2 / (2 sigma^2) - log_std - log(2 pi) / 2 ]   on the UNCLIPPED a (as SB3 does),
+ *     a_env = clip(a, lo, 1),  lo = -1 or 0: the reference's two action boxes, the meaning of ev2g_mlp's out_lo.
+ * A row's results do not depend on which other rows are in the launch or where the row sits in it.  log_prob is summed in float64 and rounded once.
+ * eps comes from a counter, not a stored stream: draw index j is Box-Muller on the uniforms 2 j and 2 j + 1 of ev2g_host_uniform's generator under
+ * the object's seed, sqrt(-2 log(1 - u[2j])) cos(2 pi u[2j+1]) evaluated in float64 and rounded to float32; element (row e, port p) of the object's
+ * n-th sampling launch over E rows draws index (n E + e) d_out + p.  n is a 64-bit counter of the object: every SAMPLING launch (ev2g_ac_act with
+ * deterministic == 0, every step of such an ev2g_ac_collect) advances it by one, ev2g_ac_seed sets it.  ev2g_ac_host_normal is the host twin: the
+ * same bits. */
+#define EV2G_AC_TANH 0 /* SB3's default activation_fn */
+#define EV2G_AC_RELU 1
+typedef struct ev2g_acpolicy ev2g_acpolicy;
+/* Needs a handle, not loaded scenarios; freed with the handle if not before.  pi_*: policy trunk, vf_*: value trunk, action_* / value_*: the two heads
+ * (SB3's mlp_extractor.policy_net.{0,2}, mlp_extractor.value_net.{0,2}, action_net, value_net).  EV2G_ERR_ARG with a message naming the field: a
+ * width outside the limits, an unknown activation, lo not -1 or 0, a log_std that is not finite. */
+int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int d_out, int activation, const float *pi_W1, const float *pi_b1,
+                   const float *pi_W2, const float *pi_b2, const float *vf_W1, const float *vf_b1, const float *vf_W2, const float *vf_b2,
+                   const float *action_W, const float *action_b, const float *value_W, const float *value_b, const float *log_std, float lo,
+                   uint64_t seed, ev2g_acpolicy **out);
+void ev2g_ac_destroy(ev2g_handle *h, ev2g_acpolicy *ac);
+/* the noise stream's seed and the launch counter n the next sampling launch uses */
+int ev2g_ac_seed(ev2g_handle *h, ev2g_acpolicy *ac, uint64_t seed, uint64_t first_draw);
+/* log_std [d_out] HOST (a learner changes it every update); the weights: same pointers as create, same shapes */
+int ev2g_ac_set_log_std(ev2g_handle *h, ev2g_acpolicy *ac, const float *log_std);
+int ev2g_ac_set_weights(ev2g_handle *h, ev2g_acpolicy *ac, const float *pi_W1, const float *pi_b1, const float *pi_W2, const float *pi_b2,
+                        const float *vf_W1, const float *vf_b1, const float *vf_W2, const float *vf_b2, const float *action_W,
+                        const float *action_b, const float *value_W, const float *value_b);
+/* mean [n_rows, d_out] and value [n_rows] of obs32 [n_rows, d_in] (float32 DEVICE pointers, each output may be NULL): no sample is taken and no
+ * counter advanced -- the bootstrap value of the row behind a segment, and the deterministic evaluation path.  Asynchronous on the handle's stream. */
+int ev2g_ac_forward(ev2g_handle *h, ev2g_acpolicy *ac, const float *obs32, int n_rows, float *mean, float *value);
+/* ONE sampling launch, no step: actions [n_rows, d_out] the unclipped sample (what SB3 stores), clipped [n_rows, d_out] what a step would read,
+ * value / log_prob [n_rows] (float32 DEVICE, each may be NULL).  deterministic != 0: a = mean (EvalCallback(deterministic=True),
+ * train_stable_baselines.py:82-87), nothing drawn, the counter stays. */
+int ev2g_ac_act(ev2g_handle *h, ev2g_acpolicy *ac, const float *obs32, int n_rows, int deterministic, float *actions, float *clipped, float *value,
+                float *log_prob);
+/* On-policy ROLLOUT COLLECTION (the collect_rollouts() half of an SB3 PPO / A2C loop): k_steps x (the launch above on observation row i -> one-step
+ * launch of the step kernel the handle selected, reading the object's clipped block and writing observation row i + 1) inside ONE episode, the rows
+ * landing in the caller's DEVICE arrays.  d_in must be the handle's observation width and d_out its ports (EV2G_ERR_ARG); a segment that would run
+ * past the episode end returns EV2G_ERR_DONE: statistics and reset in between are the caller's (ev2g_get_stats_reset_f32).  The two routes of
+ * ev2g_collect's unfused loop: on the fast path the step takes the float32 rows per launch; elsewhere it works on the hand-over pair registered with
+ * ev2g_set_step_extras (observation step stride 0; EV2G_ERR_ARG without it) and the rows are copied device-to-device around it.  Timed like
+ * ev2g_step_n (ev2g_last_step_n_kernel_ms).  The chain is NOT captured into a graph and has NO fused-launch variant (ev2g_rollout's single launch
+ * has no place for the sampling epilogue).  The entry takes no link, grid or action wrapper: the chain holds none of their stages (an
+ * actor-critic is refused next to them inside one chain), and objects of those kinds that live on the handle are neither used nor touched. */
+typedef struct ev2g_onpolicy_rows {
+    float *obs;       /* [k_steps + 1, E, D]; row 0 read, rows 1.. written */
+    float *actions;   /* [k_steps, E, P] the unclipped samples, written */
+    float *values;    /* [k_steps, E] written */
+    float *log_probs; /* [k_steps, E] written */
+    double *reward;   /* [k_steps, E] written */
+    uint8_t *done;    /* [k_steps, E] written */
+    uint8_t *mask;    /* [k_steps, E, P] written */
+} ev2g_onpolicy_rows;
+int ev2g_ac_collect(ev2g_handle *h, ev2g_acpolicy *ac, int k_steps, int deterministic, const ev2g_onpolicy_rows *r);
+/* dst [n_values] float32 HOST: the standard normals of draw indices first_index .. first_index + n_values - 1 under `seed` */
+void ev2g_ac_host_normal(float *dst, int64_t n_values, uint64_t seed, uint64_t first_index);
+/* SB3's RolloutBuffer.compute_returns_and_advantage in float32, one thread per env walking the k rows backwards, with g = (float)gamma and
+ * c = (float)(gamma * lambda) (the float64 product rounded once):
+ *     nnt = 1 - next_start;  delta = (r + (g * next_v) * nnt) - v;  adv = delta + (c * nnt) * last;  ret = adv + v;  r = (float)reward
+ * reward [k, n_envs] float64, values [k, n_envs] float32, episode_starts [k, n_envs] uint8 (row t: step t is the first of an episode), last_values
+ * [n_envs] float32 the value of the observation behind the last row, last_dones [n_envs] uint8 whether the last row ended an episode; advantages /
+ * returns [k, n_envs] float32 written.  DEVICE pointers; ev2g_host_gae is the same function on HOST pointers (one source, the same bits).  n_envs is
+ * passed explicitly -- the host twin has no handle to take it from, and the device entry works on any [k, n_envs] block, not only the handle's E. */
+int ev2g_gae(ev2g_handle *h, const double *reward, const float *values, const uint8_t *episode_starts, const float *last_values,
+             const uint8_t *last_dones, int k, int n_envs, double gamma, double lambda, float *advantages, float *returns);
+int ev2g_host_gae(const double *reward, const float *values, const uint8_t *episode_starts, const float *last_values, const uint8_t *last_dones,
+                  int k, int n_envs, double gamma, double lambda, float *advantages, float *returns);
+
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
 void ev2g_free(ev2g_handle *h, void *p);
