@@ -193,6 +193,10 @@ struct ev2g_handle {
     double *d_stats_inl = nullptr;              // [E, EV2G_N_STATS]: the loaded shape has the in-launch phase (V2P::stats_inl points here), else nullptr
     const char *inl_shape_reason = "";          // ... why not
     bool inl_stats = false, no_inl_stats = false;
+    // fast-forward of EV-free stretches (ev2g_step_wave's FFW path): per-workgroup counts of the last eligible launch; EV2G_NO_FAST_FORWARD=1 at load
+    // time leaves the block (and V2P::ff_count) null, and every step is stepped (A/B, parity tests)
+    unsigned long long *d_ff_count = nullptr;   // [n_groups]
+    bool no_fast_forward = false, ff_launch = false;   // ff_launch: the last launch was one whose kernel counts (ev2g_last_launch_fast_forwarded)
     int last_stats_route = -1;                  // ev2g_last_stats_route
     const char *inl_reason = "";                // why the in-launch results are not available (the last step launch did not compute them, or they were discarded)
     const char *stats_reason = "";              // ev2g_last_stats_reason: inl_reason at the last ev2g_get_stats / ev2g_get_stats_reset
@@ -407,6 +411,20 @@ const char *ev2g_big_kernel_reason(const ev2g_handle *h) { return (h && h->loade
 int ev2g_last_launch_specialisation(const ev2g_handle *h) { return (h && h->loaded) ? h->last_spec : -1; }
 int ev2g_last_stats_route(const ev2g_handle *h) { return (h && h->loaded) ? h->last_stats_route : -1; }
 const char *ev2g_last_stats_reason(const ev2g_handle *h) { return (h && h->loaded && h->last_stats_route == 0) ? h->stats_reason : ""; }
+int ev2g_last_launch_fast_forwarded(ev2g_handle *h, int64_t *steps, int64_t *stretches) {
+    if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_last_launch_fast_forwarded: no scenarios loaded");
+    int64_t n = 0, m = 0;
+    if (h->ff_launch) {   // the counts of the launch's workgroups, summed on demand
+        (void)hipSetDevice(h->device);
+        std::vector<unsigned long long> c((size_t)h->scn.n_groups);
+        HIPCHK(h, hipMemcpyAsync(c.data(), h->d_ff_count, sizeof(unsigned long long) * c.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (unsigned long long v : c) { n += (int64_t)(v & 0xffffffffull); m += (int64_t)(v >> 32); }
+    }
+    if (steps) *steps = n;
+    if (stretches) *stretches = m;
+    return EV2G_OK;
+}
 const char *ev2g_last_launch_general_reason(const ev2g_handle *h) { return (h && h->loaded && h->last_spec == 0) ? h->general_reason : ""; }
 
 static const char *kStatNames[EV2G_N_STATS] = {
@@ -454,6 +472,7 @@ static int load_route(ev2g_handle *h, const LoadPlan &p, const LoadSwitches &sw)
     h->wave_path = h->fallback_reason.empty();
     h->no_full = sw.no_full; h->no_wide = sw.no_wide; h->last_spec = -1;
     h->no_strided = sw.no_strided;
+    h->no_fast_forward = sw.no_fast_forward; h->ff_launch = false;
     h->no_inl_stats = sw.no_inl_stats; h->inl_stats = false; h->last_stats_route = -1; h->inl_reason = "no step launch since the scenarios were loaded";
     h->state_epoch += 1;
     if (h->wave_path) {   // ev2g_step_wave addresses every array as base + 32-bit byte offset: all of them must stay below 4 GiB
@@ -740,6 +759,13 @@ static int load_decide_inl_stats(ev2g_handle *h) {
     else if (h->wave_epw != 1 || stats_pair(h)) why = "several envs per wavefront (the in-launch phase computes one env per wavefront, like the statistics kernel at this shape)";
     else if (h->lds_bytes < ev2g_inl_stats_lds_bytes()) why = "the step kernel's LDS is smaller than the phase's blocks";
     h->inl_shape_reason = why;
+    h->d_ff_count = nullptr;
+    if (h->wave_path && h->wave_epw == 1 && !h->no_fast_forward) {   // the fast-forward's per-workgroup counts: what switches it on
+        int rc = 0;
+        if ((rc = dalloc(h, h->st_allocs, (size_t)h->scn.n_groups, &h->d_ff_count))) return rc;
+        unsigned long long *p = h->d_ff_count;
+        HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, ff_count), &p, sizeof p, hipMemcpyHostToDevice));
+    }
     if (!why[0]) {
         int rc = 0;
         if ((rc = dalloc(h, h->st_allocs, (size_t)h->E * EV2G_N_STATS, &h->d_stats_inl))) return rc;
@@ -881,6 +907,7 @@ static StepIO make_io(const ev2g_handle *h, const StepRows &r, long long step0, 
 static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int auto_reset) {
     const DevScn &s = h->scn;
     h->inl_stats = false; h->inl_reason = "the step kernel is not ev2g_step_wave"; h->state_epoch += 1;
+    h->ff_launch = false;
     if (h->wave_path) {
         // the fast path advances its output pointers by 32-bit byte strides
         const long long lim = 1ll << 32;
@@ -908,6 +935,8 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
         const bool str3 = strided && wide0 && f64io && !h->no_strided;
         const bool full = full0 && (!strided || str3), wide = wide0 && full;
         h->last_spec = full ? (str3 ? 3 : (wide ? 2 : 1)) : 0;
+        // (the kernel applies the same rule: a stride-0 float64 full instantiation of a head-table state, V2P::ff_count set -- one env per wavefront --, k > 1)
+        h->ff_launch = full && !str3 && f64io && k > 1 && h->d_ff_count != nullptr && s.state_kind != EV2G_STATE_PUBLIC_PST;
         {   // why not the full instantiation: the FIRST thing the caller passed (or configured) that rules it out -- ev2g_last_launch_general_reason
             const char *why = "";
             if (!full) {
@@ -1354,6 +1383,7 @@ static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, int k, const float *o
     const DevState &st = h->st;
     const long long lim = 1ll << 32;
     h->inl_stats = false; h->inl_reason = "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)"; h->state_epoch += 1;
+    h->ff_launch = false;
     if (obs.stride * 4 >= lim || act.stride * 4 >= lim || reward.stride * 8 >= lim || done.stride >= lim || mask.stride >= lim || obs.stride < 0 ||
         act.stride < 0 || reward.stride < 0 || done.stride < 0 || mask.stride < 0)
         return fail(h, EV2G_ERR_ARG, "ev2g_collect / ev2g_rollout: a step stride is negative or reaches 4 GiB");

@@ -28,6 +28,7 @@ struct LoadSwitches {
     long long pool_session_cap = 0;   // EV2G_POOL_SESSION_CAP: at least this many session slots per scenario of a refillable pool
     bool no_full = false, no_wide = false, no_strided = false;   // EV2G_NO_FULL / EV2G_NO_WIDE / EV2G_NO_STRIDED
     bool no_inl_stats = false;        // EV2G_NO_INLAUNCH_STATS
+    bool no_fast_forward = false;     // EV2G_NO_FAST_FORWARD: every EV-free step of a persistent launch is stepped
     bool kernel_v2 = false;           // EV2G_KERNEL=v2: the general kernel on the common shape
     bool no_dict = false;             // EV2G_NO_DICT: one ClsRec per session
     bool no_big = false;              // EV2G_NO_BIG: ev2g_step_v2<1024> where ev2g_step_big would run
@@ -39,6 +40,7 @@ inline LoadSwitches load_switches_from_env() {
     sw.no_wide = std::getenv("EV2G_NO_WIDE") != nullptr;
     sw.no_strided = std::getenv("EV2G_NO_STRIDED") != nullptr;
     sw.no_inl_stats = std::getenv("EV2G_NO_INLAUNCH_STATS") != nullptr;
+    sw.no_fast_forward = std::getenv("EV2G_NO_FAST_FORWARD") != nullptr;
     const char *kn = std::getenv("EV2G_KERNEL");
     sw.kernel_v2 = kn && std::string(kn) == "v2";
     sw.no_dict = std::getenv("EV2G_NO_DICT") != nullptr;

@@ -17,6 +17,10 @@
 #include "ev2g_mlp.h"
 
 #define EV2G_WAVE_BLOCK 256
+// the shortest EV-free stretch ev2g_step_wave fast-forwards (FFW): a one-step pass costs a barrier and one memory round trip, like the step it replaces
+#ifndef EV2G_FF_N_MIN
+#define EV2G_FF_N_MIN 1
+#endif
 
 __host__ __device__ inline size_t ev2g_wave_lds_bytes(int envs_per_group, int block = EV2G_WAVE_BLOCK) {
     const size_t NS = (size_t)block;
@@ -241,6 +245,31 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
     const double dtd = (double)S->dt, sixty_over_dt = S->sixty_over_dt, dt_over_60 = S->dt_over_60;
     const bool pow2_dt = S->pow2_dt != 0;
 
+    // FFW: EV-free stretches of a stride-0 float64 launch are fast-forwarded (below, behind the step's first barrier).  A step in which no port of
+    // the workgroup's envs holds an EV or receives one writes nothing but three history words and the reward's share of the episode return, all of
+    // them functions of the step's own step-table row: a stretch of n such steps is ONE pass with lane = step instead of n trips round the loop.
+    // Every wavefront tells the others through LDS how long ITS env stays EV-free (ffx: 16 bits per wavefront, relative to the step in work,
+    // double-buffered by step parity like cnt); n is the minimum of the four values, read by all wavefronts behind the same barrier, so the branch
+    // -- and the barriers executed -- are the same in every wavefront of the workgroup by construction.
+    // Off (ff_lim == 0) unless V2P::ff_count is set (EV2G_NO_FAST_FORWARD at load time), one env per wavefront, more than one step.  The launch's last
+    // step always takes the normal path: it writes the outputs and publishes the accumulators.  (Phase-timing builds: compiled out.)
+    // Not for PublicPST (SK 1): its benchmark shape, cfg3, runs three envs per wavefront and could never take the path, yet carrying it cost that kernel 3.5 %
+    // (profiles/r15_ev_free_stretches.txt) -- every instantiation without the path is, instruction for instruction, what it was before.
+#if defined(EV2G_PHASE_TIMING)
+    constexpr bool FFW = false;
+#else
+    constexpr bool FFW = F64 && LSO && !ACT && RK != 3 && SK != 1 && BLOCK == EV2G_WAVE_BLOCK;
+#endif
+    unsigned short *ffx = (unsigned short *)(cnt + 4);   // [2][4]
+    // (both wave-uniform, but kept in VECTOR registers: the scalar registers of these instantiations are spoken for, and one parked there is a
+    // v_readlane / v_writelane pair in every step)
+    int ff_lim_v = 0;    // index of the launch's last step; 0: no fast-forward in this launch
+    int ff_next_v = -1;  // the step in which this wavefront's env is next live (== t while it is); recomputed only behind a live step
+    if (FFW && EPW == 1 && k_steps > 1 && S->ff_count != nullptr) {   // (uniform)
+        ff_lim_v = k_steps - 1;
+        // this workgroup's count (bits 0..31 steps, 32.. stretches), cleared here: the prologue's wait below completes the store before the first addition
+        if (tid == 0) stg32<unsigned long long>(S->ff_count, (unsigned)blockIdx.x * 8u, 0ull);
+    }
     // ---- home lane set-up ----
     const int elw = lane / ES;           // env inside the wavefront
     const int q = (ACT && AE == 1) ? lane : lane - elw * ES;       // port slot (== reference port: one transformer, single-port chargers)
@@ -490,6 +519,21 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         // (one env per wavefront only: with two or three a wavefront is rarely empty and the test costs more than it saves -- cfg3 +0.8 %, cfg2 -3 %,
         // profiles/r05_ab_empty_wavefront_path.txt)
         const bool wave_live = !FULL || EPW != 1 || __ballot(valid && ((r_ta <= t && t <= r_td) || r_ta == sstep)) != 0ull;   // (uniform)
+        if (FFW) asm volatile("" : "+v"(ff_lim_v), "+v"(ff_next_v));
+        // (EPW first: a scalar the loop holds anyway -- with several envs per wavefront, cfg3, the path costs a scalar compare and no vector instruction)
+        if (FFW && EPW == 1 && __builtin_amdgcn_readfirstlane(ff_lim_v) != 0) {   // (uniform) how long this wavefront's env stays EV-free, for the other wavefronts (read behind the barrier below)
+            int ff_next = __builtin_amdgcn_readfirstlane(ff_next_v);
+            if (wave_live) ff_next = t;
+            else if (ff_next <= t) {   // the first EV-free step behind a live one (or of the launch): the env wakes in the step at whose end its
+                                       // earliest EV arrives (sstep == r_ta); idle lanes and wavefronts without an env never constrain
+                int m = (valid && r_ta > sstep) ? r_ta : EV2G_INT_MAX;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+                ff_next = __builtin_amdgcn_readfirstlane(m) - 1;
+            }
+            ff_next_v = ff_next;
+            if (lane_l == 0) ffx[4 * (kk & 1) + (tid_l >> 6)] = (unsigned short)min(ff_next - t, 0xffff);
+        }
         if (valid && wave_live) {
             // every LDS operand of the phase in one batch (one wait) instead of one round trip per branch
             int ta = FULL ? r_ta : s_ta[tid_l], td = FULL ? r_td : s_td[tid_l];
@@ -548,6 +592,68 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         // The wavefronts that hold list items are the critical path of the whole workgroup (the others wait at the next
         // barrier): they issue at raised priority until their items are done.
         const int nch = cntk[0], ndis = cntk[1];
+        if (FFW) asm volatile("" : "+v"(ff_lim_v));   // (read again: nothing of this is kept in a scalar register across phase A)
+        const int ff_lim = (FFW && EPW == 1) ? __builtin_amdgcn_readfirstlane(ff_lim_v) : 0;
+        if (FFW && ff_lim != 0) {   // (uniform)
+            const uint2 fx = *(const uint2 *)(ffx + 4 * (kk & 1));
+            const unsigned f01 = min(fx.x & 0xffffu, fx.x >> 16), f23 = min(fx.y & 0xffffu, fx.y >> 16);
+            // EV-free steps from this one on, in all four envs, short of the launch's last step and at most one per lane: the same number in every wavefront
+            // (a longer stretch takes another pass, behind the next step's exchange)
+            const int n = __builtin_amdgcn_readfirstlane(min(min((int)min(f01, f23), 64), ff_lim - kk));
+            if (n >= EV2G_FF_N_MIN) {
+                // all wavefronts have read the four values before any of them writes the next ones: after an even number of steps the parity repeats
+                lds_barrier();
+                // (sizes and bases from the parameter block, read here: nothing of this rare path is computed ahead of the step loop and kept in scalar registers)
+                const int ew = __builtin_amdgcn_readfirstlane(e_l);   // this wavefront's env (lane 0 is its port 0)
+                const int Tf = S->T;
+                int bx = (int)blockIdx.x;
+                asm volatile("" : "+s"(bx));
+                if (ew < S->E) {   // lane i = step t + i
+                    const int ts = t + lane_l;
+                    const unsigned row = (unsigned)__builtin_amdgcn_readfirstlane(hb_step) + (unsigned)min(ts, Tf - 1) * 64u;   // the env's scenario's rows in the step table
+                    const d2v tr0 = ldg32_nt<d2v>(S->step_tab, row + 16u), tr1 = ldg32_nt<d2v>(S->step_tab, row + 32u);   // {inflexible + solar, max power}, {min power, setpoint}
+                    double *ea = eacc + (tid_l >> 6) * 7;
+                    double n0 = ea[0], n1 = ea[1], n2 = ea[2], n3 = ea[3], n4 = ea[4];
+                    const double pot_t = ea[5];   // charge_power_potential of the first step; +0.0 for the later ones
+                    // phase E with every per-env sum an exact +0.0
+                    const double usage = 0.0, costs = 0.0, user = 0.0;
+                    const double tr_power = tr0.x + usage;
+                    const double over = (tr_power > tr0.y + 0.0001 || tr_power < tr1.x - 0.0001) ? fabs(tr_power - tr0.y) : 0.0;
+                    double reward;
+                    if (RK == 1) {
+                        const double pp = (lane_l == 0) ? pot_t : 0.0;
+                        const double mn = (pp < tr1.y) ? pp : tr1.y;
+                        const double d = mn - usage;
+                        reward = -(d * d);
+                    } else if (RK == 2) {
+                        reward = costs - user;
+                    } else {
+                        reward = costs - 100.0 * over - user;
+                    }
+                    if (lane_l < n) {   // the step's history row {usage, (potential), overload} and the next row's potential
+                        const unsigned h8 = (unsigned)(ew * Tf + ts) * 24u;
+                        stg32<double>(S->hist, h8, usage);
+                        stg32<double>(S->hist, h8 + 16u, over);
+                        if (ts + 1 < Tf) stg32<double>(S->hist, h8 + 32u, 0.0);
+                    }
+                    // the episode return takes the rewards one by one, in step order, like the steps would
+                    const int r_lo = __double2loint(reward), r_hi = __double2hiint(reward);
+                    for (int j = 0; j < n; j++)
+                        n0 += __hiloint2double(__builtin_amdgcn_readlane(r_hi, j), __builtin_amdgcn_readlane(r_lo, j));
+                    n1 += 0.0; n2 += 0.0; n3 += 0.0; n4 += 0.0;   // (x + 0.0 once is x + 0.0 n times)
+                    if (lane_l == 0) { ea[0] = n0; ea[1] = n1; ea[2] = n2; ea[3] = n3; ea[4] = n4; ea[5] = 0.0; }
+                }
+                if (tid_l == 0)
+                    __hip_atomic_fetch_add((unsigned long long __attribute__((address_space(1))) *)((gptr)S->ff_count + (unsigned)bx * 8u),
+                                           (1ull << 32) | (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                // on to step t + n: its action row (act_run already stands one row behind this step's)
+                a_next = ldg32_nt<double>(act_run + (long long)(n - 1) * io.a_stride, (unsigned)gc * 8u);
+                act_run += (long long)(n - 1) * io.a_stride;
+                t += n;
+                kk += n - 1;
+                continue;
+            }
+        }
         // A step in which no port of the workgroup has an EV to integrate (the night half of a workplace episode, the early morning: 40 % of the
         // workgroup-steps at cfg2) has no battery-maths phase to fence: the second barrier is skipped.  Every wavefront reads the same counts.
         if (nch + ndis != 0) {
@@ -944,9 +1050,15 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                 stg32<double>(S->x_cost + (long long)(io.step0 + kk) * S->x_c_stride, e8, (S->cost_kind == 2) ? costs : 100.0 * over + esum[2]);
             if (sstep >= T || last_step) {  // publish the running episode totals (get_statistics reads them)
                 const unsigned a8 = (unsigned)e_l * 64u;
-                stg32<d2v>(env_acc, a8, (d2v){n0, n1});
-                stg32<d2v>(env_acc, a8 + 16u, (d2v){n2, n3});
-                stg32<double>(env_acc, a8 + 32u, n4);
+                if (FFW) {   // (the base from the parameter block, here: a launch publishes once, and the pointer is not held in scalar registers across the step loop)
+                    stg32<d2v>(S->env_acc, a8, (d2v){n0, n1});
+                    stg32<d2v>(S->env_acc, a8 + 16u, (d2v){n2, n3});
+                    stg32<double>(S->env_acc, a8 + 32u, n4);
+                } else {
+                    stg32<d2v>(env_acc, a8, (d2v){n0, n1});
+                    stg32<d2v>(env_acc, a8 + 16u, (d2v){n2, n3});
+                    stg32<double>(env_acc, a8 + 32u, n4);
+                }
             }
         }
         if ((valid || hcopy) && ((F32 && out) || (!FULL && obs32))) {

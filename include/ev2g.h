@@ -286,6 +286,15 @@ const char *ev2g_last_launch_general_reason(const ev2g_handle *h);
 int ev2g_last_stats_route(const ev2g_handle *h);
 /* When ev2g_last_stats_route is 0: why the in-launch statistics were not available, "" otherwise. */
 const char *ev2g_last_stats_reason(const ev2g_handle *h);
+/* Fast-forwarded EV-free stretches.  A persistent launch (k > 1) of the stride-0 float64 specialisations (ev2g_last_launch_specialisation 1 or 2) with
+ * one env per wavefront (33..64 ports) and a head-table state (V2G_profit_max, V2G_profit_max_loads; not PublicPST) does not step a stretch of steps in which none of a workgroup's four envs holds an EV or receives one: it
+ * writes those steps' history rows and adds their rewards to the episode return in one pass, up to but never including the launch's last step.
+ * `hist`, the accumulators and everything derived from them (the statistics) are bit-identical to stepping those steps one by one.
+ * This call reports what the LAST launch skipped that way, summed over its workgroups: workgroup-steps, and stretches counted as passes of at most 64
+ * steps each (either pointer may be NULL).
+ * Both are 0 after any launch that is not eligible (other instantiations and kernels, single steps, several envs per wavefront) and when the
+ * library was loaded with EV2G_NO_FAST_FORWARD=1, which steps every step (A/B runs, parity tests).  Synchronises the stream. */
+int ev2g_last_launch_fast_forwarded(ev2g_handle *h, int64_t *steps, int64_t *stretches);
 /* data-dependent faults recorded since the last reset (per-env flag word, device side):
  * returns 0 or EV2G_ERR_OVERCURRENT; synchronises the stream. */
 int ev2g_check_faults(ev2g_handle *h, int32_t *first_bad_env);
