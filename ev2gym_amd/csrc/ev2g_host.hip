@@ -13,11 +13,13 @@
 #include <array>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ev2g.h"
 #include "ev2g_device.h"
 #include "ev2g_load_host.h"
+#include "ev2g_route_host.h"
 #include "ev2g_step_v2.h"
 #include "ev2g_step_wave.h"
 #include "ev2g_step_big.h"
@@ -158,7 +160,6 @@ struct ev2g_handle {
     double *d_ss_afap = nullptr;                // [S] device order
     double *d_step_tab = nullptr;               // [M,T,8] (fast path)
     V2P *d_v2p = nullptr;                       // device copy of the v2 kernel's parameter block
-    int block = 0;                              // 256/512/1024: v2 kernel; 0: generic kernel (P > 1024)
     double *d_head_tab = nullptr; int head_nh = 0;   // observation head table of the fast path (rebuilt for refilled slots)
     double *d_lut_rowmax = nullptr;             // [n_lut] largest entry of every efficiency table
     bool refilled = false;                      // ev2g_pool_refill ran: the host copies of the scenarios (peek) no longer describe the pool
@@ -169,14 +170,13 @@ struct ev2g_handle {
         RefillArgs args{};
     } refill_cache;
     int sess_cap = 0;                           // EV2G_FLAG_REFILLABLE: session slots per scenario of the resident pool (0: packed storage)
-    bool wave_path = false;                     // ev2g_step_wave: P <= 64, one transformer, single-port chargers
-    int wave_epw = 1, wave_es = 64;             // ... its envs per wavefront and the lane stride between them (WaveArgs::epw / es)
-    bool big_path = false;                      // ev2g_step_big (512 < P <= 1024, two workgroups per CU) takes the launches ev2g_step_v2<1024, 1> would
-    std::string big_reason;                     // why not ("" when it does / when the shape is not a big env)
+    // a launch's route (ev2g_route_host.h): what the load fixed of it, and what route_step made of the last step launch (launch_fused: 4) --
+    // the reporters and launch_stats read `last`; every call that changes the envs' state discards its in-launch statistics
+    RouteShape shape;
+    StepRoute last;
+    std::string big_reason;                     // why ev2g_step_big does not take the launches ev2g_step_v2<1024, 1> would ("" when it does / when the shape is not a big env)
     size_t lds_big = 0;
     BigArgs big_args{};
-    bool no_full = false, no_wide = false;      // EV2G_NO_FULL / EV2G_NO_WIDE at load time: A/B and routing tests only
-    bool no_strided = false;                    // EV2G_NO_STRIDED at load time: strided outputs run the general instantiation (round 4's routing; parity tests)
     // battery-maths dictionary (ClsRec, ev2g_device.h): host mirror of the entries in use, so that ev2g_pool_refill can append the
     // classes its fleet may draw; d_cls_rec has room for EV2G_CLS_CAP entries when DevScn::dict is set
     std::map<ClsKey, int> cls_map;
@@ -186,22 +186,15 @@ struct ev2g_handle {
     std::vector<double> cs_imax_host;           // [C] max_charge_current of the loaded chargers: only so that the refill can call ev2g_sess_consts, the one
                                                 // place the record constants are formed (the potc it yields is not part of a dictionary entry: ev2g_cls_of)
     int load_gen = 0;                           // counts ev2g_load_scenarios calls (part of the refill cache's key)
-    int last_spec = -1;                         // ev2g_last_launch_specialisation
     // in-launch episode statistics (ev2g_step_wave's INL phase): the last step launch closed the episode and wrote get_statistics of every env
     // into d_stats_inl; ev2g_get_stats / ev2g_get_stats_reset copy those rows while nothing has changed the state since (every state-changing
     // call clears the flag).  EV2G_NO_INLAUNCH_STATS=1 at load time: every episode end runs ev2g_stats_kernel (A/B, parity tests)
     double *d_stats_inl = nullptr;              // [E, EV2G_N_STATS]: the loaded shape has the in-launch phase (V2P::stats_inl points here), else nullptr
-    const char *inl_shape_reason = "";          // ... why not
-    bool inl_stats = false, no_inl_stats = false;
     // fast-forward of EV-free stretches (ev2g_step_wave's FFW path): per-workgroup counts of the last eligible launch; EV2G_NO_FAST_FORWARD=1 at load
     // time leaves the block (and V2P::ff_count) null, and every step is stepped (A/B, parity tests)
     unsigned long long *d_ff_count = nullptr;   // [n_groups]
-    bool no_fast_forward = false, ff_launch = false;   // ff_launch: the last launch was one whose kernel counts (ev2g_last_launch_fast_forwarded)
     int last_stats_route = -1;                  // ev2g_last_stats_route
-    const char *inl_reason = "";                // why the in-launch results are not available (the last step launch did not compute them, or they were discarded)
-    const char *stats_reason = "";              // ev2g_last_stats_reason: inl_reason at the last ev2g_get_stats / ev2g_get_stats_reset
-    const char *general_reason = "";            // ev2g_last_launch_general_reason
-    bool pow2_dt = false;                       // 60 / timescale is a power of two (15, 30, 60 minutes): compiled into ev2g_step_v2<.., 1>
+    const char *stats_reason = "";              // ev2g_last_stats_reason: last.inl_reason at the last ev2g_get_stats / ev2g_get_stats_reset
     std::string kernel_name;                    // the step kernel ev2g_load_scenarios selected (ev2g_kernel_name)
     std::string fallback_reason;                // why the common-shape fast path was NOT taken ("" when it was / does not apply)
     int current_step = 0;
@@ -213,7 +206,7 @@ struct ev2g_handle {
     hipEvent_t ev0s[EV2G_EV_RING] = {}, ev1s[EV2G_EV_RING] = {};
     int ev_slot = 0;
     bool ev_valid[EV2G_EV_RING] = {};          // the slot's closing event was recorded (a call that failed half-way leaves it false: its duration reads -1)
-    unsigned fused_attr_mask = 0;               // fused instantiations whose dynamic-LDS attribute was set for THIS handle's device (bit = state kind * 4 + reward kind)
+    unsigned fused_attr_mask = 0;               // fused instantiations whose dynamic-LDS attribute was set for THIS handle's device (bit = FusedRoute::index)
     long long ev_calls = 0;
     bool timed = false;
     std::string err;
@@ -274,6 +267,12 @@ static int dalloc(ev2g_handle *h, std::vector<void *> &pool, size_t n, T **dst) 
     *dst = (T *)p;
     return 0;
 }
+// every call that changes the envs' state: the last launch's in-launch statistics are no longer those of the state (`why`: what
+// ev2g_last_stats_reason reports), and a grid's float32 row is stale
+static void state_changed(ev2g_handle *h, const char *why) {
+    h->last.inl_stats = false; h->last.inl_reason = why; h->state_epoch += 1;
+}
+
 static void free_pool(std::vector<void *> &pool) {
     for (void *p : pool) (void)hipFree(p);
     pool.clear();
@@ -320,6 +319,72 @@ static void owned_destroy(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T
     (void)hipStreamSynchronize(h->stream);
     release(x);
 }
+
+// ---- the step kernels' launch tables ----
+// ev2g_route_host.h decides which instantiation a launch gets; these are the instantiations, one typed launch per entry, under the header's
+// indices.  An entry that does not exist is null (and never instantiated): tuning builds with -DEV2G_ONLY_00 (tools/) keep the cfg2 plugin
+// pair's and compile in seconds.
+#ifdef EV2G_ONLY_00
+constexpr bool kOnly00 = true;
+#else
+constexpr bool kOnly00 = false;
+#endif
+struct LaunchDims { dim3 grid; size_t lds; hipStream_t stream; };
+
+typedef void (*WaveLaunch)(const LaunchDims &, const V2P *, const StepIO &, int t0, int k, int auto_reset, const WaveArgs &);
+template <int SK, int RK, bool IO32, int FULLK>
+static void launch_wave(const LaunchDims &d, const V2P *pp, const StepIO &io, int t0, int k, int auto_reset, const WaveArgs &wa) {
+    hipLaunchKernelGGL((ev2g_step_wave<SK, RK, IO32, FULLK>), d.grid, dim3(EV2G_WAVE_BLOCK), d.lds, d.stream, pp, io, t0, k, auto_reset, wa, FusedArgs{});
+}
+template <int I>
+constexpr WaveLaunch wave_entry() {   // I == route_wave_index(SK, RK, IO32, FULLK)
+    constexpr int SK = I / 32, RK = I / 8 % 4, FULLK = I % 4;
+    constexpr bool IO32 = I / 4 % 2 != 0;
+    static_assert(route_wave_index(SK, RK, IO32, FULLK) == I, "the table's order is route_wave_index's");
+    if constexpr (route_wave_exists(SK, RK, IO32, FULLK) && (!kOnly00 || (SK == 0 && RK == 0))) return &launch_wave<SK, RK, IO32, FULLK>;
+    else return nullptr;
+}
+
+// ev2g_step_v2<block, SPEC>: the kernel (load_route sets its dynamic-LDS attribute) and its launch
+struct V2Entry {
+    const void *fn;
+    void (*launch)(const LaunchDims &, const V2P *, const StepIO &, int t0, int k, int auto_reset);
+};
+template <int BLOCK, int SPEC>
+static void launch_v2(const LaunchDims &d, const V2P *pp, const StepIO &io, int t0, int k, int auto_reset) {
+    hipLaunchKernelGGL((ev2g_step_v2<BLOCK, SPEC>), d.grid, dim3(BLOCK), d.lds, d.stream, pp, io, t0, k, auto_reset);
+}
+template <int BLOCK, int SPEC>
+static V2Entry v2_entry() { return {(const void *)ev2g_step_v2<BLOCK, SPEC>, &launch_v2<BLOCK, SPEC>}; }
+static const V2Entry &v2_kernel(int block, bool spec) {
+    static const V2Entry tab[3][2] = {{v2_entry<256, 0>(), v2_entry<256, 1>()}, {v2_entry<512, 0>(), v2_entry<512, 1>()}, {v2_entry<1024, 0>(), v2_entry<1024, 1>()}};
+    return tab[block == 256 ? 0 : block == 512 ? 1 : 2][spec ? 1 : 0];
+}
+
+// the fused actor + step instantiations (FusedRoute::index): the kernel (launch_fused sets its dynamic-LDS attribute once per handle) and its launch
+struct FusedEntry {
+    const void *fn;
+    void (*launch)(const LaunchDims &, const V2P *, const StepIO &, int t0, int k, const WaveArgs &, const FusedArgs &);
+};
+template <int SK, int RK, int AE, int NWF>
+static void launch_fused_kernel(const LaunchDims &d, const V2P *pp, const StepIO &io, int t0, int k, const WaveArgs &wa, const FusedArgs &fa) {
+    hipLaunchKernelGGL((ev2g_step_wave<SK, RK, true, 2, EV2G_FUSED_BLOCK, true, AE, NWF>), d.grid, dim3(EV2G_FUSED_BLOCK), d.lds, d.stream, pp, io, t0, k, 0, wa, fa);
+}
+template <int I>
+static FusedEntry fused_entry() {
+    constexpr FusedKey K = route_fused_key(I);
+    static_assert(!K.exists || route_fused_index(K.sk, K.rk, K.ae, K.nwf) == I, "the table's order is route_fused_index's");
+    if constexpr (K.exists && (!kOnly00 || K.sk == 0))
+        return {(const void *)ev2g_step_wave<K.sk, K.rk, true, 2, EV2G_FUSED_BLOCK, true, K.ae, K.nwf>, &launch_fused_kernel<K.sk, K.rk, K.ae, K.nwf>};
+    else return {nullptr, nullptr};
+}
+
+template <size_t... I>
+constexpr std::array<WaveLaunch, sizeof...(I)> wave_table(std::index_sequence<I...>) { return {wave_entry<(int)I>()...}; }
+template <size_t... I>
+static std::array<FusedEntry, sizeof...(I)> fused_table(std::index_sequence<I...>) { return {fused_entry<(int)I>()...}; }
+static constexpr std::array<WaveLaunch, ROUTE_WAVE_ENTRIES> kWaveTable = wave_table(std::make_index_sequence<ROUTE_WAVE_ENTRIES>{});
+static const std::array<FusedEntry, ROUTE_FUSED_ENTRIES> kFusedTable = fused_table(std::make_index_sequence<ROUTE_FUSED_ENTRIES>{});
 
 #include "ev2g_refill_host.h"
 
@@ -408,13 +473,13 @@ int ev2g_current_step(const ev2g_handle *h) { return h ? h->current_step : 0; }
 const char *ev2g_kernel_name(const ev2g_handle *h) { return (h && h->loaded) ? h->kernel_name.c_str() : ""; }
 const char *ev2g_fallback_reason(const ev2g_handle *h) { return (h && h->loaded) ? h->fallback_reason.c_str() : ""; }
 const char *ev2g_big_kernel_reason(const ev2g_handle *h) { return (h && h->loaded) ? h->big_reason.c_str() : ""; }
-int ev2g_last_launch_specialisation(const ev2g_handle *h) { return (h && h->loaded) ? h->last_spec : -1; }
+int ev2g_last_launch_specialisation(const ev2g_handle *h) { return (h && h->loaded) ? h->last.specialisation : -1; }
 int ev2g_last_stats_route(const ev2g_handle *h) { return (h && h->loaded) ? h->last_stats_route : -1; }
 const char *ev2g_last_stats_reason(const ev2g_handle *h) { return (h && h->loaded && h->last_stats_route == 0) ? h->stats_reason : ""; }
 int ev2g_last_launch_fast_forwarded(ev2g_handle *h, int64_t *steps, int64_t *stretches) {
     if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_last_launch_fast_forwarded: no scenarios loaded");
     int64_t n = 0, m = 0;
-    if (h->ff_launch) {   // the counts of the launch's workgroups, summed on demand
+    if (h->last.ff) {   // the counts of the launch's workgroups, summed on demand
         (void)hipSetDevice(h->device);
         std::vector<unsigned long long> c((size_t)h->scn.n_groups);
         HIPCHK(h, hipMemcpyAsync(c.data(), h->d_ff_count, sizeof(unsigned long long) * c.size(), hipMemcpyDeviceToHost, h->stream));
@@ -425,7 +490,7 @@ int ev2g_last_launch_fast_forwarded(ev2g_handle *h, int64_t *steps, int64_t *str
     if (stretches) *stretches = m;
     return EV2G_OK;
 }
-const char *ev2g_last_launch_general_reason(const ev2g_handle *h) { return (h && h->loaded && h->last_spec == 0) ? h->general_reason : ""; }
+const char *ev2g_last_launch_general_reason(const ev2g_handle *h) { return (h && h->loaded && h->last.specialisation == 0) ? h->last.general_reason : ""; }
 
 static const char *kStatNames[EV2G_N_STATS] = {
     "total_ev_served", "total_profits", "total_energy_charged", "total_energy_discharged",
@@ -459,9 +524,12 @@ static int load_route(ev2g_handle *h, const LoadPlan &p, const LoadSwitches &sw)
     s.E = E; s.M = M; s.T = T; s.C = C; s.npc = npc; s.P = P; s.R = R; s.D = D; s.ND = std::max(p.ND, 1); s.dt = p.dt;
     s.reward_kind = h->cfg.reward_kind; s.state_kind = sk; s.flags = h->cfg.flags; s.cost_kind = h->cfg.cost_kind; s.n_lut = p.n_lut;
     s.het = p.het ? 1 : 0;
+    RouteShape &rs = h->shape;
+    rs = RouteShape{};
+    rs.P = P; rs.T = T; rs.D = D; rs.npc = npc; rs.state_kind = sk; rs.reward_kind = h->cfg.reward_kind; rs.flags = h->cfg.flags;
     // v2 kernel: one home lane per port, BLOCK >= P; the generic kernel handles larger envs
-    h->block = p.het ? 0 : (P <= 256) ? 256 : (P <= 512) ? 512 : (P <= 1024) ? 1024 : 0;   // different port counts per charger: generic kernel
-    const int blk = h->block ? h->block : EV2G_BLOCK;
+    rs.block = p.het ? 0 : (P <= 256) ? 256 : (P <= 512) ? 512 : (P <= 1024) ? 1024 : 0;   // different port counts per charger: generic kernel
+    const int blk = rs.block ? rs.block : EV2G_BLOCK;
     s.G = std::max(1, blk / P);
     s.G = std::min(s.G, E);
     h->fallback_reason.clear();
@@ -469,33 +537,32 @@ static int load_route(ev2g_handle *h, const LoadPlan &p, const LoadSwitches &sw)
     else if (R != 1) h->fallback_reason = "more than one transformer";
     else if (npc != 1) h->fallback_reason = "multi-port chargers";
     if (p.het) h->fallback_reason = "chargers with different port counts (topology file)";
-    h->wave_path = h->fallback_reason.empty();
-    h->no_full = sw.no_full; h->no_wide = sw.no_wide; h->last_spec = -1;
-    h->no_strided = sw.no_strided;
-    h->no_fast_forward = sw.no_fast_forward; h->ff_launch = false;
-    h->no_inl_stats = sw.no_inl_stats; h->inl_stats = false; h->last_stats_route = -1; h->inl_reason = "no step launch since the scenarios were loaded";
+    bool wave = h->fallback_reason.empty();
+    rs.no_full = sw.no_full; rs.no_wide = sw.no_wide; rs.no_strided = sw.no_strided; rs.no_inl_stats = sw.no_inl_stats;
+    h->last = StepRoute{}; h->last.inl_reason = "no step launch since the scenarios were loaded"; h->last_stats_route = -1;
     h->state_epoch += 1;
-    if (h->wave_path) {   // ev2g_step_wave addresses every array as base + 32-bit byte offset: all of them must stay below 4 GiB
+    if (wave) {   // ev2g_step_wave addresses every array as base + 32-bit byte offset: all of them must stay below 4 GiB
         const unsigned long long lim = 1ull << 32;
         const unsigned long long biggest = std::max({(unsigned long long)E * P * 8, (unsigned long long)E * D * 8,
                                                      (unsigned long long)M * (T + 1) * 60 * 8, (unsigned long long)p.SD * sizeof(SessRec),
                                                      (unsigned long long)M * T * 64, (unsigned long long)E * T * 8 * 3, (unsigned long long)M * P * 8, (unsigned long long)E * P * sizeof(PortLine),
                                                      (h->cfg.flags & EV2G_FLAG_LOG_SOC) ? (unsigned long long)E * T * P * 8 : 0ull,
                                                      (h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) ? (unsigned long long)T * E * C * 8 : 0ull});
-        if (biggest >= lim) { h->wave_path = false; h->fallback_reason = "an array of the batch reaches 4 GiB (32-bit byte offsets)"; }
+        if (biggest >= lim) { wave = false; h->fallback_reason = "an array of the batch reaches 4 GiB (32-bit byte offsets)"; }
     }
-    if (h->wave_path) {   // wave-aligned: 64/P envs per wavefront, packed
-        h->wave_epw = 64 / P; h->wave_es = P;
-        s.G = (EV2G_WAVE_BLOCK / 64) * h->wave_epw;
+    if (wave && sw.kernel_v2) {   // EV2G_KERNEL=v2 forces the general kernel on the common shape (parity tests compare the two)
+        wave = false; h->fallback_reason = "EV2G_KERNEL=v2";
     }
-    if (h->wave_path && sw.kernel_v2) {   // EV2G_KERNEL=v2 forces the general kernel on the common shape (parity tests compare the two)
-        h->wave_path = false; h->fallback_reason = "EV2G_KERNEL=v2"; s.G = std::min(std::max(1, blk / P), E);
+    rs.family = wave ? ROUTE_WAVE : rs.block ? ROUTE_V2 : ROUTE_GENERIC;   // (load_route_big: ROUTE_V2 -> ROUTE_BIG)
+    if (wave) {   // wave-aligned: 64/P envs per wavefront, packed
+        rs.epw = 64 / P;
+        s.G = (EV2G_WAVE_BLOCK / 64) * rs.epw;
+        if (p.n_lut > 4094) rs.no_full = true;   // the full kernels keep table id + 1 in 12 bits of a port's LDS word
     }
-    if (h->wave_path && p.n_lut > 4094) h->no_full = true;   // the full kernels keep table id + 1 in 12 bits of a port's LDS word
     {
         char nm[64];
-        if (h->wave_path) std::snprintf(nm, sizeof nm, "ev2g_step_wave<%d,%d>", sk, std::min(h->cfg.reward_kind, 3));
-        else if (h->block) std::snprintf(nm, sizeof nm, "ev2g_step_v2<%d>", h->block);
+        if (wave) std::snprintf(nm, sizeof nm, "ev2g_step_wave<%d,%d>", sk, std::min(h->cfg.reward_kind, 3));
+        else if (rs.block) std::snprintf(nm, sizeof nm, "ev2g_step_v2<%d>", rs.block);
         else std::snprintf(nm, sizeof nm, "ev2g_step_kernel");
         h->kernel_name = nm;
     }
@@ -507,24 +574,18 @@ static int load_route(ev2g_handle *h, const LoadPlan &p, const LoadSwitches &sw)
     s.n_groups = (E + s.G - 1) / s.G;
     s.sixty_over_dt = 60.0 / (double)p.dt;
     s.dt_over_60 = (double)p.dt / 60.0;
-    if (h->wave_path)
+    if (wave)
         h->lds_bytes = ev2g_wave_lds_bytes(s.G);
-    else if (h->block)
+    else if (rs.block)
         h->lds_bytes = ev2g_v2_lds_bytes(s.G * P, s.G * R, s.G, R);
     else
         h->lds_bytes = ev2g_generic_lds_bytes(s.G, P, R, npc);
     if (h->lds_bytes > 160 * 1024)
         return fail(h, EV2G_ERR_ARG, "ev2g_load_scenarios: ports per env exceed the LDS staging capacity (P <= ~2400)");
-    const void *fn = h->block == 256 ? (const void *)ev2g_step_v2<256>
-                     : h->block == 512 ? (const void *)ev2g_step_v2<512>
-                     : h->block == 1024 ? (const void *)ev2g_step_v2<1024> : (const void *)ev2g_step_kernel;
-    if (h->lds_bytes > 48 * 1024)
-        HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    const void *fs = h->block == 256 ? (const void *)ev2g_step_v2<256, 1>
-                     : h->block == 512 ? (const void *)ev2g_step_v2<512, 1>
-                     : h->block == 1024 ? (const void *)ev2g_step_v2<1024, 1> : nullptr;
-    if (fs && h->lds_bytes > 48 * 1024)
-        HIPCHK(h, hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    if (h->lds_bytes > 48 * 1024) {
+        HIPCHK(h, hipFuncSetAttribute(rs.block ? v2_kernel(rs.block, false).fn : (const void *)ev2g_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        if (rs.block) HIPCHK(h, hipFuncSetAttribute(v2_kernel(rs.block, true).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    }
     return EV2G_OK;
 }
 
@@ -532,8 +593,8 @@ static int load_route(ev2g_handle *h, const LoadPlan &p, const LoadSwitches &sw)
 // of the specialised instantiation: single-port chargers, at most 50 transformers, at most EV2G_BIG_NCC distinct charger tuples, windows that fit
 // 16-bit step numbers.  EV2G_NO_BIG keeps ev2g_step_v2<1024> (A/B runs, parity tests).
 static int load_route_big(ev2g_handle *h, LoadPlan &p, const ev2g_scenario_batch *b, const LoadSwitches &sw) {
-    h->big_path = false; h->big_reason.clear(); h->big_args = BigArgs{};
-    if (h->block != 1024 || h->wave_path) return EV2G_OK;
+    h->big_reason.clear(); h->big_args = BigArgs{};
+    if (h->shape.block != 1024 || h->shape.wave()) return EV2G_OK;
     load_plan_big(p, b, EV2G_BIG_NCC);
     const size_t lb = ev2g_big_lds_bytes(p.P, p.R);
     if (sw.no_big) h->big_reason = "EV2G_NO_BIG is set";
@@ -547,7 +608,7 @@ static int load_route_big(ev2g_handle *h, LoadPlan &p, const ev2g_scenario_batch
     else if (p.E < 1) h->big_reason = "no envs";
     else {
         h->big_args.ncc = (int)(p.ctab.size() / 6);
-        h->lds_big = lb; h->big_path = true;
+        h->lds_big = lb; h->shape.family = ROUTE_BIG;
         HIPCHK(h, hipFuncSetAttribute((const void *)ev2g_step_big<EV2G_BIG_BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
     }
     return EV2G_OK;
@@ -584,7 +645,7 @@ static int load_upload(ev2g_handle *h, const LoadPlan &p, const ev2g_scenario_ba
     UP(dp, p.cs_min_kw) h->d_heur_cs_min_kw = dp;
     UP(ip, p.port_slot) h->d_port_slot = ip;
     UP(dp, p.cs_pack) s.cs_pack = dp;
-    if (h->big_path) {
+    if (h->shape.big()) {
         unsigned char *cp; UP(cp, p.ccls) h->big_args.slot_ccls = cp;
         UP(dp, p.ctab) h->big_args.ccls_tab = dp;
         UP(dp, p.ptab) h->big_args.potc_tab = dp;
@@ -639,7 +700,7 @@ static int load_upload(ev2g_handle *h, const LoadPlan &p, const ev2g_scenario_ba
     { SessRec *rp; UP(rp, p.recs) s.rec = rp; }
     { SessTail *tp; UP(tp, p.tails) s.tail = tp; }
     s.sess_dyn = nullptr; s.cls_rec = nullptr; s.dict = 0; s.n_cls = 0; h->d_cls_rec = nullptr;
-    if (h->wave_path) {
+    if (h->shape.wave()) {
         SessDyn *dp2; UP(dp2, p.dyns) s.sess_dyn = dp2;
         ClsRec *cp; UP(cp, p.cls_tab) s.cls_rec = cp; h->d_cls_rec = cp;
         s.dict = p.dict ? 1 : 0; s.n_cls = p.dict ? (int)p.cls_map.size() : 0;
@@ -656,7 +717,7 @@ static int load_build_tables(ev2g_handle *h) {
     auto &pool = h->scn_allocs;
     const int M = s.M, T = s.T, R = s.R, sk = s.state_kind;
     s.win_tab = nullptr;
-    if (sk == EV2G_STATE_V2G_PROFIT_MAX_LOADS && h->block) {
+    if (sk == EV2G_STATE_V2G_PROFIT_MAX_LOADS && h->shape.block) {
         double *tab = nullptr;
         const size_t n = (size_t)M * R * (T + 1) * 40;
         HIPCHK(h, hipMalloc((void **)&tab, n * sizeof(double)));
@@ -667,7 +728,7 @@ static int load_build_tables(ev2g_handle *h) {
         s.win_tab = tab;
     }
     h->d_step_tab = nullptr;
-    if (h->wave_path) {   // R == 1: [M,T] series interleaved per (env, step)
+    if (h->shape.wave()) {   // R == 1: [M,T] series interleaved per (env, step)
         double *d_step_tab = nullptr;
         const size_t n = (size_t)M * T * 8;
         HIPCHK(h, hipMalloc((void **)&d_step_tab, n * sizeof(double)));
@@ -681,7 +742,7 @@ static int load_build_tables(ev2g_handle *h) {
     }
     h->d_head_tab = nullptr; h->head_nh = 0;
     s.head_tab = nullptr; s.head_nh = 0;
-    if (h->wave_path && sk != EV2G_STATE_PUBLIC_PST) {
+    if (h->shape.wave() && sk != EV2G_STATE_PUBLIC_PST) {
         double *d_head_tab = nullptr;
         const int NH = (sk == EV2G_STATE_V2G_PROFIT_MAX_LOADS) ? 60 : 20;
         const size_t n = (size_t)M * (T + 1) * NH;
@@ -709,7 +770,7 @@ static int load_alloc_state(ev2g_handle *h, long long SD) {
     {   // per-port state: one 64-byte line per port + one slab of EV2G_PS_* slices for what is not on the step's path
         AL(line, EP)
         HIPCHK(h, hipMemsetAsync(st.line, 0, EP * sizeof(PortLine), h->stream));
-        if (h->wave_path) { AL(port_dyn, EP) }
+        if (h->shape.wave()) { AL(port_dyn, EP) }
         const size_t slice = std::max(EP, EC) * 8;
         if ((rc = dalloc(h, sp, slice * EV2G_PS_N, &st.slab_port))) return rc;
         st.slab_port_slice = slice;
@@ -746,21 +807,22 @@ static int load_params(ev2g_handle *h, double *d_lut_eta, V2P &v2p) {
     EV2G_SETP(v2p.ss_afap, h->d_ss_afap);
     int ex = 0;   // 60/dt a power of two and dt/60 its exact reciprocal -> divisions by them are multiplications
     v2p.pow2_dt = (std::frexp(h->scn.sixty_over_dt, &ex) == 0.5 && h->scn.sixty_over_dt * h->scn.dt_over_60 == 1.0) ? 1 : 0;
-    h->pow2_dt = v2p.pow2_dt != 0;
+    h->shape.pow2_dt = v2p.pow2_dt != 0;
     return upload(h, h->st_allocs, &v2p, 1, &h->d_v2p);
 }
 
 // The in-launch statistics phase: a shape the statistics kernel runs with one env per wavefront (its summation order), like the phase
-static int load_decide_inl_stats(ev2g_handle *h) {
+static int load_decide_inl_stats(ev2g_handle *h, const LoadSwitches &sw) {
+    RouteShape &rs = h->shape;
     h->d_stats_inl = nullptr;
     const char *why = "";
-    if (h->no_inl_stats) why = "EV2G_NO_INLAUNCH_STATS is set";
-    else if (!h->wave_path || !(h->cfg.flags & EV2G_FLAG_LOG_SOC)) why = "the step kernel is not ev2g_step_wave with the SoC log";
-    else if (h->wave_epw != 1 || stats_pair(h)) why = "several envs per wavefront (the in-launch phase computes one env per wavefront, like the statistics kernel at this shape)";
+    if (rs.no_inl_stats) why = "EV2G_NO_INLAUNCH_STATS is set";
+    else if (!rs.wave() || !(h->cfg.flags & EV2G_FLAG_LOG_SOC)) why = "the step kernel is not ev2g_step_wave with the SoC log";
+    else if (rs.epw != 1 || stats_pair(h)) why = "several envs per wavefront (the in-launch phase computes one env per wavefront, like the statistics kernel at this shape)";
     else if (h->lds_bytes < ev2g_inl_stats_lds_bytes()) why = "the step kernel's LDS is smaller than the phase's blocks";
-    h->inl_shape_reason = why;
+    rs.inl_shape_reason = why;
     h->d_ff_count = nullptr;
-    if (h->wave_path && h->wave_epw == 1 && !h->no_fast_forward) {   // the fast-forward's per-workgroup counts: what switches it on
+    if (rs.wave() && rs.epw == 1 && !sw.no_fast_forward) {   // the fast-forward's per-workgroup counts: what switches it on
         int rc = 0;
         if ((rc = dalloc(h, h->st_allocs, (size_t)h->scn.n_groups, &h->d_ff_count))) return rc;
         unsigned long long *p = h->d_ff_count;
@@ -772,6 +834,7 @@ static int load_decide_inl_stats(ev2g_handle *h) {
         double *p = h->d_stats_inl;
         HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, stats_inl), &p, sizeof p, hipMemcpyHostToDevice));
     }
+    rs.ff_count = h->d_ff_count != nullptr; rs.stats_inl = h->d_stats_inl != nullptr;
     return EV2G_OK;
 }
 
@@ -797,7 +860,7 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     load_plan_constants(plan, b);
     load_plan_records(plan, b);
     if ((rc = load_route(h, plan, sw))) return rc;
-    load_plan_dictionary(plan, h->wave_path, sw);
+    load_plan_dictionary(plan, h->shape.wave(), sw);
     if ((rc = load_route_big(h, plan, b, sw))) return rc;
 
     double *d_lut_eta = nullptr;
@@ -809,7 +872,7 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the plan's vectors and v2p are free to die from here
 
     h->E = plan.E; h->M = plan.M; h->scn_off = 0; h->T = plan.T; h->C = plan.C; h->npc = plan.npc; h->P = plan.P; h->R = plan.R; h->D = plan.D; h->S = plan.S;
-    if ((rc = load_decide_inl_stats(h))) return rc;
+    if ((rc = load_decide_inl_stats(h, sw))) return rc;
     // host mirrors for peek / stats / refill
     h->slot_port = std::move(plan.slot_port);
     h->port_slot = std::move(plan.port_slot);
@@ -845,7 +908,7 @@ int ev2g_reset_ex(ev2g_handle *h, double *obs, int64_t scenario_offset) {
     hipLaunchKernelGGL(ev2g_reset_kernel, dim3(s.n_groups), dim3(EV2G_BLOCK), 0, h->stream, s, h->st, obs, h->extras.obs_f32, (int)off);
     HIPCHK(h, hipGetLastError());
     h->current_step = 0;
-    h->inl_stats = false; h->inl_reason = "the episode was reset"; h->state_epoch += 1;
+    state_changed(h, "the episode was reset");
     return EV2G_OK;
 }
 
@@ -904,136 +967,45 @@ static StepIO make_io(const ev2g_handle *h, const StepRows &r, long long step0, 
     return io;
 }
 
+// One step launch: route_step (ev2g_route_host.h) decides from the loaded shape and from what this call passes, the decision is stored for the
+// reporters and for launch_stats, and its table entry is launched.
 static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int auto_reset) {
     const DevScn &s = h->scn;
-    h->inl_stats = false; h->inl_reason = "the step kernel is not ev2g_step_wave"; h->state_epoch += 1;
-    h->ff_launch = false;
-    if (h->wave_path) {
-        // the fast path advances its output pointers by 32-bit byte strides
-        const long long lim = 1ll << 32;
-        const ev2g_step_extras &x = h->extras;
-        if (io.a_stride * 8 >= lim || io.o_stride * 8 >= lim || io.r_stride * 8 >= lim || io.d_stride >= lim || io.m_stride >= lim ||
-            x.cost_step_stride * 8 >= lim || x.obs_f32_step_stride * 4 >= lim || io.a_stride < 0 || io.o_stride < 0 || io.r_stride < 0 ||
-            io.d_stride < 0 || io.m_stride < 0 || x.cost_step_stride < 0 || x.obs_f32_step_stride < 0)
-            return fail(h, EV2G_ERR_ARG, "ev2g_step_n: a step stride is negative or reaches 4 GiB (unsupported by the fast-path kernel)");
-        const V2P *pp = (const V2P *)h->d_v2p;
+    const ev2g_step_extras &x = h->extras;
+    h->state_epoch += 1;
+    RouteCall c;
+    c.actions = io.actions != nullptr; c.act32 = io.act32 != nullptr; c.obs = io.obs != nullptr; c.obs32 = io.obs32 != nullptr;
+    c.reward = io.reward != nullptr; c.done = io.done != nullptr; c.mask = io.mask != nullptr;
+    c.a_stride = io.a_stride; c.o_stride = io.o_stride; c.r_stride = io.r_stride; c.d_stride = io.d_stride; c.m_stride = io.m_stride;
+    c.x_cost = x.cost != nullptr; c.x_obs_f32 = x.obs_f32 != nullptr; c.x_actions_f32 = x.actions_f32 != nullptr;
+    c.x_cost_stride = x.cost_step_stride; c.x_obs_f32_stride = x.obs_f32_step_stride;
+    c.t0 = t0; c.k = k; c.auto_reset = auto_reset;
+    const StepRoute r = route_step(h->shape, c);
+    if (r.refusal) {   // (nothing ran: the specialisation and its reason stay those of the launch before; its side results are gone all the same)
+        h->last.inl_stats = false; h->last.ff = false; h->last.inl_reason = r.inl_reason;
+        return fail(h, EV2G_ERR_ARG, r.refusal);
+    }
+    h->last = r;
+    const V2P *pp = (const V2P *)h->d_v2p;
+    const LaunchDims d{dim3(s.n_groups), h->lds_bytes, h->stream};
+    switch (r.family) {
+    case ROUTE_WAVE: {
         const DevState &st = h->st;
-        const FusedArgs fa0{};
         const WaveArgs wa{s.P, s.T, s.E, s.D, s.M, st.slab_port, st.slab_port_slice, st.hist,
-                    st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->wave_epw, h->wave_es};
-        // every float64 output present, no extras, no charger histories: the specialisation without their checks (not for the run-time rewards)
-        // ... in two flavours: float64 actions in / float64 observations out (a loop that consumes them, the benchmark), or the policy
-        // network's hand-over, float32 actions in / float32 observations out and no float64 observation (ev2g_rollout)
-        const bool f64io = io.actions && io.obs && !x.obs_f32, f32io = !io.actions && io.act32 && !io.obs && io.obs32;
-        const bool full0 = (f64io || f32io) && io.reward && io.done && io.mask && !x.cost && !(h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) &&
-                           !auto_reset && t0 + k <= s.T && std::min(s.reward_kind, 3) != 3 && !h->no_full;
-        // ... and: SoC log on, one observation-head column pair per lane at most (PublicPST has no head table), three lanes for the history store
-        const bool wide0 = full0 && (h->cfg.flags & EV2G_FLAG_LOG_SOC) && s.P >= 3 && !h->no_wide &&
-                           s.P >= (s.state_kind == EV2G_STATE_PUBLIC_PST ? 3 : (s.state_kind == EV2G_STATE_V2G_PROFIT_MAX_LOADS ? 30 : 10));
-        // outputs with step strides ([K, E, *] blocks): the wide float64 instantiation with running output pointers (3); elsewhere stride 0 only
-        const bool strided = io.o_stride != 0 || io.r_stride != 0 || io.d_stride != 0 || io.m_stride != 0;
-        const bool str3 = strided && wide0 && f64io && !h->no_strided;
-        const bool full = full0 && (!strided || str3), wide = wide0 && full;
-        h->last_spec = full ? (str3 ? 3 : (wide ? 2 : 1)) : 0;
-        // (the kernel applies the same rule: a stride-0 float64 full instantiation of a head-table state, V2P::ff_count set -- one env per wavefront --, k > 1)
-        h->ff_launch = full && !str3 && f64io && k > 1 && h->d_ff_count != nullptr && s.state_kind != EV2G_STATE_PUBLIC_PST;
-        {   // why not the full instantiation: the FIRST thing the caller passed (or configured) that rules it out -- ev2g_last_launch_general_reason
-            const char *why = "";
-            if (!full) {
-                if (h->no_full) why = "EV2G_NO_FULL is set (or the batch has more than 4094 efficiency tables)";
-                else if (std::min(s.reward_kind, 3) == 3) why = "the reward function is one of the eight selected at run time (only the shipped configs' three are compiled in)";
-                else if (h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) why = "EV2G_FLAG_LOG_CS_HISTORY (charger histories)";
-                else if (x.cost) why = "a cost buffer is registered (ev2g_set_step_extras)";
-                else if (auto_reset) why = "auto_reset";
-                else if (!(io.reward && io.done && io.mask)) why = "a reward / done / mask output is NULL";
-                else if (!(f64io || f32io)) why = "the observation / action buffers are neither the float64 pair nor the float32 hand-over pair (e.g. obs NULL, or a float32 observation copy next to the float64 one)";
-                else if (strided) why = "an output step stride is not 0 (strided outputs keep the specialisation only with float64 observations, EV2G_FLAG_LOG_SOC and an env wide enough for the wide instantiation)";
-                else why = "the launch would run past the episode end";
-            }
-            h->general_reason = why;
-        }
-        {   // a launch of the float64 wide instantiation (2) that ends the episode computes its statistics in its tail (INL, ev2g_step_wave.h)
-            const char *why = "";
-            if (h->no_inl_stats) why = "EV2G_NO_INLAUNCH_STATS is set";
-            else if (t0 + k != s.T) why = "the last step launch did not end the episode";
-            else if (k < 2) why = "the episode ended in a single-step launch (per-step launches keep the statistics kernel)";
-            else if (!(wide && !str3 && f64io)) why = "the last step launch was not the float64 wide instantiation with step stride 0 (ev2g_last_launch_specialisation 2)";
-            else if (!h->d_stats_inl) why = h->inl_shape_reason;
-            h->inl_reason = why;
-            h->inl_stats = why[0] == 0;   // (the kernel applies the same rule: V2P::stats_inl set, k > 1, the launch ends at T -- ev2g_step_wave.h)
-        }
-#define EV2G_WAVE_CASE(SK, RK)                                                                                              \
-    case SK * 4 + RK:                                                                                                       \
-        if (full && RK != 3 && str3)                                                                                        \
-            hipLaunchKernelGGL((ev2g_step_wave<SK, (RK == 3 ? 0 : RK), false, 3>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, \
-                               h->stream, pp, io, t0, k, auto_reset, wa, fa0);                                                   \
-        else if (full && RK != 3 && wide && f32io)                                                                          \
-            hipLaunchKernelGGL((ev2g_step_wave<SK, (RK == 3 ? 0 : RK), true, 2>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, \
-                               h->stream, pp, io, t0, k, auto_reset, wa, fa0);                                                   \
-        else if (full && RK != 3 && f32io)                                                                                  \
-            hipLaunchKernelGGL((ev2g_step_wave<SK, (RK == 3 ? 0 : RK), true, 1>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, \
-                               h->stream, pp, io, t0, k, auto_reset, wa, fa0);                                                   \
-        else if (full && RK != 3 && wide)                                                                                   \
-            hipLaunchKernelGGL((ev2g_step_wave<SK, (RK == 3 ? 0 : RK), false, 2>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, \
-                               h->stream, pp, io, t0, k, auto_reset, wa, fa0);                                                   \
-        else if (full && RK != 3)                                                                                           \
-            hipLaunchKernelGGL((ev2g_step_wave<SK, (RK == 3 ? 0 : RK), false, 1>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes, \
-                               h->stream, pp, io, t0, k, auto_reset, wa, fa0);                                                   \
-        else if (!io.actions)                                                                                               \
-            hipLaunchKernelGGL((ev2g_step_wave<SK, RK, true>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes,       \
-                               h->stream, pp, io, t0, k, auto_reset, wa, fa0);                                                   \
-        else                                                                                                                \
-            hipLaunchKernelGGL((ev2g_step_wave<SK, RK, false>), dim3(s.n_groups), dim3(EV2G_WAVE_BLOCK), h->lds_bytes,      \
-                               h->stream, pp, io, t0, k, auto_reset, wa, fa0);                                                   \
+                    st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->shape.epw, s.P};
+        const WaveLaunch launch = kWaveTable[route_wave_index(r.sk, r.rk, r.io32, r.fullk)];
+        if (!launch) return fail(h, EV2G_ERR_ARG, "EV2G_ONLY_00 build: only the cfg2 specialisation exists");   // (every entry a route names exists in a full build: tests/host/route_check.cpp)
+        launch(d, pp, io, t0, k, auto_reset, wa);
+    } break;
+    case ROUTE_BIG:
+        hipLaunchKernelGGL(ev2g_step_big<EV2G_BIG_BLOCK>, dim3(s.E), dim3(EV2G_BIG_BLOCK), h->lds_big, h->stream, pp, io, t0, k, h->big_args);
         break;
-        switch (s.state_kind * 4 + std::min(s.reward_kind, 3)) {   // rewards beyond the three compiled-in ones share instantiation 3
-#ifdef EV2G_ONLY_00   /* tuning builds (tools/): one specialisation, seconds to compile */
-            EV2G_WAVE_CASE(0, 0)
-            default: return fail(h, EV2G_ERR_ARG, "EV2G_ONLY_00 build: only the cfg2 specialisation exists");
-#else
-            EV2G_WAVE_CASE(0, 0) EV2G_WAVE_CASE(0, 1) EV2G_WAVE_CASE(0, 2) EV2G_WAVE_CASE(0, 3)
-            EV2G_WAVE_CASE(1, 0) EV2G_WAVE_CASE(1, 1) EV2G_WAVE_CASE(1, 2) EV2G_WAVE_CASE(1, 3)
-            EV2G_WAVE_CASE(2, 0) EV2G_WAVE_CASE(2, 1) EV2G_WAVE_CASE(2, 2) EV2G_WAVE_CASE(2, 3)
-#endif
-        }
-#undef EV2G_WAVE_CASE
-        HIPCHK(h, hipGetLastError());
-        return EV2G_OK;
-    }
-    // the general kernel's instantiation for the default plugin pair launched with everything present (ev2g_step_v2.h, SPEC)
-    const bool spec = h->block && s.state_kind == EV2G_STATE_V2G_PROFIT_MAX_LOADS && s.reward_kind == 0 && s.npc == 1 && io.actions && io.obs &&
-                      io.reward && io.done && io.mask && !h->extras.cost && !h->extras.obs_f32 && !(h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) &&
-                      (h->cfg.flags & EV2G_FLAG_LOG_SOC) && io.o_stride == 0 && io.r_stride == 0 && io.d_stride == 0 && io.m_stride == 0 &&
-                      !auto_reset && t0 + k <= s.T && h->pow2_dt && !h->no_full;
-    h->last_spec = h->block ? (spec ? (h->big_path ? 5 : 1) : 0) : -1;
-    if (spec && h->big_path) {   // big envs: 512 threads, two ports per home lane, two workgroups per CU (ev2g_step_big.h)
-        hipLaunchKernelGGL(ev2g_step_big<EV2G_BIG_BLOCK>, dim3(s.E), dim3(EV2G_BIG_BLOCK), h->lds_big, h->stream, (const V2P *)h->d_v2p, io, t0, k, h->big_args);
-        HIPCHK(h, hipGetLastError());
-        return EV2G_OK;
-    }
-    if (spec) {
-        switch (h->block) {
-        case 256: hipLaunchKernelGGL((ev2g_step_v2<256, 1>), dim3(s.n_groups), dim3(256), h->lds_bytes, h->stream, (const V2P *)h->d_v2p, io, t0, k, auto_reset); break;
-        case 512: hipLaunchKernelGGL((ev2g_step_v2<512, 1>), dim3(s.n_groups), dim3(512), h->lds_bytes, h->stream, (const V2P *)h->d_v2p, io, t0, k, auto_reset); break;
-        default: hipLaunchKernelGGL((ev2g_step_v2<1024, 1>), dim3(s.n_groups), dim3(1024), h->lds_bytes, h->stream, (const V2P *)h->d_v2p, io, t0, k, auto_reset); break;
-        }
-        HIPCHK(h, hipGetLastError());
-        return EV2G_OK;
-    }
-    switch (h->block) {
-    case 256:
-        hipLaunchKernelGGL(ev2g_step_v2<256>, dim3(s.n_groups), dim3(256), h->lds_bytes, h->stream, (const V2P *)h->d_v2p, io, t0, k, auto_reset);
-        break;
-    case 512:
-        hipLaunchKernelGGL(ev2g_step_v2<512>, dim3(s.n_groups), dim3(512), h->lds_bytes, h->stream, (const V2P *)h->d_v2p, io, t0, k, auto_reset);
-        break;
-    case 1024:
-        hipLaunchKernelGGL(ev2g_step_v2<1024>, dim3(s.n_groups), dim3(1024), h->lds_bytes, h->stream, (const V2P *)h->d_v2p, io, t0, k, auto_reset);
+    case ROUTE_V2:
+        v2_kernel(r.block, r.spec).launch(d, pp, io, t0, k, auto_reset);
         break;
     default:
-        hipLaunchKernelGGL(ev2g_step_kernel, dim3(s.n_groups), dim3(EV2G_BLOCK), h->lds_bytes, h->stream, s, h->st, io,
-                           StepExtras{h->extras.cost, h->extras.cost_step_stride, h->extras.obs_f32, h->extras.obs_f32_step_stride, h->extras.actions_f32},
-                           t0, k, auto_reset);
+        hipLaunchKernelGGL(ev2g_step_kernel, d.grid, dim3(EV2G_BLOCK), d.lds, d.stream, s, h->st, io,
+                           StepExtras{x.cost, x.cost_step_stride, x.obs_f32, x.obs_f32_step_stride, x.actions_f32}, t0, k, auto_reset);
     }
     HIPCHK(h, hipGetLastError());
     return EV2G_OK;
@@ -1361,89 +1333,42 @@ int ev2g_mlp_debug_stamps(ev2g_handle *h, const ev2g_mlp *m, unsigned long long 
 #endif
 
 // ---- one launch per rollout segment (round 5): ev2g_step_wave<.., 1024, true> evaluates the policy between the steps, inside the launch ----
-// Eligible: the fast path (3..64 ports: the shipped YAMLs' 25 chargers, BASELINE configs[1] / configs[4]'s 50; every env gets a wavefront of its own in
-// this instantiation, whatever its width), a head-table state (V2G_profit_max_loads /
-// V2G_profit_max), one of the three compiled-in rewards, EV2G_FLAG_LOG_SOC, no extras beyond the float32 hand-over, and the bf16 policy in the
-// streaming kernel's 162 -> 400 -> 300 -> 64 packing.  Anything else (and EV2G_NO_FUSED=1) keeps the two launches per step.
-static bool fused_eligible(const ev2g_handle *h, const ev2g_mlp *m) {
-    const DevScn &s = h->scn;
-    // (round 6: PublicPST too -- its 3 + 3 P <= 63 inputs and P <= 20 outputs in the 64 -> 400 -> 300 -> 32 packing; the other states in 192 -> 400 -> 300 -> 64)
-    const bool pst = s.state_kind == EV2G_STATE_PUBLIC_PST;
-    return h->wave_path && s.P >= 3 && s.P <= 64 && std::min(s.reward_kind, 3) != 3 && (h->cfg.flags & EV2G_FLAG_LOG_SOC) &&
-           !(h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) && !h->extras.cost && !h->no_full && !h->no_wide && (pst || (s.D & 1) == 0) &&
-           m->s16_ks1 == (pst ? 2 : 6) && m->s16_nt1 == 25 && m->s16_nt2 == 19 && m->s16_nt3 == (pst ? 2 : 4) &&
-           (m->s16_nw == 1 || (m->s16_nw == 2 && !std::getenv("EV2G_NO_FUSED_F32"))) &&   // (last session of round 6: the float32 policy, two bf16 terms per weight; one env per wavefront)
-           !std::getenv("EV2G_NO_FUSED");
+// route_fused (ev2g_route_host.h) says whether the loaded shape and this policy get it, and which instantiation; EV2G_NO_FUSED=1 and (the
+// float32 policy) EV2G_NO_FUSED_F32=1, read at every call, keep the two launches per step.
+static FusedRoute fused_route(const ev2g_handle *h, const ev2g_mlp *m) {
+    return route_fused(h->shape, h->extras.cost != nullptr, FusedPacking{m->s16_ks1, m->s16_nt1, m->s16_nt2, m->s16_nt3, m->s16_nw},
+                       std::getenv("EV2G_NO_FUSED") != nullptr, std::getenv("EV2G_NO_FUSED_F32") != nullptr);
 }
 // k steps from the current one; obs0: the [E, D] float32 rows the first forward reads; obs / act / reward / done / mask: the rows of the segment's first
 // step with their step strides
-static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, int k, const float *obs0, Rows<float> obs, Rows<float> act, Rows<double> reward,
-                        Rows<uint8_t> done, Rows<uint8_t> mask) {
+static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, const FusedRoute &fr, int k, const float *obs0, Rows<float> obs, Rows<float> act,
+                        Rows<double> reward, Rows<uint8_t> done, Rows<uint8_t> mask) {
     const DevScn &s = h->scn;
     const DevState &st = h->st;
     const long long lim = 1ll << 32;
-    h->inl_stats = false; h->inl_reason = "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)"; h->state_epoch += 1;
-    h->ff_launch = false;
+    state_changed(h, "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)");
+    h->last.ff = false;
     if (obs.stride * 4 >= lim || act.stride * 4 >= lim || reward.stride * 8 >= lim || done.stride >= lim || mask.stride >= lim || obs.stride < 0 ||
         act.stride < 0 || reward.stride < 0 || done.stride < 0 || mask.stride < 0)
         return fail(h, EV2G_ERR_ARG, "ev2g_collect / ev2g_rollout: a step stride is negative or reaches 4 GiB");
     StepIO io = make_io(h, StepRows{{nullptr, act.stride}, {nullptr, obs.stride}, reward, done, mask}, 0, 0);
     io.act32 = act.p; io.obs32 = obs.p;
     // round 6: PublicPST envs of at most 32 ports go TWO to a wavefront (32 policy rows per workgroup)
-    const int ae = (s.state_kind == EV2G_STATE_PUBLIC_PST && s.P <= 32 && m->s16_nw == 1) ? 2 : 1;
+    const int ae = fr.ae;
     const WaveArgs wa{s.P, s.T, s.E, s.D, s.M, st.slab_port, st.slab_port_slice, st.hist, st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, ae, ae == 1 ? s.P : 32};
     FusedArgs fa{};
     fa.m = m->dev; fa.obs0 = obs0;
-    const V2P *pp = (const V2P *)h->d_v2p;
-    const int nwf = m->s16_nw;
-    const size_t lds = ev2g_fused_lds_bytes(ae, nwf);
-    const dim3 grid((s.E + 16 * ae - 1) / (16 * ae)), block(EV2G_FUSED_BLOCK);
-    const int t0 = h->current_step;
-#define EV2G_FUSED_CASE(SK, RK)                                                                                                            \
-    case SK * 4 + RK: {                                                                                                                    \
-        auto kfn = ev2g_step_wave<SK, RK, true, 2, EV2G_FUSED_BLOCK, true>;                                                                 \
-        if (!(h->fused_attr_mask & (1u << (SK * 4 + RK)))) {   /* function attributes are per device: once per handle, not per process */       \
-            HIPCHK(h, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-            h->fused_attr_mask |= 1u << (SK * 4 + RK);                                                                                     \
-        }                                                                                                                                  \
-        hipLaunchKernelGGL(kfn, grid, block, lds, h->stream, pp, io, t0, k, 0, wa, fa);                                                     \
-    } break;
-#define EV2G_FUSED_CASE2(RK)                                                                                                               \
-    case 16 + RK: {                                                                                                                        \
-        auto kfn = ev2g_step_wave<1, RK, true, 2, EV2G_FUSED_BLOCK, true, 2>;                                                               \
-        if (!(h->fused_attr_mask & (1u << (16 + RK)))) {                                                                                   \
-            HIPCHK(h, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-            h->fused_attr_mask |= 1u << (16 + RK);                                                                                         \
-        }                                                                                                                                  \
-        hipLaunchKernelGGL(kfn, grid, block, lds, h->stream, pp, io, t0, k, 0, wa, fa);                                                     \
-    } break;
-#define EV2G_FUSED_CASEF(SK, RK)   /* the float32 policy (two bf16 terms per weight) inside the launch */                                  \
-    case 20 + SK * 4 + RK: {                                                                                                               \
-        auto kfn = ev2g_step_wave<SK, RK, true, 2, EV2G_FUSED_BLOCK, true, 1, 2>;                                                           \
-        if (!(h->fused_attr_mask & (1u << (20 + SK * 4 + RK)))) {                                                                          \
-            HIPCHK(h, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-            h->fused_attr_mask |= 1u << (20 + SK * 4 + RK);                                                                                \
-        }                                                                                                                                  \
-        hipLaunchKernelGGL(kfn, grid, block, lds, h->stream, pp, io, t0, k, 0, wa, fa);                                                     \
-    } break;
-    switch (nwf == 2 ? 20 + s.state_kind * 4 + std::min(s.reward_kind, 3) : (ae == 2 ? 16 + std::min(s.reward_kind, 3) : s.state_kind * 4 + std::min(s.reward_kind, 3))) {
-        EV2G_FUSED_CASE(0, 0) EV2G_FUSED_CASE(0, 1) EV2G_FUSED_CASE(0, 2)
-        EV2G_FUSED_CASEF(0, 0) EV2G_FUSED_CASEF(0, 1) EV2G_FUSED_CASEF(0, 2)
-#ifndef EV2G_ONLY_00
-        EV2G_FUSED_CASEF(2, 0) EV2G_FUSED_CASEF(2, 1) EV2G_FUSED_CASEF(2, 2)
-        EV2G_FUSED_CASEF(1, 0) EV2G_FUSED_CASEF(1, 1) EV2G_FUSED_CASEF(1, 2)
-        EV2G_FUSED_CASE(1, 0) EV2G_FUSED_CASE(1, 1) EV2G_FUSED_CASE(1, 2)
-        EV2G_FUSED_CASE(2, 0) EV2G_FUSED_CASE(2, 1) EV2G_FUSED_CASE(2, 2)
-        EV2G_FUSED_CASE2(0) EV2G_FUSED_CASE2(1) EV2G_FUSED_CASE2(2)
-#endif
-        default: return fail(h, EV2G_ERR_STATE, "internal: no fused instantiation for this plugin pair");
+    const LaunchDims d{dim3((s.E + 16 * ae - 1) / (16 * ae)), ev2g_fused_lds_bytes(ae, fr.nwf), h->stream};
+    const FusedEntry *e = (fr.index >= 0 && fr.index < ROUTE_FUSED_ENTRIES) ? &kFusedTable[(size_t)fr.index] : nullptr;
+    if (!e || !e->fn) return fail(h, EV2G_ERR_STATE, "internal: no fused instantiation for this plugin pair");
+    if (!(h->fused_attr_mask & (1u << fr.index))) {   // function attributes are per device: once per handle, not per process
+        HIPCHK(h, hipFuncSetAttribute(e->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds));
+        h->fused_attr_mask |= 1u << fr.index;
     }
-#undef EV2G_FUSED_CASE
-#undef EV2G_FUSED_CASE2
-#undef EV2G_FUSED_CASEF
+    e->launch(d, (const V2P *)h->d_v2p, io, h->current_step, k, wa, fa);
     HIPCHK(h, hipGetLastError());
-    h->last_spec = 4;
-    h->general_reason = "";
+    h->last.specialisation = 4;
+    h->last.general_reason = "";
     return EV2G_OK;
 }
 
@@ -1466,8 +1391,9 @@ int ev2g_rollout(ev2g_handle *h, const ev2g_mlp *m, int k_steps, double *reward,
     int rc = EV2G_OK;
     static const bool use_graphs = [] { const char *e = std::getenv("EV2G_ROLLOUT_GRAPHS"); return !(e && e[0] == '0'); }();
     const bool whole = h->current_step + k_steps <= h->T;   // no episode end inside the segment: nothing but kernel launches
-    if (whole && k_steps >= 1 && reward && done && mask && fused_eligible(h, m)) {   // ONE launch: the policy between the steps, inside it
-        rc = launch_fused(h, m, k_steps, x.obs_f32, {x.obs_f32}, {(float *)x.actions_f32}, c.reward, c.done, c.mask);
+    const FusedRoute fr = (whole && k_steps >= 1 && reward && done && mask) ? fused_route(h, m) : FusedRoute{};
+    if (fr.eligible) {   // ONE launch: the policy between the steps, inside it
+        rc = launch_fused(h, m, fr, k_steps, x.obs_f32, {x.obs_f32}, {(float *)x.actions_f32}, c.reward, c.done, c.mask);
         if (rc) return rc;
         h->current_step += k_steps;
     } else
@@ -1508,13 +1434,10 @@ int ev2g_rollout(ev2g_handle *h, const ev2g_mlp *m, int k_steps, double *reward,
 
 long long ev2g_rollout_graph_launches(const ev2g_handle *h) { return h ? h->graph_launches : 0; }
 
-// The collectors' route (ev2g_collect's unfused loop, ev2g_ac_collect): true where a one-step launch can take float32 action and observation
-// rows of its own (StepIO::act32 / obs32) and gets the full instantiation for them -- the fast path with nothing registered, no charger
-// histories, a compiled-in reward; elsewhere the step works on the registered hand-over pair and the rows are copied around it.
+// the collectors' route (ev2g_route_host.h) of this handle, as things are registered now
 static bool collect_direct(const ev2g_handle *h) {
     const ev2g_step_extras &x = h->extras;
-    return h->wave_path && !x.cost && !x.obs_f32 && !x.actions_f32 && !(h->cfg.flags & EV2G_FLAG_LOG_CS_HISTORY) &&
-           std::min(h->scn.reward_kind, 3) != 3 && !h->no_full;
+    return collect_direct(h->shape, x.cost != nullptr, x.obs_f32 != nullptr, x.actions_f32 != nullptr);
 }
 
 int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_transitions *tr) {
@@ -1537,8 +1460,9 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
     const Rows<double> reward{tr->reward, h->E};
     const Rows<uint8_t> done{tr->done, h->E}, mask{tr->mask, (long long)EP};
     if (int rc = timed_open(h)) return rc;
-    if (direct && k_steps >= 1 && fused_eligible(h, m)) {   // ONE launch for the segment: rows read and written in place, the policy inside the launch
-        const int rc = launch_fused(h, m, k_steps, tr->obs, {obs.at(1), obs.stride}, act, reward, done, mask);
+    const FusedRoute fr = (direct && k_steps >= 1) ? fused_route(h, m) : FusedRoute{};
+    if (fr.eligible) {   // ONE launch for the segment: rows read and written in place, the policy inside the launch
+        const int rc = launch_fused(h, m, fr, k_steps, tr->obs, {obs.at(1), obs.stride}, act, reward, done, mask);
         if (rc) return rc;
         h->current_step += k_steps;
         k_steps = 0;
@@ -1551,7 +1475,7 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
             if ((rc = ev2g_mlp_forward(h, m, obs_i, act_i, h->E))) return rc;
             io.act32 = act_i; io.obs32 = obs_n;
             if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-            if (h->last_spec <= 0) return fail(h, EV2G_ERR_STATE, "ev2g_collect: internal: the direct path needs the full instantiation");
+            if (h->last.specialisation <= 0) return fail(h, EV2G_ERR_STATE, "ev2g_collect: internal: the direct path needs the full instantiation");
         } else {
             if (i == 0) HIPCHK(h, hipMemcpyAsync(x.obs_f32, obs_i, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
             if ((rc = ev2g_mlp_forward(h, m, x.obs_f32, (float *)x.actions_f32, h->E))) return rc;
@@ -1975,7 +1899,7 @@ static int chain_steps(ev2g_handle *h, const StepChain &c, int k) {
         if (g && (rc = grid_launch_step(h, g, c.vm.at(i), c.reward.at(i), c.base_weight, c.voltage_weight))) return rc;
         h->current_step += 1;
         // (collect_direct promises the full instantiation; were it ever wrong the step has run and is counted, the rows of this step are not to be trusted)
-        if (c.ac && c.ac_direct && h->last_spec <= 0) return fail(h, EV2G_ERR_STATE, std::string(c.who) + ": internal: the direct path needs the full instantiation");
+        if (c.ac && c.ac_direct && h->last.specialisation <= 0) return fail(h, EV2G_ERR_STATE, std::string(c.who) + ": internal: the direct path needs the full instantiation");
         if (l && l->p_delay > 0.0) {
             if ((rc = link_launch_obs(h, l, h->current_step, c.obs.at(i), c.actor ? l->obs32 : nullptr))) return rc;
         } else if (l && c.actor) {
@@ -2472,9 +2396,9 @@ int ev2g_check_faults(ev2g_handle *h, int32_t *first_bad_env) {
 static int launch_stats(ev2g_handle *h, double *stats, bool reset, double *obs, long long off, float *obs32 = nullptr) {
     (void)hipSetDevice(h->device);
     // the step launch that closed the episode computed the statistics (and nothing has changed the state since): copy them
-    const bool copy = h->inl_stats && h->current_step == h->T;
+    const bool copy = h->last.inl_stats && h->current_step == h->T;
     h->last_stats_route = copy ? 1 : 0;
-    h->stats_reason = copy ? "" : h->inl_reason;
+    h->stats_reason = copy ? "" : h->last.inl_reason;
     if (copy && !reset) {
         HIPCHK(h, hipMemcpyAsync(stats, h->d_stats_inl, sizeof(double) * (size_t)h->E * EV2G_N_STATS, hipMemcpyDeviceToDevice, h->stream));
         return EV2G_OK;
@@ -2517,7 +2441,7 @@ static int stats_reset_impl(ev2g_handle *h, double *stats, double *obs, float *o
     }
     h->scn_off = off;
     h->current_step = 0;
-    h->inl_stats = false; h->inl_reason = "the episode was reset"; h->state_epoch += 1;
+    state_changed(h, "the episode was reset");
     return EV2G_OK;
 }
 int ev2g_get_stats_reset(ev2g_handle *h, double *stats, double *obs, int64_t scenario_offset) { return stats_reset_impl(h, stats, obs, nullptr, scenario_offset); }
@@ -2798,7 +2722,7 @@ void ev2g_host_uniform(double *dst, int64_t n, uint64_t seed, double lo, double 
 // ---- scenario generator (host only) ----
 int ev2g_gen_default_config(int kind, ev2g_gen_config *cfg) { return ev2g_gen_default_config_impl(kind, cfg); }
 int ev2g_pool_refill(ev2g_handle *h, const ev2g_gen_config *cfg, uint64_t seed, int64_t first_index, int32_t first_slot, int32_t n) {
-    if (h) { h->inl_stats = false; h->inl_reason = "scenarios were refilled since the last step launch"; h->state_epoch += 1; }
+    if (h) state_changed(h, "scenarios were refilled since the last step launch");
     try { return ev2g_pool_refill_impl(h, cfg, seed, first_index, first_slot, n); }
     catch (const std::exception &e) { return fail(h, EV2G_ERR_ARG, std::string("ev2g_pool_refill: ") + e.what()); }
 }

@@ -1143,7 +1143,7 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
     PT_FLUSH
     // ---- in-launch episode statistics (INL: the float64 wide instantiation) ----
     // A launch of more than one step that ends the episode (t == T) computes get_statistics into V2P::stats_inl -- set by the loader only for a shape
-    // the statistics kernel runs one env per wavefront, like this phase (launch_steps in ev2g_host.hip applies the same rule) -- for
+    // the statistics kernel runs one env per wavefront, like this phase (route_step in ev2g_route_host.h applies the same rule) -- for
     // for its own envs right here, while other workgroups are still stepping: everything the statistics read of env e -- its SoC log, history
     // rows, charger counters, state lines, per-session results and episode accumulators -- was written by this workgroup, and the barrier
     // below orders those stores (and the departures' atomics) before the loads.  Wavefront w computes env e0 + w with ev2g_env_stats, the
