@@ -20,6 +20,7 @@
 #include "ev2g_device.h"
 #include "ev2g_load_host.h"
 #include "ev2g_route_host.h"
+#include "ev2g_policy_host.h"
 #include "ev2g_step_v2.h"
 #include "ev2g_step_wave.h"
 #include "ev2g_step_big.h"
@@ -120,6 +121,7 @@ static void wrap_free(ev2g_wrap *w) {
 // block [E, P] the step of ev2g_ac_collect reads (allocated on first use)
 struct ev2g_acpolicy {
     AcDev dev{};
+    AcPlan plan{};   // the padded sizes the weight images are packed for (ev2g_policy_host.h)
     std::vector<void *> allocs;
     size_t lds = 0;
     int relu = 0;
@@ -1127,175 +1129,86 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
 struct ev2g_mlp {
     MlpDev dev{};
     std::vector<void *> allocs;
-    size_t lds = 0;
-    const void *fn = nullptr;   // the kernel for this shape
-    int rows = EV2G_MLP_ROWS;   // env rows per workgroup of that kernel
-    int threads = EV2G_MLP_BLOCK;
-    // batches of more rows than 16 x CUs: the same streaming kernel with 32 rows per workgroup -- a weight fragment then feeds two MFMAs, and the
-    // weights are streamed once per CU instead of once per 16-row workgroup (two or more of which would share a CU)
-    const void *fn_big = nullptr;
-    size_t lds_big = 0;
-    int rows_big = 0, threads_big = 0, big_from = 0;
-    int s16_ks1 = 0, s16_nt1 = 0, s16_nt2 = 0, s16_nt3 = 0, s16_nw = 0;   // the streaming kernel's fragment packing (0: another kernel's)
+    MlpPlan plan;               // the kernel for this shape and what a launch of it takes (ev2g_policy_host.h)
+    const void *fn = nullptr, *fn_big = nullptr;   // kMlpTable[plan.index], kMlpTable[plan.big_index] (null: no 32-row variant)
+    int big_from = 0;           // the 32-row variant runs batches of at least this many rows: more than 16 x CUs
+    std::string kernel_name;    // ev2g_mlp_kernel_name
 };
 
-// the fixed-shape kernels exist for the layer widths of the shipped configs (obs 162 / 63 -> 400 -> 300 -> ports); anything else
-// runs the generic one
-static const void *mlp_kernel_for(const MlpDev &d) {
-    const int k1 = d.k1 / 16, k2 = d.n1 / 16, k3 = d.n2 / 16;
-    // (the fixed kernels unroll over at most 4 / 3 / 1 column tiles per wavefront: 400 -> 13 tiles, 300 -> 10, ports <= 128)
-    if (d.n1 / 32 > 16 || d.n2 / 32 > 12 || d.n3 / 32 > 4) return (const void *)ev2g_mlp3_any;
-    if (k1 == 11 && k2 == 26 && k3 == 20) return (const void *)ev2g_mlp3_fixed<11, 26, 20>;
-    if (k1 == 4 && k2 == 26 && k3 == 20) return (const void *)ev2g_mlp3_fixed<4, 26, 20>;
-    return (const void *)ev2g_mlp3_any;
-}
-
-// the 16-row streaming kernel (ev2g_mlp3_s16) exists for the shipped shapes
-struct MlpS16Pick { const void *fn; size_t lds; int ks1, nt1, nt2, nt3, nw, threads; };
-// nw: bf16 terms per weight -- 1: the bf16 network; 2 / 3: the float32 network as split bf16 operands (EV2G_MLP_F32 / EV2G_MLP_F32X3, ev2g_mlp.h)
-static MlpS16Pick mlp_s16_for(int d_in, int h1, int h2, int d_out, int nw) {
-    // The instantiations are for the shipped shapes (162 / 63 observations -> 400 -> 300 -> 50 / 20 ports); a network that FITS one of them runs on
-    // it zero-padded (weights and biases of the missing rows / columns are zeros, ReLU(0) = 0): any input up to 192 (64), hidden layers up to
-    // 400 / 304, outputs up to 64 (32).  Small networks (both hidden layers under 128) keep the generic kernel: they would pay the full-size stream.
-    int ks1 = (d_in + 31) / 32, nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16, nt3 = (d_out + 15) / 16;
-    if (nt1 <= 25 && nt2 <= 19 && (h1 >= 128 || h2 >= 128)) {
-        if (ks1 <= 2 && nt3 <= 2) { ks1 = 2; nt1 = 25; nt2 = 19; nt3 = 2; }
-        else if (ks1 <= 6 && nt3 <= 4) { ks1 = 6; nt1 = 25; nt2 = 19; nt3 = 4; }
+extern "C++" {   // (templates: C++ linkage inside the C-ABI block)
+// the actor kernels (MlpPlan::index / big_index): the table's order is mlp_table_key's
+template <int I>
+static const void *mlp_entry() {
+    constexpr MlpKey K = mlp_table_key(I);
+    if constexpr (K.kind == MLP_KIND_ANY) return (const void *)ev2g_mlp3_any;
+    else if constexpr (K.kind == MLP_KIND_F32) return (const void *)ev2g_mlp3_f32;
+    else if constexpr (K.kind == MLP_KIND_FIXED) {
+        static_assert(mlp_fixed_index(K.a, K.b, K.c) == I, "the table's order is mlp_fixed_index's");
+        return (const void *)ev2g_mlp3_fixed<K.a, K.b, K.c>;
+    } else {
+        static_assert(mlp_s16_index(K.a == 6 ? 0 : 1, K.nw, K.rb) == I, "the table's order is mlp_s16_index's");
+        return (const void *)ev2g_mlp3_s16<K.a, K.b, K.c, K.d, K.nw, K.wv, K.rb>;
     }
-    // the bf16 network runs eight wavefronts per workgroup (two per SIMD: one's epilogue and LDS waits under the other's MFMAs -- 7.48 -> 7.39 us at
-    // 162 inputs, 6.35 -> 5.88 at 63); the float32 modes need the registers of four.
-    const int wv = nw == 1 ? 8 : 4;
-#define EV2G_S16_CASE(K, A, B, Cc, N, W) \
-    if (ks1 == K && nt1 == A && nt2 == B && nt3 == Cc && nw == N && wv == W) return {(const void *)ev2g_mlp3_s16<K, A, B, Cc, N, W>, MlpS16<K, A, B, Cc, N, W>::lds_bytes, ks1, nt1, nt2, nt3, nw, W * 64};
-    EV2G_S16_CASE(6, 25, 19, 4, 2, 4) EV2G_S16_CASE(2, 25, 19, 2, 2, 4)
-    EV2G_S16_CASE(6, 25, 19, 4, 3, 4) EV2G_S16_CASE(2, 25, 19, 2, 3, 4)
-    EV2G_S16_CASE(6, 25, 19, 4, 1, 8) EV2G_S16_CASE(2, 25, 19, 2, 1, 8)
-#undef EV2G_S16_CASE
-    return {nullptr, 0, 0, 0, 0, 0, 0, 0};
+}
+template <size_t... I>
+static std::array<const void *, sizeof...(I)> mlp_table(std::index_sequence<I...>) { return {mlp_entry<(int)I>()...}; }
+static const std::array<const void *, MLP_TABLE_ENTRIES> kMlpTable = mlp_table(std::make_index_sequence<MLP_TABLE_ENTRIES>{});
 }
 
-static uint16_t host_bf16(float f) {   // round to nearest even (same as the kernel's)
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// torch.nn.Linear weight W[n_out, n_in] -> MFMA B-fragment order [n_tile][k_step][lane][8] (bf16, zero padded):
-// lane l of tile (nt, ks) holds B[k][j] = W[j][k] for j = nt*32 + (l & 31), k = ks*16 + (l >> 5)*8 + 0..7
-static std::vector<uint16_t> pack_linear(const float *W, int n_out, int n_in, int N, int K) {
-    const int NT = N / 32, KS = K / 16;
-    std::vector<uint16_t> p((size_t)NT * KS * 64 * 8, 0);
-    for (int nt = 0; nt < NT; nt++)
-        for (int ks = 0; ks < KS; ks++)
-            for (int l = 0; l < 64; l++) {
-                const int j = nt * 32 + (l & 31);
-                for (int i = 0; i < 8; i++) {
-                    const int k = ks * 16 + (l >> 5) * 8 + i;
-                    if (j < n_out && k < n_in) p[(((size_t)nt * KS + ks) * 64 + l) * 8 + i] = host_bf16(W[(size_t)j * n_in + k]);
-                }
-            }
-    return p;
-}
-
-// ... and for ev2g_mlp3_s16 (weights are the MFMA's A operand there): [tile of 16 outputs][k-step of 32][term][lane][8],
-// lane l holds W[tile*16 + (l & 15)][ks*32 + 8*(l >> 4) + 0..7]; term t of NW is the bf16 rounding of what terms 0..t-1 left of the float32 weight
-static std::vector<uint16_t> pack_linear_s16(const float *W, int n_out, int n_in, int NT, int KS, int NW) {
-    std::vector<uint16_t> p((size_t)NT * KS * NW * 64 * 8, 0);
-    for (int t = 0; t < NT; t++)
-        for (int ks = 0; ks < KS; ks++)
-            for (int l = 0; l < 64; l++) {
-                const int j = t * 16 + (l & 15);
-                for (int i = 0; i < 8; i++) {
-                    const int k = ks * 32 + (l >> 4) * 8 + i;
-                    if (j >= n_out || k >= n_in) continue;
-                    float r = W[(size_t)j * n_in + k];
-                    for (int q = 0; q < NW; q++) {
-                        const uint16_t hb = host_bf16(r);
-                        p[((((size_t)t * KS + ks) * NW + q) * 64 + l) * 8 + i] = hb;
-                        uint32_t u = (uint32_t)hb << 16; float hf; std::memcpy(&hf, &u, 4);
-                        r -= hf;   // (exact)
-                    }
-                }
-            }
-    return p;
-}
-
-// float32 weights in the operand order of ev2g_mlp32_layer: [n_tile][k_group of 8][lane][4], lane l <-> (n = tile*32 + (l & 31), k = 8 g + 4 (l >> 5) + 0..3)
-static std::vector<float> pack_linear_f32(const float *W, int n_out, int n_in, int N, int K) {
-    std::vector<float> v((size_t)N * K, 0.f);
-    const int KG = K / 8;
-    for (int nt = 0; nt < N / 32; nt++)
-        for (int g = 0; g < KG; g++)
-            for (int l = 0; l < 64; l++)
-                for (int j = 0; j < 4; j++) {
-                    const int n = nt * 32 + (l & 31), k = g * 8 + 4 * (l >> 5) + j;
-                    v[(((size_t)nt * KG + g) * 64 + l) * 4 + j] = (n < n_out && k < n_in) ? W[(size_t)n * n_in + k] : 0.f;
-                }
-    return v;
+// the device stage of a policy: uploads the plan's images, sets the kernels' dynamic-LDS attributes and drains the stream (the images are temporaries)
+static int mlp_upload(ev2g_handle *h, ev2g_mlp *m, const MlpImages &img) {
+    MlpDev &d = m->dev;
+    const MlpPlan &p = m->plan;
+#ifdef EV2G_MLP_TIMING
+    if (int rc = dalloc(h, m->allocs, 16, &d.dbg)) return rc;
+#endif
+    const uint16_t **w[3] = {&d.w1, &d.w2, &d.w3};
+    const float **b[3] = {&d.b1, &d.b2, &d.b3};
+    for (int i = 0; i < 3; i++) {
+        char *q = nullptr;
+        if (int rc = upload(h, m->allocs, (const char *)img.weight(i), img.weight_bytes(i), &q)) return rc;
+        *w[i] = (const uint16_t *)q;
+    }
+    for (int i = 0; i < 3; i++) {   // (the streaming kernel's biases are one array: layers 2 and 3 point into it)
+        float *q = nullptr;
+        if (img.bias[i].empty()) { *b[i] = d.b1 + img.bias_off[i]; continue; }
+        if (int rc = upload(h, m->allocs, img.bias[i].data(), img.bias[i].size(), &q)) return rc;
+        *b[i] = q;
+    }
+    if (p.lds > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(m->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    if (m->fn_big && p.big_lds > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(m->fn_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.big_lds));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
 }
 
 int ev2g_mlp_create_ex(ev2g_handle *h, int d_in, int h1, int h2, int d_out, const float *W1, const float *b1, const float *W2,
                     const float *b2, const float *W3, const float *b3, float out_lo, int precision, ev2g_mlp **out) {
-    if (!h || !out || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || d_in <= 0 || h1 <= 0 || h2 <= 0 || d_out <= 0)
-        return fail(h, EV2G_ERR_ARG, "ev2g_mlp_create: bad arguments");
-    if (out_lo != -1.0f && out_lo != 0.0f) return fail(h, EV2G_ERR_ARG, "ev2g_mlp_create: out_lo must be -1 or 0");
+    if (!h || !out || !W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(h, EV2G_ERR_ARG, "ev2g_mlp_create: bad arguments");
+    const MlpPlan p = plan_mlp(d_in, h1, h2, d_out, out_lo, precision);
+    if (p.err) return fail(h, p.err, p.refusal);
     (void)hipSetDevice(h->device);
-    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
     ev2g_mlp *m = new ev2g_mlp();
+    m->plan = p;
     MlpDev &d = m->dev;
     d.d_in = d_in; d.h1 = h1; d.h2 = h2; d.d_out = d_out;
-    d.k1 = up(d_in, 16); d.n1 = up(h1, 32); d.n2 = up(h2, 32); d.n3 = up(d_out, 32);
+    d.k1 = p.k1; d.n1 = p.n1; d.n2 = p.n2; d.n3 = p.n3;
     d.out_lo = out_lo;
     d.dbg = nullptr;
-#ifdef EV2G_MLP_TIMING
-    { unsigned long long *p; if (dalloc(h, m->allocs, 16, &p)) { delete m; return EV2G_ERR_HIP; } d.dbg = p; }
-#endif
-    if (precision != EV2G_MLP_BF16 && precision != EV2G_MLP_F32 && precision != EV2G_MLP_F32X3) { delete m; return fail(h, EV2G_ERR_ARG, "ev2g_mlp_create_ex: precision must be EV2G_MLP_BF16, EV2G_MLP_F32 or EV2G_MLP_F32X3"); }
-    const bool f32 = precision != EV2G_MLP_BF16;
-    const MlpS16Pick s16 = mlp_s16_for(d_in, h1, h2, d_out, precision == EV2G_MLP_BF16 ? 1 : (precision == EV2G_MLP_F32 ? 2 : 3));
-    m->lds = s16.fn ? s16.lds : (f32 ? ev2g_mlp32_lds_bytes(d) : ev2g_mlp_lds_bytes(d));
-    if (s16.fn) { m->rows = EV2G_MLPS_ROWS; m->threads = s16.threads; m->s16_ks1 = s16.ks1; m->s16_nt1 = s16.nt1; m->s16_nt2 = s16.nt2; m->s16_nt3 = s16.nt3; m->s16_nw = s16.nw; }
-    if (s16.fn && s16.nw == 1) {
-        if (s16.ks1 == 6 && s16.nt3 == 4) { m->fn_big = (const void *)ev2g_mlp3_s16<6, 25, 19, 4, 1, 4, 2>; m->lds_big = MlpS16<6, 25, 19, 4, 1, 4, 2>::lds_bytes; }
-        else if (s16.ks1 == 2 && s16.nt3 == 2) { m->fn_big = (const void *)ev2g_mlp3_s16<2, 25, 19, 2, 1, 4, 2>; m->lds_big = MlpS16<2, 25, 19, 2, 1, 4, 2>::lds_bytes; }
-        if (m->fn_big) {
-            int cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-            m->rows_big = 2 * EV2G_MLPS_ROWS; m->threads_big = 256; m->big_from = EV2G_MLPS_ROWS * cus + 1;
-            if (m->lds_big > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(m->fn_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_big));
-        }
+    m->fn = kMlpTable[(size_t)p.index];
+    m->kernel_name = mlp_kernel_name(p.index);
+    if (p.big_index >= 0) {
+        int cus = 256;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+        m->fn_big = kMlpTable[(size_t)p.big_index];
+        m->big_from = EV2G_MLPS_ROWS * cus + 1;
+        m->kernel_name += "; from " + std::to_string(m->big_from) + " rows " + mlp_kernel_name(p.big_index);
     }
-    if (m->lds > 160 * 1024) { delete m; return fail(h, EV2G_ERR_ARG, "ev2g_mlp_create: layers too wide for the LDS-resident activations"); }
-    int rc = 0;
-    auto upw = [&](const std::vector<uint16_t> &v, const uint16_t **dst) { uint16_t *p; rc = upload(h, m->allocs, v.data(), v.size(), &p); *dst = p; return rc; };
-    auto upb = [&](const float *b, int n, int N, const float **dst) { std::vector<float> v((size_t)N, 0.f); std::copy(b, b + n, v.begin()); float *p; rc = upload(h, m->allocs, v.data(), v.size(), &p); *dst = p; return rc; };
-    auto upw32 = [&](const std::vector<float> &v, const uint16_t **dst) { float *p; rc = upload(h, m->allocs, v.data(), v.size(), &p); *dst = (const uint16_t *)p; return rc; };
-    if (f32 && !s16.fn) {
-        if (upw32(pack_linear_f32(W1, h1, d_in, d.n1, d.k1), &d.w1) || upw32(pack_linear_f32(W2, h2, h1, d.n2, d.n1), &d.w2) ||
-            upw32(pack_linear_f32(W3, d_out, h2, d.n3, d.n2), &d.w3) || upb(b1, h1, d.n1, &d.b1) || upb(b2, h2, d.n2, &d.b2) || upb(b3, d_out, d.n3, &d.b3)) {
-            free_pool(m->allocs); delete m; return rc;
-        }
-    } else if (s16.fn) {
-        if (upw(pack_linear_s16(W1, h1, d_in, s16.nt1, s16.ks1, s16.nw), &d.w1) || upw(pack_linear_s16(W2, h2, h1, s16.nt2, (s16.nt1 * 16 + 31) / 32, s16.nw), &d.w2) ||
-            upw(pack_linear_s16(W3, d_out, h2, s16.nt3, (s16.nt2 * 16 + 31) / 32, s16.nw), &d.w3)) {
-            free_pool(m->allocs); delete m; return rc;
-        }
-        {   // the three bias vectors as ONE array (b1 | b2 | b3, each padded with zeros to its 16-column tiles): one coalesced load in the kernel
-            std::vector<float> ball((size_t)(s16.nt1 + s16.nt2 + s16.nt3) * 16, 0.f);
-            std::copy(b1, b1 + h1, ball.begin()); std::copy(b2, b2 + h2, ball.begin() + s16.nt1 * 16); std::copy(b3, b3 + d_out, ball.begin() + (s16.nt1 + s16.nt2) * 16);
-            float *p;
-            if ((rc = upload(h, m->allocs, ball.data(), ball.size(), &p))) { free_pool(m->allocs); delete m; return rc; }
-            d.b1 = p; d.b2 = p + s16.nt1 * 16; d.b3 = p + (s16.nt1 + s16.nt2) * 16;
-        }
-    } else
-    if (upw(pack_linear(W1, h1, d_in, d.n1, d.k1), &d.w1) || upw(pack_linear(W2, h2, h1, d.n2, d.n1), &d.w2) ||
-        upw(pack_linear(W3, d_out, h2, d.n3, d.n2), &d.w3) || upb(b1, h1, d.n1, &d.b1) || upb(b2, h2, d.n2, &d.b2) || upb(b3, d_out, d.n3, &d.b3)) {
-        free_pool(m->allocs); delete m; return rc;
+    if (const int rc = mlp_upload(h, m, pack_mlp(p, W1, b1, W2, b2, W3, b3))) {   // the one cleanup path
+        (void)hipStreamSynchronize(h->stream);   // (copies of the images enqueued before the failure)
+        free_pool(m->allocs);
+        delete m;
+        return rc;
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));   // the staging vectors are temporaries
-    m->fn = s16.fn ? s16.fn : (f32 ? (const void *)ev2g_mlp3_f32 : mlp_kernel_for(d));
-    if (m->lds > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(m->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds));
     *out = m;
     return EV2G_OK;
 }
@@ -1317,12 +1230,15 @@ int ev2g_mlp_forward(ev2g_handle *h, const ev2g_mlp *m, const float *x, float *y
     (void)hipSetDevice(h->device);
     MlpDev dev = m->dev;
     void *args[] = {&dev, &x, &y, &n_rows};
+    const MlpPlan &p = m->plan;
     if (m->fn_big && n_rows >= m->big_from)
-        HIPCHK(h, hipLaunchKernel(m->fn_big, dim3((n_rows + m->rows_big - 1) / m->rows_big), dim3(m->threads_big), args, m->lds_big, h->stream));
+        HIPCHK(h, hipLaunchKernel(m->fn_big, dim3((n_rows + p.big_rows - 1) / p.big_rows), dim3(p.big_threads), args, p.big_lds, h->stream));
     else
-        HIPCHK(h, hipLaunchKernel(m->fn, dim3((n_rows + m->rows - 1) / m->rows), dim3(m->threads), args, m->lds, h->stream));
+        HIPCHK(h, hipLaunchKernel(m->fn, dim3((n_rows + p.rows - 1) / p.rows), dim3(p.threads), args, p.lds, h->stream));
     return EV2G_OK;
 }
+
+const char *ev2g_mlp_kernel_name(const ev2g_mlp *m) { return m ? m->kernel_name.c_str() : ""; }
 
 #ifdef EV2G_MLP_TIMING
 int ev2g_mlp_debug_stamps(ev2g_handle *h, const ev2g_mlp *m, unsigned long long *out8) {
@@ -1336,7 +1252,7 @@ int ev2g_mlp_debug_stamps(ev2g_handle *h, const ev2g_mlp *m, unsigned long long 
 // route_fused (ev2g_route_host.h) says whether the loaded shape and this policy get it, and which instantiation; EV2G_NO_FUSED=1 and (the
 // float32 policy) EV2G_NO_FUSED_F32=1, read at every call, keep the two launches per step.
 static FusedRoute fused_route(const ev2g_handle *h, const ev2g_mlp *m) {
-    return route_fused(h->shape, h->extras.cost != nullptr, FusedPacking{m->s16_ks1, m->s16_nt1, m->s16_nt2, m->s16_nt3, m->s16_nw},
+    return route_fused(h->shape, h->extras.cost != nullptr, m->plan.s16,
                        std::getenv("EV2G_NO_FUSED") != nullptr, std::getenv("EV2G_NO_FUSED_F32") != nullptr);
 }
 // k steps from the current one; obs0: the [E, D] float32 rows the first forward reads; obs / act / reward / done / mask: the rows of the segment's first
@@ -2162,7 +2078,10 @@ int ev2g_wrap_rollout(ev2g_handle *h, ev2g_wrap *w, const ev2g_mlp *m, int k_ste
 }
 
 // ---- the Gaussian actor-critic and GAE (ev2g_ac.h) ----
-struct AcWeights { const float *pW1, *pb1, *pW2, *pb2, *vW1, *vb1, *vW2, *vb2, *aW, *ab, *cW, *cb; };
+// the twelve device arrays in the order of ac_array_sizes / pack_ac (ev2g_policy_host.h)
+static std::array<const float **, AC_ARRAYS> ac_arrays(AcDev &d) {
+    return {&d.w1, &d.b1, &d.w2, &d.b2, &d.w3, &d.b3, &d.u1, &d.c1, &d.u2, &d.c2, &d.u3, &d.c3};
+}
 
 static int ac_check(ev2g_handle *h, ev2g_acpolicy *ac, const char *who) {
     if (!h || !ac) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
@@ -2174,20 +2093,10 @@ static int ac_check(ev2g_handle *h, ev2g_acpolicy *ac, const char *who) {
 
 // packs the twelve host arrays into the object's device arrays (allocated at create) and drains the stream: the staging vectors are temporaries
 static int ac_upload_weights(ev2g_handle *h, ev2g_acpolicy *ac, const AcWeights &w) {
-    const AcDev &d = ac->dev;
-    std::vector<std::vector<float>> stage;
-    auto put = [&](const float *dst, std::vector<float> v) -> hipError_t {
-        stage.push_back(std::move(v));
-        return hipMemcpyAsync((void *)dst, stage.back().data(), stage.back().size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
-    };
-    auto padded = [](const float *b, int n, int N) { std::vector<float> v((size_t)N, 0.f); std::copy(b, b + n, v.begin()); return v; };
-    stage.reserve(12);
-    HIPCHK(h, put(d.w1, pack_linear_f32(w.pW1, d.h1, d.d_in, d.n1, d.k1))); HIPCHK(h, put(d.b1, padded(w.pb1, d.h1, d.n1)));
-    HIPCHK(h, put(d.w2, pack_linear_f32(w.pW2, d.h2, d.h1, d.n2, d.n1))); HIPCHK(h, put(d.b2, padded(w.pb2, d.h2, d.n2)));
-    HIPCHK(h, put(d.w3, pack_linear_f32(w.aW, d.d_out, d.h2, d.n3, d.n2))); HIPCHK(h, put(d.b3, padded(w.ab, d.d_out, d.n3)));
-    HIPCHK(h, put(d.u1, pack_linear_f32(w.vW1, d.v1, d.d_in, d.m1, d.k1))); HIPCHK(h, put(d.c1, padded(w.vb1, d.v1, d.m1)));
-    HIPCHK(h, put(d.u2, pack_linear_f32(w.vW2, d.v2, d.v1, d.m2, d.m1))); HIPCHK(h, put(d.c2, padded(w.vb2, d.v2, d.m2)));
-    HIPCHK(h, put(d.u3, padded(w.cW, d.v2, d.m2))); HIPCHK(h, put(d.c3, padded(w.cb, 1, 1)));
+    const auto stage = pack_ac(ac->plan, w);
+    const auto dst = ac_arrays(ac->dev);
+    for (int i = 0; i < AC_ARRAYS; i++)
+        HIPCHK(h, hipMemcpyAsync((void *)*dst[i], stage[i].data(), stage[i].size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return EV2G_OK;
 }
@@ -2235,11 +2144,12 @@ int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int
     for (int p = 0; p < d_out; p++)
         if (!std::isfinite(log_std[p])) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: log_std[" + std::to_string(p) + "] is not finite");
     (void)hipSetDevice(h->device);
-    auto up = [](int x, int m) { return (x + m - 1) / m * m; };
     ev2g_acpolicy *ac = new ev2g_acpolicy();
+    ac->plan = plan_ac(d_in, h1, h2, v1, v2, d_out);
+    const AcPlan &p = ac->plan;
     AcDev &d = ac->dev;
     d.d_in = d_in; d.h1 = h1; d.h2 = h2; d.v1 = v1; d.v2 = v2; d.d_out = d_out;
-    d.k1 = up(d_in, 8); d.n1 = up(h1, 32); d.n2 = up(h2, 32); d.m1 = up(v1, 32); d.m2 = up(v2, 32); d.n3 = up(d_out, 32);
+    d.k1 = p.k1; d.n1 = p.n1; d.n2 = p.n2; d.m1 = p.m1; d.m2 = p.m2; d.n3 = p.n3;
     d.lo = lo;
     ac->relu = activation == EV2G_AC_RELU;
     ac->seed = seed; ac->n = 0;
@@ -2249,9 +2159,10 @@ int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int
     double *g = nullptr;
     auto fa = [&](size_t n, const float **dst) { rc = dalloc(h, ac->allocs, n, &f); *dst = f; return rc; };
     auto da = [&](size_t n, const double **dst) { rc = dalloc(h, ac->allocs, n, &g); *dst = g; return rc; };
-    if (fa((size_t)d.n1 * d.k1, &d.w1) || fa(d.n1, &d.b1) || fa((size_t)d.n2 * d.n1, &d.w2) || fa(d.n2, &d.b2) || fa((size_t)d.n3 * d.n2, &d.w3) ||
-        fa(d.n3, &d.b3) || fa((size_t)d.m1 * d.k1, &d.u1) || fa(d.m1, &d.c1) || fa((size_t)d.m2 * d.m1, &d.u2) || fa(d.m2, &d.c2) || fa(d.m2, &d.u3) ||
-        fa(1, &d.c3) || fa(d_out, &d.sigma) || da(d_out, &d.lp_a) || da(d_out, &d.lp_c) || (rc = ac_upload_weights(h, ac, w)) ||
+    const auto sizes = ac_array_sizes(p);
+    const auto arrays = ac_arrays(d);
+    for (int i = 0; i < AC_ARRAYS && !rc; i++) fa(sizes[(size_t)i], arrays[(size_t)i]);
+    if (rc || fa(d_out, &d.sigma) || da(d_out, &d.lp_a) || da(d_out, &d.lp_c) || (rc = ac_upload_weights(h, ac, w)) ||
         (rc = ac_upload_log_std(h, ac, log_std, "ev2g_ac_create"))) {
         ac_free(ac);
         return rc;

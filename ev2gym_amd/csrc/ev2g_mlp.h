@@ -21,8 +21,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#define EV2G_MLP_ROWS 32
-#define EV2G_MLP_BLOCK 256
+#include "ev2g_policy_host.h"   // EV2G_MLP_ROWS / _BLOCK, EV2G_MLPS_ROWS / _RING and the LDS geometry: one definition for the kernels and the host's plan
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -40,11 +39,6 @@ struct MlpDev {
 #else
 #define MLP_STAMP(i)
 #endif
-__host__ __device__ inline int ev2g_mlp_lds_stride(int k) { return k + 8; }   // bf16 elements per LDS row: +16 bytes against bank conflicts
-__host__ __device__ inline size_t ev2g_mlp_lds_bytes(const MlpDev &m) {
-    const int a = ev2g_mlp_lds_stride(m.k1 > m.n2 ? m.k1 : m.n2), b = ev2g_mlp_lds_stride(m.n1);
-    return (size_t)EV2G_MLP_ROWS * (a + b) * sizeof(uint16_t) + (size_t)(m.n1 + m.n2 + m.n3) * sizeof(float);   // + the staged biases
-}
 
 __device__ __forceinline__ uint16_t ev2g_f32_to_bf16(float f) {   // round to nearest even
     uint32_t u = __float_as_uint(f);
@@ -338,8 +332,6 @@ __global__ void __launch_bounds__(EV2G_MLP_BLOCK) ev2g_mlp3_fixed(MlpDev m, cons
 //     rows have arrived), and fragment s + RING is requested the moment fragment s has been consumed, across layer boundaries and barriers:
 //     the stream never waits for the compute, only the other way round.
 // Weights are packed per layer as [tile][k-step][lane] 16-byte fragments: lane l holds W[tile*16 + (l & 15)][ks*32 + 8*(l >> 4) + 0..7].
-#define EV2G_MLPS_ROWS 16
-#define EV2G_MLPS_RING 52
 typedef float f32x4m __attribute__((ext_vector_type(4)));
 
 // NW > 1: the FLOAT32 network on the bf16 matrix cores (precision = EV2G_MLP_F32).  A float32 weight is stored as NW bf16 terms
@@ -349,16 +341,10 @@ typedef float f32x4m __attribute__((ext_vector_type(4)));
 // below for NW = 3: the same level as float32 operands) and the accumulation order.  The float32 MFMA (v_mfma_f32_32x32x2_f32, ev2g_mlp3_f32)
 // runs at 1/16 of the bf16 rate; here the cost is the weight stream, NW times the bf16 kernel's.
 template <int KS1, int NT1, int NT2, int NT3, int NW = 1, int WV = 4, int RB = 1> struct MlpS16 {   // WV: wavefronts per workgroup (4: one per SIMD; 8: two); RB: blocks of 16 env rows per workgroup
-    static constexpr int ROWS = EV2G_MLPS_ROWS * RB;
-    static constexpr int NX = NW == 1 ? 1 : 3;   // terms of an activation
-    static constexpr int KS2 = (NT1 * 16 + 31) / 32, KS3 = (NT2 * 16 + 31) / 32;
-    static constexpr int NTH = WV * 64;
-    static constexpr int MT1 = (NT1 + WV - 1) / WV, MT2 = (NT2 + WV - 1) / WV, MT3 = (NT3 + WV - 1) / WV;   // tile slots per wavefront
-    static constexpr int S1 = MT1 * KS1 * NW, S2 = MT2 * KS2 * NW, S3 = MT3 * KS3 * NW, STOT = S1 + S2 + S3;   // fragments of the sequence, per layer
-    static constexpr int SX = KS1 * 32 + 8, SH1 = KS2 * 32 + 8, SH2 = KS3 * 32 + 8;             // LDS row strides (bf16 elements; +16 bytes against bank conflicts)
-    static constexpr int NB = (NT1 + NT2 + NT3) * 16;                                          // staged biases (floats)
-    static constexpr int RING = (NW == 1 ? EV2G_MLPS_RING : 36) * 4 / WV;                                 // (three operand copies per k-step take the registers)
-    static constexpr size_t lds_bytes = (size_t)ROWS * (SX + SH1 + SH2) * 2 * NX + (size_t)NB * 4;
+    static constexpr MlpS16Geom G = mlp_s16_geom(KS1, NT1, NT2, NT3, NW, WV, RB);   // (ev2g_policy_host.h: what each of these is)
+    static constexpr int ROWS = G.ROWS, NX = G.NX, KS2 = G.KS2, KS3 = G.KS3, NTH = G.NTH, MT1 = G.MT1, MT2 = G.MT2, MT3 = G.MT3;
+    static constexpr int S1 = G.S1, S2 = G.S2, S3 = G.S3, STOT = G.STOT, SX = G.SX, SH1 = G.SH1, SH2 = G.SH2, NB = G.NB, RING = G.RING;
+    static constexpr size_t lds_bytes = G.lds_bytes;
 };
 
 // float32 -> NX bf16 terms, two values at a time (packed words); term k is the bf16 rounding of what terms 0..k-1 left
@@ -1006,11 +992,6 @@ __global__ void __launch_bounds__(EV2G_MLP_BLOCK) ev2g_mlp3_any(MlpDev m, const 
 // k's.  Here MFMA j of a group of eight k's uses k = 8 g + 4 (l >> 5) + j, so a lane's four A values and four weights are contiguous:
 // one 16-byte LDS read and one 16-byte (pre-packed, coalesced) global load feed four MFMAs.  Activations stay in LDS as float32.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-__host__ __device__ inline int ev2g_mlp32_lds_stride(int k) { return k + 4; }   // floats per LDS row (+16 bytes against bank conflicts)
-__host__ __device__ inline size_t ev2g_mlp32_lds_bytes(const MlpDev &m) {
-    const int a = ev2g_mlp32_lds_stride(m.k1 > m.n2 ? m.k1 : m.n2), b = ev2g_mlp32_lds_stride(m.n1);
-    return (size_t)EV2G_MLP_ROWS * (a + b) * sizeof(float);
-}
 #define EV2G_MLP32_DEPTH 8
 template <bool FINAL>
 __device__ __forceinline__ void ev2g_mlp32_layer(const float *__restrict__ A, int sa, int K, int N, const float *__restrict__ W,

@@ -128,6 +128,7 @@ def load_library(path: Optional[str] = None):
         "ev2g_mlp_create_ex": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, C.POINTER(vp)]),
         "ev2g_mlp_destroy": (None, [vp, vp]),
         "ev2g_mlp_forward": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "ev2g_mlp_kernel_name": (C.c_char_p, [vp]),
         "ev2g_rollout": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, i64, vp, i64, C.c_int]),
         "ev2g_rollout_graph_launches": (C.c_longlong, [vp]),
         "ev2g_comm_get_unique_id": (C.c_int, [vp]),
@@ -162,7 +163,7 @@ EXPORTED_SYMBOLS = [
     "ev2g_scenario_offset", "ev2g_set_step_extras", "ev2g_kernel_name", "ev2g_last_launch_specialisation", "ev2g_last_launch_general_reason", "ev2g_last_stats_route", "ev2g_last_stats_reason", "ev2g_last_launch_fast_forwarded", "ev2g_fallback_reason", "ev2g_big_kernel_reason", "ev2g_step", "ev2g_step_n",
     "ev2g_check_faults", "ev2g_get_stats", "ev2g_get_stats_reset", "ev2g_get_stats_reset_f32", "ev2g_reset_f32", "ev2g_collect", "ev2g_stat_name", "ev2g_peek", "ev2g_malloc", "ev2g_free",
     "ev2g_memcpy_h2d", "ev2g_memcpy_d2h", "ev2g_host_malloc", "ev2g_host_free", "ev2g_synchronize", "ev2g_fill_uniform", "ev2g_host_uniform",
-    "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_rollout",
+    "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_mlp_kernel_name", "ev2g_rollout",
     "ev2g_rollout_graph_launches", "ev2g_comm_get_unique_id", "ev2g_comm_init", "ev2g_comm_destroy", "ev2g_comm_world_size", "ev2g_comm_gathers", "ev2g_gather_stats",
     "ev2g_pool_refill", "ev2g_pool_refill_overflows", "ev2g_pool_session_capacity", "ev2g_gen_default_config", "ev2g_generate", "ev2g_gen_batch", "ev2g_gen_free", "ev2g_gen_table",
     "ev2g_heuristic_create", "ev2g_heuristic_destroy", "ev2g_heuristic_actions", "ev2g_heuristic_run",
@@ -399,6 +400,11 @@ class Engine:
 
     def mlp_forward(self, m, x, y, n_rows):
         self._check(self._lib.ev2g_mlp_forward(self._h, m, _ptr(x), _ptr(y), int(n_rows)))
+
+    def mlp_kernel_name(self, m) -> str:
+        """The actor kernel instantiation the policy got, e.g. "ev2g_mlp3_s16<6,25,19,4,1,8>; from 4097 rows ev2g_mlp3_s16<6,25,19,4,1,4,2>"
+        (include/ev2g.h: ev2g_mlp_kernel_name)."""
+        return (self._lib.ev2g_mlp_kernel_name(m) or b"").decode()
 
     def rollout(self, m, k, reward=None, r_stride=0, done=None, d_stride=0, mask=None, m_stride=0, auto_reset=0):
         """k x (actor forward on the registered float32 observation -> float32 actions -> env step), one C call."""

@@ -379,6 +379,12 @@ int ev2g_mlp_create(ev2g_handle *h, int d_in, int h1, int h2, int d_out, const f
 #define EV2G_MLP_F32X3 2
 int ev2g_mlp_create_ex(ev2g_handle *h, int d_in, int h1, int h2, int d_out, const float *W1, const float *b1, const float *W2,
                     const float *b2, const float *W3, const float *b3, float out_lo, int precision, ev2g_mlp **out);
+/* Which actor kernel the policy got (csrc/ev2g_policy_host.h: plan_mlp), as the instantiation's name: "ev2g_mlp3_any", "ev2g_mlp3_f32",
+ * "ev2g_mlp3_fixed<11,26,20>", "ev2g_mlp3_s16<6,25,19,4,1,8>" (the streaming kernel: k-steps of layer 1, 16-column tiles of the three layers,
+ * bf16 terms per weight, wavefronts per workgroup).  A bf16 streaming policy runs large batches on the 32-row variant; the string then goes on
+ * with "; from <rows> rows <that instantiation>", e.g. "ev2g_mlp3_s16<6,25,19,4,1,8>; from 4097 rows ev2g_mlp3_s16<6,25,19,4,1,4,2>".
+ * Owned by the policy, valid until ev2g_mlp_destroy; "" for NULL. */
+const char *ev2g_mlp_kernel_name(const ev2g_mlp *m);
 void ev2g_mlp_destroy(ev2g_handle *h, ev2g_mlp *m);
 /* y[n_rows,d_out] = actor(x[n_rows,d_in]); float32 DEVICE pointers; asynchronous on the handle's stream. */
 int ev2g_mlp_forward(ev2g_handle *h, const ev2g_mlp *m, const float *x, float *y, int n_rows);
