@@ -120,6 +120,18 @@ AC_ACTIVATIONS = {"tanh": 0, "relu": 1}   # EV2G_AC_TANH (SB3's default activati
 AC_MAX_IN, AC_MAX_HIDDEN, AC_MAX_OUT = 192, 256, 64   # the limits of ev2g_ac_create
 
 
+class PpoConfigC(C.Structure):   # ev2g_ppo_config, in header order
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double), ("clip_range", C.c_double),
+                ("vf_coef", C.c_double), ("ent_coef", C.c_double), ("max_grad_norm", C.c_double), ("normalize_advantage", C.c_int32)]
+
+
+class PpoInfoC(C.Structure):   # ev2g_ppo_info
+    _fields_ = [("lds_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("grid_cap", C.c_int32), ("n_params", C.c_int32)]
+
+
+PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction")   # the six statistics of ev2g_ppo_grad
+
+
 class EnvViewC(C.Structure):
     _fields_ = [
         ("current_step", C.c_int32), ("n_ports", C.c_int32), ("n_chargers", C.c_int32),

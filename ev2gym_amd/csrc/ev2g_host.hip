@@ -32,6 +32,7 @@
 #include "ev2g_grid.h"
 #include "ev2g_wrap.h"
 #include "ev2g_ac.h"
+#include "ev2g_ppo.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -128,7 +129,31 @@ struct ev2g_acpolicy {
     unsigned long long seed = 0, n = 0;
     float *clipped = nullptr;
     size_t clipped_elems = 0;
+    std::vector<float> log_std;           // the values last uploaded (ev2g_ac_get_weights returns them when no learner is bound)
+    struct ev2g_ppo *learner = nullptr;   // the PPO learner bound to this policy (ev2g_ppo_create), destroyed with it
 };
+
+// a PPO learner (ev2g_ppo_create, ev2g_ppo.h): float32 masters of the thirteen arrays in SB3's layout with Adam's m and v, the gradient of the
+// last ev2g_ppo_grad, the transposed images backprop reads, and the gradient kernel's workspace
+struct ev2g_ppo {
+    ev2g_acpolicy *ac = nullptr;
+    PpoPlan plan;
+    ev2g_ppo_config cfg{};
+    std::vector<void *> allocs;
+    float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *work = nullptr;
+    double *stat_part = nullptr, *norm_part = nullptr, *advstat = nullptr;
+    PpoDev dev{};
+    PpoMap map{};
+    int n_blocks = 0;          // blocks of the reduce / apply launches: ceil(n_params / 256)
+    long long t = 0;           // Adam's step count
+    bool have_grad = false;    // a gradient no ev2g_ppo_apply has consumed yet
+};
+
+static void ppo_free(ev2g_ppo *p) {
+    if (p->ac) p->ac->learner = nullptr;
+    for (void *q : p->allocs) (void)hipFree(q);
+    delete p;
+}
 
 static void ac_free(ev2g_acpolicy *ac) {
     for (void *p : ac->allocs) (void)hipFree(p);
@@ -231,6 +256,8 @@ struct ev2g_handle {
     std::vector<ev2g_grid *> grids;             // the distribution grids created on this handle (freed with it)
     std::vector<ev2g_wrap *> wraps;             // the action wrappers created on this handle (freed with it)
     std::vector<ev2g_acpolicy *> acs;           // the Gaussian actor-critics created on this handle (freed with it)
+    std::vector<ev2g_ppo *> ppos;               // the PPO learners created on this handle (freed with it, or with their policy)
+    unsigned ppo_attr_mask = 0;                 // ev2g_ppo_grad_kernel instantiations whose dynamic-LDS attribute was set
     unsigned ac_attr_mask = 0;                  // ev2g_ac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
 };
 
@@ -458,6 +485,7 @@ void ev2g_destroy(ev2g_handle *h) {
     h->grids.clear();
     for (ev2g_wrap *w : h->wraps) wrap_free(w);
     h->wraps.clear();
+    for (ev2g_ppo *p : h->ppos) ppo_free(p);
     for (ev2g_acpolicy *ac : h->acs) ac_free(ac);
     h->acs.clear();
     ev2g_comm_destroy(h);
@@ -2117,6 +2145,23 @@ static int ac_upload_log_std(ev2g_handle *h, ev2g_acpolicy *ac, const float *log
     HIPCHK(h, hipMemcpyAsync((void *)ac->dev.lp_a, a.data(), P * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync((void *)ac->dev.lp_c, c.data(), P * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    ac->log_std.assign(log_std, log_std + P);
+    return EV2G_OK;
+}
+
+// a bound learner's masters (and its transposed images) follow ev2g_ac_set_weights / ev2g_ac_set_log_std; Adam's state is kept
+static int ppo_reset_masters(ev2g_handle *h, ev2g_ppo *p, const AcWeights *w, const float *log_std) {
+    const PpoPlan &pl = p->plan;
+    if (w) {
+        const float *src[AC_ARRAYS] = {w->pW1, w->pb1, w->pW2, w->pb2, w->vW1, w->vb1, w->vW2, w->vb2, w->aW, w->ab, w->cW, w->cb};
+        for (int i = 0; i < AC_ARRAYS; i++)
+            HIPCHK(h, hipMemcpyAsync(p->theta + pl.off[i], src[i], (size_t)(pl.off[i + 1] - pl.off[i]) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(ev2g_ppo_repack_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->theta, 1);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (log_std)
+        HIPCHK(h, hipMemcpyAsync(p->theta + pl.off[12], log_std, (size_t)(pl.off[13] - pl.off[12]) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // the sources are the caller's
     return EV2G_OK;
 }
 
@@ -2178,7 +2223,12 @@ int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int
     return EV2G_OK;
 }
 
-void ev2g_ac_destroy(ev2g_handle *h, ev2g_acpolicy *ac) { owned_destroy(h, &ev2g_handle::acs, ac, ac_free); }
+static void ppo_free(ev2g_ppo *p);
+// (a bound learner goes with its policy)
+void ev2g_ac_destroy(ev2g_handle *h, ev2g_acpolicy *ac) {
+    if (h && ac && std::find(h->acs.begin(), h->acs.end(), ac) != h->acs.end() && ac->learner) owned_destroy(h, &ev2g_handle::ppos, ac->learner, ppo_free);
+    owned_destroy(h, &ev2g_handle::acs, ac, ac_free);
+}
 
 int ev2g_ac_seed(ev2g_handle *h, ev2g_acpolicy *ac, uint64_t seed, uint64_t first_draw) {
     if (int rc = ac_check(h, ac, "ev2g_ac_seed")) return rc;
@@ -2192,7 +2242,8 @@ int ev2g_ac_set_log_std(ev2g_handle *h, ev2g_acpolicy *ac, const float *log_std)
     for (int p = 0; p < ac->dev.d_out; p++)   // (checked before anything is enqueued: a refused call leaves the object as it was)
         if (!std::isfinite(log_std[p])) return fail(h, EV2G_ERR_ARG, "ev2g_ac_set_log_std: log_std[" + std::to_string(p) + "] is not finite");
     HIPCHK(h, hipStreamSynchronize(h->stream));   // launches still reading the old values
-    return ac_upload_log_std(h, ac, log_std, "ev2g_ac_set_log_std");
+    if (int rc = ac_upload_log_std(h, ac, log_std, "ev2g_ac_set_log_std")) return rc;
+    return ac->learner ? ppo_reset_masters(h, ac->learner, nullptr, log_std) : EV2G_OK;
 }
 
 int ev2g_ac_set_weights(ev2g_handle *h, ev2g_acpolicy *ac, const float *pi_W1, const float *pi_b1, const float *pi_W2, const float *pi_b2,
@@ -2201,7 +2252,8 @@ int ev2g_ac_set_weights(ev2g_handle *h, ev2g_acpolicy *ac, const float *pi_W1, c
     if (int rc = ac_check(h, ac, "ev2g_ac_set_weights")) return rc;
     const AcWeights w{pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b};
     if (ac_weights_null(w)) return fail(h, EV2G_ERR_ARG, "ev2g_ac_set_weights: a weight or bias pointer is null");
-    return ac_upload_weights(h, ac, w);   // (stream-ordered behind the launches that read the old weights)
+    if (int rc = ac_upload_weights(h, ac, w)) return rc;   // (stream-ordered behind the launches that read the old weights)
+    return ac->learner ? ppo_reset_masters(h, ac->learner, &w, nullptr) : EV2G_OK;
 }
 
 // one launch of ev2g_ac_act_kernel over n_rows rows; a sampling launch takes the object's counter and advances it
@@ -2287,6 +2339,277 @@ int ev2g_host_gae(const double *reward, const float *values, const uint8_t *epis
     if (int rc = gae_args(nullptr, "ev2g_host_gae", reward, values, episode_starts, last_values, last_dones, advantages, returns, k, n_envs)) return rc;
     const float g = (float)gamma, c = (float)(gamma * lambda);
     for (int e = 0; e < n_envs; e++) ev2g_gae_env(reward, values, episode_starts, last_values, last_dones, k, n_envs, e, g, c, advantages, returns);
+    return EV2G_OK;
+}
+
+// ---- the PPO learner (ev2g_ppo.h) ----
+static int ppo_check(ev2g_handle *h, ev2g_ppo *p, const char *who) {
+    if (!h || !p) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (std::find(h->ppos.begin(), h->ppos.end(), p) == h->ppos.end())
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the learner was not created on this handle");
+    (void)hipSetDevice(h->device);
+    return EV2G_OK;
+}
+
+int ev2g_ppo_query(int d_in, int h1, int h2, int v1, int v2, int d_out, ev2g_ppo_info *info) {
+    if (!info) return fail(nullptr, EV2G_ERR_ARG, "ev2g_ppo_query: info is null");
+    const PpoPlan p = plan_ppo(d_in, h1, h2, v1, v2, d_out);
+    if (p.err) return fail(nullptr, p.err, p.refusal);
+    info->lds_bytes = (int64_t)p.lds.bytes; info->workspace_bytes = (int64_t)p.workspace_bytes;
+    info->grid_cap = p.grid_cap; info->n_params = p.n_params;
+    return EV2G_OK;
+}
+
+static int ppo_config_check(ev2g_handle *h, const char *who, double lr, double clip_range, const ev2g_ppo_config *c) {
+    auto bad = [&](const char *name, const char *range) { return fail(h, EV2G_ERR_ARG, std::string(who) + ": " + name + " must be " + range); };
+    if (!std::isfinite(lr) || lr < 0.0) return bad("lr", "finite and >= 0");
+    if (!std::isfinite(clip_range) || clip_range <= 0.0) return bad("clip_range", "finite and > 0");
+    if (!c) return EV2G_OK;
+    if (!std::isfinite(c->beta1) || c->beta1 < 0.0 || c->beta1 >= 1.0) return bad("beta1", "in [0, 1)");
+    if (!std::isfinite(c->beta2) || c->beta2 < 0.0 || c->beta2 >= 1.0) return bad("beta2", "in [0, 1)");
+    if (!std::isfinite(c->adam_eps) || c->adam_eps <= 0.0) return bad("adam_eps", "finite and > 0");
+    if (!std::isfinite(c->vf_coef) || c->vf_coef < 0.0) return bad("vf_coef", "finite and >= 0");
+    if (!std::isfinite(c->ent_coef) || c->ent_coef < 0.0) return bad("ent_coef", "finite and >= 0");
+    if (!std::isfinite(c->max_grad_norm) || c->max_grad_norm <= 0.0) return bad("max_grad_norm", "finite and > 0");
+    return EV2G_OK;
+}
+
+// the twelve arrays of a policy in SB3's layout from its packed images (out[i]: n_params-ordered host pointers)
+static int ac_read_images(ev2g_handle *h, ev2g_acpolicy *ac, float *const out[AC_ARRAYS]) {
+    const AcPlan &a = ac->plan;
+    const auto sizes = ac_array_sizes(a);
+    const AcDev &d = ac->dev;
+    // AcWeights' order <- the device arrays of AcDev
+    const float *src[AC_ARRAYS] = {d.w1, d.b1, d.w2, d.b2, d.u1, d.c1, d.u2, d.c2, d.w3, d.b3, d.u3, d.c3};
+    const size_t sz[AC_ARRAYS] = {sizes[0], sizes[1], sizes[2], sizes[3], sizes[6], sizes[7], sizes[8], sizes[9], sizes[4], sizes[5], sizes[10], sizes[11]};
+    const int rows[AC_ARRAYS] = {a.h1, a.h1, a.h2, a.h2, a.v1, a.v1, a.v2, a.v2, a.d_out, a.d_out, a.v2, 1};
+    const int cols[AC_ARRAYS] = {a.d_in, 0, a.h1, 0, a.d_in, 0, a.v1, 0, a.h2, 0, 0, 0};
+    const int K[AC_ARRAYS] = {a.k1, 0, a.n1, 0, a.k1, 0, a.m1, 0, a.n2, 0, 0, 0};
+    std::vector<float> stage[AC_ARRAYS];
+    for (int i = 0; i < AC_ARRAYS; i++) {
+        stage[i].resize(sz[i]);
+        HIPCHK(h, hipMemcpyAsync(stage[i].data(), src[i], sz[i] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < AC_ARRAYS; i++) {
+        if (cols[i]) unpack_linear_f32(stage[i].data(), rows[i], cols[i], K[i], out[i]);
+        else std::copy(stage[i].begin(), stage[i].begin() + rows[i], out[i]);
+    }
+    return EV2G_OK;
+}
+
+static void ppo_launch_repack(ev2g_handle *h, ev2g_ppo *p, bool transposed_only) {
+    hipLaunchKernelGGL(ev2g_ppo_repack_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->theta, transposed_only ? 1 : 0);
+}
+
+int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cfg, ev2g_ppo **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: null argument");
+    *out = nullptr;
+    if (!cfg) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: cfg is null");
+    if (int rc = ac_check(h, ac, "ev2g_ppo_create")) return rc;
+    if (int rc = ppo_config_check(h, "ev2g_ppo_create", cfg->lr, cfg->clip_range, cfg)) return rc;
+    if (ac->learner) return fail(h, EV2G_ERR_STATE, "ev2g_ppo_create: the policy already has a learner");
+    const AcPlan &a = ac->plan;
+    PpoPlan plan = plan_ppo(a.d_in, a.h1, a.h2, a.v1, a.v2, a.d_out);
+    if (plan.err) return fail(h, plan.err, plan.refusal);
+    ev2g_ppo *p = new ev2g_ppo();
+    p->plan = plan; p->cfg = *cfg;
+    p->n_blocks = (plan.n_params + 255) / 256;
+    const size_t G = (size_t)plan.n_params;
+    float *w2t = nullptr, *w3t = nullptr, *u2t = nullptr;
+    int rc = 0;
+    if ((rc = dalloc(h, p->allocs, G, &p->theta)) || (rc = dalloc(h, p->allocs, G, &p->m)) || (rc = dalloc(h, p->allocs, G, &p->v)) ||
+        (rc = dalloc(h, p->allocs, G, &p->grad)) || (rc = dalloc(h, p->allocs, (size_t)plan.grid_cap * plan.slab_floats, &p->work)) ||
+        (rc = dalloc(h, p->allocs, (size_t)plan.grid_cap * 8, &p->stat_part)) || (rc = dalloc(h, p->allocs, (size_t)p->n_blocks, &p->norm_part)) ||
+        (rc = dalloc(h, p->allocs, 2, &p->advstat)) || (rc = dalloc(h, p->allocs, (size_t)a.n1 * a.n2, &w2t)) ||
+        (rc = dalloc(h, p->allocs, (size_t)a.n2 * a.n3, &w3t)) || (rc = dalloc(h, p->allocs, (size_t)a.m1 * a.m2, &u2t))) {
+        ppo_free(p);
+        return rc;
+    }
+    // the masters: the policy's current numbers, read back from its images (exact: the images hold the float32 values themselves)
+    std::vector<float> host(G, 0.f);
+    float *dst[AC_ARRAYS];
+    for (int i = 0; i < AC_ARRAYS; i++) dst[i] = host.data() + plan.off[i];
+    if ((rc = ac_read_images(h, ac, dst))) { ppo_free(p); return rc; }
+    std::copy(ac->log_std.begin(), ac->log_std.end(), host.begin() + plan.off[12]);
+    PpoDev &d = p->dev;
+    d.k1r = plan.k1r; d.w2t = w2t; d.w3t = w3t; d.u2t = u2t; d.log_std = p->theta + plan.off[12];
+    PpoMap &mp = p->map;
+    const AcDev &ad = ac->dev;
+    float *img[EV2G_PPO_ARRAYS] = {(float *)ad.w1, (float *)ad.b1, (float *)ad.w2, (float *)ad.b2, (float *)ad.u1, (float *)ad.c1, (float *)ad.u2,
+                                   (float *)ad.c2, (float *)ad.w3, (float *)ad.b3, (float *)ad.u3, (float *)ad.c3, nullptr};
+    const int img_k[EV2G_PPO_ARRAYS] = {a.k1, 0, a.n1, 0, a.k1, 0, a.m1, 0, a.n2, 0, 0, 0, 0};
+    float *imgT[EV2G_PPO_ARRAYS] = {nullptr, nullptr, w2t, nullptr, nullptr, nullptr, u2t, nullptr, w3t, nullptr, nullptr, nullptr, nullptr};
+    const int imgT_k[EV2G_PPO_ARRAYS] = {0, 0, a.n2, 0, 0, 0, a.m2, 0, a.n3, 0, 0, 0, 0};
+    for (int i = 0; i < EV2G_PPO_ARRAYS; i++) {
+        mp.off[i] = plan.off[i]; mp.cols[i] = plan.cols[i]; mp.slab_off[i] = plan.slab_off[i]; mp.slab_ld[i] = plan.slab_ld[i];
+        mp.img[i] = img[i]; mp.img_k[i] = img_k[i]; mp.imgT[i] = imgT[i]; mp.imgT_k[i] = imgT_k[i];
+        d.slab_off[i] = plan.slab_off[i];
+    }
+    mp.off[EV2G_PPO_ARRAYS] = plan.off[EV2G_PPO_ARRAYS];
+    mp.slab_floats = d.slab_floats = plan.slab_floats; mp.n_params = plan.n_params; mp.P = a.d_out;
+    hipError_t e = hipMemcpyAsync(p->theta, host.data(), G * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) { ppo_launch_repack(h, p, true); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    const int relu = ac->relu;
+    if (e == hipSuccess && plan.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & (1u << relu))) {   // (function attributes are per device: once per handle)
+        const void *fn = relu ? (const void *)ev2g_ppo_grad_kernel<EV2G_AC_RELU> : (const void *)ev2g_ppo_grad_kernel<EV2G_AC_TANH>;
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
+        if (e == hipSuccess) h->ppo_attr_mask |= 1u << relu;
+    }
+    if (e != hipSuccess) { ppo_free(p); return fail(h, EV2G_ERR_HIP, std::string("ev2g_ppo_create: ") + hipGetErrorString(e)); }
+    p->ac = ac; ac->learner = p;
+    h->ppos.push_back(p);
+    *out = p;
+    return EV2G_OK;
+}
+
+void ev2g_ppo_destroy(ev2g_handle *h, ev2g_ppo *ppo) { owned_destroy(h, &ev2g_handle::ppos, ppo, ppo_free); }
+
+int ev2g_ppo_set_rates(ev2g_handle *h, ev2g_ppo *p, double lr, double clip_range) {
+    if (int rc = ppo_check(h, p, "ev2g_ppo_set_rates")) return rc;
+    if (int rc = ppo_config_check(h, "ev2g_ppo_set_rates", lr, clip_range, nullptr)) return rc;
+    p->cfg.lr = lr; p->cfg.clip_range = clip_range;
+    return EV2G_OK;
+}
+
+static int ppo_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, const float *obs, const float *actions, const float *old_lp, const float *adv,
+                    const float *ret, const int32_t *idx, int B, float *stats) {
+    if (int rc = ppo_check(h, p, who)) return rc;
+    if (!obs || !actions || !old_lp || !adv || !ret || !idx) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B must be at least 1");
+    const PpoPlan &pl = p->plan;
+    const PpoHyper hp{(float)p->cfg.clip_range, (float)p->cfg.vf_coef, (float)p->cfg.ent_coef, p->cfg.normalize_advantage ? 1 : 0};
+    if (hp.normalize && B > 1) hipLaunchKernelGGL(ev2g_ppo_advstat_kernel, dim3(1), dim3(1024), 0, h->stream, adv, (const int *)idx, B, p->advstat);
+    const int chunks = (B + EV2G_PPO_ROWS - 1) / EV2G_PPO_ROWS, n_wg = chunks < pl.grid_cap ? chunks : pl.grid_cap;
+    const dim3 grid((unsigned)n_wg), block(EV2G_PPO_BLOCK);
+    if (p->ac->relu)
+        hipLaunchKernelGGL(ev2g_ppo_grad_kernel<EV2G_AC_RELU>, grid, block, pl.lds.bytes, h->stream, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv,
+                           ret, (const int *)idx, B, (const double *)p->advstat, p->work, p->stat_part);
+    else
+        hipLaunchKernelGGL(ev2g_ppo_grad_kernel<EV2G_AC_TANH>, grid, block, pl.lds.bytes, h->stream, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv,
+                           ret, (const int *)idx, B, (const double *)p->advstat, p->work, p->stat_part);
+    hipLaunchKernelGGL(ev2g_ppo_reduce_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->work,
+                       (const double *)p->stat_part, n_wg, B, hp, p->dev.log_std, p->grad, p->norm_part, stats);
+    HIPCHK(h, hipGetLastError());
+    p->have_grad = true;
+    return EV2G_OK;
+}
+
+static AdamStep adam_step(double lr, double beta1, double beta2, double eps, long long t) {
+    const double bc1 = 1.0 - std::pow(beta1, (double)t), bc2 = 1.0 - std::pow(beta2, (double)t);
+    return {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps};
+}
+
+static int ppo_apply(ev2g_handle *h, ev2g_ppo *p, const char *who) {
+    if (int rc = ppo_check(h, p, who)) return rc;
+    if (!p->have_grad) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_ppo_grad first)");
+    const ev2g_ppo_config &c = p->cfg;
+    p->t += 1;
+    hipLaunchKernelGGL(ev2g_ppo_apply_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->grad,
+                       (const double *)p->norm_part, p->n_blocks, (float)c.max_grad_norm, adam_step(c.lr, c.beta1, c.beta2, c.adam_eps, p->t), p->theta,
+                       p->m, p->v);
+    HIPCHK(h, hipGetLastError());
+    p->have_grad = false;
+    return EV2G_OK;
+}
+
+int ev2g_ppo_grad(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
+                  const float *returns, const int32_t *idx, int B, float *stats) {
+    return ppo_grad(h, ppo, "ev2g_ppo_grad", obs, actions, old_log_prob, advantages, returns, idx, B, stats);
+}
+
+int ev2g_ppo_apply(ev2g_handle *h, ev2g_ppo *ppo) { return ppo_apply(h, ppo, "ev2g_ppo_apply"); }
+
+int ev2g_ppo_minibatch(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
+                       const float *returns, const int32_t *idx, int B, float *stats) {
+    if (int rc = ppo_grad(h, ppo, "ev2g_ppo_minibatch", obs, actions, old_log_prob, advantages, returns, idx, B, stats)) return rc;
+    return ppo_apply(h, ppo, "ev2g_ppo_minibatch");
+}
+
+// a flat [n_params] device buffer into the thirteen host arrays
+static int ppo_read_flat(ev2g_handle *h, const PpoPlan &pl, const float *src, float *const out[EV2G_PPO_ARRAYS]) {
+    for (int i = 0; i < EV2G_PPO_ARRAYS; i++)
+        if (out[i])
+            HIPCHK(h, hipMemcpyAsync(out[i], src + pl.off[i], (size_t)(pl.off[i + 1] - pl.off[i]) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+int ev2g_ppo_get_grads(ev2g_handle *h, ev2g_ppo *ppo, float *pi_W1, float *pi_b1, float *pi_W2, float *pi_b2, float *vf_W1, float *vf_b1,
+                       float *vf_W2, float *vf_b2, float *action_W, float *action_b, float *value_W, float *value_b, float *log_std) {
+    if (int rc = ppo_check(h, ppo, "ev2g_ppo_get_grads")) return rc;
+    float *const out[EV2G_PPO_ARRAYS] = {pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b, log_std};
+    for (float *o : out)
+        if (!o) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_get_grads: null argument");
+    return ppo_read_flat(h, ppo->plan, ppo->grad, out);
+}
+
+int ev2g_ppo_sync(ev2g_handle *h, ev2g_ppo *ppo) {
+    if (int rc = ppo_check(h, ppo, "ev2g_ppo_sync")) return rc;
+    std::vector<float> ls((size_t)ppo->ac->dev.d_out);
+    HIPCHK(h, hipMemcpyAsync(ls.data(), ppo->dev.log_std, ls.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return ac_upload_log_std(h, ppo->ac, ls.data(), "ev2g_ppo_sync");
+}
+
+int ev2g_ac_get_weights(ev2g_handle *h, ev2g_acpolicy *ac, float *pi_W1, float *pi_b1, float *pi_W2, float *pi_b2, float *vf_W1, float *vf_b1,
+                        float *vf_W2, float *vf_b2, float *action_W, float *action_b, float *value_W, float *value_b, float *log_std) {
+    if (int rc = ac_check(h, ac, "ev2g_ac_get_weights")) return rc;
+    float *const out[EV2G_PPO_ARRAYS] = {pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b, log_std};
+    for (float *o : out)
+        if (!o) return fail(h, EV2G_ERR_ARG, "ev2g_ac_get_weights: null argument");
+    if (ac->learner) return ppo_read_flat(h, ac->learner->plan, ac->learner->theta, out);
+    if (int rc = ac_read_images(h, ac, out)) return rc;
+    std::copy(ac->log_std.begin(), ac->log_std.end(), log_std);
+    return EV2G_OK;
+}
+
+int ev2g_host_adam(float *theta, float *m, float *v, const float *g, int64_t n, int64_t t, double lr, double beta1, double beta2, double eps) {
+    if (!theta || !m || !v || !g || n < 0 || t < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_adam: null argument, n < 0 or t < 1");
+    if (!std::isfinite(lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0))
+        return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_adam: lr must be finite, the betas in [0, 1), eps > 0");
+    const AdamStep a = adam_step(lr, beta1, beta2, eps, (long long)t);
+    for (int64_t i = 0; i < n; i++) ev2g_adam_elem(theta + i, m + i, v + i, g[i], a);
+    return EV2G_OK;
+}
+
+int ev2g_host_ppo_head(const float *mean, const float *value, const float *actions, const float *log_std, const float *old_log_prob,
+                       const float *advantages, const float *returns, int B, int P, const ev2g_ppo_config *cfg, float *d_mean, float *d_value,
+                       float *d_log_std, float *stats) {
+    if (!mean || !value || !actions || !log_std || !old_log_prob || !advantages || !returns || !cfg || !d_mean || !d_value || !d_log_std || !stats)
+        return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ppo_head: null argument");
+    if (B < 1 || P < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ppo_head: B and P must be positive");
+    const bool norm = cfg->normalize_advantage && B > 1;
+    double a_mean = 0.0, a_scale = 1.0;
+    if (norm) {
+        double s = 0.0;
+        for (int i = 0; i < B; i++) s += (double)advantages[i];
+        a_mean = s / B;
+        s = 0.0;
+        for (int i = 0; i < B; i++) { const double d = (double)advantages[i] - a_mean; s += d * d; }
+        a_scale = 1.0 / (std::sqrt(s / (double)(B - 1)) + 1e-8);
+    }
+    std::vector<double> iv((size_t)P), dls((size_t)P, 0.0);
+    for (int p = 0; p < P; p++) iv[(size_t)p] = std::exp(-2.0 * (double)log_std[p]);
+    const double inv_b = 1.0 / (double)B;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < B; i++) {
+        const float *mu = mean + (size_t)i * P, *a = actions + (size_t)i * P;
+        double q[8];
+        for (int j = 0; j < 8; j++) q[j] = ev2g_ppo_lp_part(mu, a, log_std, iv.data(), P, j, 8);
+        const float A = norm ? (float)(((double)advantages[i] - a_mean) * a_scale) : advantages[i];
+        const PpoRow o = ev2g_ppo_head_row(ev2g_ppo_join8(q), old_log_prob[i], A, returns[i], value[i], (float)cfg->clip_range, (float)cfg->vf_coef, inv_b);
+        d_value[i] = o.g_v;
+        sum[0] += o.pol; sum[1] += o.vsq; sum[2] += o.kl; sum[3] += o.clipped;
+        for (int p = 0; p < P; p++) {
+            float dl;
+            ev2g_ppo_head_port(a[p], mu[p], iv[(size_t)p], o.g_lp, d_mean + (size_t)i * P + p, &dl);
+            dls[(size_t)p] += (double)dl;
+        }
+    }
+    for (int p = 0; p < P; p++) d_log_std[p] = (float)(dls[(size_t)p] - cfg->ent_coef);
+    ev2g_ppo_stats(sum, log_std, P, inv_b, (float)cfg->vf_coef, (float)cfg->ent_coef, stats);
     return EV2G_OK;
 }
 

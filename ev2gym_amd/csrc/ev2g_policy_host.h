@@ -4,7 +4,8 @@
 // index into ev2g_host.hip's kMlpTable), the streaming kernel's fragment packing (the FusedPacking route_fused reads), LDS bytes, rows per
 // workgroup and threads, and the 32-row variant bf16 streaming policies run on large batches.  pack_mlp(plan, weights) builds the host
 // images of the three weight matrices in that kernel's MFMA fragment order and of the biases.  plan_ac / pack_ac are the same for the
-// Gaussian actor-critic (ev2g_ac.h), which reads float32 operands in ev2g_mlp3_f32's layout.  ev2g_host.hip is the device stage: it
+// Gaussian actor-critic (ev2g_ac.h), which reads float32 operands in ev2g_mlp3_f32's layout; plan_ppo is the plan of its PPO learner
+// (ev2g_ppo.h): accepted widths, LDS layout, grid cap, workspace.  ev2g_host.hip is the device stage: it
 // uploads the images and launches the table's entry.  Nothing here needs HIP, a handle or a kernel header, so a plain C++17 program can
 // enumerate the plan and check every packed element (tests/host/policy_plan_check.cpp).
 //
@@ -291,4 +292,103 @@ inline std::array<std::vector<float>, AC_ARRAYS> pack_ac(const AcPlan &p, const 
             pack_linear_f32(w.vW1, p.v1, p.d_in, p.m1, p.k1), pad_bias(w.vb1, p.v1, p.m1),
             pack_linear_f32(w.vW2, p.v2, p.v1, p.m2, p.m1),   pad_bias(w.vb2, p.v2, p.m2),
             pad_bias(w.cW, p.v2, p.m2),                       pad_bias(w.cb, 1, 1)};
+}
+
+// inverse of pack_linear_f32 / pad_bias: the [n_out, n_in] matrix an image holds (ev2g_ac_get_weights on a policy without a learner)
+inline void unpack_linear_f32(const float *img, int n_out, int n_in, int K, float *W) {
+    const int KG = K / 8;
+    for (int n = 0; n < n_out; n++)
+        for (int k = 0; k < n_in; k++)
+            W[(size_t)n * n_in + k] = img[(((size_t)(n >> 5) * KG + (k >> 3)) * 64 + (n & 31) + 32 * ((k & 7) >> 2)) * 4 + (k & 3)];
+}
+// where element (n, k) of a matrix sits in its pack_linear_f32 image of K padded inputs (the device repack of ev2g_ppo.h writes by it)
+constexpr size_t packed_f32_index(int n, int k, int K) {
+    return (((size_t)(n >> 5) * (size_t)(K / 8) + (size_t)(k >> 3)) * 64 + (size_t)((n & 31) + 32 * ((k & 7) >> 2))) * 4 + (size_t)(k & 3);
+}
+
+// ---- the PPO learner of a Gaussian actor-critic (ev2g_ppo.h) ----
+// Thirteen gradient arrays in SB3's parameter order: the twelve of AcWeights, then log_std.  The gradient kernel's workgroup keeps, per 32 gathered
+// rows, every activation and every layer's delta in LDS (float32 rows of stride width + 4, as ev2g_ac_lds), and its partial sums in a slab of
+// its own in the workspace: matrices [padded out][padded in] row-major with the inputs of the first layers padded to 32 (the weight-gradient
+// tiles are 32 x 32), vectors padded likewise.
+#define EV2G_PPO_ROWS 32
+#define EV2G_PPO_BLOCK 256
+#define EV2G_PPO_GRID_CAP 256   // workgroups of the gradient kernel at most (one per CU of an MI355X); more chunks loop
+#define EV2G_PPO_ARRAYS 13
+#define EV2G_PPO_MAX_IN 192
+#define EV2G_PPO_MAX_OUT 64
+#define EV2G_PPO_LDS_LIMIT (160 * 1024)
+
+struct PpoLds {   // offsets in floats from the 16-byte aligned base; the first n3 doubles are exp(-2 log_std)
+    int sX, sH1, sH2, sV1, sV2, sMU;   // row strides: x, the trunks' hidden layers, the mean (and the actions)
+    int oIV, oX, oH1, oH2, oV1, oV2, oMU, oACT, oD1, oD2, oE1, oE2, oROW;   // D / E: the deltas of H / V; ROW: [3][32] per-row head values
+    size_t bytes;
+};
+constexpr PpoLds ppo_lds(int k1r, int n1, int n2, int m1, int m2, int n3) {
+    PpoLds l{};
+    l.sX = k1r + 4; l.sH1 = n1 + 4; l.sH2 = n2 + 4; l.sV1 = m1 + 4; l.sV2 = m2 + 4; l.sMU = n3 + 4;
+    int o = 2 * n3;
+    const int R = EV2G_PPO_ROWS;
+    l.oIV = 0;
+    l.oX = o; o += R * l.sX;
+    l.oH1 = o; o += R * l.sH1;
+    l.oH2 = o; o += R * l.sH2;
+    l.oV1 = o; o += R * l.sV1;
+    l.oV2 = o; o += R * l.sV2;
+    l.oMU = o; o += R * l.sMU;
+    l.oACT = o; o += R * l.sMU;
+    l.oD1 = o; o += R * l.sH1;
+    l.oD2 = o; o += R * l.sH2;
+    l.oE1 = o; o += R * l.sV1;
+    l.oE2 = o; o += R * l.sV2;
+    l.oROW = o; o += 3 * R;
+    l.bytes = (size_t)o * sizeof(float);
+    return l;
+}
+
+struct PpoPlan {
+    int err = EV2G_OK;
+    std::string refusal;
+    AcPlan ac{};
+    int k1r = 0;                            // the first layers' inputs padded to 32
+    PpoLds lds{};
+    int grid_cap = EV2G_PPO_GRID_CAP;
+    int rows[EV2G_PPO_ARRAYS] = {}, cols[EV2G_PPO_ARRAYS] = {};   // the arrays' own shapes (vectors: cols 1)
+    int off[EV2G_PPO_ARRAYS + 1] = {};      // where each starts in the flat [n_params] master / m / v / gradient buffers
+    int slab_off[EV2G_PPO_ARRAYS] = {}, slab_ld[EV2G_PPO_ARRAYS] = {};   // ... and in a workgroup's slab (row stride; vectors: 1)
+    int slab_floats = 0;
+    int n_params = 0;
+    size_t workspace_bytes = 0;             // grid_cap slabs + grid_cap x 8 doubles of statistics partials
+};
+inline PpoPlan plan_ppo(int d_in, int h1, int h2, int v1, int v2, int d_out) {
+    PpoPlan p;
+    auto refuse = [&p](const std::string &why) { p.err = EV2G_ERR_ARG; p.refusal = why; return p; };
+    if (d_in < 1 || d_in > EV2G_PPO_MAX_IN) return refuse("ev2g_ppo: d_in " + std::to_string(d_in) + " is outside 1 .. " + std::to_string(EV2G_PPO_MAX_IN));
+    if (d_out < 1 || d_out > EV2G_PPO_MAX_OUT) return refuse("ev2g_ppo: d_out " + std::to_string(d_out) + " is outside 1 .. " + std::to_string(EV2G_PPO_MAX_OUT));
+    const int hid[4] = {h1, h2, v1, v2};
+    const char *name[4] = {"h1", "h2", "v1", "v2"};
+    for (int i = 0; i < 4; i++)
+        if (hid[i] < 1 || hid[i] > 256) return refuse(std::string("ev2g_ppo: ") + name[i] + " " + std::to_string(hid[i]) + " is outside 1 .. 256");
+    p.ac = plan_ac(d_in, h1, h2, v1, v2, d_out);
+    const AcPlan &a = p.ac;
+    p.k1r = mlp_round_up(d_in, 32);
+    p.lds = ppo_lds(p.k1r, a.n1, a.n2, a.m1, a.m2, a.n3);
+    if (p.lds.bytes > EV2G_PPO_LDS_LIMIT) {
+        int w = 0;   // the widest hidden layer is the one to name
+        for (int i = 1; i < 4; i++) if (hid[i] > hid[w]) w = i;
+        return refuse(std::string("ev2g_ppo: ") + name[w] + " " + std::to_string(hid[w]) + " is too wide: the gradient kernel's LDS plan takes " +
+                      std::to_string(p.lds.bytes) + " bytes of the CU's " + std::to_string(EV2G_PPO_LDS_LIMIT));
+    }
+    const int R[EV2G_PPO_ARRAYS] = {h1, h1, h2, h2, v1, v1, v2, v2, d_out, d_out, 1, 1, d_out};
+    const int C[EV2G_PPO_ARRAYS] = {d_in, 1, h1, 1, d_in, 1, v1, 1, h2, 1, v2, 1, 1};
+    const int SR[EV2G_PPO_ARRAYS] = {a.n1, a.n1, a.n2, a.n2, a.m1, a.m1, a.m2, a.m2, a.n3, a.n3, 1, 4, a.n3};   // slab rows
+    const int SL[EV2G_PPO_ARRAYS] = {p.k1r, 1, a.n1, 1, p.k1r, 1, a.m1, 1, a.n2, 1, a.m2, 1, 1};               // slab row stride
+    int o = 0, s = 0;
+    for (int i = 0; i < EV2G_PPO_ARRAYS; i++) {
+        p.rows[i] = R[i]; p.cols[i] = C[i]; p.off[i] = o; o += R[i] * C[i];
+        p.slab_off[i] = s; p.slab_ld[i] = SL[i]; s += SR[i] * SL[i];
+    }
+    p.off[EV2G_PPO_ARRAYS] = o; p.n_params = o; p.slab_floats = s;
+    p.workspace_bytes = (size_t)p.grid_cap * ((size_t)s * sizeof(float) + 8 * sizeof(double));
+    return p;
 }

@@ -112,6 +112,18 @@ def load_library(path: Optional[str] = None):
         "ev2g_ac_host_normal": (None, [vp, i64, C.c_uint64, C.c_uint64]),
         "ev2g_gae": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, dbl, dbl, vp, vp]),
         "ev2g_host_gae": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, dbl, dbl, vp, vp]),
+        "ev2g_ppo_query": (C.c_int, [C.c_int] * 6 + [C.POINTER(_abi.PpoInfoC)]),
+        "ev2g_ppo_create": (C.c_int, [vp, vp, C.POINTER(_abi.PpoConfigC), C.POINTER(vp)]),
+        "ev2g_ppo_destroy": (None, [vp, vp]),
+        "ev2g_ppo_set_rates": (C.c_int, [vp, vp, dbl, dbl]),
+        "ev2g_ppo_grad": (C.c_int, [vp, vp] + [vp] * 6 + [C.c_int, vp]),
+        "ev2g_ppo_apply": (C.c_int, [vp, vp]),
+        "ev2g_ppo_minibatch": (C.c_int, [vp, vp] + [vp] * 6 + [C.c_int, vp]),
+        "ev2g_ppo_get_grads": (C.c_int, [vp, vp] + [vp] * 13),
+        "ev2g_ppo_sync": (C.c_int, [vp, vp]),
+        "ev2g_ac_get_weights": (C.c_int, [vp, vp] + [vp] * 13),
+        "ev2g_host_adam": (C.c_int, [vp, vp, vp, vp, i64, i64, dbl, dbl, dbl, dbl]),
+        "ev2g_host_ppo_head": (C.c_int, [vp] * 7 + [C.c_int, C.c_int, C.POINTER(_abi.PpoConfigC), vp, vp, vp, vp]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -173,7 +185,9 @@ EXPORTED_SYMBOLS = [
     "ev2g_grid_state_attach", "ev2g_grid_state_dim", "ev2g_grid_observe", "ev2g_grid_run_observed", "ev2g_grid_rollout", "ev2g_grid_get_stats",
     "ev2g_wrap_create", "ev2g_wrap_destroy", "ev2g_wrap_reset_state", "ev2g_wrap_actions", "ev2g_wrap_run", "ev2g_wrap_rollout",
     "ev2g_ac_create", "ev2g_ac_destroy", "ev2g_ac_seed", "ev2g_ac_set_log_std", "ev2g_ac_set_weights", "ev2g_ac_forward", "ev2g_ac_act",
-    "ev2g_ac_collect", "ev2g_ac_host_normal", "ev2g_gae", "ev2g_host_gae"]
+    "ev2g_ac_collect", "ev2g_ac_host_normal", "ev2g_gae", "ev2g_host_gae",
+    "ev2g_ppo_query", "ev2g_ppo_create", "ev2g_ppo_destroy", "ev2g_ppo_set_rates", "ev2g_ppo_grad", "ev2g_ppo_apply", "ev2g_ppo_minibatch",
+    "ev2g_ppo_get_grads", "ev2g_ppo_sync", "ev2g_ac_get_weights", "ev2g_host_adam", "ev2g_host_ppo_head"]
 
 
 def _ptr(x):
@@ -678,6 +692,55 @@ class Engine:
                                        int(n_envs), float(gamma), float(gae_lambda), _ptr(advantages), _ptr(returns)))
 
     # ---- statistics / inspection ---------------------------------------------------------------
+    # ---- the PPO learner (include/ev2g.h: ev2g_ppo_*) ---------------------------------------------------------------------------------
+    def _ac_shapes(self, ac_shape):
+        D, h1, h2, v1, v2, P = ac_shape
+        return ((h1, D), (h1,), (h2, h1), (h2,), (v1, D), (v1,), (v2, v1), (v2,), (P, h2), (P,), (1, v2), (1,), (P,))
+
+    def ac_get_weights(self, ac, ac_shape):
+        """(the twelve arrays, log_std) of a device policy as host float32 arrays (ev2g_ac_get_weights): the learner's masters when one is bound.
+        ac_shape: (d_in, h1, h2, v1, v2, d_out)."""
+        out = [np.empty(s, np.float32) for s in self._ac_shapes(ac_shape)]
+        self._check(self._lib.ev2g_ac_get_weights(self._h, ac, *[a.ctypes.data for a in out]))
+        return out[:12], out[12]
+
+    def ppo_create(self, ac, lr=3e-4, beta1=0.9, beta2=0.999, adam_eps=1e-5, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5,
+                   normalize_advantage=True):
+        """A PPO learner bound to the device policy `ac` (ev2g_ppo_create), freed by ppo_destroy, with its policy or with the engine."""
+        cfg = _abi.PpoConfigC(float(lr), float(beta1), float(beta2), float(adam_eps), float(clip_range), float(vf_coef), float(ent_coef),
+                              float(max_grad_norm), int(bool(normalize_advantage)))
+        out = C.c_void_p()
+        self._check(self._lib.ev2g_ppo_create(self._h, ac, C.byref(cfg), C.byref(out)))
+        return out.value
+
+    def ppo_destroy(self, ppo):
+        if ppo and self._h:
+            self._lib.ev2g_ppo_destroy(self._h, ppo)
+
+    def ppo_set_rates(self, ppo, lr, clip_range):
+        self._check(self._lib.ev2g_ppo_set_rates(self._h, ppo, float(lr), float(clip_range)))
+
+    def ppo_grad(self, ppo, obs, actions, old_log_prob, advantages, returns, idx, B, stats=None):
+        """The gradient of the minibatch idx [B] (int32) of the DEVICE float32 arrays; stays in the learner.  stats: float32 [6] DEVICE or None."""
+        self._check(self._lib.ev2g_ppo_grad(self._h, ppo, _ptr(obs), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(returns), _ptr(idx),
+                                            int(B), _ptr(stats)))
+
+    def ppo_apply(self, ppo):
+        self._check(self._lib.ev2g_ppo_apply(self._h, ppo))
+
+    def ppo_minibatch(self, ppo, obs, actions, old_log_prob, advantages, returns, idx, B, stats=None):
+        self._check(self._lib.ev2g_ppo_minibatch(self._h, ppo, _ptr(obs), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(returns),
+                                                 _ptr(idx), int(B), _ptr(stats)))
+
+    def ppo_get_grads(self, ppo, ac_shape):
+        """The last gradient (unclipped) as thirteen host float32 arrays in SB3's layout: the twelve of ac_create's order, then log_std."""
+        out = [np.empty(s, np.float32) for s in self._ac_shapes(ac_shape)]
+        self._check(self._lib.ev2g_ppo_get_grads(self._h, ppo, *[a.ctypes.data for a in out]))
+        return out
+
+    def ppo_sync(self, ppo):
+        self._check(self._lib.ev2g_ppo_sync(self._h, ppo))
+
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
         if out is not None:
@@ -831,3 +894,42 @@ def host_gae(reward, values, episode_starts, last_values, last_dones, gamma, gae
     if rc != 0:
         raise EngineError(rc, (load_library().ev2g_last_error(None) or b"").decode())
     return adv, ret
+
+
+def ppo_query(d_in, h1, h2, v1, v2, d_out) -> dict:
+    """The learner's plan of a network (ev2g_ppo_query; host-only): lds_bytes, workspace_bytes, grid_cap, n_params.  EngineError if refused."""
+    L = load_library()
+    info = _abi.PpoInfoC()
+    rc = L.ev2g_ppo_query(int(d_in), int(h1), int(h2), int(v1), int(v2), int(d_out), C.byref(info))
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+    return {k: int(getattr(info, k)) for k, _ in _abi.PpoInfoC._fields_}
+
+
+def host_adam(theta, m, v, g, t, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-5):
+    """Host twin of the learner's Adam (ev2g_host_adam, the device's element function): float32 arrays theta / m / v are updated IN PLACE."""
+    for a in (theta, m, v):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    g = np.ascontiguousarray(g, np.float32)
+    L = load_library()
+    rc = L.ev2g_host_adam(theta.ctypes.data, m.ctypes.data, v.ctypes.data, g.ctypes.data, theta.size, int(t), float(lr), float(beta1), float(beta2),
+                          float(eps))
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+
+
+def host_ppo_head(mean, value, actions, log_std, old_log_prob, advantages, returns, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
+                  normalize_advantage=True):
+    """Host twin of the gradient kernel's head (ev2g_host_ppo_head): (d_mean [B, P], d_value [B], d_log_std [P], stats [6]) float32."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
+    mean, value, actions, log_std, old_log_prob, advantages, returns = map(f, (mean, value, actions, log_std, old_log_prob, advantages, returns))
+    B, P = mean.shape
+    cfg = _abi.PpoConfigC(0.0, 0.9, 0.999, 1e-5, float(clip_range), float(vf_coef), float(ent_coef), 0.5, int(bool(normalize_advantage)))
+    dm, dv, dl, st = np.empty((B, P), np.float32), np.empty(B, np.float32), np.empty(P, np.float32), np.empty(6, np.float32)
+    L = load_library()
+    rc = L.ev2g_host_ppo_head(mean.ctypes.data, value.ctypes.data, actions.ctypes.data, log_std.ctypes.data, old_log_prob.ctypes.data,
+                              advantages.ctypes.data, returns.ctypes.data, B, P, C.byref(cfg), dm.ctypes.data, dv.ctypes.data, dl.ctypes.data,
+                              st.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+    return dm, dv, dl, st

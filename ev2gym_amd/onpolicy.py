@@ -11,7 +11,7 @@ value trunk with a linear value head, one activation, a state-independent log_st
 
 Stable-Baselines3 itself is not a dependency and is not installed where this was written: the state-dict key mapping below follows the parameter
 names SB3 gives `ActorCriticPolicy(net_arch=dict(pi=[h1, h2], vf=[v1, v2]))` and is checked against those names only, not against a live SB3
-policy.  Out of scope: action masks, SAC's squashed Gaussian, recurrent policies, and the learner.
+policy.  Out of scope: action masks, SAC's squashed Gaussian, recurrent policies.  The learner is `ev2gym_amd.ppo.PPOLearner`.
 """
 from __future__ import annotations
 
@@ -162,6 +162,13 @@ class GaussianActorCritic:
         self.weights = fresh.weights
         if self.ac:
             self.engine.ac_set_weights(self.ac, self.weights)
+
+    def get_weights(self):
+        """Refresh `weights` / `log_std` from the device (ev2g_ac_get_weights: a bound learner's masters, else the packed images) and return
+        them; without a device object, the host arrays as they are."""
+        if self.ac:
+            self.weights, self.log_std = self.engine.ac_get_weights(self.ac, (self.d_in, self.h1, self.h2, self.v1, self.v2, self.d_out))
+        return self.weights, self.log_std
 
     def load_state_dict(self, state_dict):
         self.set_weights([state_dict[k] for k in SB3_KEYS])

@@ -1,0 +1,200 @@
+"""The learner of the on-policy collector: SB3's `PPO.train()` with default settings, on the device (`csrc/ev2g_ppo.h`, `ev2g_ppo_*`).
+
+`PPOLearner(collector)` binds a device learner to the collector's `GaussianActorCritic`; `train(batch)` runs n_epochs passes of minibatch
+steps over a `RolloutBatch` -- forward, clipped-surrogate / value / entropy loss, backprop, `clip_grad_norm_`, Adam, and the rewrite of the
+packed weights the collector's launches read -- without the batch or the weights leaving the device; `learn(total_timesteps)` alternates
+`collector.collect()` and `train()`.
+
+`ppo_minibatch_numpy` and `adam_numpy` / `clip_grad_norm_numpy` are float64 restatements of the arithmetic (analytic backprop, no torch): the
+numerics references the tests hold the kernels to.  SB3 is not a dependency; the formulas follow `PPO.train()` for `ActorCriticPolicy` on a
+Box action space:
+
+    lp = sum_p [-(a - mu)^2 / (2 sigma^2) - log_std - log(2 pi) / 2] on the unclipped action,  r = exp(lp - old_lp)
+    A^ = (A - mean(A)) / (std(A) + 1e-8), unbiased std, if normalize_advantage and the minibatch has more than one row
+    loss = -mean(min(A^ r, A^ clip(r, 1 - c, 1 + c))) + ent_coef * (-entropy) + vf_coef * mean((R - v)^2)
+    g <- g * min(1, max_grad_norm / (|g| + 1e-6));  torch.optim.Adam(eps=1e-5), no amsgrad, no weight decay
+
+Out of scope, refused where a caller could ask for them: `clip_range_vf`, `target_kl`, A2C and TRPO, learning-rate schedules as objects (the
+rate is settable between calls: `set_rates`), action masks, orthogonal initialisation (weights arrive from the caller).
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _abi
+from .onpolicy import SB3_KEYS, SB3_LOG_STD
+
+STAT_NAMES = _abi.PPO_STATS
+_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+
+
+def ppo_minibatch_numpy(weights, log_std, obs, actions, old_log_prob, advantages, returns, idx, activation="tanh", clip_range=0.2, vf_coef=0.5,
+                        ent_coef=0.0, normalize_advantage=True):
+    """One minibatch of PPO's loss in float64 with analytic backprop.  weights: the twelve arrays of GaussianActorCritic's order; idx: the rows
+    of the flattened rollout.  Returns (grads, stats, aux): the thirteen gradients (the twelve arrays' order, then log_std), the six statistics
+    (STAT_NAMES' order) and a dict of intermediates (lp, ratio, adv, mean, value, the pre-activations z) for the tests' branch checks."""
+    w = [np.asarray(a, np.float64) for a in weights]
+    ls = np.asarray(log_std, np.float64)
+    idx = np.asarray(idx, np.int64)
+    x, a = np.asarray(obs, np.float64)[idx], np.asarray(actions, np.float64)[idx]
+    old, A, R = (np.asarray(v, np.float64)[idx] for v in (old_log_prob, advantages, returns))
+    B, c = len(idx), float(clip_range)
+    tanh = activation == "tanh"
+    act = np.tanh if tanh else (lambda z: np.maximum(z, 0.0))
+    dact = (lambda h: 1.0 - h * h) if tanh else (lambda h: (h > 0.0).astype(np.float64))
+    z1 = x @ w[0].T + w[1]; h1 = act(z1)
+    z2 = h1 @ w[2].T + w[3]; h2 = act(z2)
+    y1 = x @ w[4].T + w[5]; v1 = act(y1)
+    y2 = v1 @ w[6].T + w[7]; v2 = act(y2)
+    mu = h2 @ w[8].T + w[9]
+    v = (v2 @ w[10].T + w[11])[:, 0]
+    iv = np.exp(-2.0 * ls)
+    d = a - mu
+    lp = (-(d * d) * (0.5 * iv) - ls - _HALF_LOG_2PI).sum(axis=1)
+    if normalize_advantage and B > 1:
+        A = (A - A.mean()) / (A.std(ddof=1) + 1e-8)
+    lr = lp - old
+    r = np.exp(lr)
+    s1, s2 = A * r, A * np.clip(r, 1.0 - c, 1.0 + c)
+    entropy = (0.5 + _HALF_LOG_2PI + ls).sum()
+    pl, vl, el = -np.minimum(s1, s2).mean(), ((R - v) ** 2).mean(), -entropy
+    stats = np.array([pl, vl, el, pl + ent_coef * el + vf_coef * vl, ((r - 1.0) - lr).mean(), (np.abs(r - 1.0) > c).mean()])
+    open_ = ((A >= 0.0) & (r <= 1.0 + c)) | ((A < 0.0) & (r >= 1.0 - c))
+    g_lp = np.where(open_, -A * r / B, 0.0)
+    g_v = 2.0 * vf_coef * (v - R) / B
+    d_mu = g_lp[:, None] * d * iv
+    d_ls = (g_lp[:, None] * (d * d * iv - 1.0)).sum(axis=0) - ent_coef
+    d2 = (d_mu @ w[8]) * dact(h2)
+    d1 = (d2 @ w[2]) * dact(h1)
+    e2 = (g_v[:, None] * w[10]) * dact(v2)
+    e1 = (e2 @ w[6]) * dact(v1)
+    grads = [d1.T @ x, d1.sum(0), d2.T @ h1, d2.sum(0), e1.T @ x, e1.sum(0), e2.T @ v1, e2.sum(0), d_mu.T @ h2, d_mu.sum(0),
+             (g_v[:, None] * v2).sum(0)[None, :], np.array([g_v.sum()]), d_ls]
+    aux = dict(lp=lp, ratio=r, adv=A, mean=mu, value=v, z=(z1, z2, y1, y2), open=open_, d_mean=d_mu, d_value=g_v)
+    return grads, stats, aux
+
+
+def clip_grad_norm_numpy(grads, max_grad_norm):
+    """torch.nn.utils.clip_grad_norm_ in float64: (the scaled gradients, the norm before scaling)."""
+    norm = math.sqrt(sum(float((np.asarray(g, np.float64) ** 2).sum()) for g in grads))
+    coef = min(1.0, float(max_grad_norm) / (norm + 1e-6))
+    return [np.asarray(g, np.float64) * coef for g in grads], norm
+
+
+def adam_numpy(theta, m, v, g, t, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-5):
+    """One step of torch.optim.Adam (no amsgrad, no weight decay) in float64 at step count t >= 1: (theta, m, v) as new arrays."""
+    theta, m, v, g = (np.asarray(a, np.float64) for a in (theta, m, v, g))
+    m = beta1 * m + (1.0 - beta1) * g
+    v = beta2 * v + (1.0 - beta2) * g * g
+    step = lr / (1.0 - beta1 ** t)
+    return theta - step * m / (np.sqrt(v) / math.sqrt(1.0 - beta2 ** t) + eps), m, v
+
+
+def check_batch(policy, batch):
+    """The row count of a RolloutBatch (its arrays flattened to [n_steps * E, ...]); ValueError unless widths and row counts fit `policy`."""
+    if getattr(batch, "use_masks", False):
+        raise ValueError("PPOLearner.train: action masks are out of scope (the batch's action_masks are not read)")
+    obs, actions = batch["observations"], batch["actions"]
+    if obs.shape[-1] != policy.d_in or actions.shape[-1] != policy.d_out:
+        raise ValueError(f"PPOLearner.train: the batch has rows {obs.shape[-1]} -> {actions.shape[-1]}, the policy maps {policy.d_in} -> {policy.d_out}")
+    N = obs.numel() // policy.d_in
+    if N < 1 or actions.numel() != N * policy.d_out or any(batch[k].numel() != N for k in ("log_probs", "advantages", "returns")):
+        raise ValueError(f"PPOLearner.train: the batch's arrays do not all have {N} rows")
+    return N
+
+
+class PPOLearner:
+    """SB3's PPO.train() on the device for an OnPolicyCollector's GaussianActorCritic.
+
+    The learner takes the policy's current weights as float32 masters on the device.  While it lives, `policy.set_weights` / `set_log_std`
+    also reset the masters (Adam's moments and step count are kept); `state_dict()` reads them back.  `close()` (or closing the policy or the
+    engine) frees it."""
+
+    def __init__(self, collector, lr=3e-4, n_epochs=10, batch_size=64, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                 normalize_advantage=True, seed=0, **unsupported):
+        for k, v in unsupported.items():
+            if k in ("clip_range_vf", "target_kl") and v is None:
+                continue
+            raise ValueError(f"PPOLearner: {k} is not supported (clip_range_vf, target_kl, schedules as objects, action masks and orthogonal "
+                             "initialisation are out of scope; see the module docstring)")
+        if callable(lr) or callable(clip_range):
+            raise ValueError("PPOLearner: lr and clip_range are numbers; drive a schedule with set_rates() between train() calls")
+        if int(batch_size) < 1:
+            raise ValueError(f"PPOLearner: batch_size {batch_size} must be at least 1")
+        if int(n_epochs) < 1:
+            raise ValueError(f"PPOLearner: n_epochs {n_epochs} must be at least 1")
+        import torch
+        self.torch = torch
+        self.collector, self.policy, self.eng = collector, collector.policy, collector.eng
+        self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
+        self.lr, self.clip_range = float(lr), float(clip_range)
+        self.device = torch.device("cuda", self.eng.device)
+        self.generator = torch.Generator(device=self.device)
+        self.generator.manual_seed(int(seed))
+        self.ppo = self.eng.ppo_create(self.policy.ac, lr=lr, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm,
+                                       normalize_advantage=normalize_advantage)
+        self.num_timesteps = 0
+
+    def set_rates(self, lr=None, clip_range=None):
+        """The learning rate and the clip range of the following minibatches (how a schedule is driven from Python)."""
+        self.lr = self.lr if lr is None else float(lr)
+        self.clip_range = self.clip_range if clip_range is None else float(clip_range)
+        self.eng.ppo_set_rates(self.ppo, self.lr, self.clip_range)
+
+    def _flat(self, batch):
+        p, t = self.policy, self.torch
+        N = check_batch(p, batch)
+        f = lambda a, *shape: a.to(device=self.device, dtype=t.float32).contiguous().view(N, *shape)  # noqa: E731
+        return (N, f(batch["observations"], p.d_in), f(batch["actions"], p.d_out), f(batch["log_probs"]), f(batch["advantages"]),
+                f(batch["returns"]))
+
+    def train(self, batch, minibatches=None):
+        """n_epochs passes over the RolloutBatch `batch` (minibatches=None: each pass a fresh device permutation from the seeded generator cut
+        into batch_size pieces, the shorter last piece included, as SB3 does), or exactly the minibatches of the iterable `minibatches` (index
+        tensors or arrays into the flattened [n_steps * E] rows).  Returns the means over the minibatches of the six statistics."""
+        t, eng = self.torch, self.eng
+        N, obs, actions, old_lp, adv, ret = self._flat(batch)
+        if minibatches is None:
+            pieces = []
+            for _ in range(self.n_epochs):
+                perm = t.randperm(N, generator=self.generator, device=self.device).to(t.int32)
+                pieces += [perm[i:i + self.batch_size] for i in range(0, N, self.batch_size)]
+        else:
+            pieces = [t.as_tensor(ix).to(device=self.device, dtype=t.int32).contiguous() for ix in minibatches]
+            if not pieces or any(ix.ndim != 1 or ix.numel() < 1 for ix in pieces):
+                raise ValueError("PPOLearner.train: every minibatch must be a non-empty 1-d index array")
+            every = t.cat(pieces)
+            if int(every.min()) < 0 or int(every.max()) >= N:
+                raise ValueError(f"PPOLearner.train: a minibatch index is outside the batch's {N} rows")
+        stats = t.zeros((len(pieces), 6), dtype=t.float32, device=self.device)
+        t.cuda.synchronize(self.device)   # the engine works on its own stream
+        for k, ix in enumerate(pieces):
+            eng.ppo_minibatch(self.ppo, obs, actions, old_lp, adv, ret, ix, ix.numel(), stats[k])
+        eng.ppo_sync(self.ppo)            # (synchronises; the policy samples from the new log_std afterwards)
+        self.last_stats = stats.cpu().numpy()
+        return dict(zip(STAT_NAMES, (float(v) for v in self.last_stats.astype(np.float64).mean(axis=0))))
+
+    def learn(self, total_timesteps):
+        """collect() and train() in turn until total_timesteps env steps were collected; returns the statistics of every train()."""
+        out = []
+        target = self.num_timesteps + int(total_timesteps)
+        while self.num_timesteps < target:
+            batch = self.collector.collect()
+            self.num_timesteps += self.collector.n_steps * self.eng.E
+            out.append(self.train(batch))
+        return out
+
+    def state_dict(self):
+        """The policy's parameters read back from the device (GaussianActorCritic.weights / log_std are refreshed), under SB3's keys."""
+        self.policy.get_weights()
+        return self.policy.state_dict()
+
+    def close(self):
+        if self.ppo:
+            self.eng.ppo_destroy(self.ppo)
+        self.ppo = None
+
+
+__all__ = ["PPOLearner", "ppo_minibatch_numpy", "adam_numpy", "clip_grad_norm_numpy", "check_batch", "STAT_NAMES", "SB3_KEYS", "SB3_LOG_STD"]

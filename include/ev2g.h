@@ -712,6 +712,68 @@ int ev2g_gae(ev2g_handle *h, const double *reward, const float *values, const ui
 int ev2g_host_gae(const double *reward, const float *values, const uint8_t *episode_starts, const float *last_values, const uint8_t *last_dones,
                   int k, int n_envs, double gamma, double lambda, float *advantages, float *returns);
 
+/* ---- the PPO learner of a Gaussian actor-critic (csrc/ev2g_ppo.h) ----------------------------
+ * SB3's PPO.train() with default settings for ActorCriticPolicy on a Box action space, one minibatch per call, on the device: the forward with
+ * every activation kept, the clipped-surrogate / value / entropy loss, backprop, clip_grad_norm_, torch.optim.Adam on float32 masters in SB3's
+ * [out, in] layout, and the rewrite of the packed weight images the policy object's launches read.  float32 throughout, matrix products on the
+ * exact-f32 MFMA.  No float atomics: the same call on the same state gives the same bits.
+ *   lp_i = sum_p [ -(a - mu)^2 / (2 sigma^2) - log_std_p - log(2 pi) / 2 ] on the UNCLIPPED action;  r = exp(lp - old_lp)
+ *   A^ = (A - mean(A)) / (std(A) + 1e-8) with the unbiased std, when normalize_advantage is set and B > 1, else A
+ *   loss = -mean(min(A^ r, A^ clip(r, 1 - c, 1 + c))) + ent_coef * (-entropy) + vf_coef * mean((R - v)^2)
+ *   statistics [6]: policy_loss, value_loss, entropy_loss, loss, approx_kl = mean((r - 1) - log r), clip_fraction = mean(|r - 1| > c)
+ * Not reproduced (there is nothing to ask them with): clip_range_vf, target_kl, A2C / TRPO, schedule objects (ev2g_ppo_set_rates between calls
+ * drives one), action masks, orthogonal initialisation.
+ * LIMITS: every network with d_in <= 192, d_out <= 64 and hidden widths <= 64 is accepted, wider ones as far as the gradient kernel's LDS plan
+ * fits the CU's 160 KiB (ev2g_ppo_query tells); anything else is EV2G_ERR_ARG at create with a message naming the width. */
+typedef struct ev2g_ppo ev2g_ppo;
+typedef struct ev2g_ppo_config {
+    double lr, beta1, beta2, adam_eps;   /* SB3's PPO: 3e-4, 0.9, 0.999, 1e-5.  lr >= 0, betas in [0, 1), adam_eps > 0 */
+    double clip_range, vf_coef, ent_coef, max_grad_norm;   /* 0.2, 0.5, 0.0, 0.5.  clip_range > 0, coefficients >= 0, max_grad_norm > 0 */
+    int32_t normalize_advantage;         /* 1 */
+} ev2g_ppo_config;
+typedef struct ev2g_ppo_info {
+    int64_t lds_bytes, workspace_bytes;  /* the gradient kernel's dynamic LDS; the per-workgroup partial sums */
+    int32_t grid_cap, n_params;          /* workgroups of the gradient kernel at most; elements of the thirteen arrays */
+} ev2g_ppo_info;
+/* Host-only (no GPU, no handle): the plan of a network's learner, or EV2G_ERR_ARG (ev2g_last_error(NULL) names the width). */
+int ev2g_ppo_query(int d_in, int h1, int h2, int v1, int v2, int d_out, ev2g_ppo_info *info);
+/* A learner bound to `ac` (created on `h`, one learner per policy: EV2G_ERR_STATE for a second), owned by the handle; the policy's current
+ * weights and log_std become the masters, Adam's state starts at zero.  EV2G_ERR_ARG: a non-finite or out-of-range config value, a network the
+ * plan refuses.  Destroying the policy destroys its learner.  While a learner is bound, ev2g_ac_set_weights / ev2g_ac_set_log_std also reset the
+ * masters; Adam's m, v and step count are kept. */
+int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cfg, ev2g_ppo **out);
+void ev2g_ppo_destroy(ev2g_handle *h, ev2g_ppo *ppo);
+int ev2g_ppo_set_rates(ev2g_handle *h, ev2g_ppo *ppo, double lr, double clip_range);
+/* The gradient of one minibatch: rows idx[0 .. B) (int32, duplicates allowed, each inside the arrays) of obs [N, d_in], actions [N, d_out]
+ * (unclipped), old_log_prob / advantages / returns [N]; all DEVICE, float32.  stats float32 [6] DEVICE, may be NULL.  The gradient stays in the
+ * learner (unclipped).  Asynchronous on the handle's stream. */
+int ev2g_ppo_grad(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
+                  const float *returns, const int32_t *idx, int B, float *stats);
+/* clip_grad_norm_, Adam, repack: consumes the gradient of the last ev2g_ppo_grad (EV2G_ERR_STATE without one).  The policy's derived sigma is
+ * NOT refreshed (ev2g_ppo_sync does that); the learner itself reads the master log_std. */
+int ev2g_ppo_apply(ev2g_handle *h, ev2g_ppo *ppo);
+/* ev2g_ppo_grad then ev2g_ppo_apply, no host round trip. */
+int ev2g_ppo_minibatch(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
+                       const float *returns, const int32_t *idx, int B, float *stats);
+/* The last gradient, unclipped, SB3's layout, into thirteen HOST arrays (the twelve of ev2g_ac_create's order, then log_std).  Synchronises. */
+int ev2g_ppo_get_grads(ev2g_handle *h, ev2g_ppo *ppo, float *pi_W1, float *pi_b1, float *pi_W2, float *pi_b2, float *vf_W1, float *vf_b1,
+                       float *vf_W2, float *vf_b2, float *action_W, float *action_b, float *value_W, float *value_b, float *log_std);
+/* Synchronises, reads the master log_std back and re-derives the policy's sampling constants through ev2g_ac_set_log_std's path: afterwards the
+ * policy samples exactly as a fresh one created from the same numbers.  Once per train(). */
+int ev2g_ppo_sync(ev2g_handle *h, ev2g_ppo *ppo);
+/* The policy's weights into twelve HOST arrays and log_std [d_out]: the masters when a learner is bound, else the packed images unpacked (and the
+ * log_std last set).  Synchronises. */
+int ev2g_ac_get_weights(ev2g_handle *h, ev2g_acpolicy *ac, float *pi_W1, float *pi_b1, float *pi_W2, float *pi_b2, float *vf_W1, float *vf_b1,
+                        float *vf_W2, float *vf_b2, float *action_W, float *action_b, float *value_W, float *value_b, float *log_std);
+/* Host twins (the device's element functions compiled for the host).  ev2g_host_adam: n elements of theta / m / v updated by gradient g at
+ * step count t >= 1 (torch.optim.Adam, no amsgrad, no weight decay). */
+int ev2g_host_adam(float *theta, float *m, float *v, const float *g, int64_t n, int64_t t, double lr, double beta1, double beta2, double eps);
+/* ev2g_host_ppo_head: one minibatch's head gradients d loss / d mean [B, P], d loss / d value [B], d loss / d log_std [P] (entropy term included)
+ * and the six statistics, from given mean [B, P], value [B], actions [B, P], log_std [P], old_log_prob / advantages / returns [B]. */
+int ev2g_host_ppo_head(const float *mean, const float *value, const float *actions, const float *log_std, const float *old_log_prob,
+                       const float *advantages, const float *returns, int B, int P, const ev2g_ppo_config *cfg, float *d_mean, float *d_value,
+                       float *d_log_std, float *stats);
+
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
 void ev2g_free(ev2g_handle *h, void *p);
