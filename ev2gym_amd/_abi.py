@@ -117,7 +117,22 @@ class OnPolicyRowsC(C.Structure):   # ev2g_onpolicy_rows: the device arrays of a
 
 
 AC_ACTIVATIONS = {"tanh": 0, "relu": 1}   # EV2G_AC_TANH (SB3's default activation_fn) / EV2G_AC_RELU
-AC_MAX_IN, AC_MAX_HIDDEN, AC_MAX_OUT = 192, 256, 64   # the limits of ev2g_ac_create
+AC_MAX_IN, AC_MAX_HIDDEN, AC_MAX_OUT = 192, 256, 64   # the limits of ev2g_ac_create (EV2G_AC_MAX_*, csrc/ev2g_policy_host.h)
+# The network's thirteen parameter arrays in the order of the ABI's argument lists (ac_params, csrc/ev2g_policy_host.h): the policy trunk, the
+# value trunk, the action head, the value head -- weights [out, in] as torch.nn.Linear keeps them -- then log_std.
+AC_PARAMS = ("pi_W1", "pi_b1", "pi_W2", "pi_b2", "vf_W1", "vf_b1", "vf_W2", "vf_b2", "action_W", "action_b", "value_W", "value_b", "log_std")
+
+
+def ac_param_shapes(d_in, h1, h2, v1, v2, d_out):
+    """The thirteen shapes, in AC_PARAMS' order."""
+    return ((h1, d_in), (h1,), (h2, h1), (h2,), (v1, d_in), (v1,), (v2, v1), (v2,), (d_out, h2), (d_out,), (1, v2), (1,), (d_out,))
+
+
+def ac_widths(weights):
+    """(d_in, h1, h2, v1, v2, d_out) as the leading arrays of AC_PARAMS' order say them (the shapes are checked by GaussianActorCritic)."""
+    shape = dict(zip(AC_PARAMS, (a.shape for a in weights)))
+    (h1, d_in), v1 = shape["pi_W1"], shape["vf_W1"][0]
+    return d_in, h1, shape["pi_W2"][0], v1, shape["vf_W2"][0], shape["action_W"][0]
 
 
 class PpoConfigC(C.Structure):   # ev2g_ppo_config, in header order

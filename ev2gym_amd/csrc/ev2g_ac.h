@@ -21,12 +21,10 @@
 // generator's own log / cos (ev2g_gen.h: fixed sequences of IEEE operations), so host (ev2g_ac_host_normal) and device give the same bits.
 // Element (row e, port p) of the object's n-th sampling launch over E rows draws index (n E + e) P + p.
 #pragma once
+#include "ev2g_policy_host.h"   // EV2G_AC_MAX_IN / _HIDDEN / _OUT: the limits plan_ac refuses by
 
 #define EV2G_AC_ROWS 32
 #define EV2G_AC_BLOCK 256
-#define EV2G_AC_MAX_IN 192
-#define EV2G_AC_MAX_HIDDEN 256
-#define EV2G_AC_MAX_OUT 64
 #define EV2G_AC_DEPTH 8   // weight groups in flight per tile
 
 struct AcDev {

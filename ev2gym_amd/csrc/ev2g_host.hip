@@ -415,6 +415,45 @@ static std::array<FusedEntry, sizeof...(I)> fused_table(std::index_sequence<I...
 static constexpr std::array<WaveLaunch, ROUTE_WAVE_ENTRIES> kWaveTable = wave_table(std::make_index_sequence<ROUTE_WAVE_ENTRIES>{});
 static const std::array<FusedEntry, ROUTE_FUSED_ENTRIES> kFusedTable = fused_table(std::make_index_sequence<ROUTE_FUSED_ENTRIES>{});
 
+// ev2g_ac_act_kernel<activation>: the kernel (ev2g_ac_create sets its dynamic-LDS attribute) and its launch
+struct AcEntry {
+    const void *fn;
+    void (*launch)(const LaunchDims &, const AcDev &, const float *x, int n_rows, int sample, uint64_t seed, uint64_t draw0, float *mean, float *actions,
+                   float *clipped, float *value, float *log_prob);
+};
+template <int ACT>
+static void launch_ac(const LaunchDims &d, const AcDev &dev, const float *x, int n_rows, int sample, uint64_t seed, uint64_t draw0, float *mean,
+                      float *actions, float *clipped, float *value, float *log_prob) {
+    hipLaunchKernelGGL(ev2g_ac_act_kernel<ACT>, d.grid, dim3(EV2G_AC_BLOCK), d.lds, d.stream, dev, x, n_rows, sample, seed, draw0, mean, actions, clipped,
+                       value, log_prob);
+}
+template <int ACT>
+static AcEntry ac_entry() { return {(const void *)ev2g_ac_act_kernel<ACT>, &launch_ac<ACT>}; }
+static const AcEntry &ac_kernel(int relu) {
+    static const AcEntry tab[2] = {ac_entry<EV2G_AC_TANH>(), ac_entry<EV2G_AC_RELU>()};
+    return tab[relu ? 1 : 0];
+}
+
+// ev2g_ppo_grad_kernel<activation>: the kernel (ev2g_ppo_create sets its dynamic-LDS attribute) and its launch
+struct PpoGradEntry {
+    const void *fn;
+    void (*launch)(const LaunchDims &, const AcDev &, const PpoDev &, const PpoLds &, const PpoHyper &, const float *obs, const float *actions,
+                   const float *old_lp, const float *adv, const float *ret, const int *idx, int B, const double *advstat, float *work, double *stat_part);
+};
+template <int ACT>
+static void launch_ppo_grad(const LaunchDims &d, const AcDev &ac, const PpoDev &dev, const PpoLds &lds, const PpoHyper &hp, const float *obs,
+                            const float *actions, const float *old_lp, const float *adv, const float *ret, const int *idx, int B, const double *advstat,
+                            float *work, double *stat_part) {
+    hipLaunchKernelGGL(ev2g_ppo_grad_kernel<ACT>, d.grid, dim3(EV2G_PPO_BLOCK), d.lds, d.stream, ac, dev, lds, hp, obs, actions, old_lp, adv, ret, idx, B, advstat,
+                       work, stat_part);
+}
+template <int ACT>
+static PpoGradEntry ppo_grad_entry() { return {(const void *)ev2g_ppo_grad_kernel<ACT>, &launch_ppo_grad<ACT>}; }
+static const PpoGradEntry &ppo_grad_kernel(int relu) {
+    static const PpoGradEntry tab[2] = {ppo_grad_entry<EV2G_AC_TANH>(), ppo_grad_entry<EV2G_AC_RELU>()};
+    return tab[relu ? 1 : 0];
+}
+
 #include "ev2g_refill_host.h"
 
 extern "C" {
@@ -2106,7 +2145,7 @@ int ev2g_wrap_rollout(ev2g_handle *h, ev2g_wrap *w, const ev2g_mlp *m, int k_ste
 }
 
 // ---- the Gaussian actor-critic and GAE (ev2g_ac.h) ----
-// the twelve device arrays in the order of ac_array_sizes / pack_ac (ev2g_policy_host.h)
+// AcDev's twelve image pointers under their AcSlot: the order of ac_array_sizes / pack_ac (ev2g_policy_host.h)
 static std::array<const float **, AC_ARRAYS> ac_arrays(AcDev &d) {
     return {&d.w1, &d.b1, &d.w2, &d.b2, &d.w3, &d.b3, &d.u1, &d.c1, &d.u2, &d.c2, &d.u3, &d.c3};
 }
@@ -2149,24 +2188,50 @@ static int ac_upload_log_std(ev2g_handle *h, ev2g_acpolicy *ac, const float *log
     return EV2G_OK;
 }
 
+static void ppo_launch_repack(ev2g_handle *h, ev2g_ppo *p, bool transposed_only) {
+    hipLaunchKernelGGL(ev2g_ppo_repack_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->theta, transposed_only ? 1 : 0);
+}
+
 // a bound learner's masters (and its transposed images) follow ev2g_ac_set_weights / ev2g_ac_set_log_std; Adam's state is kept
 static int ppo_reset_masters(ev2g_handle *h, ev2g_ppo *p, const AcWeights *w, const float *log_std) {
     const PpoPlan &pl = p->plan;
+    auto master = [&](int i, const float *src) {
+        return hipMemcpyAsync(p->theta + pl.off[i], src, (size_t)(pl.off[i + 1] - pl.off[i]) * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    };
     if (w) {
-        const float *src[AC_ARRAYS] = {w->pW1, w->pb1, w->pW2, w->pb2, w->vW1, w->vb1, w->vW2, w->vb2, w->aW, w->ab, w->cW, w->cb};
-        for (int i = 0; i < AC_ARRAYS; i++)
-            HIPCHK(h, hipMemcpyAsync(p->theta + pl.off[i], src[i], (size_t)(pl.off[i + 1] - pl.off[i]) * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(ev2g_ppo_repack_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->theta, 1);
+        for (int i = 0; i < AC_ARRAYS; i++) HIPCHK(h, master(i, w->a[i]));
+        ppo_launch_repack(h, p, true);
         HIPCHK(h, hipGetLastError());
     }
-    if (log_std)
-        HIPCHK(h, hipMemcpyAsync(p->theta + pl.off[12], log_std, (size_t)(pl.off[13] - pl.off[12]) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (log_std) HIPCHK(h, master(AC_ARRAYS, log_std));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // the sources are the caller's
     return EV2G_OK;
 }
 
 static bool ac_weights_null(const AcWeights &w) {
-    return !w.pW1 || !w.pb1 || !w.pW2 || !w.pb2 || !w.vW1 || !w.vb1 || !w.vW2 || !w.vb2 || !w.aW || !w.ab || !w.cW || !w.cb;
+    for (const float *a : w.a)
+        if (!a) return true;
+    return false;
+}
+
+// the device stage of an actor-critic: allocates the twelve images and the log_std arrays, uploads them and sets the kernel's dynamic-LDS attribute
+static int ac_device_stage(ev2g_handle *h, ev2g_acpolicy *ac, const AcWeights &w, const float *log_std) {
+    AcDev &d = ac->dev;
+    const auto sizes = ac_array_sizes(ac->plan);
+    const auto arrays = ac_arrays(d);
+    for (size_t i = 0; i < AC_ARRAYS; i++)
+        if (int rc = dalloc(h, ac->allocs, sizes[i], arrays[i])) return rc;
+    if (int rc = dalloc(h, ac->allocs, (size_t)d.d_out, &d.sigma)) return rc;
+    for (const double **dst : {&d.lp_a, &d.lp_c})
+        if (int rc = dalloc(h, ac->allocs, (size_t)d.d_out, dst)) return rc;
+    if (int rc = ac_upload_weights(h, ac, w)) return rc;
+    if (int rc = ac_upload_log_std(h, ac, log_std, "ev2g_ac_create")) return rc;
+    if (ac->lds > 48 * 1024 && !(h->ac_attr_mask & (1u << ac->relu))) {   // (function attributes are per device: once per handle)
+        const hipError_t e = hipFuncSetAttribute(ac_kernel(ac->relu).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev2g_ac_lds_max());
+        if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string("ev2g_ac_create: hipFuncSetAttribute: ") + hipGetErrorString(e));
+        h->ac_attr_mask |= 1u << ac->relu;
+    }
+    return EV2G_OK;
 }
 
 int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int d_out, int activation, const float *pi_W1, const float *pi_b1,
@@ -2175,23 +2240,17 @@ int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int
                    uint64_t seed, ev2g_acpolicy **out) {
     if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: null argument");
     *out = nullptr;
-    const AcWeights w{pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b};
+    const AcWeights w{{pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b}};
     if (ac_weights_null(w) || !log_std) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: a weight, bias or log_std pointer is null");
-    if (d_in < 1 || d_in > EV2G_AC_MAX_IN) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: d_in must be 1 .. " + std::to_string(EV2G_AC_MAX_IN));
-    const int hid[4] = {h1, h2, v1, v2};
-    const char *hid_name[4] = {"h1", "h2", "v1", "v2"};
-    for (int i = 0; i < 4; i++)
-        if (hid[i] < 1 || hid[i] > EV2G_AC_MAX_HIDDEN)
-            return fail(h, EV2G_ERR_ARG, std::string("ev2g_ac_create: ") + hid_name[i] + " must be 1 .. " + std::to_string(EV2G_AC_MAX_HIDDEN));
-    if (d_out < 1 || d_out > EV2G_AC_MAX_OUT) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: d_out must be 1 .. " + std::to_string(EV2G_AC_MAX_OUT));
+    const AcPlan p = plan_ac(d_in, h1, h2, v1, v2, d_out);
+    if (p.err) return fail(h, p.err, p.refusal);
     if (activation != EV2G_AC_TANH && activation != EV2G_AC_RELU) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: activation must be EV2G_AC_TANH or EV2G_AC_RELU");
     if (lo != -1.0f && lo != 0.0f) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: lo must be -1 or 0");
-    for (int p = 0; p < d_out; p++)
-        if (!std::isfinite(log_std[p])) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: log_std[" + std::to_string(p) + "] is not finite");
+    for (int i = 0; i < d_out; i++)
+        if (!std::isfinite(log_std[i])) return fail(h, EV2G_ERR_ARG, "ev2g_ac_create: log_std[" + std::to_string(i) + "] is not finite");
     (void)hipSetDevice(h->device);
     ev2g_acpolicy *ac = new ev2g_acpolicy();
-    ac->plan = plan_ac(d_in, h1, h2, v1, v2, d_out);
-    const AcPlan &p = ac->plan;
+    ac->plan = p;
     AcDev &d = ac->dev;
     d.d_in = d_in; d.h1 = h1; d.h2 = h2; d.v1 = v1; d.v2 = v2; d.d_out = d_out;
     d.k1 = p.k1; d.n1 = p.n1; d.n2 = p.n2; d.m1 = p.m1; d.m2 = p.m2; d.n3 = p.n3;
@@ -2199,31 +2258,15 @@ int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int
     ac->relu = activation == EV2G_AC_RELU;
     ac->seed = seed; ac->n = 0;
     ac->lds = ev2g_ac_lds(d).bytes;
-    int rc = 0;
-    float *f = nullptr;
-    double *g = nullptr;
-    auto fa = [&](size_t n, const float **dst) { rc = dalloc(h, ac->allocs, n, &f); *dst = f; return rc; };
-    auto da = [&](size_t n, const double **dst) { rc = dalloc(h, ac->allocs, n, &g); *dst = g; return rc; };
-    const auto sizes = ac_array_sizes(p);
-    const auto arrays = ac_arrays(d);
-    for (int i = 0; i < AC_ARRAYS && !rc; i++) fa(sizes[(size_t)i], arrays[(size_t)i]);
-    if (rc || fa(d_out, &d.sigma) || da(d_out, &d.lp_a) || da(d_out, &d.lp_c) || (rc = ac_upload_weights(h, ac, w)) ||
-        (rc = ac_upload_log_std(h, ac, log_std, "ev2g_ac_create"))) {
+    if (const int rc = ac_device_stage(h, ac, w, log_std)) {   // the one cleanup path
         ac_free(ac);
         return rc;
-    }
-    if (ac->lds > 48 * 1024 && !(h->ac_attr_mask & (1u << ac->relu))) {   // (function attributes are per device: once per handle)
-        const void *fn = ac->relu ? (const void *)ev2g_ac_act_kernel<EV2G_AC_RELU> : (const void *)ev2g_ac_act_kernel<EV2G_AC_TANH>;
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev2g_ac_lds_max());
-        if (e != hipSuccess) { ac_free(ac); return fail(h, EV2G_ERR_HIP, std::string("ev2g_ac_create: hipFuncSetAttribute: ") + hipGetErrorString(e)); }
-        h->ac_attr_mask |= 1u << ac->relu;
     }
     h->acs.push_back(ac);
     *out = ac;
     return EV2G_OK;
 }
 
-static void ppo_free(ev2g_ppo *p);
 // (a bound learner goes with its policy)
 void ev2g_ac_destroy(ev2g_handle *h, ev2g_acpolicy *ac) {
     if (h && ac && std::find(h->acs.begin(), h->acs.end(), ac) != h->acs.end() && ac->learner) owned_destroy(h, &ev2g_handle::ppos, ac->learner, ppo_free);
@@ -2250,7 +2293,7 @@ int ev2g_ac_set_weights(ev2g_handle *h, ev2g_acpolicy *ac, const float *pi_W1, c
                         const float *vf_W1, const float *vf_b1, const float *vf_W2, const float *vf_b2, const float *action_W,
                         const float *action_b, const float *value_W, const float *value_b) {
     if (int rc = ac_check(h, ac, "ev2g_ac_set_weights")) return rc;
-    const AcWeights w{pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b};
+    const AcWeights w{{pi_W1, pi_b1, pi_W2, pi_b2, vf_W1, vf_b1, vf_W2, vf_b2, action_W, action_b, value_W, value_b}};
     if (ac_weights_null(w)) return fail(h, EV2G_ERR_ARG, "ev2g_ac_set_weights: a weight or bias pointer is null");
     if (int rc = ac_upload_weights(h, ac, w)) return rc;   // (stream-ordered behind the launches that read the old weights)
     return ac->learner ? ppo_reset_masters(h, ac->learner, &w, nullptr) : EV2G_OK;
@@ -2259,14 +2302,9 @@ int ev2g_ac_set_weights(ev2g_handle *h, ev2g_acpolicy *ac, const float *pi_W1, c
 // one launch of ev2g_ac_act_kernel over n_rows rows; a sampling launch takes the object's counter and advances it
 static int ac_launch(ev2g_handle *h, ev2g_acpolicy *ac, const float *x, int n_rows, bool sample, float *mean, float *actions, float *clipped,
                      float *value, float *log_prob) {
-    const dim3 grid((unsigned)((n_rows + EV2G_AC_ROWS - 1) / EV2G_AC_ROWS)), block(EV2G_AC_BLOCK);
-    const uint64_t draw0 = (uint64_t)ac->n * (uint64_t)n_rows;
-    if (ac->relu)
-        hipLaunchKernelGGL(ev2g_ac_act_kernel<EV2G_AC_RELU>, grid, block, ac->lds, h->stream, ac->dev, x, n_rows, sample ? 1 : 0, (uint64_t)ac->seed, draw0,
-                           mean, actions, clipped, value, log_prob);
-    else
-        hipLaunchKernelGGL(ev2g_ac_act_kernel<EV2G_AC_TANH>, grid, block, ac->lds, h->stream, ac->dev, x, n_rows, sample ? 1 : 0, (uint64_t)ac->seed, draw0,
-                           mean, actions, clipped, value, log_prob);
+    const LaunchDims dims{dim3((unsigned)((n_rows + EV2G_AC_ROWS - 1) / EV2G_AC_ROWS)), ac->lds, h->stream};
+    ac_kernel(ac->relu).launch(dims, ac->dev, x, n_rows, sample ? 1 : 0, (uint64_t)ac->seed, (uint64_t)ac->n * (uint64_t)n_rows, mean, actions, clipped, value,
+                               log_prob);
     HIPCHK(h, hipGetLastError());
     if (sample) ac->n += 1;
     return EV2G_OK;
@@ -2374,32 +2412,59 @@ static int ppo_config_check(ev2g_handle *h, const char *who, double lr, double c
     return EV2G_OK;
 }
 
-// the twelve arrays of a policy in SB3's layout from its packed images (out[i]: n_params-ordered host pointers)
+// the twelve arrays of a policy in SB3's layout from its packed images (out[i]: host pointers in the table's order)
 static int ac_read_images(ev2g_handle *h, ev2g_acpolicy *ac, float *const out[AC_ARRAYS]) {
-    const AcPlan &a = ac->plan;
-    const auto sizes = ac_array_sizes(a);
-    const AcDev &d = ac->dev;
-    // AcWeights' order <- the device arrays of AcDev
-    const float *src[AC_ARRAYS] = {d.w1, d.b1, d.w2, d.b2, d.u1, d.c1, d.u2, d.c2, d.w3, d.b3, d.u3, d.c3};
-    const size_t sz[AC_ARRAYS] = {sizes[0], sizes[1], sizes[2], sizes[3], sizes[6], sizes[7], sizes[8], sizes[9], sizes[4], sizes[5], sizes[10], sizes[11]};
-    const int rows[AC_ARRAYS] = {a.h1, a.h1, a.h2, a.h2, a.v1, a.v1, a.v2, a.v2, a.d_out, a.d_out, a.v2, 1};
-    const int cols[AC_ARRAYS] = {a.d_in, 0, a.h1, 0, a.d_in, 0, a.v1, 0, a.h2, 0, 0, 0};
-    const int K[AC_ARRAYS] = {a.k1, 0, a.n1, 0, a.k1, 0, a.m1, 0, a.n2, 0, 0, 0};
-    std::vector<float> stage[AC_ARRAYS];
-    for (int i = 0; i < AC_ARRAYS; i++) {
-        stage[i].resize(sz[i]);
-        HIPCHK(h, hipMemcpyAsync(stage[i].data(), src[i], sz[i] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    const auto sizes = ac_array_sizes(ac->plan);
+    const auto src = ac_arrays(ac->dev);
+    std::array<std::vector<float>, AC_ARRAYS> stage;
+    for (size_t i = 0; i < AC_ARRAYS; i++) {
+        stage[i].resize(sizes[i]);
+        HIPCHK(h, hipMemcpyAsync(stage[i].data(), *src[i], sizes[i] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < AC_ARRAYS; i++) {
-        if (cols[i]) unpack_linear_f32(stage[i].data(), rows[i], cols[i], K[i], out[i]);
-        else std::copy(stage[i].begin(), stage[i].begin() + rows[i], out[i]);
-    }
+    unpack_ac(ac->plan, stage, out);
     return EV2G_OK;
 }
 
-static void ppo_launch_repack(ev2g_handle *h, ev2g_ppo *p, bool transposed_only) {
-    hipLaunchKernelGGL(ev2g_ppo_repack_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->theta, transposed_only ? 1 : 0);
+// the device stage of a learner: allocates its buffers, takes the masters from the policy's images, builds the map the kernels place elements by,
+// fills the transposed images and sets the gradient kernel's dynamic-LDS attribute
+static int ppo_device_stage(ev2g_handle *h, ev2g_ppo *p, ev2g_acpolicy *ac) {
+    const PpoPlan &pl = p->plan;
+    const size_t G = (size_t)pl.n_params;
+    const struct { float **dst; size_t n; } f32[] = {{&p->theta, G}, {&p->m, G}, {&p->v, G}, {&p->grad, G}, {&p->work, (size_t)pl.grid_cap * pl.slab_floats}};
+    const struct { double **dst; size_t n; } f64[] = {{&p->stat_part, (size_t)pl.grid_cap * 8}, {&p->norm_part, (size_t)p->n_blocks}, {&p->advstat, 2}};
+    for (const auto &b : f32)
+        if (int rc = dalloc(h, p->allocs, b.n, b.dst)) return rc;
+    for (const auto &b : f64)
+        if (int rc = dalloc(h, p->allocs, b.n, b.dst)) return rc;
+    float *img_t[3] = {nullptr, nullptr, nullptr};
+    for (const AcParam &a : ac_params(pl.ac))
+        if (a.slot_t != AC_NO_IMAGE_T)
+            if (int rc = dalloc(h, p->allocs, a.img_floats, &img_t[a.slot_t])) return rc;
+    // the masters: the policy's current numbers, read back from its images (exact: the images hold the float32 values themselves)
+    std::vector<float> host(G, 0.f);
+    float *dst[AC_ARRAYS];
+    for (int i = 0; i < AC_ARRAYS; i++) dst[i] = host.data() + pl.off[i];
+    if (int rc = ac_read_images(h, ac, dst)) return rc;
+    std::copy(ac->log_std.begin(), ac->log_std.end(), host.begin() + pl.off[AC_ARRAYS]);
+    PpoDev &d = p->dev;
+    d.k1r = pl.k1r; d.w2t = img_t[AC_W2T]; d.w3t = img_t[AC_W3T]; d.u2t = img_t[AC_U2T]; d.log_std = p->theta + pl.off[AC_ARRAYS];
+    std::copy(pl.slab_off, pl.slab_off + EV2G_PPO_ARRAYS, d.slab_off);
+    d.slab_floats = pl.slab_floats;
+    float *img[AC_ARRAYS];
+    const auto arrays = ac_arrays(ac->dev);
+    for (size_t i = 0; i < AC_ARRAYS; i++) img[i] = (float *)*arrays[i];
+    p->map = ppo_map(pl, img, img_t);
+    hipError_t e = hipMemcpyAsync(p->theta, host.data(), G * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) { ppo_launch_repack(h, p, true); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    const int relu = ac->relu;
+    if (e == hipSuccess && pl.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & (1u << relu))) {   // (function attributes are per device: once per handle)
+        e = hipFuncSetAttribute(ppo_grad_kernel(relu).fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
+        if (e == hipSuccess) h->ppo_attr_mask |= 1u << relu;
+    }
+    if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string("ev2g_ppo_create: ") + hipGetErrorString(e));
+    return EV2G_OK;
 }
 
 int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cfg, ev2g_ppo **out) {
@@ -2410,54 +2475,15 @@ int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cf
     if (int rc = ppo_config_check(h, "ev2g_ppo_create", cfg->lr, cfg->clip_range, cfg)) return rc;
     if (ac->learner) return fail(h, EV2G_ERR_STATE, "ev2g_ppo_create: the policy already has a learner");
     const AcPlan &a = ac->plan;
-    PpoPlan plan = plan_ppo(a.d_in, a.h1, a.h2, a.v1, a.v2, a.d_out);
+    const PpoPlan plan = plan_ppo(a.d_in, a.h1, a.h2, a.v1, a.v2, a.d_out);
     if (plan.err) return fail(h, plan.err, plan.refusal);
     ev2g_ppo *p = new ev2g_ppo();
     p->plan = plan; p->cfg = *cfg;
     p->n_blocks = (plan.n_params + 255) / 256;
-    const size_t G = (size_t)plan.n_params;
-    float *w2t = nullptr, *w3t = nullptr, *u2t = nullptr;
-    int rc = 0;
-    if ((rc = dalloc(h, p->allocs, G, &p->theta)) || (rc = dalloc(h, p->allocs, G, &p->m)) || (rc = dalloc(h, p->allocs, G, &p->v)) ||
-        (rc = dalloc(h, p->allocs, G, &p->grad)) || (rc = dalloc(h, p->allocs, (size_t)plan.grid_cap * plan.slab_floats, &p->work)) ||
-        (rc = dalloc(h, p->allocs, (size_t)plan.grid_cap * 8, &p->stat_part)) || (rc = dalloc(h, p->allocs, (size_t)p->n_blocks, &p->norm_part)) ||
-        (rc = dalloc(h, p->allocs, 2, &p->advstat)) || (rc = dalloc(h, p->allocs, (size_t)a.n1 * a.n2, &w2t)) ||
-        (rc = dalloc(h, p->allocs, (size_t)a.n2 * a.n3, &w3t)) || (rc = dalloc(h, p->allocs, (size_t)a.m1 * a.m2, &u2t))) {
+    if (const int rc = ppo_device_stage(h, p, ac)) {   // the one cleanup path
         ppo_free(p);
         return rc;
     }
-    // the masters: the policy's current numbers, read back from its images (exact: the images hold the float32 values themselves)
-    std::vector<float> host(G, 0.f);
-    float *dst[AC_ARRAYS];
-    for (int i = 0; i < AC_ARRAYS; i++) dst[i] = host.data() + plan.off[i];
-    if ((rc = ac_read_images(h, ac, dst))) { ppo_free(p); return rc; }
-    std::copy(ac->log_std.begin(), ac->log_std.end(), host.begin() + plan.off[12]);
-    PpoDev &d = p->dev;
-    d.k1r = plan.k1r; d.w2t = w2t; d.w3t = w3t; d.u2t = u2t; d.log_std = p->theta + plan.off[12];
-    PpoMap &mp = p->map;
-    const AcDev &ad = ac->dev;
-    float *img[EV2G_PPO_ARRAYS] = {(float *)ad.w1, (float *)ad.b1, (float *)ad.w2, (float *)ad.b2, (float *)ad.u1, (float *)ad.c1, (float *)ad.u2,
-                                   (float *)ad.c2, (float *)ad.w3, (float *)ad.b3, (float *)ad.u3, (float *)ad.c3, nullptr};
-    const int img_k[EV2G_PPO_ARRAYS] = {a.k1, 0, a.n1, 0, a.k1, 0, a.m1, 0, a.n2, 0, 0, 0, 0};
-    float *imgT[EV2G_PPO_ARRAYS] = {nullptr, nullptr, w2t, nullptr, nullptr, nullptr, u2t, nullptr, w3t, nullptr, nullptr, nullptr, nullptr};
-    const int imgT_k[EV2G_PPO_ARRAYS] = {0, 0, a.n2, 0, 0, 0, a.m2, 0, a.n3, 0, 0, 0, 0};
-    for (int i = 0; i < EV2G_PPO_ARRAYS; i++) {
-        mp.off[i] = plan.off[i]; mp.cols[i] = plan.cols[i]; mp.slab_off[i] = plan.slab_off[i]; mp.slab_ld[i] = plan.slab_ld[i];
-        mp.img[i] = img[i]; mp.img_k[i] = img_k[i]; mp.imgT[i] = imgT[i]; mp.imgT_k[i] = imgT_k[i];
-        d.slab_off[i] = plan.slab_off[i];
-    }
-    mp.off[EV2G_PPO_ARRAYS] = plan.off[EV2G_PPO_ARRAYS];
-    mp.slab_floats = d.slab_floats = plan.slab_floats; mp.n_params = plan.n_params; mp.P = a.d_out;
-    hipError_t e = hipMemcpyAsync(p->theta, host.data(), G * sizeof(float), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) { ppo_launch_repack(h, p, true); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    const int relu = ac->relu;
-    if (e == hipSuccess && plan.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & (1u << relu))) {   // (function attributes are per device: once per handle)
-        const void *fn = relu ? (const void *)ev2g_ppo_grad_kernel<EV2G_AC_RELU> : (const void *)ev2g_ppo_grad_kernel<EV2G_AC_TANH>;
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
-        if (e == hipSuccess) h->ppo_attr_mask |= 1u << relu;
-    }
-    if (e != hipSuccess) { ppo_free(p); return fail(h, EV2G_ERR_HIP, std::string("ev2g_ppo_create: ") + hipGetErrorString(e)); }
     p->ac = ac; ac->learner = p;
     h->ppos.push_back(p);
     *out = p;
@@ -2482,13 +2508,9 @@ static int ppo_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, const float *o
     const PpoHyper hp{(float)p->cfg.clip_range, (float)p->cfg.vf_coef, (float)p->cfg.ent_coef, p->cfg.normalize_advantage ? 1 : 0};
     if (hp.normalize && B > 1) hipLaunchKernelGGL(ev2g_ppo_advstat_kernel, dim3(1), dim3(1024), 0, h->stream, adv, (const int *)idx, B, p->advstat);
     const int chunks = (B + EV2G_PPO_ROWS - 1) / EV2G_PPO_ROWS, n_wg = chunks < pl.grid_cap ? chunks : pl.grid_cap;
-    const dim3 grid((unsigned)n_wg), block(EV2G_PPO_BLOCK);
-    if (p->ac->relu)
-        hipLaunchKernelGGL(ev2g_ppo_grad_kernel<EV2G_AC_RELU>, grid, block, pl.lds.bytes, h->stream, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv,
-                           ret, (const int *)idx, B, (const double *)p->advstat, p->work, p->stat_part);
-    else
-        hipLaunchKernelGGL(ev2g_ppo_grad_kernel<EV2G_AC_TANH>, grid, block, pl.lds.bytes, h->stream, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv,
-                           ret, (const int *)idx, B, (const double *)p->advstat, p->work, p->stat_part);
+    const LaunchDims dims{dim3((unsigned)n_wg), pl.lds.bytes, h->stream};
+    ppo_grad_kernel(p->ac->relu).launch(dims, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv, ret, (const int *)idx, B, (const double *)p->advstat, p->work,
+                                        p->stat_part);
     hipLaunchKernelGGL(ev2g_ppo_reduce_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->work,
                        (const double *)p->stat_part, n_wg, B, hp, p->dev.log_std, p->grad, p->norm_part, stats);
     HIPCHK(h, hipGetLastError());

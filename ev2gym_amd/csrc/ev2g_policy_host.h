@@ -3,11 +3,12 @@
 // plan_mlp(sizes, out_lo, precision) is the whole decision of ev2g_mlp_create_ex: the refusals, the padded sizes, the kernel (a kind and an
 // index into ev2g_host.hip's kMlpTable), the streaming kernel's fragment packing (the FusedPacking route_fused reads), LDS bytes, rows per
 // workgroup and threads, and the 32-row variant bf16 streaming policies run on large batches.  pack_mlp(plan, weights) builds the host
-// images of the three weight matrices in that kernel's MFMA fragment order and of the biases.  plan_ac / pack_ac are the same for the
-// Gaussian actor-critic (ev2g_ac.h), which reads float32 operands in ev2g_mlp3_f32's layout; plan_ppo is the plan of its PPO learner
-// (ev2g_ppo.h): accepted widths, LDS layout, grid cap, workspace.  ev2g_host.hip is the device stage: it
-// uploads the images and launches the table's entry.  Nothing here needs HIP, a handle or a kernel header, so a plain C++17 program can
-// enumerate the plan and check every packed element (tests/host/policy_plan_check.cpp).
+// images of the three weight matrices in that kernel's MFMA fragment order and of the biases.  plan_ac is the same for the Gaussian
+// actor-critic (ev2g_ac.h), which reads float32 operands in ev2g_mlp3_f32's layout, and ac_params(plan) is the one table of its thirteen
+// parameter arrays: pack_ac / unpack_ac / ac_array_sizes, the offsets and slabs of plan_ppo (the plan of its PPO learner, ev2g_ppo.h: accepted
+// widths, LDS layout, grid cap, workspace) and ppo_map (where the learner's kernels place every element) are loops over it.  ev2g_host.hip is
+// the device stage: it uploads the images and launches the table's entry.  Nothing here needs HIP, a handle or a kernel header, so a plain C++17 program can
+// enumerate the plan and check every packed element (tests/host/policy_plan_check.cpp, ppo_plan_check.cpp).
 //
 // The LDS geometry of the actor kernels lives here too, as constexpr functions of ints: ev2g_mlp.h includes this header and lays its LDS
 // out by them, so the plan's byte counts and the kernels' pointers come from one definition.
@@ -223,6 +224,18 @@ inline std::vector<float> pack_linear_f32(const float *W, int n_out, int n_in, i
     return v;
 }
 
+// inverse of pack_linear_f32 / pad_bias: the [n_out, n_in] matrix an image holds (ev2g_ac_get_weights on a policy without a learner)
+inline void unpack_linear_f32(const float *img, int n_out, int n_in, int K, float *W) {
+    const int KG = K / 8;
+    for (int n = 0; n < n_out; n++)
+        for (int k = 0; k < n_in; k++)
+            W[(size_t)n * n_in + k] = img[(((size_t)(n >> 5) * KG + (k >> 3)) * 64 + (n & 31) + 32 * ((k & 7) >> 2)) * 4 + (k & 3)];
+}
+// where element (n, k) of a matrix sits in its pack_linear_f32 image of K padded inputs (the device repack of ev2g_ppo.h writes by it)
+constexpr size_t packed_f32_index(int n, int k, int K) {
+    return (((size_t)(n >> 5) * (size_t)(K / 8) + (size_t)(k >> 3)) * 64 + (size_t)((n & 31) + 32 * ((k & 7) >> 2))) * 4 + (size_t)(k & 3);
+}
+
 inline std::vector<float> pad_bias(const float *b, int n, int N) {
     std::vector<float> v((size_t)N, 0.f);
     std::copy(b, b + n, v.begin());
@@ -269,48 +282,10 @@ inline MlpImages pack_mlp(const MlpPlan &p, const float *W1, const float *b1, co
 }
 
 // ---- the Gaussian actor-critic (ev2g_ac.h): float32 operands in ev2g_mlp32_layer's order, inputs padded to 8, every layer's columns to 32 ----
-struct AcPlan {
-    int d_in, h1, h2, v1, v2, d_out;   // the network's own widths
-    int k1, n1, n2, m1, m2, n3;        // padded (AcDev's)
-};
-inline AcPlan plan_ac(int d_in, int h1, int h2, int v1, int v2, int d_out) {
-    return {d_in, h1, h2, v1, v2, d_out,
-            mlp_round_up(d_in, 8), mlp_round_up(h1, 32), mlp_round_up(h2, 32), mlp_round_up(v1, 32), mlp_round_up(v2, 32), mlp_round_up(d_out, 32)};
-}
-// the twelve device arrays, in AcDev's order: policy trunk w1 b1 w2 b2, action head w3 b3, value trunk u1 c1 u2 c2, value head u3 (the weight
-// row padded with zeros to m2) c3 (one float)
-constexpr int AC_ARRAYS = 12;
-inline std::array<size_t, AC_ARRAYS> ac_array_sizes(const AcPlan &p) {
-    return {(size_t)p.n1 * p.k1, (size_t)p.n1, (size_t)p.n2 * p.n1, (size_t)p.n2, (size_t)p.n3 * p.n2, (size_t)p.n3,
-            (size_t)p.m1 * p.k1, (size_t)p.m1, (size_t)p.m2 * p.m1, (size_t)p.m2, (size_t)p.m2, (size_t)1};
-}
-struct AcWeights { const float *pW1, *pb1, *pW2, *pb2, *vW1, *vb1, *vW2, *vb2, *aW, *ab, *cW, *cb; };
-inline std::array<std::vector<float>, AC_ARRAYS> pack_ac(const AcPlan &p, const AcWeights &w) {
-    return {pack_linear_f32(w.pW1, p.h1, p.d_in, p.n1, p.k1), pad_bias(w.pb1, p.h1, p.n1),
-            pack_linear_f32(w.pW2, p.h2, p.h1, p.n2, p.n1),   pad_bias(w.pb2, p.h2, p.n2),
-            pack_linear_f32(w.aW, p.d_out, p.h2, p.n3, p.n2), pad_bias(w.ab, p.d_out, p.n3),
-            pack_linear_f32(w.vW1, p.v1, p.d_in, p.m1, p.k1), pad_bias(w.vb1, p.v1, p.m1),
-            pack_linear_f32(w.vW2, p.v2, p.v1, p.m2, p.m1),   pad_bias(w.vb2, p.v2, p.m2),
-            pad_bias(w.cW, p.v2, p.m2),                       pad_bias(w.cb, 1, 1)};
-}
-
-// inverse of pack_linear_f32 / pad_bias: the [n_out, n_in] matrix an image holds (ev2g_ac_get_weights on a policy without a learner)
-inline void unpack_linear_f32(const float *img, int n_out, int n_in, int K, float *W) {
-    const int KG = K / 8;
-    for (int n = 0; n < n_out; n++)
-        for (int k = 0; k < n_in; k++)
-            W[(size_t)n * n_in + k] = img[(((size_t)(n >> 5) * KG + (k >> 3)) * 64 + (n & 31) + 32 * ((k & 7) >> 2)) * 4 + (k & 3)];
-}
-// where element (n, k) of a matrix sits in its pack_linear_f32 image of K padded inputs (the device repack of ev2g_ppo.h writes by it)
-constexpr size_t packed_f32_index(int n, int k, int K) {
-    return (((size_t)(n >> 5) * (size_t)(K / 8) + (size_t)(k >> 3)) * 64 + (size_t)((n & 31) + 32 * ((k & 7) >> 2))) * 4 + (size_t)(k & 3);
-}
-
-// ---- the PPO learner of a Gaussian actor-critic (ev2g_ppo.h) ----
-// Thirteen gradient arrays in SB3's parameter order: the twelve of AcWeights, then log_std.  The gradient kernel's workgroup keeps, per 32 gathered
-// rows, every activation and every layer's delta in LDS (float32 rows of stride width + 4, as ev2g_ac_lds), and its partial sums in a slab of
-// its own in the workspace: matrices [padded out][padded in] row-major with the inputs of the first layers padded to 32 (the weight-gradient
-// tiles are 32 x 32), vectors padded likewise.
+#define EV2G_AC_MAX_IN 192
+#define EV2G_AC_MAX_HIDDEN 256
+#define EV2G_AC_MAX_OUT 64
+// ... and its PPO learner (ev2g_ppo.h)
 #define EV2G_PPO_ROWS 32
 #define EV2G_PPO_BLOCK 256
 #define EV2G_PPO_GRID_CAP 256   // workgroups of the gradient kernel at most (one per CU of an MI355X); more chunks loop
@@ -319,6 +294,96 @@ constexpr size_t packed_f32_index(int n, int k, int K) {
 #define EV2G_PPO_MAX_OUT 64
 #define EV2G_PPO_LDS_LIMIT (160 * 1024)
 
+struct AcPlan {
+    int d_in, h1, h2, v1, v2, d_out;   // the network's own widths
+    int k1, n1, n2, m1, m2, n3;        // padded (AcDev's)
+    int err = EV2G_OK;                 // a refusal of ev2g_ac_create: the code ...
+    std::string refusal;               // ... and the message; the padded widths are not decided then
+};
+inline AcPlan plan_ac(int d_in, int h1, int h2, int v1, int v2, int d_out) {
+    AcPlan p{d_in, h1, h2, v1, v2, d_out, 0, 0, 0, 0, 0, 0};
+    auto refuse = [&p](const char *what, int hi) {
+        p.err = EV2G_ERR_ARG; p.refusal = std::string("ev2g_ac_create: ") + what + " must be 1 .. " + std::to_string(hi);
+        return p;
+    };
+    if (d_in < 1 || d_in > EV2G_AC_MAX_IN) return refuse("d_in", EV2G_AC_MAX_IN);
+    const int hid[4] = {h1, h2, v1, v2};
+    const char *name[4] = {"h1", "h2", "v1", "v2"};
+    for (int i = 0; i < 4; i++)
+        if (hid[i] < 1 || hid[i] > EV2G_AC_MAX_HIDDEN) return refuse(name[i], EV2G_AC_MAX_HIDDEN);
+    if (d_out < 1 || d_out > EV2G_AC_MAX_OUT) return refuse("d_out", EV2G_AC_MAX_OUT);
+    p.k1 = mlp_round_up(d_in, 8); p.n1 = mlp_round_up(h1, 32); p.n2 = mlp_round_up(h2, 32);
+    p.m1 = mlp_round_up(v1, 32); p.m2 = mlp_round_up(v2, 32); p.n3 = mlp_round_up(d_out, 32);
+    return p;
+}
+constexpr int ppo_k1r(int d_in) { return mlp_round_up(d_in, 32); }   // the learner pads the first layers' inputs to 32 (PpoDev's k1r)
+
+// The network's thirteen parameter arrays, in the one order the ABI, SB3's state dict and the learner's flat buffers share.  Everything that
+// places an array -- the images' sizes and packing, the read-back, the learner's offsets, slabs and PpoMap -- is derived from this table.
+constexpr int AC_ARRAYS = 12;   // the arrays with a device image: all but log_std
+enum AcSlot { AC_NO_IMAGE = -1, AC_W1, AC_B1, AC_W2, AC_B2, AC_W3, AC_B3, AC_U1, AC_C1, AC_U2, AC_C2, AC_U3, AC_C3 };   // AcDev's pointer members, in its order
+enum AcSlotT { AC_NO_IMAGE_T = -1, AC_W2T, AC_W3T, AC_U2T };   // PpoDev's transposed images, in its order
+struct AcParam {
+    const char *name;       // as in messages and in Python (_abi.AC_PARAMS)
+    int rows, cols;         // the array's own shape: [out, in] as torch.nn.Linear keeps it; a vector: cols 1
+    int slot;               // the AcDev member its image lives in (log_std: AC_NO_IMAGE)
+    int img_k;              // the image's padded input width (pack_linear_f32's K); 0: a vector image, element e at e
+    size_t img_floats;      // the image's allocated size
+    int slot_t, img_t_k;    // the learner's transposed image (pack_linear_f32 of the transpose) and its padded width, or AC_NO_IMAGE_T, 0
+    int slab_rows, slab_ld; // the region in a gradient workgroup's slab: rows and row stride (vectors: stride 1)
+};
+inline std::array<AcParam, EV2G_PPO_ARRAYS> ac_params(const AcPlan &p) {
+    const int k1r = ppo_k1r(p.d_in);
+    auto mat = [](const char *name, int rows, int cols, int slot, int N, int K, int slot_t, int slab_ld) {
+        return AcParam{name, rows, cols, slot, K, (size_t)N * K, slot_t, slot_t == AC_NO_IMAGE_T ? 0 : N, N, slab_ld};
+    };
+    auto vec = [](const char *name, int n, int slot, int N) { return AcParam{name, n, 1, slot, 0, (size_t)N, AC_NO_IMAGE_T, 0, N, 1}; };
+    return {mat("pi_W1", p.h1, p.d_in, AC_W1, p.n1, p.k1, AC_NO_IMAGE_T, k1r), vec("pi_b1", p.h1, AC_B1, p.n1),
+            mat("pi_W2", p.h2, p.h1, AC_W2, p.n2, p.n1, AC_W2T, p.n1),         vec("pi_b2", p.h2, AC_B2, p.n2),
+            mat("vf_W1", p.v1, p.d_in, AC_U1, p.m1, p.k1, AC_NO_IMAGE_T, k1r), vec("vf_b1", p.v1, AC_C1, p.m1),
+            mat("vf_W2", p.v2, p.v1, AC_U2, p.m2, p.m1, AC_U2T, p.m1),         vec("vf_b2", p.v2, AC_C2, p.m2),
+            mat("action_W", p.d_out, p.h2, AC_W3, p.n3, p.n2, AC_W3T, p.n2),   vec("action_b", p.d_out, AC_B3, p.n3),
+            // the value head: [1, v2] in SB3's layout, but a vector image of m2 floats (the kernel's FMA chain reads it as a row); its bias is one
+            // float with a slab region of four
+            AcParam{"value_W", 1, p.v2, AC_U3, 0, (size_t)p.m2, AC_NO_IMAGE_T, 0, 1, p.m2},
+            AcParam{"value_b", 1, 1, AC_C3, 0, (size_t)1, AC_NO_IMAGE_T, 0, 4, 1},
+            AcParam{"log_std", p.d_out, 1, AC_NO_IMAGE, 0, (size_t)0, AC_NO_IMAGE_T, 0, p.n3, 1}};
+}
+
+// the twelve host arrays of a network, in the table's order
+struct AcWeights { const float *a[AC_ARRAYS]; };
+// the twelve device images, in AcDev's order: their sizes, their contents, and the arrays they hold (unpack_ac inverts pack_ac)
+inline std::array<size_t, AC_ARRAYS> ac_array_sizes(const AcPlan &p) {
+    std::array<size_t, AC_ARRAYS> s{};
+    const auto tab = ac_params(p);
+    for (int i = 0; i < AC_ARRAYS; i++) s[(size_t)tab[i].slot] = tab[i].img_floats;
+    return s;
+}
+inline std::array<std::vector<float>, AC_ARRAYS> pack_ac(const AcPlan &p, const AcWeights &w) {
+    std::array<std::vector<float>, AC_ARRAYS> img;
+    const auto tab = ac_params(p);
+    for (int i = 0; i < AC_ARRAYS; i++) {
+        const AcParam &a = tab[i];
+        img[(size_t)a.slot] = a.img_k ? pack_linear_f32(w.a[i], a.rows, a.cols, (int)(a.img_floats / (size_t)a.img_k), a.img_k)
+                                      : pad_bias(w.a[i], a.rows * a.cols, (int)a.img_floats);
+    }
+    return img;
+}
+inline void unpack_ac(const AcPlan &p, const std::array<std::vector<float>, AC_ARRAYS> &img, float *const out[AC_ARRAYS]) {
+    const auto tab = ac_params(p);
+    for (int i = 0; i < AC_ARRAYS; i++) {
+        const AcParam &a = tab[i];
+        const float *src = img[(size_t)a.slot].data();
+        if (a.img_k) unpack_linear_f32(src, a.rows, a.cols, a.img_k, out[i]);
+        else std::copy(src, src + a.rows * a.cols, out[i]);
+    }
+}
+
+// ---- the PPO learner of a Gaussian actor-critic (ev2g_ppo.h) ----
+// Thirteen gradient arrays in SB3's parameter order: the twelve of AcWeights, then log_std.  The gradient kernel's workgroup keeps, per 32 gathered
+// rows, every activation and every layer's delta in LDS (float32 rows of stride width + 4, as ev2g_ac_lds), and its partial sums in a slab of
+// its own in the workspace: matrices [padded out][padded in] row-major with the inputs of the first layers padded to 32 (the weight-gradient
+// tiles are 32 x 32), vectors padded likewise.
 struct PpoLds {   // offsets in floats from the 16-byte aligned base; the first n3 doubles are exp(-2 log_std)
     int sX, sH1, sH2, sV1, sV2, sMU;   // row strides: x, the trunks' hidden layers, the mean (and the actions)
     int oIV, oX, oH1, oH2, oV1, oV2, oMU, oACT, oD1, oD2, oE1, oE2, oROW;   // D / E: the deltas of H / V; ROW: [3][32] per-row head values
@@ -371,7 +436,7 @@ inline PpoPlan plan_ppo(int d_in, int h1, int h2, int v1, int v2, int d_out) {
         if (hid[i] < 1 || hid[i] > 256) return refuse(std::string("ev2g_ppo: ") + name[i] + " " + std::to_string(hid[i]) + " is outside 1 .. 256");
     p.ac = plan_ac(d_in, h1, h2, v1, v2, d_out);
     const AcPlan &a = p.ac;
-    p.k1r = mlp_round_up(d_in, 32);
+    p.k1r = ppo_k1r(d_in);
     p.lds = ppo_lds(p.k1r, a.n1, a.n2, a.m1, a.m2, a.n3);
     if (p.lds.bytes > EV2G_PPO_LDS_LIMIT) {
         int w = 0;   // the widest hidden layer is the one to name
@@ -379,16 +444,37 @@ inline PpoPlan plan_ppo(int d_in, int h1, int h2, int v1, int v2, int d_out) {
         return refuse(std::string("ev2g_ppo: ") + name[w] + " " + std::to_string(hid[w]) + " is too wide: the gradient kernel's LDS plan takes " +
                       std::to_string(p.lds.bytes) + " bytes of the CU's " + std::to_string(EV2G_PPO_LDS_LIMIT));
     }
-    const int R[EV2G_PPO_ARRAYS] = {h1, h1, h2, h2, v1, v1, v2, v2, d_out, d_out, 1, 1, d_out};
-    const int C[EV2G_PPO_ARRAYS] = {d_in, 1, h1, 1, d_in, 1, v1, 1, h2, 1, v2, 1, 1};
-    const int SR[EV2G_PPO_ARRAYS] = {a.n1, a.n1, a.n2, a.n2, a.m1, a.m1, a.m2, a.m2, a.n3, a.n3, 1, 4, a.n3};   // slab rows
-    const int SL[EV2G_PPO_ARRAYS] = {p.k1r, 1, a.n1, 1, p.k1r, 1, a.m1, 1, a.n2, 1, a.m2, 1, 1};               // slab row stride
+    const auto tab = ac_params(a);
     int o = 0, s = 0;
     for (int i = 0; i < EV2G_PPO_ARRAYS; i++) {
-        p.rows[i] = R[i]; p.cols[i] = C[i]; p.off[i] = o; o += R[i] * C[i];
-        p.slab_off[i] = s; p.slab_ld[i] = SL[i]; s += SR[i] * SL[i];
+        p.rows[i] = tab[i].rows; p.cols[i] = tab[i].cols; p.off[i] = o; o += tab[i].rows * tab[i].cols;
+        p.slab_off[i] = s; p.slab_ld[i] = tab[i].slab_ld; s += tab[i].slab_rows * tab[i].slab_ld;
     }
     p.off[EV2G_PPO_ARRAYS] = o; p.n_params = o; p.slab_floats = s;
     p.workspace_bytes = (size_t)p.grid_cap * ((size_t)s * sizeof(float) + 8 * sizeof(double));
     return p;
+}
+
+// where the thirteen arrays sit: the flat buffers, the slabs, the packed images.  Passed to the kernels of ev2g_ppo.h by value.
+struct PpoMap {
+    int off[EV2G_PPO_ARRAYS + 1], cols[EV2G_PPO_ARRAYS], slab_off[EV2G_PPO_ARRAYS], slab_ld[EV2G_PPO_ARRAYS];
+    int slab_floats, n_params, P;
+    float *img[EV2G_PPO_ARRAYS];    // the image AcDev points at (log_std: null)
+    int img_k[EV2G_PPO_ARRAYS];     // a matrix: the padded inputs of its pack_linear_f32 image; a vector: 0 (element i at i)
+    float *imgT[EV2G_PPO_ARRAYS];   // the transposed image, or null
+    int imgT_k[EV2G_PPO_ARRAYS];
+};
+// img: the policy's twelve images in AcDev's order (AcSlot); img_t: the learner's three transposed images in PpoDev's (AcSlotT)
+inline PpoMap ppo_map(const PpoPlan &pl, float *const img[AC_ARRAYS], float *const img_t[3]) {
+    PpoMap mp{};
+    const auto tab = ac_params(pl.ac);
+    for (int i = 0; i < EV2G_PPO_ARRAYS; i++) {
+        const AcParam &a = tab[i];
+        mp.off[i] = pl.off[i]; mp.cols[i] = pl.cols[i]; mp.slab_off[i] = pl.slab_off[i]; mp.slab_ld[i] = pl.slab_ld[i];
+        mp.img[i] = a.slot == AC_NO_IMAGE ? nullptr : img[a.slot]; mp.img_k[i] = a.img_k;
+        mp.imgT[i] = a.slot_t == AC_NO_IMAGE_T ? nullptr : img_t[a.slot_t]; mp.imgT_k[i] = a.img_t_k;
+    }
+    mp.off[EV2G_PPO_ARRAYS] = pl.off[EV2G_PPO_ARRAYS];
+    mp.slab_floats = pl.slab_floats; mp.n_params = pl.n_params; mp.P = pl.ac.d_out;
+    return mp;
 }

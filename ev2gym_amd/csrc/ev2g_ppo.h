@@ -339,16 +339,7 @@ __global__ void __launch_bounds__(EV2G_PPO_BLOCK) ev2g_ppo_grad_kernel(AcDev m, 
     }
 }
 
-// where the thirteen arrays sit: the flat buffers, the slabs, the packed images
-struct PpoMap {
-    int off[EV2G_PPO_ARRAYS + 1], cols[EV2G_PPO_ARRAYS], slab_off[EV2G_PPO_ARRAYS], slab_ld[EV2G_PPO_ARRAYS];
-    int slab_floats, n_params, P;
-    float *img[EV2G_PPO_ARRAYS];    // the image AcDev points at (log_std: null)
-    int img_k[EV2G_PPO_ARRAYS];     // a matrix: the padded inputs of its pack_linear_f32 image; a vector: 0 (element i at i)
-    float *imgT[EV2G_PPO_ARRAYS];   // the transposed image, or null
-    int imgT_k[EV2G_PPO_ARRAYS];
-};
-
+// PpoMap (ev2g_policy_host.h: ppo_map builds it on the host) says where the thirteen arrays sit: the flat buffers, the slabs, the packed images
 __device__ __forceinline__ int ev2g_ppo_which(const PpoMap &mp, int i) {
     int a = 0;
 #pragma unroll

@@ -645,10 +645,10 @@ class Engine:
         arrs = [np.ascontiguousarray(a, np.float32) for a in weights]
         assert len(arrs) == 12
         ls = np.ascontiguousarray(log_std, np.float32)
-        (h1, d_in), h2, (v1, _), v2, d_out = arrs[0].shape, arrs[2].shape[0], arrs[4].shape, arrs[6].shape[0], arrs[8].shape[0]
+        widths = _abi.ac_widths(arrs)
         act = _abi.AC_ACTIVATIONS[activation] if isinstance(activation, str) else int(activation)
         ac = C.c_void_p()
-        self._check(self._lib.ev2g_ac_create(self._h, d_in, h1, h2, v1, v2, d_out, act, *[a.ctypes.data for a in arrs], ls.ctypes.data,
+        self._check(self._lib.ev2g_ac_create(self._h, *widths, act, *[a.ctypes.data for a in arrs], ls.ctypes.data,
                                              float(lo), int(seed) & (2 ** 64 - 1), C.byref(ac)))
         return ac
 
@@ -693,14 +693,10 @@ class Engine:
 
     # ---- statistics / inspection ---------------------------------------------------------------
     # ---- the PPO learner (include/ev2g.h: ev2g_ppo_*) ---------------------------------------------------------------------------------
-    def _ac_shapes(self, ac_shape):
-        D, h1, h2, v1, v2, P = ac_shape
-        return ((h1, D), (h1,), (h2, h1), (h2,), (v1, D), (v1,), (v2, v1), (v2,), (P, h2), (P,), (1, v2), (1,), (P,))
-
     def ac_get_weights(self, ac, ac_shape):
         """(the twelve arrays, log_std) of a device policy as host float32 arrays (ev2g_ac_get_weights): the learner's masters when one is bound.
         ac_shape: (d_in, h1, h2, v1, v2, d_out)."""
-        out = [np.empty(s, np.float32) for s in self._ac_shapes(ac_shape)]
+        out = [np.empty(s, np.float32) for s in _abi.ac_param_shapes(*ac_shape)]
         self._check(self._lib.ev2g_ac_get_weights(self._h, ac, *[a.ctypes.data for a in out]))
         return out[:12], out[12]
 
@@ -734,7 +730,7 @@ class Engine:
 
     def ppo_get_grads(self, ppo, ac_shape):
         """The last gradient (unclipped) as thirteen host float32 arrays in SB3's layout: the twelve of ac_create's order, then log_std."""
-        out = [np.empty(s, np.float32) for s in self._ac_shapes(ac_shape)]
+        out = [np.empty(s, np.float32) for s in _abi.ac_param_shapes(*ac_shape)]
         self._check(self._lib.ev2g_ppo_get_grads(self._h, ppo, *[a.ctypes.data for a in out]))
         return out
 

@@ -26,7 +26,7 @@ SB3_KEYS = (
     "action_net.weight", "action_net.bias", "value_net.weight", "value_net.bias",
 )
 SB3_LOG_STD = "log_std"
-_FIELDS = ("pi_W1", "pi_b1", "pi_W2", "pi_b2", "vf_W1", "vf_b1", "vf_W2", "vf_b2", "action_W", "action_b", "value_W", "value_b")
+_FIELDS = _abi.AC_PARAMS[:12]   # the weight and bias arrays; log_std is held apart
 
 
 def _host(a):
@@ -39,10 +39,11 @@ def _host(a):
 def init_ac_weights(D, P, seed=0, h=(64, 64), v=(64, 64)):
     """torch.nn.Linear-style uniform(-1/sqrt(in), 1/sqrt(in)) weights, in the twelve-array order, as numpy float32."""
     rng = np.random.default_rng(seed)
+    shapes = _abi.ac_param_shapes(D, h[0], h[1], v[0], v[1], P)[:12]
     out = []
-    for n_in, n_out in ((D, h[0]), (h[0], h[1]), (D, v[0]), (v[0], v[1]), (h[1], P), (v[1], 1)):
-        k = 1.0 / np.sqrt(n_in)
-        out += [rng.uniform(-k, k, (n_out, n_in)).astype(np.float32), rng.uniform(-k, k, n_out).astype(np.float32)]
+    for w_shape, b_shape in zip(shapes[0::2], shapes[1::2]):   # (a layer's weight, then its bias, drawn in that order)
+        k = 1.0 / np.sqrt(w_shape[1])
+        out += [rng.uniform(-k, k, w_shape).astype(np.float32), rng.uniform(-k, k, b_shape[0]).astype(np.float32)]
     return out
 
 
@@ -93,10 +94,8 @@ class GaussianActorCritic:
         w = [np.ascontiguousarray(_host(a), np.float32) for a in weights]
         if w[0].ndim != 2 or w[4].ndim != 2:
             raise ValueError("GaussianActorCritic: pi_W1 and vf_W1 must be [out, in] matrices")
-        (h1, D), (v1, _) = w[0].shape, w[4].shape
-        h2, v2, P = w[2].shape[0], w[6].shape[0], w[8].shape[0]
-        want = ((h1, D), (h1,), (h2, h1), (h2,), (v1, D), (v1,), (v2, v1), (v2,), (P, h2), (P,), (1, v2), (1,))
-        for name, a, s in zip(_FIELDS, w, want):
+        D, h1, h2, v1, v2, P = _abi.ac_widths(w)
+        for name, a, s in zip(_FIELDS, w, _abi.ac_param_shapes(D, h1, h2, v1, v2, P)):
             if a.shape != s:
                 raise ValueError(f"GaussianActorCritic: {name} has shape {a.shape}, expected {s}")
         if not 1 <= D <= _abi.AC_MAX_IN:

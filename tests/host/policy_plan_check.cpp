@@ -1,7 +1,7 @@
 // policy_plan_check.cpp -- enumerates a policy's plan (ev2gym_amd/csrc/ev2g_policy_host.h: plan_mlp) and checks it against predicates written
 // here from the contract's wording (include/ev2g.h: ev2g_mlp_create_ex; the kernels' own descriptions in csrc/ev2g_mlp.h; the packing
 // route_fused expects), then checks every element of the weight and bias images (pack_linear, pack_linear_s16, pack_linear_f32, pack_mlp,
-// pack_ac) against the index each layout documents, and host_bf16 against a round-to-nearest-even written on the two halves of the word.
+// pack_ac and its inverse unpack_ac) against the index each layout documents, plan_ac's refusals, and host_bf16 against a round-to-nearest-even written on the two halves of the word.
 // Exits non-zero at the first failure.
 //
 //   c++ -std=c++17 -O1 -ffp-contract=off tests/host/policy_plan_check.cpp -o policy_plan_check && ./policy_plan_check
@@ -333,7 +333,39 @@ static void check_ac() {
             want_linear_f32(vW1.data(), v1, d_in, p.m1, p.k1), want_padded(vb1.data(), v1, p.m1), want_linear_f32(vW2.data(), v2, v1, p.m2, p.m1),
             want_padded(vb2.data(), v2, p.m2), want_padded(cW.data(), v2, p.m2), want_padded(cb.data(), 1, 1)};
         for (int i = 0; i < 12; i++) CHECK(sizes[(size_t)i] == want[i].size() && same_bits(img[(size_t)i], want[i]));
+        // unpack_ac inverts pack_ac: the twelve arrays come back bit for bit, and nothing is written past an array's own size
+        const std::vector<float> *src[12] = {&pW1, &pb1, &pW2, &pb2, &vW1, &vb1, &vW2, &vb2, &aW, &ab, &cW, &cb};
+        std::vector<float> back[12];
+        float *out[12];
+        const float guard = 12345.f;
+        for (int i = 0; i < 12; i++) { back[i].assign(src[i]->size() + 1, guard); out[i] = back[i].data(); }
+        unpack_ac(p, img, out);
+        for (int i = 0; i < 12; i++) {
+            CHECK(back[i].back() == guard);
+            back[i].pop_back();
+            CHECK(same_bits(back[i], *src[i]));
+        }
     }
+    // plan_ac's refusals: each limit holds, one past it (and zero) names its width in ev2g_ac_create's words, the first bad width in argument order wins
+    g_case = "actor-critic refusals";
+    const int ok[6] = {192, 256, 256, 256, 256, 64};   // d_in, h1, h2, v1, v2, d_out at their limits
+    const char *const word[6] = {"d_in must be 1 .. 192", "h1 must be 1 .. 256", "h2 must be 1 .. 256", "v1 must be 1 .. 256", "v2 must be 1 .. 256", "d_out must be 1 .. 64"};
+    CHECK(plan_ac(ok[0], ok[1], ok[2], ok[3], ok[4], ok[5]).err == EV2G_OK && plan_ac(1, 1, 1, 1, 1, 1).err == EV2G_OK);
+    CHECK(plan_ac(1, 1, 1, 1, 1, 1).refusal.empty());
+    for (int i = 0; i < 6; i++)
+        for (int bad : {ok[i] + 1, 0, -1}) {
+            int n[6];
+            for (int j = 0; j < 6; j++) n[j] = j == i ? bad : ok[j] - 1;
+            const AcPlan p = plan_ac(n[0], n[1], n[2], n[3], n[4], n[5]);
+            CHECK(p.err == EV2G_ERR_ARG && p.refusal == std::string("ev2g_ac_create: ") + word[i]);
+            for (int j = i + 1; j < 6; j++) {   // a second bad width behind it does not change the message
+                int m[6];
+                for (int k = 0; k < 6; k++) m[k] = k == j ? ok[k] + 1 : n[k];
+                CHECK(plan_ac(m[0], m[1], m[2], m[3], m[4], m[5]).refusal == p.refusal);
+            }
+            n[i] = bad > 0 ? ok[i] : 1;   // the limit itself, and the smallest width
+            CHECK(plan_ac(n[0], n[1], n[2], n[3], n[4], n[5]).err == EV2G_OK);
+        }
 }
 
 int main() {
