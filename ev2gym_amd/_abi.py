@@ -140,6 +140,11 @@ class PpoConfigC(C.Structure):   # ev2g_ppo_config, in header order
                 ("vf_coef", C.c_double), ("ent_coef", C.c_double), ("max_grad_norm", C.c_double), ("normalize_advantage", C.c_int32)]
 
 
+class A2cConfigC(C.Structure):   # ev2g_a2c_config, in header order
+    _fields_ = [("lr", C.c_double), ("alpha", C.c_double), ("rms_eps", C.c_double), ("vf_coef", C.c_double), ("ent_coef", C.c_double),
+                ("max_grad_norm", C.c_double), ("normalize_advantage", C.c_int32), ("use_rms_prop", C.c_int32)]
+
+
 class PpoInfoC(C.Structure):   # ev2g_ppo_info
     _fields_ = [("lds_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("grid_cap", C.c_int32), ("n_params", C.c_int32)]
 

@@ -130,23 +130,27 @@ struct ev2g_acpolicy {
     float *clipped = nullptr;
     size_t clipped_elems = 0;
     std::vector<float> log_std;           // the values last uploaded (ev2g_ac_get_weights returns them when no learner is bound)
-    struct ev2g_ppo *learner = nullptr;   // the PPO learner bound to this policy (ev2g_ppo_create), destroyed with it
+    struct ev2g_ppo *learner = nullptr;   // the learner bound to this policy (ev2g_ppo_create / ev2g_a2c_create), destroyed with it
 };
 
-// a PPO learner (ev2g_ppo_create, ev2g_ppo.h): float32 masters of the thirteen arrays in SB3's layout with Adam's m and v, the gradient of the
-// last ev2g_ppo_grad, the transposed images backprop reads, and the gradient kernel's workspace
+// the learner of an actor-critic (ev2g_ppo_create / ev2g_a2c_create, ev2g_ppo.h): float32 masters of the thirteen arrays in SB3's layout with
+// the optimiser's state (Adam's m and v; RMSprop's square average in v), the gradient of the last grad call, the transposed images backprop
+// reads, and the gradient kernel's workspace
+enum { LEARNER_PPO = 0, LEARNER_A2C = 1 };
 struct ev2g_ppo {
+    int kind = LEARNER_PPO;
     ev2g_acpolicy *ac = nullptr;
     PpoPlan plan;
-    ev2g_ppo_config cfg{};
+    ev2g_ppo_config cfg{};     // LEARNER_PPO
+    ev2g_a2c_config a2c{};     // LEARNER_A2C
     std::vector<void *> allocs;
     float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *work = nullptr;
     double *stat_part = nullptr, *norm_part = nullptr, *advstat = nullptr;
     PpoDev dev{};
     PpoMap map{};
     int n_blocks = 0;          // blocks of the reduce / apply launches: ceil(n_params / 256)
-    long long t = 0;           // Adam's step count
-    bool have_grad = false;    // a gradient no ev2g_ppo_apply has consumed yet
+    long long t = 0;           // the optimiser's step count
+    bool have_grad = false;    // a gradient no apply has consumed yet
 };
 
 static void ppo_free(ev2g_ppo *p) {
@@ -256,8 +260,8 @@ struct ev2g_handle {
     std::vector<ev2g_grid *> grids;             // the distribution grids created on this handle (freed with it)
     std::vector<ev2g_wrap *> wraps;             // the action wrappers created on this handle (freed with it)
     std::vector<ev2g_acpolicy *> acs;           // the Gaussian actor-critics created on this handle (freed with it)
-    std::vector<ev2g_ppo *> ppos;               // the PPO learners created on this handle (freed with it, or with their policy)
-    unsigned ppo_attr_mask = 0;                 // ev2g_ppo_grad_kernel instantiations whose dynamic-LDS attribute was set
+    std::vector<ev2g_ppo *> ppos;               // the learners (PPO and A2C) created on this handle (freed with it, or with their policy)
+    unsigned ppo_attr_mask = 0;                 // ev2g_ppo_grad_kernel instantiations (bit relu + 2 head) whose dynamic-LDS attribute was set
     unsigned ac_attr_mask = 0;                  // ev2g_ac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
 };
 
@@ -434,24 +438,25 @@ static const AcEntry &ac_kernel(int relu) {
     return tab[relu ? 1 : 0];
 }
 
-// ev2g_ppo_grad_kernel<activation>: the kernel (ev2g_ppo_create sets its dynamic-LDS attribute) and its launch
+// ev2g_ppo_grad_kernel<activation, head>: the kernel (ev2g_ppo_create sets its dynamic-LDS attribute) and its launch
 struct PpoGradEntry {
     const void *fn;
     void (*launch)(const LaunchDims &, const AcDev &, const PpoDev &, const PpoLds &, const PpoHyper &, const float *obs, const float *actions,
                    const float *old_lp, const float *adv, const float *ret, const int *idx, int B, const double *advstat, float *work, double *stat_part);
 };
-template <int ACT>
+template <int ACT, int HEAD>
 static void launch_ppo_grad(const LaunchDims &d, const AcDev &ac, const PpoDev &dev, const PpoLds &lds, const PpoHyper &hp, const float *obs,
                             const float *actions, const float *old_lp, const float *adv, const float *ret, const int *idx, int B, const double *advstat,
                             float *work, double *stat_part) {
-    hipLaunchKernelGGL(ev2g_ppo_grad_kernel<ACT>, d.grid, dim3(EV2G_PPO_BLOCK), d.lds, d.stream, ac, dev, lds, hp, obs, actions, old_lp, adv, ret, idx, B, advstat,
+    hipLaunchKernelGGL((ev2g_ppo_grad_kernel<ACT, HEAD>), d.grid, dim3(EV2G_PPO_BLOCK), d.lds, d.stream, ac, dev, lds, hp, obs, actions, old_lp, adv, ret, idx, B, advstat,
                        work, stat_part);
 }
-template <int ACT>
-static PpoGradEntry ppo_grad_entry() { return {(const void *)ev2g_ppo_grad_kernel<ACT>, &launch_ppo_grad<ACT>}; }
-static const PpoGradEntry &ppo_grad_kernel(int relu) {
-    static const PpoGradEntry tab[2] = {ppo_grad_entry<EV2G_AC_TANH>(), ppo_grad_entry<EV2G_AC_RELU>()};
-    return tab[relu ? 1 : 0];
+template <int ACT, int HEAD>
+static PpoGradEntry ppo_grad_entry() { return {(const void *)ev2g_ppo_grad_kernel<ACT, HEAD>, &launch_ppo_grad<ACT, HEAD>}; }
+static const PpoGradEntry &ppo_grad_kernel(int relu, int head) {
+    static const PpoGradEntry tab[2][2] = {{ppo_grad_entry<EV2G_AC_TANH, EV2G_HEAD_PPO>(), ppo_grad_entry<EV2G_AC_RELU, EV2G_HEAD_PPO>()},
+                                           {ppo_grad_entry<EV2G_AC_TANH, EV2G_HEAD_A2C>(), ppo_grad_entry<EV2G_AC_RELU, EV2G_HEAD_A2C>()}};
+    return tab[head ? 1 : 0][relu ? 1 : 0];
 }
 
 #include "ev2g_refill_host.h"
@@ -2380,12 +2385,21 @@ int ev2g_host_gae(const double *reward, const float *values, const uint8_t *epis
     return EV2G_OK;
 }
 
-// ---- the PPO learner (ev2g_ppo.h) ----
+// ---- the learners (ev2g_ppo.h): PPO and A2C ----
 static int ppo_check(ev2g_handle *h, ev2g_ppo *p, const char *who) {
     if (!h || !p) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
     if (std::find(h->ppos.begin(), h->ppos.end(), p) == h->ppos.end())
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the learner was not created on this handle");
     (void)hipSetDevice(h->device);
+    return EV2G_OK;
+}
+
+// an entry that drives one kind of learner on the other kind
+static int learner_check(ev2g_handle *h, ev2g_ppo *p, const char *who, int kind) {
+    if (int rc = ppo_check(h, p, who)) return rc;
+    if (p->kind != kind)
+        return fail(h, EV2G_ERR_STATE, std::string(who) + (p->kind == LEARNER_A2C ? ": the learner is an A2C learner (the ev2g_a2c_* entries drive it)"
+                                                                                 : ": the learner is a PPO learner (the ev2g_ppo_* entries drive it)"));
     return EV2G_OK;
 }
 
@@ -2428,7 +2442,7 @@ static int ac_read_images(ev2g_handle *h, ev2g_acpolicy *ac, float *const out[AC
 
 // the device stage of a learner: allocates its buffers, takes the masters from the policy's images, builds the map the kernels place elements by,
 // fills the transposed images and sets the gradient kernel's dynamic-LDS attribute
-static int ppo_device_stage(ev2g_handle *h, ev2g_ppo *p, ev2g_acpolicy *ac) {
+static int ppo_device_stage(ev2g_handle *h, ev2g_ppo *p, ev2g_acpolicy *ac, const char *who) {
     const PpoPlan &pl = p->plan;
     const size_t G = (size_t)pl.n_params;
     const struct { float **dst; size_t n; } f32[] = {{&p->theta, G}, {&p->m, G}, {&p->v, G}, {&p->grad, G}, {&p->work, (size_t)pl.grid_cap * pl.slab_floats}};
@@ -2458,29 +2472,29 @@ static int ppo_device_stage(ev2g_handle *h, ev2g_ppo *p, ev2g_acpolicy *ac) {
     hipError_t e = hipMemcpyAsync(p->theta, host.data(), G * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) { ppo_launch_repack(h, p, true); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    const int relu = ac->relu;
-    if (e == hipSuccess && pl.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & (1u << relu))) {   // (function attributes are per device: once per handle)
-        e = hipFuncSetAttribute(ppo_grad_kernel(relu).fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
-        if (e == hipSuccess) h->ppo_attr_mask |= 1u << relu;
+    const int relu = ac->relu ? 1 : 0, head = p->kind == LEARNER_A2C ? EV2G_HEAD_A2C : EV2G_HEAD_PPO;
+    const unsigned bit = 1u << (relu + 2 * head);
+    if (e == hipSuccess && pl.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & bit)) {   // (function attributes are per device: once per handle)
+        e = hipFuncSetAttribute(ppo_grad_kernel(relu, head).fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
+        if (e == hipSuccess) h->ppo_attr_mask |= bit;
     }
-    if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string("ev2g_ppo_create: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return EV2G_OK;
 }
 
-int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cfg, ev2g_ppo **out) {
-    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: null argument");
-    *out = nullptr;
-    if (!cfg) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: cfg is null");
-    if (int rc = ac_check(h, ac, "ev2g_ppo_create")) return rc;
-    if (int rc = ppo_config_check(h, "ev2g_ppo_create", cfg->lr, cfg->clip_range, cfg)) return rc;
-    if (ac->learner) return fail(h, EV2G_ERR_STATE, "ev2g_ppo_create: the policy already has a learner");
+// plans, allocates and binds a learner of `kind` whose config (the one of its kind; the other is null) the caller has checked
+static int learner_create(ev2g_handle *h, ev2g_acpolicy *ac, const char *who, int kind, const ev2g_ppo_config *ppo_cfg, const ev2g_a2c_config *a2c_cfg,
+                          ev2g_ppo **out) {
+    if (ac->learner) return fail(h, EV2G_ERR_STATE, std::string(who) + ": the policy already has a learner");
     const AcPlan &a = ac->plan;
     const PpoPlan plan = plan_ppo(a.d_in, a.h1, a.h2, a.v1, a.v2, a.d_out);
     if (plan.err) return fail(h, plan.err, plan.refusal);
     ev2g_ppo *p = new ev2g_ppo();
-    p->plan = plan; p->cfg = *cfg;
+    p->kind = kind; p->plan = plan;
+    if (ppo_cfg) p->cfg = *ppo_cfg;
+    if (a2c_cfg) p->a2c = *a2c_cfg;
     p->n_blocks = (plan.n_params + 255) / 256;
-    if (const int rc = ppo_device_stage(h, p, ac)) {   // the one cleanup path
+    if (const int rc = ppo_device_stage(h, p, ac, who)) {   // the one cleanup path
         ppo_free(p);
         return rc;
     }
@@ -2490,32 +2504,48 @@ int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cf
     return EV2G_OK;
 }
 
+int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cfg, ev2g_ppo **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: null argument");
+    *out = nullptr;
+    if (!cfg) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: cfg is null");
+    if (int rc = ac_check(h, ac, "ev2g_ppo_create")) return rc;
+    if (int rc = ppo_config_check(h, "ev2g_ppo_create", cfg->lr, cfg->clip_range, cfg)) return rc;
+    return learner_create(h, ac, "ev2g_ppo_create", LEARNER_PPO, cfg, nullptr, out);
+}
+
 void ev2g_ppo_destroy(ev2g_handle *h, ev2g_ppo *ppo) { owned_destroy(h, &ev2g_handle::ppos, ppo, ppo_free); }
 
 int ev2g_ppo_set_rates(ev2g_handle *h, ev2g_ppo *p, double lr, double clip_range) {
-    if (int rc = ppo_check(h, p, "ev2g_ppo_set_rates")) return rc;
+    if (int rc = learner_check(h, p, "ev2g_ppo_set_rates", LEARNER_PPO)) return rc;
     if (int rc = ppo_config_check(h, "ev2g_ppo_set_rates", lr, clip_range, nullptr)) return rc;
     p->cfg.lr = lr; p->cfg.clip_range = clip_range;
     return EV2G_OK;
 }
 
-static int ppo_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, const float *obs, const float *actions, const float *old_lp, const float *adv,
-                    const float *ret, const int32_t *idx, int B, float *stats) {
-    if (int rc = ppo_check(h, p, who)) return rc;
-    if (!obs || !actions || !old_lp || !adv || !ret || !idx) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (B < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B must be at least 1");
+// the launches of a gradient: the advantage statistics if asked for, the gradient kernel with the learner's head, the reduction
+static int learner_grad_launch(ev2g_handle *h, ev2g_ppo *p, const PpoHyper &hp, const float *obs, const float *actions, const float *old_lp,
+                               const float *adv, const float *ret, const int32_t *idx, int B, float *stats) {
     const PpoPlan &pl = p->plan;
-    const PpoHyper hp{(float)p->cfg.clip_range, (float)p->cfg.vf_coef, (float)p->cfg.ent_coef, p->cfg.normalize_advantage ? 1 : 0};
     if (hp.normalize && B > 1) hipLaunchKernelGGL(ev2g_ppo_advstat_kernel, dim3(1), dim3(1024), 0, h->stream, adv, (const int *)idx, B, p->advstat);
     const int chunks = (B + EV2G_PPO_ROWS - 1) / EV2G_PPO_ROWS, n_wg = chunks < pl.grid_cap ? chunks : pl.grid_cap;
     const LaunchDims dims{dim3((unsigned)n_wg), pl.lds.bytes, h->stream};
-    ppo_grad_kernel(p->ac->relu).launch(dims, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv, ret, (const int *)idx, B, (const double *)p->advstat, p->work,
-                                        p->stat_part);
+    const int head = p->kind == LEARNER_A2C ? EV2G_HEAD_A2C : EV2G_HEAD_PPO;
+    ppo_grad_kernel(p->ac->relu, head).launch(dims, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv, ret, (const int *)idx, B, (const double *)p->advstat,
+                                              p->work, p->stat_part);
     hipLaunchKernelGGL(ev2g_ppo_reduce_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->work,
                        (const double *)p->stat_part, n_wg, B, hp, p->dev.log_std, p->grad, p->norm_part, stats);
     HIPCHK(h, hipGetLastError());
     p->have_grad = true;
     return EV2G_OK;
+}
+
+static int ppo_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, const float *obs, const float *actions, const float *old_lp, const float *adv,
+                    const float *ret, const int32_t *idx, int B, float *stats) {
+    if (int rc = learner_check(h, p, who, LEARNER_PPO)) return rc;
+    if (!obs || !actions || !old_lp || !adv || !ret || !idx) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B must be at least 1");
+    const PpoHyper hp{(float)p->cfg.clip_range, (float)p->cfg.vf_coef, (float)p->cfg.ent_coef, p->cfg.normalize_advantage ? 1 : 0};
+    return learner_grad_launch(h, p, hp, obs, actions, old_lp, adv, ret, idx, B, stats);
 }
 
 static AdamStep adam_step(double lr, double beta1, double beta2, double eps, long long t) {
@@ -2524,7 +2554,7 @@ static AdamStep adam_step(double lr, double beta1, double beta2, double eps, lon
 }
 
 static int ppo_apply(ev2g_handle *h, ev2g_ppo *p, const char *who) {
-    if (int rc = ppo_check(h, p, who)) return rc;
+    if (int rc = learner_check(h, p, who, LEARNER_PPO)) return rc;
     if (!p->have_grad) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_ppo_grad first)");
     const ev2g_ppo_config &c = p->cfg;
     p->t += 1;
@@ -2547,6 +2577,78 @@ int ev2g_ppo_minibatch(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const fl
                        const float *returns, const int32_t *idx, int B, float *stats) {
     if (int rc = ppo_grad(h, ppo, "ev2g_ppo_minibatch", obs, actions, old_log_prob, advantages, returns, idx, B, stats)) return rc;
     return ppo_apply(h, ppo, "ev2g_ppo_minibatch");
+}
+
+// ---- A2C: the same learner object with the ratio-free head and RMSprop (or Adam(eps 1e-5) when use_rms_prop is 0) ----
+static int a2c_config_check(ev2g_handle *h, const char *who, double lr, const ev2g_a2c_config *c) {
+    auto bad = [&](const char *name, const char *range) { return fail(h, EV2G_ERR_ARG, std::string(who) + ": " + name + " must be " + range); };
+    if (!std::isfinite(lr) || lr < 0.0) return bad("lr", "finite and >= 0");
+    if (!c) return EV2G_OK;
+    if (!std::isfinite(c->alpha) || c->alpha < 0.0 || c->alpha >= 1.0) return bad("alpha", "in [0, 1)");
+    if (!std::isfinite(c->rms_eps) || c->rms_eps <= 0.0) return bad("rms_eps", "finite and > 0");
+    if (!std::isfinite(c->vf_coef) || c->vf_coef < 0.0) return bad("vf_coef", "finite and >= 0");
+    if (!std::isfinite(c->ent_coef) || c->ent_coef < 0.0) return bad("ent_coef", "finite and >= 0");
+    if (!std::isfinite(c->max_grad_norm) || c->max_grad_norm <= 0.0) return bad("max_grad_norm", "finite and > 0");
+    return EV2G_OK;
+}
+
+int ev2g_a2c_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_a2c_config *cfg, ev2g_ppo **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_a2c_create: null argument");
+    *out = nullptr;
+    if (!cfg) return fail(h, EV2G_ERR_ARG, "ev2g_a2c_create: cfg is null");
+    if (int rc = ac_check(h, ac, "ev2g_a2c_create")) return rc;
+    if (int rc = a2c_config_check(h, "ev2g_a2c_create", cfg->lr, cfg)) return rc;
+    return learner_create(h, ac, "ev2g_a2c_create", LEARNER_A2C, nullptr, cfg, out);
+}
+
+int ev2g_a2c_set_rate(ev2g_handle *h, ev2g_ppo *p, double lr) {
+    if (int rc = learner_check(h, p, "ev2g_a2c_set_rate", LEARNER_A2C)) return rc;
+    if (int rc = a2c_config_check(h, "ev2g_a2c_set_rate", lr, nullptr)) return rc;
+    p->a2c.lr = lr;
+    return EV2G_OK;
+}
+
+static int a2c_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, const float *obs, const float *actions, const float *adv, const float *ret,
+                    const int32_t *idx, int B, float *stats) {
+    if (int rc = learner_check(h, p, who, LEARNER_A2C)) return rc;
+    if (!obs || !actions || !adv || !ret || !idx) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B must be at least 1");
+    if (p->a2c.normalize_advantage && B == 1)
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": normalize_advantage needs B >= 2 (the unbiased std of one advantage is undefined)");
+    const PpoHyper hp{0.0f, (float)p->a2c.vf_coef, (float)p->a2c.ent_coef, p->a2c.normalize_advantage ? 1 : 0};
+    return learner_grad_launch(h, p, hp, obs, actions, nullptr, adv, ret, idx, B, stats);
+}
+
+static RmsStep rms_step(double lr, double alpha, double eps) { return {(float)alpha, (float)(1.0 - alpha), (float)lr, (float)eps}; }
+
+static int a2c_apply(ev2g_handle *h, ev2g_ppo *p, const char *who) {
+    if (int rc = learner_check(h, p, who, LEARNER_A2C)) return rc;
+    if (!p->have_grad) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_a2c_grad first)");
+    const ev2g_a2c_config &c = p->a2c;
+    p->t += 1;
+    if (c.use_rms_prop)
+        hipLaunchKernelGGL(ev2g_a2c_apply_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->grad,
+                           (const double *)p->norm_part, p->n_blocks, (float)c.max_grad_norm, rms_step(c.lr, c.alpha, c.rms_eps), p->theta, p->v);
+    else   // what SB3's policy builds when RMSprop is switched off: torch.optim.Adam(eps = 1e-5)
+        hipLaunchKernelGGL(ev2g_ppo_apply_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->grad,
+                           (const double *)p->norm_part, p->n_blocks, (float)c.max_grad_norm, adam_step(c.lr, 0.9, 0.999, 1e-5, p->t), p->theta, p->m,
+                           p->v);
+    HIPCHK(h, hipGetLastError());
+    p->have_grad = false;
+    return EV2G_OK;
+}
+
+int ev2g_a2c_grad(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *advantages, const float *returns,
+                  const int32_t *idx, int B, float *stats) {
+    return a2c_grad(h, learner, "ev2g_a2c_grad", obs, actions, advantages, returns, idx, B, stats);
+}
+
+int ev2g_a2c_apply(ev2g_handle *h, ev2g_ppo *learner) { return a2c_apply(h, learner, "ev2g_a2c_apply"); }
+
+int ev2g_a2c_update(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *advantages, const float *returns,
+                    const int32_t *idx, int B, float *stats) {
+    if (int rc = a2c_grad(h, learner, "ev2g_a2c_update", obs, actions, advantages, returns, idx, B, stats)) return rc;
+    return a2c_apply(h, learner, "ev2g_a2c_update");
 }
 
 // a flat [n_params] device buffer into the thirteen host arrays
@@ -2622,6 +2724,54 @@ int ev2g_host_ppo_head(const float *mean, const float *value, const float *actio
         for (int j = 0; j < 8; j++) q[j] = ev2g_ppo_lp_part(mu, a, log_std, iv.data(), P, j, 8);
         const float A = norm ? (float)(((double)advantages[i] - a_mean) * a_scale) : advantages[i];
         const PpoRow o = ev2g_ppo_head_row(ev2g_ppo_join8(q), old_log_prob[i], A, returns[i], value[i], (float)cfg->clip_range, (float)cfg->vf_coef, inv_b);
+        d_value[i] = o.g_v;
+        sum[0] += o.pol; sum[1] += o.vsq; sum[2] += o.kl; sum[3] += o.clipped;
+        for (int p = 0; p < P; p++) {
+            float dl;
+            ev2g_ppo_head_port(a[p], mu[p], iv[(size_t)p], o.g_lp, d_mean + (size_t)i * P + p, &dl);
+            dls[(size_t)p] += (double)dl;
+        }
+    }
+    for (int p = 0; p < P; p++) d_log_std[p] = (float)(dls[(size_t)p] - cfg->ent_coef);
+    ev2g_ppo_stats(sum, log_std, P, inv_b, (float)cfg->vf_coef, (float)cfg->ent_coef, stats);
+    return EV2G_OK;
+}
+
+int ev2g_host_rmsprop(float *theta, float *sq, const float *g, int64_t n, double lr, double alpha, double eps) {
+    if (!theta || !sq || !g || n < 0) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_rmsprop: null argument or n < 0");
+    if (!std::isfinite(lr) || !(alpha >= 0.0 && alpha < 1.0) || !(eps > 0.0))
+        return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_rmsprop: lr must be finite, alpha in [0, 1), eps > 0");
+    const RmsStep s = rms_step(lr, alpha, eps);
+    for (int64_t i = 0; i < n; i++) ev2g_rmsprop_elem(theta + i, sq + i, g[i], s);
+    return EV2G_OK;
+}
+
+int ev2g_host_a2c_head(const float *mean, const float *value, const float *actions, const float *log_std, const float *advantages,
+                       const float *returns, int B, int P, const ev2g_a2c_config *cfg, float *d_mean, float *d_value, float *d_log_std, float *stats) {
+    if (!mean || !value || !actions || !log_std || !advantages || !returns || !cfg || !d_mean || !d_value || !d_log_std || !stats)
+        return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: null argument");
+    if (B < 1 || P < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: B and P must be positive");
+    const bool norm = cfg->normalize_advantage != 0;
+    if (norm && B == 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: normalize_advantage needs B >= 2");
+    double a_mean = 0.0, a_scale = 1.0;
+    if (norm) {
+        double s = 0.0;
+        for (int i = 0; i < B; i++) s += (double)advantages[i];
+        a_mean = s / B;
+        s = 0.0;
+        for (int i = 0; i < B; i++) { const double d = (double)advantages[i] - a_mean; s += d * d; }
+        a_scale = 1.0 / (std::sqrt(s / (double)(B - 1)) + 1e-8);
+    }
+    std::vector<double> iv((size_t)P), dls((size_t)P, 0.0);
+    for (int p = 0; p < P; p++) iv[(size_t)p] = std::exp(-2.0 * (double)log_std[p]);
+    const double inv_b = 1.0 / (double)B;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < B; i++) {
+        const float *mu = mean + (size_t)i * P, *a = actions + (size_t)i * P;
+        double q[8];
+        for (int j = 0; j < 8; j++) q[j] = ev2g_ppo_lp_part(mu, a, log_std, iv.data(), P, j, 8);
+        const float A = norm ? (float)(((double)advantages[i] - a_mean) * a_scale) : advantages[i];
+        const PpoRow o = ev2g_a2c_head_row(ev2g_ppo_join8(q), A, returns[i], value[i], (float)cfg->vf_coef, inv_b);
         d_value[i] = o.g_v;
         sum[0] += o.pol; sum[1] += o.vsq; sum[2] += o.kl; sum[3] += o.clipped;
         for (int p = 0; p < P; p++) {

@@ -1,4 +1,5 @@
-// ev2g_ppo.h -- the learner of the Gaussian actor-critic (ev2g_ac.h): SB3's PPO.train() with default settings, one minibatch per call.
+// ev2g_ppo.h -- the learner of the Gaussian actor-critic (ev2g_ac.h): SB3's PPO.train() with default settings, one minibatch per call, and SB3's
+// A2C.train(), one update over the rows it is given.  The two differ in the head of the gradient kernel (a compile-time choice) and the optimiser.
 //
 //   ev2g_ppo_advstat_kernel   mean and unbiased std of the minibatch's gathered advantages (one workgroup, float64, fixed order)
 //   ev2g_ppo_grad_kernel      per 32 gathered rows: forward with every activation kept, the head gradients, backprop, weight gradients; a
@@ -7,6 +8,7 @@
 //                             writes one partial of the squared norm per block
 //   ev2g_ppo_apply_kernel     sums those partials in block order, clips, Adam on the float32 masters ([out, in] row-major, SB3's layout), and
 //                             rewrites the element's places in the packed images AcDev points at (pack_linear_f32's order; padding is never written)
+//   ev2g_a2c_apply_kernel     the same with torch.optim.RMSprop in Adam's place (its square average lives in the learner's v buffer)
 //
 // No float atomics anywhere and every sum has one fixed order: the same call on the same state gives the same bits.  No kernel waits on another
 // workgroup: the stages are separate launches on the handle's stream.
@@ -56,6 +58,20 @@ __host__ __device__ inline PpoRow ev2g_ppo_head_row(double lp, float old_lp, flo
     return o;
 }
 
+// A2C's head of one row: no ratio and no clip, policy_loss = -mean(A lp); the two ratio statistics are exact zeros
+__host__ __device__ inline PpoRow ev2g_a2c_head_row(double lp, float adv, float ret, float v, float vf_coef, double inv_b) {
+    PpoRow o;
+    const double A = (double)adv;
+    o.pol = A * lp;
+    o.g_lp = (float)(-A * inv_b);
+    const double dv = (double)v - (double)ret;
+    o.vsq = dv * dv;
+    o.g_v = (float)(2.0 * (double)vf_coef * dv * inv_b);
+    o.kl = 0.0;
+    o.clipped = 0.0;
+    return o;
+}
+
 // one (row, port): d loss / d mean and the row's term of d loss / d log_std
 __host__ __device__ inline void ev2g_ppo_head_port(float a, float mu, double iv, float g_lp, float *d_mu, float *d_ls) {
     const double d = (double)a - (double)mu;
@@ -84,6 +100,17 @@ __host__ __device__ inline void ev2g_adam_elem(float *theta, float *m, float *v,
     *m = mn; *v = vn;
     const float denom = sqrtf(vn) / bc2_sqrt + eps;
     *theta = *theta - step_size * (mn / denom);
+}
+
+// torch.optim.RMSprop's step of one element (no weight decay, no momentum, not centered): sq moves as mul_ then addcmul_ (oma is 1 - alpha
+// rounded from float64, as for Adam), the denominator is sqrt().add_(eps), theta moves as addcdiv_ with value -lr: (lr g) / avg.
+struct RmsStep { float alpha, oma, lr, eps; };
+__host__ __device__ inline void ev2g_rmsprop_elem(float *theta, float *sq, float g, const RmsStep &s) {
+    const float alpha = s.alpha, oma = s.oma, lr = s.lr, eps = s.eps;
+    const float sn = alpha * *sq + (oma * g) * g;
+    *sq = sn;
+    const float avg = sqrtf(sn) + eps;
+    *theta = *theta - (lr * g) / avg;
 }
 
 #ifdef __HIPCC__
@@ -173,7 +200,10 @@ __device__ __forceinline__ void ev2g_ppo_colsum(const float *__restrict__ D, int
     }
 }
 
-template <int ACT>
+// HEAD: the loss of a row, a compile-time choice.  EV2G_HEAD_A2C reads no old_lp (the host passes null).
+#define EV2G_HEAD_PPO 0
+#define EV2G_HEAD_A2C 1
+template <int ACT, int HEAD>
 __global__ void __launch_bounds__(EV2G_PPO_BLOCK) ev2g_ppo_grad_kernel(AcDev m, PpoDev q, PpoLds L, PpoHyper hp, const float *__restrict__ obs,
                                                                      const float *__restrict__ actions, const float *__restrict__ old_lp,
                                                                      const float *__restrict__ adv, const float *__restrict__ ret,
@@ -243,7 +273,8 @@ __global__ void __launch_bounds__(EV2G_PPO_BLOCK) ev2g_ppo_grad_kernel(AcDev m, 
                 if (row < nr) {
                     const int i = idx[row0 + row];
                     const float A = norm ? (float)(((double)adv[i] - a_mean) * a_scale) : adv[i];
-                    const PpoRow o = ev2g_ppo_head_row(lp, old_lp[i], A, ret[i], pv, hp.clip, hp.vf_coef, inv_b);
+                    const PpoRow o = HEAD == EV2G_HEAD_PPO ? ev2g_ppo_head_row(lp, old_lp[i], A, ret[i], pv, hp.clip, hp.vf_coef, inv_b)
+                                                           : ev2g_a2c_head_row(lp, A, ret[i], pv, hp.vf_coef, inv_b);
                     gl = o.g_lp; gv = o.g_v;
                     st0 += o.pol; st1 += o.vsq; st2 += o.kl; st3 += o.clipped;
                 }
@@ -381,29 +412,52 @@ __global__ void __launch_bounds__(256) ev2g_ppo_reduce_kernel(PpoMap mp, const f
     }
 }
 
-// clip_grad_norm_ and Adam on element i of the masters, and the element's places in the packed images
-__global__ void __launch_bounds__(256) ev2g_ppo_apply_kernel(PpoMap mp, const float *__restrict__ grad, const double *__restrict__ norm_part, int n_blocks,
-                                                           float max_grad_norm, AdamStep adam, float *__restrict__ theta, float *__restrict__ am, float *__restrict__ av) {
-    __shared__ float coef_s;
+// clip_grad_norm_'s coefficient from the reduce kernel's partials, summed in block order (thread 0 of every block; the others read coef_s after the barrier)
+__device__ __forceinline__ void ev2g_ppo_clip_coef(const double *__restrict__ norm_part, int n_blocks, float max_grad_norm, float *coef_s) {
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int b = 0; b < n_blocks; b++) s += norm_part[b];
         const float norm = (float)sqrt(s);
         const float coef = max_grad_norm / (norm + 1e-6f);
-        coef_s = coef < 1.0f ? coef : 1.0f;
+        *coef_s = coef < 1.0f ? coef : 1.0f;
     }
     __syncthreads();
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= mp.n_params) return;
-    float t = theta[i], mm = am[i], vv = av[i];
-    ev2g_adam_elem(&t, &mm, &vv, grad[i] * coef_s, adam);
-    theta[i] = t; am[i] = mm; av[i] = vv;
+}
+
+// the new value t of master element i into its places in the packed image and the transposed image
+__device__ __forceinline__ void ev2g_ppo_place(const PpoMap &mp, int i, float t) {
     const int a = ev2g_ppo_which(mp, i), e = i - mp.off[a];
     if (!mp.img[a]) return;
     if (mp.img_k[a] == 0) { mp.img[a][e] = t; return; }
     const int r = e / mp.cols[a], c = e - r * mp.cols[a];
     mp.img[a][packed_f32_index(r, c, mp.img_k[a])] = t;
     if (mp.imgT[a]) mp.imgT[a][packed_f32_index(c, r, mp.imgT_k[a])] = t;
+}
+
+// clip_grad_norm_ and Adam on element i of the masters, and the element's places in the packed images
+__global__ void __launch_bounds__(256) ev2g_ppo_apply_kernel(PpoMap mp, const float *__restrict__ grad, const double *__restrict__ norm_part, int n_blocks,
+                                                           float max_grad_norm, AdamStep adam, float *__restrict__ theta, float *__restrict__ am, float *__restrict__ av) {
+    __shared__ float coef_s;
+    ev2g_ppo_clip_coef(norm_part, n_blocks, max_grad_norm, &coef_s);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= mp.n_params) return;
+    float t = theta[i], mm = am[i], vv = av[i];
+    ev2g_adam_elem(&t, &mm, &vv, grad[i] * coef_s, adam);
+    theta[i] = t; am[i] = mm; av[i] = vv;
+    ev2g_ppo_place(mp, i, t);
+}
+
+// clip_grad_norm_ and RMSprop on element i of the masters (sq: the learner's v buffer), and the element's places in the packed images
+__global__ void __launch_bounds__(256) ev2g_a2c_apply_kernel(PpoMap mp, const float *__restrict__ grad, const double *__restrict__ norm_part, int n_blocks,
+                                                           float max_grad_norm, RmsStep rms, float *__restrict__ theta, float *__restrict__ sq) {
+    __shared__ float coef_s;
+    ev2g_ppo_clip_coef(norm_part, n_blocks, max_grad_norm, &coef_s);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= mp.n_params) return;
+    float t = theta[i], s = sq[i];
+    ev2g_rmsprop_elem(&t, &s, grad[i] * coef_s, rms);
+    theta[i] = t; sq[i] = s;
+    ev2g_ppo_place(mp, i, t);
 }
 
 // masters -> images for every element (ev2g_ppo_create, and ev2g_ac_set_weights on a bound policy, refresh the transposed images by it)

@@ -124,6 +124,13 @@ def load_library(path: Optional[str] = None):
         "ev2g_ac_get_weights": (C.c_int, [vp, vp] + [vp] * 13),
         "ev2g_host_adam": (C.c_int, [vp, vp, vp, vp, i64, i64, dbl, dbl, dbl, dbl]),
         "ev2g_host_ppo_head": (C.c_int, [vp] * 7 + [C.c_int, C.c_int, C.POINTER(_abi.PpoConfigC), vp, vp, vp, vp]),
+        "ev2g_a2c_create": (C.c_int, [vp, vp, C.POINTER(_abi.A2cConfigC), C.POINTER(vp)]),
+        "ev2g_a2c_set_rate": (C.c_int, [vp, vp, dbl]),
+        "ev2g_a2c_grad": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_a2c_apply": (C.c_int, [vp, vp]),
+        "ev2g_a2c_update": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_host_rmsprop": (C.c_int, [vp, vp, vp, i64, dbl, dbl, dbl]),
+        "ev2g_host_a2c_head": (C.c_int, [vp] * 6 + [C.c_int, C.c_int, C.POINTER(_abi.A2cConfigC), vp, vp, vp, vp]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -187,7 +194,8 @@ EXPORTED_SYMBOLS = [
     "ev2g_ac_create", "ev2g_ac_destroy", "ev2g_ac_seed", "ev2g_ac_set_log_std", "ev2g_ac_set_weights", "ev2g_ac_forward", "ev2g_ac_act",
     "ev2g_ac_collect", "ev2g_ac_host_normal", "ev2g_gae", "ev2g_host_gae",
     "ev2g_ppo_query", "ev2g_ppo_create", "ev2g_ppo_destroy", "ev2g_ppo_set_rates", "ev2g_ppo_grad", "ev2g_ppo_apply", "ev2g_ppo_minibatch",
-    "ev2g_ppo_get_grads", "ev2g_ppo_sync", "ev2g_ac_get_weights", "ev2g_host_adam", "ev2g_host_ppo_head"]
+    "ev2g_ppo_get_grads", "ev2g_ppo_sync", "ev2g_ac_get_weights", "ev2g_host_adam", "ev2g_host_ppo_head",
+    "ev2g_a2c_create", "ev2g_a2c_set_rate", "ev2g_a2c_grad", "ev2g_a2c_apply", "ev2g_a2c_update", "ev2g_host_rmsprop", "ev2g_host_a2c_head"]
 
 
 def _ptr(x):
@@ -737,6 +745,31 @@ class Engine:
     def ppo_sync(self, ppo):
         self._check(self._lib.ev2g_ppo_sync(self._h, ppo))
 
+    # ---- the A2C learner (include/ev2g.h: ev2g_a2c_*); ppo_destroy / ppo_get_grads / ppo_sync serve it too ------------------------------
+    def a2c_create(self, ac, lr=7e-4, alpha=0.99, rms_eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=False,
+                   use_rms_prop=True):
+        """An A2C learner bound to the device policy `ac` (ev2g_a2c_create), freed by ppo_destroy, with its policy or with the engine."""
+        cfg = _abi.A2cConfigC(float(lr), float(alpha), float(rms_eps), float(vf_coef), float(ent_coef), float(max_grad_norm),
+                              int(bool(normalize_advantage)), int(bool(use_rms_prop)))
+        out = C.c_void_p()
+        self._check(self._lib.ev2g_a2c_create(self._h, ac, C.byref(cfg), C.byref(out)))
+        return out.value
+
+    def a2c_set_rate(self, learner, lr):
+        self._check(self._lib.ev2g_a2c_set_rate(self._h, learner, float(lr)))
+
+    def a2c_grad(self, learner, obs, actions, advantages, returns, idx, B, stats=None):
+        """The gradient of one update over rows idx [B] (int32) of the DEVICE float32 arrays; stays in the learner.  stats: float32 [6] DEVICE or None."""
+        self._check(self._lib.ev2g_a2c_grad(self._h, learner, _ptr(obs), _ptr(actions), _ptr(advantages), _ptr(returns), _ptr(idx), int(B),
+                                            _ptr(stats)))
+
+    def a2c_apply(self, learner):
+        self._check(self._lib.ev2g_a2c_apply(self._h, learner))
+
+    def a2c_update(self, learner, obs, actions, advantages, returns, idx, B, stats=None):
+        self._check(self._lib.ev2g_a2c_update(self._h, learner, _ptr(obs), _ptr(actions), _ptr(advantages), _ptr(returns), _ptr(idx), int(B),
+                                              _ptr(stats)))
+
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
         if out is not None:
@@ -926,6 +959,32 @@ def host_ppo_head(mean, value, actions, log_std, old_log_prob, advantages, retur
     rc = L.ev2g_host_ppo_head(mean.ctypes.data, value.ctypes.data, actions.ctypes.data, log_std.ctypes.data, old_log_prob.ctypes.data,
                               advantages.ctypes.data, returns.ctypes.data, B, P, C.byref(cfg), dm.ctypes.data, dv.ctypes.data, dl.ctypes.data,
                               st.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+    return dm, dv, dl, st
+
+
+def host_rmsprop(theta, sq, g, lr=7e-4, alpha=0.99, eps=1e-5):
+    """Host twin of the A2C learner's RMSprop (ev2g_host_rmsprop, the device's element function): float32 arrays theta / sq are updated IN PLACE."""
+    for a in (theta, sq):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    g = np.ascontiguousarray(g, np.float32)
+    L = load_library()
+    rc = L.ev2g_host_rmsprop(theta.ctypes.data, sq.ctypes.data, g.ctypes.data, theta.size, float(lr), float(alpha), float(eps))
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+
+
+def host_a2c_head(mean, value, actions, log_std, advantages, returns, vf_coef=0.5, ent_coef=0.0, normalize_advantage=False):
+    """Host twin of the gradient kernel's A2C head (ev2g_host_a2c_head): (d_mean [B, P], d_value [B], d_log_std [P], stats [6]) float32."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
+    mean, value, actions, log_std, advantages, returns = map(f, (mean, value, actions, log_std, advantages, returns))
+    B, P = mean.shape
+    cfg = _abi.A2cConfigC(0.0, 0.99, 1e-5, float(vf_coef), float(ent_coef), 0.5, int(bool(normalize_advantage)), 1)
+    dm, dv, dl, st = np.empty((B, P), np.float32), np.empty(B, np.float32), np.empty(P, np.float32), np.empty(6, np.float32)
+    L = load_library()
+    rc = L.ev2g_host_a2c_head(mean.ctypes.data, value.ctypes.data, actions.ctypes.data, log_std.ctypes.data, advantages.ctypes.data,
+                              returns.ctypes.data, B, P, C.byref(cfg), dm.ctypes.data, dv.ctypes.data, dl.ctypes.data, st.ctypes.data)
     if rc != 0:
         raise EngineError(rc, L.ev2g_last_error(None).decode())
     return dm, dv, dl, st

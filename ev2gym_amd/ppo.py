@@ -14,8 +14,9 @@ Box action space:
     loss = -mean(min(A^ r, A^ clip(r, 1 - c, 1 + c))) + ent_coef * (-entropy) + vf_coef * mean((R - v)^2)
     g <- g * min(1, max_grad_norm / (|g| + 1e-6));  torch.optim.Adam(eps=1e-5), no amsgrad, no weight decay
 
-Out of scope, refused where a caller could ask for them: `clip_range_vf`, `target_kl`, A2C and TRPO, learning-rate schedules as objects (the
-rate is settable between calls: `set_rates`), action masks, orthogonal initialisation (weights arrive from the caller).
+A2C is `ev2gym_amd.a2c.A2CLearner`.  Out of scope, refused where a caller could ask for them: `clip_range_vf`, `target_kl`, TRPO, learning-rate
+schedules as objects (the rate is settable between calls: `set_rates`), action masks, orthogonal initialisation (weights arrive from the
+caller).
 """
 from __future__ import annotations
 
@@ -92,16 +93,16 @@ def adam_numpy(theta, m, v, g, t, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-5):
     return theta - step * m / (np.sqrt(v) / math.sqrt(1.0 - beta2 ** t) + eps), m, v
 
 
-def check_batch(policy, batch):
+def check_batch(policy, batch, who="PPOLearner.train"):
     """The row count of a RolloutBatch (its arrays flattened to [n_steps * E, ...]); ValueError unless widths and row counts fit `policy`."""
     if getattr(batch, "use_masks", False):
-        raise ValueError("PPOLearner.train: action masks are out of scope (the batch's action_masks are not read)")
+        raise ValueError(f"{who}: action masks are out of scope (the batch's action_masks are not read)")
     obs, actions = batch["observations"], batch["actions"]
     if obs.shape[-1] != policy.d_in or actions.shape[-1] != policy.d_out:
-        raise ValueError(f"PPOLearner.train: the batch has rows {obs.shape[-1]} -> {actions.shape[-1]}, the policy maps {policy.d_in} -> {policy.d_out}")
+        raise ValueError(f"{who}: the batch has rows {obs.shape[-1]} -> {actions.shape[-1]}, the policy maps {policy.d_in} -> {policy.d_out}")
     N = obs.numel() // policy.d_in
     if N < 1 or actions.numel() != N * policy.d_out or any(batch[k].numel() != N for k in ("log_probs", "advantages", "returns")):
-        raise ValueError(f"PPOLearner.train: the batch's arrays do not all have {N} rows")
+        raise ValueError(f"{who}: the batch's arrays do not all have {N} rows")
     return N
 
 

@@ -712,7 +712,8 @@ int ev2g_gae(ev2g_handle *h, const double *reward, const float *values, const ui
 int ev2g_host_gae(const double *reward, const float *values, const uint8_t *episode_starts, const float *last_values, const uint8_t *last_dones,
                   int k, int n_envs, double gamma, double lambda, float *advantages, float *returns);
 
-/* ---- the PPO learner of a Gaussian actor-critic (csrc/ev2g_ppo.h) ----------------------------
+/* ---- the learners of a Gaussian actor-critic (csrc/ev2g_ppo.h): PPO here, A2C below ------------
+ * A learner object (struct ev2g_ppo, of either kind) belongs to one policy; a policy has at most one.
  * SB3's PPO.train() with default settings for ActorCriticPolicy on a Box action space, one minibatch per call, on the device: the forward with
  * every activation kept, the clipped-surrogate / value / entropy loss, backprop, clip_grad_norm_, torch.optim.Adam on float32 masters in SB3's
  * [out, in] layout, and the rewrite of the packed weight images the policy object's launches read.  float32 throughout, matrix products on the
@@ -721,7 +722,7 @@ int ev2g_host_gae(const double *reward, const float *values, const uint8_t *epis
  *   A^ = (A - mean(A)) / (std(A) + 1e-8) with the unbiased std, when normalize_advantage is set and B > 1, else A
  *   loss = -mean(min(A^ r, A^ clip(r, 1 - c, 1 + c))) + ent_coef * (-entropy) + vf_coef * mean((R - v)^2)
  *   statistics [6]: policy_loss, value_loss, entropy_loss, loss, approx_kl = mean((r - 1) - log r), clip_fraction = mean(|r - 1| > c)
- * Not reproduced (there is nothing to ask them with): clip_range_vf, target_kl, A2C / TRPO, schedule objects (ev2g_ppo_set_rates between calls
+ * Not reproduced (there is nothing to ask them with): clip_range_vf, target_kl, TRPO, schedule objects (ev2g_ppo_set_rates between calls
  * drives one), action masks, orthogonal initialisation.
  * LIMITS: every network with d_in <= 192, d_out <= 64 and hidden widths <= 64 is accepted, wider ones as far as the gradient kernel's LDS plan
  * fits the CU's 160 KiB (ev2g_ppo_query tells); anything else is EV2G_ERR_ARG at create with a message naming the width. */
@@ -773,6 +774,43 @@ int ev2g_host_adam(float *theta, float *m, float *v, const float *g, int64_t n, 
 int ev2g_host_ppo_head(const float *mean, const float *value, const float *actions, const float *log_std, const float *old_log_prob,
                        const float *advantages, const float *returns, int B, int P, const ev2g_ppo_config *cfg, float *d_mean, float *d_value,
                        float *d_log_std, float *stats);
+
+/* ---- the A2C learner: SB3's A2C.train() with default settings, one update per call over the rows it is given ----
+ * The same learner object, gradient kernel (with a ratio-free head, a compile-time choice), reduction and limits as PPO's; the optimiser is
+ * torch.optim.RMSprop, which is what SB3's A2C builds by default.
+ *   lp_i as above;  A^ = (A - mean(A)) / (std(A) + 1e-8), unbiased std, if normalize_advantage (default off), else A
+ *   loss = -mean(A^ lp) + ent_coef * (-entropy) + vf_coef * mean((R - v)^2);   g <- g * min(1, max_grad_norm / (|g| + 1e-6))
+ *   RMSprop(lr, alpha, eps, no weight decay, no momentum, not centered): sq <- alpha sq + (1 - alpha) g g;  theta <- theta - lr g / (sqrt(sq) + eps)
+ *   statistics [6] in ev2g_ppo_grad's order; approx_kl and clip_fraction are exactly 0.
+ * use_rms_prop = 0 selects torch.optim.Adam(betas 0.9 / 0.999, eps 1e-5), what SB3's policy builds when RMSprop is switched off.
+ * Not reproduced: RMSpropTFLike, schedule objects (ev2g_a2c_set_rate between calls drives one), action masks, TRPO.
+ * ev2g_ppo_destroy, ev2g_ppo_get_grads, ev2g_ppo_sync, ev2g_ppo_query and ev2g_ac_get_weights serve both kinds, and ev2g_ac_set_weights /
+ * ev2g_ac_set_log_std reset the masters of both (the optimiser's state is kept).  ev2g_ppo_grad / _apply / _minibatch / _set_rates on an A2C
+ * learner, and the ev2g_a2c_* entries on a PPO learner, are EV2G_ERR_STATE. */
+typedef struct ev2g_a2c_config {
+    double lr, alpha, rms_eps;                 /* SB3's A2C: 7e-4, 0.99, 1e-5.  lr >= 0, alpha in [0, 1), rms_eps > 0 */
+    double vf_coef, ent_coef, max_grad_norm;   /* 0.5, 0.0, 0.5.  coefficients >= 0, max_grad_norm > 0 */
+    int32_t normalize_advantage;               /* 0 */
+    int32_t use_rms_prop;                      /* 1; 0: Adam(0.9, 0.999, eps 1e-5) */
+} ev2g_a2c_config;
+/* As ev2g_ppo_create: one learner per policy of either kind (EV2G_ERR_STATE for a second), the same accepted networks, EV2G_ERR_ARG naming the
+ * field for a non-finite or out-of-range config value.  The optimiser's state starts at zero. */
+int ev2g_a2c_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_a2c_config *cfg, ev2g_ppo **out);
+int ev2g_a2c_set_rate(ev2g_handle *h, ev2g_ppo *learner, double lr);
+/* The gradient of one update over rows idx[0 .. B) of the DEVICE float32 arrays (as ev2g_ppo_grad, without old_log_prob): duplicates allowed,
+ * B >= 1; normalize_advantage with B == 1 is EV2G_ERR_ARG (SB3 would produce NaN).  stats float32 [6] DEVICE, may be NULL. */
+int ev2g_a2c_grad(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *advantages, const float *returns,
+                  const int32_t *idx, int B, float *stats);
+/* clip_grad_norm_, the optimiser's step, repack: consumes the gradient of the last ev2g_a2c_grad (EV2G_ERR_STATE without one). */
+int ev2g_a2c_apply(ev2g_handle *h, ev2g_ppo *learner);
+/* ev2g_a2c_grad then ev2g_a2c_apply, no host round trip. */
+int ev2g_a2c_update(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *advantages, const float *returns,
+                    const int32_t *idx, int B, float *stats);
+/* Host twins.  ev2g_host_rmsprop: n elements of theta / sq updated by gradient g (torch.optim.RMSprop as above).  ev2g_host_a2c_head: as
+ * ev2g_host_ppo_head with A2C's head. */
+int ev2g_host_rmsprop(float *theta, float *sq, const float *g, int64_t n, double lr, double alpha, double eps);
+int ev2g_host_a2c_head(const float *mean, const float *value, const float *actions, const float *log_std, const float *advantages,
+                       const float *returns, int B, int P, const ev2g_a2c_config *cfg, float *d_mean, float *d_value, float *d_log_std, float *stats);
 
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
