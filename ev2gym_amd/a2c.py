@@ -21,16 +21,13 @@ ask for them: `RMSpropTFLike` (and any other `policy_kwargs`), learning-rate sch
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 
 from . import _abi
 from .onpolicy import SB3_KEYS, SB3_LOG_STD
-from .ppo import check_batch, clip_grad_norm_numpy
+from .ppo import _backward, _forward, _Learner, check_batch, clip_grad_norm_numpy
 
 STAT_NAMES = _abi.PPO_STATS[:4]   # ev2g_a2c_grad writes six statistics in ev2g_ppo_grad's order; the two ratio ones are exact zeros
-_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
 def a2c_update_numpy(weights, log_std, obs, actions, advantages, returns, idx, activation="tanh", vf_coef=0.5, ent_coef=0.0,
@@ -38,42 +35,20 @@ def a2c_update_numpy(weights, log_std, obs, actions, advantages, returns, idx, a
     """One update of A2C's loss in float64 with analytic backprop.  weights: the twelve arrays of GaussianActorCritic's order; idx: the rows of
     the flattened rollout.  Returns (grads, stats, aux): the thirteen gradients (the twelve arrays' order, then log_std), the six statistics
     (ev2g_ppo_grad's order, the last two 0) and a dict of intermediates (lp, adv, mean, value, the pre-activations z)."""
-    w = [np.asarray(a, np.float64) for a in weights]
-    ls = np.asarray(log_std, np.float64)
     idx = np.asarray(idx, np.int64)
-    x, a = np.asarray(obs, np.float64)[idx], np.asarray(actions, np.float64)[idx]
+    n = _forward(weights, log_std, obs, actions, idx, activation)
     A, R = (np.asarray(v, np.float64)[idx] for v in (advantages, returns))
-    B = len(idx)
-    tanh = activation == "tanh"
-    act = np.tanh if tanh else (lambda z: np.maximum(z, 0.0))
-    dact = (lambda h: 1.0 - h * h) if tanh else (lambda h: (h > 0.0).astype(np.float64))
-    z1 = x @ w[0].T + w[1]; h1 = act(z1)
-    z2 = h1 @ w[2].T + w[3]; h2 = act(z2)
-    y1 = x @ w[4].T + w[5]; v1 = act(y1)
-    y2 = v1 @ w[6].T + w[7]; v2 = act(y2)
-    mu = h2 @ w[8].T + w[9]
-    v = (v2 @ w[10].T + w[11])[:, 0]
-    iv = np.exp(-2.0 * ls)
-    d = a - mu
-    lp = (-(d * d) * (0.5 * iv) - ls - _HALF_LOG_2PI).sum(axis=1)
+    B, lp, v = len(idx), n.lp, n.v
     if normalize_advantage:
         if B < 2:
             raise ValueError("a2c_update_numpy: normalize_advantage needs at least two rows (the unbiased std of one advantage is undefined)")
         A = (A - A.mean()) / (A.std(ddof=1) + 1e-8)
-    entropy = (0.5 + _HALF_LOG_2PI + ls).sum()
-    pl, vl, el = -(A * lp).mean(), ((R - v) ** 2).mean(), -entropy
+    pl, vl, el = -(A * lp).mean(), ((R - v) ** 2).mean(), -n.entropy
     stats = np.array([pl, vl, el, pl + ent_coef * el + vf_coef * vl, 0.0, 0.0])
     g_lp = -A / B
     g_v = 2.0 * vf_coef * (v - R) / B
-    d_mu = g_lp[:, None] * d * iv
-    d_ls = (g_lp[:, None] * (d * d * iv - 1.0)).sum(axis=0) - ent_coef
-    d2 = (d_mu @ w[8]) * dact(h2)
-    d1 = (d2 @ w[2]) * dact(h1)
-    e2 = (g_v[:, None] * w[10]) * dact(v2)
-    e1 = (e2 @ w[6]) * dact(v1)
-    grads = [d1.T @ x, d1.sum(0), d2.T @ h1, d2.sum(0), e1.T @ x, e1.sum(0), e2.T @ v1, e2.sum(0), d_mu.T @ h2, d_mu.sum(0),
-             (g_v[:, None] * v2).sum(0)[None, :], np.array([g_v.sum()]), d_ls]
-    aux = dict(lp=lp, adv=A, mean=mu, value=v, z=(z1, z2, y1, y2), d_mean=d_mu, d_value=g_v)
+    grads, d_mu = _backward(n, g_lp, g_v, ent_coef)
+    aux = dict(lp=lp, adv=A, mean=n.mu, value=v, z=n.z, d_mean=d_mu, d_value=g_v)
     return grads, stats, aux
 
 
@@ -84,12 +59,14 @@ def rmsprop_numpy(theta, sq, g, lr=7e-4, alpha=0.99, eps=1e-5):
     return theta - lr * g / (np.sqrt(sq) + eps), sq
 
 
-class A2CLearner:
+class A2CLearner(_Learner):
     """SB3's A2C.train() on the device for an OnPolicyCollector's GaussianActorCritic.
 
     The learner takes the policy's current weights as float32 masters on the device.  While it lives, `policy.set_weights` / `set_log_std`
     also reset the masters (the optimiser's state is kept); `state_dict()` reads them back.  `close()` (or closing the policy or the engine)
     frees it."""
+
+    a2c = property(lambda self: self.learner)   # the device learner
 
     def __init__(self, collector, lr=7e-4, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, rms_prop_eps=1e-5, use_rms_prop=True,
                  normalize_advantage=False, **unsupported):
@@ -97,37 +74,30 @@ class A2CLearner:
             raise ValueError(f"A2CLearner: {k} is not supported (RMSpropTFLike and other policy_kwargs, schedules as objects, action masks and "
                              "orthogonal initialisation are out of scope; n_steps, gamma and gae_lambda belong to the collector; see the module "
                              "docstring)")
-        if callable(lr):
-            raise ValueError("A2CLearner: lr is a number; drive a schedule with set_rate() between train() calls")
-        import torch
-        self.torch = torch
-        self.collector, self.policy, self.eng = collector, collector.policy, collector.eng
+        self._numbers("A2CLearner: lr is a number; drive a schedule with set_rate() between train() calls", lr)
+        self._bind(collector)
         self.lr, self.normalize_advantage = float(lr), bool(normalize_advantage)
-        self.device = torch.device("cuda", self.eng.device)
-        self.a2c = self.eng.a2c_create(self.policy.ac, lr=lr, rms_eps=rms_prop_eps, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm,
-                                       normalize_advantage=normalize_advantage, use_rms_prop=use_rms_prop)
+        self.learner = self.eng.a2c_create(self.policy.ac, lr=lr, rms_eps=rms_prop_eps, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm,
+                                           normalize_advantage=normalize_advantage, use_rms_prop=use_rms_prop)
         self._arange = None   # the one device arange: an update takes every row of the batch, in order
-        self._stats = torch.zeros(6, dtype=torch.float32, device=self.device)
-        self.num_timesteps = 0
+        self._stats = self.torch.zeros(6, dtype=self.torch.float32, device=self.device)
 
     def set_rate(self, lr):
         """The learning rate of the following updates (how a schedule is driven from Python)."""
-        if callable(lr):
-            raise ValueError("A2CLearner.set_rate: lr is a number")
+        self._numbers("A2CLearner.set_rate: lr is a number", lr)
         self.lr = float(lr)
         self.eng.a2c_set_rate(self.a2c, self.lr)
 
     def train(self, batch):
         """One update over every row of the RolloutBatch `batch`.  Returns policy_loss, value_loss, entropy_loss, loss and explained_variance
         (of the batch's stored values against its returns, as SB3 logs it: 1 - var(returns - values) / var(returns), nan when var(returns) is 0)."""
-        t, eng, p = self.torch, self.eng, self.policy
-        N = check_batch(p, batch, "A2CLearner.train")
+        t, eng = self.torch, self.eng
+        N = check_batch(self.policy, batch, "A2CLearner.train")
         if batch["values"].numel() != N:
             raise ValueError(f"A2CLearner.train: the batch's arrays do not all have {N} rows")
         if self.normalize_advantage and N < 2:
             raise ValueError("A2CLearner.train: normalize_advantage needs a batch of at least two rows")
-        f = lambda a, *shape: a.to(device=self.device, dtype=t.float32).contiguous().view(N, *shape)  # noqa: E731
-        obs, actions, adv, ret, values = f(batch["observations"], p.d_in), f(batch["actions"], p.d_out), f(batch["advantages"]), f(batch["returns"]), f(batch["values"])
+        obs, actions, adv, ret, values = self._flat(batch, N, "advantages", "returns", "values")
         if self._arange is None or self._arange.numel() != N:
             self._arange = t.arange(N, dtype=t.int32, device=self.device)
         # (float64: returns far from zero with a small spread lose digits in a float32 variance, and the two casts cost nothing next to an update)
@@ -141,26 +111,6 @@ class A2CLearner:
         out = dict(zip(STAT_NAMES, (float(v) for v in self.last_stats[:4])))
         out["explained_variance"] = float(ev)
         return out
-
-    def learn(self, total_timesteps):
-        """collect() and train() in turn until total_timesteps env steps were collected; returns the statistics of every train()."""
-        out = []
-        target = self.num_timesteps + int(total_timesteps)
-        while self.num_timesteps < target:
-            batch = self.collector.collect()
-            self.num_timesteps += self.collector.n_steps * self.eng.E
-            out.append(self.train(batch))
-        return out
-
-    def state_dict(self):
-        """The policy's parameters read back from the device (GaussianActorCritic.weights / log_std are refreshed), under SB3's keys."""
-        self.policy.get_weights()
-        return self.policy.state_dict()
-
-    def close(self):
-        if self.a2c:
-            self.eng.ppo_destroy(self.a2c)
-        self.a2c = None
 
 
 __all__ = ["A2CLearner", "a2c_update_numpy", "rmsprop_numpy", "clip_grad_norm_numpy", "check_batch", "STAT_NAMES", "SB3_KEYS", "SB3_LOG_STD"]

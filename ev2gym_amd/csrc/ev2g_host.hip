@@ -33,6 +33,7 @@
 #include "ev2g_wrap.h"
 #include "ev2g_ac.h"
 #include "ev2g_ppo.h"
+#include "ev2g_learner_host.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -136,13 +137,11 @@ struct ev2g_acpolicy {
 // the learner of an actor-critic (ev2g_ppo_create / ev2g_a2c_create, ev2g_ppo.h): float32 masters of the thirteen arrays in SB3's layout with
 // the optimiser's state (Adam's m and v; RMSprop's square average in v), the gradient of the last grad call, the transposed images backprop
 // reads, and the gradient kernel's workspace
-enum { LEARNER_PPO = 0, LEARNER_A2C = 1 };
+static_assert(LEARNER_HEAD_PPO == EV2G_HEAD_PPO && LEARNER_HEAD_A2C == EV2G_HEAD_A2C, "LearnerSpec::head is ev2g_ppo_grad_kernel's HEAD");
 struct ev2g_ppo {
-    int kind = LEARNER_PPO;
+    LearnerSpec spec;          // kind, head, hyper-parameters, optimiser (ev2g_learner_host.h)
     ev2g_acpolicy *ac = nullptr;
     PpoPlan plan;
-    ev2g_ppo_config cfg{};     // LEARNER_PPO
-    ev2g_a2c_config a2c{};     // LEARNER_A2C
     std::vector<void *> allocs;
     float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *work = nullptr;
     double *stat_part = nullptr, *norm_part = nullptr, *advstat = nullptr;
@@ -2397,9 +2396,9 @@ static int ppo_check(ev2g_handle *h, ev2g_ppo *p, const char *who) {
 // an entry that drives one kind of learner on the other kind
 static int learner_check(ev2g_handle *h, ev2g_ppo *p, const char *who, int kind) {
     if (int rc = ppo_check(h, p, who)) return rc;
-    if (p->kind != kind)
-        return fail(h, EV2G_ERR_STATE, std::string(who) + (p->kind == LEARNER_A2C ? ": the learner is an A2C learner (the ev2g_a2c_* entries drive it)"
-                                                                                 : ": the learner is a PPO learner (the ev2g_ppo_* entries drive it)"));
+    if (p->spec.kind != kind)
+        return fail(h, EV2G_ERR_STATE, std::string(who) + (p->spec.kind == LEARNER_A2C ? ": the learner is an A2C learner (the ev2g_a2c_* entries drive it)"
+                                                                                      : ": the learner is a PPO learner (the ev2g_ppo_* entries drive it)"));
     return EV2G_OK;
 }
 
@@ -2412,18 +2411,10 @@ int ev2g_ppo_query(int d_in, int h1, int h2, int v1, int v2, int d_out, ev2g_ppo
     return EV2G_OK;
 }
 
-static int ppo_config_check(ev2g_handle *h, const char *who, double lr, double clip_range, const ev2g_ppo_config *c) {
-    auto bad = [&](const char *name, const char *range) { return fail(h, EV2G_ERR_ARG, std::string(who) + ": " + name + " must be " + range); };
-    if (!std::isfinite(lr) || lr < 0.0) return bad("lr", "finite and >= 0");
-    if (!std::isfinite(clip_range) || clip_range <= 0.0) return bad("clip_range", "finite and > 0");
-    if (!c) return EV2G_OK;
-    if (!std::isfinite(c->beta1) || c->beta1 < 0.0 || c->beta1 >= 1.0) return bad("beta1", "in [0, 1)");
-    if (!std::isfinite(c->beta2) || c->beta2 < 0.0 || c->beta2 >= 1.0) return bad("beta2", "in [0, 1)");
-    if (!std::isfinite(c->adam_eps) || c->adam_eps <= 0.0) return bad("adam_eps", "finite and > 0");
-    if (!std::isfinite(c->vf_coef) || c->vf_coef < 0.0) return bad("vf_coef", "finite and >= 0");
-    if (!std::isfinite(c->ent_coef) || c->ent_coef < 0.0) return bad("ent_coef", "finite and >= 0");
-    if (!std::isfinite(c->max_grad_norm) || c->max_grad_norm <= 0.0) return bad("max_grad_norm", "finite and > 0");
-    return EV2G_OK;
+// a config's fields, or the ones a set-rate entry sets, against their rules (ev2g_learner_host.h)
+static int fields_check(ev2g_handle *h, const char *who, const std::vector<LearnerField> &fields) {
+    const std::string refusal = learner_refusal(who, fields);
+    return refusal.empty() ? EV2G_OK : fail(h, EV2G_ERR_ARG, refusal);
 }
 
 // the twelve arrays of a policy in SB3's layout from its packed images (out[i]: host pointers in the table's order)
@@ -2472,7 +2463,7 @@ static int ppo_device_stage(ev2g_handle *h, ev2g_ppo *p, ev2g_acpolicy *ac, cons
     hipError_t e = hipMemcpyAsync(p->theta, host.data(), G * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) { ppo_launch_repack(h, p, true); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    const int relu = ac->relu ? 1 : 0, head = p->kind == LEARNER_A2C ? EV2G_HEAD_A2C : EV2G_HEAD_PPO;
+    const int relu = ac->relu ? 1 : 0, head = p->spec.head;
     const unsigned bit = 1u << (relu + 2 * head);
     if (e == hipSuccess && pl.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & bit)) {   // (function attributes are per device: once per handle)
         e = hipFuncSetAttribute(ppo_grad_kernel(relu, head).fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
@@ -2482,17 +2473,21 @@ static int ppo_device_stage(ev2g_handle *h, ev2g_ppo *p, ev2g_acpolicy *ac, cons
     return EV2G_OK;
 }
 
-// plans, allocates and binds a learner of `kind` whose config (the one of its kind; the other is null) the caller has checked
-static int learner_create(ev2g_handle *h, ev2g_acpolicy *ac, const char *who, int kind, const ev2g_ppo_config *ppo_cfg, const ev2g_a2c_config *a2c_cfg,
-                          ev2g_ppo **out) {
+// a create entry (ev2g_ppo_create, ev2g_a2c_create; CONFIG: its kind's): checks, then plans, allocates and binds a learner with the config's spec
+// (a template needs C++ linkage inside this file's extern "C" block)
+extern "C++" template <class CONFIG>
+static int learner_create(ev2g_handle *h, ev2g_acpolicy *ac, const char *who, const CONFIG *cfg, ev2g_ppo **out) {
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    *out = nullptr;
+    if (!cfg) return fail(h, EV2G_ERR_ARG, std::string(who) + ": cfg is null");
+    if (int rc = ac_check(h, ac, who)) return rc;
+    if (int rc = fields_check(h, who, learner_fields(*cfg))) return rc;
     if (ac->learner) return fail(h, EV2G_ERR_STATE, std::string(who) + ": the policy already has a learner");
     const AcPlan &a = ac->plan;
     const PpoPlan plan = plan_ppo(a.d_in, a.h1, a.h2, a.v1, a.v2, a.d_out);
     if (plan.err) return fail(h, plan.err, plan.refusal);
     ev2g_ppo *p = new ev2g_ppo();
-    p->kind = kind; p->plan = plan;
-    if (ppo_cfg) p->cfg = *ppo_cfg;
-    if (a2c_cfg) p->a2c = *a2c_cfg;
+    p->spec = learner_spec(*cfg); p->plan = plan;
     p->n_blocks = (plan.n_params + 255) / 256;
     if (const int rc = ppo_device_stage(h, p, ac, who)) {   // the one cleanup path
         ppo_free(p);
@@ -2504,34 +2499,23 @@ static int learner_create(ev2g_handle *h, ev2g_acpolicy *ac, const char *who, in
     return EV2G_OK;
 }
 
-int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cfg, ev2g_ppo **out) {
-    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: null argument");
-    *out = nullptr;
-    if (!cfg) return fail(h, EV2G_ERR_ARG, "ev2g_ppo_create: cfg is null");
-    if (int rc = ac_check(h, ac, "ev2g_ppo_create")) return rc;
-    if (int rc = ppo_config_check(h, "ev2g_ppo_create", cfg->lr, cfg->clip_range, cfg)) return rc;
-    return learner_create(h, ac, "ev2g_ppo_create", LEARNER_PPO, cfg, nullptr, out);
-}
-
-void ev2g_ppo_destroy(ev2g_handle *h, ev2g_ppo *ppo) { owned_destroy(h, &ev2g_handle::ppos, ppo, ppo_free); }
-
-int ev2g_ppo_set_rates(ev2g_handle *h, ev2g_ppo *p, double lr, double clip_range) {
-    if (int rc = learner_check(h, p, "ev2g_ppo_set_rates", LEARNER_PPO)) return rc;
-    if (int rc = ppo_config_check(h, "ev2g_ppo_set_rates", lr, clip_range, nullptr)) return rc;
-    p->cfg.lr = lr; p->cfg.clip_range = clip_range;
-    return EV2G_OK;
-}
-
-// the launches of a gradient: the advantage statistics if asked for, the gradient kernel with the learner's head, the reduction
-static int learner_grad_launch(ev2g_handle *h, ev2g_ppo *p, const PpoHyper &hp, const float *obs, const float *actions, const float *old_lp,
-                               const float *adv, const float *ret, const int32_t *idx, int B, float *stats) {
+// the gradient of either kind: the advantage statistics if asked for, the gradient kernel with the learner's head, the reduction
+// (old_lp: null from the entries of a head that does not read it)
+static int learner_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, int kind, const float *obs, const float *actions, const float *old_lp,
+                        const float *adv, const float *ret, const int32_t *idx, int B, float *stats) {
+    if (int rc = learner_check(h, p, who, kind)) return rc;
+    const LearnerSpec &s = p->spec;
+    if (!obs || !actions || (s.reads_old_lp && !old_lp) || !adv || !ret || !idx) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B must be at least 1");
+    if (s.one_row_norm_refused && s.hyper.normalize && B == 1)
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": normalize_advantage needs B >= 2 (the unbiased std of one advantage is undefined)");
     const PpoPlan &pl = p->plan;
+    const PpoHyper &hp = s.hyper;
     if (hp.normalize && B > 1) hipLaunchKernelGGL(ev2g_ppo_advstat_kernel, dim3(1), dim3(1024), 0, h->stream, adv, (const int *)idx, B, p->advstat);
     const int chunks = (B + EV2G_PPO_ROWS - 1) / EV2G_PPO_ROWS, n_wg = chunks < pl.grid_cap ? chunks : pl.grid_cap;
     const LaunchDims dims{dim3((unsigned)n_wg), pl.lds.bytes, h->stream};
-    const int head = p->kind == LEARNER_A2C ? EV2G_HEAD_A2C : EV2G_HEAD_PPO;
-    ppo_grad_kernel(p->ac->relu, head).launch(dims, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv, ret, (const int *)idx, B, (const double *)p->advstat,
-                                              p->work, p->stat_part);
+    ppo_grad_kernel(p->ac->relu, s.head).launch(dims, p->ac->dev, p->dev, pl.lds, hp, obs, actions, old_lp, adv, ret, (const int *)idx, B, (const double *)p->advstat,
+                                                p->work, p->stat_part);
     hipLaunchKernelGGL(ev2g_ppo_reduce_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->work,
                        (const double *)p->stat_part, n_wg, B, hp, p->dev.log_std, p->grad, p->norm_part, stats);
     HIPCHK(h, hipGetLastError());
@@ -2539,116 +2523,68 @@ static int learner_grad_launch(ev2g_handle *h, ev2g_ppo *p, const PpoHyper &hp, 
     return EV2G_OK;
 }
 
-static int ppo_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, const float *obs, const float *actions, const float *old_lp, const float *adv,
-                    const float *ret, const int32_t *idx, int B, float *stats) {
-    if (int rc = learner_check(h, p, who, LEARNER_PPO)) return rc;
-    if (!obs || !actions || !old_lp || !adv || !ret || !idx) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (B < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B must be at least 1");
-    const PpoHyper hp{(float)p->cfg.clip_range, (float)p->cfg.vf_coef, (float)p->cfg.ent_coef, p->cfg.normalize_advantage ? 1 : 0};
-    return learner_grad_launch(h, p, hp, obs, actions, old_lp, adv, ret, idx, B, stats);
-}
-
-static AdamStep adam_step(double lr, double beta1, double beta2, double eps, long long t) {
-    const double bc1 = 1.0 - std::pow(beta1, (double)t), bc2 = 1.0 - std::pow(beta2, (double)t);
-    return {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps};
-}
-
-static int ppo_apply(ev2g_handle *h, ev2g_ppo *p, const char *who) {
-    if (int rc = learner_check(h, p, who, LEARNER_PPO)) return rc;
-    if (!p->have_grad) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_ppo_grad first)");
-    const ev2g_ppo_config &c = p->cfg;
+// clip_grad_norm_, the spec's optimiser, repack
+static int learner_apply(ev2g_handle *h, ev2g_ppo *p, const char *who, int kind) {
+    if (int rc = learner_check(h, p, who, kind)) return rc;
+    const LearnerSpec &s = p->spec;
+    if (!p->have_grad) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (" + s.grad_entry + " first)");
     p->t += 1;
-    hipLaunchKernelGGL(ev2g_ppo_apply_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->grad,
-                       (const double *)p->norm_part, p->n_blocks, (float)c.max_grad_norm, adam_step(c.lr, c.beta1, c.beta2, c.adam_eps, p->t), p->theta,
-                       p->m, p->v);
-    HIPCHK(h, hipGetLastError());
-    p->have_grad = false;
-    return EV2G_OK;
-}
-
-int ev2g_ppo_grad(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
-                  const float *returns, const int32_t *idx, int B, float *stats) {
-    return ppo_grad(h, ppo, "ev2g_ppo_grad", obs, actions, old_log_prob, advantages, returns, idx, B, stats);
-}
-
-int ev2g_ppo_apply(ev2g_handle *h, ev2g_ppo *ppo) { return ppo_apply(h, ppo, "ev2g_ppo_apply"); }
-
-int ev2g_ppo_minibatch(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
-                       const float *returns, const int32_t *idx, int B, float *stats) {
-    if (int rc = ppo_grad(h, ppo, "ev2g_ppo_minibatch", obs, actions, old_log_prob, advantages, returns, idx, B, stats)) return rc;
-    return ppo_apply(h, ppo, "ev2g_ppo_minibatch");
-}
-
-// ---- A2C: the same learner object with the ratio-free head and RMSprop (or Adam(eps 1e-5) when use_rms_prop is 0) ----
-static int a2c_config_check(ev2g_handle *h, const char *who, double lr, const ev2g_a2c_config *c) {
-    auto bad = [&](const char *name, const char *range) { return fail(h, EV2G_ERR_ARG, std::string(who) + ": " + name + " must be " + range); };
-    if (!std::isfinite(lr) || lr < 0.0) return bad("lr", "finite and >= 0");
-    if (!c) return EV2G_OK;
-    if (!std::isfinite(c->alpha) || c->alpha < 0.0 || c->alpha >= 1.0) return bad("alpha", "in [0, 1)");
-    if (!std::isfinite(c->rms_eps) || c->rms_eps <= 0.0) return bad("rms_eps", "finite and > 0");
-    if (!std::isfinite(c->vf_coef) || c->vf_coef < 0.0) return bad("vf_coef", "finite and >= 0");
-    if (!std::isfinite(c->ent_coef) || c->ent_coef < 0.0) return bad("ent_coef", "finite and >= 0");
-    if (!std::isfinite(c->max_grad_norm) || c->max_grad_norm <= 0.0) return bad("max_grad_norm", "finite and > 0");
-    return EV2G_OK;
-}
-
-int ev2g_a2c_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_a2c_config *cfg, ev2g_ppo **out) {
-    if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_a2c_create: null argument");
-    *out = nullptr;
-    if (!cfg) return fail(h, EV2G_ERR_ARG, "ev2g_a2c_create: cfg is null");
-    if (int rc = ac_check(h, ac, "ev2g_a2c_create")) return rc;
-    if (int rc = a2c_config_check(h, "ev2g_a2c_create", cfg->lr, cfg)) return rc;
-    return learner_create(h, ac, "ev2g_a2c_create", LEARNER_A2C, nullptr, cfg, out);
-}
-
-int ev2g_a2c_set_rate(ev2g_handle *h, ev2g_ppo *p, double lr) {
-    if (int rc = learner_check(h, p, "ev2g_a2c_set_rate", LEARNER_A2C)) return rc;
-    if (int rc = a2c_config_check(h, "ev2g_a2c_set_rate", lr, nullptr)) return rc;
-    p->a2c.lr = lr;
-    return EV2G_OK;
-}
-
-static int a2c_grad(ev2g_handle *h, ev2g_ppo *p, const char *who, const float *obs, const float *actions, const float *adv, const float *ret,
-                    const int32_t *idx, int B, float *stats) {
-    if (int rc = learner_check(h, p, who, LEARNER_A2C)) return rc;
-    if (!obs || !actions || !adv || !ret || !idx) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (B < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B must be at least 1");
-    if (p->a2c.normalize_advantage && B == 1)
-        return fail(h, EV2G_ERR_ARG, std::string(who) + ": normalize_advantage needs B >= 2 (the unbiased std of one advantage is undefined)");
-    const PpoHyper hp{0.0f, (float)p->a2c.vf_coef, (float)p->a2c.ent_coef, p->a2c.normalize_advantage ? 1 : 0};
-    return learner_grad_launch(h, p, hp, obs, actions, nullptr, adv, ret, idx, B, stats);
-}
-
-static RmsStep rms_step(double lr, double alpha, double eps) { return {(float)alpha, (float)(1.0 - alpha), (float)lr, (float)eps}; }
-
-static int a2c_apply(ev2g_handle *h, ev2g_ppo *p, const char *who) {
-    if (int rc = learner_check(h, p, who, LEARNER_A2C)) return rc;
-    if (!p->have_grad) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_a2c_grad first)");
-    const ev2g_a2c_config &c = p->a2c;
-    p->t += 1;
-    if (c.use_rms_prop)
+    if (s.optimiser == LEARNER_RMSPROP)
         hipLaunchKernelGGL(ev2g_a2c_apply_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->grad,
-                           (const double *)p->norm_part, p->n_blocks, (float)c.max_grad_norm, rms_step(c.lr, c.alpha, c.rms_eps), p->theta, p->v);
-    else   // what SB3's policy builds when RMSprop is switched off: torch.optim.Adam(eps = 1e-5)
+                           (const double *)p->norm_part, p->n_blocks, (float)s.max_grad_norm, rms_step(s.lr, s.alpha, s.eps), p->theta, p->v);
+    else
         hipLaunchKernelGGL(ev2g_ppo_apply_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->grad,
-                           (const double *)p->norm_part, p->n_blocks, (float)c.max_grad_norm, adam_step(c.lr, 0.9, 0.999, 1e-5, p->t), p->theta, p->m,
+                           (const double *)p->norm_part, p->n_blocks, (float)s.max_grad_norm, adam_step(s.lr, s.beta1, s.beta2, s.eps, p->t), p->theta, p->m,
                            p->v);
     HIPCHK(h, hipGetLastError());
     p->have_grad = false;
     return EV2G_OK;
 }
 
-int ev2g_a2c_grad(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *advantages, const float *returns,
-                  const int32_t *idx, int B, float *stats) {
-    return a2c_grad(h, learner, "ev2g_a2c_grad", obs, actions, advantages, returns, idx, B, stats);
+int ev2g_ppo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_ppo_config *cfg, ev2g_ppo **out) { return learner_create(h, ac, "ev2g_ppo_create", cfg, out); }
+
+int ev2g_a2c_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_a2c_config *cfg, ev2g_ppo **out) { return learner_create(h, ac, "ev2g_a2c_create", cfg, out); }
+
+void ev2g_ppo_destroy(ev2g_handle *h, ev2g_ppo *ppo) { owned_destroy(h, &ev2g_handle::ppos, ppo, ppo_free); }
+
+int ev2g_ppo_set_rates(ev2g_handle *h, ev2g_ppo *p, double lr, double clip_range) {
+    if (int rc = learner_check(h, p, "ev2g_ppo_set_rates", LEARNER_PPO)) return rc;
+    if (int rc = fields_check(h, "ev2g_ppo_set_rates", ppo_rate_fields(lr, clip_range))) return rc;
+    p->spec.lr = lr; p->spec.hyper.clip = (float)clip_range;
+    return EV2G_OK;
 }
 
-int ev2g_a2c_apply(ev2g_handle *h, ev2g_ppo *learner) { return a2c_apply(h, learner, "ev2g_a2c_apply"); }
+int ev2g_a2c_set_rate(ev2g_handle *h, ev2g_ppo *p, double lr) {
+    if (int rc = learner_check(h, p, "ev2g_a2c_set_rate", LEARNER_A2C)) return rc;
+    if (int rc = fields_check(h, "ev2g_a2c_set_rate", a2c_rate_fields(lr))) return rc;
+    p->spec.lr = lr;
+    return EV2G_OK;
+}
+
+int ev2g_ppo_grad(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
+                  const float *returns, const int32_t *idx, int B, float *stats) {
+    return learner_grad(h, ppo, "ev2g_ppo_grad", LEARNER_PPO, obs, actions, old_log_prob, advantages, returns, idx, B, stats);
+}
+
+int ev2g_ppo_apply(ev2g_handle *h, ev2g_ppo *ppo) { return learner_apply(h, ppo, "ev2g_ppo_apply", LEARNER_PPO); }
+
+int ev2g_ppo_minibatch(ev2g_handle *h, ev2g_ppo *ppo, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
+                       const float *returns, const int32_t *idx, int B, float *stats) {
+    if (int rc = learner_grad(h, ppo, "ev2g_ppo_minibatch", LEARNER_PPO, obs, actions, old_log_prob, advantages, returns, idx, B, stats)) return rc;
+    return learner_apply(h, ppo, "ev2g_ppo_minibatch", LEARNER_PPO);
+}
+
+int ev2g_a2c_grad(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *advantages, const float *returns,
+                  const int32_t *idx, int B, float *stats) {
+    return learner_grad(h, learner, "ev2g_a2c_grad", LEARNER_A2C, obs, actions, nullptr, advantages, returns, idx, B, stats);
+}
+
+int ev2g_a2c_apply(ev2g_handle *h, ev2g_ppo *learner) { return learner_apply(h, learner, "ev2g_a2c_apply", LEARNER_A2C); }
 
 int ev2g_a2c_update(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *advantages, const float *returns,
                     const int32_t *idx, int B, float *stats) {
-    if (int rc = a2c_grad(h, learner, "ev2g_a2c_update", obs, actions, advantages, returns, idx, B, stats)) return rc;
-    return a2c_apply(h, learner, "ev2g_a2c_update");
+    if (int rc = learner_grad(h, learner, "ev2g_a2c_update", LEARNER_A2C, obs, actions, nullptr, advantages, returns, idx, B, stats)) return rc;
+    return learner_apply(h, learner, "ev2g_a2c_update", LEARNER_A2C);
 }
 
 // a flat [n_params] device buffer into the thirteen host arrays
@@ -2704,36 +2640,7 @@ int ev2g_host_ppo_head(const float *mean, const float *value, const float *actio
     if (!mean || !value || !actions || !log_std || !old_log_prob || !advantages || !returns || !cfg || !d_mean || !d_value || !d_log_std || !stats)
         return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ppo_head: null argument");
     if (B < 1 || P < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ppo_head: B and P must be positive");
-    const bool norm = cfg->normalize_advantage && B > 1;
-    double a_mean = 0.0, a_scale = 1.0;
-    if (norm) {
-        double s = 0.0;
-        for (int i = 0; i < B; i++) s += (double)advantages[i];
-        a_mean = s / B;
-        s = 0.0;
-        for (int i = 0; i < B; i++) { const double d = (double)advantages[i] - a_mean; s += d * d; }
-        a_scale = 1.0 / (std::sqrt(s / (double)(B - 1)) + 1e-8);
-    }
-    std::vector<double> iv((size_t)P), dls((size_t)P, 0.0);
-    for (int p = 0; p < P; p++) iv[(size_t)p] = std::exp(-2.0 * (double)log_std[p]);
-    const double inv_b = 1.0 / (double)B;
-    double sum[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i < B; i++) {
-        const float *mu = mean + (size_t)i * P, *a = actions + (size_t)i * P;
-        double q[8];
-        for (int j = 0; j < 8; j++) q[j] = ev2g_ppo_lp_part(mu, a, log_std, iv.data(), P, j, 8);
-        const float A = norm ? (float)(((double)advantages[i] - a_mean) * a_scale) : advantages[i];
-        const PpoRow o = ev2g_ppo_head_row(ev2g_ppo_join8(q), old_log_prob[i], A, returns[i], value[i], (float)cfg->clip_range, (float)cfg->vf_coef, inv_b);
-        d_value[i] = o.g_v;
-        sum[0] += o.pol; sum[1] += o.vsq; sum[2] += o.kl; sum[3] += o.clipped;
-        for (int p = 0; p < P; p++) {
-            float dl;
-            ev2g_ppo_head_port(a[p], mu[p], iv[(size_t)p], o.g_lp, d_mean + (size_t)i * P + p, &dl);
-            dls[(size_t)p] += (double)dl;
-        }
-    }
-    for (int p = 0; p < P; p++) d_log_std[p] = (float)(dls[(size_t)p] - cfg->ent_coef);
-    ev2g_ppo_stats(sum, log_std, P, inv_b, (float)cfg->vf_coef, (float)cfg->ent_coef, stats);
+    learner_host_head(learner_spec(*cfg), mean, value, actions, log_std, old_log_prob, advantages, returns, B, P, d_mean, d_value, d_log_std, stats);
     return EV2G_OK;
 }
 
@@ -2751,37 +2658,9 @@ int ev2g_host_a2c_head(const float *mean, const float *value, const float *actio
     if (!mean || !value || !actions || !log_std || !advantages || !returns || !cfg || !d_mean || !d_value || !d_log_std || !stats)
         return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: null argument");
     if (B < 1 || P < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: B and P must be positive");
-    const bool norm = cfg->normalize_advantage != 0;
-    if (norm && B == 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: normalize_advantage needs B >= 2");
-    double a_mean = 0.0, a_scale = 1.0;
-    if (norm) {
-        double s = 0.0;
-        for (int i = 0; i < B; i++) s += (double)advantages[i];
-        a_mean = s / B;
-        s = 0.0;
-        for (int i = 0; i < B; i++) { const double d = (double)advantages[i] - a_mean; s += d * d; }
-        a_scale = 1.0 / (std::sqrt(s / (double)(B - 1)) + 1e-8);
-    }
-    std::vector<double> iv((size_t)P), dls((size_t)P, 0.0);
-    for (int p = 0; p < P; p++) iv[(size_t)p] = std::exp(-2.0 * (double)log_std[p]);
-    const double inv_b = 1.0 / (double)B;
-    double sum[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i < B; i++) {
-        const float *mu = mean + (size_t)i * P, *a = actions + (size_t)i * P;
-        double q[8];
-        for (int j = 0; j < 8; j++) q[j] = ev2g_ppo_lp_part(mu, a, log_std, iv.data(), P, j, 8);
-        const float A = norm ? (float)(((double)advantages[i] - a_mean) * a_scale) : advantages[i];
-        const PpoRow o = ev2g_a2c_head_row(ev2g_ppo_join8(q), A, returns[i], value[i], (float)cfg->vf_coef, inv_b);
-        d_value[i] = o.g_v;
-        sum[0] += o.pol; sum[1] += o.vsq; sum[2] += o.kl; sum[3] += o.clipped;
-        for (int p = 0; p < P; p++) {
-            float dl;
-            ev2g_ppo_head_port(a[p], mu[p], iv[(size_t)p], o.g_lp, d_mean + (size_t)i * P + p, &dl);
-            dls[(size_t)p] += (double)dl;
-        }
-    }
-    for (int p = 0; p < P; p++) d_log_std[p] = (float)(dls[(size_t)p] - cfg->ent_coef);
-    ev2g_ppo_stats(sum, log_std, P, inv_b, (float)cfg->vf_coef, (float)cfg->ent_coef, stats);
+    const LearnerSpec spec = learner_spec(*cfg);
+    if (spec.one_row_norm_refused && spec.hyper.normalize && B == 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: normalize_advantage needs B >= 2");
+    learner_host_head(spec, mean, value, actions, log_std, nullptr, advantages, returns, B, P, d_mean, d_value, d_log_std, stats);
     return EV2G_OK;
 }
 

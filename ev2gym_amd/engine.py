@@ -724,17 +724,19 @@ class Engine:
     def ppo_set_rates(self, ppo, lr, clip_range):
         self._check(self._lib.ev2g_ppo_set_rates(self._h, ppo, float(lr), float(clip_range)))
 
+    def _learner_rows(self, entry, learner, arrays, idx, B, stats):
+        """A grad / minibatch / update entry of either kind over rows idx [B] (int32) of the DEVICE float32 `arrays`."""
+        self._check(getattr(self._lib, entry)(self._h, learner, *map(_ptr, arrays), _ptr(idx), int(B), _ptr(stats)))
+
     def ppo_grad(self, ppo, obs, actions, old_log_prob, advantages, returns, idx, B, stats=None):
         """The gradient of the minibatch idx [B] (int32) of the DEVICE float32 arrays; stays in the learner.  stats: float32 [6] DEVICE or None."""
-        self._check(self._lib.ev2g_ppo_grad(self._h, ppo, _ptr(obs), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(returns), _ptr(idx),
-                                            int(B), _ptr(stats)))
+        self._learner_rows("ev2g_ppo_grad", ppo, (obs, actions, old_log_prob, advantages, returns), idx, B, stats)
 
     def ppo_apply(self, ppo):
         self._check(self._lib.ev2g_ppo_apply(self._h, ppo))
 
     def ppo_minibatch(self, ppo, obs, actions, old_log_prob, advantages, returns, idx, B, stats=None):
-        self._check(self._lib.ev2g_ppo_minibatch(self._h, ppo, _ptr(obs), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(returns),
-                                                 _ptr(idx), int(B), _ptr(stats)))
+        self._learner_rows("ev2g_ppo_minibatch", ppo, (obs, actions, old_log_prob, advantages, returns), idx, B, stats)
 
     def ppo_get_grads(self, ppo, ac_shape):
         """The last gradient (unclipped) as thirteen host float32 arrays in SB3's layout: the twelve of ac_create's order, then log_std."""
@@ -760,15 +762,13 @@ class Engine:
 
     def a2c_grad(self, learner, obs, actions, advantages, returns, idx, B, stats=None):
         """The gradient of one update over rows idx [B] (int32) of the DEVICE float32 arrays; stays in the learner.  stats: float32 [6] DEVICE or None."""
-        self._check(self._lib.ev2g_a2c_grad(self._h, learner, _ptr(obs), _ptr(actions), _ptr(advantages), _ptr(returns), _ptr(idx), int(B),
-                                            _ptr(stats)))
+        self._learner_rows("ev2g_a2c_grad", learner, (obs, actions, advantages, returns), idx, B, stats)
 
     def a2c_apply(self, learner):
         self._check(self._lib.ev2g_a2c_apply(self._h, learner))
 
     def a2c_update(self, learner, obs, actions, advantages, returns, idx, B, stats=None):
-        self._check(self._lib.ev2g_a2c_update(self._h, learner, _ptr(obs), _ptr(actions), _ptr(advantages), _ptr(returns), _ptr(idx), int(B),
-                                              _ptr(stats)))
+        self._learner_rows("ev2g_a2c_update", learner, (obs, actions, advantages, returns), idx, B, stats)
 
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
@@ -947,21 +947,24 @@ def host_adam(theta, m, v, g, t, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-5):
         raise EngineError(rc, L.ev2g_last_error(None).decode())
 
 
+def _host_head(entry, cfg, mean, *rows):
+    """A host twin of the gradient kernel's head: stages mean [B, P] and `rows` (the entry's arrays after mean, in its order) as float32,
+    allocates (d_mean [B, P], d_value [B], d_log_std [P], stats [6]) and calls `entry` with the config `cfg`."""
+    mean, *rows = (np.ascontiguousarray(a, np.float32) for a in (mean, *rows))
+    B, P = mean.shape
+    out = np.empty((B, P), np.float32), np.empty(B, np.float32), np.empty(P, np.float32), np.empty(6, np.float32)
+    L = load_library()
+    rc = getattr(L, entry)(mean.ctypes.data, *[a.ctypes.data for a in rows], B, P, C.byref(cfg), *[a.ctypes.data for a in out])
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+    return out
+
+
 def host_ppo_head(mean, value, actions, log_std, old_log_prob, advantages, returns, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
                   normalize_advantage=True):
     """Host twin of the gradient kernel's head (ev2g_host_ppo_head): (d_mean [B, P], d_value [B], d_log_std [P], stats [6]) float32."""
-    f = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
-    mean, value, actions, log_std, old_log_prob, advantages, returns = map(f, (mean, value, actions, log_std, old_log_prob, advantages, returns))
-    B, P = mean.shape
     cfg = _abi.PpoConfigC(0.0, 0.9, 0.999, 1e-5, float(clip_range), float(vf_coef), float(ent_coef), 0.5, int(bool(normalize_advantage)))
-    dm, dv, dl, st = np.empty((B, P), np.float32), np.empty(B, np.float32), np.empty(P, np.float32), np.empty(6, np.float32)
-    L = load_library()
-    rc = L.ev2g_host_ppo_head(mean.ctypes.data, value.ctypes.data, actions.ctypes.data, log_std.ctypes.data, old_log_prob.ctypes.data,
-                              advantages.ctypes.data, returns.ctypes.data, B, P, C.byref(cfg), dm.ctypes.data, dv.ctypes.data, dl.ctypes.data,
-                              st.ctypes.data)
-    if rc != 0:
-        raise EngineError(rc, L.ev2g_last_error(None).decode())
-    return dm, dv, dl, st
+    return _host_head("ev2g_host_ppo_head", cfg, mean, value, actions, log_std, old_log_prob, advantages, returns)
 
 
 def host_rmsprop(theta, sq, g, lr=7e-4, alpha=0.99, eps=1e-5):
@@ -977,14 +980,5 @@ def host_rmsprop(theta, sq, g, lr=7e-4, alpha=0.99, eps=1e-5):
 
 def host_a2c_head(mean, value, actions, log_std, advantages, returns, vf_coef=0.5, ent_coef=0.0, normalize_advantage=False):
     """Host twin of the gradient kernel's A2C head (ev2g_host_a2c_head): (d_mean [B, P], d_value [B], d_log_std [P], stats [6]) float32."""
-    f = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
-    mean, value, actions, log_std, advantages, returns = map(f, (mean, value, actions, log_std, advantages, returns))
-    B, P = mean.shape
     cfg = _abi.A2cConfigC(0.0, 0.99, 1e-5, float(vf_coef), float(ent_coef), 0.5, int(bool(normalize_advantage)), 1)
-    dm, dv, dl, st = np.empty((B, P), np.float32), np.empty(B, np.float32), np.empty(P, np.float32), np.empty(6, np.float32)
-    L = load_library()
-    rc = L.ev2g_host_a2c_head(mean.ctypes.data, value.ctypes.data, actions.ctypes.data, log_std.ctypes.data, advantages.ctypes.data,
-                              returns.ctypes.data, B, P, C.byref(cfg), dm.ctypes.data, dv.ctypes.data, dl.ctypes.data, st.ctypes.data)
-    if rc != 0:
-        raise EngineError(rc, L.ev2g_last_error(None).decode())
-    return dm, dv, dl, st
+    return _host_head("ev2g_host_a2c_head", cfg, mean, value, actions, log_std, advantages, returns)

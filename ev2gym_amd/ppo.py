@@ -21,6 +21,7 @@ caller).
 from __future__ import annotations
 
 import math
+import types
 
 import numpy as np
 
@@ -31,17 +32,11 @@ STAT_NAMES = _abi.PPO_STATS
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
-def ppo_minibatch_numpy(weights, log_std, obs, actions, old_log_prob, advantages, returns, idx, activation="tanh", clip_range=0.2, vf_coef=0.5,
-                        ent_coef=0.0, normalize_advantage=True):
-    """One minibatch of PPO's loss in float64 with analytic backprop.  weights: the twelve arrays of GaussianActorCritic's order; idx: the rows
-    of the flattened rollout.  Returns (grads, stats, aux): the thirteen gradients (the twelve arrays' order, then log_std), the six statistics
-    (STAT_NAMES' order) and a dict of intermediates (lp, ratio, adv, mean, value, the pre-activations z) for the tests' branch checks."""
+def _forward(weights, log_std, obs, actions, idx, activation):
+    """The float64 network on rows idx of obs / actions with every activation kept: what both learners' references share before the head."""
     w = [np.asarray(a, np.float64) for a in weights]
     ls = np.asarray(log_std, np.float64)
-    idx = np.asarray(idx, np.int64)
     x, a = np.asarray(obs, np.float64)[idx], np.asarray(actions, np.float64)[idx]
-    old, A, R = (np.asarray(v, np.float64)[idx] for v in (old_log_prob, advantages, returns))
-    B, c = len(idx), float(clip_range)
     tanh = activation == "tanh"
     act = np.tanh if tanh else (lambda z: np.maximum(z, 0.0))
     dact = (lambda h: 1.0 - h * h) if tanh else (lambda h: (h > 0.0).astype(np.float64))
@@ -54,26 +49,45 @@ def ppo_minibatch_numpy(weights, log_std, obs, actions, old_log_prob, advantages
     iv = np.exp(-2.0 * ls)
     d = a - mu
     lp = (-(d * d) * (0.5 * iv) - ls - _HALF_LOG_2PI).sum(axis=1)
+    entropy = (0.5 + _HALF_LOG_2PI + ls).sum()
+    return types.SimpleNamespace(w=w, x=x, dact=dact, h1=h1, h2=h2, v1=v1, v2=v2, z=(z1, z2, y1, y2), mu=mu, v=v, iv=iv, d=d, lp=lp, entropy=entropy)
+
+
+def _backward(n, g_lp, g_v, ent_coef):
+    """Backprop through _forward's network from the head's d loss / d lp and d loss / d value: (the thirteen gradients, d loss / d mean)."""
+    w, x, d, iv, dact = n.w, n.x, n.d, n.iv, n.dact
+    d_mu = g_lp[:, None] * d * iv
+    d_ls = (g_lp[:, None] * (d * d * iv - 1.0)).sum(axis=0) - ent_coef
+    d2 = (d_mu @ w[8]) * dact(n.h2)
+    d1 = (d2 @ w[2]) * dact(n.h1)
+    e2 = (g_v[:, None] * w[10]) * dact(n.v2)
+    e1 = (e2 @ w[6]) * dact(n.v1)
+    grads = [d1.T @ x, d1.sum(0), d2.T @ n.h1, d2.sum(0), e1.T @ x, e1.sum(0), e2.T @ n.v1, e2.sum(0), d_mu.T @ n.h2, d_mu.sum(0),
+             (g_v[:, None] * n.v2).sum(0)[None, :], np.array([g_v.sum()]), d_ls]
+    return grads, d_mu
+
+
+def ppo_minibatch_numpy(weights, log_std, obs, actions, old_log_prob, advantages, returns, idx, activation="tanh", clip_range=0.2, vf_coef=0.5,
+                        ent_coef=0.0, normalize_advantage=True):
+    """One minibatch of PPO's loss in float64 with analytic backprop.  weights: the twelve arrays of GaussianActorCritic's order; idx: the rows
+    of the flattened rollout.  Returns (grads, stats, aux): the thirteen gradients (the twelve arrays' order, then log_std), the six statistics
+    (STAT_NAMES' order) and a dict of intermediates (lp, ratio, adv, mean, value, the pre-activations z) for the tests' branch checks."""
+    idx = np.asarray(idx, np.int64)
+    n = _forward(weights, log_std, obs, actions, idx, activation)
+    old, A, R = (np.asarray(v, np.float64)[idx] for v in (old_log_prob, advantages, returns))
+    B, c, lp, v = len(idx), float(clip_range), n.lp, n.v
     if normalize_advantage and B > 1:
         A = (A - A.mean()) / (A.std(ddof=1) + 1e-8)
     lr = lp - old
     r = np.exp(lr)
     s1, s2 = A * r, A * np.clip(r, 1.0 - c, 1.0 + c)
-    entropy = (0.5 + _HALF_LOG_2PI + ls).sum()
-    pl, vl, el = -np.minimum(s1, s2).mean(), ((R - v) ** 2).mean(), -entropy
+    pl, vl, el = -np.minimum(s1, s2).mean(), ((R - v) ** 2).mean(), -n.entropy
     stats = np.array([pl, vl, el, pl + ent_coef * el + vf_coef * vl, ((r - 1.0) - lr).mean(), (np.abs(r - 1.0) > c).mean()])
     open_ = ((A >= 0.0) & (r <= 1.0 + c)) | ((A < 0.0) & (r >= 1.0 - c))
     g_lp = np.where(open_, -A * r / B, 0.0)
     g_v = 2.0 * vf_coef * (v - R) / B
-    d_mu = g_lp[:, None] * d * iv
-    d_ls = (g_lp[:, None] * (d * d * iv - 1.0)).sum(axis=0) - ent_coef
-    d2 = (d_mu @ w[8]) * dact(h2)
-    d1 = (d2 @ w[2]) * dact(h1)
-    e2 = (g_v[:, None] * w[10]) * dact(v2)
-    e1 = (e2 @ w[6]) * dact(v1)
-    grads = [d1.T @ x, d1.sum(0), d2.T @ h1, d2.sum(0), e1.T @ x, e1.sum(0), e2.T @ v1, e2.sum(0), d_mu.T @ h2, d_mu.sum(0),
-             (g_v[:, None] * v2).sum(0)[None, :], np.array([g_v.sum()]), d_ls]
-    aux = dict(lp=lp, ratio=r, adv=A, mean=mu, value=v, z=(z1, z2, y1, y2), open=open_, d_mean=d_mu, d_value=g_v)
+    grads, d_mu = _backward(n, g_lp, g_v, ent_coef)
+    aux = dict(lp=lp, ratio=r, adv=A, mean=n.mu, value=v, z=n.z, open=open_, d_mean=d_mu, d_value=g_v)
     return grads, stats, aux
 
 
@@ -106,12 +120,58 @@ def check_batch(policy, batch, who="PPOLearner.train"):
     return N
 
 
-class PPOLearner:
+class _Learner:
+    """What PPOLearner and A2CLearner share: the torch and device set-up behind a collector, the refusal of schedule objects, a batch's arrays
+    flattened on the device, learn(), state_dict() and close().  self.learner is the device learner (ev2g_ppo_create / ev2g_a2c_create)."""
+
+    @staticmethod
+    def _numbers(message, *values):
+        if any(callable(v) for v in values):
+            raise ValueError(message)
+
+    def _bind(self, collector):
+        import torch
+        self.torch = torch
+        self.collector, self.policy, self.eng = collector, collector.policy, collector.eng
+        self.device = torch.device("cuda", self.eng.device)
+        self.learner = None
+        self.num_timesteps = 0
+
+    def _flat(self, batch, N, *names):
+        """observations [N, d_in], actions [N, d_out] and batch[name] [N] for each name: contiguous float32 on the device."""
+        p, t = self.policy, self.torch
+        f = lambda a, *shape: a.to(device=self.device, dtype=t.float32).contiguous().view(N, *shape)  # noqa: E731
+        return [f(batch["observations"], p.d_in), f(batch["actions"], p.d_out)] + [f(batch[k]) for k in names]
+
+    def learn(self, total_timesteps):
+        """collect() and train() in turn until total_timesteps env steps were collected; returns the statistics of every train()."""
+        out = []
+        target = self.num_timesteps + int(total_timesteps)
+        while self.num_timesteps < target:
+            batch = self.collector.collect()
+            self.num_timesteps += self.collector.n_steps * self.eng.E
+            out.append(self.train(batch))
+        return out
+
+    def state_dict(self):
+        """The policy's parameters read back from the device (GaussianActorCritic.weights / log_std are refreshed), under SB3's keys."""
+        self.policy.get_weights()
+        return self.policy.state_dict()
+
+    def close(self):
+        if self.learner:
+            self.eng.ppo_destroy(self.learner)
+        self.learner = None
+
+
+class PPOLearner(_Learner):
     """SB3's PPO.train() on the device for an OnPolicyCollector's GaussianActorCritic.
 
     The learner takes the policy's current weights as float32 masters on the device.  While it lives, `policy.set_weights` / `set_log_std`
     also reset the masters (Adam's moments and step count are kept); `state_dict()` reads them back.  `close()` (or closing the policy or the
     engine) frees it."""
+
+    ppo = property(lambda self: self.learner)   # the device learner
 
     def __init__(self, collector, lr=3e-4, n_epochs=10, batch_size=64, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, seed=0, **unsupported):
@@ -120,23 +180,18 @@ class PPOLearner:
                 continue
             raise ValueError(f"PPOLearner: {k} is not supported (clip_range_vf, target_kl, schedules as objects, action masks and orthogonal "
                              "initialisation are out of scope; see the module docstring)")
-        if callable(lr) or callable(clip_range):
-            raise ValueError("PPOLearner: lr and clip_range are numbers; drive a schedule with set_rates() between train() calls")
+        self._numbers("PPOLearner: lr and clip_range are numbers; drive a schedule with set_rates() between train() calls", lr, clip_range)
         if int(batch_size) < 1:
             raise ValueError(f"PPOLearner: batch_size {batch_size} must be at least 1")
         if int(n_epochs) < 1:
             raise ValueError(f"PPOLearner: n_epochs {n_epochs} must be at least 1")
-        import torch
-        self.torch = torch
-        self.collector, self.policy, self.eng = collector, collector.policy, collector.eng
+        self._bind(collector)
         self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
         self.lr, self.clip_range = float(lr), float(clip_range)
-        self.device = torch.device("cuda", self.eng.device)
-        self.generator = torch.Generator(device=self.device)
+        self.generator = self.torch.Generator(device=self.device)
         self.generator.manual_seed(int(seed))
-        self.ppo = self.eng.ppo_create(self.policy.ac, lr=lr, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm,
-                                       normalize_advantage=normalize_advantage)
-        self.num_timesteps = 0
+        self.learner = self.eng.ppo_create(self.policy.ac, lr=lr, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm,
+                                           normalize_advantage=normalize_advantage)
 
     def set_rates(self, lr=None, clip_range=None):
         """The learning rate and the clip range of the following minibatches (how a schedule is driven from Python)."""
@@ -144,19 +199,13 @@ class PPOLearner:
         self.clip_range = self.clip_range if clip_range is None else float(clip_range)
         self.eng.ppo_set_rates(self.ppo, self.lr, self.clip_range)
 
-    def _flat(self, batch):
-        p, t = self.policy, self.torch
-        N = check_batch(p, batch)
-        f = lambda a, *shape: a.to(device=self.device, dtype=t.float32).contiguous().view(N, *shape)  # noqa: E731
-        return (N, f(batch["observations"], p.d_in), f(batch["actions"], p.d_out), f(batch["log_probs"]), f(batch["advantages"]),
-                f(batch["returns"]))
-
     def train(self, batch, minibatches=None):
         """n_epochs passes over the RolloutBatch `batch` (minibatches=None: each pass a fresh device permutation from the seeded generator cut
         into batch_size pieces, the shorter last piece included, as SB3 does), or exactly the minibatches of the iterable `minibatches` (index
         tensors or arrays into the flattened [n_steps * E] rows).  Returns the means over the minibatches of the six statistics."""
         t, eng = self.torch, self.eng
-        N, obs, actions, old_lp, adv, ret = self._flat(batch)
+        N = check_batch(self.policy, batch)
+        obs, actions, old_lp, adv, ret = self._flat(batch, N, "log_probs", "advantages", "returns")
         if minibatches is None:
             pieces = []
             for _ in range(self.n_epochs):
@@ -176,26 +225,6 @@ class PPOLearner:
         eng.ppo_sync(self.ppo)            # (synchronises; the policy samples from the new log_std afterwards)
         self.last_stats = stats.cpu().numpy()
         return dict(zip(STAT_NAMES, (float(v) for v in self.last_stats.astype(np.float64).mean(axis=0))))
-
-    def learn(self, total_timesteps):
-        """collect() and train() in turn until total_timesteps env steps were collected; returns the statistics of every train()."""
-        out = []
-        target = self.num_timesteps + int(total_timesteps)
-        while self.num_timesteps < target:
-            batch = self.collector.collect()
-            self.num_timesteps += self.collector.n_steps * self.eng.E
-            out.append(self.train(batch))
-        return out
-
-    def state_dict(self):
-        """The policy's parameters read back from the device (GaussianActorCritic.weights / log_std are refreshed), under SB3's keys."""
-        self.policy.get_weights()
-        return self.policy.state_dict()
-
-    def close(self):
-        if self.ppo:
-            self.eng.ppo_destroy(self.ppo)
-        self.ppo = None
 
 
 __all__ = ["PPOLearner", "ppo_minibatch_numpy", "adam_numpy", "clip_grad_norm_numpy", "check_batch", "STAT_NAMES", "SB3_KEYS", "SB3_LOG_STD"]

@@ -10,77 +10,21 @@ Every d32 and every device deviation is printed before it is asserted, and appen
 
 Handles: the 37-env, 12-step generated PublicPST pool (D 63, P 20) and the v2gppl_rand_s2 fixture's engine; the D 162 / P 50 networks are
 created with their shape spelled out, as tests/test_ppo_gpu.py does."""
+import functools
+
 import numpy as np
 import pytest
 
+from tests import learner_cases
+from tests.learner_cases import N_ROWS, NAMES, SHAPES, _index_sets, _shape, engines  # noqa: F401 (engines: the fixture)
 from tests.test_a2c_cpu import a2c_reference, a2c_torch_grads, a2c_torch_train
-from tests.test_onpolicy_gpu import _bits, _fixture_engine, _gen_engine, _up
+from tests.test_onpolicy_gpu import _bits, _gen_engine, _up
 from tests.test_ppo_cpu import _record, grad_tol, make_case, value_tol
 
 pytestmark = pytest.mark.gpu
 
 ARG, STATE = -1, -3
-NAMES = ("pi_W1", "pi_b1", "pi_W2", "pi_b2", "vf_W1", "vf_b1", "vf_W2", "vf_b2", "action_W", "action_b", "value_W", "value_b", "log_std")
-SHAPES = {"pst": (63, 20), "ppl": (162, 50)}   # (D, P) of the networks run on each handle
-N_ROWS = {"tanh": 600, "relu": 96}   # distinct rows of a case (ReLU: few enough that a seed with no pre-activation near 0 exists)
-
-
-@pytest.fixture(scope="module")
-def engines():
-    engs = {"pst": _gen_engine("pst"), "ppl": _fixture_engine("ppl")}
-    assert (engs["pst"].D, engs["pst"].P) == SHAPES["pst"]
-    yield engs
-    for e in engs.values():
-        e.close()
-
-
-def _shape(case):
-    return (case["D"], case["h"][0], case["h"][1], case["v"][0], case["v"][1], case["P"])
-
-
-class _Device:
-    """A case's rows, a policy object and an A2C learner on an engine."""
-
-    def __init__(self, eng, case, lo=-1.0, **cfg):
-        from ev2gym_amd.onpolicy import GaussianActorCritic
-        self.eng, self.case = eng, case
-        self.pol = GaussianActorCritic(case["weights"], case["log_std"], activation=case["activation"], lo=lo, seed=5).attach(eng)
-        self.a2c = eng.a2c_create(self.pol.ac, **cfg)
-        self.bufs = [_up(eng, case[k]) for k in ("obs", "actions", "advantages", "returns")]
-        self.stats = eng.empty((6,), np.float32)
-
-    def grad(self, idx):
-        ix = _up(self.eng, np.asarray(idx, np.int32))
-        self.eng.a2c_grad(self.a2c, *self.bufs, ix, len(idx), self.stats)
-        g = self.eng.ppo_get_grads(self.a2c, _shape(self.case))
-        st = self.stats.to_host()
-        ix.free()
-        return g, st
-
-    def update(self, idx):
-        ix = _up(self.eng, np.asarray(idx, np.int32))
-        self.eng.a2c_update(self.a2c, *self.bufs, ix, len(idx), self.stats)
-        st = self.stats.to_host()   # (synchronises)
-        ix.free()
-        return st
-
-    def weights(self):
-        w, ls = self.eng.ac_get_weights(self.pol.ac, _shape(self.case))
-        return w + [ls]
-
-    def close(self):
-        self.pol.close()   # (the learner goes with its policy)
-        for b in self.bufs + [self.stats]:
-            b.free()
-
-
-def _index_sets(cap, n_rows, normalize):
-    rng = np.random.default_rng(12)
-    sets = [rng.choice(n_rows, B, replace=False) for B in (1, 31, 32, 33)]
-    dup = rng.integers(0, n_rows, 97)
-    dup[5:9] = dup[0]                                      # duplicates for certain
-    sets += [dup, rng.integers(0, n_rows, 32 * cap + 37)]   # the last: every workgroup loops and the cross-workgroup reduction runs
-    return sets[1:] if normalize else sets                  # (one normalised row is refused: test_refusals_through_the_abi)
+_Device = functools.partial(learner_cases._Device, "a2c")
 
 
 def _compare_grads(tag, got, got_stats, ref, ref_stats, y32, y32_stats):
