@@ -1,6 +1,7 @@
-"""What tests/test_ppo_gpu.py and tests/test_a2c_gpu.py share: the array names, the networks' shapes per handle, the row counts, the engines,
-the index sets of a gradient case, and one device harness parameterised by the learner's kind.  A plain module: each test module imports what
-it uses (the `engines` fixture included)."""
+"""What tests/test_ppo_gpu.py, tests/test_a2c_gpu.py and tests/test_learner_shapes_gpu.py share: the array names, the networks' shapes per
+handle, the row counts, the engines, the index sets of a gradient case, one device harness parameterised by the learner's kind, and the table of
+networks that take the learner's kernels off width 64 (tests/test_ppo_plan_cpu.py pins its LDS figures without a GPU).  A plain module: each
+test module imports what it uses (the `engines` fixture included)."""
 import numpy as np
 import pytest
 
@@ -10,6 +11,32 @@ from tests.test_ppo_cpu import CLIP
 NAMES = ("pi_W1", "pi_b1", "pi_W2", "pi_b2", "vf_W1", "vf_b1", "vf_W2", "vf_b2", "action_W", "action_b", "value_W", "value_b", "log_std")
 SHAPES = {"pst": (63, 20), "ppl": (162, 50)}   # (D, P) of the networks run on each handle
 N_ROWS = {"tanh": 600, "relu": 96}   # distinct rows of a case (ReLU: few enough that a seed with no pre-activation near 0 exists)
+
+# Networks that reach what the (64, 64) learners never run (csrc/ev2g_ppo.h; padded widths k1 = ceil8(d_in), k1r = ceil32(d_in), n1 / n2 / m1 /
+# m2 / n3 = ceil32 of h / v / d_out; the gradient kernel has 4 wavefronts): tag -> (d_in, h, v, d_out, activations, the plan's LDS bytes).
+#   wide         8 tiles in both trunk stages, forward and back: every wavefront's second trip.  Back tiles of KG 16, dW decode with kn 4,
+#                output tile rows 2 and 3 of both packed images.
+#   lopsided     9 tiles in the first stage (8 + 1) and 4 in the second (1 + 3): a 256-wide layer, KG 32 forward and 4 back, unequal trunks.
+#   limits       1,664 bytes under the LDS limit; k1r == d_in (no zero-filled x column); n3 == P (no padded port); tile counts 3 and 5.
+#   tiny         kx 1; k1 8 < k1r 32 (only the dW tiles read x columns 8..31); P 1: seven of a row's eight head lanes have no port; one tile
+#                per stage, so three wavefronts idle.
+#   past-a-tile  d_in and d_out both 33: 31 zero-filled input columns, 31 padded ports.
+# (128, 128) / (128, 128) runs tanh only: no seed of RELU_SEEDS keeps its ReLU pre-activations away from 0.
+LEARNER_NETS = {
+    "wide": (63, (128, 128), (128, 128), 20, ("tanh",), 153728),
+    "lopsided": (162, (256, 32), (32, 96), 50, ("relu",), 153984),
+    "limits": (192, (96, 160), (160, 32), 64, ("relu",), 162176),
+    "tiny": (5, (8, 8), (8, 8), 1, ("tanh", "relu"), 51328),
+    "past-a-tile": (33, (64, 64), (64, 64), 33, ("tanh",), 96640),
+}
+NEAREST_THE_LDS_LIMIT = "limits"
+
+
+def net_shape(tag):
+    """(d_in, h1, h2, v1, v2, d_out) of a row of LEARNER_NETS, the order ev2g_ppo_query takes"""
+    d_in, h, v, d_out, _, _ = LEARNER_NETS[tag]
+    return (d_in, h[0], h[1], v[0], v[1], d_out)
+
 
 # per kind: the create call with its fixed arguments, the case's arrays a call reads, the gradient call, the grad-then-apply call
 KINDS = {

@@ -52,15 +52,17 @@ def a2c_torch_grads(case, idx, dtype, **cfg):
     return [p.grad.numpy().astype(np.float64) for p in params], np.array([float(s.detach()) for s in stats])
 
 
-def a2c_torch_train(cases, index_sets, dtype, lr=7e-4, max_grad_norm=0.5, use_rms_prop=True, **cfg):
+def a2c_torch_train(cases, index_sets, dtype, lr=7e-4, max_grad_norm=0.5, use_rms_prop=True, lrs=None, **cfg):
     """The loop a user has today: clip_grad_norm_ and torch.optim.RMSprop(alpha=0.99, eps=1e-5) (or Adam(eps=1e-5)), one update per
-    (case, index set); the parameters start from cases[0]'s.  (final parameters as float64 numpy, the statistics [n, 6], the gradient norms
-    before clipping)"""
+    (case, index set); the parameters start from cases[0]'s; lrs: the rate of each update, set in the optimiser's param group before it.
+    (final parameters as float64 numpy, the statistics [n, 6], the gradient norms before clipping)"""
     import torch
     params = torch_params(cases[0], dtype)
     opt = torch.optim.RMSprop(params, lr=lr, alpha=0.99, eps=1e-5) if use_rms_prop else torch.optim.Adam(params, lr=lr, eps=1e-5)
     stats, norms = [], []
-    for case, idx in zip(cases, index_sets):
+    for k, (case, idx) in enumerate(zip(cases, index_sets)):
+        if lrs is not None:
+            opt.param_groups[0]["lr"] = lrs[k]
         loss, st = a2c_torch_loss(params, case, idx, dtype, **cfg)
         opt.zero_grad()
         loss.backward()
