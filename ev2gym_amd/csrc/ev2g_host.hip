@@ -39,26 +39,34 @@
 static thread_local std::string g_create_error;
 #include "ev2g_gen_host.h"
 
-// an env-reading heuristic agent on the device (ev2g_heuristic_create): its kind, the shape it was made for, the RoundRobin agents' queues
-// (RoundRobin_GF*: with every entry's min_power / max_power) and the action block ev2g_heuristic_run writes when the caller passes none
-struct ev2g_heuristic {
-    int kind = 0, E = 0, P = 0;
-    int *queue = nullptr, *qlen = nullptr;   // [E, P], [E]
-    double *qmin = nullptr, *qmax = nullptr; // [E, P] each
-    double *act = nullptr;                   // [E, P]
+// What every object a handle owns (and ev2g_destroy, a destroy entry or a failed create releases) keeps of its device memory: each block
+// is allocated into one of the two pools with `upload` / `dalloc`, and release_owned frees the pools.  The named pointers of an object are
+// what the kernels' argument structs are filled from, not a record of ownership.
+struct DevOwner {
+    std::vector<void *> allocs;        // the blocks of create, and those allocated on first use: kept for the object's life
+    std::vector<void *> swap_allocs;   // the blocks a later call drops and refills as a whole (a grid's attached state, a policy's clipped block)
 };
 
-// releases an agent's device memory and the agent (wherever one ends: ev2g_heuristic_destroy, ev2g_destroy, a failed create)
-static void heuristic_free(ev2g_heuristic *a) {
-    (void)hipFree(a->queue); (void)hipFree(a->qlen); (void)hipFree(a->qmin); (void)hipFree(a->qmax); (void)hipFree(a->act);
-    delete a;
-}
+// a queue of ports per env, the RoundRobin agents' and Rescale_RepairLayer's (queue_alloc): the entries, each env's length and, where the kind
+// keeps them, every entry's min_power / max_power
+struct PortQueue {
+    int *queue = nullptr, *qlen = nullptr;   // [E, P], [E]
+    double *qmin = nullptr, *qmax = nullptr; // [E, P] each, or nullptr
+};
+
+// an env-reading heuristic agent on the device (ev2g_heuristic_create): its kind, the shape it was made for, the RoundRobin agents' queues
+// (RoundRobin_GF*: with every entry's min_power / max_power) and the action block ev2g_heuristic_run writes when the caller passes none
+struct ev2g_heuristic : DevOwner {
+    int kind = 0, E = 0, P = 0;
+    PortQueue q;
+    double *act = nullptr;                   // [E, P]
+};
 
 // a communication-fault link (ev2g_link_create, ev2g_link.h): the two probabilities, the uniforms of each half (a [T, E, P] device matrix, or
 // the seed of the generated ones), the shape it was made for, the held commands (FailedActionCommunication.previous_actions_list) and the two
 // remembered energy columns (DelayedObservation.previous_obs_list / actual_previous_obs_list, column 4 + 3 i), and the blocks ev2g_link_run /
 // ev2g_link_rollout work on when the caller passes none (allocated on first use)
-struct ev2g_link {
+struct ev2g_link : DevOwner {
     int E = 0, P = 0, T = 0;
     double p_fail = 0.0, p_delay = 0.0;
     unsigned long long seed_act = 0, seed_obs = 0;
@@ -68,17 +76,10 @@ struct ev2g_link {
     float *obs32 = nullptr, *act32 = nullptr;          // [E, D], [E, P]: the policy's input and output rows
 };
 
-static void link_free(ev2g_link *l) {
-    for (void *p : {(void *)l->rand_act, (void *)l->rand_obs, (void *)l->held, (void *)l->prev, (void *)l->actual, (void *)l->raw, (void *)l->obs,
-                    (void *)l->obs32, (void *)l->act32})
-        (void)hipFree(p);
-    delete l;
-}
-
 // a distribution grid (ev2g_grid_create, ev2g_grid.h): the network's K (transposed) and L, the solver's settings, the base profiles of every
 // resident scenario when the grid was made for ev2g_grid_run, the shape it was made for, and the per-env rows ev2g_grid_run works on when the
 // caller passes none
-struct ev2g_grid {
+struct ev2g_grid : DevOwner {
     int E = 0, T = 0, M = 0, n = 0, max_iter = 0;
     double s_base = 0.0, tolerance = 0.0;
     double2 *Kt = nullptr, *L = nullptr;            // [n, n], [n]
@@ -87,9 +88,9 @@ struct ev2g_grid {
     // the episode's voltage statistics (ev2g_grid_kernel<true>'s accumulators), with profiles only: [E] each
     double *vv_sum = nullptr, *rew_sum = nullptr;
     int *vv_count = nullptr, *vv_steps = nullptr;
-    // V2G_grid_state (ev2g_grid_state_attach): the time-feature table [M or 1, T + 1, 3], the row width 6 + 2 n + 3 P, the grid's own rows
-    // [E, Dg] and the blocks ev2g_grid_rollout works on ([E, P] each); obs32 holds the state of step counter obs32_step as long as nothing
-    // has changed the engine's state since (obs32_epoch == the handle's state_epoch), -1: nothing
+    // V2G_grid_state (ev2g_grid_state_attach, in swap_allocs): the time-feature table [M or 1, T + 1, 3], the row width 6 + 2 n + 3 P, the grid's
+    // own rows [E, Dg] and the blocks ev2g_grid_rollout works on ([E, P] each); obs32 holds the state of step counter obs32_step as long as
+    // nothing has changed the engine's state since (obs32_epoch == the handle's state_epoch), -1: nothing
     double *tf = nullptr;
     int tf_per_scn = 0, Dg = 0;
     double *obs = nullptr, *act = nullptr;
@@ -98,33 +99,19 @@ struct ev2g_grid {
     long long obs32_epoch = -1;
 };
 
-static void grid_free(ev2g_grid *g) {
-    for (void *p : {(void *)g->Kt, (void *)g->L, (void *)g->p_base, (void *)g->q_base, (void *)g->vm, (void *)g->rew, (void *)g->vv_sum, (void *)g->rew_sum,
-                    (void *)g->vv_count, (void *)g->vv_steps, (void *)g->tf, (void *)g->obs, (void *)g->act, (void *)g->obs32, (void *)g->act32})
-        (void)hipFree(p);
-    delete g;
-}
-
 // an action wrapper (ev2g_wrap_create, ev2g_wrap.h): its kind, the shape it was made for, Rescale_RepairLayer's queue of every env with each
 // entry's min_power / max_power, and the float64 block the step reads when the caller passes no `wrapped` rows
-struct ev2g_wrap {
+struct ev2g_wrap : DevOwner {
     int kind = 0, E = 0, P = 0;
-    int *queue = nullptr, *qlen = nullptr;   // [E, P], [E]
-    double *qmin = nullptr, *qmax = nullptr; // [E, P] each
+    PortQueue q;
     double *act = nullptr;                   // [E, P]
 };
 
-static void wrap_free(ev2g_wrap *w) {
-    (void)hipFree(w->queue); (void)hipFree(w->qlen); (void)hipFree(w->qmin); (void)hipFree(w->qmax); (void)hipFree(w->act);
-    delete w;
-}
-
 // a Gaussian actor-critic (ev2g_ac_create, ev2g_ac.h): the packed network, the noise stream's seed and launch counter, and the clipped action
-// block [E, P] the step of ev2g_ac_collect reads (allocated on first use)
-struct ev2g_acpolicy {
+// block [E, P] the step of ev2g_ac_collect reads (in swap_allocs: allocated on first use, regrown when E * P grows)
+struct ev2g_acpolicy : DevOwner {
     AcDev dev{};
     AcPlan plan{};   // the padded sizes the weight images are packed for (ev2g_policy_host.h)
-    std::vector<void *> allocs;
     size_t lds = 0;
     int relu = 0;
     unsigned long long seed = 0, n = 0;
@@ -138,11 +125,10 @@ struct ev2g_acpolicy {
 // the optimiser's state (Adam's m and v; RMSprop's square average in v), the gradient of the last grad call, the transposed images backprop
 // reads, and the gradient kernel's workspace
 static_assert(LEARNER_HEAD_PPO == EV2G_HEAD_PPO && LEARNER_HEAD_A2C == EV2G_HEAD_A2C, "LearnerSpec::head is ev2g_ppo_grad_kernel's HEAD");
-struct ev2g_ppo {
+struct ev2g_ppo : DevOwner {
     LearnerSpec spec;          // kind, head, hyper-parameters, optimiser (ev2g_learner_host.h)
     ev2g_acpolicy *ac = nullptr;
     PpoPlan plan;
-    std::vector<void *> allocs;
     float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *work = nullptr;
     double *stat_part = nullptr, *norm_part = nullptr, *advstat = nullptr;
     PpoDev dev{};
@@ -151,18 +137,6 @@ struct ev2g_ppo {
     long long t = 0;           // the optimiser's step count
     bool have_grad = false;    // a gradient no apply has consumed yet
 };
-
-static void ppo_free(ev2g_ppo *p) {
-    if (p->ac) p->ac->learner = nullptr;
-    for (void *q : p->allocs) (void)hipFree(q);
-    delete p;
-}
-
-static void ac_free(ev2g_acpolicy *ac) {
-    for (void *p : ac->allocs) (void)hipFree(p);
-    (void)hipFree(ac->clipped);
-    delete ac;
-}
 
 #define EV2G_EV_RING 32
 struct ev2g_handle {
@@ -305,6 +279,12 @@ static void state_changed(ev2g_handle *h, const char *why) {
     h->last.inl_stats = false; h->last.inl_reason = why; h->state_epoch += 1;
 }
 
+// waits for everything queued on the handle's stream: what a call does before host memory that queued copies read goes away
+static int drain(ev2g_handle *h) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
 static void free_pool(std::vector<void *> &pool) {
     for (void *p : pool) (void)hipFree(p);
     pool.clear();
@@ -331,18 +311,48 @@ struct Rows {
     T *at(long long i) const { return p ? p + i * stride : nullptr; }
 };
 
-// The objects a handle owns (`list`: its heuristics, links or grids).  owned_check: the front of every *_check; owned_destroy: nothing for
-// an object the handle does not own, else out of the list, the stream drained, freed.
+// The objects a handle owns (`list`: its heuristics, links, grids, wrappers, actor-critics or learners).  release_owned: where every one of
+// them ends.  owned_check: the front of every *_check (`need_load` off for the kinds whose entries run without scenarios).  owned_created: the
+// tail of every create behind its device stage's `rc`.  owned_destroy: nothing for an object the handle does not own, else out of the list,
+// the stream drained, released.
 template <typename T>
-static int owned_check(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T *x, const char *thing, const char *who) {
+static void release_owned(T *x) {
+    free_pool(x->allocs);
+    free_pool(x->swap_allocs);
+    delete x;
+}
+// (a learner leaves its policy first)
+static void ppo_free(ev2g_ppo *p) {
+    if (p->ac) p->ac->learner = nullptr;
+    release_owned(p);
+}
+template <typename T>
+static void release_all(std::vector<T *> &list, void (*release)(T *) = release_owned<T>) {
+    for (T *x : list) release(x);
+    list.clear();
+}
+template <typename T>
+static int owned_check(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T *x, const char *thing, const char *who, bool need_load = true) {
     if (!h || !x) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (need_load && !h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
     if (std::find((h->*list).begin(), (h->*list).end(), x) == (h->*list).end())
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the " + thing + " was not created on this handle");
+    (void)hipSetDevice(h->device);
     return EV2G_OK;
 }
 template <typename T>
-static void owned_destroy(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T *x, void (*release)(T *)) {
+static int owned_created(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T *x, int rc, T **out) {
+    if (rc) {
+        (void)hipStreamSynchronize(h->stream);   // (copies enqueued before the failure may still read host temporaries)
+        release_owned(x);
+        return rc;
+    }
+    (h->*list).push_back(x);
+    *out = x;
+    return EV2G_OK;
+}
+template <typename T>
+static void owned_destroy(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T *x, void (*release)(T *) = release_owned<T>) {
     if (!h || !x) return;
     auto it = std::find((h->*list).begin(), (h->*list).end(), x);
     if (it == (h->*list).end()) return;
@@ -350,6 +360,16 @@ static void owned_destroy(ev2g_handle *h, std::vector<T *> ev2g_handle::*list, T
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     release(x);
+}
+
+// a PortQueue of E envs x P ports into `pool`, empty (all zero); `powers`: with the two power lists
+static int queue_alloc(ev2g_handle *h, std::vector<void *> &pool, int E, int P, bool powers, PortQueue *q) {
+    const size_t EP = (size_t)E * P;
+    if (int rc = dalloc(h, pool, EP, &q->queue)) return rc;
+    if (int rc = dalloc(h, pool, (size_t)E, &q->qlen)) return rc;
+    if (!powers) return EV2G_OK;
+    if (int rc = dalloc(h, pool, EP, &q->qmin)) return rc;
+    return dalloc(h, pool, EP, &q->qmax);
 }
 
 // ---- the step kernels' launch tables ----
@@ -520,17 +540,12 @@ void ev2g_destroy(ev2g_handle *h) {
     if (h->peek_stage) (void)hipHostFree(h->peek_stage);
     free_pool(h->refill_cache.allocs);
     if (h->d_refill_overflow) (void)hipFree(h->d_refill_overflow);
-    for (ev2g_heuristic *a : h->heuristics) heuristic_free(a);
-    h->heuristics.clear();
-    for (ev2g_link *l : h->links) link_free(l);
-    h->links.clear();
-    for (ev2g_grid *g : h->grids) grid_free(g);
-    h->grids.clear();
-    for (ev2g_wrap *w : h->wraps) wrap_free(w);
-    h->wraps.clear();
-    for (ev2g_ppo *p : h->ppos) ppo_free(p);
-    for (ev2g_acpolicy *ac : h->acs) ac_free(ac);
-    h->acs.clear();
+    release_all(h->heuristics);
+    release_all(h->links);
+    release_all(h->grids);
+    release_all(h->wraps);
+    release_all(h->ppos, ppo_free);   // (learners before their policies)
+    release_all(h->acs);
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
     for (int i = 0; i < EV2G_EV_RING; i++) { if (h->ev0s[i]) (void)hipEventDestroy(h->ev0s[i]); if (h->ev1s[i]) (void)hipEventDestroy(h->ev1s[i]); }
@@ -1493,34 +1508,27 @@ static int heuristic_shape_check(ev2g_handle *h, int kind, const std::string &wh
     return EV2G_OK;
 }
 
+// the device stage of an agent: its action block and, for the RoundRobin kinds, the queue
+static int heuristic_device_stage(ev2g_handle *h, ev2g_heuristic *a) {
+    const bool gf = a->kind == EV2G_AGENT_ROUND_ROBIN_GF || a->kind == EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED;
+    if (int rc = dalloc(h, a->allocs, (size_t)a->E * a->P, &a->act)) return rc;
+    return a->kind == EV2G_HEURISTIC_ROUND_ROBIN || gf ? queue_alloc(h, a->allocs, a->E, a->P, gf, &a->q) : EV2G_OK;
+}
+
 int ev2g_heuristic_create(ev2g_handle *h, int kind, ev2g_heuristic **out) {
     if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_create: null argument");
     *out = nullptr;
     if (!h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_heuristic_create: no scenarios loaded");
     if (kind < EV2G_HEURISTIC_CHARGE_AS_LATE_AS_POSSIBLE || kind > EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED)
         return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_create: unknown heuristic kind");
-    const bool gf = kind == EV2G_AGENT_ROUND_ROBIN_GF || kind == EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED;
     if (int rc = heuristic_shape_check(h, kind, "ev2g_heuristic_create")) return rc;
     (void)hipSetDevice(h->device);
     ev2g_heuristic *a = new ev2g_heuristic();
     a->kind = kind; a->E = h->E; a->P = h->P;
-    const size_t EP = (size_t)h->E * h->P;
-    bool ok = hipMalloc(&a->act, EP * sizeof(double)) == hipSuccess;
-    if (ok && (kind == EV2G_HEURISTIC_ROUND_ROBIN || gf)) {
-        ok = hipMalloc(&a->queue, EP * sizeof(int)) == hipSuccess && hipMalloc(&a->qlen, (size_t)h->E * sizeof(int)) == hipSuccess &&
-             hipMemsetAsync(a->qlen, 0, (size_t)h->E * sizeof(int), h->stream) == hipSuccess;
-    }
-    if (ok && gf) ok = hipMalloc(&a->qmin, EP * sizeof(double)) == hipSuccess && hipMalloc(&a->qmax, EP * sizeof(double)) == hipSuccess;
-    if (!ok) {
-        heuristic_free(a);
-        return fail(h, EV2G_ERR_HIP, "ev2g_heuristic_create: device allocation failed");
-    }
-    h->heuristics.push_back(a);
-    *out = a;
-    return EV2G_OK;
+    return owned_created(h, &ev2g_handle::heuristics, a, heuristic_device_stage(h, a), out);
 }
 
-void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a) { owned_destroy(h, &ev2g_handle::heuristics, a, heuristic_free); }
+void ev2g_heuristic_destroy(ev2g_handle *h, ev2g_heuristic *a) { owned_destroy(h, &ev2g_handle::heuristics, a); }
 
 static int heuristic_check(ev2g_handle *h, ev2g_heuristic *a, const char *who) {
     if (int rc = owned_check(h, &ev2g_handle::heuristics, a, "heuristic", who)) return rc;
@@ -1532,8 +1540,8 @@ static int heuristic_check(ev2g_handle *h, ev2g_heuristic *a, const char *who) {
 // the agent's actions for the current step into actions [E, P] (device); the RoundRobin agents' queues advance
 static int heuristic_launch(ev2g_handle *h, ev2g_heuristic *a, double *actions) {
     const DevScn &s = h->scn;
-    const HeurArgs ha{h->d_port_slot, h->d_heur_cs_kw, h->heur_avg_power, a->queue, a->qlen, (int)h->scn_off,
-                      h->d_heur_cs_min_kw, h->heur_min_action, a->qmin, a->qmax};
+    const HeurArgs ha{h->d_port_slot, h->d_heur_cs_kw, h->heur_avg_power, a->q.queue, a->q.qlen, (int)h->scn_off,
+                      h->d_heur_cs_min_kw, h->heur_min_action, a->q.qmin, a->q.qmax};
     const int t = h->current_step;
     if (a->kind == EV2G_AGENT_ROUND_ROBIN_GF || a->kind == EV2G_AGENT_ROUND_ROBIN_GF_OFF_ALLOWED) {
         // as RoundRobin below, with the two power lists in the stage
@@ -1569,7 +1577,6 @@ int ev2g_heuristic_actions(ev2g_handle *h, ev2g_heuristic *a, double *actions) {
     if (rc) return rc;
     if (!actions) return fail(h, EV2G_ERR_ARG, "ev2g_heuristic_actions: actions is null");
     if (h->current_step >= h->T) return fail(h, EV2G_ERR_DONE, "ev2g_heuristic_actions: episode is done, reset the environment");
-    (void)hipSetDevice(h->device);
     return heuristic_launch(h, a, actions);
 }
 
@@ -1583,18 +1590,26 @@ int ev2g_heuristic_run(ev2g_handle *h, ev2g_heuristic *a, int k_steps, double *a
 }
 
 // ---- communication-fault links (ev2g_link.h) ----
-// a host matrix in the reference's layout [E, P, T] as a device matrix [T, E, P]
-static int link_upload(ev2g_handle *h, const double *src, int E, int P, int T, double **dst) {
+// a host matrix in the reference's layout [E, P, T] in the device's [T, E, P]
+static std::vector<double> link_transposed(const double *src, int E, int P, int T) {
     std::vector<double> tr((size_t)E * P * T);
     for (int e = 0; e < E; e++)
         for (int p = 0; p < P; p++)
             for (int t = 0; t < T; t++) tr[((size_t)t * E + e) * P + p] = src[((size_t)e * P + p) * T + t];
-    HIPCHK(h, hipMalloc((void **)dst, tr.size() * sizeof(double)));
-    HIPCHK(h, hipMemcpy(*dst, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
-    return EV2G_OK;
+    return tr;
 }
 
-int ev2g_link_reset_state(ev2g_handle *h, ev2g_link *l);
+// the device stage of a link: the held commands and the two energy columns (zero: what ev2g_link_reset_state leaves), the uniforms the caller
+// gave (empty: none), and the stream drained behind their copies
+static int link_device_stage(ev2g_handle *h, ev2g_link *l, const std::vector<double> &rand_act, const std::vector<double> &rand_obs) {
+    for (double **b : {&l->held, &l->prev, &l->actual})
+        if (int rc = dalloc(h, l->allocs, (size_t)l->E * l->P, b)) return rc;
+    if (!rand_act.empty())
+        if (int rc = upload(h, l->allocs, rand_act.data(), rand_act.size(), &l->rand_act)) return rc;
+    if (!rand_obs.empty())
+        if (int rc = upload(h, l->allocs, rand_obs.data(), rand_obs.size(), &l->rand_obs)) return rc;
+    return drain(h);
+}
 
 int ev2g_link_create(ev2g_handle *h, double p_fail, double p_delay, uint64_t seed_act, uint64_t seed_obs, const double *rand_act,
                      const double *rand_obs, ev2g_link **out) {
@@ -1609,25 +1624,19 @@ int ev2g_link_create(ev2g_handle *h, double p_fail, double p_delay, uint64_t see
     ev2g_link *l = new ev2g_link();
     l->E = h->E; l->P = h->P; l->T = h->T;
     l->p_fail = p_fail; l->p_delay = p_delay; l->seed_act = seed_act; l->seed_obs = seed_obs;
-    const size_t EP = (size_t)h->E * h->P * sizeof(double);
-    int rc = EV2G_OK;
-    if (hipMalloc((void **)&l->held, EP) != hipSuccess || hipMalloc((void **)&l->prev, EP) != hipSuccess || hipMalloc((void **)&l->actual, EP) != hipSuccess)
-        rc = fail(h, EV2G_ERR_HIP, "ev2g_link_create: device allocation failed");
-    if (!rc && rand_act && p_fail > 0.0) rc = link_upload(h, rand_act, l->E, l->P, l->T, &l->rand_act);
-    if (!rc && rand_obs && p_delay > 0.0) rc = link_upload(h, rand_obs, l->E, l->P, l->T, &l->rand_obs);
-    if (!rc) { h->links.push_back(l); rc = ev2g_link_reset_state(h, l); if (rc) h->links.pop_back(); }
-    if (rc) { link_free(l); return rc; }
-    *out = l;
-    return EV2G_OK;
+    // (the copies' sources: they outlive the stage's drain, and the tail's behind a failure)
+    std::vector<double> ta, to;
+    if (rand_act && p_fail > 0.0) ta = link_transposed(rand_act, l->E, l->P, l->T);
+    if (rand_obs && p_delay > 0.0) to = link_transposed(rand_obs, l->E, l->P, l->T);
+    return owned_created(h, &ev2g_handle::links, l, link_device_stage(h, l, ta, to), out);
 }
 
-void ev2g_link_destroy(ev2g_handle *h, ev2g_link *l) { owned_destroy(h, &ev2g_handle::links, l, link_free); }
+void ev2g_link_destroy(ev2g_handle *h, ev2g_link *l) { owned_destroy(h, &ev2g_handle::links, l); }
 
 static int link_check(ev2g_handle *h, ev2g_link *l, const char *who) {
     if (int rc = owned_check(h, &ev2g_handle::links, l, "link", who)) return rc;
     if (l->E != h->E || l->P != h->P || l->T != h->T)
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports / steps differ from those the link was created for");
-    (void)hipSetDevice(h->device);
     return EV2G_OK;
 }
 
@@ -1640,10 +1649,10 @@ int ev2g_link_reset_state(ev2g_handle *h, ev2g_link *l) {
     return EV2G_OK;
 }
 
-// one of the link's own blocks, allocated on first use
-static int link_buffer(ev2g_handle *h, void **p, size_t bytes) {
-    if (!*p) HIPCHK(h, hipMalloc(p, std::max<size_t>(bytes, 1)));
-    return EV2G_OK;
+// one of the link's own blocks of n elements, allocated on first use
+extern "C++" template <typename T>
+static int link_buffer(ev2g_handle *h, ev2g_link *l, T **p, size_t n) {
+    return *p ? EV2G_OK : dalloc(h, l->allocs, n, p);
 }
 
 // the fail kernel for step t: in [E, P] (float64, or float32 with in32) -> the link's held block, and `out` when given
@@ -1687,7 +1696,7 @@ int ev2g_link_observe(ev2g_handle *h, ev2g_link *l, int t, double *obs, float *o
 
 float *ev2g_link_obs_f32(ev2g_handle *h, ev2g_link *l) {
     if (link_check(h, l, "ev2g_link_obs_f32")) return nullptr;
-    if (link_buffer(h, (void **)&l->obs32, (size_t)l->E * h->D * sizeof(float))) return nullptr;
+    if (link_buffer(h, l, &l->obs32, (size_t)l->E * h->D)) return nullptr;
     return l->obs32;
 }
 
@@ -1717,10 +1726,25 @@ int ev2g_link_rollout(ev2g_handle *h, ev2g_link *l, const ev2g_mlp *m, int k_ste
 }
 
 // ---- distribution grid: the Laurent power flow after each step (ev2g_grid.h) ----
-static int grid_upload(ev2g_handle *h, const void *src, size_t bytes, void **dst) {
-    HIPCHK(h, hipMalloc(dst, std::max<size_t>(bytes, 1)));
-    HIPCHK(h, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return EV2G_OK;
+// the device stage of a grid: the network (kt: K transposed, n x n complex), the base profiles if any with the episode's voltage statistics
+// (zero until the first step of an episode overwrites them), the per-env rows, and the stream drained behind the copies
+static int grid_device_stage(ev2g_handle *h, ev2g_grid *g, const std::vector<double> &kt, const double *L, const double *p_base, const double *q_base) {
+    const size_t n = (size_t)g->n, E = (size_t)g->E, prof = (size_t)g->M * (g->T + 1) * n;
+    if (int rc = upload(h, g->allocs, (const double2 *)kt.data(), n * n, &g->Kt)) return rc;
+    if (int rc = upload(h, g->allocs, (const double2 *)L, n, &g->L)) return rc;
+    if (p_base) {
+        if (int rc = upload(h, g->allocs, p_base, prof, &g->p_base)) return rc;
+        if (int rc = upload(h, g->allocs, q_base, prof, &g->q_base)) return rc;
+    }
+    if (int rc = dalloc(h, g->allocs, E * (n + 1), &g->vm)) return rc;
+    if (int rc = dalloc(h, g->allocs, E, &g->rew)) return rc;
+    if (p_base) {
+        for (double **b : {&g->vv_sum, &g->rew_sum})
+            if (int rc = dalloc(h, g->allocs, E, b)) return rc;
+        for (int **b : {&g->vv_count, &g->vv_steps})
+            if (int rc = dalloc(h, g->allocs, E, b)) return rc;
+    }
+    return drain(h);
 }
 
 int ev2g_grid_create(ev2g_handle *h, int n_bus, const double *K, const double *L, double s_base, double tolerance, int max_iter,
@@ -1746,28 +1770,10 @@ int ev2g_grid_create(ev2g_handle *h, int n_bus, const double *K, const double *L
             kt[((size_t)j * n + i) * 2] = K[((size_t)i * n + j) * 2];
             kt[((size_t)j * n + i) * 2 + 1] = K[((size_t)i * n + j) * 2 + 1];
         }
-    int rc = grid_upload(h, kt.data(), kt.size() * sizeof(double), (void **)&g->Kt);
-    if (!rc) rc = grid_upload(h, L, (size_t)n * 2 * sizeof(double), (void **)&g->L);
-    const size_t prof = (size_t)h->M * (h->T + 1) * n * sizeof(double);
-    if (!rc && p_base) rc = grid_upload(h, p_base, prof, (void **)&g->p_base);
-    if (!rc && q_base) rc = grid_upload(h, q_base, prof, (void **)&g->q_base);
-    if (!rc && (hipMalloc((void **)&g->vm, (size_t)h->E * n_bus * sizeof(double)) != hipSuccess || hipMalloc((void **)&g->rew, (size_t)h->E * sizeof(double)) != hipSuccess))
-        rc = fail(h, EV2G_ERR_HIP, "ev2g_grid_create: device allocation failed");
-    if (!rc && p_base) {   // the episode's voltage statistics: zero until the first step of an episode overwrites them
-        const size_t Ed = (size_t)h->E * sizeof(double), Ei = (size_t)h->E * sizeof(int);
-        if (hipMalloc((void **)&g->vv_sum, Ed) != hipSuccess || hipMalloc((void **)&g->rew_sum, Ed) != hipSuccess ||
-            hipMalloc((void **)&g->vv_count, Ei) != hipSuccess || hipMalloc((void **)&g->vv_steps, Ei) != hipSuccess ||
-            hipMemset(g->vv_sum, 0, Ed) != hipSuccess || hipMemset(g->rew_sum, 0, Ed) != hipSuccess ||
-            hipMemset(g->vv_count, 0, Ei) != hipSuccess || hipMemset(g->vv_steps, 0, Ei) != hipSuccess)
-            rc = fail(h, EV2G_ERR_HIP, "ev2g_grid_create: device allocation failed");
-    }
-    if (rc) { grid_free(g); return rc; }
-    h->grids.push_back(g);
-    *out = g;
-    return EV2G_OK;
+    return owned_created(h, &ev2g_handle::grids, g, grid_device_stage(h, g, kt, L, p_base, q_base), out);
 }
 
-void ev2g_grid_destroy(ev2g_handle *h, ev2g_grid *g) { owned_destroy(h, &ev2g_handle::grids, g, grid_free); }
+void ev2g_grid_destroy(ev2g_handle *h, ev2g_grid *g) { owned_destroy(h, &ev2g_handle::grids, g); }
 
 static int grid_check(ev2g_handle *h, ev2g_grid *g, bool run, const char *who) {
     if (int rc = owned_check(h, &ev2g_handle::grids, g, "grid", who)) return rc;
@@ -1776,7 +1782,6 @@ static int grid_check(ev2g_handle *h, ev2g_grid *g, bool run, const char *who) {
         if (g->E != h->E || g->T != h->T || g->M != h->M || g->n != h->R)
             return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / steps / pool / transformers differ from those the grid was created for");
     }
-    (void)hipSetDevice(h->device);
     return EV2G_OK;
 }
 
@@ -1919,9 +1924,9 @@ static int run_chain(ev2g_handle *h, StepChain c, int k) {
     int rc;
     if (l) {   // (the link's blocks are allocated on first use)
         const size_t ED = (size_t)l->E * h->D, EP = (size_t)l->E * l->P;
-        if (c.agent && !c.actions.p) { if ((rc = link_buffer(h, (void **)&l->raw, EP * sizeof(double)))) return rc; c.actions = {l->raw}; }
-        if ((c.actor || l->p_delay > 0.0) && !c.obs.p) { if ((rc = link_buffer(h, (void **)&l->obs, ED * sizeof(double)))) return rc; c.obs = {l->obs}; }
-        if (c.actor && ((rc = link_buffer(h, (void **)&l->obs32, ED * sizeof(float))) || (rc = link_buffer(h, (void **)&l->act32, EP * sizeof(float))))) return rc;
+        if (c.agent && !c.actions.p) { if ((rc = link_buffer(h, l, &l->raw, EP))) return rc; c.actions = {l->raw}; }
+        if ((c.actor || l->p_delay > 0.0) && !c.obs.p) { if ((rc = link_buffer(h, l, &l->obs, ED))) return rc; c.obs = {l->obs}; }
+        if (c.actor && ((rc = link_buffer(h, l, &l->obs32, ED)) || (rc = link_buffer(h, l, &l->act32, EP)))) return rc;
     }
     if (c.agent && !c.actions.p) c.actions = {c.agent->act};
     if (g) {
@@ -1966,16 +1971,23 @@ int ev2g_grid_state_attach(ev2g_handle *h, ev2g_grid *g, const double *time_feat
     if (int rc = grid_check(h, g, true, "ev2g_grid_state_attach")) return rc;
     if (!time_features) return fail(h, EV2G_ERR_ARG, "ev2g_grid_state_attach: time_features is null");
     const int Dg = 6 + 2 * g->n + 3 * h->P;
-    const size_t ED = (size_t)h->E * Dg, EP = (size_t)h->E * h->P, tfb = (size_t)(per_scenario ? h->M : 1) * (h->T + 1) * 3 * sizeof(double);
+    const size_t ED = (size_t)h->E * Dg, EP = (size_t)h->E * h->P, tfn = (size_t)(per_scenario ? h->M : 1) * (h->T + 1) * 3;
+    const auto detach = [g] {
+        free_pool(g->swap_allocs);
+        g->tf = g->obs = g->act = nullptr; g->obs32 = g->act32 = nullptr;
+        g->Dg = 0; g->obs32_step = -1; g->obs32_epoch = -1;
+    };
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (a second attach replaces blocks that queued kernels may still read)
-    for (void **p : {(void **)&g->tf, (void **)&g->obs, (void **)&g->act, (void **)&g->obs32, (void **)&g->act32}) { (void)hipFree(*p); *p = nullptr; }
-    g->Dg = 0; g->obs32_step = -1; g->obs32_epoch = -1;
-    int rc = grid_upload(h, time_features, tfb, (void **)&g->tf);
-    if (!rc && (hipMalloc((void **)&g->obs, ED * sizeof(double)) != hipSuccess || hipMalloc((void **)&g->obs32, ED * sizeof(float)) != hipSuccess ||
-                hipMalloc((void **)&g->act, EP * sizeof(double)) != hipSuccess || hipMalloc((void **)&g->act32, EP * sizeof(float)) != hipSuccess))
-        rc = fail(h, EV2G_ERR_HIP, "ev2g_grid_state_attach: device allocation failed");
+    detach();
+    int rc = upload(h, g->swap_allocs, time_features, tfn, &g->tf);
+    if (!rc) rc = dalloc(h, g->swap_allocs, ED, &g->obs);
+    if (!rc) rc = dalloc(h, g->swap_allocs, ED, &g->obs32);
+    if (!rc) rc = dalloc(h, g->swap_allocs, EP, &g->act);
+    if (!rc) rc = dalloc(h, g->swap_allocs, EP, &g->act32);
+    const int drained = drain(h);   // (time_features is the caller's: also behind a failure)
+    if (!rc) rc = drained;
     if (rc) {
-        for (void **p : {(void **)&g->tf, (void **)&g->obs, (void **)&g->act, (void **)&g->obs32, (void **)&g->act32}) { (void)hipFree(*p); *p = nullptr; }
+        detach();
         return rc;
     }
     g->tf_per_scn = per_scenario ? 1 : 0;
@@ -2047,6 +2059,12 @@ static int wrap_shape_check(ev2g_handle *h, int kind, const std::string &who) {
     return EV2G_OK;
 }
 
+// the device stage of a wrapper: its float64 block and, for the repair layer, the queue with its power lists
+static int wrap_device_stage(ev2g_handle *h, ev2g_wrap *w) {
+    if (int rc = dalloc(h, w->allocs, (size_t)w->E * w->P, &w->act)) return rc;
+    return w->kind == EV2G_WRAP_RESCALE_REPAIR ? queue_alloc(h, w->allocs, w->E, w->P, true, &w->q) : EV2G_OK;
+}
+
 int ev2g_wrap_create(ev2g_handle *h, int kind, ev2g_wrap **out) {
     if (!h || !out) return fail(h, EV2G_ERR_ARG, "ev2g_wrap_create: null argument");
     *out = nullptr;
@@ -2056,35 +2074,21 @@ int ev2g_wrap_create(ev2g_handle *h, int kind, ev2g_wrap **out) {
     (void)hipSetDevice(h->device);
     ev2g_wrap *w = new ev2g_wrap();
     w->kind = kind; w->E = h->E; w->P = h->P;
-    const size_t EP = (size_t)h->E * h->P;
-    bool ok = hipMalloc((void **)&w->act, EP * sizeof(double)) == hipSuccess;
-    if (ok && kind == EV2G_WRAP_RESCALE_REPAIR)
-        ok = hipMalloc((void **)&w->queue, EP * sizeof(int)) == hipSuccess && hipMalloc((void **)&w->qlen, (size_t)h->E * sizeof(int)) == hipSuccess &&
-             hipMalloc((void **)&w->qmin, EP * sizeof(double)) == hipSuccess && hipMalloc((void **)&w->qmax, EP * sizeof(double)) == hipSuccess &&
-             hipMemsetAsync(w->qlen, 0, (size_t)h->E * sizeof(int), h->stream) == hipSuccess;
-    if (!ok) {
-        wrap_free(w);
-        return fail(h, EV2G_ERR_HIP, "ev2g_wrap_create: device allocation failed");
-    }
-    h->wraps.push_back(w);
-    *out = w;
-    return EV2G_OK;
+    return owned_created(h, &ev2g_handle::wraps, w, wrap_device_stage(h, w), out);
 }
 
-void ev2g_wrap_destroy(ev2g_handle *h, ev2g_wrap *w) { owned_destroy(h, &ev2g_handle::wraps, w, wrap_free); }
+void ev2g_wrap_destroy(ev2g_handle *h, ev2g_wrap *w) { owned_destroy(h, &ev2g_handle::wraps, w); }
 
 static int wrap_check(ev2g_handle *h, ev2g_wrap *w, const char *who) {
     if (int rc = owned_check(h, &ev2g_handle::wraps, w, "wrapper", who)) return rc;
     if (w->E != h->E || w->P != h->P)
         return fail(h, EV2G_ERR_ARG, std::string(who) + ": the loaded scenarios' envs / ports differ from those the wrapper was created for");
-    if (int rc = wrap_shape_check(h, w->kind, who)) return rc;
-    (void)hipSetDevice(h->device);
-    return EV2G_OK;
+    return wrap_shape_check(h, w->kind, who);
 }
 
 int ev2g_wrap_reset_state(ev2g_handle *h, ev2g_wrap *w) {
     if (int rc = wrap_check(h, w, "ev2g_wrap_reset_state")) return rc;
-    if (w->qlen) HIPCHK(h, hipMemsetAsync(w->qlen, 0, (size_t)w->E * sizeof(int), h->stream));
+    if (w->q.qlen) HIPCHK(h, hipMemsetAsync(w->q.qlen, 0, (size_t)w->E * sizeof(int), h->stream));
     return EV2G_OK;
 }
 
@@ -2094,7 +2098,7 @@ static int wrap_launch(ev2g_handle *h, ev2g_wrap *w, const void *in, bool in32, 
     const DevScn &s = h->scn;
     if (w->kind == EV2G_WRAP_RESCALE_REPAIR) {
         // one wavefront per env, up to four per workgroup while their LDS stages fit 64 KiB
-        const WrapArgs wa{h->d_port_slot, h->d_heur_cs_kw, h->d_heur_cs_min_kw, w->queue, w->qlen, w->qmin, w->qmax, (int)h->scn_off};
+        const WrapArgs wa{h->d_port_slot, h->d_heur_cs_kw, h->d_heur_cs_min_kw, w->q.queue, w->q.qlen, w->q.qmin, w->q.qmax, (int)h->scn_off};
         const size_t wb = ev2g_wrap_wave_bytes(s.P);   // (<= 64 KiB: wrap_shape_check)
         const int epb = (int)std::min<size_t>(EV2G_WRAP_BLOCK / 64, 65536 / wb);
         const dim3 grid((s.E + epb - 1) / epb), block(64 * epb);
@@ -2154,13 +2158,8 @@ static std::array<const float **, AC_ARRAYS> ac_arrays(AcDev &d) {
     return {&d.w1, &d.b1, &d.w2, &d.b2, &d.w3, &d.b3, &d.u1, &d.c1, &d.u2, &d.c2, &d.u3, &d.c3};
 }
 
-static int ac_check(ev2g_handle *h, ev2g_acpolicy *ac, const char *who) {
-    if (!h || !ac) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (std::find(h->acs.begin(), h->acs.end(), ac) == h->acs.end())
-        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the actor-critic was not created on this handle");
-    (void)hipSetDevice(h->device);
-    return EV2G_OK;
-}
+// (a policy's entries run without scenarios, ev2g_ac_collect apart)
+static int ac_check(ev2g_handle *h, ev2g_acpolicy *ac, const char *who) { return owned_check(h, &ev2g_handle::acs, ac, "actor-critic", who, false); }
 
 // packs the twelve host arrays into the object's device arrays (allocated at create) and drains the stream: the staging vectors are temporaries
 static int ac_upload_weights(ev2g_handle *h, ev2g_acpolicy *ac, const AcWeights &w) {
@@ -2262,19 +2261,13 @@ int ev2g_ac_create(ev2g_handle *h, int d_in, int h1, int h2, int v1, int v2, int
     ac->relu = activation == EV2G_AC_RELU;
     ac->seed = seed; ac->n = 0;
     ac->lds = ev2g_ac_lds(d).bytes;
-    if (const int rc = ac_device_stage(h, ac, w, log_std)) {   // the one cleanup path
-        ac_free(ac);
-        return rc;
-    }
-    h->acs.push_back(ac);
-    *out = ac;
-    return EV2G_OK;
+    return owned_created(h, &ev2g_handle::acs, ac, ac_device_stage(h, ac, w, log_std), out);
 }
 
 // (a bound learner goes with its policy)
 void ev2g_ac_destroy(ev2g_handle *h, ev2g_acpolicy *ac) {
     if (h && ac && std::find(h->acs.begin(), h->acs.end(), ac) != h->acs.end() && ac->learner) owned_destroy(h, &ev2g_handle::ppos, ac->learner, ppo_free);
-    owned_destroy(h, &ev2g_handle::acs, ac, ac_free);
+    owned_destroy(h, &ev2g_handle::acs, ac);
 }
 
 int ev2g_ac_seed(ev2g_handle *h, ev2g_acpolicy *ac, uint64_t seed, uint64_t first_draw) {
@@ -2342,8 +2335,8 @@ int ev2g_ac_collect(ev2g_handle *h, ev2g_acpolicy *ac, int k_steps, int determin
                                      "ev2g_set_step_extras (observation step stride 0) first");
     if (ac->clipped_elems < EP) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(ac->clipped); ac->clipped = nullptr; ac->clipped_elems = 0;
-        HIPCHK(h, hipMalloc((void **)&ac->clipped, EP * sizeof(float)));
+        free_pool(ac->swap_allocs); ac->clipped = nullptr; ac->clipped_elems = 0;
+        if (int rc = dalloc(h, ac->swap_allocs, EP, &ac->clipped)) return rc;
         ac->clipped_elems = EP;
     }
     StepChain c{"ev2g_ac_collect"};
@@ -2385,13 +2378,7 @@ int ev2g_host_gae(const double *reward, const float *values, const uint8_t *epis
 }
 
 // ---- the learners (ev2g_ppo.h): PPO and A2C ----
-static int ppo_check(ev2g_handle *h, ev2g_ppo *p, const char *who) {
-    if (!h || !p) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    if (std::find(h->ppos.begin(), h->ppos.end(), p) == h->ppos.end())
-        return fail(h, EV2G_ERR_ARG, std::string(who) + ": the learner was not created on this handle");
-    (void)hipSetDevice(h->device);
-    return EV2G_OK;
-}
+static int ppo_check(ev2g_handle *h, ev2g_ppo *p, const char *who) { return owned_check(h, &ev2g_handle::ppos, p, "learner", who, false); }
 
 // an entry that drives one kind of learner on the other kind
 static int learner_check(ev2g_handle *h, ev2g_ppo *p, const char *who, int kind) {
@@ -2489,14 +2476,9 @@ static int learner_create(ev2g_handle *h, ev2g_acpolicy *ac, const char *who, co
     ev2g_ppo *p = new ev2g_ppo();
     p->spec = learner_spec(*cfg); p->plan = plan;
     p->n_blocks = (plan.n_params + 255) / 256;
-    if (const int rc = ppo_device_stage(h, p, ac, who)) {   // the one cleanup path
-        ppo_free(p);
-        return rc;
-    }
-    p->ac = ac; ac->learner = p;
-    h->ppos.push_back(p);
-    *out = p;
-    return EV2G_OK;
+    const int rc = owned_created(h, &ev2g_handle::ppos, p, ppo_device_stage(h, p, ac, who), out);
+    if (!rc) { p->ac = ac; ac->learner = p; }
+    return rc;
 }
 
 // the gradient of either kind: the advantage statistics if asked for, the gradient kernel with the learner's head, the reduction
