@@ -149,6 +149,26 @@ class PpoInfoC(C.Structure):   # ev2g_ppo_info
     _fields_ = [("lds_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("grid_cap", C.c_int32), ("n_params", C.c_int32)]
 
 
+class Td3ConfigC(C.Structure):   # ev2g_td3_config, in header order
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double), ("tau", C.c_double), ("gamma", C.c_double),
+                ("target_policy_noise", C.c_double), ("target_noise_clip", C.c_double), ("n_critics", C.c_int32), ("policy_delay", C.c_int32)]
+
+
+class ReplayRingC(C.Structure):   # ev2g_replay_ring
+    _fields_ = [("n_blocks", C.c_int32), ("T", C.c_int32), ("E", C.c_int32), ("D", C.c_int32), ("P", C.c_int32), ("obs", C.c_void_p),
+                ("actions", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p)]
+
+
+TD3_MAX_BATCH = 1024   # EV2G_TD3_MAX_BATCH
+
+
+def td3_param_shapes(d_in, h1, h2, d_out, n_critics):
+    """The 6 + 6 n_critics shapes in SB3's parameter order: the actor's six arrays, then each critic's."""
+    actor = [(h1, d_in), (h1,), (h2, h1), (h2,), (d_out, h2), (d_out,)]
+    critic = [(h1, d_in + d_out), (h1,), (h2, h1), (h2,), (1, h2), (1,)]
+    return actor + critic * int(n_critics)
+
+
 PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction")   # the six statistics of ev2g_ppo_grad
 
 

@@ -7,7 +7,8 @@ takes float32 actions (ev2g_step_extras.actions_f32), so no conversion pass sits
 `FusedMLPActor` evaluates the whole network in ONE kernel (`ev2g_mlp_forward`: bf16 MFMA, fp32 accumulation) enqueued together
 with the env step by one C call per rollout segment (`ev2g_rollout`).  `TorchMLPActor` is the same network through
 torch.nn (fp32, a dozen launches per forward): the comparison point, and the numerics reference of the fused kernel.
-The policy network itself is outside the hot path of SURVEY.md par.8 -- random weights, no learner.
+The policy network itself is outside the hot path of SURVEY.md par.8; the weights here are random draws, and the learner that trains such an
+actor on the device is ev2gym_amd.td3 (TD3 / DDPG behind a DeviceReplayCollector).
 """
 from __future__ import annotations
 

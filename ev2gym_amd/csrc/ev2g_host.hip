@@ -34,6 +34,7 @@
 #include "ev2g_ac.h"
 #include "ev2g_ppo.h"
 #include "ev2g_learner_host.h"
+#include "ev2g_td3_host.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -138,6 +139,22 @@ struct ev2g_ppo : DevOwner {
     bool have_grad = false;    // a gradient no apply has consumed yet
 };
 
+// the TD3 / DDPG learner of a policy (ev2g_td3_create, ev2g_td3.h): float32 masters, targets, Adam's state and the last gradient in the plan's
+// flat layout (actor | critic 0 | critic 1), the workspace of one batch, the two losses, and the map its refresh writes the policy's images by
+struct ev2g_mlp;
+struct ev2g_td3 : DevOwner {
+    ev2g_td3_config cfg{};
+    ev2g_mlp *policy = nullptr;
+    Td3Plan plan;
+    MlpImageMap map{};
+    float lo = -1.0f;
+    float *theta = nullptr, *target = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *work = nullptr, *loss = nullptr;
+    unsigned long long seed = 0, next_draw = 0;
+    long long n = 0, t_critic = 0, t_actor = 0;   // updates applied to the critics; Adam's step counts
+    int pending = 0, last_B = 0;                  // gradients no apply has consumed yet (bit 0: the critics', bit 1: the actor's); the batch size of the last critic gradient
+};
+static void td3_free(ev2g_td3 *t);
+
 #define EV2G_EV_RING 32
 struct ev2g_handle {
     int device = 0;
@@ -234,6 +251,7 @@ struct ev2g_handle {
     std::vector<ev2g_wrap *> wraps;             // the action wrappers created on this handle (freed with it)
     std::vector<ev2g_acpolicy *> acs;           // the Gaussian actor-critics created on this handle (freed with it)
     std::vector<ev2g_ppo *> ppos;               // the learners (PPO and A2C) created on this handle (freed with it, or with their policy)
+    std::vector<ev2g_td3 *> td3s;               // the TD3 / DDPG learners created on this handle (freed with it, or with their policy)
     unsigned ppo_attr_mask = 0;                 // ev2g_ppo_grad_kernel instantiations (bit relu + 2 head) whose dynamic-LDS attribute was set
     unsigned ac_attr_mask = 0;                  // ev2g_ac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
 };
@@ -545,6 +563,7 @@ void ev2g_destroy(ev2g_handle *h) {
     release_all(h->grids);
     release_all(h->wraps);
     release_all(h->ppos, ppo_free);   // (learners before their policies)
+    release_all(h->td3s, td3_free);
     release_all(h->acs);
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
@@ -1219,7 +1238,13 @@ struct ev2g_mlp {
     const void *fn = nullptr, *fn_big = nullptr;   // kMlpTable[plan.index], kMlpTable[plan.big_index] (null: no 32-row variant)
     int big_from = 0;           // the 32-row variant runs batches of at least this many rows: more than 16 x CUs
     std::string kernel_name;    // ev2g_mlp_kernel_name
+    ev2g_td3 *learner = nullptr;   // the TD3 / DDPG learner bound to this policy (ev2g_td3_create), destroyed with it
 };
+// (a learner leaves its policy first)
+static void td3_free(ev2g_td3 *t) {
+    if (t->policy) t->policy->learner = nullptr;
+    release_owned(t);
+}
 
 extern "C++" {   // (templates: C++ linkage inside the C-ABI block)
 // the actor kernels (MlpPlan::index / big_index): the table's order is mlp_table_key's
@@ -1306,6 +1331,9 @@ int ev2g_mlp_create(ev2g_handle *h, int d_in, int h1, int h2, int d_out, const f
 
 void ev2g_mlp_destroy(ev2g_handle *h, ev2g_mlp *m) {
     if (!m) return;
+    if (h && m->learner) owned_destroy(h, &ev2g_handle::td3s, m->learner, td3_free);   // (clears m->learner when `h` owns it)
+    // no handle, or not the learner's: the learner stays its handle's, without a policy -- its entries then refuse (td3_check), its images are gone
+    if (m->learner) m->learner->policy = nullptr;
     if (h) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); drop_rollout_graphs(h); }
     free_pool(m->allocs);
     delete m;
@@ -2643,6 +2671,336 @@ int ev2g_host_a2c_head(const float *mean, const float *value, const float *actio
     const LearnerSpec spec = learner_spec(*cfg);
     if (spec.one_row_norm_refused && spec.hyper.normalize && B == 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: normalize_advantage needs B >= 2");
     learner_host_head(spec, mean, value, actions, log_std, nullptr, advantages, returns, B, P, d_mean, d_value, d_log_std, stats);
+    return EV2G_OK;
+}
+
+// ---- the TD3 / DDPG learner (ev2g_td3.h) and the replay ring's sampler ----
+static int td3_check(ev2g_handle *h, ev2g_td3 *t, const char *who) {
+    if (int rc = owned_check(h, &ev2g_handle::td3s, t, "learner", who, false)) return rc;
+    if (!t->policy) return fail(h, EV2G_ERR_STATE, std::string(who) + ": the learner's policy was destroyed without its handle");   // (its images are gone)
+    return EV2G_OK;
+}
+
+static void td3_gemm(ev2g_handle *h, const Td3Gemm &g, int nz) {
+    const dim3 grid((unsigned)((g.N + EV2G_TD3_TILE - 1) / EV2G_TD3_TILE), (unsigned)((g.M + EV2G_TD3_TILE - 1) / EV2G_TD3_TILE), (unsigned)nz);
+    hipLaunchKernelGGL(ev2g_td3_gemm_kernel, grid, dim3(EV2G_TD3_TILE, EV2G_TD3_TILE), 0, h->stream, g);
+}
+static unsigned td3_blocks(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 1024); }
+
+// nz networks of one kind (parameter blocks th + z zP, the six arrays at off[]), all reading x [B, k0]: the two hidden layers into H1 / H2
+// (z strides B h1 / B h2) and the output layer [B, n_out] into O (z stride B n_out) under out_epi
+struct Td3Net { const float *th; long long zP; const int *off; int k0, h1, h2, n_out; float *H1, *H2, *O; };
+static void td3_forward(ev2g_handle *h, const Td3Net &n, const float *x, int B, int out_epi, int nz) {
+    const long long z1 = (long long)B * n.h1, z2 = (long long)B * n.h2, zo = (long long)B * n.n_out;
+    Td3Gemm g{};
+    g.M = B; g.sak = 1; g.sbk = 1; g.zB = n.zP; g.zbias = n.zP;
+    g.A = x; g.zA = 0; g.sam = n.k0; g.K = n.k0; g.N = n.h1; g.Bm = n.th + n.off[0]; g.sbn = n.k0; g.bias = n.th + n.off[1]; g.C = n.H1; g.ldc = n.h1; g.zC = z1;
+    g.epi = TD3_EPI_BIAS_RELU;
+    td3_gemm(h, g, nz);
+    g.A = n.H1; g.zA = z1; g.sam = n.h1; g.K = n.h1; g.N = n.h2; g.Bm = n.th + n.off[2]; g.sbn = n.h1; g.bias = n.th + n.off[3]; g.C = n.H2; g.ldc = n.h2; g.zC = z2;
+    td3_gemm(h, g, nz);
+    g.A = n.H2; g.zA = z2; g.sam = n.h2; g.K = n.h2; g.N = n.n_out; g.Bm = n.th + n.off[4]; g.sbn = n.h2; g.bias = n.th + n.off[5]; g.C = n.O; g.ldc = n.n_out; g.zC = zo;
+    g.epi = out_epi;
+    td3_gemm(h, g, nz);
+}
+// backprop from dO [nz][B, n_out] (the delta at the output layer's pre-activation) through the networks td3_forward ran: the hidden deltas into
+// D2 / D1, the six gradients into grad + z zP (grad null: none), and -- dX not null, nz 1 -- the delta of input columns [x_col0, x_col0 + x_cols)
+static void td3_backward(ev2g_handle *h, const Td3Net &n, const float *x, int B, const float *dO, float *D2, float *D1, float *grad, float *dX, int x_col0,
+                         int x_cols, int nz) {
+    const long long z1 = (long long)B * n.h1, z2 = (long long)B * n.h2, zo = (long long)B * n.n_out;
+    auto wgrad = [&](const float *delta, long long zd, int rows, const float *in, long long zin, int cols, int iw, int ib) {
+        Td3Gemm g{};
+        g.M = rows; g.N = cols; g.K = B; g.A = delta; g.zA = zd; g.sam = 1; g.sak = rows; g.Bm = in; g.zB = zin; g.sbk = cols; g.sbn = 1;
+        g.C = grad + n.off[iw]; g.ldc = cols; g.zC = n.zP; g.epi = TD3_EPI_NONE;
+        td3_gemm(h, g, nz);
+        hipLaunchKernelGGL(ev2g_td3_colsum_kernel, dim3((unsigned)((rows + 15) / 16), (unsigned)nz), dim3(256), 0, h->stream, delta, zd, B, rows, grad + n.off[ib], n.zP);
+    };
+    auto bdata = [&](const float *delta, long long zd, int k, const float *W, int ldw, int cols, const float *H, long long zH, float *out, long long zout) {
+        Td3Gemm g{};
+        g.M = B; g.N = cols; g.K = k; g.A = delta; g.zA = zd; g.sam = k; g.sak = 1; g.Bm = W; g.zB = n.zP; g.sbk = ldw; g.sbn = 1;
+        g.C = out; g.ldc = cols; g.zC = zout; g.H = H; g.ldh = cols; g.zH = zH; g.epi = H ? TD3_EPI_MASK : TD3_EPI_NONE;
+        td3_gemm(h, g, nz);
+    };
+    if (grad) wgrad(dO, zo, n.n_out, n.H2, z2, n.h2, 4, 5);
+    bdata(dO, zo, n.n_out, n.th + n.off[4], n.h2, n.h2, n.H2, z2, D2, z2);
+    if (grad) wgrad(D2, z2, n.h2, n.H1, z1, n.h1, 2, 3);
+    bdata(D2, z2, n.h2, n.th + n.off[2], n.h1, n.h1, n.H1, z1, D1, z1);
+    if (grad) wgrad(D1, z1, n.h1, x, 0, n.k0, 0, 1);
+    if (dX) bdata(D1, z1, n.h1, n.th + n.off[0] + x_col0, n.k0, x_cols, nullptr, 0, dX, 0);
+}
+static Td3Net td3_actor_net(const ev2g_td3 *t, const float *params) {
+    const Td3Plan &p = t->plan;
+    return {params, 0, p.aoff, p.d_in, p.h1, p.h2, p.d_out, t->work + p.w_ah1, t->work + p.w_ah2, t->work + p.w_amu};
+}
+static Td3Net td3_critic_net(const ev2g_td3 *t, const float *params, float *out) {
+    const Td3Plan &p = t->plan;
+    return {params + p.n_actor, p.n_critic, p.coff, p.da, p.h1, p.h2, 1, t->work + p.w_ch1, t->work + p.w_ch2, out};
+}
+
+static int td3_launch_refresh(ev2g_handle *h, ev2g_td3 *t) {
+    hipLaunchKernelGGL(ev2g_td3_refresh_kernel, dim3(td3_blocks((long long)t->plan.h1 * std::max(t->plan.d_in, t->plan.h2))), dim3(256), 0, h->stream, t->map,
+                       (const float *)t->theta);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_td3_default_config(int ddpg, ev2g_td3_config *cfg) {
+    if (!cfg) return fail(nullptr, EV2G_ERR_ARG, "ev2g_td3_default_config: cfg is null");
+    td3_default_config(ddpg, cfg);
+    return EV2G_OK;
+}
+
+static int td3_device_stage(ev2g_handle *h, ev2g_td3 *t, ev2g_mlp *m, const float *const *actor, const float *const *critics) {
+    const Td3Plan &p = t->plan;
+    const size_t G = (size_t)p.n_params;
+    float **bufs[] = {&t->theta, &t->target, &t->m, &t->v, &t->grad};
+    for (float **b : bufs)
+        if (int rc = dalloc(h, t->allocs, G, b)) return rc;
+    if (int rc = dalloc(h, t->allocs, (size_t)p.w_floats, &t->work)) return rc;
+    if (int rc = dalloc(h, t->allocs, 2, &t->loss)) return rc;
+    std::vector<float> host(G);
+    for (int i = 0; i < 6; i++) std::copy(actor[i], actor[i] + (p.aoff[i + 1] - p.aoff[i]), host.begin() + p.aoff[i]);
+    for (int j = 0; j < p.nc; j++)
+        for (int i = 0; i < 6; i++) std::copy(critics[6 * j + i], critics[6 * j + i] + (p.coff[i + 1] - p.coff[i]), host.begin() + p.n_actor + (size_t)j * p.n_critic + p.coff[i]);
+    HIPCHK(h, hipMemcpyAsync(t->theta, host.data(), G * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t->target, t->theta, G * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    const MlpDev &d = m->dev;
+    void *const w[3] = {(void *)d.w1, (void *)d.w2, (void *)d.w3};
+    float *const b[3] = {(float *)d.b1, (float *)d.b2, (float *)d.b3};
+    t->map = mlp_image_map(m->plan, w, b);
+    if (int rc = td3_launch_refresh(h, t)) return rc;   // the policy's images from the masters: the two agree by construction
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+int ev2g_td3_create(ev2g_handle *h, ev2g_mlp *policy, const ev2g_td3_config *cfg, int d_in, int h1, int h2, int d_out, const float *const *actor,
+                    const float *const *critics, uint64_t seed, ev2g_td3 **out) {
+    const char *who = "ev2g_td3_create";
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    *out = nullptr;
+    if (!policy || !cfg || !actor || !critics) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (int rc = fields_check(h, who, td3_fields(*cfg))) return rc;
+    const Td3Plan plan = plan_td3(d_in, h1, h2, d_out, cfg->n_critics);
+    if (plan.err) return fail(h, plan.err, plan.refusal);
+    const MlpDev &d = policy->dev;
+    const int want[4] = {d.d_in, d.h1, d.h2, d.d_out}, got[4] = {d_in, h1, h2, d_out};
+    const char *name[4] = {"d_in", "h1", "h2", "d_out"};
+    for (int i = 0; i < 4; i++)
+        if (want[i] != got[i])
+            return fail(h, EV2G_ERR_ARG, std::string(who) + ": " + name[i] + " " + std::to_string(got[i]) + " is not the policy's " + std::to_string(want[i]));
+    for (int i = 0; i < 6 * (1 + cfg->n_critics); i++)
+        if (!(i < 6 ? actor[i] : critics[i - 6])) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null weight array");
+    if (policy->learner) return fail(h, EV2G_ERR_STATE, std::string(who) + ": the policy already has a learner");
+    (void)hipSetDevice(h->device);
+    ev2g_td3 *t = new ev2g_td3();
+    t->cfg = *cfg; t->plan = plan; t->lo = d.out_lo; t->seed = seed;
+    const int rc = owned_created(h, &ev2g_handle::td3s, t, td3_device_stage(h, t, policy, actor, critics), out);
+    if (!rc) { t->policy = policy; policy->learner = t; }
+    return rc;
+}
+
+void ev2g_td3_destroy(ev2g_handle *h, ev2g_td3 *t) { owned_destroy(h, &ev2g_handle::td3s, t, td3_free); }
+
+static int td3_critic_stage(ev2g_handle *h, ev2g_td3 *t, const char *who, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                            const uint8_t *done, int B, float *losses) {
+    if (int rc = td3_check(h, t, who)) return rc;
+    if (!obs || !actions || !reward || !next_obs || !done) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const Td3Plan &p = t->plan;
+    float *W = t->work, *L = losses ? losses : t->loss;
+    const float sigma = (float)t->cfg.target_policy_noise, clip = (float)t->cfg.target_noise_clip;
+    const unsigned nb = td3_blocks((long long)B * p.da);
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(nb), dim3(256), 0, h->stream, obs, actions, B, p.d_in, p.d_out, t->lo, W + p.w_xa);
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(nb), dim3(256), 0, h->stream, next_obs, (const float *)nullptr, B, p.d_in, p.d_out, t->lo, W + p.w_xb);
+    td3_forward(h, td3_actor_net(t, t->target), next_obs, B, TD3_EPI_BIAS_TANH, 1);
+    hipLaunchKernelGGL(ev2g_td3_action_cols_kernel<true>, dim3(td3_blocks((long long)B * p.d_out)), dim3(256), 0, h->stream, (const float *)(W + p.w_amu), B, p.d_in,
+                       p.d_out, sigma, clip, (uint64_t)t->seed, (uint64_t)t->next_draw, W + p.w_xb);
+    if (sigma > 0.0f) t->next_draw += (unsigned long long)B * (unsigned long long)p.d_out;
+    td3_forward(h, td3_critic_net(t, t->target, W + p.w_tq), W + p.w_xb, B, TD3_EPI_BIAS, p.nc);
+    const Td3Net cn = td3_critic_net(t, t->theta, W + p.w_q);
+    td3_forward(h, cn, W + p.w_xa, B, TD3_EPI_BIAS, p.nc);
+    hipLaunchKernelGGL(ev2g_td3_critic_head_kernel, dim3(1), dim3(256), 0, h->stream, (const float *)(W + p.w_tq), (const float *)(W + p.w_q), reward, done, B, p.nc,
+                       (float)t->cfg.gamma, W + p.w_y, W + p.w_dq, L);
+    td3_backward(h, cn, W + p.w_xa, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, t->grad + p.n_actor, nullptr, 0, 0, p.nc);
+    HIPCHK(h, hipGetLastError());
+    t->pending |= 1; t->last_B = B;
+    return EV2G_OK;
+}
+
+static int td3_actor_stage(ev2g_handle *h, ev2g_td3 *t, const char *who, const float *obs, int B, float *losses) {
+    if (int rc = td3_check(h, t, who)) return rc;
+    if (!obs) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const Td3Plan &p = t->plan;
+    float *W = t->work, *L = losses ? losses : t->loss;
+    const Td3Net an = td3_actor_net(t, t->theta);
+    td3_forward(h, an, obs, B, TD3_EPI_BIAS_TANH, 1);
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(td3_blocks((long long)B * p.da)), dim3(256), 0, h->stream, obs, (const float *)nullptr, B, p.d_in, p.d_out, t->lo,
+                       W + p.w_xb);
+    hipLaunchKernelGGL(ev2g_td3_action_cols_kernel<false>, dim3(td3_blocks((long long)B * p.d_out)), dim3(256), 0, h->stream, (const float *)(W + p.w_amu), B, p.d_in,
+                       p.d_out, 0.0f, 0.0f, (uint64_t)0, (uint64_t)0, W + p.w_xb);
+    const Td3Net c0 = td3_critic_net(t, t->theta, W + p.w_q);
+    td3_forward(h, c0, W + p.w_xb, B, TD3_EPI_BIAS, 1);
+    hipLaunchKernelGGL(ev2g_td3_actor_head_kernel, dim3(1), dim3(256), 0, h->stream, (const float *)(W + p.w_q), B, W + p.w_dq, L);
+    td3_backward(h, c0, W + p.w_xb, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, nullptr, W + p.w_dmu, p.d_in, p.d_out, 1);
+    hipLaunchKernelGGL(ev2g_td3_tanh_back_kernel, dim3(td3_blocks((long long)B * p.d_out)), dim3(256), 0, h->stream, W + p.w_dmu, (const float *)(W + p.w_amu),
+                       (long long)B * p.d_out);
+    td3_backward(h, an, obs, B, W + p.w_dmu, W + p.w_e2, W + p.w_e1, t->grad, nullptr, 0, 0, 1);
+    HIPCHK(h, hipGetLastError());
+    t->pending |= 2;
+    return EV2G_OK;
+}
+
+static int td3_apply_stage(ev2g_handle *h, ev2g_td3 *t, const char *who) {
+    if (int rc = td3_check(h, t, who)) return rc;
+    if (!t->pending) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_td3_critic_grad or ev2g_td3_actor_grad first)");
+    const Td3Plan &p = t->plan;
+    const ev2g_td3_config &c = t->cfg;
+    if (t->pending & 1) {
+        const long long n = (long long)p.nc * p.n_critic;
+        t->t_critic += 1; t->n += 1;
+        hipLaunchKernelGGL(ev2g_td3_adam_kernel, dim3(td3_blocks(n)), dim3(256), 0, h->stream, t->theta + p.n_actor, t->m + p.n_actor, t->v + p.n_actor,
+                           (const float *)(t->grad + p.n_actor), n, adam_step(c.lr, c.beta1, c.beta2, c.adam_eps, t->t_critic));
+    }
+    if (t->pending & 2) {
+        t->t_actor += 1;
+        hipLaunchKernelGGL(ev2g_td3_adam_kernel, dim3(td3_blocks(p.n_actor)), dim3(256), 0, h->stream, t->theta, t->m, t->v, (const float *)t->grad, (long long)p.n_actor,
+                           adam_step(c.lr, c.beta1, c.beta2, c.adam_eps, t->t_actor));
+        hipLaunchKernelGGL(ev2g_td3_polyak_kernel, dim3(td3_blocks(p.n_params)), dim3(256), 0, h->stream, t->target, (const float *)t->theta, (long long)p.n_params,
+                           (float)(1.0 - c.tau), (float)c.tau);
+        if (int rc = td3_launch_refresh(h, t)) return rc;
+    }
+    HIPCHK(h, hipGetLastError());
+    t->pending = 0;
+    return EV2G_OK;
+}
+
+int ev2g_td3_critic_grad(ev2g_handle *h, ev2g_td3 *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                         const uint8_t *done, int B, float *losses) {
+    return td3_critic_stage(h, t, "ev2g_td3_critic_grad", obs, actions, reward, next_obs, done, B, losses);
+}
+int ev2g_td3_actor_grad(ev2g_handle *h, ev2g_td3 *t, const float *obs, int B, float *losses) { return td3_actor_stage(h, t, "ev2g_td3_actor_grad", obs, B, losses); }
+int ev2g_td3_apply(ev2g_handle *h, ev2g_td3 *t) { return td3_apply_stage(h, t, "ev2g_td3_apply"); }
+
+int ev2g_td3_update(ev2g_handle *h, ev2g_td3 *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                    const uint8_t *done, int B, float *losses) {
+    const char *who = "ev2g_td3_update";
+    if (int rc = td3_critic_stage(h, t, who, obs, actions, reward, next_obs, done, B, losses)) return rc;
+    if (int rc = td3_apply_stage(h, t, who)) return rc;
+    if (t->n % t->cfg.policy_delay != 0) return EV2G_OK;
+    if (int rc = td3_actor_stage(h, t, who, obs, B, losses)) return rc;
+    return td3_apply_stage(h, t, who);
+}
+
+// a flat buffer in the plan's layout into 6 + 6 n_critics host arrays (null entries skipped)
+static int td3_read_flat(ev2g_handle *h, const Td3Plan &p, const float *src, float *const *out) {
+    for (int i = 0; i < 6; i++)
+        if (out[i]) HIPCHK(h, hipMemcpyAsync(out[i], src + p.aoff[i], (size_t)(p.aoff[i + 1] - p.aoff[i]) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    for (int j = 0; j < p.nc; j++)
+        for (int i = 0; i < 6; i++)
+            if (out[6 + 6 * j + i])
+                HIPCHK(h, hipMemcpyAsync(out[6 + 6 * j + i], src + p.n_actor + (size_t)j * p.n_critic + p.coff[i], (size_t)(p.coff[i + 1] - p.coff[i]) * sizeof(float),
+                                         hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+int ev2g_td3_get_grads(ev2g_handle *h, ev2g_td3 *t, float *const *out) {
+    if (int rc = td3_check(h, t, "ev2g_td3_get_grads")) return rc;
+    if (!out) return fail(h, EV2G_ERR_ARG, "ev2g_td3_get_grads: null argument");
+    return td3_read_flat(h, t->plan, t->grad, out);
+}
+int ev2g_td3_get_weights(ev2g_handle *h, ev2g_td3 *t, int target, float *const *out) {
+    if (int rc = td3_check(h, t, "ev2g_td3_get_weights")) return rc;
+    if (!out) return fail(h, EV2G_ERR_ARG, "ev2g_td3_get_weights: null argument");
+    return td3_read_flat(h, t->plan, target ? t->target : t->theta, out);
+}
+int ev2g_td3_get_y(ev2g_handle *h, ev2g_td3 *t, float *y, int B) {
+    if (int rc = td3_check(h, t, "ev2g_td3_get_y")) return rc;
+    if (!y) return fail(h, EV2G_ERR_ARG, "ev2g_td3_get_y: null argument");
+    if (B < 1 || B != t->last_B) return fail(h, EV2G_ERR_ARG, "ev2g_td3_get_y: B is not the batch size of the last critic gradient");
+    HIPCHK(h, hipMemcpyAsync(y, t->work + t->plan.w_y, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+int ev2g_td3_set_rate(ev2g_handle *h, ev2g_td3 *t, double lr) {
+    if (int rc = td3_check(h, t, "ev2g_td3_set_rate")) return rc;
+    if (int rc = fields_check(h, "ev2g_td3_set_rate", td3_rate_fields(lr))) return rc;
+    t->cfg.lr = lr;
+    return EV2G_OK;
+}
+int ev2g_td3_seed(ev2g_handle *h, ev2g_td3 *t, uint64_t seed, uint64_t first_draw) {
+    if (int rc = td3_check(h, t, "ev2g_td3_seed")) return rc;
+    t->seed = seed; t->next_draw = first_draw;
+    return EV2G_OK;
+}
+int ev2g_td3_counters(ev2g_handle *h, ev2g_td3 *t, int64_t *updates, int64_t *actor_steps, uint64_t *next_draw) {
+    if (int rc = td3_check(h, t, "ev2g_td3_counters")) return rc;
+    if (updates) *updates = t->n;
+    if (actor_steps) *actor_steps = t->t_actor;
+    if (next_draw) *next_draw = t->next_draw;
+    return EV2G_OK;
+}
+
+static int replay_args(ev2g_handle *h, const char *who, int B, int n_blocks, int T, int E) {
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    if (n_blocks < 1 || n_blocks > EV2G_REPLAY_MAX_BLOCKS) return fail(h, EV2G_ERR_ARG, std::string(who) + ": n_blocks must be 1 .. " + std::to_string(EV2G_REPLAY_MAX_BLOCKS));
+    if (T < 1 || E < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": T and E must be positive");
+    return EV2G_OK;
+}
+int ev2g_replay_sample(ev2g_handle *h, const ev2g_replay_ring *ring, int B, uint64_t seed, uint64_t counter, float *obs, float *actions, float *reward,
+                       float *next_obs, uint8_t *done, int32_t *index) {
+    const char *who = "ev2g_replay_sample";
+    if (!h || !ring || !ring->obs || !ring->actions || !ring->reward || !ring->done || !obs || !actions || !reward || !next_obs || !done)
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (int rc = replay_args(h, who, B, ring->n_blocks, ring->T, ring->E)) return rc;
+    if (ring->D < 1 || ring->P < 1) return fail(h, EV2G_ERR_ARG, std::string(who) + ": D and P must be positive");
+    ReplayTable tb{};
+    for (int i = 0; i < ring->n_blocks; i++) {
+        if (!ring->obs[i] || !ring->actions[i] || !ring->reward[i] || !ring->done[i]) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null block pointer");
+        tb.obs[i] = ring->obs[i]; tb.actions[i] = ring->actions[i]; tb.reward[i] = ring->reward[i]; tb.done[i] = ring->done[i];
+    }
+    tb.n = ring->n_blocks; tb.T = ring->T; tb.E = ring->E; tb.D = ring->D; tb.P = ring->P;
+    (void)hipSetDevice(h->device);
+    hipLaunchKernelGGL(ev2g_replay_sample_kernel, dim3((unsigned)B), dim3(64), 0, h->stream, tb, seed, counter, obs, actions, reward, next_obs, done, (int *)index);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+int ev2g_host_replay_indices(int32_t *index, int B, int n_blocks, int T, int E, uint64_t seed, uint64_t counter) {
+    if (!index) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_replay_indices: null argument");
+    if (int rc = replay_args(nullptr, "ev2g_host_replay_indices", B, n_blocks, T, E)) return rc;
+    for (int row = 0; row < B; row++) {
+        const uint64_t i0 = ev2g_replay_stream_index(counter, row);
+        index[3 * row] = ev2g_replay_pick(ev2g_u01(seed, i0), n_blocks);
+        index[3 * row + 1] = ev2g_replay_pick(ev2g_u01(seed, i0 + 1), T);
+        index[3 * row + 2] = ev2g_replay_pick(ev2g_u01(seed, i0 + 2), E);
+    }
+    return EV2G_OK;
+}
+
+int ev2g_host_td3_target(const float *a_target, const float *tq, const float *reward, const uint8_t *done, int B, int P, int n_critics, double sigma,
+                         double clip, double gamma, uint64_t seed, uint64_t first_draw, float *a_next, float *y) {
+    const char *who = "ev2g_host_td3_target";
+    if (B < 1 || P < 1 || n_critics < 1 || n_critics > 2) return fail(nullptr, EV2G_ERR_ARG, std::string(who) + ": B and P must be positive, n_critics 1 or 2");
+    if (!(sigma >= 0.0) || !(clip >= 0.0) || !std::isfinite(sigma) || !std::isfinite(clip))
+        return fail(nullptr, EV2G_ERR_ARG, std::string(who) + ": sigma and clip must be finite and >= 0");
+    if (a_target && a_next) {
+        std::vector<float> normals((size_t)B * P, 0.0f);
+        if (sigma > 0.0) ev2g_ac_host_normal(normals.data(), (int64_t)B * P, seed, first_draw);
+        td3_host_smooth(a_target, normals.data(), (long long)B * P, sigma, clip, a_next);
+    }
+    if (tq) {
+        if (!reward || !done || !y) return fail(nullptr, EV2G_ERR_ARG, std::string(who) + ": null argument");
+        td3_host_y(tq, reward, done, B, n_critics, gamma, y);
+    }
+    return EV2G_OK;
+}
+int ev2g_host_polyak(float *target, const float *param, int64_t n, double tau) {
+    if (!target || !param || n < 0) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_polyak: null argument or n < 0");
+    if (!(tau >= 0.0 && tau <= 1.0)) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_polyak: tau must be in [0, 1]");
+    td3_host_polyak(target, param, (long long)n, tau);
     return EV2G_OK;
 }
 

@@ -52,7 +52,7 @@ inline LearnerSpec learner_spec(const ev2g_a2c_config &c) {
 }
 
 // ---- config checks: one checker over {field name, value, rule}, the fields in the order their refusals have always been reported in ----
-enum LearnerRule { LEARNER_GE0 = 0, LEARNER_GT0, LEARNER_UNIT };
+enum LearnerRule { LEARNER_GE0 = 0, LEARNER_GT0, LEARNER_UNIT, LEARNER_UNIT_CLOSED, LEARNER_GE1 };   // (the last two: the TD3 learner's tau / gamma and policy_delay)
 struct LearnerField { const char *name; double value; int rule; };
 
 // the fields the set-rate entries set (ev2g_ppo_set_rates, ev2g_a2c_set_rate); a config's list starts with them
@@ -74,10 +74,11 @@ inline std::vector<LearnerField> learner_fields(const ev2g_a2c_config &c) {
 
 // the EV2G_ERR_ARG message of the first field that breaks its rule ("<who>: <field> must be <range>"), or empty
 inline std::string learner_refusal(const char *who, const std::vector<LearnerField> &fields) {
-    static const char *const range[] = {"finite and >= 0", "finite and > 0", "in [0, 1)"};
+    static const char *const range[] = {"finite and >= 0", "finite and > 0", "in [0, 1)", "in [0, 1]", "finite and >= 1"};
     for (const LearnerField &f : fields) {
         const double v = f.value;
-        const bool ok = std::isfinite(v) && (f.rule == LEARNER_GE0 ? v >= 0.0 : f.rule == LEARNER_GT0 ? v > 0.0 : v >= 0.0 && v < 1.0);
+        const bool ok = std::isfinite(v) && (f.rule == LEARNER_GE0 ? v >= 0.0 : f.rule == LEARNER_GT0 ? v > 0.0 : f.rule == LEARNER_UNIT ? v >= 0.0 && v < 1.0
+                                              : f.rule == LEARNER_UNIT_CLOSED ? v >= 0.0 && v <= 1.0 : v >= 1.0);
         if (!ok) return std::string(who) + ": " + f.name + " must be " + range[f.rule];
     }
     return std::string();

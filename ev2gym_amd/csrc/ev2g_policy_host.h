@@ -7,7 +7,8 @@
 // actor-critic (ev2g_ac.h), which reads float32 operands in ev2g_mlp3_f32's layout, and ac_params(plan) is the one table of its thirteen
 // parameter arrays: pack_ac / unpack_ac / ac_array_sizes, the offsets and slabs of plan_ppo (the plan of its PPO learner, ev2g_ppo.h: accepted
 // widths, LDS layout, grid cap, workspace) and ppo_map (where the learner's kernels place every element) are loops over it.  ev2g_host.hip is
-// the device stage: it uploads the images and launches the table's entry.  Nothing here needs HIP, a handle or a kernel header, so a plain C++17 program can
+// the device stage: it uploads the images and launches the table's entry.  mlp_image_map(plan, images) is pack_mlp's inverse element by element: where
+// element (n, k) of a layer sits in its image and which bf16 term it is (the TD3 learner's refresh writes by it, ev2g_td3.h).  Nothing here needs HIP, a handle or a kernel header, so a plain C++17 program can
 // enumerate the plan and check every packed element (tests/host/policy_plan_check.cpp, ppo_plan_check.cpp).
 //
 // The LDS geometry of the actor kernels lives here too, as constexpr functions of ints: ev2g_mlp.h includes this header and lays its LDS
@@ -476,5 +477,46 @@ inline PpoMap ppo_map(const PpoPlan &pl, float *const img[AC_ARRAYS], float *con
     }
     mp.off[EV2G_PPO_ARRAYS] = pl.off[EV2G_PPO_ARRAYS];
     mp.slab_floats = pl.slab_floats; mp.n_params = pl.n_params; mp.P = pl.ac.d_out;
+    return mp;
+}
+
+// ---- the element map of a policy's images: the inverse of pack_mlp, element by element (the TD3 learner's refresh, ev2g_td3.h) ----
+// Where element (n, k) of a layer's [n_out, n_in] matrix sits in the image pack_mlp built for the plan, for each of its rounding terms: the bf16
+// fragment packing (pack_linear: one term), the streaming kernel's 16-column packing (pack_linear_s16: nw terms, term q the bf16 rounding of
+// what terms 0 .. q - 1 left), the generic float32 packing (pack_linear_f32: the float itself).  The 32-row variant of a bf16 streaming policy
+// reads the same images.  Bias element n of layer i sits at bias[i][n] (the streaming kernel's single array: bias[i] points into it).  Only
+// positions (n < n_out, k < n_in) exist in the map: padding is never addressed.
+enum MlpImageKind { MLP_IMG_BF16 = 0, MLP_IMG_S16, MLP_IMG_F32 };
+struct MlpLayerMap {
+    int kind, n_out, n_in;
+    int K;            // BF16 / F32: the image's padded input width; S16: its k-steps of 32
+    int nw;           // terms per weight (F32: 1, the float itself)
+    void *w;          // the image (uint16_t, F32: float)
+    float *bias;
+    int w_off, b_off; // where the layer's matrix and bias start in a flat buffer W1 | b1 | W2 | b2 | W3 | b3
+};
+struct MlpImageMap { MlpLayerMap layer[3]; };
+constexpr size_t mlp_image_index(const MlpLayerMap &L, int n, int k, int q) {
+    return L.kind == MLP_IMG_F32 ? packed_f32_index(n, k, L.K)
+         : L.kind == MLP_IMG_BF16 ? (((size_t)(n >> 5) * (size_t)(L.K / 16) + (size_t)(k >> 4)) * 64 + (size_t)((n & 31) + 32 * ((k & 15) >> 3))) * 8 + (size_t)(k & 7)
+                                  : ((((size_t)(n >> 4) * (size_t)L.K + (size_t)(k >> 5)) * (size_t)L.nw + (size_t)q) * 64 + (size_t)((n & 15) + 16 * ((k & 31) >> 3))) * 8 + (size_t)(k & 7);
+}
+inline MlpImageMap mlp_image_map(const MlpPlan &p, void *const w[3], float *const bias[3]) {
+    MlpImageMap mp{};
+    const int n_out[3] = {p.h1, p.h2, p.d_out}, n_in[3] = {p.d_in, p.h1, p.h2};
+    const int pad_in[3] = {p.k1, p.n1, p.n2};
+    const FusedPacking &s = p.s16;
+    const int ks[3] = {s.ks1, (s.nt1 * 16 + 31) / 32, (s.nt2 * 16 + 31) / 32};
+    int off = 0;
+    for (int i = 0; i < 3; i++) {
+        MlpLayerMap &L = mp.layer[i];
+        L.kind = p.kind == MLP_KIND_S16 ? MLP_IMG_S16 : p.kind == MLP_KIND_F32 ? MLP_IMG_F32 : MLP_IMG_BF16;
+        L.n_out = n_out[i]; L.n_in = n_in[i];
+        L.K = L.kind == MLP_IMG_S16 ? ks[i] : pad_in[i];
+        L.nw = L.kind == MLP_IMG_S16 ? s.nw : 1;
+        L.w = w[i]; L.bias = bias[i];
+        L.w_off = off; off += n_out[i] * n_in[i];
+        L.b_off = off; off += n_out[i];
+    }
     return mp;
 }

@@ -131,6 +131,23 @@ def load_library(path: Optional[str] = None):
         "ev2g_a2c_update": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
         "ev2g_host_rmsprop": (C.c_int, [vp, vp, vp, i64, dbl, dbl, dbl]),
         "ev2g_host_a2c_head": (C.c_int, [vp] * 6 + [C.c_int, C.c_int, C.POINTER(_abi.A2cConfigC), vp, vp, vp, vp]),
+        "ev2g_td3_default_config": (C.c_int, [C.c_int, C.POINTER(_abi.Td3ConfigC)]),
+        "ev2g_td3_create": (C.c_int, [vp, vp, C.POINTER(_abi.Td3ConfigC)] + [C.c_int] * 4 + [vp, vp, C.c_uint64, C.POINTER(vp)]),
+        "ev2g_td3_destroy": (None, [vp, vp]),
+        "ev2g_td3_update": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_td3_critic_grad": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_td3_actor_grad": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+        "ev2g_td3_apply": (C.c_int, [vp, vp]),
+        "ev2g_td3_get_grads": (C.c_int, [vp, vp, vp]),
+        "ev2g_td3_get_weights": (C.c_int, [vp, vp, C.c_int, vp]),
+        "ev2g_td3_get_y": (C.c_int, [vp, vp, vp, C.c_int]),
+        "ev2g_td3_set_rate": (C.c_int, [vp, vp, dbl]),
+        "ev2g_td3_seed": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ev2g_td3_counters": (C.c_int, [vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64)]),
+        "ev2g_replay_sample": (C.c_int, [vp, C.POINTER(_abi.ReplayRingC), C.c_int, C.c_uint64, C.c_uint64] + [vp] * 6),
+        "ev2g_host_replay_indices": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64]),
+        "ev2g_host_td3_target": (C.c_int, [vp] * 4 + [C.c_int] * 3 + [dbl] * 3 + [C.c_uint64, C.c_uint64, vp, vp]),
+        "ev2g_host_polyak": (C.c_int, [vp, vp, i64, dbl]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -195,7 +212,10 @@ EXPORTED_SYMBOLS = [
     "ev2g_ac_collect", "ev2g_ac_host_normal", "ev2g_gae", "ev2g_host_gae",
     "ev2g_ppo_query", "ev2g_ppo_create", "ev2g_ppo_destroy", "ev2g_ppo_set_rates", "ev2g_ppo_grad", "ev2g_ppo_apply", "ev2g_ppo_minibatch",
     "ev2g_ppo_get_grads", "ev2g_ppo_sync", "ev2g_ac_get_weights", "ev2g_host_adam", "ev2g_host_ppo_head",
-    "ev2g_a2c_create", "ev2g_a2c_set_rate", "ev2g_a2c_grad", "ev2g_a2c_apply", "ev2g_a2c_update", "ev2g_host_rmsprop", "ev2g_host_a2c_head"]
+    "ev2g_a2c_create", "ev2g_a2c_set_rate", "ev2g_a2c_grad", "ev2g_a2c_apply", "ev2g_a2c_update", "ev2g_host_rmsprop", "ev2g_host_a2c_head",
+    "ev2g_td3_default_config", "ev2g_td3_create", "ev2g_td3_destroy", "ev2g_td3_update", "ev2g_td3_critic_grad", "ev2g_td3_actor_grad", "ev2g_td3_apply",
+    "ev2g_td3_get_grads", "ev2g_td3_get_weights", "ev2g_td3_get_y", "ev2g_td3_set_rate", "ev2g_td3_seed", "ev2g_td3_counters", "ev2g_replay_sample",
+    "ev2g_host_replay_indices", "ev2g_host_td3_target", "ev2g_host_polyak"]
 
 
 def _ptr(x):
@@ -770,6 +790,83 @@ class Engine:
     def a2c_update(self, learner, obs, actions, advantages, returns, idx, B, stats=None):
         self._learner_rows("ev2g_a2c_update", learner, (obs, actions, advantages, returns), idx, B, stats)
 
+    # ---- the TD3 / DDPG learner and the replay ring's sampler (include/ev2g.h: ev2g_td3_*, ev2g_replay_sample) ------------------------------
+    def td3_create(self, mlp, actor, critics, seed=0, ddpg=False, **config):
+        """A TD3 (or, ddpg=True, DDPG) learner bound to the policy `mlp` (ev2g_td3_create): actor six host arrays, critics a list of six-array
+        lists; config overrides fields of the preset (ev2g_td3_config).  Freed by td3_destroy, with its policy or with the engine."""
+        cfg = td3_default_config(ddpg)
+        for k, v in config.items():
+            if k not in dict(_abi.Td3ConfigC._fields_):
+                raise TypeError(f"td3_create: unknown config field {k}")
+            setattr(cfg, k, int(v) if k in ("n_critics", "policy_delay") else float(v))
+        actor = [np.ascontiguousarray(a, np.float32) for a in actor]
+        flat = [np.ascontiguousarray(a, np.float32) for c in critics for a in c]
+        if len(actor) != 6 or len(flat) != 6 * cfg.n_critics:
+            raise ValueError(f"td3_create: six actor arrays and six per critic for {cfg.n_critics} critics are needed")
+        (h1, d_in), h2, d_out = actor[0].shape, actor[2].shape[0], actor[4].shape[0]
+        for a, shape in zip(actor + flat, _abi.td3_param_shapes(d_in, h1, h2, d_out, cfg.n_critics)):
+            if a.shape != shape:
+                raise ValueError(f"td3_create: a weight array has shape {a.shape}, expected {shape}")
+        pa, pc = (C.c_void_p * 6)(*[a.ctypes.data for a in actor]), (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
+        out = C.c_void_p()
+        self._check(self._lib.ev2g_td3_create(self._h, mlp, C.byref(cfg), d_in, h1, h2, d_out, pa, pc, int(seed) & (2 ** 64 - 1), C.byref(out)))
+        return out.value
+
+    def td3_destroy(self, t):
+        if t and self._h:
+            self._lib.ev2g_td3_destroy(self._h, t)
+
+    def td3_update(self, t, obs, actions, reward, next_obs, done, B, losses=None):
+        """One gradient step on contiguous DEVICE batch arrays (ev2g_td3_update); losses: float32 [2] DEVICE or None."""
+        self._check(self._lib.ev2g_td3_update(self._h, t, _ptr(obs), _ptr(actions), _ptr(reward), _ptr(next_obs), _ptr(done), int(B), _ptr(losses)))
+
+    def td3_critic_grad(self, t, obs, actions, reward, next_obs, done, B, losses=None):
+        self._check(self._lib.ev2g_td3_critic_grad(self._h, t, _ptr(obs), _ptr(actions), _ptr(reward), _ptr(next_obs), _ptr(done), int(B), _ptr(losses)))
+
+    def td3_actor_grad(self, t, obs, B, losses=None):
+        self._check(self._lib.ev2g_td3_actor_grad(self._h, t, _ptr(obs), int(B), _ptr(losses)))
+
+    def td3_apply(self, t):
+        self._check(self._lib.ev2g_td3_apply(self._h, t))
+
+    def _td3_arrays(self, entry, t, shape, *args):
+        out = [np.empty(s, np.float32) for s in _abi.td3_param_shapes(*shape)]
+        self._check(getattr(self._lib, entry)(self._h, t, *args, (C.c_void_p * len(out))(*[a.ctypes.data for a in out])))
+        return out
+
+    def td3_get_grads(self, t, shape):
+        """The last gradient of each half as 6 + 6 n_critics host float32 arrays; shape: (d_in, h1, h2, d_out, n_critics)."""
+        return self._td3_arrays("ev2g_td3_get_grads", t, shape)
+
+    def td3_get_weights(self, t, shape, target=False):
+        """The masters (or the target networks) as 6 + 6 n_critics host float32 arrays in SB3's parameter order."""
+        return self._td3_arrays("ev2g_td3_get_weights", t, shape, int(bool(target)))
+
+    def td3_get_y(self, t, B):
+        y = np.empty(int(B), np.float32)
+        self._check(self._lib.ev2g_td3_get_y(self._h, t, y.ctypes.data, int(B)))
+        return y
+
+    def td3_set_rate(self, t, lr):
+        self._check(self._lib.ev2g_td3_set_rate(self._h, t, float(lr)))
+
+    def td3_seed(self, t, seed, first_draw=0):
+        self._check(self._lib.ev2g_td3_seed(self._h, t, int(seed) & (2 ** 64 - 1), int(first_draw)))
+
+    def td3_counters(self, t):
+        """(updates applied to the critics, actor steps, the next noise draw index)."""
+        n, a, d = C.c_int64(0), C.c_int64(0), C.c_uint64(0)
+        self._check(self._lib.ev2g_td3_counters(self._h, t, C.byref(n), C.byref(a), C.byref(d)))
+        return int(n.value), int(a.value), int(d.value)
+
+    def replay_sample(self, blocks, T, E, D, P, B, seed, counter, obs, actions, reward, next_obs, done, index=None):
+        """Draw `counter` of B uniform transitions from the COMPLETE episode blocks `blocks` (a list of (obs, actions, reward, done) device arrays)
+        into the contiguous DEVICE batch arrays (ev2g_replay_sample); index: int32 [B, 3] DEVICE or None."""
+        cols = [(C.c_void_p * len(blocks))(*[_ptr(b[i]) for b in blocks]) for i in range(4)]
+        ring = _abi.ReplayRingC(len(blocks), int(T), int(E), int(D), int(P), *[C.cast(c, C.c_void_p) for c in cols])
+        self._check(self._lib.ev2g_replay_sample(self._h, C.byref(ring), int(B), int(seed) & (2 ** 64 - 1), int(counter), _ptr(obs), _ptr(actions),
+                                                 _ptr(reward), _ptr(next_obs), _ptr(done), _ptr(index)))
+
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
         if out is not None:
@@ -982,3 +1079,45 @@ def host_a2c_head(mean, value, actions, log_std, advantages, returns, vf_coef=0.
     """Host twin of the gradient kernel's A2C head (ev2g_host_a2c_head): (d_mean [B, P], d_value [B], d_log_std [P], stats [6]) float32."""
     cfg = _abi.A2cConfigC(0.0, 0.99, 1e-5, float(vf_coef), float(ent_coef), 0.5, int(bool(normalize_advantage)), 1)
     return _host_head("ev2g_host_a2c_head", cfg, mean, value, actions, log_std, advantages, returns)
+
+
+def _host_call(rc):
+    if rc != 0:
+        raise EngineError(rc, (load_library().ev2g_last_error(None) or b"").decode())
+
+
+def td3_default_config(ddpg=False):
+    """SB3's defaults of TD3, or of DDPG, as an _abi.Td3ConfigC (ev2g_td3_default_config)."""
+    cfg = _abi.Td3ConfigC()
+    _host_call(load_library().ev2g_td3_default_config(int(bool(ddpg)), C.byref(cfg)))
+    return cfg
+
+
+def host_replay_indices(B, n_blocks, T, E, seed, counter):
+    """Host twin of the sampler's draw (ev2g_host_replay_indices): int32 [B, 3] of (entry of the complete list, t, e)."""
+    out = np.empty((int(B), 3), np.int32)
+    _host_call(load_library().ev2g_host_replay_indices(out.ctypes.data, int(B), int(n_blocks), int(T), int(E), int(seed) & (2 ** 64 - 1), int(counter)))
+    return out
+
+
+def host_td3_target(a_target, tq, reward, done, sigma, clip, gamma, seed, first_draw):
+    """Host twin of the target path (ev2g_host_td3_target): (a_next [B, P], y [B] or None when tq is None) float32."""
+    a_target = np.ascontiguousarray(a_target, np.float32)
+    B, P = a_target.shape
+    a_next = np.empty((B, P), np.float32)
+    if tq is None:
+        _host_call(load_library().ev2g_host_td3_target(a_target.ctypes.data, None, None, None, B, P, 1, float(sigma), float(clip), float(gamma),
+                                                       int(seed) & (2 ** 64 - 1), int(first_draw), a_next.ctypes.data, None))
+        return a_next, None
+    tq, reward, done = np.ascontiguousarray(tq, np.float32), np.ascontiguousarray(reward, np.float32), np.ascontiguousarray(done, np.uint8)
+    y = np.empty(B, np.float32)
+    _host_call(load_library().ev2g_host_td3_target(a_target.ctypes.data, tq.ctypes.data, reward.ctypes.data, done.ctypes.data, B, P, tq.shape[0], float(sigma),
+                                                   float(clip), float(gamma), int(seed) & (2 ** 64 - 1), int(first_draw), a_next.ctypes.data, y.ctypes.data))
+    return a_next, y
+
+
+def host_polyak(target, param, tau):
+    """Host twin of the Polyak step (ev2g_host_polyak, the device's element function): float32 `target` is updated IN PLACE."""
+    assert target.dtype == np.float32 and target.flags.c_contiguous
+    param = np.ascontiguousarray(param, np.float32)
+    _host_call(load_library().ev2g_host_polyak(target.ctypes.data, param.ctypes.data, target.size, float(tau)))

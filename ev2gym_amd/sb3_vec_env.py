@@ -228,6 +228,7 @@ class DeviceReplayCollector:
         col.collect_episode()                       # one episode of all E envs: T x (actor forward -> env step), no host copies
         obs, act, rew, nxt, done = col.sample(256)  # host-side draw of indices, device gathers (torch) -- what a learner consumes
         col.set_weights(new_weights)                # the learner's updated actor
+        learner = TD3Learner(col)                   # ev2gym_amd.td3: samples and trains on the device and rewrites the collector's actor there
 
     `engine` must not have float32 hand-over buffers registered (`ev2g_set_step_extras`): the collector's rows are the hand-over.
     Arrays are torch tensors when torch is importable (PyTorch-ROCm is the SB3 side's tensor type), DeviceBuffers otherwise.
@@ -241,7 +242,9 @@ class DeviceReplayCollector:
         self.eng = eng = engine
         self.E, self.P, self.D, self.T, self.M = eng.E, eng.P, eng.D, eng.T, eng.M
         self.lo, self.precision = float(lo), precision
-        self.mlp = eng.mlp_create(*weights, out_lo=self.lo, precision=precision)
+        self.weights = [np.ascontiguousarray(w, np.float32) for w in weights]   # what the policy was created with (a TD3 / DDPG learner's initial actor)
+        self.mlp = eng.mlp_create(*self.weights, out_lo=self.lo, precision=precision)
+        self.learner = None      # the TD3Learner / DDPGLearner bound to the policy, if any (it registers itself)
         self.cap = max(2, int(capacity_episodes))   # (the reset observation of the next episode is written into the NEXT block)
         if use_torch is None:
             try:
@@ -276,9 +279,14 @@ class DeviceReplayCollector:
         eng.reset_f32(self.obs[0], self.offset)
 
     def set_weights(self, weights):
-        """The learner's new actor (host float32 arrays, torch.nn.Linear layout)."""
+        """The learner's new actor (host float32 arrays, torch.nn.Linear layout): a fresh policy object replaces the old one.  Refused while a
+        device learner (ev2gym_amd.td3) is bound to the policy: it rewrites the policy itself, and replacing the object would take it along."""
+        if getattr(self.learner, "learner", None):
+            raise RuntimeError("set_weights: a device learner is bound to this collector's policy and keeps it up to date; close() the learner first")
+        weights = [np.ascontiguousarray(w, np.float32) for w in weights]
         old = self.mlp
         self.mlp = self.eng.mlp_create(*weights, out_lo=self.lo, precision=self.precision)
+        self.weights = weights
         self.eng.mlp_destroy(old)
 
     def collect_episode(self):

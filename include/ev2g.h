@@ -812,6 +812,94 @@ int ev2g_host_rmsprop(float *theta, float *sq, const float *g, int64_t n, double
 int ev2g_host_a2c_head(const float *mean, const float *value, const float *actions, const float *log_std, const float *advantages,
                        const float *returns, int B, int P, const ev2g_a2c_config *cfg, float *d_mean, float *d_value, float *d_log_std, float *stats);
 
+/* ---- the off-policy learner of the device replay ring: SB3's TD3.train() for TD3Policy, with DDPG as a preset (csrc/ev2g_td3.h) ----
+ * One gradient step per call on a batch (s, a, r, s', done) of B rows, the update counter n incremented first:
+ *   eps = clamp(target_policy_noise * N(0, 1), -target_noise_clip, +target_noise_clip);  a' = clamp(actor_target(s') + eps, -1, 1)
+ *   y = r + ((1 - done) * gamma) * min_j critic_target_j(s', a');  critic_loss = sum_j mean((critic_j(s, a~) - y)^2) -> Adam over all critics
+ *   n % policy_delay == 0: actor_loss = -mean(critic_0(s, actor(s))), critic_0 AFTER its step -> Adam on the actor, then
+ *                          target <- (1 - tau) * target + tau * param for the critics and the actor (SB3's polyak_update)
+ * Networks: actor d_in -> h1 -> h2 -> d_out (ReLU, tanh), each critic (d_in + d_out) -> h1 -> h2 -> 1 (ReLU), the hidden widths of the bound policy.
+ * torch.optim.Adam with TD3Policy's eps 1e-8, no gradient clipping.  float32 throughout, every sum in one fixed order, no float atomics: the same
+ * call on the same state gives the same bits.  Everything is enqueued on the handle's stream; no host round trip happens inside an update.
+ * ACTIONS: `actions` holds what the replay ring stores, the env's action in [lo, 1] (lo: the bound policy's out_lo).  The critics take SB3's scaled
+ * action in [-1, 1]: the learner reads a~ = 2 a - 1 when lo = 0 and a itself when lo = -1.  `done` is used as stored (the reference registers
+ * no time limit and returns truncated = False: SB3 treats its episode ends as terminal).  reward is float32, as SB3's buffer stores it.
+ * NOISE: element (row b, port p) of a noisy update draws standard normal index next_draw + b * d_out + p of ev2g_ac_host_normal's generator under
+ * the learner's seed; next_draw then advances by B * d_out.  target_policy_noise = 0 draws nothing and advances nothing.
+ * LIMITS (a message per field otherwise): d_in <= 192, d_out <= 64, hidden widths 1 .. 400, 1 <= B <= EV2G_TD3_MAX_BATCH, n_critics 1 or 2.
+ * THE BOUND POLICY: ev2g_td3_create takes the ev2g_mlp that ev2g_collect / ev2g_rollout / ev2g_mlp_forward run and the actor's six float32
+ * arrays as masters; it rewrites the policy's packed images from them at creation and after every actor step, in the precision the policy was
+ * created with (every packing of csrc/ev2g_policy_host.h, padding untouched), so the collector reads the new actor without the weights leaving
+ * the device.  A policy has at most one learner (EV2G_ERR_STATE for a second); the learner is owned by the handle and ends with it, with
+ * ev2g_td3_destroy, or with ev2g_mlp_destroy of its policy.  Rollout graphs captured for the policy stay valid (the images keep their addresses).
+ * Not reproduced: action_noise, learning_starts, schedule objects (ev2g_td3_set_rate between calls drives one), SAC / TQC. */
+#define EV2G_TD3_MAX_BATCH 1024
+typedef struct ev2g_td3 ev2g_td3;
+typedef struct ev2g_td3_config {
+    double lr, beta1, beta2, adam_eps;                     /* 1e-3, 0.9, 0.999, 1e-8.  lr >= 0, betas in [0, 1), adam_eps > 0 */
+    double tau, gamma;                                     /* 0.005, 0.99.  both in [0, 1] */
+    double target_policy_noise, target_noise_clip;         /* TD3: 0.2, 0.5; DDPG: 0, 0.5.  finite and >= 0 */
+    int32_t n_critics, policy_delay;                       /* TD3: 2, 2; DDPG: 1, 1.  n_critics 1 or 2, policy_delay >= 1 */
+} ev2g_td3_config;
+/* SB3's defaults of TD3 (ddpg == 0) or of DDPG (ddpg != 0: one critic, no delay, no target noise) */
+int ev2g_td3_default_config(int ddpg, ev2g_td3_config *cfg);
+/* actor: six HOST float32 arrays W1 [h1, d_in], b1, W2 [h2, h1], b2, W3 [d_out, h2], b3 (d_in, h1, h2, d_out must be the policy's widths: EV2G_ERR_ARG); critics:
+ * 6 * n_critics HOST arrays, critic j's W1 [h1, d_in + d_out], b1, W2 [h2, h1], b2, W3 [1, h2], b3 [1] at [6 j, 6 j + 6).  The targets start as
+ * copies, Adam's state at zero.  Synchronises. */
+int ev2g_td3_create(ev2g_handle *h, ev2g_mlp *policy, const ev2g_td3_config *cfg, int d_in, int h1, int h2, int d_out, const float *const *actor,
+                    const float *const *critics, uint64_t seed, ev2g_td3 **out);
+void ev2g_td3_destroy(ev2g_handle *h, ev2g_td3 *t);
+/* One gradient step: obs / next_obs [B, d_in], actions [B, d_out], reward [B] float32, done [B] uint8, contiguous DEVICE arrays; losses float32
+ * [2] DEVICE (critic_loss; actor_loss, written only by an update that steps the actor), may be NULL. */
+int ev2g_td3_update(ev2g_handle *h, ev2g_td3 *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                    const uint8_t *done, int B, float *losses);
+/* The two gradient stages without the apply.  ev2g_td3_critic_grad leaves the critics' gradient and y in the learner and draws the noise;
+ * ev2g_td3_actor_grad leaves the actor's gradient (through critic_0 as it is now).  ev2g_td3_apply consumes the pending one (EV2G_ERR_STATE
+ * without one): for a critic gradient Adam on the critics and n += 1; for an actor gradient Adam on the actor, the Polyak step and the
+ * rewrite of the bound policy's images.  ev2g_td3_update is critic_grad, apply and -- when n % policy_delay == 0 -- actor_grad, apply.
+ * Both halves may be pending at once (ev2g_td3_actor_grad after ev2g_td3_critic_grad without an apply in between: the actor's gradient through
+ * critic_0 BEFORE its step); ev2g_td3_apply then consumes both, the critics' first, and drops neither.  Computing a half again replaces it. */
+int ev2g_td3_critic_grad(ev2g_handle *h, ev2g_td3 *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                         const uint8_t *done, int B, float *losses);
+int ev2g_td3_actor_grad(ev2g_handle *h, ev2g_td3 *t, const float *obs, int B, float *losses);
+int ev2g_td3_apply(ev2g_handle *h, ev2g_td3 *t);
+/* out: 6 + 6 * n_critics HOST arrays in SB3's parameter order (the actor's six, then each critic's six), each may be NULL.  get_grads: the
+ * last gradient of each half.  get_weights: the masters (target == 0) or the target networks (target != 0).  ev2g_td3_get_y: y [B] of the last
+ * critic gradient (B: its batch size).  All synchronise.  ev2g_td3_get_y and ev2g_td3_counters below are read-only additions for tests and
+ * for TD3Learner.train()'s update count: nothing else depends on them. */
+int ev2g_td3_get_grads(ev2g_handle *h, ev2g_td3 *t, float *const *out);
+int ev2g_td3_get_weights(ev2g_handle *h, ev2g_td3 *t, int target, float *const *out);
+int ev2g_td3_get_y(ev2g_handle *h, ev2g_td3 *t, float *y, int B);
+int ev2g_td3_set_rate(ev2g_handle *h, ev2g_td3 *t, double lr);
+/* the noise stream's seed and the draw index the next noisy update starts at */
+int ev2g_td3_seed(ev2g_handle *h, ev2g_td3 *t, uint64_t seed, uint64_t first_draw);
+/* updates applied to the critics (n), actor steps (each one a refresh of the bound policy), the next draw index; each may be NULL */
+int ev2g_td3_counters(ev2g_handle *h, ev2g_td3 *t, int64_t *updates, int64_t *actor_steps, uint64_t *next_draw);
+/* ---- the uniform sampler of a device replay ring of episode blocks ----
+ * A block holds one episode of E envs: obs [T + 1, E, D] float32 (row t + 1 is row t's next observation, row T the terminal one), actions
+ * [T, E, P] float32, reward [T, E] float64, done [T, E] uint8.  The ring lists its COMPLETE blocks only (HOST arrays of n_blocks DEVICE pointers
+ * each, n_blocks <= 32).  Row i of draw `counter` reads the uniforms 3 j, 3 j + 1, 3 j + 2 of ev2g_host_uniform's generator under `seed`, j =
+ * counter * EV2G_TD3_MAX_BATCH + i, and picks (entry of the list, t, e) as min(floor(u * n), n - 1) for n = n_blocks, T, E: a pure function of
+ * (seed, counter, row, bounds), which ev2g_host_replay_indices repeats on the host.  The row's s, a, (float) r, s' = obs[t + 1, e] and done go to
+ * the contiguous DEVICE batch arrays; index int32 [B, 3] DEVICE (may be NULL) receives the picks.  1 <= B <= EV2G_TD3_MAX_BATCH.  The caller
+ * advances `counter` by one per draw.  Asynchronous on the handle's stream. */
+typedef struct ev2g_replay_ring {
+    int32_t n_blocks, T, E, D, P;
+    const float *const *obs;
+    const float *const *actions;
+    const double *const *reward;
+    const uint8_t *const *done;
+} ev2g_replay_ring;
+int ev2g_replay_sample(ev2g_handle *h, const ev2g_replay_ring *ring, int B, uint64_t seed, uint64_t counter, float *obs, float *actions,
+                       float *reward, float *next_obs, uint8_t *done, int32_t *index);
+int ev2g_host_replay_indices(int32_t *index, int B, int n_blocks, int T, int E, uint64_t seed, uint64_t counter);
+/* Host twins of the learner's element functions.  ev2g_host_td3_target: a_next [B, P] = clamp(a_target + clamp(sigma N, -clip, clip), -1, 1) with
+ * the draws first_draw + b P + p under `seed` (tq == NULL: only that), and -- given the target critics' values tq [n_critics, B] the caller
+ * computed on (s', a_next) -- y [B].  ev2g_host_polyak: n elements of target moved towards param. */
+int ev2g_host_td3_target(const float *a_target, const float *tq, const float *reward, const uint8_t *done, int B, int P, int n_critics, double sigma,
+                         double clip, double gamma, uint64_t seed, uint64_t first_draw, float *a_next, float *y);
+int ev2g_host_polyak(float *target, const float *param, int64_t n, double tau);
+
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
 void ev2g_free(ev2g_handle *h, void *p);
