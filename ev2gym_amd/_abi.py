@@ -159,12 +159,25 @@ class ReplayRingC(C.Structure):   # ev2g_replay_ring
                 ("actions", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p)]
 
 
+class SacConfigC(C.Structure):   # ev2g_sac_config, in header order
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double), ("tau", C.c_double), ("gamma", C.c_double),
+                ("ent_coef", C.c_double), ("target_entropy", C.c_double), ("n_critics", C.c_int32), ("target_update_interval", C.c_int32),
+                ("ent_coef_auto", C.c_int32), ("target_entropy_auto", C.c_int32)]
+
+
 TD3_MAX_BATCH = 1024   # EV2G_TD3_MAX_BATCH
 
 
 def td3_param_shapes(d_in, h1, h2, d_out, n_critics):
     """The 6 + 6 n_critics shapes in SB3's parameter order: the actor's six arrays, then each critic's."""
     actor = [(h1, d_in), (h1,), (h2, h1), (h2,), (d_out, h2), (d_out,)]
+    critic = [(h1, d_in + d_out), (h1,), (h2, h1), (h2,), (1, h2), (1,)]
+    return actor + critic * int(n_critics)
+
+
+def sac_param_shapes(d_in, h1, h2, d_out, n_critics):
+    """The 8 + 6 n_critics shapes in SB3's parameter order: actor.latent_pi.{0,2}, actor.mu, actor.log_std (weight, bias each), then each critic's."""
+    actor = [(h1, d_in), (h1,), (h2, h1), (h2,), (d_out, h2), (d_out,), (d_out, h2), (d_out,)]
     critic = [(h1, d_in + d_out), (h1,), (h2, h1), (h2,), (1, h2), (1,)]
     return actor + critic * int(n_critics)
 

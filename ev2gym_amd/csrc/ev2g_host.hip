@@ -35,6 +35,7 @@
 #include "ev2g_ppo.h"
 #include "ev2g_learner_host.h"
 #include "ev2g_td3_host.h"
+#include "ev2g_sac_host.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -155,6 +156,23 @@ struct ev2g_td3 : DevOwner {
 };
 static void td3_free(ev2g_td3 *t);
 
+// a SAC learner with its collection actor (ev2g_sac_create, ev2g_sac.h): float32 masters, Adam's state and the last gradient in the plan's flat
+// layout (actor | critic 0 | critic 1), the target critics, log_ent_coef with its Adam state and gradient, the workspace of one batch, the four
+// losses, the collection actor's packed images, and the two noise streams
+struct ev2g_sac : DevOwner {
+    ev2g_sac_config cfg{};
+    SacPlan plan;
+    SacDev dev{};
+    size_t lds = 0;
+    float lo = -1.0f;
+    double target_entropy = 0.0;
+    float *theta = nullptr, *target = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *work = nullptr, *loss = nullptr;
+    float *alpha = nullptr, *g_alpha = nullptr;   // {log_ent_coef, m, v}; its gradient
+    unsigned long long seed = 0, next_draw = 0, act_seed = 0, act_n = 0;
+    long long n = 0, n_target = 0, t_critic = 0, t_actor = 0;   // updates applied, Polyak steps among them; Adam's step counts
+    int pending = 0, last_B = 0, last_actor_B = 0;              // bit 0: the critics' gradient, bit 1: the actor's and log_ent_coef's
+};
+
 #define EV2G_EV_RING 32
 struct ev2g_handle {
     int device = 0;
@@ -252,6 +270,8 @@ struct ev2g_handle {
     std::vector<ev2g_acpolicy *> acs;           // the Gaussian actor-critics created on this handle (freed with it)
     std::vector<ev2g_ppo *> ppos;               // the learners (PPO and A2C) created on this handle (freed with it, or with their policy)
     std::vector<ev2g_td3 *> td3s;               // the TD3 / DDPG learners created on this handle (freed with it, or with their policy)
+    std::vector<ev2g_sac *> sacs;               // the SAC learners created on this handle (freed with it)
+    unsigned sac_attr_mask = 0;                 // ev2g_sac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
     unsigned ppo_attr_mask = 0;                 // ev2g_ppo_grad_kernel instantiations (bit relu + 2 head) whose dynamic-LDS attribute was set
     unsigned ac_attr_mask = 0;                  // ev2g_ac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
 };
@@ -564,6 +584,7 @@ void ev2g_destroy(ev2g_handle *h) {
     release_all(h->wraps);
     release_all(h->ppos, ppo_free);   // (learners before their policies)
     release_all(h->td3s, td3_free);
+    release_all(h->sacs);
     release_all(h->acs);
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
@@ -1470,12 +1491,15 @@ static bool collect_direct(const ev2g_handle *h) {
     return collect_direct(h->shape, x.cost != nullptr, x.obs_f32 != nullptr, x.actions_f32 != nullptr);
 }
 
-int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_transitions *tr) {
-    if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_collect: no scenarios loaded");
-    if (!m || !tr || k_steps < 0 || !tr->obs || !tr->actions || !tr->reward || !tr->done || !tr->mask)
-        return fail(h, EV2G_ERR_ARG, "ev2g_collect: null argument (every transition array is required)");
-    if (m->dev.d_in != h->D || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_collect: actor shape != (obs dim, ports)");
-    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, "ev2g_collect: the segment would run past the episode end");
+// The collectors' loop (ev2g_collect, ev2g_sac_collect): k_steps x (actor(observation row, action row, E rows) -> one-step launch) over the
+// caller's transition rows.  `fused`: the policy whose eligible segments run as ONE launch, or null.
+extern "C++" template <class Actor>
+static int collect_rows(ev2g_handle *h, const char *who_c, int k_steps, const ev2g_transitions *tr, const ev2g_mlp *fused, Actor actor) {
+    const std::string who(who_c);
+    if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, who + ": no scenarios loaded");
+    if (!tr || k_steps < 0 || !tr->obs || !tr->actions || !tr->reward || !tr->done || !tr->mask)
+        return fail(h, EV2G_ERR_ARG, who + ": null argument (every transition array is required)");
+    if (h->current_step + k_steps > h->T) return fail(h, EV2G_ERR_DONE, who + ": the segment would run past the episode end");
     (void)hipSetDevice(h->device);
     const size_t ED = (size_t)h->E * h->D, EP = (size_t)h->E * h->P;
     // On the fast path the policy hand-over instantiations take their float32 buffers per launch (StepIO::act32 / obs32): every step
@@ -1484,15 +1508,15 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
     const ev2g_step_extras &x = h->extras;
     const bool direct = collect_direct(h);
     if (!direct && !(x.obs_f32 && x.actions_f32 && x.obs_f32_step_stride == 0))
-        return fail(h, EV2G_ERR_ARG, "ev2g_collect: this configuration steps through the registered float32 hand-over buffers: register them with "
+        return fail(h, EV2G_ERR_ARG, who + ": this configuration steps through the registered float32 hand-over buffers: register them with "
                                      "ev2g_set_step_extras (observation step stride 0) first");
     const Rows<float> obs{tr->obs, (long long)ED}, act{tr->actions, (long long)EP};
     const Rows<double> reward{tr->reward, h->E};
     const Rows<uint8_t> done{tr->done, h->E}, mask{tr->mask, (long long)EP};
     if (int rc = timed_open(h)) return rc;
-    const FusedRoute fr = (direct && k_steps >= 1) ? fused_route(h, m) : FusedRoute{};
+    const FusedRoute fr = (fused && direct && k_steps >= 1) ? fused_route(h, fused) : FusedRoute{};
     if (fr.eligible) {   // ONE launch for the segment: rows read and written in place, the policy inside the launch
-        const int rc = launch_fused(h, m, fr, k_steps, tr->obs, {obs.at(1), obs.stride}, act, reward, done, mask);
+        const int rc = launch_fused(h, fused, fr, k_steps, tr->obs, {obs.at(1), obs.stride}, act, reward, done, mask);
         if (rc) return rc;
         h->current_step += k_steps;
         k_steps = 0;
@@ -1502,13 +1526,13 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
         StepIO io = make_io(h, StepRows{{}, {}, {reward.at(i)}, {done.at(i)}, {mask.at(i)}}, 0, 0);
         int rc;
         if (direct) {
-            if ((rc = ev2g_mlp_forward(h, m, obs_i, act_i, h->E))) return rc;
+            if ((rc = actor(obs_i, act_i, h->E))) return rc;
             io.act32 = act_i; io.obs32 = obs_n;
             if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
-            if (h->last.specialisation <= 0) return fail(h, EV2G_ERR_STATE, "ev2g_collect: internal: the direct path needs the full instantiation");
+            if (h->last.specialisation <= 0) return fail(h, EV2G_ERR_STATE, who + ": internal: the direct path needs the full instantiation");
         } else {
             if (i == 0) HIPCHK(h, hipMemcpyAsync(x.obs_f32, obs_i, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-            if ((rc = ev2g_mlp_forward(h, m, x.obs_f32, (float *)x.actions_f32, h->E))) return rc;
+            if ((rc = actor((const float *)x.obs_f32, (float *)x.actions_f32, h->E))) return rc;
             if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
             HIPCHK(h, hipMemcpyAsync(act_i, x.actions_f32, EP * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
             HIPCHK(h, hipMemcpyAsync(obs_n, x.obs_f32, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
@@ -1516,6 +1540,14 @@ int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_tran
         h->current_step += 1;
     }
     return timed_close(h);
+}
+
+int ev2g_collect(ev2g_handle *h, const ev2g_mlp *m, int k_steps, const ev2g_transitions *tr) {
+    if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_collect: no scenarios loaded");
+    if (!m || !tr || k_steps < 0 || !tr->obs || !tr->actions || !tr->reward || !tr->done || !tr->mask)   // (ahead of the actor's shape, as ever)
+        return fail(h, EV2G_ERR_ARG, "ev2g_collect: null argument (every transition array is required)");
+    if (m->dev.d_in != h->D || m->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, "ev2g_collect: actor shape != (obs dim, ports)");
+    return collect_rows(h, "ev2g_collect", k_steps, tr, m, [&](const float *obs, float *act, int n) { return ev2g_mlp_forward(h, m, obs, act, n); });
 }
 
 // ---- env-reading heuristic agents (ev2g_heuristic.h) ----
@@ -2703,30 +2735,35 @@ static void td3_forward(ev2g_handle *h, const Td3Net &n, const float *x, int B, 
     g.epi = out_epi;
     td3_gemm(h, g, nz);
 }
+// the weight gradient of nz layers: grad_w[z] [rows, cols] = delta[z]^T in[z] (k: the batch rows ascending) and grad_b[z] [rows] = the column sums of delta[z]
+static void td3_wgrad(ev2g_handle *h, int B, const float *delta, long long zd, int rows, const float *in, long long zin, int cols, float *grad_w, float *grad_b,
+                      long long zP, int nz) {
+    Td3Gemm g{};
+    g.M = rows; g.N = cols; g.K = B; g.A = delta; g.zA = zd; g.sam = 1; g.sak = rows; g.Bm = in; g.zB = zin; g.sbk = cols; g.sbn = 1;
+    g.C = grad_w; g.ldc = cols; g.zC = zP; g.epi = TD3_EPI_NONE;
+    td3_gemm(h, g, nz);
+    hipLaunchKernelGGL(ev2g_td3_colsum_kernel, dim3((unsigned)((rows + 15) / 16), (unsigned)nz), dim3(256), 0, h->stream, delta, zd, B, rows, grad_b, zP);
+}
+// backward data of nz layers: out[z] [B, cols] = delta[z] [B, k] W[z][:, 0 .. cols) (row stride ldw), masked by H[z] > 0 when H is given
+static void td3_bdata(ev2g_handle *h, int B, const float *delta, long long zd, int k, const float *W, long long zW, int ldw, int cols, const float *H, long long zH,
+                      float *out, long long zout, int nz) {
+    Td3Gemm g{};
+    g.M = B; g.N = cols; g.K = k; g.A = delta; g.zA = zd; g.sam = k; g.sak = 1; g.Bm = W; g.zB = zW; g.sbk = ldw; g.sbn = 1;
+    g.C = out; g.ldc = cols; g.zC = zout; g.H = H; g.ldh = cols; g.zH = zH; g.epi = H ? TD3_EPI_MASK : TD3_EPI_NONE;
+    td3_gemm(h, g, nz);
+}
 // backprop from dO [nz][B, n_out] (the delta at the output layer's pre-activation) through the networks td3_forward ran: the hidden deltas into
-// D2 / D1, the six gradients into grad + z zP (grad null: none), and -- dX not null, nz 1 -- the delta of input columns [x_col0, x_col0 + x_cols)
+// D2 / D1, the six gradients into grad + z zP (grad null: none), and -- dX not null -- the delta of input columns [x_col0, x_col0 + x_cols) into
+// dX [nz][B, x_cols]
 static void td3_backward(ev2g_handle *h, const Td3Net &n, const float *x, int B, const float *dO, float *D2, float *D1, float *grad, float *dX, int x_col0,
                          int x_cols, int nz) {
     const long long z1 = (long long)B * n.h1, z2 = (long long)B * n.h2, zo = (long long)B * n.n_out;
-    auto wgrad = [&](const float *delta, long long zd, int rows, const float *in, long long zin, int cols, int iw, int ib) {
-        Td3Gemm g{};
-        g.M = rows; g.N = cols; g.K = B; g.A = delta; g.zA = zd; g.sam = 1; g.sak = rows; g.Bm = in; g.zB = zin; g.sbk = cols; g.sbn = 1;
-        g.C = grad + n.off[iw]; g.ldc = cols; g.zC = n.zP; g.epi = TD3_EPI_NONE;
-        td3_gemm(h, g, nz);
-        hipLaunchKernelGGL(ev2g_td3_colsum_kernel, dim3((unsigned)((rows + 15) / 16), (unsigned)nz), dim3(256), 0, h->stream, delta, zd, B, rows, grad + n.off[ib], n.zP);
-    };
-    auto bdata = [&](const float *delta, long long zd, int k, const float *W, int ldw, int cols, const float *H, long long zH, float *out, long long zout) {
-        Td3Gemm g{};
-        g.M = B; g.N = cols; g.K = k; g.A = delta; g.zA = zd; g.sam = k; g.sak = 1; g.Bm = W; g.zB = n.zP; g.sbk = ldw; g.sbn = 1;
-        g.C = out; g.ldc = cols; g.zC = zout; g.H = H; g.ldh = cols; g.zH = zH; g.epi = H ? TD3_EPI_MASK : TD3_EPI_NONE;
-        td3_gemm(h, g, nz);
-    };
-    if (grad) wgrad(dO, zo, n.n_out, n.H2, z2, n.h2, 4, 5);
-    bdata(dO, zo, n.n_out, n.th + n.off[4], n.h2, n.h2, n.H2, z2, D2, z2);
-    if (grad) wgrad(D2, z2, n.h2, n.H1, z1, n.h1, 2, 3);
-    bdata(D2, z2, n.h2, n.th + n.off[2], n.h1, n.h1, n.H1, z1, D1, z1);
-    if (grad) wgrad(D1, z1, n.h1, x, 0, n.k0, 0, 1);
-    if (dX) bdata(D1, z1, n.h1, n.th + n.off[0] + x_col0, n.k0, x_cols, nullptr, 0, dX, 0);
+    if (grad) td3_wgrad(h, B, dO, zo, n.n_out, n.H2, z2, n.h2, grad + n.off[4], grad + n.off[5], n.zP, nz);
+    td3_bdata(h, B, dO, zo, n.n_out, n.th + n.off[4], n.zP, n.h2, n.h2, n.H2, z2, D2, z2, nz);
+    if (grad) td3_wgrad(h, B, D2, z2, n.h2, n.H1, z1, n.h1, grad + n.off[2], grad + n.off[3], n.zP, nz);
+    td3_bdata(h, B, D2, z2, n.h2, n.th + n.off[2], n.zP, n.h1, n.h1, n.H1, z1, D1, z1, nz);
+    if (grad) td3_wgrad(h, B, D1, z1, n.h1, x, 0, n.k0, grad + n.off[0], grad + n.off[1], n.zP, nz);
+    if (dX) td3_bdata(h, B, D1, z1, n.h1, n.th + n.off[0] + x_col0, n.zP, n.k0, x_cols, nullptr, 0, dX, (long long)B * x_cols, nz);
 }
 static Td3Net td3_actor_net(const ev2g_td3 *t, const float *params) {
     const Td3Plan &p = t->plan;
@@ -3001,6 +3038,346 @@ int ev2g_host_polyak(float *target, const float *param, int64_t n, double tau) {
     if (!target || !param || n < 0) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_polyak: null argument or n < 0");
     if (!(tau >= 0.0 && tau <= 1.0)) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_polyak: tau must be in [0, 1]");
     td3_host_polyak(target, param, (long long)n, tau);
+    return EV2G_OK;
+}
+
+// ---- the SAC learner and its collection actor (ev2g_sac.h) ----
+static int sac_check(ev2g_handle *h, ev2g_sac *s, const char *who) { return owned_check(h, &ev2g_handle::sacs, s, "SAC learner", who, false); }
+
+// ev2g_sac_act_kernel<SAMPLE>: the kernel (ev2g_sac_create sets its dynamic-LDS attribute) and its launch
+struct SacActEntry {
+    const void *fn;
+    void (*launch)(const LaunchDims &, const SacDev &, const float *x, int n_rows, uint64_t seed, uint64_t draw0, float *act, float *mu, float *ls, float *logp);
+};
+extern "C++" template <bool SAMPLE>
+static void launch_sac_act(const LaunchDims &d, const SacDev &dev, const float *x, int n_rows, uint64_t seed, uint64_t draw0, float *act, float *mu, float *ls,
+                           float *logp) {
+    hipLaunchKernelGGL(ev2g_sac_act_kernel<SAMPLE>, d.grid, dim3(EV2G_AC_BLOCK), d.lds, d.stream, dev, x, n_rows, seed, draw0, act, mu, ls, logp);
+}
+static const SacActEntry &sac_act_kernel(bool sample) {
+    static const SacActEntry tab[2] = {{(const void *)ev2g_sac_act_kernel<false>, &launch_sac_act<false>}, {(const void *)ev2g_sac_act_kernel<true>, &launch_sac_act<true>}};
+    return tab[sample ? 1 : 0];
+}
+
+// the actor's trunk and mu head as a Td3Net (the log_std head is the z = 1 block behind mu's: SacPlan::head_block), and the critics
+static Td3Net sac_actor_net(const ev2g_sac *s) {
+    const SacPlan &p = s->plan;
+    return {s->theta, 0, p.aoff, p.d_in, p.h1, p.h2, p.d_out, s->work + p.w_ah1, s->work + p.w_ah2, s->work + p.w_head};
+}
+static Td3Net sac_critic_net(const ev2g_sac *s, const float *critic_params, float *out) {
+    const SacPlan &p = s->plan;
+    return {critic_params, p.n_critic, p.coff, p.da, p.h1, p.h2, 1, s->work + p.w_ch1, s->work + p.w_ch2, out};
+}
+
+// the actor on x [B, d_in] with the draws draw0 + b P + p: the trunk, both heads (the z dimension of one launch), then the squashed-Gaussian
+// head: mu | raw log_std, eps and a into the workspace, a into the action columns of xcols [B, da], log pi into logp
+static void sac_actor_forward(ev2g_handle *h, ev2g_sac *s, const float *x, int B, uint64_t draw0, float *xcols, float *logp) {
+    const SacPlan &p = s->plan;
+    float *W = s->work;
+    const Td3Net an = sac_actor_net(s);
+    const long long z1 = (long long)B * p.h1, z2 = (long long)B * p.h2;
+    Td3Gemm g{};
+    g.M = B; g.sak = 1; g.sbk = 1;
+    g.A = x; g.sam = p.d_in; g.K = p.d_in; g.N = p.h1; g.Bm = an.th + p.aoff[0]; g.sbn = p.d_in; g.bias = an.th + p.aoff[1]; g.C = an.H1; g.ldc = p.h1; g.zC = z1;
+    g.epi = TD3_EPI_BIAS_RELU;
+    td3_gemm(h, g, 1);
+    g.A = an.H1; g.sam = p.h1; g.K = p.h1; g.N = p.h2; g.Bm = an.th + p.aoff[2]; g.sbn = p.h1; g.bias = an.th + p.aoff[3]; g.C = an.H2; g.ldc = p.h2; g.zC = z2;
+    td3_gemm(h, g, 1);
+    g.A = an.H2; g.zA = 0; g.sam = p.h2; g.K = p.h2; g.N = p.d_out; g.Bm = an.th + p.aoff[4]; g.zB = p.head_block; g.sbn = p.h2; g.bias = an.th + p.aoff[5];
+    g.zbias = p.head_block; g.C = W + p.w_head; g.ldc = p.d_out; g.zC = (long long)B * p.d_out; g.epi = TD3_EPI_BIAS;
+    td3_gemm(h, g, 2);
+    hipLaunchKernelGGL(ev2g_sac_head_kernel, dim3((unsigned)((B + 31) / 32)), dim3(256), 0, h->stream, (const float *)(W + p.w_head),
+                       (const float *)(W + p.w_head + (long long)B * p.d_out), B, p.d_out, (uint64_t)s->seed, draw0, W + p.w_eps, W + p.w_a, xcols, p.da, p.d_in, logp);
+}
+
+static int sac_launch_repack(ev2g_handle *h, ev2g_sac *s) {
+    SacRepack r{};
+    for (int i = 0; i <= EV2G_SAC_ACTOR_ARRAYS; i++) r.off[i] = s->plan.aoff[i];
+    hipLaunchKernelGGL(ev2g_sac_repack_kernel, dim3(td3_blocks((long long)s->plan.h1 * std::max(s->plan.d_in, s->plan.h2))), dim3(256), 0, h->stream, s->dev, r,
+                       (const float *)s->theta);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_sac_default_config(ev2g_sac_config *cfg) {
+    if (!cfg) return fail(nullptr, EV2G_ERR_ARG, "ev2g_sac_default_config: cfg is null");
+    sac_default_config(cfg);
+    return EV2G_OK;
+}
+
+static int sac_device_stage(ev2g_handle *h, ev2g_sac *s, const float *const *actor, const float *const *critics) {
+    const SacPlan &p = s->plan;
+    const size_t G = (size_t)p.n_params, GC = (size_t)p.nc * p.n_critic;
+    float **bufs[] = {&s->theta, &s->m, &s->v, &s->grad};
+    for (float **b : bufs)
+        if (int rc = dalloc(h, s->allocs, G, b)) return rc;
+    if (int rc = dalloc(h, s->allocs, GC, &s->target)) return rc;
+    if (int rc = dalloc(h, s->allocs, (size_t)p.w_floats, &s->work)) return rc;
+    if (int rc = dalloc(h, s->allocs, 4, &s->loss)) return rc;
+    if (int rc = dalloc(h, s->allocs, 3, &s->alpha)) return rc;
+    if (int rc = dalloc(h, s->allocs, 1, &s->g_alpha)) return rc;
+    size_t img[6];
+    sac_image_sizes(p, img);
+    float **imgs[6] = {&s->dev.w1, &s->dev.b1, &s->dev.w2, &s->dev.b2, &s->dev.wh, &s->dev.bh};
+    for (int i = 0; i < 6; i++)
+        if (int rc = dalloc(h, s->allocs, img[i], imgs[i])) return rc;   // (zeros: the padding the repack never writes)
+    std::vector<float> host(G);
+    for (int i = 0; i < EV2G_SAC_ACTOR_ARRAYS; i++) std::copy(actor[i], actor[i] + (p.aoff[i + 1] - p.aoff[i]), host.begin() + p.aoff[i]);
+    for (int j = 0; j < p.nc; j++)
+        for (int i = 0; i < 6; i++) std::copy(critics[6 * j + i], critics[6 * j + i] + (p.coff[i + 1] - p.coff[i]), host.begin() + p.n_actor + (size_t)j * p.n_critic + p.coff[i]);
+    const float la = (float)std::log(s->cfg.ent_coef);
+    HIPCHK(h, hipMemcpyAsync(s->theta, host.data(), G * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->target, s->theta + p.n_actor, GC * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->alpha, &la, sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (int rc = sac_launch_repack(h, s)) return rc;
+    for (unsigned k = 0; k < 2; k++)
+        if (s->lds > 48 * 1024 && !(h->sac_attr_mask & (1u << k))) {   // (function attributes are per device: once per handle, for the largest network)
+            const hipError_t e = hipFuncSetAttribute(sac_act_kernel(k != 0).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev2g_sac_lds_max());
+            if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string("ev2g_sac_create: hipFuncSetAttribute: ") + hipGetErrorString(e));
+            h->sac_attr_mask |= 1u << k;
+        }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+int ev2g_sac_create(ev2g_handle *h, const ev2g_sac_config *cfg, int d_in, int h1, int h2, int d_out, float lo, const float *const *actor,
+                    const float *const *critics, uint64_t seed, ev2g_sac **out) {
+    const char *who = "ev2g_sac_create";
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    *out = nullptr;
+    if (!cfg || !actor || !critics) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (int rc = fields_check(h, who, sac_fields(*cfg))) return rc;
+    const SacPlan plan = plan_sac(d_in, h1, h2, d_out, cfg->n_critics);
+    if (plan.err) return fail(h, plan.err, plan.refusal);
+    if (lo != -1.0f && lo != 0.0f) return fail(h, EV2G_ERR_ARG, std::string(who) + ": lo must be -1 or 0");
+    for (int i = 0; i < EV2G_SAC_ACTOR_ARRAYS + 6 * cfg->n_critics; i++)
+        if (!(i < EV2G_SAC_ACTOR_ARRAYS ? actor[i] : critics[i - EV2G_SAC_ACTOR_ARRAYS])) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null weight array");
+    (void)hipSetDevice(h->device);
+    ev2g_sac *s = new ev2g_sac();
+    s->cfg = *cfg; s->plan = plan; s->lo = lo; s->seed = seed; s->act_seed = seed;
+    s->target_entropy = sac_target_entropy(*cfg, d_out);
+    s->dev = sac_dev(plan, lo);
+    s->lds = ev2g_sac_lds(s->dev).bytes;
+    const int rc = owned_created(h, &ev2g_handle::sacs, s, sac_device_stage(h, s, actor, critics), out);
+    return rc;
+}
+
+void ev2g_sac_destroy(ev2g_handle *h, ev2g_sac *s) { owned_destroy(h, &ev2g_handle::sacs, s); }
+
+static int sac_critic_stage(ev2g_handle *h, ev2g_sac *s, const char *who, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                            const uint8_t *done, int B, float *losses) {
+    if (int rc = sac_check(h, s, who)) return rc;
+    if (!obs || !actions || !reward || !next_obs || !done) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const SacPlan &p = s->plan;
+    float *W = s->work, *L = losses ? losses : s->loss;
+    const unsigned nb = td3_blocks((long long)B * p.da);
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(nb), dim3(256), 0, h->stream, obs, actions, B, p.d_in, p.d_out, s->lo, W + p.w_xa);
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(nb), dim3(256), 0, h->stream, next_obs, (const float *)nullptr, B, p.d_in, p.d_out, s->lo, W + p.w_xb);
+    sac_actor_forward(h, s, next_obs, B, (uint64_t)s->next_draw + (uint64_t)B * (uint64_t)p.d_out, W + p.w_xb, W + p.w_lp2);
+    td3_forward(h, sac_critic_net(s, s->target, W + p.w_tq), W + p.w_xb, B, TD3_EPI_BIAS, p.nc);
+    const Td3Net cn = sac_critic_net(s, s->theta + p.n_actor, W + p.w_q);
+    td3_forward(h, cn, W + p.w_xa, B, TD3_EPI_BIAS, p.nc);
+    hipLaunchKernelGGL(ev2g_sac_critic_head_kernel, dim3(1), dim3(256), 0, h->stream, (const float *)(W + p.w_tq), (const float *)(W + p.w_q),
+                       (const float *)(W + p.w_lp2), reward, done, B, p.nc, s->cfg.gamma, (const float *)s->alpha, W + p.w_y, W + p.w_dq, L);
+    td3_backward(h, cn, W + p.w_xa, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, s->grad + p.n_actor, nullptr, 0, 0, p.nc);
+    HIPCHK(h, hipGetLastError());
+    s->pending |= 1; s->last_B = B;
+    return EV2G_OK;
+}
+
+static int sac_actor_stage(ev2g_handle *h, ev2g_sac *s, const char *who, const float *obs, int B, float *losses) {
+    if (int rc = sac_check(h, s, who)) return rc;
+    if (!obs) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const SacPlan &p = s->plan;
+    float *W = s->work, *L = losses ? losses : s->loss;
+    const long long BP = (long long)B * p.d_out, z2 = (long long)B * p.h2;
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(td3_blocks((long long)B * p.da)), dim3(256), 0, h->stream, obs, (const float *)nullptr, B, p.d_in, p.d_out, s->lo,
+                       W + p.w_xb);
+    sac_actor_forward(h, s, obs, B, (uint64_t)s->next_draw, W + p.w_xb, W + p.w_lp);
+    const Td3Net cn = sac_critic_net(s, s->theta + p.n_actor, W + p.w_q);
+    td3_forward(h, cn, W + p.w_xb, B, TD3_EPI_BIAS, p.nc);
+    hipLaunchKernelGGL(ev2g_sac_actor_head_kernel, dim3(1), dim3(256), 0, h->stream, (const float *)(W + p.w_q), (const float *)(W + p.w_lp), B, p.nc,
+                       (const float *)s->alpha, s->target_entropy, s->cfg.ent_coef_auto ? 1 : 0, W + p.w_dq, L, s->g_alpha);
+    // dQ_j / da of both critics from the selector as output delta: the critic that is not a row's argmin propagates exact zeros
+    td3_backward(h, cn, W + p.w_xb, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, nullptr, W + p.w_dxa, p.d_in, p.d_out, p.nc);
+    hipLaunchKernelGGL(ev2g_sac_head_back_kernel, dim3(td3_blocks(BP)), dim3(256), 0, h->stream, (const float *)(W + p.w_head), (const float *)(W + p.w_head + BP),
+                       (const float *)(W + p.w_eps), (const float *)(W + p.w_dxa), p.nc, B, p.d_out, (const float *)s->alpha, W + p.w_dhead);
+    // the heads (z = 0: mu, 1: log_std): their gradients, their backward-data products joined under the second hidden layer's ReLU, then the trunk
+    const Td3Net an = sac_actor_net(s);
+    td3_wgrad(h, B, W + p.w_dhead, BP, p.d_out, an.H2, 0, p.h2, s->grad + p.aoff[4], s->grad + p.aoff[5], p.head_block, 2);
+    td3_bdata(h, B, W + p.w_dhead, BP, p.d_out, s->theta + p.aoff[4], p.head_block, p.h2, p.h2, nullptr, 0, W + p.w_e2z, z2, 2);
+    hipLaunchKernelGGL(ev2g_sac_join_kernel, dim3(td3_blocks(z2)), dim3(256), 0, h->stream, (const float *)(W + p.w_e2z), (const float *)(W + p.w_e2z + z2),
+                       (const float *)an.H2, z2, W + p.w_e2);
+    td3_wgrad(h, B, W + p.w_e2, z2, p.h2, an.H1, 0, p.h1, s->grad + p.aoff[2], s->grad + p.aoff[3], 0, 1);
+    td3_bdata(h, B, W + p.w_e2, z2, p.h2, s->theta + p.aoff[2], 0, p.h1, p.h1, an.H1, 0, W + p.w_e1, 0, 1);
+    td3_wgrad(h, B, W + p.w_e1, 0, p.h1, obs, 0, p.d_in, s->grad + p.aoff[0], s->grad + p.aoff[1], 0, 1);
+    HIPCHK(h, hipGetLastError());
+    s->pending |= 2; s->last_actor_B = B;
+    return EV2G_OK;
+}
+
+static int sac_apply_stage(ev2g_handle *h, ev2g_sac *s, const char *who) {
+    if (int rc = sac_check(h, s, who)) return rc;
+    if (!s->pending) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_sac_critic_grad or ev2g_sac_actor_grad first)");
+    const SacPlan &p = s->plan;
+    const ev2g_sac_config &c = s->cfg;
+    if (s->pending & 1) {
+        const long long n = (long long)p.nc * p.n_critic;
+        s->t_critic += 1;
+        hipLaunchKernelGGL(ev2g_td3_adam_kernel, dim3(td3_blocks(n)), dim3(256), 0, h->stream, s->theta + p.n_actor, s->m + p.n_actor, s->v + p.n_actor,
+                           (const float *)(s->grad + p.n_actor), n, adam_step(c.lr, c.beta1, c.beta2, c.adam_eps, s->t_critic));
+    }
+    if (s->pending & 2) {
+        s->t_actor += 1; s->n += 1;
+        const AdamStep a = adam_step(c.lr, c.beta1, c.beta2, c.adam_eps, s->t_actor);
+        hipLaunchKernelGGL(ev2g_td3_adam_kernel, dim3(td3_blocks(p.n_actor)), dim3(256), 0, h->stream, s->theta, s->m, s->v, (const float *)s->grad, (long long)p.n_actor, a);
+        if (c.ent_coef_auto) hipLaunchKernelGGL(ev2g_sac_alpha_adam_kernel, dim3(1), dim3(64), 0, h->stream, s->alpha, (const float *)s->g_alpha, a);
+        if (s->n % c.target_update_interval == 0) {
+            const long long n = (long long)p.nc * p.n_critic;
+            s->n_target += 1;
+            hipLaunchKernelGGL(ev2g_td3_polyak_kernel, dim3(td3_blocks(n)), dim3(256), 0, h->stream, s->target, (const float *)(s->theta + p.n_actor), n,
+                               (float)(1.0 - c.tau), (float)c.tau);
+        }
+        s->next_draw += 2ull * (unsigned long long)s->last_actor_B * (unsigned long long)p.d_out;
+        if (int rc = sac_launch_repack(h, s)) return rc;
+    }
+    HIPCHK(h, hipGetLastError());
+    s->pending = 0;
+    return EV2G_OK;
+}
+
+int ev2g_sac_critic_grad(ev2g_handle *h, ev2g_sac *s, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                         const uint8_t *done, int B, float *losses) {
+    return sac_critic_stage(h, s, "ev2g_sac_critic_grad", obs, actions, reward, next_obs, done, B, losses);
+}
+int ev2g_sac_actor_grad(ev2g_handle *h, ev2g_sac *s, const float *obs, int B, float *losses) { return sac_actor_stage(h, s, "ev2g_sac_actor_grad", obs, B, losses); }
+int ev2g_sac_apply(ev2g_handle *h, ev2g_sac *s) { return sac_apply_stage(h, s, "ev2g_sac_apply"); }
+
+int ev2g_sac_update(ev2g_handle *h, ev2g_sac *s, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                    const uint8_t *done, int B, float *losses) {
+    const char *who = "ev2g_sac_update";
+    if (int rc = sac_critic_stage(h, s, who, obs, actions, reward, next_obs, done, B, losses)) return rc;
+    if (int rc = sac_apply_stage(h, s, who)) return rc;
+    if (int rc = sac_actor_stage(h, s, who, obs, B, losses)) return rc;
+    return sac_apply_stage(h, s, who);
+}
+
+// one launch of ev2g_sac_act_kernel over n_rows rows; a sampling launch takes the collection stream's counter and advances it
+static int sac_act_launch(ev2g_handle *h, ev2g_sac *s, const float *x, int n_rows, bool sample, float *act, float *mu, float *ls, float *logp) {
+    const LaunchDims dims{dim3((unsigned)((n_rows + EV2G_AC_ROWS - 1) / EV2G_AC_ROWS)), s->lds, h->stream};
+    sac_act_kernel(sample).launch(dims, s->dev, x, n_rows, (uint64_t)s->act_seed, (uint64_t)s->act_n * (uint64_t)n_rows, act, mu, ls, logp);
+    HIPCHK(h, hipGetLastError());
+    if (sample) s->act_n += 1;
+    return EV2G_OK;
+}
+
+int ev2g_sac_act(ev2g_handle *h, ev2g_sac *s, const float *obs32, int n_rows, int deterministic, float *actions, float *mu, float *log_std, float *log_pi) {
+    if (int rc = sac_check(h, s, "ev2g_sac_act")) return rc;
+    if (!obs32 || !actions || n_rows <= 0) return fail(h, EV2G_ERR_ARG, "ev2g_sac_act: obs32 or actions is null, or n_rows is not positive");
+    return sac_act_launch(h, s, obs32, n_rows, !deterministic, actions, mu, log_std, log_pi);
+}
+
+int ev2g_sac_collect(ev2g_handle *h, ev2g_sac *s, int k_steps, int deterministic, const ev2g_transitions *tr) {
+    const char *who = "ev2g_sac_collect";
+    if (int rc = sac_check(h, s, who)) return rc;
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (s->plan.d_in != h->D || s->plan.d_out != h->P) return fail(h, EV2G_ERR_ARG, std::string(who) + ": actor shape != (obs dim, ports)");
+    return collect_rows(h, who, k_steps, tr, nullptr,
+                        [&](const float *obs, float *act, int n) { return sac_act_launch(h, s, obs, n, !deterministic, act, nullptr, nullptr, nullptr); });
+}
+
+// a flat buffer in the plan's layout into 8 + 6 n_critics host arrays (null entries skipped); actor_src null: the actor's entries are not written
+static int sac_read_flat(ev2g_handle *h, const SacPlan &p, const float *actor_src, const float *critic_src, float *const *out) {
+    for (int i = 0; i < EV2G_SAC_ACTOR_ARRAYS; i++)
+        if (actor_src && out[i]) HIPCHK(h, hipMemcpyAsync(out[i], actor_src + p.aoff[i], (size_t)(p.aoff[i + 1] - p.aoff[i]) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    for (int j = 0; j < p.nc; j++)
+        for (int i = 0; i < 6; i++)
+            if (float *dst = out[EV2G_SAC_ACTOR_ARRAYS + 6 * j + i])
+                HIPCHK(h, hipMemcpyAsync(dst, critic_src + (size_t)j * p.n_critic + p.coff[i], (size_t)(p.coff[i + 1] - p.coff[i]) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+int ev2g_sac_get_grads(ev2g_handle *h, ev2g_sac *s, float *const *out, float *g_log_ent_coef) {
+    if (int rc = sac_check(h, s, "ev2g_sac_get_grads")) return rc;
+    if (!out) return fail(h, EV2G_ERR_ARG, "ev2g_sac_get_grads: null argument");
+    if (g_log_ent_coef) HIPCHK(h, hipMemcpyAsync(g_log_ent_coef, s->g_alpha, sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    return sac_read_flat(h, s->plan, s->grad, s->grad + s->plan.n_actor, out);
+}
+int ev2g_sac_get_weights(ev2g_handle *h, ev2g_sac *s, int target, float *const *out) {
+    if (int rc = sac_check(h, s, "ev2g_sac_get_weights")) return rc;
+    if (!out) return fail(h, EV2G_ERR_ARG, "ev2g_sac_get_weights: null argument");
+    return target ? sac_read_flat(h, s->plan, nullptr, s->target, out) : sac_read_flat(h, s->plan, s->theta, s->theta + s->plan.n_actor, out);
+}
+static int sac_read_rows(ev2g_handle *h, const char *who, float *dst, const float *src, float *dst2, const float *src2, int B, int want_B) {
+    if (!dst) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (B < 1 || B != want_B) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B is not the batch size of the last gradient of that half");
+    HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (dst2) HIPCHK(h, hipMemcpyAsync(dst2, src2, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+int ev2g_sac_get_y(ev2g_handle *h, ev2g_sac *s, float *y, float *log_pi_next, int B) {
+    if (int rc = sac_check(h, s, "ev2g_sac_get_y")) return rc;
+    return sac_read_rows(h, "ev2g_sac_get_y", y, s->work + s->plan.w_y, log_pi_next, s->work + s->plan.w_lp2, B, s->last_B);
+}
+int ev2g_sac_get_log_pi(ev2g_handle *h, ev2g_sac *s, float *log_pi, int B) {
+    if (int rc = sac_check(h, s, "ev2g_sac_get_log_pi")) return rc;
+    return sac_read_rows(h, "ev2g_sac_get_log_pi", log_pi, s->work + s->plan.w_lp, nullptr, nullptr, B, s->last_actor_B);
+}
+int ev2g_sac_get_ent_coef(ev2g_handle *h, ev2g_sac *s, float *out3) {
+    if (int rc = sac_check(h, s, "ev2g_sac_get_ent_coef")) return rc;
+    if (!out3) return fail(h, EV2G_ERR_ARG, "ev2g_sac_get_ent_coef: null argument");
+    HIPCHK(h, hipMemcpyAsync(out3, s->alpha, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+int ev2g_sac_set_rate(ev2g_handle *h, ev2g_sac *s, double lr) {
+    if (int rc = sac_check(h, s, "ev2g_sac_set_rate")) return rc;
+    if (int rc = fields_check(h, "ev2g_sac_set_rate", sac_rate_fields(lr))) return rc;
+    s->cfg.lr = lr;
+    return EV2G_OK;
+}
+int ev2g_sac_seed(ev2g_handle *h, ev2g_sac *s, uint64_t seed, uint64_t first_draw) {
+    if (int rc = sac_check(h, s, "ev2g_sac_seed")) return rc;
+    s->seed = seed; s->next_draw = first_draw;
+    return EV2G_OK;
+}
+int ev2g_sac_act_seed(ev2g_handle *h, ev2g_sac *s, uint64_t seed, uint64_t first_launch) {
+    if (int rc = sac_check(h, s, "ev2g_sac_act_seed")) return rc;
+    s->act_seed = seed; s->act_n = first_launch;
+    return EV2G_OK;
+}
+int ev2g_sac_counters(ev2g_handle *h, ev2g_sac *s, int64_t *updates, int64_t *target_updates, uint64_t *next_draw, uint64_t *act_launches) {
+    if (int rc = sac_check(h, s, "ev2g_sac_counters")) return rc;
+    if (updates) *updates = s->n;
+    if (target_updates) *target_updates = s->n_target;
+    if (next_draw) *next_draw = s->next_draw;
+    if (act_launches) *act_launches = s->act_n;
+    return EV2G_OK;
+}
+
+int ev2g_host_sac_head(const float *mu, const float *log_std, const float *eps, int B, int P, float lo, float *a, float *a_env, float *log_pi) {
+    if (!mu || !log_std || !eps || !a || !log_pi) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_head: null argument");
+    if (B < 1 || P < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_head: B and P must be positive");
+    sac_host_head(mu, log_std, eps, B, P, lo, a, a_env, log_pi);
+    return EV2G_OK;
+}
+int ev2g_host_sac_head_back(const float *mu, const float *log_std, const float *eps, const float *g, int B, int P, float log_ent_coef, float *d_mu,
+                            float *d_log_std) {
+    if (!mu || !log_std || !eps || !g || !d_mu || !d_log_std) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_head_back: null argument");
+    if (B < 1 || P < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_head_back: B and P must be positive");
+    sac_host_head_back(mu, log_std, eps, g, B, P, log_ent_coef, d_mu, d_log_std);
+    return EV2G_OK;
+}
+int ev2g_host_sac_y(const float *tq, const float *log_pi_next, const float *reward, const uint8_t *done, int B, int n_critics, double gamma,
+                    float log_ent_coef, float *y) {
+    if (!tq || !log_pi_next || !reward || !done || !y) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_y: null argument");
+    if (B < 1 || n_critics < 1 || n_critics > 2) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_y: B must be positive, n_critics 1 or 2");
+    sac_host_y(tq, log_pi_next, reward, done, B, n_critics, gamma, log_ent_coef, y);
     return EV2G_OK;
 }
 

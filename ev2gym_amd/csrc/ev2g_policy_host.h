@@ -236,6 +236,9 @@ inline void unpack_linear_f32(const float *img, int n_out, int n_in, int K, floa
 constexpr size_t packed_f32_index(int n, int k, int K) {
     return (((size_t)(n >> 5) * (size_t)(K / 8) + (size_t)(k >> 3)) * 64 + (size_t)((n & 31) + 32 * ((k & 7) >> 2))) * 4 + (size_t)(k & 3);
 }
+// ... and of element (p, k) of head `head` (0: mu, 1: log_std) in the SAC actor's stacked-head image: pack_linear_f32 of the [2 n3, n_in] matrix
+// whose rows head * n3 + p are the head's, so that each head starts on a 32-column tile (ev2g_sac.h; n3: the ports padded to 32)
+constexpr size_t sac_head_index(int head, int p, int k, int n3, int K) { return packed_f32_index(head * n3 + p, k, K); }
 
 inline std::vector<float> pad_bias(const float *b, int n, int N) {
     std::vector<float> v((size_t)N, 0.f);

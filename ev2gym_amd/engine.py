@@ -148,6 +148,27 @@ def load_library(path: Optional[str] = None):
         "ev2g_host_replay_indices": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64]),
         "ev2g_host_td3_target": (C.c_int, [vp] * 4 + [C.c_int] * 3 + [dbl] * 3 + [C.c_uint64, C.c_uint64, vp, vp]),
         "ev2g_host_polyak": (C.c_int, [vp, vp, i64, dbl]),
+        "ev2g_sac_default_config": (C.c_int, [C.POINTER(_abi.SacConfigC)]),
+        "ev2g_sac_create": (C.c_int, [vp, C.POINTER(_abi.SacConfigC)] + [C.c_int] * 4 + [C.c_float, vp, vp, C.c_uint64, C.POINTER(vp)]),
+        "ev2g_sac_destroy": (None, [vp, vp]),
+        "ev2g_sac_update": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_sac_critic_grad": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_sac_actor_grad": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+        "ev2g_sac_apply": (C.c_int, [vp, vp]),
+        "ev2g_sac_act": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "ev2g_sac_collect": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+        "ev2g_sac_get_grads": (C.c_int, [vp, vp, vp, vp]),
+        "ev2g_sac_get_weights": (C.c_int, [vp, vp, C.c_int, vp]),
+        "ev2g_sac_get_y": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "ev2g_sac_get_log_pi": (C.c_int, [vp, vp, vp, C.c_int]),
+        "ev2g_sac_get_ent_coef": (C.c_int, [vp, vp, vp]),
+        "ev2g_sac_set_rate": (C.c_int, [vp, vp, dbl]),
+        "ev2g_sac_seed": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ev2g_sac_act_seed": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ev2g_sac_counters": (C.c_int, [vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "ev2g_host_sac_head": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
+        "ev2g_host_sac_head_back": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),
+        "ev2g_host_sac_y": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, dbl, C.c_float, vp]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -215,7 +236,10 @@ EXPORTED_SYMBOLS = [
     "ev2g_a2c_create", "ev2g_a2c_set_rate", "ev2g_a2c_grad", "ev2g_a2c_apply", "ev2g_a2c_update", "ev2g_host_rmsprop", "ev2g_host_a2c_head",
     "ev2g_td3_default_config", "ev2g_td3_create", "ev2g_td3_destroy", "ev2g_td3_update", "ev2g_td3_critic_grad", "ev2g_td3_actor_grad", "ev2g_td3_apply",
     "ev2g_td3_get_grads", "ev2g_td3_get_weights", "ev2g_td3_get_y", "ev2g_td3_set_rate", "ev2g_td3_seed", "ev2g_td3_counters", "ev2g_replay_sample",
-    "ev2g_host_replay_indices", "ev2g_host_td3_target", "ev2g_host_polyak"]
+    "ev2g_host_replay_indices", "ev2g_host_td3_target", "ev2g_host_polyak",
+    "ev2g_sac_default_config", "ev2g_sac_create", "ev2g_sac_destroy", "ev2g_sac_update", "ev2g_sac_critic_grad", "ev2g_sac_actor_grad", "ev2g_sac_apply",
+    "ev2g_sac_act", "ev2g_sac_collect", "ev2g_sac_get_grads", "ev2g_sac_get_weights", "ev2g_sac_get_y", "ev2g_sac_get_log_pi", "ev2g_sac_get_ent_coef",
+    "ev2g_sac_set_rate", "ev2g_sac_seed", "ev2g_sac_act_seed", "ev2g_sac_counters", "ev2g_host_sac_head", "ev2g_host_sac_head_back", "ev2g_host_sac_y"]
 
 
 def _ptr(x):
@@ -867,6 +891,100 @@ class Engine:
         self._check(self._lib.ev2g_replay_sample(self._h, C.byref(ring), int(B), int(seed) & (2 ** 64 - 1), int(counter), _ptr(obs), _ptr(actions),
                                                  _ptr(reward), _ptr(next_obs), _ptr(done), _ptr(index)))
 
+    # ---- the SAC learner and its collection actor (include/ev2g.h: ev2g_sac_*) ----------------------------------------------------------------
+    def sac_create(self, actor, critics, lo, seed=0, **config):
+        """A SAC learner with its stochastic collection actor (ev2g_sac_create): actor eight host arrays, critics a list of six-array lists;
+        config overrides fields of SB3's defaults (ev2g_sac_config).  Freed by sac_destroy or with the engine."""
+        cfg = sac_default_config()
+        ints = ("n_critics", "target_update_interval", "ent_coef_auto", "target_entropy_auto")
+        for k, v in config.items():
+            if k not in dict(_abi.SacConfigC._fields_):
+                raise TypeError(f"sac_create: unknown config field {k}")
+            setattr(cfg, k, int(v) if k in ints else float(v))
+        actor = [np.ascontiguousarray(a, np.float32) for a in actor]
+        flat = [np.ascontiguousarray(a, np.float32) for c in critics for a in c]
+        if len(actor) != 8 or len(flat) != 6 * cfg.n_critics:
+            raise ValueError(f"sac_create: eight actor arrays and six per critic for {cfg.n_critics} critics are needed")
+        (h1, d_in), h2, d_out = actor[0].shape, actor[2].shape[0], actor[4].shape[0]
+        for a, shape in zip(actor + flat, _abi.sac_param_shapes(d_in, h1, h2, d_out, cfg.n_critics)):
+            if a.shape != shape:
+                raise ValueError(f"sac_create: a weight array has shape {a.shape}, expected {shape}")
+        pa, pc = (C.c_void_p * 8)(*[a.ctypes.data for a in actor]), (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
+        out = C.c_void_p()
+        self._check(self._lib.ev2g_sac_create(self._h, C.byref(cfg), d_in, h1, h2, d_out, float(lo), pa, pc, int(seed) & (2 ** 64 - 1), C.byref(out)))
+        return out.value
+
+    def sac_destroy(self, s):
+        if s and self._h:
+            self._lib.ev2g_sac_destroy(self._h, s)
+
+    def sac_update(self, s, obs, actions, reward, next_obs, done, B, losses=None):
+        """One gradient step on contiguous DEVICE batch arrays (ev2g_sac_update); losses: float32 [4] DEVICE or None."""
+        self._check(self._lib.ev2g_sac_update(self._h, s, _ptr(obs), _ptr(actions), _ptr(reward), _ptr(next_obs), _ptr(done), int(B), _ptr(losses)))
+
+    def sac_critic_grad(self, s, obs, actions, reward, next_obs, done, B, losses=None):
+        self._check(self._lib.ev2g_sac_critic_grad(self._h, s, _ptr(obs), _ptr(actions), _ptr(reward), _ptr(next_obs), _ptr(done), int(B), _ptr(losses)))
+
+    def sac_actor_grad(self, s, obs, B, losses=None):
+        self._check(self._lib.ev2g_sac_actor_grad(self._h, s, _ptr(obs), int(B), _ptr(losses)))
+
+    def sac_apply(self, s):
+        self._check(self._lib.ev2g_sac_apply(self._h, s))
+
+    def sac_act(self, s, obs32, n_rows, actions, deterministic=False, mu=None, log_std=None, log_pi=None):
+        """The collection actor on n_rows DEVICE observation rows (ev2g_sac_act): env actions in [lo, 1]; mu, raw log_std, log pi optional."""
+        self._check(self._lib.ev2g_sac_act(self._h, s, _ptr(obs32), int(n_rows), int(bool(deterministic)), _ptr(actions), _ptr(mu), _ptr(log_std), _ptr(log_pi)))
+
+    def sac_collect(self, s, k, obs, actions, reward, done, mask, deterministic=False):
+        """k x (SAC actor -> env step) into the caller's DEVICE arrays (ev2g_sac_collect; the arrays of collect())."""
+        tr = (C.c_void_p * 5)(_ptr(obs), _ptr(actions), _ptr(reward), _ptr(done), _ptr(mask))
+        self._check(self._lib.ev2g_sac_collect(self._h, s, int(k), int(bool(deterministic)), C.cast(tr, C.c_void_p)))
+
+    def sac_get_grads(self, s, shape):
+        """(the last gradient of each half as 8 + 6 n_critics host float32 arrays, the gradient of log_ent_coef); shape: (d_in, h1, h2, d_out, n_critics)."""
+        out = [np.empty(sh, np.float32) for sh in _abi.sac_param_shapes(*shape)]
+        g = np.zeros(1, np.float32)
+        self._check(self._lib.ev2g_sac_get_grads(self._h, s, (C.c_void_p * len(out))(*[a.ctypes.data for a in out]), g.ctypes.data))
+        return out, float(g[0])
+
+    def sac_get_weights(self, s, shape, target=False):
+        """The masters as 8 + 6 n_critics host float32 arrays in SB3's parameter order, or (target) the target critics' 6 n_critics."""
+        out = [np.empty(sh, np.float32) for sh in _abi.sac_param_shapes(*shape)]
+        self._check(self._lib.ev2g_sac_get_weights(self._h, s, int(bool(target)), (C.c_void_p * len(out))(*[a.ctypes.data for a in out])))
+        return out[8:] if target else out
+
+    def sac_get_y(self, s, B):
+        """(y, log pi') of the last critic gradient."""
+        y, lp = np.empty(int(B), np.float32), np.empty(int(B), np.float32)
+        self._check(self._lib.ev2g_sac_get_y(self._h, s, y.ctypes.data, lp.ctypes.data, int(B)))
+        return y, lp
+
+    def sac_get_log_pi(self, s, B):
+        lp = np.empty(int(B), np.float32)
+        self._check(self._lib.ev2g_sac_get_log_pi(self._h, s, lp.ctypes.data, int(B)))
+        return lp
+
+    def sac_get_ent_coef(self, s):
+        """float32 [3]: log_ent_coef and its Adam moments m, v."""
+        out = np.empty(3, np.float32)
+        self._check(self._lib.ev2g_sac_get_ent_coef(self._h, s, out.ctypes.data))
+        return out
+
+    def sac_set_rate(self, s, lr):
+        self._check(self._lib.ev2g_sac_set_rate(self._h, s, float(lr)))
+
+    def sac_seed(self, s, seed, first_draw=0):
+        self._check(self._lib.ev2g_sac_seed(self._h, s, int(seed) & (2 ** 64 - 1), int(first_draw)))
+
+    def sac_act_seed(self, s, seed, first_launch=0):
+        self._check(self._lib.ev2g_sac_act_seed(self._h, s, int(seed) & (2 ** 64 - 1), int(first_launch)))
+
+    def sac_counters(self, s):
+        """(updates applied, Polyak steps among them, the learner's next draw base, the collection stream's launch counter)."""
+        n, t, d, a = C.c_int64(0), C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.ev2g_sac_counters(self._h, s, C.byref(n), C.byref(t), C.byref(d), C.byref(a)))
+        return int(n.value), int(t.value), int(d.value), int(a.value)
+
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
         if out is not None:
@@ -1121,3 +1239,40 @@ def host_polyak(target, param, tau):
     assert target.dtype == np.float32 and target.flags.c_contiguous
     param = np.ascontiguousarray(param, np.float32)
     _host_call(load_library().ev2g_host_polyak(target.ctypes.data, param.ctypes.data, target.size, float(tau)))
+
+
+def sac_default_config():
+    """SB3's defaults of SAC as an _abi.SacConfigC (ev2g_sac_default_config)."""
+    cfg = _abi.SacConfigC()
+    _host_call(load_library().ev2g_sac_default_config(C.byref(cfg)))
+    return cfg
+
+
+def host_sac_head(mu, log_std, eps, lo=-1.0):
+    """Host twin of the squashed-Gaussian head (ev2g_host_sac_head): (a [B, P] tanh, a_env [B, P] in [lo, 1], log pi [B]) float32."""
+    mu, log_std, eps = (np.ascontiguousarray(a, np.float32) for a in (mu, log_std, eps))
+    B, P = mu.shape
+    a, a_env, lp = np.empty((B, P), np.float32), np.empty((B, P), np.float32), np.empty(B, np.float32)
+    _host_call(load_library().ev2g_host_sac_head(mu.ctypes.data, log_std.ctypes.data, eps.ctypes.data, B, P, float(lo), a.ctypes.data, a_env.ctypes.data,
+                                                 lp.ctypes.data))
+    return a, a_env, lp
+
+
+def host_sac_head_back(mu, log_std, eps, g, log_ent_coef):
+    """Host twin of the head's backward (ev2g_host_sac_head_back): (d_mu, d_log_std) [B, P] float32 from g = dQ_min / da."""
+    mu, log_std, eps, g = (np.ascontiguousarray(a, np.float32) for a in (mu, log_std, eps, g))
+    B, P = mu.shape
+    dm, dl = np.empty((B, P), np.float32), np.empty((B, P), np.float32)
+    _host_call(load_library().ev2g_host_sac_head_back(mu.ctypes.data, log_std.ctypes.data, eps.ctypes.data, g.ctypes.data, B, P, float(log_ent_coef),
+                                                      dm.ctypes.data, dl.ctypes.data))
+    return dm, dl
+
+
+def host_sac_y(tq, log_pi_next, reward, done, gamma, log_ent_coef):
+    """Host twin of the target (ev2g_host_sac_y): y [B] float32 from the target critics' values tq [n_critics, B] and log pi' [B]."""
+    tq, lp, reward = (np.ascontiguousarray(a, np.float32) for a in (tq, log_pi_next, reward))
+    done = np.ascontiguousarray(done, np.uint8)
+    y = np.empty(tq.shape[1], np.float32)
+    _host_call(load_library().ev2g_host_sac_y(tq.ctypes.data, lp.ctypes.data, reward.ctypes.data, done.ctypes.data, tq.shape[1], tq.shape[0], float(gamma),
+                                              float(log_ent_coef), y.ctypes.data))
+    return y

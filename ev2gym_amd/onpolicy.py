@@ -11,7 +11,7 @@ value trunk with a linear value head, one activation, a state-independent log_st
 
 Stable-Baselines3 itself is not a dependency and is not installed where this was written: the state-dict key mapping below follows the parameter
 names SB3 gives `ActorCriticPolicy(net_arch=dict(pi=[h1, h2], vf=[v1, v2]))` and is checked against those names only, not against a live SB3
-policy.  Out of scope: action masks, SAC's squashed Gaussian, recurrent policies.  The learner is `ev2gym_amd.ppo.PPOLearner`.
+policy.  Out of scope: action masks, recurrent policies (SAC's squashed Gaussian is `ev2gym_amd.sac`, behind the replay ring).  The learner is `ev2gym_amd.ppo.PPOLearner`.
 """
 from __future__ import annotations
 

@@ -213,38 +213,16 @@ class EV2GymSB3VecEnv(_SB3VecEnv):
         return None
 
 
-class DeviceReplayCollector:
-    """Off-policy rollout collection that never leaves the device: the `collect_rollouts()` half of an SB3 DDPG / TD3 / SAC loop
-    (`/root/reference/train_stable_baselines.py:62-130`) for thousands of envs.
+class ReplayRing:
+    """The replay buffer of the device collectors (DeviceReplayCollector here, ev2gym_amd.sac.SACCollector): a ring of EPISODE BLOCKS in device
+    memory -- `obs` [T + 1, E, D], `actions` [T, E, P], `reward`, `done`, `mask` per block -- with its bookkeeping (`head`: the block the next
+    episode goes into, `filled`: complete episodes, `cap`), `terminal_observation` and the torch-side `sample`.  A collector fills the head
+    block and calls `_advance()`."""
 
-    SB3's `VecEnv` protocol (the adapter above) moves numpy arrays every step -- 3.6 MB per step at 4096 x 50 -- and its replay buffer lives on
-    the host.  Here the replay buffer is a ring of EPISODE BLOCKS in device memory and `ev2g_collect` fills a block in place: the fused actor
-    reads observation row t and writes action row t, the step kernel reads that action row and writes observation row t + 1, reward, done and
-    action-mask row t.  `next_obs[t] = obs[t + 1]`, so a block IS the (obs, action, reward, next_obs, done) sequence of its episode (SB3's
-    `ReplayBuffer(optimize_memory_usage=True)` layout); its row T is every env's `terminal_observation`, and the reset observation of the
-    next episode lands in row 0 of the next block (`ev2g_get_stats_reset_f32`, which also yields the terminal `info` statistics).
-
-        col = DeviceReplayCollector(engine, actor_weights, lo=-1.0, capacity_episodes=4)
-        col.collect_episode()                       # one episode of all E envs: T x (actor forward -> env step), no host copies
-        obs, act, rew, nxt, done = col.sample(256)  # host-side draw of indices, device gathers (torch) -- what a learner consumes
-        col.set_weights(new_weights)                # the learner's updated actor
-        learner = TD3Learner(col)                   # ev2gym_amd.td3: samples and trains on the device and rewrites the collector's actor there
-
-    `engine` must not have float32 hand-over buffers registered (`ev2g_set_step_extras`): the collector's rows are the hand-over.
-    Arrays are torch tensors when torch is importable (PyTorch-ROCm is the SB3 side's tensor type), DeviceBuffers otherwise.
-
-    Stream order: the engine works on ITS OWN stream (non-blocking unless it was created on torch's), the torch side on torch's current
-    stream.  The blocks are allocated uninitialised and torch's stream is drained once before the engine first writes them (nothing torch
-    queued can land behind the reset observation); `sample()` / `terminal_observation()` wait for the engine's stream before torch reads."""
-
-    def __init__(self, engine, weights, lo: float, capacity_episodes: int = 2, precision: str = "bf16", offset_stride: Optional[int] = None, use_torch: Optional[bool] = None):
+    def _init_ring(self, engine, capacity_episodes, offset_stride, use_torch):
         from . import _abi
         self.eng = eng = engine
         self.E, self.P, self.D, self.T, self.M = eng.E, eng.P, eng.D, eng.T, eng.M
-        self.lo, self.precision = float(lo), precision
-        self.weights = [np.ascontiguousarray(w, np.float32) for w in weights]   # what the policy was created with (a TD3 / DDPG learner's initial actor)
-        self.mlp = eng.mlp_create(*self.weights, out_lo=self.lo, precision=precision)
-        self.learner = None      # the TD3Learner / DDPGLearner bound to the policy, if any (it registers itself)
         self.cap = max(2, int(capacity_episodes))   # (the reset observation of the next episode is written into the NEXT block)
         if use_torch is None:
             try:
@@ -278,22 +256,10 @@ class DeviceReplayCollector:
             self._torch.cuda.synchronize()   # the caching allocator may hand out memory with work of torch's stream still queued on it
         eng.reset_f32(self.obs[0], self.offset)
 
-    def set_weights(self, weights):
-        """The learner's new actor (host float32 arrays, torch.nn.Linear layout): a fresh policy object replaces the old one.  Refused while a
-        device learner (ev2gym_amd.td3) is bound to the policy: it rewrites the policy itself, and replacing the object would take it along."""
-        if getattr(self.learner, "learner", None):
-            raise RuntimeError("set_weights: a device learner is bound to this collector's policy and keeps it up to date; close() the learner first")
-        weights = [np.ascontiguousarray(w, np.float32) for w in weights]
-        old = self.mlp
-        self.mlp = self.eng.mlp_create(*weights, out_lo=self.lo, precision=self.precision)
-        self.weights = weights
-        self.eng.mlp_destroy(old)
-
-    def collect_episode(self):
-        """One whole episode of every env into the head block; statistics of the finished episode; reset onto the next pool window with the
-        reset observation in row 0 of the next block.  Returns the index of the block that was filled."""
+    def _advance(self):
+        """Behind a collected episode in the head block: statistics of the finished episode, reset onto the next pool window with the reset
+        observation in row 0 of the next block, the ring's bookkeeping.  Returns the index of the block that was filled."""
         b, eng = self.head, self.eng
-        eng.collect(self.mlp, self.T - eng.current_step, self.obs[b], self.actions[b], self.reward[b], self.done[b], self.mask[b])
         nb = (b + 1) % self.cap
         self.offset = (self.offset + self.offset_stride) % self.M
         eng.stats_reset_f32(self.stats, self.obs[nb], self.offset)
@@ -330,6 +296,58 @@ class DeviceReplayCollector:
             out[0].append(self.obs[b][tt, ee]); out[1].append(self.actions[b][tt, ee]); out[2].append(self.reward[b][tt, ee])
             out[3].append(self.obs[b][tt + 1, ee]); out[4].append(self.done[b][tt, ee])
         return tuple(torch.cat(x) for x in out)
+
+
+
+class DeviceReplayCollector(ReplayRing):
+    """Off-policy rollout collection that never leaves the device: the `collect_rollouts()` half of an SB3 DDPG / TD3 loop (SAC's, with its
+    stochastic actor, is `ev2gym_amd.sac.SACCollector` over the same ring)
+    (`/root/reference/train_stable_baselines.py:62-130`) for thousands of envs.
+
+    SB3's `VecEnv` protocol (the adapter above) moves numpy arrays every step -- 3.6 MB per step at 4096 x 50 -- and its replay buffer lives on
+    the host.  Here the replay buffer is a ring of EPISODE BLOCKS in device memory and `ev2g_collect` fills a block in place: the fused actor
+    reads observation row t and writes action row t, the step kernel reads that action row and writes observation row t + 1, reward, done and
+    action-mask row t.  `next_obs[t] = obs[t + 1]`, so a block IS the (obs, action, reward, next_obs, done) sequence of its episode (SB3's
+    `ReplayBuffer(optimize_memory_usage=True)` layout); its row T is every env's `terminal_observation`, and the reset observation of the
+    next episode lands in row 0 of the next block (`ev2g_get_stats_reset_f32`, which also yields the terminal `info` statistics).
+
+        col = DeviceReplayCollector(engine, actor_weights, lo=-1.0, capacity_episodes=4)
+        col.collect_episode()                       # one episode of all E envs: T x (actor forward -> env step), no host copies
+        obs, act, rew, nxt, done = col.sample(256)  # host-side draw of indices, device gathers (torch) -- what a learner consumes
+        col.set_weights(new_weights)                # the learner's updated actor
+        learner = TD3Learner(col)                   # ev2gym_amd.td3: samples and trains on the device and rewrites the collector's actor there
+
+    `engine` must not have float32 hand-over buffers registered (`ev2g_set_step_extras`): the collector's rows are the hand-over.
+    Arrays are torch tensors when torch is importable (PyTorch-ROCm is the SB3 side's tensor type), DeviceBuffers otherwise.
+
+    Stream order: the engine works on ITS OWN stream (non-blocking unless it was created on torch's), the torch side on torch's current
+    stream.  The blocks are allocated uninitialised and torch's stream is drained once before the engine first writes them (nothing torch
+    queued can land behind the reset observation); `sample()` / `terminal_observation()` wait for the engine's stream before torch reads."""
+
+    def __init__(self, engine, weights, lo: float, capacity_episodes: int = 2, precision: str = "bf16", offset_stride: Optional[int] = None, use_torch: Optional[bool] = None):
+        self.lo, self.precision = float(lo), precision
+        self.weights = [np.ascontiguousarray(w, np.float32) for w in weights]   # what the policy was created with (a TD3 / DDPG learner's initial actor)
+        self.mlp = engine.mlp_create(*self.weights, out_lo=self.lo, precision=precision)
+        self.learner = None      # the TD3Learner / DDPGLearner bound to the policy, if any (it registers itself)
+        self._init_ring(engine, capacity_episodes, offset_stride, use_torch)
+
+    def set_weights(self, weights):
+        """The learner's new actor (host float32 arrays, torch.nn.Linear layout): a fresh policy object replaces the old one.  Refused while a
+        device learner (ev2gym_amd.td3) is bound to the policy: it rewrites the policy itself, and replacing the object would take it along."""
+        if getattr(self.learner, "learner", None):
+            raise RuntimeError("set_weights: a device learner is bound to this collector's policy and keeps it up to date; close() the learner first")
+        weights = [np.ascontiguousarray(w, np.float32) for w in weights]
+        old = self.mlp
+        self.mlp = self.eng.mlp_create(*weights, out_lo=self.lo, precision=self.precision)
+        self.weights = weights
+        self.eng.mlp_destroy(old)
+
+    def collect_episode(self):
+        """One whole episode of every env into the head block; statistics of the finished episode; reset onto the next pool window with the
+        reset observation in row 0 of the next block.  Returns the index of the block that was filled."""
+        b, eng = self.head, self.eng
+        eng.collect(self.mlp, self.T - eng.current_step, self.obs[b], self.actions[b], self.reward[b], self.done[b], self.mask[b])
+        return self._advance()
 
     def close(self):
         self.eng.mlp_destroy(self.mlp)

@@ -20,7 +20,7 @@ The ring stores the env's action in [lo, 1]; the critics take SB3's scaled actio
 
 `td3_update_numpy` (with `td3_critic_numpy` / `td3_actor_numpy`) is the float64 restatement with analytic backprop, no torch: the numerics
 reference the tests hold the kernels to.  Refused with a message: `action_noise`, a `learning_starts` warm-up, schedule objects (drive one with
-`set_rate()`), `optimize_memory_usage` options, SAC / TQC (`make_learner`).  SB3's default for both algorithms is `action_noise=None`, which
+`set_rate()`), `optimize_memory_usage` options, SAC / TQC (`make_learner`: SAC is `ev2gym_amd.sac.SACLearner`, behind its own collector).  SB3's default for both algorithms is `action_noise=None`, which
 is what the reference script runs.
 """
 from __future__ import annotations
@@ -295,10 +295,12 @@ class DDPGLearner(TD3Learner):
 
 
 def make_learner(algo, collector, **kw):
-    """The learner of an off-policy algorithm by SB3's name: "TD3" or "DDPG".  SAC and TQC (squashed Gaussian, entropy tuning) are refused."""
+    """The learner of an off-policy algorithm by SB3's name: "TD3" or "DDPG".  SAC is refused here -- this module's collector owns a deterministic
+    policy object; ev2gym_amd.sac.SACLearner trains SAC behind a SACCollector -- and so is TQC."""
     kinds = {"td3": TD3Learner, "ddpg": DDPGLearner}
     if str(algo).lower() not in kinds:
-        raise ValueError(f"make_learner: {algo} is not supported (TD3 and DDPG are; SAC / TQC are out of scope)")
+        raise ValueError(f"make_learner: {algo} is not supported (TD3 and DDPG are; SAC / TQC are not this module's: SAC is "
+                         "ev2gym_amd.sac.SACLearner behind a SACCollector, TQC is out of scope)")
     return kinds[str(algo).lower()](collector, **kw)
 
 

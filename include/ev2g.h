@@ -406,8 +406,8 @@ int ev2g_rollout(ev2g_handle *h, const ev2g_mlp *m, int k_steps, double *reward,
  * EV2G_ROLLOUT_GRAPHS=0 in the environment falls back to plain launches.  Number of graph replays so far: */
 long long ev2g_rollout_graph_launches(const ev2g_handle *h);
 
-/* Off-policy ROLLOUT COLLECTION into device memory (the collect_rollouts() half of an SB3 DDPG / TD3 / SAC loop,
- * train_stable_baselines.py:62-130): k_steps x (actor forward -> env step) whose transitions land directly in the caller's device arrays --
+/* Off-policy ROLLOUT COLLECTION into device memory (the collect_rollouts() half of an SB3 DDPG / TD3 loop,
+ * train_stable_baselines.py:62-130; SAC's, with its stochastic actor, is ev2g_sac_collect over the same arrays): k_steps x (actor forward -> env step) whose transitions land directly in the caller's device arrays --
  * no host copy, no staging copy: the actor reads observation row i and writes action row i, the step kernel reads that action row and writes
  * observation row i + 1, reward / done / mask row i.  With next_obs[i] = obs[i + 1] these arrays ARE a replay-buffer segment (SB3's
  * ReplayBuffer(optimize_memory_usage=True) layout).  obs[0] is input: the observation the first action is computed from (the reset
@@ -832,7 +832,8 @@ int ev2g_host_a2c_head(const float *mean, const float *value, const float *actio
  * created with (every packing of csrc/ev2g_policy_host.h, padding untouched), so the collector reads the new actor without the weights leaving
  * the device.  A policy has at most one learner (EV2G_ERR_STATE for a second); the learner is owned by the handle and ends with it, with
  * ev2g_td3_destroy, or with ev2g_mlp_destroy of its policy.  Rollout graphs captured for the policy stay valid (the images keep their addresses).
- * Not reproduced: action_noise, learning_starts, schedule objects (ev2g_td3_set_rate between calls drives one), SAC / TQC. */
+ * Not reproduced: action_noise, learning_starts, schedule objects (ev2g_td3_set_rate between calls drives one), TQC.  SAC is not this learner's
+ * either: it has its own object with a stochastic actor, ev2g_sac_* below. */
 #define EV2G_TD3_MAX_BATCH 1024
 typedef struct ev2g_td3 ev2g_td3;
 typedef struct ev2g_td3_config {
@@ -899,6 +900,82 @@ int ev2g_host_replay_indices(int32_t *index, int B, int n_blocks, int T, int E, 
 int ev2g_host_td3_target(const float *a_target, const float *tq, const float *reward, const uint8_t *done, int B, int P, int n_critics, double sigma,
                          double clip, double gamma, uint64_t seed, uint64_t first_draw, float *a_next, float *y);
 int ev2g_host_polyak(float *target, const float *param, int64_t n, double tau);
+
+/* ---- SAC on the device: SB3's SAC.train() for SACPolicy (MlpPolicy, Box actions, use_sde off), and its stochastic collection actor
+ * (csrc/ev2g_sac.h) ----
+ *   actor: h = ReLU(W2 ReLU(W1 s + b1) + b2), mu = Wmu h + bmu, log_std = clamp(Wls h + bls, -20, 2), a = tanh(mu + exp(log_std) eps),
+ *          log pi = sum_p [-eps^2 / 2 - log_std - log(2 pi) / 2] - sum_p log(1 - a^2 + 1e-6)
+ *   critics: n_critics (1 or 2) of (s, a) -> h1 -> h2 -> 1 with ReLU, and their targets; no actor target.
+ * One update on the contiguous DEVICE batch (s, a~, r, s', done) of B rows, alpha = exp(log_ent_coef) as it stands before the update, d the
+ * learner's draw base (ev2g_sac_seed):
+ *   a_pi, log pi on s with the draws d + b P + p;  a', log pi' on s' with the draws d + B P + b P + p;
+ *   y = r + ((1 - done) gamma) (min_j target_j(s', a') - alpha log pi');  critic_loss = 0.5 sum_j mean((Q_j(s, a~) - y)^2) -> Adam on the critics;
+ *   actor_loss = mean(alpha log pi - min_j Q_j(s, a_pi)) with the critics after their step, through each row's argmin critic -> Adam on the actor;
+ *   ent_coef_loss = -mean(log_ent_coef (log pi + target_entropy)) -> Adam on log_ent_coef (ent_coef_auto only);
+ *   every target_update_interval-th update target <- (1 - tau) target + tau param for the critics; d += 2 B P;
+ *   the collection actor's packed weights are rewritten from the float32 masters.
+ * `actions` holds what the replay ring stores, the env's action in [lo, 1]; the critics read SB3's scaled action (2 a - 1 for lo = 0).
+ * float32 layer products, the heads in float64 from the stored float32 mu, raw log_std and eps with every output rounded once, every sum in one
+ * fixed order, no float atomics: the same call on the same state gives the same bits.
+ * LIMITS (a message per field otherwise): d_in <= 192, hidden widths 1 .. 256, d_out <= 64, 1 <= B <= EV2G_TD3_MAX_BATCH, n_critics 1 or 2.
+ * actor: the 8 host arrays actor.latent_pi.{0,2}.{weight,bias}, actor.mu.{weight,bias}, actor.log_std.{weight,bias}; critics: 6 per critic; all
+ * float32 in SB3's [out, in] layout.  The object belongs to the handle: freed by ev2g_sac_destroy or with ev2g_destroy.
+ * Not reproduced: use_sde, action_noise, learning_starts, schedule objects (ev2g_sac_set_rate between calls drives one), TQC. */
+typedef struct ev2g_sac ev2g_sac;
+typedef struct ev2g_sac_config {
+    double lr, beta1, beta2, adam_eps, tau, gamma;         /* 3e-4 (all three optimisers), 0.9, 0.999, 1e-8, 0.005, 0.99 */
+    double ent_coef;                                       /* the coefficient log_ent_coef starts from ("auto": 1.0, "auto_0.1": 0.1), or the fixed one.  > 0 */
+    double target_entropy;                                 /* read when target_entropy_auto == 0 */
+    int32_t n_critics, target_update_interval;             /* 2, 1 */
+    int32_t ent_coef_auto, target_entropy_auto;            /* 1: log_ent_coef is trained; 1: target_entropy = -d_out */
+} ev2g_sac_config;
+int ev2g_sac_default_config(ev2g_sac_config *cfg);
+int ev2g_sac_create(ev2g_handle *h, const ev2g_sac_config *cfg, int d_in, int h1, int h2, int d_out, float lo, const float *const *actor,
+                    const float *const *critics, uint64_t seed, ev2g_sac **out);
+void ev2g_sac_destroy(ev2g_handle *h, ev2g_sac *s);
+/* losses (DEVICE float32 [4], may be NULL): critic_loss, actor_loss, ent_coef_loss (0 for a fixed coefficient), ent_coef.  Asynchronous. */
+int ev2g_sac_update(ev2g_handle *h, ev2g_sac *s, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                    const uint8_t *done, int B, float *losses);
+/* The two gradient stages without the apply.  ev2g_sac_critic_grad draws eps' (base d + B P) and leaves y, log pi' and the critics' gradient;
+ * ev2g_sac_actor_grad draws eps (base d) and leaves log pi, the actor's gradient through the critics as they are now and the gradient of
+ * log_ent_coef.  ev2g_sac_apply consumes what is pending (EV2G_ERR_STATE when nothing is), the critics' half first; applying an actor half
+ * steps log_ent_coef, advances d by 2 B P, counts one update (the Polyak step on every target_update_interval-th) and rewrites the packed
+ * weights.  ev2g_sac_update is critic_grad, apply, actor_grad, apply. */
+int ev2g_sac_critic_grad(ev2g_handle *h, ev2g_sac *s, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                         const uint8_t *done, int B, float *losses);
+int ev2g_sac_actor_grad(ev2g_handle *h, ev2g_sac *s, const float *obs, int B, float *losses);
+int ev2g_sac_apply(ev2g_handle *h, ev2g_sac *s);
+/* The collection actor on n_rows DEVICE observation rows [n_rows, d_in]: actions [n_rows, d_out] in the env's box [lo, 1]; mu, log_std (raw,
+ * before the clamp) [n_rows, d_out] and log_pi [n_rows] may be NULL.  deterministic != 0: a = tanh(mu), nothing is drawn and the collection
+ * counter does not move; else element (e, p) of the object's n-th sampling launch takes draw (n n_rows + e) d_out + p of the collection stream
+ * (ev2g_sac_act_seed), which is not the learner's.  A row's outputs do not depend on the rows it is launched with. */
+int ev2g_sac_act(ev2g_handle *h, ev2g_sac *s, const float *obs32, int n_rows, int deterministic, float *actions, float *mu, float *log_std,
+                 float *log_pi);
+/* ev2g_collect's unfused loop with ev2g_sac_act in the actor's place (same arrays, same refusals, the registered hand-over route included) */
+int ev2g_sac_collect(ev2g_handle *h, ev2g_sac *s, int k_steps, int deterministic, const ev2g_transitions *tr);
+/* Read-backs into HOST arrays; all synchronise.  `out`: 8 + 6 n_critics float32 arrays in SB3's parameter order (NULL entries skipped).
+ * get_grads: the last gradient of each half, g_log_ent_coef (may be NULL) that of log_ent_coef.  get_weights: the masters (target == 0) or the
+ * target critics (target != 0: the actor's 8 entries are not written).  get_y / get_log_pi: y and log pi' [B] of the last critic gradient / log pi
+ * [B] of the last actor gradient.  get_ent_coef: out3 = {log_ent_coef, Adam's m, Adam's v}. */
+int ev2g_sac_get_grads(ev2g_handle *h, ev2g_sac *s, float *const *out, float *g_log_ent_coef);
+int ev2g_sac_get_weights(ev2g_handle *h, ev2g_sac *s, int target, float *const *out);
+int ev2g_sac_get_y(ev2g_handle *h, ev2g_sac *s, float *y, float *log_pi_next, int B);
+int ev2g_sac_get_log_pi(ev2g_handle *h, ev2g_sac *s, float *log_pi, int B);
+int ev2g_sac_get_ent_coef(ev2g_handle *h, ev2g_sac *s, float *out3);
+int ev2g_sac_set_rate(ev2g_handle *h, ev2g_sac *s, double lr);
+/* the learner's noise stream: its seed and the base d of the next update; and the collection stream: its seed and the launch counter n */
+int ev2g_sac_seed(ev2g_handle *h, ev2g_sac *s, uint64_t seed, uint64_t first_draw);
+int ev2g_sac_act_seed(ev2g_handle *h, ev2g_sac *s, uint64_t seed, uint64_t first_launch);
+/* updates applied, Polyak steps among them, the learner's next draw base, the collection stream's launch counter (each may be NULL) */
+int ev2g_sac_counters(ev2g_handle *h, ev2g_sac *s, int64_t *updates, int64_t *target_updates, uint64_t *next_draw, uint64_t *act_launches);
+/* Host twins of the head's element functions (HOST arrays).  ev2g_host_sac_head: a [B, P] (tanh), a_env [B, P] in [lo, 1] (may be NULL) and
+ * log_pi [B] from mu, raw log_std and the standard normals eps [B, P].  ev2g_host_sac_head_back: d_mu, d_log_std [B, P] from g = dQ_min / da.
+ * ev2g_host_sac_y: y [B] from the target critics' values tq [n_critics, B] and log pi' [B]. */
+int ev2g_host_sac_head(const float *mu, const float *log_std, const float *eps, int B, int P, float lo, float *a, float *a_env, float *log_pi);
+int ev2g_host_sac_head_back(const float *mu, const float *log_std, const float *eps, const float *g, int B, int P, float log_ent_coef, float *d_mu,
+                            float *d_log_std);
+int ev2g_host_sac_y(const float *tq, const float *log_pi_next, const float *reward, const uint8_t *done, int B, int n_critics, double gamma,
+                    float log_ent_coef, float *y);
 
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);

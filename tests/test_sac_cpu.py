@@ -1,0 +1,202 @@
+"""The SAC learner's arithmetic without a GPU (ev2gym_amd/sac.py, csrc/ev2g_sac.h's host twins, the host-only plan):
+
+  * `sac_update_numpy` and its two halves (float64, analytic backprop) against torch float64 autograd and three torch.optim.Adam(eps=1e-8), to
+    1e-9 of each array's largest magnitude (the project's float64 parity bound; the analytic form measured 3e-11 against autograd with an
+    upper-clamped log_std column): gradients, y, log pi, the three losses, the gradient of log_ent_coef, and three consecutive updates with
+    target_update_interval 2; auto and fixed ent_coef, one and two critics, both action boxes, B in {1, 37};
+  * the clamp case: the two log_std columns clamped for every row have gradient exactly 0.0;
+  * torch's literal Normal(mu, sigma).log_prob(u) on a case without a column at -20 gives the same gradients: the reduced Gaussian term the twin
+    uses is the same function, written so that it does not cancel;
+  * tests/host/sac_check.cpp, a stand-alone C++17 program, plain and under -fsanitize=address,undefined;
+  * the host twins through the library and the Python-side refusals."""
+import math
+import os
+import shutil
+import subprocess
+import types
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from tests import sac_cases as sc
+
+BOUND = 1e-9
+
+
+def _close(tag, got, ref):
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    scale = max(float(np.abs(ref).max()), 1e-300)
+    dev = float(np.abs(got - ref).max())
+    print(f"{tag}: deviation {dev:.3e} scale {scale:.3e}")
+    assert dev <= BOUND * scale, (tag, dev, scale)
+
+
+def _numpy_halves(case):
+    from ev2gym_amd.sac import sac_actor_numpy, sac_critic_numpy
+    cg, closs, aux = sac_critic_numpy(case["actor"], case["critics"], case["critics"], case["obs"], case["actions"], case["reward"], case["next_obs"],
+                                      case["done"], case["eps_next"], case["log_ent_coef"], case["lo"], case["gamma"])
+    ag, aloss, ga, eloss, aaux = sac_actor_numpy(case["actor"], case["critics"], case["obs"], case["eps"], case["log_ent_coef"], case["target_entropy"], case["auto"])
+    return dict(y=aux.y, log_pi_next=aux.logp_next, log_pi=aaux.fa.logp, critic_loss=closs, actor_loss=aloss, ent_coef_loss=eloss, ent_coef_grad=ga,
+                critic_grads=cg, actor_grads=ag, aux=aaux)
+
+
+def _check_halves(got, ref, n_critics):
+    for k in ("y", "log_pi_next", "log_pi", "critic_loss", "actor_loss"):
+        _close(k, got[k], ref[k])
+    for k in ("ent_coef_loss", "ent_coef_grad"):
+        if ref[k] == 0.0:
+            assert got[k] == 0.0, k
+        else:
+            _close(k, got[k], ref[k])
+    for j in range(n_critics):
+        for i in range(6):
+            _close(f"critic {j} grad {i}", got["critic_grads"][j][i], ref["critic_grads"][j][i])
+    for i in range(8):
+        if not np.any(ref["actor_grads"][i]):
+            assert not np.any(got["actor_grads"][i]), f"actor grad {i} must be exactly 0"
+        else:
+            _close(f"actor grad {i}", got["actor_grads"][i], ref["actor_grads"][i])
+
+
+@pytest.mark.parametrize("lo", [-1.0, 0.0])
+@pytest.mark.parametrize("B", [1, 37])
+@pytest.mark.parametrize("n_critics", [1, 2])
+@pytest.mark.parametrize("auto", [True, False])
+def test_numpy_halves_match_torch_float64_autograd(auto, n_critics, B, lo):
+    import torch
+    case = sc.make_case(63, 20, "64-64", n_critics, B, lo, 0.7, auto)
+    got = _numpy_halves(case)
+    _check_halves(got, sc.torch_grads(case, torch.float64), n_critics)
+    if n_critics == 2 and B > 1:
+        assert 0 < got["aux"].argmin.sum() < B   # both critics are some row's argmin
+    assert (got["ent_coef_grad"] != 0.0) == auto
+
+
+@pytest.mark.parametrize("B", [1, 37])
+def test_clamped_log_std_columns_have_gradient_exactly_zero(B):
+    import torch
+    case = sc.make_case(11, 5, "33-17", 2, B, -1.0, 0.7, True, clamp=True)
+    got = _numpy_halves(case)
+    _check_halves(got, sc.torch_grads(case, torch.float64), 2)
+    W, b = got["actor_grads"][6], got["actor_grads"][7]
+    assert np.array_equal(W[:2], np.zeros_like(W[:2])) and np.array_equal(b[:2], np.zeros(2)), "the clamped columns' weight rows and biases"
+    assert np.abs(W[2:]).max(axis=1).min() > 0.0 and np.abs(b[2:]).min() > 0.0   # (the other columns' are not)
+    assert np.array_equal(got["aux"].d_log_std[:, :2], np.zeros((B, 2)))
+
+
+def test_literal_normal_log_prob_gives_the_same_gradients_without_a_column_at_the_lower_clamp():
+    """SB3 writes Normal(mu, sigma).log_prob(mu + sigma eps).  Without a column at sigma = e^-20 -- where (mu + sigma eps) - mu cancels -- it agrees
+    with the reduced form to the same bound, which is why the reduced form is the twin."""
+    import torch
+    case = sc.make_case(11, 5, "33-17", 2, 37, -1.0, 0.7, True)
+    case["actor"][7][0] = 3.0   # an upper-clamped column stays
+    _check_halves(_numpy_halves(case), sc.torch_grads(case, torch.float64, literal=True), 2)
+
+
+@pytest.mark.parametrize("lo", [-1.0, 0.0])
+@pytest.mark.parametrize("B", [1, 37])
+@pytest.mark.parametrize("n_critics", [1, 2])
+@pytest.mark.parametrize("auto", [True, False])
+def test_three_numpy_updates_match_a_torch_float64_loop(auto, n_critics, B, lo):
+    import torch
+    from ev2gym_amd.sac import sac_state, sac_update_numpy
+    case = sc.make_case(63, 20, "64-64", n_critics, 3 * B, lo, 0.7, auto)
+    batches = sc.loop_batches(case, 3, B)
+    ref = sc.torch_loop(case, batches, torch.float64, target_update_interval=2)
+    st = sac_state(case["actor"], case["critics"], math.exp(case["log_ent_coef"]))
+    la0 = float(st.log_ent_coef)
+    for k, (rows, eps, eps_next) in enumerate(batches):
+        out = sac_update_numpy(st, case["obs"][rows], case["actions"][rows], case["reward"][rows], case["next_obs"][rows], case["done"][rows], eps, eps_next, lo,
+                               gamma=case["gamma"], target_update_interval=2, target_entropy=case["target_entropy"], ent_coef_auto=auto)
+        r = ref[k]
+        for name in ("critic_loss", "actor_loss", "ent_coef"):
+            _close(f"step {k} {name}", getattr(out, name), r[name])
+        if auto:
+            _close(f"step {k} ent_coef_loss", out.ent_coef_loss, r["ent_coef_loss"])
+        _close(f"step {k} log_ent_coef", st.log_ent_coef + 10.0, r["log_ent_coef"] + 10.0)   # (log 0.7 + 10: the bound is relative)
+        for i in range(8):
+            _close(f"step {k} actor {i}", st.actor[i], r["actor"][i])
+        for j in range(n_critics):
+            for i in range(6):
+                _close(f"step {k} critic {j} {i}", st.critics[j][i], r["critics"][j][i])
+                _close(f"step {k} critic_target {j} {i}", st.critics_target[j][i], r["critics_target"][j][i])
+        if k == 0:   # target_update_interval 2: the targets have not moved yet
+            assert all(np.array_equal(st.critics_target[j][i], np.asarray(case["critics"][j][i], np.float64)) for j in range(n_critics) for i in range(6))
+    assert st.n == 3 and (float(st.log_ent_coef) != la0) == auto
+
+
+def test_sac_check_host_program(tmp_path):
+    cxx = next((c for c in (os.environ.get("CXX"), shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"), "/opt/rocm/llvm/bin/clang++")
+                if c and os.path.exists(c)), None)
+    if cxx is None:
+        pytest.fail("no host C++ compiler found (CXX, c++, g++, clang++)")
+    for tag, extra in (("plain", []), ("sanitized", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"])):
+        exe = str(tmp_path / f"sac_check_{tag}")
+        subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *extra, os.path.join(ROOT, "tests", "host", "sac_check.cpp"), "-o", exe], timeout=300)
+        run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+        print(run.stdout[-3000:])
+        assert run.returncode == 0, tag + ": " + run.stdout[-3000:] + run.stderr[-3000:]
+        assert "sac_check: ok" in run.stdout
+
+
+def test_host_twins_of_the_head_and_of_y():
+    from ev2gym_amd.engine import EngineError, host_sac_head, host_sac_head_back, host_sac_y
+    rng = np.random.default_rng(4)
+    B, P = 33, 20
+    mu = rng.normal(0.0, 1.5, (B, P)).astype(np.float32)
+    ls = rng.uniform(-23.0, 3.0, (B, P)).astype(np.float32)
+    eps = rng.normal(size=(B, P)).astype(np.float32)
+    a, a_env, lp = host_sac_head(mu, ls, eps, lo=0.0)
+    lsc = np.clip(ls.astype(np.float64), -20.0, 2.0)
+    a64 = np.tanh(mu + np.exp(lsc) * eps.astype(np.float64))
+    lp64 = (-0.5 * eps.astype(np.float64) ** 2 - lsc - sc.HALF_LOG_2PI).sum(1) - np.log(1.0 - a64 * a64 + 1e-6).sum(1)
+    assert np.abs(a - a64).max() <= 2.0 ** -23 and np.array_equal(a_env, np.float32(0.5) * (a + np.float32(1.0)))   # (|a| <= 1: one float32 rounding)
+    assert np.abs(lp - lp64).max() <= 2.0 ** -23 * np.abs(lp64).max()   # one float32 rounding of a float64 sum
+    assert (ls < -20).any() and (ls > 2).any() and np.array_equal(host_sac_head(mu, ls, eps, lo=-1.0)[1], a)
+    g = rng.normal(size=(B, P)).astype(np.float32)
+    la = float(np.float32(math.log(0.3)))
+    dm, dl = host_sac_head_back(mu, ls, eps, g, la)
+    alpha, omt = math.exp(la), 1.0 - a64 * a64
+    du = (alpha * 2.0 * a64 * omt / (omt + 1e-6) - g * omt) / B
+    dls = np.where((ls > -20.0) & (ls < 2.0), du * np.exp(lsc) * eps - alpha / B, 0.0)
+    assert np.abs(dm - du).max() <= 2.0 ** -23 * np.abs(du).max() and np.abs(dl - dls).max() <= 2.0 ** -23 * np.abs(dls).max()
+    assert np.array_equal(dl[(ls <= -20.0) | (ls >= 2.0)], np.zeros(int(((ls <= -20.0) | (ls >= 2.0)).sum()), np.float32))
+    tq = rng.normal(size=(2, B)).astype(np.float32)
+    r, d = rng.normal(size=B).astype(np.float32), (rng.uniform(size=B) < 0.4).astype(np.uint8)
+    for nc in (1, 2):
+        y = host_sac_y(tq[:nc], lp, r, d, 0.99, la)
+        want = r.astype(np.float64) + (1.0 - d) * 0.99 * (tq[:nc].min(0).astype(np.float64) - alpha * lp.astype(np.float64))
+        assert np.abs(y - want).max() <= 2.0 ** -23 * np.abs(want).max()
+    with pytest.raises(EngineError):
+        host_sac_y(np.zeros((3, B), np.float32), lp, r, d, 0.99, la)
+
+
+def test_python_refusals():
+    from ev2gym_amd.sac import SACLearner, init_sac_actor_weights, make_learner, parse_ent_coef
+    from ev2gym_amd import td3
+    col = types.SimpleNamespace(eng=None, weights=init_sac_actor_weights(5, 2, 0, 8, 8), sac=None, cap=2, lo=-1.0)
+    for kw, word in ((dict(use_sde=True), "use_sde"), (dict(action_noise=object()), "action_noise"), (dict(learning_starts=100), "learning_starts"),
+                     (dict(lr=lambda f: 3e-4), "schedule"), (dict(optimize_memory_usage=True), "optimize_memory_usage"),
+                     (dict(top_quantiles_to_drop_per_net=2), "TQC"), (dict(ent_coef="automatic"), "ent_coef"), (dict(ent_coef="auto_x"), "ent_coef"),
+                     (dict(ent_coef="auto_-1"), "ent_coef"), (dict(ent_coef=0.0), "ent_coef"), (dict(target_entropy="half"), "target_entropy"),
+                     (dict(batch_size=0), "batch_size"), (dict(batch_size=1025), "batch_size"), (dict(policy_delay=2), "policy_delay")):
+        with pytest.raises(ValueError, match=word):
+            SACLearner(col, **kw)
+    assert parse_ent_coef("auto") == (1.0, True) and parse_ent_coef("auto_0.1") == (0.1, True) and parse_ent_coef(0.2) == (0.2, False)
+    big = types.SimpleNamespace(eng=None, weights=col.weights, sac=None, cap=34, lo=-1.0)
+    with pytest.raises(ValueError, match="capacity_episodes must be at most 33"):
+        SACLearner(big)
+    bound = types.SimpleNamespace(eng=None, weights=col.weights, sac=1, cap=2, lo=-1.0, learner=types.SimpleNamespace(learner=1))
+    with pytest.raises(ValueError, match="already has a learner"):
+        SACLearner(bound)
+    replay = types.SimpleNamespace(eng=None, weights=col.weights, mlp=None, cap=2, lo=-1.0)   # a DeviceReplayCollector's shape: no `sac`
+    with pytest.raises(ValueError, match="not a SACCollector"):
+        SACLearner(replay)
+    for algo in ("TD3", "TQC"):
+        with pytest.raises(ValueError, match="not supported"):
+            make_learner(algo, col)
+    with pytest.raises(ValueError, match="SAC / TQC") as e:
+        td3.make_learner("SAC", col)
+    assert "ev2gym_amd.sac.SACLearner" in str(e.value)
+    assert SACLearner.PRESET["lr"] == 3e-4 and SACLearner.PRESET["batch_size"] == 256 and SACLearner.PRESET["ent_coef"] == "auto"
