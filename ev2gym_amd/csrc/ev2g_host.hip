@@ -2740,7 +2740,7 @@ static void td3_wgrad(ev2g_handle *h, int B, const float *delta, long long zd, i
                       long long zP, int nz) {
     Td3Gemm g{};
     g.M = rows; g.N = cols; g.K = B; g.A = delta; g.zA = zd; g.sam = 1; g.sak = rows; g.Bm = in; g.zB = zin; g.sbk = cols; g.sbn = 1;
-    g.C = grad_w; g.ldc = cols; g.zC = zP; g.epi = TD3_EPI_NONE;
+    g.C = grad_w; g.ldc = cols; g.zC = zP; g.epi = TD3_EPI_NONE; g.acc64 = 1;
     td3_gemm(h, g, nz);
     hipLaunchKernelGGL(ev2g_td3_colsum_kernel, dim3((unsigned)((rows + 15) / 16), (unsigned)nz), dim3(256), 0, h->stream, delta, zd, B, rows, grad_b, zP);
 }

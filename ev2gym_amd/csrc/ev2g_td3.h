@@ -15,8 +15,10 @@
 // global workspace, and the twin critics (and their targets) are the z dimension of the same launch.
 //
 // One product kernel serves the forward layer, the backward-data layer and the weight gradient: C[m, n] = sum_k A(m, k) Bm(k, n) with strided
-// operands, 16 x 16 tiles staged through LDS, and ONE float32 fused-multiply-add chain per output element that runs k ascending from 0 (the
-// weight gradient's k is the batch row: rows ascending, no slab reduction).  Bias gradients are float64 column sums and the losses float64 sums,
+// operands, 16 x 16 tiles staged through LDS, and ONE fused-multiply-add chain per output element that runs k ascending from 0: float32 for the
+// layers (k: a layer's width), float64 rounded once for the weight gradient (k: the batch row, rows ascending, no slab reduction -- a float32
+// chain over 1024 rows drifts by about sqrt(1024) roundings, ten float32 ulps of the array's largest element where torch's float32 keeps one;
+// a float32 product is exact in float64).  Bias gradients are float64 column sums and the losses float64 sums,
 // each in one fixed order of rows (strided partials, rows ascending within one, joined in lane order) and rounded once.  No atomics, no kernel waits on another workgroup: the same call on the same state gives the same bits.  Masters are
 // float32 in SB3's [out, in] layout; the bound policy object's packed images are rewritten from the actor's masters after every actor step,
 // element by element through mlp_image_map (ev2g_policy_host.h), padding untouched.
@@ -61,10 +63,11 @@ __host__ __device__ inline uint16_t ev2g_bf16_term(float *r) {
 enum { TD3_EPI_NONE = 0, TD3_EPI_BIAS, TD3_EPI_BIAS_RELU, TD3_EPI_BIAS_TANH, TD3_EPI_MASK };
 // C[z][m, n] = epilogue(sum_k A[z](m, k) * Bm[z](k, n)); element (m, k) of A at A + z zA + m sam + k sak, (k, n) of Bm at Bm + z zB + k sbk + n sbn,
 // C row stride ldc.  BIAS*: + bias[z][n] then the activation.  MASK: 0 where H[z][m, n] <= 0 (ReLU's derivative from its output; H row stride ldh).
+// acc64: the chain runs in float64 and is rounded to float32 once, ahead of the epilogue (the weight gradient).
 struct Td3Gemm {
     const float *A, *Bm, *bias, *H;
     float *C;
-    int M, N, K, sam, sak, sbk, sbn, ldc, ldh, epi;
+    int M, N, K, sam, sak, sbk, sbn, ldc, ldh, epi, acc64;
     long long zA, zB, zbias, zH, zC;
 };
 __global__ void __launch_bounds__(EV2G_TD3_TILE *EV2G_TD3_TILE) ev2g_td3_gemm_kernel(const Td3Gemm g) {
@@ -73,15 +76,20 @@ __global__ void __launch_bounds__(EV2G_TD3_TILE *EV2G_TD3_TILE) ev2g_td3_gemm_ke
     const int m = blockIdx.y * EV2G_TD3_TILE + ty, n = blockIdx.x * EV2G_TD3_TILE + tx;
     const float *A = g.A + (long long)z * g.zA, *Bm = g.Bm + (long long)z * g.zB;
     float acc = 0.0f;
+    double acc_d = 0.0;
     for (int k0 = 0; k0 < g.K; k0 += EV2G_TD3_TILE) {
         const int ka = k0 + tx, kb = k0 + ty;
         As[ty][tx] = (m < g.M && ka < g.K) ? A[(long long)m * g.sam + (long long)ka * g.sak] : 0.0f;
         Bs[ty][tx] = (kb < g.K && n < g.N) ? Bm[(long long)kb * g.sbk + (long long)n * g.sbn] : 0.0f;
         __syncthreads();
         const int kn = g.K - k0 < EV2G_TD3_TILE ? g.K - k0 : EV2G_TD3_TILE;   // (a padded product would be + 0 * 0: the same bits, skipped)
-        for (int k = 0; k < kn; k++) acc = fmaf(As[ty][k], Bs[k][tx], acc);
+        if (g.acc64)
+            for (int k = 0; k < kn; k++) acc_d = fma((double)As[ty][k], (double)Bs[k][tx], acc_d);
+        else
+            for (int k = 0; k < kn; k++) acc = fmaf(As[ty][k], Bs[k][tx], acc);
         __syncthreads();
     }
+    if (g.acc64) acc = (float)acc_d;
     if (m >= g.M || n >= g.N) return;
     if (g.epi == TD3_EPI_BIAS || g.epi == TD3_EPI_BIAS_RELU || g.epi == TD3_EPI_BIAS_TANH) {
         acc += g.bias[(long long)z * g.zbias + n];

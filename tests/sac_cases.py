@@ -6,10 +6,51 @@ import math
 
 import numpy as np
 
-from tests.td3_cases import KINK, check_arrays  # noqa: F401  (check_arrays: re-exported for the tests)
+from tests.td3_cases import KINK, SATURATED, check_arrays, check_ring_wrap, grad_tol, nonzero_grads, saturated_ports  # noqa: F401  (re-exported for the tests)
 
 NETS = {"256-256": (256, 256), "64-64": (64, 64), "33-17": (33, 17)}
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+# The plan's limits and the head's lane edges (csrc/ev2g_sac.h: eight lanes per row, lane j takes ports j, j + 8, ...; the collection actor pads
+# inputs to k1 = ceil8(D) and ports to n3 = ceil32(P)): tag -> (D, h1, h2, P).  A table of its own: the GPU module's _grad_cases() cycles over NETS.
+#   limits   every plan maximum; n3 == P, so no padded port; lane 0's (every lane's) eighth port
+#   lanes    one port per head lane; k1 == D
+#   lanes+1  lane 0 alone takes a second port; k1 16 with 7 zero columns
+#   eighth   lane 0 alone takes an eighth port (P 57 > 56)
+#   tiny     seven idle head lanes; k1 8 with 7 zero columns
+EDGE_NETS = {"limits": (192, 256, 256, 64), "lanes": (8, 16, 16, 8), "lanes+1": (9, 33, 17, 9), "eighth": (63, 64, 64, 57), "tiny": (1, 5, 2, 1)}
+
+
+# (tag, n_critics, lo, auto, B): B in {1, 37, 1023, 1024} at limits and {37, 1024} elsewhere; n_critics, lo and auto are spread so that each
+# value meets each network, and both large batches at limits run two critics.
+EDGE_GRAD_CASES = [("limits", 1, 0.0, True, 1), ("limits", 1, -1.0, False, 37), ("limits", 2, -1.0, False, 1023), ("limits", 2, 0.0, True, 1024),
+                   ("lanes", 2, -1.0, True, 37), ("lanes", 1, 0.0, False, 1024), ("lanes+1", 1, 0.0, False, 37), ("lanes+1", 2, -1.0, True, 1024),
+                   ("eighth", 2, 0.0, False, 37), ("eighth", 1, -1.0, True, 1024), ("tiny", 1, -1.0, True, 37), ("tiny", 2, 0.0, False, 1024)]
+# (net, (D, P), n_critics, lo, auto, B) with a saturated actor
+SATURATED_GRAD_CASES = [("64-64", (63, 20), 2, -1.0, True, 37), ("limits", (192, 64), 2, 0.0, True, 257)]
+ACT_EDGE_CASES = [("limits", 0.0), ("lanes+1", -1.0), ("tiny", 0.0)]   # (tag, lo) of the collection actor's cases off NETS
+
+
+def edge_grad_case(tag, n_critics, lo, auto, B):
+    return edge_case(tag, n_critics, B, lo, 0.7, auto, seed=7 + B, first_draw=1000)
+
+
+def saturated_grad_case(net, dp, n_critics, lo, auto, B):
+    return make_case(*dp, net, n_critics, B, lo, 0.7, auto, seed=7 + B, first_draw=1000, saturate=True, live=True)
+
+
+def act_case(net, dp, lo, saturate=False):
+    """the collection actor's case (70 rows; the clamped log_std columns need three ports)"""
+    return make_case(*dp, net, 1, 70, lo, 0.7, True, clamp=dp[1] >= 3, seed=3, saturate=saturate)
+
+
+def _hidden(net):
+    return NETS[net] if net in NETS else EDGE_NETS[net][1:3]
+
+
+def edge_case(tag, *args, **kw):
+    """make_case on a row of EDGE_NETS, with the live-gradient condition."""
+    D, _, _, P = EDGE_NETS[tag]
+    return make_case(D, P, tag, *args, live=True, **kw)
 
 
 def _row_margin(case, rows):
@@ -32,28 +73,46 @@ def _row_margin(case, rows):
     return np.min(m, axis=0)
 
 
-def make_case(D, P, net="64-64", n_critics=2, B=37, lo=-1.0, ent_coef=0.7, auto=True, clamp=False, seed=7, noise_seed=11, first_draw=0):
+def make_case(D, P, net="64-64", n_critics=2, B=37, lo=-1.0, ent_coef=0.7, auto=True, clamp=False, seed=7, noise_seed=11, first_draw=0, saturate=False,
+              live=False):
     """_draw_case(seed), asserting that fewer than a quarter of the rows needed a redraw.  With ONE row a quarter means none: only then the first
-    of ten fixed seeds (seed, seed + 1000, ...) that needs no redraw is taken.  case["seeds_skipped"] says how many seeds were passed over."""
-    for i in range(10 if B == 1 else 1):
-        case = _draw_case(D, P, net, n_critics, B, lo, ent_coef, auto, clamp, seed + 1000 * i, noise_seed, first_draw)
+    of ten fixed seeds (seed, seed + 1000, ...) that needs no redraw is taken.  case["seeds_skipped"] says how many seeds were passed over.
+
+    live (the EDGE_NETS and the saturated cases): every float64 reference gradient array must also have a non-zero element
+    (tests/td3_cases.nonzero_grads: a dead ReLU in a narrow network zeroes whole arrays), and a seed that misses that or the cap is passed over
+    at any B, again among the ten fixed seeds.  The float64 reference is kept as case["ref64"]."""
+    import torch
+    for i in range(10 if (B == 1 or live) else 1):
+        case = _draw_case(D, P, net, n_critics, B, lo, ent_coef, auto, clamp, seed + 1000 * i, noise_seed, first_draw, saturate)
         case["seeds_skipped"] = i
-        if case["redrawn"] < B / 4.0:
+        ok = case["redrawn"] < B / 4.0
+        if live and ok:
+            case["ref64"] = torch_grads(case, torch.float64)
+            ok = nonzero_grads(case["ref64"])
+        if ok:
             break
     assert case["redrawn"] < B / 4.0, f"{case['redrawn']} of {B} rows needed a redraw"
+    if live:
+        assert nonzero_grads(case["ref64"]), "a reference gradient array is all zeros (dead ReLU)"
     return case
 
 
-def _draw_case(D, P, net, n_critics, B, lo, ent_coef, auto, clamp, seed, noise_seed, first_draw):
+def _draw_case(D, P, net, n_critics, B, lo, ent_coef, auto, clamp, seed, noise_seed, first_draw, saturate=False):
     """One batch and the networks of a learner: torch-style initial weights, observations in [0, 1], stored actions in [lo, 1], rewards of both
     signs, `done` mixed, the standard normals of a_pi (draws first_draw + b P + p) and of a' (first_draw + B P + b P + p) from the host twin.
-    clamp: log_std bias 0 is +3 and bias 1 is -25, so those two columns are clamped for every row (asserted)."""
+    clamp: log_std bias 0 is +3 and bias 1 is -25, so those two columns are clamped for every row (asserted).
+    saturate: the bias of mu of every second port is moved by +12, -12, +12, ... before the redraws, so that |mu| >= 10 in float64 on those
+    ports for every row of obs and next_obs (asserted): a = +-1 to float32 and log(1 - a^2 + 1e-6) sits at its floor wherever the noise does not
+    pull u back.  case["share_at_1"]: the share of a_pi and a' elements that are +-1 once rounded to float32."""
     from ev2gym_amd.engine import host_normal
     from ev2gym_amd.sac import init_sac_actor_weights, sac_actor_forward
     from ev2gym_amd.td3 import init_critic_weights
-    h1, h2 = NETS[net]
+    h1, h2 = _hidden(net)
     rng = np.random.default_rng(seed)
     actor = init_sac_actor_weights(D, P, seed, h1, h2)
+    if saturate:
+        ports, sign = saturated_ports(P)
+        actor[5][ports] += (SATURATED * sign).astype(np.float32)
     if clamp:
         assert P >= 3
         actor[7][0], actor[7][1] = 3.0, -25.0
@@ -91,6 +150,13 @@ def _draw_case(D, P, net, n_critics, B, lo, ent_coef, auto, clamp, seed, noise_s
         for x, e in ((case["obs"], case["eps"]), (case["next_obs"], case["eps_next"])):
             raw = sac_actor_forward(actor, x, e).raw
             assert (raw[:, 0] > 2.0).all() and (raw[:, 1] < -20.0).all() and (np.abs(raw[:, 2:]) < 2.0).all(), "the clamp case's columns"
+    if saturate:
+        ports, at_1 = saturated_ports(P)[0], []
+        for x, e in ((case["obs"], case["eps"]), (case["next_obs"], case["eps_next"])):
+            f = sac_actor_forward(actor, x, e)
+            assert np.abs(f.mu[:, ports]).min() >= 10.0, "a saturated port's mu is inside 10"
+            at_1.append(np.abs(f.a.astype(np.float32)) == 1.0)
+        case["share_at_1"] = float(np.mean(at_1))
     return case
 
 
@@ -106,16 +172,24 @@ def _mlp(w, x):
     return F.linear(torch.relu(F.linear(torch.relu(F.linear(x, w[0], w[1])), w[2], w[3])), w[4], w[5])
 
 
-def torch_actor(w, s, eps, literal=False):
-    """(a, log pi) of the squashed Gaussian.  literal: SB3's Normal(mu, sigma).log_prob(u) instead of the reduced Gaussian term."""
+def torch_actor(w, s, eps, literal=False, mixed=False):
+    """(a, log pi) of the squashed Gaussian.  literal: SB3's Normal(mu, sigma).log_prob(u) instead of the reduced Gaussian term.
+    mixed: the precision split csrc/ev2g_sac.h states for the device -- the networks in the tensors' own precision (float32), the head in float64
+    from mu, the raw log_std and eps as they stand, a and log pi rounded back once; autograd flows through the casts.  The yardstick of the
+    saturated cases, where plain float32 forms 1 - a^2 in float32 and its own error exceeds what it is meant to measure."""
     import torch
     F = torch.nn.functional
     h = torch.relu(F.linear(torch.relu(F.linear(s, w[0], w[1])), w[2], w[3]))
-    mu, ls = F.linear(h, w[4], w[5]), torch.clamp(F.linear(h, w[6], w[7]), -20.0, 2.0)
+    mu, raw = F.linear(h, w[4], w[5]), F.linear(h, w[6], w[7])
+    dtype = mu.dtype
+    if mixed:
+        mu, raw, eps = mu.double(), raw.double(), eps.double()
+    ls = torch.clamp(raw, -20.0, 2.0)
     u = mu + ls.exp() * eps
     a = torch.tanh(u)
     gauss = torch.distributions.Normal(mu, ls.exp()).log_prob(u) if literal else -0.5 * eps * eps - ls - HALF_LOG_2PI
-    return a, gauss.sum(1) - torch.log(1.0 - a * a + 1e-6).sum(1)
+    lp = gauss.sum(1) - torch.log(1.0 - a * a + 1e-6).sum(1)
+    return a.to(dtype), lp.to(dtype)
 
 
 def _batch(case, dtype, rows=None):
@@ -128,26 +202,26 @@ def _batch(case, dtype, rows=None):
     return s, a, r, s2, d
 
 
-def torch_critic_loss(case, actor, critics, critics_t, batch, eps_next, alpha, literal=False):
+def torch_critic_loss(case, actor, critics, critics_t, batch, eps_next, alpha, literal=False, mixed=False):
     """(critic_loss, y, log pi') as SB3 writes them."""
     import torch
     s, a, r, s2, d = batch
     with torch.no_grad():
-        a2, lp2 = torch_actor(actor, s2, eps_next, literal)
+        a2, lp2 = torch_actor(actor, s2, eps_next, literal, mixed)
         tq = torch.cat([_mlp(c, torch.cat([s2, a2], 1)) for c in critics_t], 1).min(1).values
         y = r + (1.0 - d) * case["gamma"] * (tq - alpha * lp2)
     xa = torch.cat([s, a], 1)
     return 0.5 * sum(torch.nn.functional.mse_loss(_mlp(c, xa)[:, 0], y) for c in critics), y, lp2
 
 
-def torch_actor_loss(actor, critics, s, eps, alpha, literal=False):
+def torch_actor_loss(actor, critics, s, eps, alpha, literal=False, mixed=False):
     import torch
-    a, lp = torch_actor(actor, s, eps, literal)
+    a, lp = torch_actor(actor, s, eps, literal, mixed)
     q = torch.cat([_mlp(c, torch.cat([s, a], 1)) for c in critics], 1).min(1).values
     return (alpha * lp - q).mean(), lp
 
 
-def torch_grads(case, dtype, literal=False):
+def torch_grads(case, dtype, literal=False, mixed=False):
     """One staged step (the critics' gradient, then the actor's and log_ent_coef's through the UNCHANGED critics) by autograd: dict of y,
     log_pi_next, log_pi, critic_loss, actor_loss, ent_coef_loss, ent_coef_grad, critic_grads (a list of six per critic), actor_grads, as
     float64 numpy."""
@@ -157,9 +231,9 @@ def torch_grads(case, dtype, literal=False):
     la = torch.tensor(case["log_ent_coef"], dtype=dtype, requires_grad=True)
     alpha = la.detach().exp()
     t = lambda a: torch.tensor(np.asarray(a), dtype=dtype)  # noqa: E731
-    closs, y, lp2 = torch_critic_loss(case, actor, critics, [[a.detach() for a in c] for c in critics], batch, t(case["eps_next"]), alpha, literal)
+    closs, y, lp2 = torch_critic_loss(case, actor, critics, [[a.detach() for a in c] for c in critics], batch, t(case["eps_next"]), alpha, literal, mixed)
     cg = torch.autograd.grad(closs, [a for c in critics for a in c])
-    aloss, lp = torch_actor_loss(actor, critics, batch[0], t(case["eps"]), alpha, literal)
+    aloss, lp = torch_actor_loss(actor, critics, batch[0], t(case["eps"]), alpha, literal, mixed)
     ag = torch.autograd.grad(aloss, actor)
     eloss = -(la * (lp.detach() + case["target_entropy"])).mean()
     eg = torch.autograd.grad(eloss, la)[0] if case["auto"] else torch.zeros(())

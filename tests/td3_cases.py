@@ -7,6 +7,59 @@ from tests.test_ppo_cpu import _record, grad_tol, value_tol
 
 NETS = {"400-300": (400, 300), "64-64": (64, 64), "33-17": (33, 17)}
 KINK = 1e-5   # no float64 pre-activation of a backpropagated ReLU layer is nearer to 0 than this
+# The plan's limits and the product kernel's tile edges (csrc/ev2g_td3_host.h: D <= 192, P <= 64, hidden widths 1 .. 400; csrc/ev2g_td3.h: 16 x 16
+# tiles, column sums over 16-column blocks): tag -> (D, h1, h2, P).  A table of its own: the _grad_cases() of the GPU modules cycle over NETS.
+#   limits   every plan maximum: 25 tiles per hidden layer, none ragged; the bound policy runs ev2g_mlp3_any (h2 > 304)
+#   tile     exactly one tile in every dimension: one trip of the k loop with kn = 16
+#   tile+1   every dimension ragged by one: the kn tail of 1, and the m < M / n < N / ka < K guards all act
+#   tiny     D 1, P 1, a critic input of 2 columns: layers narrower than a tile
+EDGE_NETS = {"limits": (192, 400, 400, 64), "tile": (16, 16, 16, 16), "tile+1": (17, 17, 33, 17), "tiny": (1, 5, 2, 1)}
+SATURATED = 12.0   # |output bias shift| of a saturated port: float32 tanh is exactly +-1 above about 9.01, in torch and on the device alike
+
+
+# (tag, n_critics, lo, sigma, B): B in {1, 33, 1023, 1024} at limits -- 1024 is the one size at which the z strides (from B) and the workspace's
+# layout (for 1024 rows) coincide, 1023 leaves the last row tile and block_sum's last trip ragged -- and {33, 1024} elsewhere; n_critics, lo and
+# sigma are spread so that each value meets each network, and both large batches at limits run two critics (the z dimension).
+EDGE_GRAD_CASES = [("limits", 1, 0.0, 0.2, 1), ("limits", 1, -1.0, 0.0, 33), ("limits", 2, -1.0, 0.0, 1023), ("limits", 2, 0.0, 0.2, 1024),
+                   ("tile", 2, -1.0, 0.2, 33), ("tile", 1, 0.0, 0.0, 1024), ("tile+1", 1, -1.0, 0.2, 33), ("tile+1", 2, 0.0, 0.0, 1024),
+                   ("tiny", 2, 0.0, 0.0, 33), ("tiny", 1, -1.0, 0.2, 1024)]
+# (net, (D, P), n_critics, lo, sigma, B) with a saturated actor
+# (the third has no noise: half of its a' elements are exactly +-1 by construction, whatever the draws)
+SATURATED_GRAD_CASES = [("64-64", (63, 20), 2, -1.0, 0.2, 100), ("limits", (192, 64), 2, 0.0, 0.2, 33), ("64-64", (63, 20), 1, 0.0, 0.0, 100)]
+# the networks of the refresh test off the handles' shapes: (tag, (D, h1, h2, P), precision, the kernel the plan gives).  The second shape is the
+# nearest one to 170-410-300-50 that plan_td3 accepts (h1 <= 400; the GPU test shows the refusal): 16-column tile counts 11 / 26 / 20 all the same.
+REFRESH_EDGE_CASES = [("limits", EDGE_NETS["limits"], "bf16", "ev2g_mlp3_any"), ("limits", EDGE_NETS["limits"], "fp32", "ev2g_mlp3_f32"),
+                      ("fixed", (170, 400, 310, 50), "bf16", "ev2g_mlp3_fixed<11,26,20>")]
+
+
+def edge_grad_case(tag, n_critics, lo, sigma, B):
+    return edge_case(tag, n_critics, B, lo, sigma, seed=7 + B, first_draw=1000)
+
+
+def saturated_grad_case(net, dp, n_critics, lo, sigma, B):
+    return make_case(*dp, net, n_critics, B, lo, sigma, seed=7 + B, first_draw=1000, saturate=True, live=True)
+
+
+def _hidden(net):
+    return NETS[net] if net in NETS else EDGE_NETS[net][1:3] if net in EDGE_NETS else tuple(net)
+
+
+def edge_case(tag, *args, **kw):
+    """make_case on a row of EDGE_NETS, with the live-gradient condition."""
+    D, _, _, P = EDGE_NETS[tag]
+    return make_case(D, P, tag, *args, live=True, **kw)
+
+
+def saturated_ports(P):
+    """every second port, and the sign of its shift: +, -, +, ..."""
+    ports = np.arange(0, P, 2)
+    return ports, np.where(np.arange(ports.size) % 2 == 0, 1.0, -1.0)
+
+
+def nonzero_grads(ref):
+    """every float64 reference gradient array of a case has a non-zero element (a dead ReLU in a narrow network makes whole arrays exactly 0, and
+    zero against zero proves nothing)"""
+    return all(np.any(g) for c in ref["critic_grads"] for g in c) and all(np.any(g) for g in ref["actor_grads"])
 
 
 def _min_preact(case, rows):
@@ -20,31 +73,53 @@ def _min_preact(case, rows):
     return np.min([np.minimum(np.abs(f.z1).min(1), np.abs(f.z2).min(1)) for f in fs], axis=0)
 
 
-def make_case(D, P, net="400-300", n_critics=2, B=37, lo=-1.0, sigma=0.2, seed=7, noise_seed=11, first_draw=0):
+def make_case(D, P, net="400-300", n_critics=2, B=37, lo=-1.0, sigma=0.2, seed=7, noise_seed=11, first_draw=0, saturate=False, live=False):
     """_draw_case(seed), asserting that fewer than a quarter of the rows needed a redraw.  With ONE row a quarter means none, which a given seed
     misses about one time in twenty: only then the first of ten fixed seeds (seed, seed + 1000, ...) that needs no redraw is taken, as the ReLU
     cases of tests/test_ppo_cpu.py take the first of ten seeds that fits.  A larger batch gets no second seed, so a redraw rate that drifted
-    upwards fails here.  case["seeds_skipped"] says how many seeds were passed over; the tests print it next to the redraw count."""
-    for i in range(10 if B == 1 else 1):
-        case = _draw_case(D, P, net, n_critics, B, lo, sigma, seed + 1000 * i, noise_seed, first_draw)
+    upwards fails here.  case["seeds_skipped"] says how many seeds were passed over; the tests print it next to the redraw count.
+
+    live (the EDGE_NETS and the saturated cases): every float64 reference gradient array must also have a non-zero element (nonzero_grads), and a
+    seed that misses that or the cap is passed over at any B, again among the ten fixed seeds.  The float64 reference is kept as case["ref64"].
+    saturate: see _draw_case; at least a quarter of the a' elements must be exactly +-1.  With noise that is the EXPECTATION -- half the ports
+    times the half of the draws that point outwards -- and it depends on (noise_seed, first_draw) alone, not on the seed: the cases' draws give
+    0.26, and other draws can miss it.  Without noise the share is a half by construction, and that is asserted."""
+    import torch
+    for i in range(10 if (B == 1 or live) else 1):
+        case = _draw_case(D, P, net, n_critics, B, lo, sigma, seed + 1000 * i, noise_seed, first_draw, saturate)
         case["seeds_skipped"] = i
-        if case["redrawn"] < B / 4.0:
+        ok = case["redrawn"] < B / 4.0
+        if live and ok:
+            case["ref64"] = torch_grads(case, torch.float64)
+            ok = nonzero_grads(case["ref64"])
+        if ok:
             break
     assert case["redrawn"] < B / 4.0, f"{case['redrawn']} of {B} rows needed a redraw"
+    if live:
+        assert nonzero_grads(case["ref64"]), "a reference gradient array is all zeros (dead ReLU)"
+    if saturate:
+        assert case["share_at_1"] >= (0.25 if sigma > 0.0 else 0.5), f"only {case['share_at_1']:.3f} of the a' elements are exactly +-1"
     return case
 
 
-def _draw_case(D, P, net, n_critics, B, lo, sigma, seed, noise_seed, first_draw):
+def _draw_case(D, P, net, n_critics, B, lo, sigma, seed, noise_seed, first_draw, saturate=False):
     """One batch and the networks of a learner: torch-style initial weights, observations in [0, 1], stored actions in [lo, 1], rewards of both
-    signs, `done` mixed, the smoothing noise's standard normals from the host twin.  Rows with a pre-activation inside KINK are redrawn."""
+    signs, `done` mixed, the smoothing noise's standard normals from the host twin.  Rows with a pre-activation inside KINK are redrawn.
+    saturate: the actor's output bias of every second port is moved by +12, -12, +12, ... BEFORE the redraws, so that |pre-tanh| >= 10 in
+    float64 on those ports for every row of obs and next_obs (asserted): tanh_back's 1 - t^2 at t = +-1 and the clamp a' in [-1, 1] are reached.
+    The band 3 .. 9, where the result depends on each tanhf's last bits, is left out on purpose.  case["share_at_1"]: the share of float32 a'
+    elements that are exactly +-1."""
     from ev2gym_amd.actor import init_mlp_weights
     from ev2gym_amd.engine import host_normal
     from ev2gym_amd.td3 import init_critic_weights
-    h1, h2 = NETS[net]
+    h1, h2 = _hidden(net)
     rng = np.random.default_rng(seed)
     case = dict(D=D, P=P, h=(h1, h2), n_critics=n_critics, B=B, lo=float(lo), sigma=float(sigma), clip=0.5, gamma=0.99, noise_seed=noise_seed,
                 first_draw=first_draw, actor=init_mlp_weights(D, P, seed, h1, h2),
                 critics=[init_critic_weights(D, P, seed + 1 + j, h1, h2) for j in range(n_critics)])
+    if saturate:
+        ports, sign = saturated_ports(P)
+        case["actor"][5][ports] += (SATURATED * sign).astype(np.float32)
     case["obs"] = rng.uniform(0.0, 1.0, (B, D)).astype(np.float32)
     case["actions"] = rng.uniform(lo, 1.0, (B, P)).astype(np.float32)
     case["reward"] = rng.normal(0.0, 1.0, B).astype(np.float32)
@@ -63,6 +138,17 @@ def _draw_case(D, P, net, n_critics, B, lo, sigma, seed, noise_seed, first_draw)
         case["actions"][bad] = rng.uniform(lo, 1.0, (bad.size, P)).astype(np.float32)
     assert _min_preact(case, np.arange(B)).min() >= KINK, "a row still sits on a ReLU kink"
     case["redrawn"] = int(redrawn.sum())
+    if saturate:
+        from ev2gym_amd.engine import host_td3_target
+        from ev2gym_amd.td3 import _f64, _forward
+        ports, _ = saturated_ports(P)
+        w = _f64(case["actor"])
+        for x in (case["obs"], case["next_obs"]):
+            f = _forward(w, x.astype(np.float64), True)
+            z3 = f.h2 @ w[4].T + w[5]
+            assert np.abs(z3[:, ports]).min() >= 10.0, "a saturated port's pre-tanh is inside 10"
+        a_next, _ = host_td3_target(np.tanh(z3).astype(np.float32), None, None, None, sigma, case["clip"], case["gamma"], noise_seed, first_draw)
+        case["share_at_1"] = float((np.abs(a_next) == 1.0).mean())
     return case
 
 
@@ -150,15 +236,86 @@ def torch_loop(case, batches, dtype, policy_delay=2, lr=1e-3, tau=0.005):
     return out
 
 
-def check_arrays(tag, got, ref, ref32, values=False):
-    """Lists of arrays under the idiom: prints every d32 and deviation, then asserts."""
+def check_arrays(tag, got, ref, ref32, values=False, plain32=None):
+    """Lists of arrays under the idiom: prints every d32 and deviation, then asserts.  plain32: a second float32 computation whose d32 is
+    printed next to the one that sets the tolerance (the saturated SAC cases, tests/sac_cases.torch_actor's `mixed`)."""
     fails = []
     for i, (g, r, r32) in enumerate(zip(got, ref, ref32)):
         g, r, r32 = np.asarray(g, np.float64).reshape(-1), np.asarray(r, np.float64).reshape(-1), np.asarray(r32, np.float64).reshape(-1)
         d32 = float(np.abs(r32 - r).max())
         tol = value_tol(r, d32) if values else grad_tol(r, d32)
         dev = np.abs(g - r)
-        _record(f"{tag}[{i}] d32 {d32:.3e} device {float(dev.max()):.3e} tol {float(np.max(tol)):.3e} scale {float(np.abs(r).max()):.3e}")
+        also = "" if plain32 is None else f" (plain float32 d32 {float(np.abs(np.asarray(plain32[i], np.float64).reshape(-1) - r).max()):.3e})"
+        _record(f"{tag}[{i}] d32 {d32:.3e}{also} device {float(dev.max()):.3e} tol {float(np.max(tol)):.3e} scale {float(np.abs(r).max()):.3e}")
         if not np.all(dev <= tol):
             fails.append((i, float(dev.max()), float(np.max(tol))))
     assert not fails, (tag, fails)
+
+
+# ---- the replay ring and its sampler (tests/test_td3_gpu.py and tests/test_sac_gpu.py) ----
+def snapshot(col, block):
+    """host copies of a ring block: (obs [T + 1, E, D], actions, reward, done)"""
+    return [a.to_host() for a in (col.obs[block], col.actions[block], col.reward[block], col.done[block])]
+
+
+def gather(blocks, idx, T):
+    """The rows of host copies of the listed blocks at idx [B, 3] (entry of the list, t, e)."""
+    bi, t, e = idx[:, 0], idx[:, 1], idx[:, 2]
+    pick = lambda k, tt: np.stack([blocks[b][k][x, y] for b, x, y in zip(bi, tt, e)])  # noqa: E731
+    return pick(0, t), pick(1, t), pick(2, t).astype(np.float32), pick(0, t + 1), pick(3, t)
+
+
+def check_sample(col, ring, host, B, seed, counters):
+    """ev2g_replay_sample on the device list `ring` for every counter: the indices are the host twin's, every row is the gather from `host` (the
+    listed blocks' host copies) bit for bit, s' of a last step is the block's row T.  Returns the indices."""
+    from ev2gym_amd.engine import host_replay_indices
+    from tests.test_onpolicy_gpu import _bits
+    eng, T, E, D, P = col.eng, col.T, col.E, col.D, col.P
+    out = [eng.empty((B, D), np.float32), eng.empty((B, P), np.float32), eng.empty((B,), np.float32), eng.empty((B, D), np.float32), eng.empty((B,), np.uint8)]
+    index = eng.empty((B, 3), np.int32)
+    seen = []
+    try:
+        for counter in counters:
+            eng.replay_sample(ring, T, E, D, P, B, seed, counter, *out, index)
+            idx = index.to_host()
+            assert np.array_equal(idx, host_replay_indices(B, len(ring), T, E, seed, counter))
+            assert idx[:, 0].min() == 0 and idx[:, 0].max() == len(ring) - 1 and idx[:, 1].max() == T - 1 and idx[:, 1].min() == 0
+            got = [o.to_host() for o in out]
+            for a, b in zip(got, gather(host, idx, T)):
+                assert np.array_equal(_bits(a), _bits(b))
+            last = idx[:, 1] == T - 1
+            assert last.any()
+            for r in np.nonzero(last)[0]:
+                assert np.array_equal(got[3][r], host[idx[r, 0]][0][T, idx[r, 2]])
+            seen.append(idx)
+    finally:
+        for b in out + [index]:
+            b.free()
+    return seen
+
+
+def check_ring_wrap(col, learner, B=256):
+    """Four episodes into a ring of capacity 3: the head wraps, the complete blocks are [0, 2] -- not contiguous -- with episode 4 in block 0 over
+    episode 1 and episode 3 in block 2; block 1 holds the stale episode 2 under the next reset row and is never drawn.  The sampler, on exactly the
+    list train() builds, gathers from the snapshots of episodes 4 and 3 (the snapshots are taken as each block fills)."""
+    assert col.cap == 3
+    snaps = []
+    for ep in range(4):
+        b = col.collect_episode()
+        assert b == ep % 3
+        snaps.append(snapshot(col, b))
+    assert (col.head, col.filled) == (1, 2) and learner.complete_blocks() == [0, 2]
+    stale = snapshot(col, 1)
+    assert all(np.array_equal(a[1:] if i == 0 else a, b[1:] if i == 0 else b) for i, (a, b) in enumerate(zip(stale, snaps[1])))
+    # Episodes of different pool windows may coincide (a deterministic actor, observations that do not tell the windows apart), so the stale block
+    # is made unmistakable: everything in it but the next reset row becomes a value no episode holds.  A row drawn from block 1 cannot pass.
+    mark = np.float32(-12345.0)
+    assert not any(np.any(a == mark) for sn in snaps for a in sn[:3])
+    obs1 = stale[0].copy()
+    obs1[1:] = mark
+    col.obs[1].upload(obs1); col.actions[1].upload(np.full_like(stale[1], mark)); col.reward[1].upload(np.full_like(stale[2], mark))
+    same = [(i + 1, j + 1) for i in range(4) for j in range(i) if all(np.array_equal(snaps[i][k], snaps[j][k]) for k in range(3))]
+    print(f"ring wrap: episode pairs that coincide in observations, actions and rewards: {same}")
+    ring = [(col.obs[b], col.actions[b], col.reward[b], col.done[b]) for b in learner.complete_blocks()]
+    seen = check_sample(col, ring, [snaps[3], snaps[2]], B, learner.sample_seed, (0, 1))
+    assert not np.array_equal(seen[0], seen[1])

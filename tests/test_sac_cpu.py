@@ -8,7 +8,9 @@
   * torch's literal Normal(mu, sigma).log_prob(u) on a case without a column at -20 gives the same gradients: the reduced Gaussian term the twin
     uses is the same function, written so that it does not cancel;
   * tests/host/sac_check.cpp, a stand-alone C++17 program, plain and under -fsanitize=address,undefined;
-  * the host twins through the library and the Python-side refusals."""
+  * the host twins through the library and the Python-side refusals;
+  * the cases tests/test_sac_gpu.py runs off NETS (tests/sac_cases.EDGE_NETS, the saturated actors): the redraw cap, a non-zero element in every
+    float64 reference gradient array, and the mixed-precision yardstick of the saturated cases next to plain float32."""
 import math
 import os
 import shutil
@@ -200,3 +202,64 @@ def test_python_refusals():
         td3.make_learner("SAC", col)
     assert "ev2gym_amd.sac.SACLearner" in str(e.value)
     assert SACLearner.PRESET["lr"] == 3e-4 and SACLearner.PRESET["batch_size"] == 256 and SACLearner.PRESET["ent_coef"] == "auto"
+
+
+# ---- the cases of tests/test_sac_gpu.py off NETS: their conditions hold, without a GPU ----
+@pytest.mark.parametrize("tag,n_critics,lo,auto,B", sc.EDGE_GRAD_CASES)
+def test_edge_cases_keep_the_redraw_cap_and_live_gradients(tag, n_critics, lo, auto, B):
+    case = sc.edge_grad_case(tag, n_critics, lo, auto, B)
+    print(f"sac {tag} nc{n_critics} lo{lo:g} auto{int(auto)} B{B}: redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}")
+    assert (case["D"], *case["h"], case["P"]) == sc.EDGE_NETS[tag] and case["obs"].shape == (B, case["D"])
+    assert case["redrawn"] < B / 4.0 and case["seeds_skipped"] <= 1   # (no case needed more than its second seed)
+    assert sc.nonzero_grads(case["ref64"]) and len(case["ref64"]["critic_grads"]) == n_critics
+
+
+def test_edge_case_lists_cover_what_they_claim():
+    for tag in sc.EDGE_NETS:
+        rows = [c for c in sc.EDGE_GRAD_CASES if c[0] == tag]
+        assert {c[4] for c in rows} == ({1, 37, 1023, 1024} if tag == "limits" else {37, 1024}), tag
+        assert {c[1] for c in rows} == {1, 2} and {c[2] for c in rows} == {-1.0, 0.0} and {c[3] for c in rows} == {True, False}, tag
+    lane0 = lambda P: len(range(0, P, 8))   # noqa: E731  (ports of head lane 0)
+    lane1 = lambda P: len(range(1, P, 8))   # noqa: E731
+    P = {tag: shape[3] for tag, shape in sc.EDGE_NETS.items()}
+    assert sc.EDGE_NETS["limits"] == (192, 256, 256, 64) and lane0(64) == 8 and P["limits"] % 32 == 0
+    assert (lane0(P["lanes"]), lane1(P["lanes"])) == (1, 1) and (lane0(P["lanes+1"]), lane1(P["lanes+1"])) == (2, 1)
+    assert (lane0(P["eighth"]), lane1(P["eighth"])) == (8, 7) and (lane0(P["tiny"]), lane1(P["tiny"])) == (1, 0)
+    for tag, lo in sc.ACT_EDGE_CASES:   # the collection actor's cases build (the clamp columns where there are three ports)
+        D, _, _, ports = sc.EDGE_NETS[tag]
+        case = sc.act_case(tag, (D, ports), lo)
+        print(f"sac act {tag}: redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}")
+        assert case["clamp"] == (ports >= 3)
+
+
+@pytest.mark.parametrize("net,dp,n_critics,lo,auto,B", sc.SATURATED_GRAD_CASES)
+def test_saturated_cases_and_the_mixed_precision_yardstick(net, dp, n_critics, lo, auto, B):
+    """With every second port's mu at +-12 plain float32 torch forms 1 - a^2 in float32 and is a poor yardstick; the mixed reference (float32
+    networks, float64 head: csrc/ev2g_sac.h's own split) stays near float32's rounding.  Both d32 are printed; under the mixed one a device that
+    returned zeros would fail on every array."""
+    import torch
+    case = sc.saturated_grad_case(net, dp, n_critics, lo, auto, B)
+    print(f"sac saturated {net} B{B}: redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}, share of a at +-1 {case['share_at_1']:.4f}")
+    assert case["share_at_1"] >= 0.25
+    ref, plain, mixed = case["ref64"], sc.torch_grads(case, torch.float32), sc.torch_grads(case, torch.float32, mixed=True)
+    for name in ("log_pi", "log_pi_next", "y"):
+        dp32, dmx = np.abs(plain[name] - ref[name]).max(), np.abs(mixed[name] - ref[name]).max()
+        print(f"{name}: scale {np.abs(ref[name]).max():.3e} plain d32 {dp32:.3e} mixed d32 {dmx:.3e}")
+        assert dmx <= 64 * 2.0 ** -23 * np.abs(ref[name]).max()   # a float32 rounding of a sum of P terms, not a float32 1 - a^2
+    assert np.abs(plain["log_pi"] - ref["log_pi"]).max() > 100 * np.abs(mixed["log_pi"] - ref["log_pi"]).max()
+    for i, (r, p, m) in enumerate(zip(ref["actor_grads"], plain["actor_grads"], mixed["actor_grads"])):
+        scale, dp32, dmx = np.abs(r).max(), np.abs(p - r).max(), np.abs(m - r).max()
+        tol = sc.grad_tol(r, dmx)
+        print(f"actor grad {i}: scale {scale:.3e} plain d32 {dp32:.3e} mixed d32 {dmx:.3e} tol {tol:.3e}")
+        assert scale > 0.0 and tol < 0.05 * scale, i
+    for lo_act in (0.0, -1.0):   # the twin test's actor builds too
+        act = sc.act_case("64-64", (63, 20), lo_act, saturate=True)
+        print(f"sac act saturated lo{lo_act:g}: redrawn {act['redrawn']}, share of a at +-1 {act['share_at_1']:.4f}")
+
+
+def test_update_cases_off_nets_keep_the_cap():
+    big = sc.edge_case("limits", 2, 1024, 0.0, 0.7, True, seed=21)
+    print(f"sac limits B1024 seed 21: redrawn {big['redrawn']}, seeds skipped {big['seeds_skipped']}")
+    assert big["redrawn"] < 256 and big["seeds_skipped"] == 0   # the GPU test's own case: no seed was passed over
+    plain = sc.make_case(192, 64, "limits", 2, 1024, 0.0, 0.7, True, seed=21)   # (as the reproducibility test builds it)
+    assert all(np.array_equal(big[k], plain[k]) for k in ("obs", "actions", "reward", "next_obs", "done", "eps", "eps_next"))

@@ -6,7 +6,11 @@ s = max(1, |y|) for values and the array's largest reference magnitude for gradi
 asserted.  Everything else is bit for bit.
 
 The case builder (tests/sac_cases.py) redraws any row with a backpropagated ReLU pre-activation, or the two critics' gap on (s, a_pi), below
-1e-5, and asserts that fewer than a quarter of the rows needed it."""
+1e-5, and asserts that fewer than a quarter of the rows needed it.
+
+Off NETS (tests/sac_cases.EDGE_NETS): the plan's limits and the head's lane edges (one port per lane, a second and an eighth port on lane 0
+alone, seven idle lanes) at batches up to 1024; a saturated actor under the mixed-precision yardstick, and the collection actor against its host
+twin to one float32 ulp; the config's edges; the ring once it has wrapped.  tests/test_sac_cpu.py proves those cases' conditions without a GPU."""
 import math
 
 import numpy as np
@@ -99,14 +103,12 @@ def _flat(actor, critics):
 
 
 # ---- 1. one staged step against the float64 reference ----
-@pytest.mark.parametrize("net,dp,n_critics,lo,auto,clamp,B", _grad_cases())
-def test_gradients_y_log_pi_and_losses_against_float64(engines, net, dp, n_critics, lo, auto, clamp, B):  # noqa: F811
-    import torch
-    D, P = dp
-    case = sc.make_case(D, P, net, n_critics, B, lo, 0.7, auto, clamp, seed=7 + B, first_draw=1000)
-    ref, ref32 = sc.torch_grads(case, torch.float64), sc.torch_grads(case, torch.float32)
-    tag = f"sac {net} D{D} P{P} nc{n_critics} lo{lo:g} auto{int(auto)} clamp{int(clamp)} B{B} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']})"
-    d = _Dev(engines["pst"], case)
+def _staged_step(eng, case, ref, ref32, tag, plain32=None):
+    """The critics' stage, then the actor's, on `case`: y, both log pi, the losses and every gradient under the idiom, d32 taken from ref32
+    (plain32: a second float32 computation whose d32 is printed next to it).  Returns the actor's gradient."""
+    n_critics, B, auto, clamp = case["n_critics"], case["B"], case["auto"], case["clamp"]
+    also = lambda *names: None if plain32 is None else [plain32[n] for n in names]   # noqa: E731
+    d = _Dev(eng, case)
     try:
         d.eng.sac_critic_grad(d.s, *d.bufs, B, d.losses)
         y, lp2 = d.eng.sac_get_y(d.s, B)
@@ -121,27 +123,64 @@ def test_gradients_y_log_pi_and_losses_against_float64(engines, net, dp, n_criti
             assert np.array_equal(_bits(a), _bits(b))
         assert abs(float(alpha) - math.exp(case["log_ent_coef"])) <= 2.0 ** -23   # (exp of the float32 log_ent_coef, rounded once; alpha 0.7)
         sc.check_arrays(tag + " y, log pi', log pi", [y, lp2, lp], [ref["y"], ref["log_pi_next"], ref["log_pi"]], [ref32["y"], ref32["log_pi_next"], ref32["log_pi"]],
-                        values=True)
-        sc.check_arrays(tag + " losses", [[closs], [aloss]], [[ref["critic_loss"]], [ref["actor_loss"]]], [[ref32["critic_loss"]], [ref32["actor_loss"]]], values=True)
+                        values=True, plain32=also("y", "log_pi_next", "log_pi"))
+        sc.check_arrays(tag + " losses", [[closs], [aloss]], [[ref["critic_loss"]], [ref["actor_loss"]]], [[ref32["critic_loss"]], [ref32["actor_loss"]]], values=True,
+                        plain32=also("critic_loss", "actor_loss"))
         if auto:
             sc.check_arrays(tag + " ent_coef loss, grad", [[eloss], [ga]], [[ref["ent_coef_loss"]], [ref["ent_coef_grad"]]],
-                            [[ref32["ent_coef_loss"]], [ref32["ent_coef_grad"]]], values=True)
+                            [[ref32["ent_coef_loss"]], [ref32["ent_coef_grad"]]], values=True, plain32=also("ent_coef_loss", "ent_coef_grad"))
         else:
             assert eloss == 0.0 and ga == 0.0
         for j in range(n_critics):
-            sc.check_arrays(tag + f" critic {j} grad", cg[j], ref["critic_grads"][j], ref32["critic_grads"][j])
-        sc.check_arrays(tag + " actor grad", ag, ref["actor_grads"], ref32["actor_grads"])
+            sc.check_arrays(tag + f" critic {j} grad", cg[j], ref["critic_grads"][j], ref32["critic_grads"][j], plain32=plain32 and plain32["critic_grads"][j])
+        sc.check_arrays(tag + " actor grad", ag, ref["actor_grads"], ref32["actor_grads"], plain32=plain32 and plain32["actor_grads"])
         if clamp:   # the two columns clamped for every row: exactly 0.0, not small
             assert np.array_equal(_bits(ag[6][:2]), _bits(np.zeros_like(ag[6][:2]))) and np.array_equal(_bits(ag[7][:2]), _bits(np.zeros(2, np.float32)))
             assert np.abs(ag[7][2:]).min() > 0.0
+        return ag
     finally:
         d.close()
 
 
+@pytest.mark.parametrize("net,dp,n_critics,lo,auto,clamp,B", _grad_cases())
+def test_gradients_y_log_pi_and_losses_against_float64(engines, net, dp, n_critics, lo, auto, clamp, B):  # noqa: F811
+    import torch
+    D, P = dp
+    case = sc.make_case(D, P, net, n_critics, B, lo, 0.7, auto, clamp, seed=7 + B, first_draw=1000)
+    ref, ref32 = sc.torch_grads(case, torch.float64), sc.torch_grads(case, torch.float32)
+    tag = f"sac {net} D{D} P{P} nc{n_critics} lo{lo:g} auto{int(auto)} clamp{int(clamp)} B{B} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']})"
+    _staged_step(engines["pst"], case, ref, ref32, tag)
+
+
+# The plan's limits and the head's lane edges (tests/sac_cases.EDGE_NETS; tests/test_sac_cpu.py pins the cases' conditions).
+@pytest.mark.parametrize("tag,n_critics,lo,auto,B", sc.EDGE_GRAD_CASES)
+def test_gradients_at_the_plans_limits_and_lane_edges(engines, tag, n_critics, lo, auto, B):  # noqa: F811
+    import torch
+    case = sc.edge_grad_case(tag, n_critics, lo, auto, B)
+    name = f"sac edge {tag} nc{n_critics} lo{lo:g} auto{int(auto)} B{B} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']})"
+    _staged_step(engines["pst"], case, case["ref64"], sc.torch_grads(case, torch.float32), name)
+
+
+# A saturated actor: mu of every second port beyond +-10 for every row, so a = +-1 to float32 and log(1 - a^2 + 1e-6) sits at its floor.  The device
+# computes the head in float64 from float32 mu / log_std (csrc/ev2g_sac.h), plain float32 torch forms 1 - a^2 in float32: its own error (1e-2 of
+# log pi, 1 % of the actor's gradients) would make 4 d32 accept a device that returned zeros.  d32 is therefore taken from the MIXED reference --
+# float32 networks, float64 head, the header's own split (sc.torch_actor) -- and the plain d32 is printed next to it.
+@pytest.mark.parametrize("net,dp,n_critics,lo,auto,B", sc.SATURATED_GRAD_CASES)
+def test_gradients_with_a_saturated_actor_against_the_mixed_reference(engines, net, dp, n_critics, lo, auto, B):  # noqa: F811
+    import torch
+    case = sc.saturated_grad_case(net, dp, n_critics, lo, auto, B)
+    name = (f"sac saturated {net} nc{n_critics} lo{lo:g} auto{int(auto)} B{B} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}, "
+            f"a at +-1 {case['share_at_1']:.4f})")
+    mixed, plain = sc.torch_grads(case, torch.float32, mixed=True), sc.torch_grads(case, torch.float32)
+    ag = _staged_step(engines["pst"], case, case["ref64"], mixed, name, plain32=plain)
+    assert all(np.isfinite(g).all() and np.any(g) for g in ag)
+
+
 # ---- 2. the same update on two fresh learners gives the same bits ----
-@pytest.mark.parametrize("net,B", [("256-256", 37), ("33-17", 257)])
+@pytest.mark.parametrize("net,B", [("256-256", 37), ("33-17", 257), ("limits", 1024)])
 def test_an_update_is_reproducible_bit_for_bit(engines, net, B):  # noqa: F811
-    case = sc.make_case(63, 20, net, 2, B, 0.0, 0.7, True, seed=21)
+    D, P = sc.EDGE_NETS[net][0::3] if net in sc.EDGE_NETS else (63, 20)
+    case = sc.make_case(D, P, net, 2, B, 0.0, 0.7, True, seed=21)
     got = []
     for _ in range(2):
         d = _Dev(engines["pst"], case)
@@ -229,12 +268,13 @@ def test_three_updates_adam_polyak_counters_and_repacked_images(engines, net, n_
 
 
 # ---- 4. the collection actor ----
-@pytest.mark.parametrize("net,dp,lo", [("256-256", (162, 50), 0.0), ("64-64", (63, 20), -1.0), ("33-17", (11, 5), 0.0)])
+@pytest.mark.parametrize("net,dp,lo", [("256-256", (162, 50), 0.0), ("64-64", (63, 20), -1.0), ("33-17", (11, 5), 0.0)] +
+                         [(tag, sc.EDGE_NETS[tag][0::3], lo) for tag, lo in sc.ACT_EDGE_CASES])
 def test_act_against_float64_draw_indices_and_row_independence(engines, net, dp, lo):  # noqa: F811
     import torch
     from ev2gym_amd.engine import host_normal
     D, P = dp
-    case = sc.make_case(D, P, net, 1, 70, lo, 0.7, True, clamp=True, seed=3)
+    case = sc.make_case(D, P, net, 1, 70, lo, 0.7, True, clamp=P >= 3, seed=3)
     x = np.random.default_rng(8).uniform(0.0, 1.0, (70, D)).astype(np.float32)
     d = _Dev(engines["ppl"], case)
     try:
@@ -261,6 +301,111 @@ def test_act_against_float64_draw_indices_and_row_independence(engines, net, dp,
         for f, s in zip(det_full, d.act(x[33:66], True)):
             assert np.array_equal(_bits(f[33:66]), _bits(s))
         assert not np.array_equal(det_full[0], full[0])
+    finally:
+        d.close()
+
+
+# The collection actor against its host twin on a saturated actor (every second port's mu beyond +-10; log_std column 0 at the upper clamp, column 1
+# at the lower).  host_sac_head is applied to THE DEVICE'S OWN mu / log_std and host_normal's eps: both sides evaluate one float64 expression on
+# identical float32 inputs and round once, and differ only by the double tanh / exp / log of two libraries.  1 - t^2 against 1e-6 amplifies that to
+# about 4e-10 relative, so a result can only move across a float32 rounding boundary: 1 float32 ulp of the twin's value (np.spacing), for the tanh
+# action -- the env action of lo 0 is held to the unscaled neighbours of the twin's tanh action -- and for log pi.  The butterfly's join order is
+# part of the twin.  Where |u| >= 10 in float64 the action is exactly lo or 1: on every saturated port of the deterministic launch.  In the
+# sampling launch the noise pulls some elements back, and those are left to the ulp bound: port 0 carries the upper clamp's sigma e^2 and is
+# set aside; on the others sigma is about 1, u stays beyond 10 unless eps points inwards by more than about 2 (one draw in forty), and the
+# float64 forward of these very inputs gives 0.976 -- at least 0.95 of them must be that deep.
+@pytest.mark.parametrize("lo", [0.0, -1.0])
+def test_act_on_a_saturated_actor_against_the_host_twin(engines, lo):  # noqa: F811
+    from ev2gym_amd.engine import host_normal, host_sac_head
+    from ev2gym_amd.sac import unscale_action
+    from tests.test_ppo_cpu import _record
+    D, P, rows = 63, 20, 70
+    case = sc.act_case("64-64", (D, P), lo, saturate=True)
+    x = np.random.default_rng(8).uniform(0.0, 1.0, (rows, D)).astype(np.float32)
+    ports, sign = sc.saturated_ports(P)
+    d = _Dev(engines["ppl"], case)
+    try:
+        for det in (True, False):
+            d.eng.sac_act_seed(d.s, 19, 0)
+            act, mu, ls, lp = d.act(x, det)
+            eps = np.zeros((rows, P), np.float32) if det else host_normal(rows * P, 19, 0).reshape(rows, P)
+            a, a_env, lp_twin = host_sac_head(mu, ls, eps, lo=lo)
+            assert all(np.isfinite(o).all() for o in (act, mu, ls, lp))
+            below, above = (unscale_action(np.nextafter(a, np.float32(s)), lo).astype(np.float32) for s in (-2.0, 2.0))
+            off_a, off_lp = float((act != a_env).mean()), float((lp != lp_twin).mean())
+            dev_lp = np.abs(lp.astype(np.float64) - lp_twin)
+            _record(f"sac act twin lo{lo:g} det{int(det)}: actions off the twin's {off_a:.4f} of {act.size}, log pi off {off_lp:.4f} of {lp.size}, "
+                    f"largest log pi deviation {dev_lp.max():.3e} against an ulp of {np.spacing(np.abs(lp_twin)).min():.3e} .. {np.spacing(np.abs(lp_twin)).max():.3e}")
+            assert ((act >= below) & (act <= above)).all()
+            assert (dev_lp <= np.spacing(np.abs(lp_twin))).all()
+            u = mu.astype(np.float64) + np.exp(np.clip(ls.astype(np.float64), -20.0, 2.0)) * eps
+            assert np.abs(mu[:, ports]).min() >= 10.0
+            deep = np.abs(u[:, ports]) >= 10.0
+            assert deep.all() if det else deep[:, 1:].mean() >= 0.95
+            want = np.where(np.sign(u[:, ports]) > 0, np.float32(1.0), np.float32(lo))
+            assert np.array_equal(act[:, ports][deep], want[deep])
+            assert act.min() >= lo and act.max() <= 1.0
+    finally:
+        d.close()
+
+
+# ---- 5b. config edges the checks accept: target_update_interval 3 with tau 1, a fixed target entropy ----
+def test_config_edges_interval_3_tau_1(engines):  # noqa: F811
+    """Three updates on 33-17: the targets stay through updates 1 and 2 and EQUAL the critics' masters bit for bit after the third
+    (target * 0 + 1 * param with finite weights); the loop under the idiom."""
+    import torch
+    D, P, B = 63, 20, 37
+    case = sc.make_case(D, P, "33-17", 2, 3 * B, -1.0, 0.7, True, seed=5)
+    batches = sc.loop_batches(case, 3, B)
+    ref, ref32 = sc.torch_loop(case, batches, torch.float64, 3, tau=1.0), sc.torch_loop(case, batches, torch.float32, 3, tau=1.0)
+    d = _Dev(engines["pst"], case, rows=batches[0][0], target_update_interval=3, tau=1.0)
+    try:
+        targets = _flat([], d.targets())
+        for k in range(3):
+            d.load(batches[k][0])
+            losses = d.update()
+            new, new_t = _flat(*d.weights()), _flat([], d.targets())
+            if k == 2:
+                for i, (t_new, t_old, p) in enumerate(zip(new_t, targets, new[8:])):
+                    assert np.array_equal(_bits(t_new), _bits(p)) and not np.array_equal(t_new, t_old), i
+            else:
+                for a, b in zip(new_t, targets):
+                    assert np.array_equal(_bits(a), _bits(b))
+            assert d.eng.sac_counters(d.s) == (k + 1, (k + 1) // 3, 2 * (k + 1) * B * P, 0)
+            tag = f"sac config edges tui3 tau1 step {k}"
+            r, r32 = ref[k], ref32[k]
+            sc.check_arrays(tag + " losses", [[x] for x in losses], [[r[n]] for n in ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef")],
+                            [[r32[n]] for n in ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef")], values=True)
+            sc.check_arrays(tag + " actor", new[:8], r["actor"], r32["actor"], values=True)
+            for j in range(2):
+                sc.check_arrays(tag + f" critic {j}", new[8 + 6 * j:14 + 6 * j], r["critics"][j], r32["critics"][j], values=True)
+                sc.check_arrays(tag + f" critic_target {j}", new_t[6 * j:6 + 6 * j], r["critics_target"][j], r32["critics_target"][j], values=True)
+    finally:
+        d.close()
+
+
+def test_config_edges_a_fixed_target_entropy(engines):  # noqa: F811
+    """target_entropy_auto 0 with target_entropy -3.5 (auto would be -P = -20): two updates against the loop given that entropy."""
+    import torch
+    D, P, B = 63, 20, 37
+    case = sc.make_case(D, P, "33-17", 2, 2 * B, 0.0, 0.7, True, seed=6)
+    case["target_entropy"] = -3.5
+    batches = sc.loop_batches(case, 2, B)
+    ref, ref32 = sc.torch_loop(case, batches, torch.float64), sc.torch_loop(case, batches, torch.float32)
+    auto_ref = sc.torch_loop(dict(case, target_entropy=-float(P)), batches, torch.float64)
+    d = _Dev(engines["pst"], case, rows=batches[0][0], target_entropy_auto=0, target_entropy=-3.5)
+    try:
+        for k in range(2):
+            d.load(batches[k][0])
+            losses = d.update()
+            ent = d.eng.sac_get_ent_coef(d.s)
+            tag = f"sac config edges target_entropy -3.5 step {k}"
+            r, r32 = ref[k], ref32[k]
+            assert abs(r["ent_coef_loss"] - auto_ref[k]["ent_coef_loss"]) > 1.0   # (the entropy in use is visible in the loss)
+            sc.check_arrays(tag + " losses", [[x] for x in losses], [[r[n]] for n in ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef")],
+                            [[r32[n]] for n in ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef")], values=True)
+            sc.check_arrays(tag + " log_ent_coef", [ent[:1]], [[r["log_ent_coef"]]], [[r32["log_ent_coef"]]], values=True)
+            sc.check_arrays(tag + " actor", _flat(*d.weights())[:8], r["actor"], r32["actor"], values=True)
     finally:
         d.close()
 
@@ -361,6 +506,20 @@ def test_learn_end_to_end(ent_coef):
             col.close(); learner.close(); eng.close(); col.close()
         else:
             eng.close(); learner.close(); col.close()
+
+
+def test_the_ring_wraps_and_the_sampler_reads_the_modular_block_list():
+    from ev2gym_amd.sac import SACLearner
+    eng = _gen_engine("pst", pool=4)
+    col = _collector(eng, seed=4)
+    learner = SACLearner(col, seed=3, batch_size=64)
+    try:
+        sc.check_ring_wrap(col, learner)
+        out = learner.train(2)
+        assert all(np.isfinite(out[k]) for k in ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef")) and out["n_updates"] == 2
+        assert learner.counters() == (2, 2, 2 * 2 * 64 * col.P, 4 * col.T) and learner.sample_counter == 2 and col.episodes == 4
+    finally:
+        learner.close(); col.close(); eng.close()
 
 
 def test_refusals_through_the_abi(engines):  # noqa: F811

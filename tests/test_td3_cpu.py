@@ -7,7 +7,9 @@
     reproduces pack_mlp's images bit for bit and touches no padding word; the config and shape refusals; the host twins against plain
     restatements;
   * `ev2g_host_replay_indices`: within bounds, a pure function of (seed, counter, row), different for different counters;
-  * the host twins of the target and of Polyak through the library, and the Python-side refusals."""
+  * the host twins of the target and of Polyak through the library, and the Python-side refusals;
+  * the cases tests/test_td3_gpu.py runs off the handles' shapes (tests/td3_cases.EDGE_NETS, the saturated actors): the redraw cap, a non-zero
+    element in every float64 reference gradient array, |pre-tanh| >= 10 on the saturated ports, tolerances that a device of zeros would miss."""
 import os
 import shutil
 import subprocess
@@ -166,3 +168,78 @@ def test_python_refusals():
         with pytest.raises(ValueError, match="SAC / TQC"):
             make_learner(algo, col)
     assert DDPGLearner.PRESET["n_critics"] == 1 and DDPGLearner.PRESET["batch_size"] == 100 and TD3Learner.PRESET["batch_size"] == 256
+
+
+# ---- the cases of tests/test_td3_gpu.py off the handles' shapes: their conditions hold, without a GPU ----
+def _tolerances_exclude_zeros(tag, ref, ref32):
+    """Under the idiom a device that returned zeros would fail on every gradient array: 4 d32 + 4 * 2^-23 * s stays far below s."""
+    for name, r, r32 in [(f"critic {j} grad {i}", g, ref32["critic_grads"][j][i]) for j, c in enumerate(ref["critic_grads"]) for i, g in enumerate(c)] + \
+                        [(f"actor grad {i}", g, ref32["actor_grads"][i]) for i, g in enumerate(ref["actor_grads"])]:
+        scale, d32 = float(np.abs(r).max()), float(np.abs(r32 - r).max())
+        tol = tc.grad_tol(r, d32)
+        print(f"{tag} {name}: scale {scale:.3e} d32 {d32:.3e} tol {tol:.3e}")
+        assert scale > 0.0 and tol < 0.05 * scale, (tag, name, scale, tol)
+
+
+@pytest.mark.parametrize("tag,n_critics,lo,sigma,B", tc.EDGE_GRAD_CASES)
+def test_edge_cases_keep_the_redraw_cap_and_live_gradients(tag, n_critics, lo, sigma, B):
+    case = tc.edge_grad_case(tag, n_critics, lo, sigma, B)
+    print(f"td3 {tag} nc{n_critics} lo{lo:g} sigma{sigma:g} B{B}: redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}")
+    assert (case["D"], *case["h"], case["P"]) == tc.EDGE_NETS[tag] and case["obs"].shape == (B, case["D"])
+    assert case["redrawn"] < B / 4.0 and case["seeds_skipped"] <= 1   # (no case needed more than its second seed)
+    assert tc.nonzero_grads(case["ref64"])
+    assert len(case["ref64"]["critic_grads"]) == n_critics and (case["normals"] is not None) == (sigma > 0.0)
+
+
+def test_edge_case_lists_cover_what_they_claim():
+    for tag in tc.EDGE_NETS:
+        rows = [c for c in tc.EDGE_GRAD_CASES if c[0] == tag]
+        assert {c[4] for c in rows} == ({1, 33, 1023, 1024} if tag == "limits" else {33, 1024}), tag
+        assert {c[1] for c in rows} == {1, 2} and {c[2] for c in rows} == {-1.0, 0.0} and {c[3] for c in rows} == {0.2, 0.0}, tag   # each value meets each network
+    assert all(c[1] == 2 for c in tc.EDGE_GRAD_CASES if c[0] == "limits" and c[4] >= 1023)
+    D, h1, h2, P = tc.EDGE_NETS["limits"]
+    assert (D, h1, h2, P) == (192, 400, 400, 64) and all(x % 16 == 0 for x in (D, h1, h2, P, D + P))      # no ragged tile
+    assert all(x == 16 for x in tc.EDGE_NETS["tile"]) and all(x % 16 == 1 for x in tc.EDGE_NETS["tile+1"])
+    assert tc.EDGE_NETS["tiny"] == (1, 5, 2, 1)
+
+
+@pytest.mark.parametrize("net,dp,n_critics,lo,sigma,B", tc.SATURATED_GRAD_CASES)
+def test_saturated_cases_reach_the_clamp_and_keep_their_tolerances(net, dp, n_critics, lo, sigma, B):
+    """The builder asserts |pre-tanh| >= 10 in float64 on every second port, for every row of obs and next_obs, and that a quarter of the a'
+    elements are exactly +-1.  Here also: float32 torch has the saturated ports' W3 rows and b3 entries at exactly 0, and the idiom's tolerances
+    stay non-degenerate."""
+    import torch
+    case = tc.saturated_grad_case(net, dp, n_critics, lo, sigma, B)
+    print(f"td3 saturated {net} B{B}: redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}, share of a' at +-1 {case['share_at_1']:.4f}")
+    assert case["share_at_1"] >= (0.25 if sigma > 0.0 else 0.5)
+    ref32 = tc.torch_grads(case, torch.float32)
+    ports, _ = tc.saturated_ports(dp[1])
+    live = np.setdiff1d(np.arange(dp[1]), ports)
+    assert not ref32["actor_grads"][4][ports].any() and not ref32["actor_grads"][5][ports].any()
+    assert np.abs(ref32["actor_grads"][4][live]).max(axis=1).min() > 0.0 and np.abs(ref32["actor_grads"][5][live]).min() > 0.0
+    _tolerances_exclude_zeros(f"td3 saturated {net} B{B}", case["ref64"], ref32)
+
+
+def test_update_cases_off_the_handles_shapes_have_live_gradients_on_every_step():
+    """tiny at B 33 over three updates (test_three_updates_adam_polyak_and_order): every critic array on every step and every actor array on the
+    second have a non-zero gradient in float64; limits at B 1024 (the reproducibility test) keeps the cap."""
+    from ev2gym_amd.engine import host_normal
+    from ev2gym_amd.td3 import td3_state, td3_update_numpy
+    case = tc.edge_case("tiny", 2, 99, -1.0, 0.2, seed=5)
+    print(f"td3 tiny loop: redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}")
+    st = td3_state(case["actor"], case["critics"])
+    for k in range(3):
+        rows = np.arange(k * 33, (k + 1) * 33)
+        out = td3_update_numpy(st, case["obs"][rows], case["actions"][rows], case["reward"][rows], case["next_obs"][rows], case["done"][rows],
+                               host_normal(33, 11, k * 33).reshape(33, 1), -1.0, policy_delay=2)
+        assert all(np.any(g) for c in out.critic_grads for g in c), k
+        assert (out.actor_grads is not None) == (k == 1) and (k != 1 or all(np.any(g) for g in out.actor_grads))
+    big = tc.edge_case("limits", 2, 1024, 0.0, 0.2, seed=21)
+    print(f"td3 limits B1024 seed 21: redrawn {big['redrawn']}, seeds skipped {big['seeds_skipped']}")
+    assert big["seeds_skipped"] == 0 and case["seeds_skipped"] == 0   # the GPU tests' own cases: no seed was passed over
+    plain = tc.make_case(192, 64, "limits", 2, 1024, 0.0, 0.2, seed=21)   # (as the reproducibility test builds it)
+    assert all(np.array_equal(big[k], plain[k]) for k in ("obs", "actions", "reward", "next_obs", "done", "normals"))
+    for tag, shape, _, _ in tc.REFRESH_EDGE_CASES:
+        c = tc.make_case(shape[0], shape[3], shape[1:3], 2, 64, 0.0, 0.2, seed=9, live=True)
+        print(f"td3 refresh {tag}: redrawn {c['redrawn']}, seeds skipped {c['seeds_skipped']}")
+        assert c["seeds_skipped"] == 0 and c["redrawn"] < 16 and tc.nonzero_grads(c["ref64"]) and (c["D"], *c["h"], c["P"]) == tuple(shape)

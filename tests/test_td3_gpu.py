@@ -6,7 +6,11 @@ s = max(1, |y|) for values and the array's largest reference magnitude for gradi
 asserted and appended to the file EV2G_PPO_RECORD names.  Everything else is bit for bit.
 
 ReLU's derivative is discontinuous, so the case builder (tests/td3_cases.py) redraws any row whose smallest float64 |pre-activation| over the
-backpropagated ReLU layers is below 1e-5, and asserts that fewer than a quarter of the rows needed it."""
+backpropagated ReLU layers is below 1e-5, and asserts that fewer than a quarter of the rows needed it.
+
+Off the handles' shapes (tests/td3_cases.EDGE_NETS): the plan's limits, one exact 16-wide tile, every dimension ragged by one, layers narrower
+than a tile, at batches up to the workspace's 1024 rows; a saturated actor; the config's edges; the ring once it has wrapped, a sampler wider
+than its 64 threads and its full 32-entry table.  tests/test_td3_cpu.py proves those cases' conditions without a GPU."""
 import numpy as np
 import pytest
 
@@ -87,15 +91,16 @@ def _flat(actor, critics):
     return list(actor) + [a for c in critics for a in c]
 
 
+def _dp(net):
+    """(D, P) of a case: a row of tc.EDGE_NETS brings its own, the others run at the "pst" handle's"""
+    return tc.EDGE_NETS[net][0::3] if net in tc.EDGE_NETS else SHAPES["pst"]
+
+
 # ---- 1. one staged step against the float64 reference ----
-@pytest.mark.parametrize("net,n_critics,lo,sigma,B,handle", _grad_cases())
-def test_gradients_y_and_losses_against_float64(engines, net, n_critics, lo, sigma, B, handle):  # noqa: F811
-    import torch
-    D, P = SHAPES[handle]
-    case = tc.make_case(D, P, net, n_critics, B, lo, sigma, seed=7 + B, first_draw=1000)
-    ref, ref32 = tc.torch_grads(case, torch.float64), tc.torch_grads(case, torch.float32)
-    tag = f"td3 {net} nc{n_critics} lo{lo:g} sigma{sigma:g} B{B} {handle} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']})"
-    d = _Dev(engines[handle], case)
+def _staged_step(eng, case, ref, ref32, tag):
+    """The critics' stage, then the actor's, on `case`: y, both losses and every gradient under the idiom.  Returns the actor's gradient."""
+    n_critics, sigma, B, P = case["n_critics"], case["sigma"], case["B"], case["P"]
+    d = _Dev(eng, case)
     try:
         d.eng.td3_critic_grad(d.t, *d.bufs, B, d.losses)
         y = d.eng.td3_get_y(d.t, B)
@@ -112,17 +117,54 @@ def test_gradients_y_and_losses_against_float64(engines, net, n_critics, lo, sig
         for j in range(n_critics):
             tc.check_arrays(tag + f" critic {j} grad", cg[j], ref["critic_grads"][j], ref32["critic_grads"][j])
         tc.check_arrays(tag + " actor grad", ag, ref["actor_grads"], ref32["actor_grads"])
+        return ag
     finally:
         d.close()
+
+
+@pytest.mark.parametrize("net,n_critics,lo,sigma,B,handle", _grad_cases())
+def test_gradients_y_and_losses_against_float64(engines, net, n_critics, lo, sigma, B, handle):  # noqa: F811
+    import torch
+    D, P = SHAPES[handle]
+    case = tc.make_case(D, P, net, n_critics, B, lo, sigma, seed=7 + B, first_draw=1000)
+    ref, ref32 = tc.torch_grads(case, torch.float64), tc.torch_grads(case, torch.float32)
+    tag = f"td3 {net} nc{n_critics} lo{lo:g} sigma{sigma:g} B{B} {handle} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']})"
+    _staged_step(engines[handle], case, ref, ref32, tag)
+
+
+# The plan's limits and the product kernel's tile edges (tests/td3_cases.EDGE_NETS; tests/test_td3_cpu.py pins the cases' conditions).  A learner
+# binds to an eng.mlp_create policy of any shape, so the handle's own (D, P) does not matter.
+@pytest.mark.parametrize("tag,n_critics,lo,sigma,B", tc.EDGE_GRAD_CASES)
+def test_gradients_at_the_plans_limits_and_tile_edges(engines, tag, n_critics, lo, sigma, B):  # noqa: F811
+    import torch
+    case = tc.edge_grad_case(tag, n_critics, lo, sigma, B)
+    name = f"td3 edge {tag} nc{n_critics} lo{lo:g} sigma{sigma:g} B{B} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']})"
+    _staged_step(engines["pst"], case, case["ref64"], tc.torch_grads(case, torch.float32), name)
+
+
+# A saturated actor: every second port's pre-tanh is beyond +-10 for every row (asserted by the builder in float64), where float32 tanh is exactly
+# +-1 in torch and on the device alike.  The target's clamp a' in [-1, 1] acts on a quarter of the elements, and tanh_back's 1 - t^2 is exactly 0
+# on the saturated ports: their rows of the actor's W3 gradient and their b3 entries are 0.0, not small.
+@pytest.mark.parametrize("net,dp,n_critics,lo,sigma,B", tc.SATURATED_GRAD_CASES)
+def test_gradients_with_a_saturated_actor(engines, net, dp, n_critics, lo, sigma, B):  # noqa: F811
+    import torch
+    case = tc.saturated_grad_case(net, dp, n_critics, lo, sigma, B)
+    name = (f"td3 saturated {net} nc{n_critics} lo{lo:g} sigma{sigma:g} B{B} (redrawn {case['redrawn']}, seeds skipped {case['seeds_skipped']}, "
+            f"a' at +-1 {case['share_at_1']:.4f})")
+    ag = _staged_step(engines["pst"], case, case["ref64"], tc.torch_grads(case, torch.float32), name)
+    ports, _ = tc.saturated_ports(dp[1])
+    live = np.setdiff1d(np.arange(dp[1]), ports)
+    assert np.array_equal(ag[4][ports], np.zeros_like(ag[4][ports])) and np.array_equal(ag[5][ports], np.zeros(ports.size, np.float32))
+    assert np.abs(ag[4][live]).max(axis=1).min() > 0.0 and np.abs(ag[5][live]).min() > 0.0
 
 
 # ---- 2. the same update twice gives the same bits ----
 # Gradients, masters and targets are read back and compared themselves.  The policy's packed images cannot be read through the ABI: they are
 # compared through a PROXY, ev2g_mlp_forward of 33 rows on the refreshed bf16 policy.  The images' contents are held to pack_mlp bit for bit by
 # tests/host/td3_check.cpp (every packing) and to a fresh policy object by test 4 below.
-@pytest.mark.parametrize("net,B", [("400-300", 100), ("33-17", 257)])
+@pytest.mark.parametrize("net,B", [("400-300", 100), ("33-17", 257), ("limits", 1024)])
 def test_an_update_is_reproducible_bit_for_bit(engines, net, B):  # noqa: F811
-    D, P = SHAPES["pst"]
+    D, P = _dp(net)
     case = tc.make_case(D, P, net, 2, B, 0.0, 0.2, seed=21)
     got = []
     for _ in range(2):
@@ -139,12 +181,12 @@ def test_an_update_is_reproducible_bit_for_bit(engines, net, B):  # noqa: F811
 
 
 # ---- 3. three updates with policy_delay 2: Adam and Polyak bit for bit by the host twins, the loop under the idiom ----
-@pytest.mark.parametrize("net,n_critics,B", [("64-64", 2, 33), ("400-300", 2, 100), ("33-17", 1, 31)])
+@pytest.mark.parametrize("net,n_critics,B", [("64-64", 2, 33), ("400-300", 2, 100), ("33-17", 1, 31), ("tiny", 2, 33)])
 def test_three_updates_adam_polyak_and_order(engines, net, n_critics, B):  # noqa: F811
     import torch
     from ev2gym_amd.engine import host_adam, host_normal, host_polyak
-    D, P = SHAPES["pst"]
-    case = tc.make_case(D, P, net, n_critics, 3 * B, -1.0, 0.2, seed=5)
+    D, P = _dp(net)
+    case = tc.make_case(D, P, net, n_critics, 3 * B, -1.0, 0.2, seed=5, live=net in tc.EDGE_NETS)   # (tiny: no dead ReLU, tests/test_td3_cpu.py)
     batches = [(np.arange(k * B, (k + 1) * B), host_normal(B * P, case["noise_seed"], k * B * P).reshape(B, P)) for k in range(3)]
     ref, ref32 = tc.torch_loop(case, batches, torch.float64), tc.torch_loop(case, batches, torch.float32)
     d = _Dev(engines["pst"], case, rows=batches[0][0], policy_delay=2)
@@ -241,6 +283,142 @@ def test_the_bound_policy_equals_a_fresh_one_from_the_masters(engines, precision
         d.close()
 
 
+# The refreshed actor off the handles' shapes: the plan's limits on the generic bf16 kernel and on the float32 one, and a shape the plan gives a
+# fixed-width kernel.  The forward comparison only: the collect half's shapes are the engine's.
+@pytest.mark.parametrize("tag,shape,precision,kernel", tc.REFRESH_EDGE_CASES)
+def test_the_bound_policy_off_the_handles_shapes_equals_a_fresh_one(engines, tag, shape, precision, kernel):  # noqa: F811
+    from ev2gym_amd import _abi
+    from ev2gym_amd.actor import init_mlp_weights
+    from ev2gym_amd.engine import EngineError
+    from ev2gym_amd.td3 import init_critic_weights
+    eng = engines["pst"]
+    D, h1, h2, P = shape
+    if tag == "fixed":   # 170-410-300-50 has the same tile counts, and the learner's plan refuses it on the host, ahead of any launch
+        wide = eng.mlp_create(*init_mlp_weights(170, 50, 0, 410, 300), out_lo=0.0, precision="bf16")
+        try:
+            assert eng.mlp_kernel_name(wide) == kernel
+            with pytest.raises(EngineError) as ei:
+                eng.td3_create(wide, init_mlp_weights(170, 50, 0, 410, 300), [init_critic_weights(170, 50, 1 + j, 410, 300) for j in range(2)])
+            assert ei.value.code == _abi.ERR_ARG and "h1 410 is outside 1 .. 400" in str(ei.value)
+        finally:
+            eng.mlp_destroy(wide)
+    case = tc.make_case(D, P, (h1, h2), 2, 64, 0.0, 0.2, seed=9, live=True)
+    d = _Dev(eng, case, precision=precision, policy_delay=1, lr=1e-2)
+    fresh = None
+    try:
+        assert eng.mlp_kernel_name(d.mlp) == kernel
+        x = np.concatenate([np.zeros((1, D), np.float32), case["obs"][:40]])
+        y0 = d.forward(x)
+        d.update(); d.update()
+        assert d.eng.td3_counters(d.t)[:2] == (2, 2)
+        actor, _ = d.weights()
+        assert all(not np.array_equal(a, b) for a, b in zip(actor, case["actor"]))
+        fresh = eng.mlp_create(*actor, out_lo=case["lo"], precision=precision)
+        assert eng.mlp_kernel_name(fresh) == kernel
+        y1, y2 = d.forward(x), d.forward(x, fresh)
+        assert np.array_equal(_bits(y1), _bits(y2))
+        assert not np.array_equal(y1, y0) and np.isfinite(y1).all() and y1.min() >= 0.0 and y1.max() <= 1.0
+    finally:
+        if fresh is not None:
+            eng.mlp_destroy(fresh)
+        d.close()
+
+
+# ---- 4b. config edges the checks accept: policy_delay 3, tau in {0, 1}, gamma in {0, 1}, target_noise_clip 0 with sigma > 0 ----
+def test_config_edges_delay_3_tau_1_gamma_0_clip_0(engines):  # noqa: F811
+    """Three updates on 33-17.  The actor and the targets move on update 3 only, and the targets then EQUAL the masters bit for bit
+    (target * 0 + 1 * param with finite weights); y is the reward bit for bit (gamma 0; no reward is -0.0); a clip of 0 silences the noise but its
+    draws are still consumed, B P per update; Adam is bit for bit by host_adam, the loop under the idiom."""
+    import torch
+    from ev2gym_amd.engine import host_adam, host_normal
+    D, P = SHAPES["pst"]
+    B = 33
+    case = tc.make_case(D, P, "33-17", 2, 3 * B, -1.0, 0.2, seed=5)
+    case["clip"], case["gamma"] = 0.0, 0.0
+    batches = [(np.arange(k * B, (k + 1) * B), host_normal(B * P, case["noise_seed"], k * B * P).reshape(B, P)) for k in range(3)]
+    kw = dict(policy_delay=3, tau=1.0)
+    ref, ref32 = tc.torch_loop(case, batches, torch.float64, **kw), tc.torch_loop(case, batches, torch.float32, **kw)
+    d = _Dev(engines["pst"], case, rows=batches[0][0], **kw)
+    try:
+        masters, targets = _flat(*d.weights()), _flat(*d.weights(True))
+        m, v = [np.zeros_like(a) for a in masters], [np.zeros_like(a) for a in masters]
+        for k in range(3):
+            d.load(batches[k][0])
+            losses = d.update()
+            y = d.eng.td3_get_y(d.t, B)
+            r = case["reward"][batches[k][0]]
+            assert not np.signbit(r[r == 0.0]).any() and np.array_equal(_bits(y), _bits(r)), k
+            grads, new, new_t = _flat(*d.grads()), _flat(*d.weights()), _flat(*d.weights(True))
+            want = [a.copy() for a in masters]
+            for i in range(6, len(want)):
+                host_adam(want[i], m[i], v[i], grads[i], k + 1, lr=1e-3, eps=1e-8)
+            if k == 2:
+                for i in range(6):
+                    host_adam(want[i], m[i], v[i], grads[i], 1, lr=1e-3, eps=1e-8)
+            for i, (a, b) in enumerate(zip(new, want)):
+                assert np.array_equal(_bits(a), _bits(b)), (k, i)
+            if k == 2:
+                for i, (t_new, t_old, p_new) in enumerate(zip(new_t, targets, new)):
+                    assert np.array_equal(_bits(t_new), _bits(p_new)) and not np.array_equal(t_new, t_old), i
+                assert all(not np.array_equal(new[i], masters[i]) for i in range(6))
+            else:
+                for i in range(6):
+                    assert np.array_equal(_bits(new[i]), _bits(masters[i])), (k, i)
+                for a, b in zip(new_t, targets):
+                    assert np.array_equal(_bits(a), _bits(b))
+            assert d.eng.td3_counters(d.t) == (k + 1, 1 if k == 2 else 0, (k + 1) * B * P)
+            tag = f"td3 config edges delay3 tau1 gamma0 clip0 step {k}"
+            tc.check_arrays(tag + " critic_loss", [[losses[0]]], [[ref[k]["critic_loss"]]], [[ref32[k]["critic_loss"]]], values=True)
+            if k == 2:
+                tc.check_arrays(tag + " actor_loss", [[losses[1]]], [[ref[k]["actor_loss"]]], [[ref32[k]["actor_loss"]]], values=True)
+                tc.check_arrays(tag + " actor", new[:6], ref[k]["actor"], ref32[k]["actor"], values=True)
+            for j in range(2):
+                tc.check_arrays(tag + f" critic {j}", new[6 + 6 * j:12 + 6 * j], ref[k]["critics"][j], ref32[k]["critics"][j], values=True)
+            masters, targets = new, new_t
+    finally:
+        d.close()
+
+
+@pytest.mark.parametrize("edge", ["tau0", "gamma1"])
+def test_config_edges_tau_0_and_gamma_1(engines, edge):  # noqa: F811
+    """Two updates with policy_delay 1.  tau 0: the actor and the critics step, the targets never move.  gamma 1: the loop under the idiom."""
+    import torch
+    from ev2gym_amd.engine import host_normal
+    D, P = SHAPES["pst"]
+    B = 33
+    case = tc.make_case(D, P, "33-17", 2, 2 * B, 0.0, 0.2, seed=6)
+    tau = 0.0 if edge == "tau0" else 0.005
+    case["gamma"] = 1.0 if edge == "gamma1" else 0.99
+    batches = [(np.arange(k * B, (k + 1) * B), host_normal(B * P, case["noise_seed"], k * B * P).reshape(B, P)) for k in range(2)]
+    kw = dict(policy_delay=1, tau=tau)
+    ref, ref32 = tc.torch_loop(case, batches, torch.float64, **kw), tc.torch_loop(case, batches, torch.float32, **kw)
+    d = _Dev(engines["pst"], case, rows=batches[0][0], **kw)
+    try:
+        masters, targets = _flat(*d.weights()), _flat(*d.weights(True))
+        for k in range(2):
+            d.load(batches[k][0])
+            losses = d.update()
+            new, new_t = _flat(*d.weights()), _flat(*d.weights(True))
+            assert all(not np.array_equal(a, b) for a, b in zip(new, masters)), k
+            if edge == "tau0":
+                for a, b in zip(new_t, targets):
+                    assert np.array_equal(_bits(a), _bits(b))
+            else:
+                assert all(not np.array_equal(a, b) for a, b in zip(new_t, targets))
+            assert d.eng.td3_counters(d.t) == (k + 1, k + 1, (k + 1) * B * P)
+            tag = f"td3 config edges {edge} step {k}"
+            tc.check_arrays(tag + " losses", [[losses[0]], [losses[1]]], [[ref[k]["critic_loss"]], [ref[k]["actor_loss"]]],
+                            [[ref32[k]["critic_loss"]], [ref32[k]["actor_loss"]]], values=True)
+            tc.check_arrays(tag + " actor", new[:6], ref[k]["actor"], ref32[k]["actor"], values=True)
+            for j in range(2):
+                tc.check_arrays(tag + f" critic {j}", new[6 + 6 * j:12 + 6 * j], ref[k]["critics"][j], ref32[k]["critics"][j], values=True)
+                tc.check_arrays(tag + f" critic_target {j}", new_t[6 + 6 * j:12 + 6 * j], ref[k]["critics_target"][j], ref32[k]["critics_target"][j], values=True)
+            tc.check_arrays(tag + " actor_target", new_t[:6], ref[k]["actor_target"], ref32[k]["actor_target"], values=True)
+            masters, targets = new, new_t
+    finally:
+        d.close()
+
+
 # ---- 5. the sampler ----
 def _collector(eng, cap=3, seed=0):
     from ev2gym_amd.actor import init_mlp_weights
@@ -295,6 +473,55 @@ def test_replay_sample_matches_the_host_twin():
         for b in out + [index]:
             b.free()
     finally:
+        col.close()
+        eng.close()
+
+
+def test_the_ring_wraps_and_the_sampler_reads_the_modular_block_list():
+    from ev2gym_amd.td3 import TD3Learner
+    eng = _gen_engine("pst", pool=4)   # four pool windows: four different episodes under one deterministic policy
+    col = _collector(eng, seed=4)
+    learner = TD3Learner(col, seed=3, batch_size=64)
+    try:
+        tc.check_ring_wrap(col, learner)
+        out = learner.train(2)
+        assert np.isfinite(out["critic_loss"]) and np.isfinite(out["actor_loss"]) and out["n_updates"] == 2
+        assert learner.counters() == (2, 1, 2 * 64 * col.P) and learner.sample_counter == 2 and col.episodes == 4
+    finally:
+        learner.close(); col.close(); eng.close()
+
+
+def test_a_wide_sampler_and_a_full_table():
+    """D > 64: the 64-thread copy loops take a second trip.  A 32-entry list (two real blocks repeated) fills the sampler's table; 33 entries are
+    refused on the host, and so is a learner on a ring that could hold 33 complete episodes."""
+    from ev2gym_amd.engine import EngineError, host_replay_indices
+    from ev2gym_amd.td3 import MAX_BLOCKS, TD3Learner
+    eng = _gen_engine("ppl", pool=2)   # (two pool windows: two different episodes)
+    col = _collector(eng)
+    big, out = None, []
+    try:
+        assert col.D > 64 and col.P <= 64 and MAX_BLOCKS == 32
+        snaps = [tc.snapshot(col, col.collect_episode()) for _ in range(2)]
+        assert (col.head, col.filled) == (2, 2)
+        assert not np.array_equal(snaps[0][0][1:], snaps[1][0][1:])   # two different episodes, by their observations
+        dev = [(col.obs[b], col.actions[b], col.reward[b], col.done[b]) for b in (1, 0)]
+        tc.check_sample(col, dev, [snaps[1], snaps[0]], 256, 77, (0, 1))
+        table = [dev[i % 2] for i in range(32)]
+        assert 31 in host_replay_indices(1024, 32, col.T, col.E, 77, 0)[:, 0]   # the last entry of the table is drawn at this seed
+        idx = tc.check_sample(col, table, [snaps[1 - i % 2] for i in range(32)], 1024, 77, (0,))[0]
+        assert 31 in idx[:, 0] and np.unique(idx[:, 0]).size == 32
+        out = [eng.empty((8, col.D), np.float32), eng.empty((8, col.P), np.float32), eng.empty((8,), np.float32), eng.empty((8, col.D), np.float32), eng.empty((8,), np.uint8)]
+        with pytest.raises(EngineError) as ei:
+            eng.replay_sample(table + dev[:1], col.T, col.E, col.D, col.P, 8, 77, 0, *out)
+        assert ei.value.code == -1 and "n_blocks must be 1 .. 32" in str(ei.value)
+        big = _collector(eng, cap=34)
+        with pytest.raises(ValueError, match="capacity_episodes must be at most 33"):
+            TD3Learner(big)
+    finally:
+        for b in out:
+            b.free()
+        if big is not None:
+            big.close()
         col.close()
         eng.close()
 
