@@ -20,6 +20,7 @@
 #include "ev2g_device.h"
 #include "ev2g_load_host.h"
 #include "ev2g_route_host.h"
+#include "ev2g_balance_host.h"
 #include "ev2g_policy_host.h"
 #include "ev2g_step_v2.h"
 #include "ev2g_step_wave.h"
@@ -232,6 +233,16 @@ struct ev2g_handle {
     // fast-forward of EV-free stretches (ev2g_step_wave's FFW path): per-workgroup counts of the last eligible launch; EV2G_NO_FAST_FORWARD=1 at load
     // time leaves the block (and V2P::ff_count) null, and every step is stepped (A/B, parity tests)
     unsigned long long *d_ff_count = nullptr;   // [n_groups]
+    unsigned *d_place = nullptr;                // [2 * n_groups + 2048] V2P::place (EV2G_PLACEMENT=1 at load time, development), else null
+    // CU balance (ev2g_balance_host.h): every scenario's live-step bitset (host, from the sessions' windows at load) and the maps made from them, one
+    // per pool window a launch started on -- a window's map depends on nothing but the pool and the offset, so it is built once and kept on the device
+    struct BalanceMap { long long off; int moved; std::vector<int> host; };   // (host: what was uploaded; slot i of d_balance holds maps[i])
+    std::vector<uint64_t> balance_bits;         // [M][BALANCE_WORDS]
+    std::vector<BalanceMap> balance_maps;       // at most kBalanceSlots, then the oldest slot is rebuilt
+    int *d_balance = nullptr;                   // [kBalanceSlots][n_groups]
+    size_t balance_next = 0;                    // the slot the next new window takes
+    int balance_cus = 0;                        // the device's CU count
+    int last_balance_moved = 0;                 // ev2g_last_launch_balance
     int last_stats_route = -1;                  // ev2g_last_stats_route
     const char *stats_reason = "";              // ev2g_last_stats_reason: last.inl_reason at the last ev2g_get_stats / ev2g_get_stats_reset
     std::string kernel_name;                    // the step kernel ev2g_load_scenarios selected (ev2g_kernel_name)
@@ -618,6 +629,22 @@ int ev2g_last_launch_fast_forwarded(ev2g_handle *h, int64_t *steps, int64_t *str
     if (stretches) *stretches = m;
     return EV2G_OK;
 }
+int ev2g_last_launch_balance(const ev2g_handle *h, int64_t *moved, const char **reason) {
+    const bool on = h && h->loaded && h->last.balance;
+    if (moved) *moved = on ? h->last_balance_moved : 0;
+    if (reason) *reason = (h && h->loaded) ? (on ? "" : h->last.balance_reason) : "no scenarios loaded";
+    return on ? 1 : 0;
+}
+int ev2g_last_launch_placement(ev2g_handle *h, uint32_t *out, int64_t n_words) {
+    if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_last_launch_placement: no scenarios loaded");
+    if (!h->d_place || !h->last.ff) return 0;   // (not loaded with EV2G_PLACEMENT=1, or the last launch does not fast-forward: nothing was recorded)
+    const int64_t n = 2 * (int64_t)h->scn.n_groups;
+    if (!out || n_words < n) return fail(h, EV2G_ERR_ARG, "ev2g_last_launch_placement: out must hold two words per workgroup");
+    (void)hipSetDevice(h->device);
+    HIPCHK(h, hipMemcpyAsync(out, h->d_place, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return (int)h->scn.n_groups;
+}
 const char *ev2g_last_launch_general_reason(const ev2g_handle *h) { return (h && h->loaded && h->last.specialisation == 0) ? h->last.general_reason : ""; }
 
 static const char *kStatNames[EV2G_N_STATS] = {
@@ -949,12 +976,17 @@ static int load_decide_inl_stats(ev2g_handle *h, const LoadSwitches &sw) {
     else if (rs.epw != 1 || stats_pair(h)) why = "several envs per wavefront (the in-launch phase computes one env per wavefront, like the statistics kernel at this shape)";
     else if (h->lds_bytes < ev2g_inl_stats_lds_bytes()) why = "the step kernel's LDS is smaller than the phase's blocks";
     rs.inl_shape_reason = why;
-    h->d_ff_count = nullptr;
+    h->d_ff_count = nullptr; h->d_place = nullptr;
     if (rs.wave() && rs.epw == 1 && !sw.no_fast_forward) {   // the fast-forward's per-workgroup counts: what switches it on
         int rc = 0;
         if ((rc = dalloc(h, h->st_allocs, (size_t)h->scn.n_groups, &h->d_ff_count))) return rc;
         unsigned long long *p = h->d_ff_count;
         HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, ff_count), &p, sizeof p, hipMemcpyHostToDevice));
+        if (sw.placement) {   // (development) the same launches record where their workgroups ran
+            if ((rc = dalloc(h, h->st_allocs, 2 * (size_t)h->scn.n_groups + 2048, &h->d_place))) return rc;
+            unsigned *q = h->d_place;
+            HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, place), &q, sizeof q, hipMemcpyHostToDevice));
+        }
     }
     if (!why[0]) {
         int rc = 0;
@@ -963,6 +995,61 @@ static int load_decide_inl_stats(ev2g_handle *h, const LoadSwitches &sw) {
         HIPCHK(h, hipMemcpy((char *)h->d_v2p + offsetof(V2P, stats_inl), &p, sizeof p, hipMemcpyHostToDevice));
     }
     rs.ff_count = h->d_ff_count != nullptr; rs.stats_inl = h->d_stats_inl != nullptr;
+    return EV2G_OK;
+}
+
+// CU balance (ev2g_balance_host.h).  The map of the pool window at `off`, on the device: kept from the launch that first started there (or from the
+// load, which builds those of the windows an episode loop over the pool visits: offsets k * E), in one of kBalanceSlots slots that are reused oldest
+// first -- the copy into a slot is ordered on the handle's stream behind the launches that read it.  nullptr: the copy failed, the kernel's own map holds.
+constexpr size_t kBalanceSlots = 64;
+static const int *balance_get(ev2g_handle *h, long long off) {
+    const size_t n = (size_t)h->scn.n_groups;
+    for (size_t i = 0; i < h->balance_maps.size(); i++)
+        if (h->balance_maps[i].off == off) { h->last_balance_moved = h->balance_maps[i].moved; return h->d_balance + i * n; }
+    const size_t slot = h->balance_next;
+    h->balance_next = (slot + 1) % kBalanceSlots;
+    if (h->balance_maps.size() <= slot) h->balance_maps.emplace_back();
+    ev2g_handle::BalanceMap &m = h->balance_maps[slot];
+    std::vector<int> weight;
+    balance_group_weights(h->balance_bits, h->M, off, h->E, 4, weight);
+    m.moved = balance_map(weight, h->balance_cus, m.host);
+    m.off = off;
+    if (m.host.size() != n || hipMemcpyAsync(h->d_balance + slot * n, m.host.data(), n * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+        m.off = -1;
+        return nullptr;
+    }
+    h->last_balance_moved = m.moved;
+    return h->d_balance + slot * n;
+}
+
+// Which launches may be balanced (RouteShape::balance; route_step adds the launch's own conditions), and what the maps are made from
+static int load_balance(ev2g_handle *h, const ev2g_scenario_batch *b, const LoadSwitches &sw) {
+    RouteShape &rs = h->shape;
+    h->balance_bits.clear(); h->balance_maps.clear();
+    h->d_balance = nullptr; h->balance_next = 0; h->last_balance_moved = 0;
+    const char *why = "";
+    if (sw.no_cu_balance) why = "EV2G_NO_CU_BALANCE is set";
+    else if (!rs.ff_count) why = "the loaded shape never fast-forwards (another kernel, several envs per wavefront, or EV2G_NO_FAST_FORWARD)";
+    else if (h->T > BALANCE_MAX_T) why = "an episode has more than 256 steps";
+    else if (h->cfg.flags & EV2G_FLAG_REFILLABLE) why = "the handle is EV2G_FLAG_REFILLABLE (a refill changes the scenarios the maps were made from)";
+    else if (h->scn.n_groups != (h->E + 3) / 4) why = "a workgroup does not step four envs";
+    rs.balance_shape_reason = why;
+    rs.balance = why[0] == 0;
+    if (!rs.balance) return EV2G_OK;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 8) cus = 256;
+    h->balance_cus = cus;
+    h->balance_bits.resize((size_t)h->M * BALANCE_WORDS);
+    for (long long m = 0; m < h->M; m++) {
+        const int64_t s0 = b->env_session_start[m], s1 = b->env_session_start[m + 1];
+        balance_live_bits(b->ev_t_arr + s0, b->ev_t_dep + s0, s1 - s0, h->T, &h->balance_bits[(size_t)m * BALANCE_WORDS]);
+    }
+    int rc = 0;
+    if ((rc = dalloc(h, h->st_allocs, kBalanceSlots * (size_t)h->scn.n_groups, &h->d_balance))) return rc;
+    for (long long k = 0; k < std::min<long long>(h->M / h->E, (long long)kBalanceSlots); k++)
+        if (!balance_get(h, k * h->E)) return fail(h, EV2G_ERR_HIP, "ev2g_load_scenarios: a CU-balance map could not be uploaded");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->last_balance_moved = 0;
     return EV2G_OK;
 }
 
@@ -1001,6 +1088,7 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
 
     h->E = plan.E; h->M = plan.M; h->scn_off = 0; h->T = plan.T; h->C = plan.C; h->npc = plan.npc; h->P = plan.P; h->R = plan.R; h->D = plan.D; h->S = plan.S;
     if ((rc = load_decide_inl_stats(h, sw))) return rc;
+    if ((rc = load_balance(h, b, sw))) return rc;
     // host mirrors for peek / stats / refill
     h->slot_port = std::move(plan.slot_port);
     h->port_slot = std::move(plan.port_slot);
@@ -1110,7 +1198,7 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
     c.t0 = t0; c.k = k; c.auto_reset = auto_reset;
     const StepRoute r = route_step(h->shape, c);
     if (r.refusal) {   // (nothing ran: the specialisation and its reason stay those of the launch before; its side results are gone all the same)
-        h->last.inl_stats = false; h->last.ff = false; h->last.inl_reason = r.inl_reason;
+        h->last.inl_stats = false; h->last.ff = false; h->last.balance = false; h->last.inl_reason = r.inl_reason; h->last.balance_reason = "the launch was refused";
         return fail(h, EV2G_ERR_ARG, r.refusal);
     }
     h->last = r;
@@ -1119,10 +1207,13 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
     switch (r.family) {
     case ROUTE_WAVE: {
         const DevState &st = h->st;
+        const int *grp_map = r.balance ? balance_get(h, h->scn_off) : nullptr;   // (the window's map: built at load, or here at a window's first launch)
+        if (r.balance && !grp_map) { h->last.balance = false; h->last.balance_reason = "the window's map could not be copied to the device"; }
         const WaveArgs wa{s.P, s.T, s.E, s.D, s.M, st.slab_port, st.slab_port_slice, st.hist,
-                    st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->shape.epw, s.P};
+                    st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->shape.epw, s.P, grp_map};
         const WaveLaunch launch = kWaveTable[route_wave_index(r.sk, r.rk, r.io32, r.fullk)];
         if (!launch) return fail(h, EV2G_ERR_ARG, "EV2G_ONLY_00 build: only the cfg2 specialisation exists");   // (every entry a route names exists in a full build: tests/host/route_check.cpp)
+        if (r.ff && h->d_place) HIPCHK(h, hipMemsetAsync(h->d_place, 0, sizeof(unsigned) * (2 * (size_t)s.n_groups + 2048), h->stream));   // (EV2G_PLACEMENT=1 only)
         launch(d, pp, io, t0, k, auto_reset, wa);
     } break;
     case ROUTE_BIG:
@@ -1398,7 +1489,7 @@ static int launch_fused(ev2g_handle *h, const ev2g_mlp *m, const FusedRoute &fr,
     const DevState &st = h->st;
     const long long lim = 1ll << 32;
     state_changed(h, "the last launch was a policy-in-the-loop segment (ev2g_rollout / ev2g_collect)");
-    h->last.ff = false;
+    h->last.ff = false; h->last.balance = false; h->last.balance_reason = "the last launch was a policy-in-the-loop segment";
     if (obs.stride * 4 >= lim || act.stride * 4 >= lim || reward.stride * 8 >= lim || done.stride >= lim || mask.stride >= lim || obs.stride < 0 ||
         act.stride < 0 || reward.stride < 0 || done.stride < 0 || mask.stride < 0)
         return fail(h, EV2G_ERR_ARG, "ev2g_collect / ev2g_rollout: a step stride is negative or reaches 4 GiB");

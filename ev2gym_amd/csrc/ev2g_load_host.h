@@ -29,6 +29,8 @@ struct LoadSwitches {
     bool no_full = false, no_wide = false, no_strided = false;   // EV2G_NO_FULL / EV2G_NO_WIDE / EV2G_NO_STRIDED
     bool no_inl_stats = false;        // EV2G_NO_INLAUNCH_STATS
     bool no_fast_forward = false;     // EV2G_NO_FAST_FORWARD: every EV-free step of a persistent launch is stepped
+    bool no_cu_balance = false;       // EV2G_NO_CU_BALANCE: every launch keeps the kernel's own workgroup -> env group map
+    bool placement = false;          // EV2G_PLACEMENT: fast-forwarding launches record where their workgroups ran (ev2g_last_launch_placement)
     bool kernel_v2 = false;           // EV2G_KERNEL=v2: the general kernel on the common shape
     bool no_dict = false;             // EV2G_NO_DICT: one ClsRec per session
     bool no_big = false;              // EV2G_NO_BIG: ev2g_step_v2<1024> where ev2g_step_big would run
@@ -41,6 +43,8 @@ inline LoadSwitches load_switches_from_env() {
     sw.no_strided = std::getenv("EV2G_NO_STRIDED") != nullptr;
     sw.no_inl_stats = std::getenv("EV2G_NO_INLAUNCH_STATS") != nullptr;
     sw.no_fast_forward = std::getenv("EV2G_NO_FAST_FORWARD") != nullptr;
+    sw.no_cu_balance = std::getenv("EV2G_NO_CU_BALANCE") != nullptr;
+    sw.placement = std::getenv("EV2G_PLACEMENT") != nullptr;
     const char *kn = std::getenv("EV2G_KERNEL");
     sw.kernel_v2 = kn && std::string(kn) == "v2";
     sw.no_dict = std::getenv("EV2G_NO_DICT") != nullptr;

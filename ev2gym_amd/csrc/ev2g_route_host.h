@@ -37,6 +37,8 @@ struct RouteShape {
     bool ff_count = false;      // V2P::ff_count is set: the fast path with one env per wavefront, no EV2G_NO_FAST_FORWARD
     bool stats_inl = false;     // V2P::stats_inl is set: the shape has the in-launch statistics phase ...
     const char *inl_shape_reason = "";   // ... why not
+    bool balance = false;       // the handle builds CU-balance maps (ev2g_balance_host.h): ff_count, T <= 256, not EV2G_FLAG_REFILLABLE, no EV2G_NO_CU_BALANCE ...
+    const char *balance_shape_reason = "";   // ... why not
     bool wave() const { return family == ROUTE_WAVE; }
     bool big() const { return family == ROUTE_BIG; }
 };
@@ -58,6 +60,8 @@ struct StepRoute {
     bool spec = false;
     int specialisation = -1;         // ev2g_last_launch_specialisation
     bool ff = false;                 // the kernel fast-forwards and counts (ev2g_last_launch_fast_forwarded)
+    bool balance = false;            // the launch gets a CU-balance map for the window it steps (ev2g_last_launch_balance) ...
+    const char *balance_reason = ""; // ... why it keeps the kernel's own map
     bool inl_stats = false;          // the kernel computes get_statistics of every env in its tail
     const char *general_reason = ""; // ev2g_last_launch_general_reason
     const char *inl_reason = "";     // why the in-launch statistics are not available (ev2g_last_stats_reason reports it)
@@ -77,7 +81,7 @@ constexpr bool route_wave_exists(int sk, int rk, bool io32, int fullk) {
 
 inline StepRoute route_step(const RouteShape &s, const RouteCall &c) {
     StepRoute r;
-    r.inl_reason = "the step kernel is not ev2g_step_wave";
+    r.inl_reason = r.balance_reason = "the step kernel is not ev2g_step_wave";
     const bool cs_hist = (s.flags & EV2G_FLAG_LOG_CS_HISTORY) != 0, log_soc = (s.flags & EV2G_FLAG_LOG_SOC) != 0;
     const bool strided = c.o_stride != 0 || c.r_stride != 0 || c.d_stride != 0 || c.m_stride != 0;
     if (s.wave()) {
@@ -110,6 +114,12 @@ inline StepRoute route_step(const RouteShape &s, const RouteCall &c) {
         // (ev2g_step_wave.h's FFW is the kernel's half: a stride-0 float64 full instantiation of a head-table state, V2P::ff_count set -- one env per
         // wavefront --, k > 1)
         r.ff = full && !str3 && f64io && c.k > 1 && s.ff_count && s.state_kind != EV2G_STATE_PUBLIC_PST;
+        // CU balance: the launches that fast-forward, from step 0 (a group's weight is its live steps of the whole episode)
+        if (!r.ff) r.balance_reason = "the launch does not fast-forward (ev2g_last_launch_fast_forwarded: a persistent stride-0 float64 launch of more than one step, one env per wavefront)";
+        else if (c.t0 != 0) r.balance_reason = "the launch does not start at step 0";
+        else if (!s.balance) r.balance_reason = s.balance_shape_reason;
+        else r.balance_reason = "";
+        r.balance = r.balance_reason[0] == 0;
         // why not the full instantiation: the FIRST thing the caller passed (or configured) that rules it out
         if (!full) {
             if (s.no_full) r.general_reason = "EV2G_NO_FULL is set (or the batch has more than 4094 efficiency tables)";

@@ -191,6 +191,7 @@ struct V2P {
     EV2G_GP(const double) ss_B; EV2G_GP(const double) ss_afap;
     EV2G_GP(double) stats_inl;   // [E, 17] rows the in-launch phase writes (the loader sets it for the shapes that have the phase), else nullptr
     EV2G_GP(unsigned long long) ff_count;   // [n_groups] steps (bits 0..31) and stretches (bits 32..) every workgroup of ev2g_step_wave fast-forwarded in the last eligible launch; nullptr: no fast-forward (the loader sets it)
+    EV2G_GP(unsigned) place;   // [2 * n_groups + 2048] EV2G_PLACEMENT=1 at load time (development, ev2g_last_launch_placement): per workgroup of a fast-forwarding launch its hardware ids and its arrival rank on its CU, then the CUs' arrival counters; else nullptr
     // StepExtras (ev2g_set_step_extras), refreshed in place when they change
     EV2G_GP(double) x_cost; long long x_c_stride;
     EV2G_GP(float) x_obs32; long long x_o32_stride;
@@ -216,7 +217,7 @@ inline void ev2g_v2_fill_params(V2P &p, const DevScn &s, const DevState &st) {
     CPS(price_ch) CPS(price_dis) CPS(setpoint) CPS(tr_infl) CPS(tr_solar) CPS(tr_base) CPS(tr_maxp) CPS(tr_minp)
     CPS(win_tab) CPS(lut) CPS(rec) CPS(tail) CPS(ss_lut) CPS(sess_dyn) CPS(cls_rec)
     CPS(scn_sess) CPS(scn_sess_end) CPS(ss_slot) CPS(ss_tarr) CPS(ss_tdep) CPS(ss_B)
-    EV2G_SETP(p.ss_afap, (const double *)nullptr); EV2G_SETP(p.stats_inl, (double *)nullptr); EV2G_SETP(p.ff_count, (unsigned long long *)nullptr);   // (set by the loader: not part of DevScn / DevState)
+    EV2G_SETP(p.ss_afap, (const double *)nullptr); EV2G_SETP(p.stats_inl, (double *)nullptr); EV2G_SETP(p.ff_count, (unsigned long long *)nullptr); EV2G_SETP(p.place, (unsigned *)nullptr);   // (set by the loader: not part of DevScn / DevState)
     CPT(line) CPT(cs_sat_sum) CPT(cs_served)
     CPT(cs_profits) CPT(cs_e_ch) CPT(cs_e_dis) CPT(cs_power_hist) CPT(cs_cur_hist) CPT(cs_power_now) CPT(cs_cur_now)
     CPT(env_acc) CPT(env_fault) CPT(hist) CPT(tr_power_now)

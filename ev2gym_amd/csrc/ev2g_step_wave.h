@@ -135,6 +135,7 @@ struct WaveArgs {
     char *port_dyn;          // [E*P] PortDyn: transition_soc, efficiencies, table id and dictionary entry of the attached EV
     int dict;                // DevScn::dict: V2P::cls_rec is a dictionary (entry = bits 20..31 of the port's LDS word); 0: one ClsRec per session
     int epw, es;             // envs per wavefront (<= 64 / P) and the lane stride between them (>= P; P: packed, 64 / epw: aligned to lane rows)
+    const int *grp_map = nullptr;   // [gridDim.x] the env group of every workgroup (a permutation, ev2g_balance_host.h); nullptr: the kernel's own map
 };
 
 // IO32: the actions are float32 (StepIO::act32) -- the policy-network interface; float32 observations (StepIO::obs32) are
@@ -204,6 +205,9 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         const int nb = gridDim.x, b = blockIdx.x, per = nb >> 3;
         grp = (nb & 7) == 0 ? (b & 7) * per + (b >> 3) : b;
     }
+    // CU balance (ev2g_balance_host.h): a fast-forwarding launch from step 0 is handed a permutation of the groups that puts heavy and light ones on one
+    // CU -- only the instantiations that fast-forward (FFW below) look at it, the others are what they were; everything past e0 is indexed by env
+    if (F64 && LSO && !ACT && RK != 3 && SK != 1 && BLOCK == EV2G_WAVE_BLOCK && wa.grp_map != nullptr) grp = wa.grp_map[blockIdx.x];
     const int e0 = grp * G;
     double *stage = lds;                                   // [NQ][RS] per-port step results, by home index (= tid)
     double *s_cap = stage + (size_t)EV2G_NQ * RS;
@@ -269,6 +273,13 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
         ff_lim_v = k_steps - 1;
         // this workgroup's count (bits 0..31 steps, 32.. stretches), cleared here: the prologue's wait below completes the store before the first addition
         if (tid == 0) stg32<unsigned long long>(S->ff_count, (unsigned)blockIdx.x * 8u, 0ull);
+        if (tid == 0 && S->place != nullptr) {   // EV2G_PLACEMENT=1 at load time (development): the CU this workgroup runs on and its arrival rank there
+            const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);   // HW_REG_HW_ID, HW_REG_XCC_ID
+            const unsigned cu = ((xcc & 7u) << 8) | ((hw >> 8) & 0xffu);   // XCC | SE | SH | CU: < 2048, the counters behind the 2 * gridDim.x words of the workgroups
+            const unsigned rank = __hip_atomic_fetch_add(S->place + 2u * gridDim.x + cu, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            S->place[2u * blockIdx.x] = (xcc << 16) | (hw & 0xffffu);
+            S->place[2u * blockIdx.x + 1u] = rank;
+        }
     }
     // ---- home lane set-up ----
     const int elw = lane / ES;           // env inside the wavefront

@@ -63,6 +63,8 @@ def load_library(path: Optional[str] = None):
         "ev2g_last_stats_route": (C.c_int, [vp]),
         "ev2g_last_stats_reason": (C.c_char_p, [vp]),
         "ev2g_last_launch_fast_forwarded": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ev2g_last_launch_placement": (C.c_int, [vp, C.c_void_p, C.c_int64]),
+        "ev2g_last_launch_balance": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]),
         "ev2g_fallback_reason": (C.c_char_p, [vp]),
         "ev2g_big_kernel_reason": (C.c_char_p, [vp]),
         "ev2g_step": (C.c_int, [vp, vp, vp, vp, vp, vp]),
@@ -217,7 +219,7 @@ def load_library(path: Optional[str] = None):
 EXPORTED_SYMBOLS = [
     "ev2g_abi_version", "ev2g_create", "ev2g_destroy", "ev2g_last_error", "ev2g_load_scenarios", "ev2g_n_envs",
     "ev2g_n_scenarios", "ev2g_n_ports", "ev2g_obs_dim", "ev2g_n_steps", "ev2g_current_step", "ev2g_reset", "ev2g_reset_ex",
-    "ev2g_scenario_offset", "ev2g_set_step_extras", "ev2g_kernel_name", "ev2g_last_launch_specialisation", "ev2g_last_launch_general_reason", "ev2g_last_stats_route", "ev2g_last_stats_reason", "ev2g_last_launch_fast_forwarded", "ev2g_fallback_reason", "ev2g_big_kernel_reason", "ev2g_step", "ev2g_step_n",
+    "ev2g_scenario_offset", "ev2g_set_step_extras", "ev2g_kernel_name", "ev2g_last_launch_specialisation", "ev2g_last_launch_general_reason", "ev2g_last_stats_route", "ev2g_last_stats_reason", "ev2g_last_launch_fast_forwarded", "ev2g_last_launch_placement", "ev2g_last_launch_balance", "ev2g_fallback_reason", "ev2g_big_kernel_reason", "ev2g_step", "ev2g_step_n",
     "ev2g_check_faults", "ev2g_get_stats", "ev2g_get_stats_reset", "ev2g_get_stats_reset_f32", "ev2g_reset_f32", "ev2g_collect", "ev2g_stat_name", "ev2g_peek", "ev2g_malloc", "ev2g_free",
     "ev2g_memcpy_h2d", "ev2g_memcpy_d2h", "ev2g_host_malloc", "ev2g_host_free", "ev2g_synchronize", "ev2g_fill_uniform", "ev2g_host_uniform",
     "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_mlp_kernel_name", "ev2g_rollout",
@@ -351,6 +353,23 @@ class Engine:
         n, m = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.ev2g_last_launch_fast_forwarded(self._h, C.byref(n), C.byref(m)))
         return int(n.value), int(m.value)
+
+    @property
+    def last_launch_balance(self):
+        """(balanced, moved, reason): whether the last step launch had a CU-balance map (include/ev2g.h: a fast-forwarding launch from step 0), how many
+        workgroups stepped another env group than without one, and -- when it had none -- why."""
+        n, why = C.c_int64(0), C.c_char_p()
+        on = self._lib.ev2g_last_launch_balance(self._h, C.byref(n), C.byref(why))
+        return bool(on), int(n.value), (why.value or b"").decode()
+
+    def last_launch_placement(self):
+        """Development (EV2G_PLACEMENT=1 at load time, include/ev2g.h): [n_workgroups, 2] uint32 -- hardware ids and arrival rank on its CU of every workgroup
+        of the last fast-forwarding launch; None when nothing was recorded.  Synchronises the stream."""
+        out = np.zeros((2 * ((self.E + 3) // 4 + 1),), np.uint32)
+        n = int(self._lib.ev2g_last_launch_placement(self._h, out.ctypes.data, out.size))
+        if n < 0:
+            self._check(n)
+        return out[:2 * n].reshape(n, 2) if n else None
 
     @property
     def fallback_reason(self) -> str:

@@ -295,6 +295,21 @@ const char *ev2g_last_stats_reason(const ev2g_handle *h);
  * Both are 0 after any launch that is not eligible (other instantiations and kernels, single steps, several envs per wavefront) and when the
  * library was loaded with EV2G_NO_FAST_FORWARD=1, which steps every step (A/B runs, parity tests).  Synchronises the stream. */
 int ev2g_last_launch_fast_forwarded(ev2g_handle *h, int64_t *steps, int64_t *stretches);
+/* CU balance.  The launches that fast-forward (above) are as long as their busiest compute unit, and a live step costs more the more workgroups
+ * its CU still holds.  Such a launch that starts at step 0 is therefore handed a map workgroup -> env group that deals the groups of the pool window
+ * it steps, heaviest first (most steps with an EV present or arriving: a function of the scenarios, not of the actions), over the CUs as a snake,
+ * so that every CU's workgroups have about the same work in sum.  A map is a permutation of the groups and all state is indexed by env: results
+ * are bit-identical with and without it.  A window's map is made once (at load for the offsets k * n_envs, else at the first launch on it) and
+ * kept on the device.  Not for episodes of more than 256 steps or EV2G_FLAG_REFILLABLE handles; EV2G_NO_CU_BALANCE=1 at load time switches it off.
+ * Returns 1 when the LAST step launch had a map (`moved`: the workgroups that stepped another group than without one), else 0 and `reason` says why
+ * (either pointer may be NULL; the string lives as long as the handle). */
+int ev2g_last_launch_balance(const ev2g_handle *h, int64_t *moved, const char **reason);
+/* Development: where the workgroups of the LAST launch ran.  Only a library loaded with EV2G_PLACEMENT=1 records it, and only in the launches that
+ * fast-forward (above); such a launch is preceded by a memset on the stream and every workgroup does one atomic addition, so do not time with it.
+ * Two words per workgroup b = blockIdx.x: out[2 b] = HW_REG_XCC_ID << 16 | the low 16 bits of HW_REG_HW_ID (bits 8..15: CU, SH, SE), out[2 b + 1] =
+ * how many workgroups of the launch had arrived on that CU before it.  Returns the number of workgroups written (`n_words` must hold twice as many),
+ * 0 when nothing was recorded, or an error code (< 0).  Synchronises the stream. */
+int ev2g_last_launch_placement(ev2g_handle *h, uint32_t *out, int64_t n_words);
 /* data-dependent faults recorded since the last reset (per-env flag word, device side):
  * returns 0 or EV2G_ERR_OVERCURRENT; synchronises the stream. */
 int ev2g_check_faults(ev2g_handle *h, int32_t *first_bad_env);
