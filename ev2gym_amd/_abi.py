@@ -165,6 +165,10 @@ class SacConfigC(C.Structure):   # ev2g_sac_config, in header order
                 ("ent_coef_auto", C.c_int32), ("target_entropy_auto", C.c_int32)]
 
 
+class TqcConfigC(C.Structure):   # ev2g_tqc_config, in header order: ev2g_sac_config's fields, then the two quantile settings
+    _fields_ = SacConfigC._fields_ + [("n_quantiles", C.c_int32), ("top_quantiles_to_drop_per_net", C.c_int32)]
+
+
 TD3_MAX_BATCH = 1024   # EV2G_TD3_MAX_BATCH
 
 
@@ -180,6 +184,15 @@ def sac_param_shapes(d_in, h1, h2, d_out, n_critics):
     actor = [(h1, d_in), (h1,), (h2, h1), (h2,), (d_out, h2), (d_out,), (d_out, h2), (d_out,)]
     critic = [(h1, d_in + d_out), (h1,), (h2, h1), (h2,), (1, h2), (1,)]
     return actor + critic * int(n_critics)
+
+
+def tqc_param_shapes(d_in, h1, h2, d_out, n_critics, n_quantiles):
+    """The 8 + 6 n_critics shapes in sb3_contrib's parameter order: SAC's actor, then each quantile critic's (the last layer has n_quantiles rows)."""
+    critic = [(h1, d_in + d_out), (h1,), (h2, h1), (h2,), (n_quantiles, h2), (n_quantiles,)]
+    return sac_param_shapes(d_in, h1, h2, d_out, 0) + critic * int(n_critics)
+
+
+TQC_MAX_CRITICS, TQC_MAX_QUANTILES, TQC_MAX_ATOMS = 5, 64, 128   # EV2G_TQC_MAX_* (csrc/ev2g_tqc.h)
 
 
 PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction")   # the six statistics of ev2g_ppo_grad

@@ -37,6 +37,7 @@
 #include "ev2g_learner_host.h"
 #include "ev2g_td3_host.h"
 #include "ev2g_sac_host.h"
+#include "ev2g_tqc_host.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -157,10 +158,12 @@ struct ev2g_td3 : DevOwner {
 };
 static void td3_free(ev2g_td3 *t);
 
-// a SAC learner with its collection actor (ev2g_sac_create, ev2g_sac.h): float32 masters, Adam's state and the last gradient in the plan's flat
-// layout (actor | critic 0 | critic 1), the target critics, log_ent_coef with its Adam state and gradient, the workspace of one batch, the four
-// losses, the collection actor's packed images, and the two noise streams
-struct ev2g_sac : DevOwner {
+// What a SAC learner and a TQC learner share -- each with its collection actor (ev2g_sac_create / ev2g_tqc_create, ev2g_sac.h): float32 masters,
+// Adam's state and the last gradient in the plan's flat layout (actor | critic 0 | critic 1 | ...), the target critics, log_ent_coef with its Adam
+// state and gradient, the workspace of one batch, the four losses, the collection actor's packed images, and the two noise streams.  `abi` is
+// the prefix of the object's entries ("ev2g_sac" / "ev2g_tqc"): what the shared stages' messages name.
+struct SacCore : DevOwner {
+    const char *abi = "ev2g_sac";
     ev2g_sac_config cfg{};
     SacPlan plan;
     SacDev dev{};
@@ -172,6 +175,12 @@ struct ev2g_sac : DevOwner {
     unsigned long long seed = 0, next_draw = 0, act_seed = 0, act_n = 0;
     long long n = 0, n_target = 0, t_critic = 0, t_actor = 0;   // updates applied, Polyak steps among them; Adam's step counts
     int pending = 0, last_B = 0, last_actor_B = 0;              // bit 0: the critics' gradient, bit 1: the actor's and log_ent_coef's
+};
+struct ev2g_sac : SacCore {};
+// a TQC learner (ev2g_tqc_create, ev2g_tqc.h): SacCore with quantile critics -- `plan` is tq's SacPlan part (q, tq, dq as [nc][B, nq]), tq adds z,
+// the rows' float64 partials and the summed input deltas
+struct ev2g_tqc : SacCore {
+    TqcPlan tq;
 };
 
 #define EV2G_EV_RING 32
@@ -282,6 +291,7 @@ struct ev2g_handle {
     std::vector<ev2g_ppo *> ppos;               // the learners (PPO and A2C) created on this handle (freed with it, or with their policy)
     std::vector<ev2g_td3 *> td3s;               // the TD3 / DDPG learners created on this handle (freed with it, or with their policy)
     std::vector<ev2g_sac *> sacs;               // the SAC learners created on this handle (freed with it)
+    std::vector<ev2g_tqc *> tqcs;               // the TQC learners created on this handle (freed with it)
     unsigned sac_attr_mask = 0;                 // ev2g_sac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
     unsigned ppo_attr_mask = 0;                 // ev2g_ppo_grad_kernel instantiations (bit relu + 2 head) whose dynamic-LDS attribute was set
     unsigned ac_attr_mask = 0;                  // ev2g_ac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
@@ -596,6 +606,7 @@ void ev2g_destroy(ev2g_handle *h) {
     release_all(h->ppos, ppo_free);   // (learners before their policies)
     release_all(h->td3s, td3_free);
     release_all(h->sacs);
+    release_all(h->tqcs);
     release_all(h->acs);
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
@@ -3151,18 +3162,18 @@ static const SacActEntry &sac_act_kernel(bool sample) {
 }
 
 // the actor's trunk and mu head as a Td3Net (the log_std head is the z = 1 block behind mu's: SacPlan::head_block), and the critics
-static Td3Net sac_actor_net(const ev2g_sac *s) {
+static Td3Net sac_actor_net(const SacCore *s) {
     const SacPlan &p = s->plan;
     return {s->theta, 0, p.aoff, p.d_in, p.h1, p.h2, p.d_out, s->work + p.w_ah1, s->work + p.w_ah2, s->work + p.w_head};
 }
-static Td3Net sac_critic_net(const ev2g_sac *s, const float *critic_params, float *out) {
+static Td3Net sac_critic_net(const SacCore *s, const float *critic_params, float *out) {
     const SacPlan &p = s->plan;
-    return {critic_params, p.n_critic, p.coff, p.da, p.h1, p.h2, 1, s->work + p.w_ch1, s->work + p.w_ch2, out};
+    return {critic_params, p.n_critic, p.coff, p.da, p.h1, p.h2, p.coff[6] - p.coff[5], s->work + p.w_ch1, s->work + p.w_ch2, out};
 }
 
 // the actor on x [B, d_in] with the draws draw0 + b P + p: the trunk, both heads (the z dimension of one launch), then the squashed-Gaussian
 // head: mu | raw log_std, eps and a into the workspace, a into the action columns of xcols [B, da], log pi into logp
-static void sac_actor_forward(ev2g_handle *h, ev2g_sac *s, const float *x, int B, uint64_t draw0, float *xcols, float *logp) {
+static void sac_actor_forward(ev2g_handle *h, SacCore *s, const float *x, int B, uint64_t draw0, float *xcols, float *logp) {
     const SacPlan &p = s->plan;
     float *W = s->work;
     const Td3Net an = sac_actor_net(s);
@@ -3181,7 +3192,7 @@ static void sac_actor_forward(ev2g_handle *h, ev2g_sac *s, const float *x, int B
                        (const float *)(W + p.w_head + (long long)B * p.d_out), B, p.d_out, (uint64_t)s->seed, draw0, W + p.w_eps, W + p.w_a, xcols, p.da, p.d_in, logp);
 }
 
-static int sac_launch_repack(ev2g_handle *h, ev2g_sac *s) {
+static int sac_launch_repack(ev2g_handle *h, SacCore *s) {
     SacRepack r{};
     for (int i = 0; i <= EV2G_SAC_ACTOR_ARRAYS; i++) r.off[i] = s->plan.aoff[i];
     hipLaunchKernelGGL(ev2g_sac_repack_kernel, dim3(td3_blocks((long long)s->plan.h1 * std::max(s->plan.d_in, s->plan.h2))), dim3(256), 0, h->stream, s->dev, r,
@@ -3196,7 +3207,7 @@ int ev2g_sac_default_config(ev2g_sac_config *cfg) {
     return EV2G_OK;
 }
 
-static int sac_device_stage(ev2g_handle *h, ev2g_sac *s, const float *const *actor, const float *const *critics) {
+static int sac_device_stage(ev2g_handle *h, SacCore *s, const float *const *actor, const float *const *critics) {
     const SacPlan &p = s->plan;
     const size_t G = (size_t)p.n_params, GC = (size_t)p.nc * p.n_critic;
     float **bufs[] = {&s->theta, &s->m, &s->v, &s->grad};
@@ -3224,7 +3235,7 @@ static int sac_device_stage(ev2g_handle *h, ev2g_sac *s, const float *const *act
     for (unsigned k = 0; k < 2; k++)
         if (s->lds > 48 * 1024 && !(h->sac_attr_mask & (1u << k))) {   // (function attributes are per device: once per handle, for the largest network)
             const hipError_t e = hipFuncSetAttribute(sac_act_kernel(k != 0).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev2g_sac_lds_max());
-            if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string("ev2g_sac_create: hipFuncSetAttribute: ") + hipGetErrorString(e));
+            if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string(s->abi) + "_create: hipFuncSetAttribute: " + hipGetErrorString(e));
             h->sac_attr_mask |= 1u << k;
         }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3278,25 +3289,15 @@ static int sac_critic_stage(ev2g_handle *h, ev2g_sac *s, const char *who, const 
     return EV2G_OK;
 }
 
-static int sac_actor_stage(ev2g_handle *h, ev2g_sac *s, const char *who, const float *obs, int B, float *losses) {
-    if (int rc = sac_check(h, s, who)) return rc;
-    if (!obs) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
-    const std::string refusal = td3_batch_refusal(who, B);
-    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+// The actor's backward from the input-delta blocks dxa [nc][B, P] that ev2g_sac_head_back_kernel sums -- SAC passes its critics' blocks (nc 1 or
+// 2: the kernel's limit), TQC always ONE block, its up to five critics' deltas already summed by ev2g_tqc_delta_sum_kernel -- of the forward
+// sac_actor_forward left in the workspace: the eight gradients into grad
+static void sac_actor_backward(ev2g_handle *h, SacCore *s, const float *obs, int B, const float *dxa, int nc) {
     const SacPlan &p = s->plan;
-    float *W = s->work, *L = losses ? losses : s->loss;
+    float *W = s->work;
     const long long BP = (long long)B * p.d_out, z2 = (long long)B * p.h2;
-    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(td3_blocks((long long)B * p.da)), dim3(256), 0, h->stream, obs, (const float *)nullptr, B, p.d_in, p.d_out, s->lo,
-                       W + p.w_xb);
-    sac_actor_forward(h, s, obs, B, (uint64_t)s->next_draw, W + p.w_xb, W + p.w_lp);
-    const Td3Net cn = sac_critic_net(s, s->theta + p.n_actor, W + p.w_q);
-    td3_forward(h, cn, W + p.w_xb, B, TD3_EPI_BIAS, p.nc);
-    hipLaunchKernelGGL(ev2g_sac_actor_head_kernel, dim3(1), dim3(256), 0, h->stream, (const float *)(W + p.w_q), (const float *)(W + p.w_lp), B, p.nc,
-                       (const float *)s->alpha, s->target_entropy, s->cfg.ent_coef_auto ? 1 : 0, W + p.w_dq, L, s->g_alpha);
-    // dQ_j / da of both critics from the selector as output delta: the critic that is not a row's argmin propagates exact zeros
-    td3_backward(h, cn, W + p.w_xb, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, nullptr, W + p.w_dxa, p.d_in, p.d_out, p.nc);
     hipLaunchKernelGGL(ev2g_sac_head_back_kernel, dim3(td3_blocks(BP)), dim3(256), 0, h->stream, (const float *)(W + p.w_head), (const float *)(W + p.w_head + BP),
-                       (const float *)(W + p.w_eps), (const float *)(W + p.w_dxa), p.nc, B, p.d_out, (const float *)s->alpha, W + p.w_dhead);
+                       (const float *)(W + p.w_eps), dxa, nc, B, p.d_out, (const float *)s->alpha, W + p.w_dhead);
     // the heads (z = 0: mu, 1: log_std): their gradients, their backward-data products joined under the second hidden layer's ReLU, then the trunk
     const Td3Net an = sac_actor_net(s);
     td3_wgrad(h, B, W + p.w_dhead, BP, p.d_out, an.H2, 0, p.h2, s->grad + p.aoff[4], s->grad + p.aoff[5], p.head_block, 2);
@@ -3306,14 +3307,33 @@ static int sac_actor_stage(ev2g_handle *h, ev2g_sac *s, const char *who, const f
     td3_wgrad(h, B, W + p.w_e2, z2, p.h2, an.H1, 0, p.h1, s->grad + p.aoff[2], s->grad + p.aoff[3], 0, 1);
     td3_bdata(h, B, W + p.w_e2, z2, p.h2, s->theta + p.aoff[2], 0, p.h1, p.h1, an.H1, 0, W + p.w_e1, 0, 1);
     td3_wgrad(h, B, W + p.w_e1, 0, p.h1, obs, 0, p.d_in, s->grad + p.aoff[0], s->grad + p.aoff[1], 0, 1);
+}
+
+static int sac_actor_stage(ev2g_handle *h, ev2g_sac *s, const char *who, const float *obs, int B, float *losses) {
+    if (int rc = sac_check(h, s, who)) return rc;
+    if (!obs) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const SacPlan &p = s->plan;
+    float *W = s->work, *L = losses ? losses : s->loss;
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(td3_blocks((long long)B * p.da)), dim3(256), 0, h->stream, obs, (const float *)nullptr, B, p.d_in, p.d_out, s->lo,
+                       W + p.w_xb);
+    sac_actor_forward(h, s, obs, B, (uint64_t)s->next_draw, W + p.w_xb, W + p.w_lp);
+    const Td3Net cn = sac_critic_net(s, s->theta + p.n_actor, W + p.w_q);
+    td3_forward(h, cn, W + p.w_xb, B, TD3_EPI_BIAS, p.nc);
+    hipLaunchKernelGGL(ev2g_sac_actor_head_kernel, dim3(1), dim3(256), 0, h->stream, (const float *)(W + p.w_q), (const float *)(W + p.w_lp), B, p.nc,
+                       (const float *)s->alpha, s->target_entropy, s->cfg.ent_coef_auto ? 1 : 0, W + p.w_dq, L, s->g_alpha);
+    // dQ_j / da of both critics from the selector as output delta: the critic that is not a row's argmin propagates exact zeros
+    td3_backward(h, cn, W + p.w_xb, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, nullptr, W + p.w_dxa, p.d_in, p.d_out, p.nc);
+    sac_actor_backward(h, s, obs, B, W + p.w_dxa, p.nc);
     HIPCHK(h, hipGetLastError());
     s->pending |= 2; s->last_actor_B = B;
     return EV2G_OK;
 }
 
-static int sac_apply_stage(ev2g_handle *h, ev2g_sac *s, const char *who) {
-    if (int rc = sac_check(h, s, who)) return rc;
-    if (!s->pending) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (ev2g_sac_critic_grad or ev2g_sac_actor_grad first)");
+// (the caller has checked the object)
+static int sac_apply_stage(ev2g_handle *h, SacCore *s, const char *who) {
+    if (!s->pending) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no gradient to apply (" + s->abi + "_critic_grad or " + s->abi + "_actor_grad first)");
     const SacPlan &p = s->plan;
     const ev2g_sac_config &c = s->cfg;
     if (s->pending & 1) {
@@ -3346,7 +3366,10 @@ int ev2g_sac_critic_grad(ev2g_handle *h, ev2g_sac *s, const float *obs, const fl
     return sac_critic_stage(h, s, "ev2g_sac_critic_grad", obs, actions, reward, next_obs, done, B, losses);
 }
 int ev2g_sac_actor_grad(ev2g_handle *h, ev2g_sac *s, const float *obs, int B, float *losses) { return sac_actor_stage(h, s, "ev2g_sac_actor_grad", obs, B, losses); }
-int ev2g_sac_apply(ev2g_handle *h, ev2g_sac *s) { return sac_apply_stage(h, s, "ev2g_sac_apply"); }
+int ev2g_sac_apply(ev2g_handle *h, ev2g_sac *s) {
+    if (int rc = sac_check(h, s, "ev2g_sac_apply")) return rc;
+    return sac_apply_stage(h, s, "ev2g_sac_apply");
+}
 
 int ev2g_sac_update(ev2g_handle *h, ev2g_sac *s, const float *obs, const float *actions, const float *reward, const float *next_obs,
                     const uint8_t *done, int B, float *losses) {
@@ -3358,7 +3381,7 @@ int ev2g_sac_update(ev2g_handle *h, ev2g_sac *s, const float *obs, const float *
 }
 
 // one launch of ev2g_sac_act_kernel over n_rows rows; a sampling launch takes the collection stream's counter and advances it
-static int sac_act_launch(ev2g_handle *h, ev2g_sac *s, const float *x, int n_rows, bool sample, float *act, float *mu, float *ls, float *logp) {
+static int sac_act_launch(ev2g_handle *h, SacCore *s, const float *x, int n_rows, bool sample, float *act, float *mu, float *ls, float *logp) {
     const LaunchDims dims{dim3((unsigned)((n_rows + EV2G_AC_ROWS - 1) / EV2G_AC_ROWS)), s->lds, h->stream};
     sac_act_kernel(sample).launch(dims, s->dev, x, n_rows, (uint64_t)s->act_seed, (uint64_t)s->act_n * (uint64_t)n_rows, act, mu, ls, logp);
     HIPCHK(h, hipGetLastError());
@@ -3366,21 +3389,18 @@ static int sac_act_launch(ev2g_handle *h, ev2g_sac *s, const float *x, int n_row
     return EV2G_OK;
 }
 
-int ev2g_sac_act(ev2g_handle *h, ev2g_sac *s, const float *obs32, int n_rows, int deterministic, float *actions, float *mu, float *log_std, float *log_pi) {
-    if (int rc = sac_check(h, s, "ev2g_sac_act")) return rc;
-    if (!obs32 || !actions || n_rows <= 0) return fail(h, EV2G_ERR_ARG, "ev2g_sac_act: obs32 or actions is null, or n_rows is not positive");
+// ---- the entries SAC and TQC share, behind each object's own check (`who`: the entry's name) ----
+static int core_act(ev2g_handle *h, SacCore *s, const char *who, const float *obs32, int n_rows, int deterministic, float *actions, float *mu, float *log_std,
+                    float *log_pi) {
+    if (!obs32 || !actions || n_rows <= 0) return fail(h, EV2G_ERR_ARG, std::string(who) + ": obs32 or actions is null, or n_rows is not positive");
     return sac_act_launch(h, s, obs32, n_rows, !deterministic, actions, mu, log_std, log_pi);
 }
-
-int ev2g_sac_collect(ev2g_handle *h, ev2g_sac *s, int k_steps, int deterministic, const ev2g_transitions *tr) {
-    const char *who = "ev2g_sac_collect";
-    if (int rc = sac_check(h, s, who)) return rc;
+static int core_collect(ev2g_handle *h, SacCore *s, const char *who, int k_steps, int deterministic, const ev2g_transitions *tr) {
     if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
     if (s->plan.d_in != h->D || s->plan.d_out != h->P) return fail(h, EV2G_ERR_ARG, std::string(who) + ": actor shape != (obs dim, ports)");
     return collect_rows(h, who, k_steps, tr, nullptr,
                         [&](const float *obs, float *act, int n) { return sac_act_launch(h, s, obs, n, !deterministic, act, nullptr, nullptr, nullptr); });
 }
-
 // a flat buffer in the plan's layout into 8 + 6 n_critics host arrays (null entries skipped); actor_src null: the actor's entries are not written
 static int sac_read_flat(ev2g_handle *h, const SacPlan &p, const float *actor_src, const float *critic_src, float *const *out) {
     for (int i = 0; i < EV2G_SAC_ACTOR_ARRAYS; i++)
@@ -3392,24 +3412,58 @@ static int sac_read_flat(ev2g_handle *h, const SacPlan &p, const float *actor_sr
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return EV2G_OK;
 }
-int ev2g_sac_get_grads(ev2g_handle *h, ev2g_sac *s, float *const *out, float *g_log_ent_coef) {
-    if (int rc = sac_check(h, s, "ev2g_sac_get_grads")) return rc;
-    if (!out) return fail(h, EV2G_ERR_ARG, "ev2g_sac_get_grads: null argument");
+static int core_get_grads(ev2g_handle *h, SacCore *s, const char *who, float *const *out, float *g_log_ent_coef) {
+    if (!out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
     if (g_log_ent_coef) HIPCHK(h, hipMemcpyAsync(g_log_ent_coef, s->g_alpha, sizeof(float), hipMemcpyDeviceToHost, h->stream));
     return sac_read_flat(h, s->plan, s->grad, s->grad + s->plan.n_actor, out);
 }
-int ev2g_sac_get_weights(ev2g_handle *h, ev2g_sac *s, int target, float *const *out) {
-    if (int rc = sac_check(h, s, "ev2g_sac_get_weights")) return rc;
-    if (!out) return fail(h, EV2G_ERR_ARG, "ev2g_sac_get_weights: null argument");
+static int core_get_weights(ev2g_handle *h, SacCore *s, const char *who, int target, float *const *out) {
+    if (!out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
     return target ? sac_read_flat(h, s->plan, nullptr, s->target, out) : sac_read_flat(h, s->plan, s->theta, s->theta + s->plan.n_actor, out);
 }
-static int sac_read_rows(ev2g_handle *h, const char *who, float *dst, const float *src, float *dst2, const float *src2, int B, int want_B) {
+// n floats per row of the last gradient of a half (dst), and one per row (dst2, may be null)
+static int sac_read_rows(ev2g_handle *h, const char *who, float *dst, const float *src, float *dst2, const float *src2, int B, int want_B, int n = 1) {
     if (!dst) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
     if (B < 1 || B != want_B) return fail(h, EV2G_ERR_ARG, std::string(who) + ": B is not the batch size of the last gradient of that half");
-    HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)B * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (dst2) HIPCHK(h, hipMemcpyAsync(dst2, src2, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return EV2G_OK;
+}
+static int core_get_ent_coef(ev2g_handle *h, SacCore *s, const char *who, float *out3) {
+    if (!out3) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    HIPCHK(h, hipMemcpyAsync(out3, s->alpha, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+static int core_set_rate(ev2g_handle *h, SacCore *s, const char *who, double lr) {
+    if (int rc = fields_check(h, who, sac_rate_fields(lr))) return rc;
+    s->cfg.lr = lr;
+    return EV2G_OK;
+}
+static int core_counters(SacCore *s, int64_t *updates, int64_t *target_updates, uint64_t *next_draw, uint64_t *act_launches) {
+    if (updates) *updates = s->n;
+    if (target_updates) *target_updates = s->n_target;
+    if (next_draw) *next_draw = s->next_draw;
+    if (act_launches) *act_launches = s->act_n;
+    return EV2G_OK;
+}
+
+int ev2g_sac_act(ev2g_handle *h, ev2g_sac *s, const float *obs32, int n_rows, int deterministic, float *actions, float *mu, float *log_std, float *log_pi) {
+    if (int rc = sac_check(h, s, "ev2g_sac_act")) return rc;
+    return core_act(h, s, "ev2g_sac_act", obs32, n_rows, deterministic, actions, mu, log_std, log_pi);
+}
+int ev2g_sac_collect(ev2g_handle *h, ev2g_sac *s, int k_steps, int deterministic, const ev2g_transitions *tr) {
+    if (int rc = sac_check(h, s, "ev2g_sac_collect")) return rc;
+    return core_collect(h, s, "ev2g_sac_collect", k_steps, deterministic, tr);
+}
+int ev2g_sac_get_grads(ev2g_handle *h, ev2g_sac *s, float *const *out, float *g_log_ent_coef) {
+    if (int rc = sac_check(h, s, "ev2g_sac_get_grads")) return rc;
+    return core_get_grads(h, s, "ev2g_sac_get_grads", out, g_log_ent_coef);
+}
+int ev2g_sac_get_weights(ev2g_handle *h, ev2g_sac *s, int target, float *const *out) {
+    if (int rc = sac_check(h, s, "ev2g_sac_get_weights")) return rc;
+    return core_get_weights(h, s, "ev2g_sac_get_weights", target, out);
 }
 int ev2g_sac_get_y(ev2g_handle *h, ev2g_sac *s, float *y, float *log_pi_next, int B) {
     if (int rc = sac_check(h, s, "ev2g_sac_get_y")) return rc;
@@ -3421,16 +3475,11 @@ int ev2g_sac_get_log_pi(ev2g_handle *h, ev2g_sac *s, float *log_pi, int B) {
 }
 int ev2g_sac_get_ent_coef(ev2g_handle *h, ev2g_sac *s, float *out3) {
     if (int rc = sac_check(h, s, "ev2g_sac_get_ent_coef")) return rc;
-    if (!out3) return fail(h, EV2G_ERR_ARG, "ev2g_sac_get_ent_coef: null argument");
-    HIPCHK(h, hipMemcpyAsync(out3, s->alpha, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return EV2G_OK;
+    return core_get_ent_coef(h, s, "ev2g_sac_get_ent_coef", out3);
 }
 int ev2g_sac_set_rate(ev2g_handle *h, ev2g_sac *s, double lr) {
     if (int rc = sac_check(h, s, "ev2g_sac_set_rate")) return rc;
-    if (int rc = fields_check(h, "ev2g_sac_set_rate", sac_rate_fields(lr))) return rc;
-    s->cfg.lr = lr;
-    return EV2G_OK;
+    return core_set_rate(h, s, "ev2g_sac_set_rate", lr);
 }
 int ev2g_sac_seed(ev2g_handle *h, ev2g_sac *s, uint64_t seed, uint64_t first_draw) {
     if (int rc = sac_check(h, s, "ev2g_sac_seed")) return rc;
@@ -3444,11 +3493,7 @@ int ev2g_sac_act_seed(ev2g_handle *h, ev2g_sac *s, uint64_t seed, uint64_t first
 }
 int ev2g_sac_counters(ev2g_handle *h, ev2g_sac *s, int64_t *updates, int64_t *target_updates, uint64_t *next_draw, uint64_t *act_launches) {
     if (int rc = sac_check(h, s, "ev2g_sac_counters")) return rc;
-    if (updates) *updates = s->n;
-    if (target_updates) *target_updates = s->n_target;
-    if (next_draw) *next_draw = s->next_draw;
-    if (act_launches) *act_launches = s->act_n;
-    return EV2G_OK;
+    return core_counters(s, updates, target_updates, next_draw, act_launches);
 }
 
 int ev2g_host_sac_head(const float *mu, const float *log_std, const float *eps, int B, int P, float lo, float *a, float *a_env, float *log_pi) {
@@ -3469,6 +3514,199 @@ int ev2g_host_sac_y(const float *tq, const float *log_pi_next, const float *rewa
     if (!tq || !log_pi_next || !reward || !done || !y) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_y: null argument");
     if (B < 1 || n_critics < 1 || n_critics > 2) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_sac_y: B must be positive, n_critics 1 or 2");
     sac_host_y(tq, log_pi_next, reward, done, B, n_critics, gamma, log_ent_coef, y);
+    return EV2G_OK;
+}
+
+// ---- the TQC learner and its collection actor (ev2g_tqc.h): SacCore with quantile critics ----
+static int tqc_check(ev2g_handle *h, ev2g_tqc *t, const char *who) { return owned_check(h, &ev2g_handle::tqcs, t, "TQC learner", who, false); }
+
+int ev2g_tqc_default_config(ev2g_tqc_config *cfg) {
+    if (!cfg) return fail(nullptr, EV2G_ERR_ARG, "ev2g_tqc_default_config: cfg is null");
+    tqc_default_config(cfg);
+    return EV2G_OK;
+}
+
+int ev2g_tqc_create(ev2g_handle *h, const ev2g_tqc_config *cfg, int d_in, int h1, int h2, int d_out, float lo, const float *const *actor,
+                    const float *const *critics, uint64_t seed, ev2g_tqc **out) {
+    const char *who = "ev2g_tqc_create";
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    *out = nullptr;
+    if (!cfg || !actor || !critics) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (int rc = fields_check(h, who, tqc_fields(*cfg))) return rc;
+    const TqcPlan plan = plan_tqc(d_in, h1, h2, d_out, cfg->n_critics, cfg->n_quantiles, cfg->top_quantiles_to_drop_per_net);
+    if (plan.err) return fail(h, plan.err, plan.refusal);
+    if (lo != -1.0f && lo != 0.0f) return fail(h, EV2G_ERR_ARG, std::string(who) + ": lo must be -1 or 0");
+    for (int i = 0; i < EV2G_SAC_ACTOR_ARRAYS + 6 * cfg->n_critics; i++)
+        if (!(i < EV2G_SAC_ACTOR_ARRAYS ? actor[i] : critics[i - EV2G_SAC_ACTOR_ARRAYS])) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null weight array");
+    (void)hipSetDevice(h->device);
+    ev2g_tqc *t = new ev2g_tqc();
+    t->abi = "ev2g_tqc";
+    t->cfg = tqc_sac_config(*cfg); t->tq = plan; t->plan = plan;   // (plan.w_floats: SAC's blocks and TQC's behind them)
+    t->lo = lo; t->seed = seed; t->act_seed = seed;
+    t->target_entropy = sac_target_entropy(t->cfg, d_out);
+    t->dev = sac_dev(plan, lo);
+    t->lds = ev2g_sac_lds(t->dev).bytes;
+    return owned_created(h, &ev2g_handle::tqcs, t, sac_device_stage(h, t, actor, critics), out);
+}
+
+void ev2g_tqc_destroy(ev2g_handle *h, ev2g_tqc *t) { owned_destroy(h, &ev2g_handle::tqcs, t); }
+
+static void tqc_launch_target(ev2g_handle *h, const float *tq, const float *lp, const float *reward, const uint8_t *done, int B, int nc, int nq, int K, double gamma,
+                              const float *log_alpha, float *z) {
+    hipLaunchKernelGGL(ev2g_tqc_target_kernel, dim3((unsigned)((B + EV2G_TQC_ROWS - 1) / EV2G_TQC_ROWS)), dim3(64 * EV2G_TQC_ROWS), 0, h->stream, tq, lp, reward, done, B, nc,
+                       nq, K, gamma, log_alpha, z);
+}
+
+static int tqc_critic_stage(ev2g_handle *h, ev2g_tqc *t, const char *who, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                            const uint8_t *done, int B, float *losses) {
+    if (int rc = tqc_check(h, t, who)) return rc;
+    if (!obs || !actions || !reward || !next_obs || !done) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const TqcPlan &p = t->tq;
+    float *W = t->work, *L = losses ? losses : t->loss;
+    double *part = (double *)(W + p.w_part);
+    const unsigned nb = td3_blocks((long long)B * p.da), rb = (unsigned)((B + EV2G_TQC_ROWS - 1) / EV2G_TQC_ROWS);
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(nb), dim3(256), 0, h->stream, obs, actions, B, p.d_in, p.d_out, t->lo, W + p.w_xa);
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(nb), dim3(256), 0, h->stream, next_obs, (const float *)nullptr, B, p.d_in, p.d_out, t->lo, W + p.w_xb);
+    sac_actor_forward(h, t, next_obs, B, (uint64_t)t->next_draw + (uint64_t)B * (uint64_t)p.d_out, W + p.w_xb, W + p.w_lp2);
+    td3_forward(h, sac_critic_net(t, t->target, W + p.w_tq), W + p.w_xb, B, TD3_EPI_BIAS, p.nc);
+    const Td3Net cn = sac_critic_net(t, t->theta + p.n_actor, W + p.w_q);
+    td3_forward(h, cn, W + p.w_xa, B, TD3_EPI_BIAS, p.nc);
+    tqc_launch_target(h, W + p.w_tq, W + p.w_lp2, reward, done, B, p.nc, p.nq, p.K, t->cfg.gamma, t->alpha, W + p.w_z);
+    hipLaunchKernelGGL(ev2g_tqc_critic_head_kernel, dim3(rb), dim3(64 * EV2G_TQC_ROWS), 0, h->stream, (const float *)(W + p.w_z), (const float *)(W + p.w_q), B, p.nc, p.nq,
+                       p.K, W + p.w_dq, part);
+    hipLaunchKernelGGL(ev2g_tqc_loss_join_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)part, B, p.nc, p.nq, p.K, L);
+    td3_backward(h, cn, W + p.w_xa, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, t->grad + p.n_actor, nullptr, 0, 0, p.nc);
+    HIPCHK(h, hipGetLastError());
+    t->pending |= 1; t->last_B = B;
+    return EV2G_OK;
+}
+
+static int tqc_actor_stage(ev2g_handle *h, ev2g_tqc *t, const char *who, const float *obs, int B, float *losses) {
+    if (int rc = tqc_check(h, t, who)) return rc;
+    if (!obs) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = td3_batch_refusal(who, B);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const TqcPlan &p = t->tq;
+    float *W = t->work, *L = losses ? losses : t->loss;
+    double *part = (double *)(W + p.w_part);
+    const long long BP = (long long)B * p.d_out;
+    hipLaunchKernelGGL(ev2g_td3_concat_kernel, dim3(td3_blocks((long long)B * p.da)), dim3(256), 0, h->stream, obs, (const float *)nullptr, B, p.d_in, p.d_out, t->lo,
+                       W + p.w_xb);
+    sac_actor_forward(h, t, obs, B, (uint64_t)t->next_draw, W + p.w_xb, W + p.w_lp);
+    const Td3Net cn = sac_critic_net(t, t->theta + p.n_actor, W + p.w_q);
+    td3_forward(h, cn, W + p.w_xb, B, TD3_EPI_BIAS, p.nc);
+    hipLaunchKernelGGL(ev2g_tqc_actor_rows_kernel, dim3(td3_blocks((long long)p.nc * B * p.nq)), dim3(256), 0, h->stream, (const float *)(W + p.w_q), B, p.nc, p.nq,
+                       W + p.w_dq, part);
+    hipLaunchKernelGGL(ev2g_tqc_actor_head_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)part, (const float *)(W + p.w_lp), B, p.nc, p.nq,
+                       (const float *)t->alpha, t->target_entropy, t->cfg.ent_coef_auto ? 1 : 0, L, t->g_alpha);
+    // d mean_{j,i} q / da: every critic's input delta from the uniform output delta, summed j ascending
+    td3_backward(h, cn, W + p.w_xb, B, W + p.w_dq, W + p.w_d2, W + p.w_d1, nullptr, W + p.w_dxa, p.d_in, p.d_out, p.nc);
+    hipLaunchKernelGGL(ev2g_tqc_delta_sum_kernel, dim3(td3_blocks(BP)), dim3(256), 0, h->stream, (const float *)(W + p.w_dxa), p.nc, BP, W + p.w_g);
+    sac_actor_backward(h, t, obs, B, W + p.w_g, 1);
+    HIPCHK(h, hipGetLastError());
+    t->pending |= 2; t->last_actor_B = B;
+    return EV2G_OK;
+}
+
+int ev2g_tqc_critic_grad(ev2g_handle *h, ev2g_tqc *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                         const uint8_t *done, int B, float *losses) {
+    return tqc_critic_stage(h, t, "ev2g_tqc_critic_grad", obs, actions, reward, next_obs, done, B, losses);
+}
+int ev2g_tqc_actor_grad(ev2g_handle *h, ev2g_tqc *t, const float *obs, int B, float *losses) { return tqc_actor_stage(h, t, "ev2g_tqc_actor_grad", obs, B, losses); }
+int ev2g_tqc_apply(ev2g_handle *h, ev2g_tqc *t) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_apply")) return rc;
+    return sac_apply_stage(h, t, "ev2g_tqc_apply");
+}
+int ev2g_tqc_update(ev2g_handle *h, ev2g_tqc *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                    const uint8_t *done, int B, float *losses) {
+    const char *who = "ev2g_tqc_update";
+    if (int rc = tqc_critic_stage(h, t, who, obs, actions, reward, next_obs, done, B, losses)) return rc;
+    if (int rc = sac_apply_stage(h, t, who)) return rc;
+    if (int rc = tqc_actor_stage(h, t, who, obs, B, losses)) return rc;
+    return sac_apply_stage(h, t, who);
+}
+int ev2g_tqc_act(ev2g_handle *h, ev2g_tqc *t, const float *obs32, int n_rows, int deterministic, float *actions, float *mu, float *log_std, float *log_pi) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_act")) return rc;
+    return core_act(h, t, "ev2g_tqc_act", obs32, n_rows, deterministic, actions, mu, log_std, log_pi);
+}
+int ev2g_tqc_collect(ev2g_handle *h, ev2g_tqc *t, int k_steps, int deterministic, const ev2g_transitions *tr) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_collect")) return rc;
+    return core_collect(h, t, "ev2g_tqc_collect", k_steps, deterministic, tr);
+}
+int ev2g_tqc_get_grads(ev2g_handle *h, ev2g_tqc *t, float *const *out, float *g_log_ent_coef) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_get_grads")) return rc;
+    return core_get_grads(h, t, "ev2g_tqc_get_grads", out, g_log_ent_coef);
+}
+int ev2g_tqc_get_weights(ev2g_handle *h, ev2g_tqc *t, int target, float *const *out) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_get_weights")) return rc;
+    return core_get_weights(h, t, "ev2g_tqc_get_weights", target, out);
+}
+int ev2g_tqc_get_z(ev2g_handle *h, ev2g_tqc *t, float *z, float *log_pi_next, int B) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_get_z")) return rc;
+    return sac_read_rows(h, "ev2g_tqc_get_z", z, t->work + t->tq.w_z, log_pi_next, t->work + t->tq.w_lp2, B, t->last_B, t->tq.K);
+}
+int ev2g_tqc_get_log_pi(ev2g_handle *h, ev2g_tqc *t, float *log_pi, int B) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_get_log_pi")) return rc;
+    return sac_read_rows(h, "ev2g_tqc_get_log_pi", log_pi, t->work + t->tq.w_lp, nullptr, nullptr, B, t->last_actor_B);
+}
+int ev2g_tqc_get_ent_coef(ev2g_handle *h, ev2g_tqc *t, float *out3) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_get_ent_coef")) return rc;
+    return core_get_ent_coef(h, t, "ev2g_tqc_get_ent_coef", out3);
+}
+int ev2g_tqc_set_rate(ev2g_handle *h, ev2g_tqc *t, double lr) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_set_rate")) return rc;
+    return core_set_rate(h, t, "ev2g_tqc_set_rate", lr);
+}
+int ev2g_tqc_seed(ev2g_handle *h, ev2g_tqc *t, uint64_t seed, uint64_t first_draw) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_seed")) return rc;
+    t->seed = seed; t->next_draw = first_draw;
+    return EV2G_OK;
+}
+int ev2g_tqc_act_seed(ev2g_handle *h, ev2g_tqc *t, uint64_t seed, uint64_t first_launch) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_act_seed")) return rc;
+    t->act_seed = seed; t->act_n = first_launch;
+    return EV2G_OK;
+}
+int ev2g_tqc_counters(ev2g_handle *h, ev2g_tqc *t, int64_t *updates, int64_t *target_updates, uint64_t *next_draw, uint64_t *act_launches) {
+    if (int rc = tqc_check(h, t, "ev2g_tqc_counters")) return rc;
+    return core_counters(t, updates, target_updates, next_draw, act_launches);
+}
+
+// the quantile arguments of ev2g_tqc_truncate and of the host twins: plan_tqc's refusal on the smallest network, or B's
+static std::string tqc_atoms_refusal(const char *who, int B, int nc, int nq, int drop) {
+    const TqcPlan p = plan_tqc(1, 1, 1, 1, nc, nq, drop);
+    if (p.err) return std::string(who) + ": " + p.refusal;
+    return td3_batch_refusal(who, B);
+}
+int ev2g_tqc_truncate(ev2g_handle *h, const float *tq, const float *log_pi_next, const float *reward, const uint8_t *done, int B, int n_critics,
+                      int n_quantiles, int top_quantiles_to_drop, double gamma, const float *log_ent_coef, float *z_out) {
+    const char *who = "ev2g_tqc_truncate";
+    if (!h) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    if (!tq || !log_pi_next || !reward || !done || !log_ent_coef || !z_out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = tqc_atoms_refusal(who, B, n_critics, n_quantiles, top_quantiles_to_drop);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    (void)hipSetDevice(h->device);
+    tqc_launch_target(h, tq, log_pi_next, reward, done, B, n_critics, n_quantiles, n_critics * (n_quantiles - top_quantiles_to_drop), gamma, log_ent_coef, z_out);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_host_tqc_target(const float *tq, const float *log_pi_next, const float *reward, const uint8_t *done, int B, int n_critics, int n_quantiles,
+                         int top_quantiles_to_drop, double gamma, float log_ent_coef, float *z) {
+    if (!tq || !log_pi_next || !reward || !done || !z) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_tqc_target: null argument");
+    const std::string refusal = tqc_atoms_refusal("ev2g_host_tqc_target", B, n_critics, n_quantiles, top_quantiles_to_drop);
+    if (!refusal.empty()) return fail(nullptr, EV2G_ERR_ARG, refusal);
+    tqc_host_target(tq, log_pi_next, reward, done, B, n_critics, n_quantiles, top_quantiles_to_drop, gamma, log_ent_coef, z);
+    return EV2G_OK;
+}
+int ev2g_host_tqc_critic_head(const float *z, const float *q, int B, int n_critics, int n_quantiles, int top_quantiles_to_drop, float *dq,
+                              float *critic_loss) {
+    if (!z || !q || !dq || !critic_loss) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_tqc_critic_head: null argument");
+    const std::string refusal = tqc_atoms_refusal("ev2g_host_tqc_critic_head", B, n_critics, n_quantiles, top_quantiles_to_drop);
+    if (!refusal.empty()) return fail(nullptr, EV2G_ERR_ARG, refusal);
+    *critic_loss = tqc_host_critic_head(z, q, B, n_critics, n_quantiles, n_critics * (n_quantiles - top_quantiles_to_drop), dq);
     return EV2G_OK;
 }
 

@@ -36,6 +36,26 @@ struct SacPlan {
     long long w_xa = 0, w_xb = 0, w_ah1 = 0, w_ah2 = 0, w_head = 0, w_eps = 0, w_a = 0, w_lp = 0, w_lp2 = 0, w_ch1 = 0, w_ch2 = 0, w_q = 0, w_tq = 0, w_y = 0,
               w_dq = 0, w_d2 = 0, w_d1 = 0, w_dxa = 0, w_dhead = 0, w_e2z = 0, w_e2 = 0, w_e1 = 0, w_floats = 0;
 };
+// the layout of an accepted shape: n_critics critics of q_out outputs each (SAC: 1; TQC's quantile critics: n_quantiles, ev2g_tqc_host.h)
+inline void sac_layout(SacPlan &p, int d_in, int h1, int h2, int d_out, int n_critics, int q_out) {
+    p.d_in = d_in; p.h1 = h1; p.h2 = h2; p.d_out = d_out; p.nc = n_critics; p.da = d_in + d_out;
+    const int ar[4] = {h1, h2, d_out, d_out}, ac[4] = {d_in, h1, h2, h2}, cr[3] = {h1, h2, q_out}, cc[3] = {p.da, h1, h2};
+    for (int i = 0; i < 4; i++) { p.aoff[2 * i + 1] = p.aoff[2 * i] + ar[i] * ac[i]; p.aoff[2 * i + 2] = p.aoff[2 * i + 1] + ar[i]; }
+    for (int i = 0; i < 3; i++) { p.coff[2 * i + 1] = p.coff[2 * i] + cr[i] * cc[i]; p.coff[2 * i + 2] = p.coff[2 * i + 1] + cr[i]; }
+    p.n_actor = p.aoff[EV2G_SAC_ACTOR_ARRAYS]; p.n_critic = p.coff[6]; p.n_params = p.n_actor + p.nc * p.n_critic; p.head_block = d_out * h2 + d_out;
+    p.k1 = mlp_round_up(d_in, 8); p.n1 = mlp_round_up(h1, 32); p.n2 = mlp_round_up(h2, 32); p.n3 = mlp_round_up(d_out, 32);
+    const long long R = EV2G_TD3_MAX_BATCH;
+    long long o = 0;
+    auto take = [&o](long long n) { const long long at = o; o += n; return at; };
+    p.w_xa = take(R * p.da); p.w_xb = take(R * p.da);
+    p.w_ah1 = take(R * h1); p.w_ah2 = take(R * h2); p.w_head = take(2 * R * d_out); p.w_eps = take(R * d_out); p.w_a = take(R * d_out);
+    p.w_lp = take(R); p.w_lp2 = take(R);
+    p.w_ch1 = take(p.nc * R * h1); p.w_ch2 = take(p.nc * R * h2);
+    p.w_q = take(p.nc * R * q_out); p.w_tq = take(p.nc * R * q_out); p.w_y = take(R); p.w_dq = take(p.nc * R * q_out);
+    p.w_d2 = take(p.nc * R * h2); p.w_d1 = take(p.nc * R * h1); p.w_dxa = take(p.nc * R * d_out);
+    p.w_dhead = take(2 * R * d_out); p.w_e2z = take(2 * R * h2); p.w_e2 = take(R * h2); p.w_e1 = take(R * h1);
+    p.w_floats = o;
+}
 inline SacPlan plan_sac(int d_in, int h1, int h2, int d_out, int n_critics) {
     SacPlan p;
     auto refuse = [&p](const char *what, int v, int lo, int hi) {
@@ -48,23 +68,7 @@ inline SacPlan plan_sac(int d_in, int h1, int h2, int d_out, int n_critics) {
     if (h2 < 1 || h2 > EV2G_SAC_MAX_HIDDEN) return refuse("h2", h2, 1, EV2G_SAC_MAX_HIDDEN);
     if (d_out < 1 || d_out > EV2G_SAC_MAX_OUT) return refuse("d_out", d_out, 1, EV2G_SAC_MAX_OUT);
     if (n_critics < 1 || n_critics > 2) return refuse("n_critics", n_critics, 1, 2);
-    p.d_in = d_in; p.h1 = h1; p.h2 = h2; p.d_out = d_out; p.nc = n_critics; p.da = d_in + d_out;
-    const int ar[4] = {h1, h2, d_out, d_out}, ac[4] = {d_in, h1, h2, h2}, cr[3] = {h1, h2, 1}, cc[3] = {p.da, h1, h2};
-    for (int i = 0; i < 4; i++) { p.aoff[2 * i + 1] = p.aoff[2 * i] + ar[i] * ac[i]; p.aoff[2 * i + 2] = p.aoff[2 * i + 1] + ar[i]; }
-    for (int i = 0; i < 3; i++) { p.coff[2 * i + 1] = p.coff[2 * i] + cr[i] * cc[i]; p.coff[2 * i + 2] = p.coff[2 * i + 1] + cr[i]; }
-    p.n_actor = p.aoff[EV2G_SAC_ACTOR_ARRAYS]; p.n_critic = p.coff[6]; p.n_params = p.n_actor + p.nc * p.n_critic; p.head_block = d_out * h2 + d_out;
-    p.k1 = mlp_round_up(d_in, 8); p.n1 = mlp_round_up(h1, 32); p.n2 = mlp_round_up(h2, 32); p.n3 = mlp_round_up(d_out, 32);
-    const long long R = EV2G_TD3_MAX_BATCH;
-    long long o = 0;
-    auto take = [&o](long long n) { const long long at = o; o += n; return at; };
-    p.w_xa = take(R * p.da); p.w_xb = take(R * p.da);
-    p.w_ah1 = take(R * h1); p.w_ah2 = take(R * h2); p.w_head = take(2 * R * d_out); p.w_eps = take(R * d_out); p.w_a = take(R * d_out);
-    p.w_lp = take(R); p.w_lp2 = take(R);
-    p.w_ch1 = take(p.nc * R * h1); p.w_ch2 = take(p.nc * R * h2);
-    p.w_q = take(p.nc * R); p.w_tq = take(p.nc * R); p.w_y = take(R); p.w_dq = take(p.nc * R);
-    p.w_d2 = take(p.nc * R * h2); p.w_d1 = take(p.nc * R * h1); p.w_dxa = take(p.nc * R * d_out);
-    p.w_dhead = take(2 * R * d_out); p.w_e2z = take(2 * R * h2); p.w_e2 = take(R * h2); p.w_e1 = take(R * h1);
-    p.w_floats = o;
+    sac_layout(p, d_in, h1, h2, d_out, n_critics, 1);
     return p;
 }
 inline SacDev sac_dev(const SacPlan &p, float lo) {

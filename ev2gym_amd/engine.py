@@ -171,6 +171,27 @@ def load_library(path: Optional[str] = None):
         "ev2g_host_sac_head": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
         "ev2g_host_sac_head_back": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),
         "ev2g_host_sac_y": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, dbl, C.c_float, vp]),
+        "ev2g_tqc_default_config": (C.c_int, [C.POINTER(_abi.TqcConfigC)]),
+        "ev2g_tqc_create": (C.c_int, [vp, C.POINTER(_abi.TqcConfigC)] + [C.c_int] * 4 + [C.c_float, vp, vp, C.c_uint64, C.POINTER(vp)]),
+        "ev2g_tqc_destroy": (None, [vp, vp]),
+        "ev2g_tqc_update": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_tqc_critic_grad": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_tqc_actor_grad": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+        "ev2g_tqc_apply": (C.c_int, [vp, vp]),
+        "ev2g_tqc_act": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "ev2g_tqc_collect": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+        "ev2g_tqc_get_grads": (C.c_int, [vp, vp, vp, vp]),
+        "ev2g_tqc_get_weights": (C.c_int, [vp, vp, C.c_int, vp]),
+        "ev2g_tqc_get_z": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "ev2g_tqc_get_log_pi": (C.c_int, [vp, vp, vp, C.c_int]),
+        "ev2g_tqc_get_ent_coef": (C.c_int, [vp, vp, vp]),
+        "ev2g_tqc_set_rate": (C.c_int, [vp, vp, dbl]),
+        "ev2g_tqc_seed": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ev2g_tqc_act_seed": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ev2g_tqc_counters": (C.c_int, [vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "ev2g_tqc_truncate": (C.c_int, [vp] * 5 + [C.c_int] * 4 + [dbl, vp, vp]),
+        "ev2g_host_tqc_target": (C.c_int, [vp] * 4 + [C.c_int] * 4 + [dbl, C.c_float, vp]),
+        "ev2g_host_tqc_critic_head": (C.c_int, [vp, vp] + [C.c_int] * 4 + [vp, vp]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -241,7 +262,10 @@ EXPORTED_SYMBOLS = [
     "ev2g_host_replay_indices", "ev2g_host_td3_target", "ev2g_host_polyak",
     "ev2g_sac_default_config", "ev2g_sac_create", "ev2g_sac_destroy", "ev2g_sac_update", "ev2g_sac_critic_grad", "ev2g_sac_actor_grad", "ev2g_sac_apply",
     "ev2g_sac_act", "ev2g_sac_collect", "ev2g_sac_get_grads", "ev2g_sac_get_weights", "ev2g_sac_get_y", "ev2g_sac_get_log_pi", "ev2g_sac_get_ent_coef",
-    "ev2g_sac_set_rate", "ev2g_sac_seed", "ev2g_sac_act_seed", "ev2g_sac_counters", "ev2g_host_sac_head", "ev2g_host_sac_head_back", "ev2g_host_sac_y"]
+    "ev2g_sac_set_rate", "ev2g_sac_seed", "ev2g_sac_act_seed", "ev2g_sac_counters", "ev2g_host_sac_head", "ev2g_host_sac_head_back", "ev2g_host_sac_y",
+    "ev2g_tqc_default_config", "ev2g_tqc_create", "ev2g_tqc_destroy", "ev2g_tqc_update", "ev2g_tqc_critic_grad", "ev2g_tqc_actor_grad", "ev2g_tqc_apply",
+    "ev2g_tqc_act", "ev2g_tqc_collect", "ev2g_tqc_get_grads", "ev2g_tqc_get_weights", "ev2g_tqc_get_z", "ev2g_tqc_get_log_pi", "ev2g_tqc_get_ent_coef",
+    "ev2g_tqc_set_rate", "ev2g_tqc_seed", "ev2g_tqc_act_seed", "ev2g_tqc_counters", "ev2g_tqc_truncate", "ev2g_host_tqc_target", "ev2g_host_tqc_critic_head"]
 
 
 def _ptr(x):
@@ -1004,6 +1028,107 @@ class Engine:
         self._check(self._lib.ev2g_sac_counters(self._h, s, C.byref(n), C.byref(t), C.byref(d), C.byref(a)))
         return int(n.value), int(t.value), int(d.value), int(a.value)
 
+    # ---- the TQC learner and its collection actor (include/ev2g.h: ev2g_tqc_*) ----------------------------------------------------------------
+    def tqc_create(self, actor, critics, lo, seed=0, **config):
+        """A TQC learner with its stochastic collection actor (ev2g_tqc_create): actor eight host arrays, critics a list of six-array lists
+        (the last layer with n_quantiles rows); config overrides fields of sb3_contrib's defaults (ev2g_tqc_config).  Freed by tqc_destroy or
+        with the engine."""
+        cfg = tqc_default_config()
+        ints = ("n_critics", "target_update_interval", "ent_coef_auto", "target_entropy_auto", "n_quantiles", "top_quantiles_to_drop_per_net")
+        for k, v in config.items():
+            if k not in dict(_abi.TqcConfigC._fields_):
+                raise TypeError(f"tqc_create: unknown config field {k}")
+            setattr(cfg, k, int(v) if k in ints else float(v))
+        actor = [np.ascontiguousarray(a, np.float32) for a in actor]
+        flat = [np.ascontiguousarray(a, np.float32) for c in critics for a in c]
+        if len(actor) != 8 or len(flat) != 6 * cfg.n_critics:
+            raise ValueError(f"tqc_create: eight actor arrays and six per critic for {cfg.n_critics} critics are needed")
+        (h1, d_in), h2, d_out = actor[0].shape, actor[2].shape[0], actor[4].shape[0]
+        for a, shape in zip(actor + flat, _abi.tqc_param_shapes(d_in, h1, h2, d_out, cfg.n_critics, cfg.n_quantiles)):
+            if a.shape != shape:
+                raise ValueError(f"tqc_create: a weight array has shape {a.shape}, expected {shape}")
+        pa, pc = (C.c_void_p * 8)(*[a.ctypes.data for a in actor]), (C.c_void_p * max(len(flat), 1))(*[a.ctypes.data for a in flat])
+        out = C.c_void_p()
+        self._check(self._lib.ev2g_tqc_create(self._h, C.byref(cfg), d_in, h1, h2, d_out, float(lo), pa, pc, int(seed) & (2 ** 64 - 1), C.byref(out)))
+        return out.value
+
+    def tqc_destroy(self, t):
+        if t and self._h:
+            self._lib.ev2g_tqc_destroy(self._h, t)
+
+    def tqc_update(self, t, obs, actions, reward, next_obs, done, B, losses=None):
+        """One gradient step on contiguous DEVICE batch arrays (ev2g_tqc_update); losses: float32 [4] DEVICE or None."""
+        self._check(self._lib.ev2g_tqc_update(self._h, t, _ptr(obs), _ptr(actions), _ptr(reward), _ptr(next_obs), _ptr(done), int(B), _ptr(losses)))
+
+    def tqc_critic_grad(self, t, obs, actions, reward, next_obs, done, B, losses=None):
+        self._check(self._lib.ev2g_tqc_critic_grad(self._h, t, _ptr(obs), _ptr(actions), _ptr(reward), _ptr(next_obs), _ptr(done), int(B), _ptr(losses)))
+
+    def tqc_actor_grad(self, t, obs, B, losses=None):
+        self._check(self._lib.ev2g_tqc_actor_grad(self._h, t, _ptr(obs), int(B), _ptr(losses)))
+
+    def tqc_apply(self, t):
+        self._check(self._lib.ev2g_tqc_apply(self._h, t))
+
+    def tqc_act(self, t, obs32, n_rows, actions, deterministic=False, mu=None, log_std=None, log_pi=None):
+        """The collection actor on n_rows DEVICE observation rows (ev2g_tqc_act): env actions in [lo, 1]; mu, raw log_std, log pi optional."""
+        self._check(self._lib.ev2g_tqc_act(self._h, t, _ptr(obs32), int(n_rows), int(bool(deterministic)), _ptr(actions), _ptr(mu), _ptr(log_std), _ptr(log_pi)))
+
+    def tqc_collect(self, t, k, obs, actions, reward, done, mask, deterministic=False):
+        """k x (TQC actor -> env step) into the caller's DEVICE arrays (ev2g_tqc_collect; the arrays of collect())."""
+        tr = (C.c_void_p * 5)(_ptr(obs), _ptr(actions), _ptr(reward), _ptr(done), _ptr(mask))
+        self._check(self._lib.ev2g_tqc_collect(self._h, t, int(k), int(bool(deterministic)), C.cast(tr, C.c_void_p)))
+
+    def tqc_get_grads(self, t, shape):
+        """(the last gradient of each half as 8 + 6 n_critics host float32 arrays, the gradient of log_ent_coef); shape: (d_in, h1, h2, d_out,
+        n_critics, n_quantiles)."""
+        out = [np.empty(sh, np.float32) for sh in _abi.tqc_param_shapes(*shape)]
+        g = np.zeros(1, np.float32)
+        self._check(self._lib.ev2g_tqc_get_grads(self._h, t, (C.c_void_p * len(out))(*[a.ctypes.data for a in out]), g.ctypes.data))
+        return out, float(g[0])
+
+    def tqc_get_weights(self, t, shape, target=False):
+        """The masters as 8 + 6 n_critics host float32 arrays in sb3_contrib's parameter order, or (target) the target critics' 6 n_critics."""
+        out = [np.empty(sh, np.float32) for sh in _abi.tqc_param_shapes(*shape)]
+        self._check(self._lib.ev2g_tqc_get_weights(self._h, t, int(bool(target)), (C.c_void_p * len(out))(*[a.ctypes.data for a in out])))
+        return out[8:] if target else out
+
+    def tqc_get_z(self, t, B, K):
+        """(z [B, K], log pi' [B]) of the last critic gradient."""
+        z, lp = np.empty((int(B), int(K)), np.float32), np.empty(int(B), np.float32)
+        self._check(self._lib.ev2g_tqc_get_z(self._h, t, z.ctypes.data, lp.ctypes.data, int(B)))
+        return z, lp
+
+    def tqc_get_log_pi(self, t, B):
+        lp = np.empty(int(B), np.float32)
+        self._check(self._lib.ev2g_tqc_get_log_pi(self._h, t, lp.ctypes.data, int(B)))
+        return lp
+
+    def tqc_get_ent_coef(self, t):
+        """float32 [3]: log_ent_coef and its Adam moments m, v."""
+        out = np.empty(3, np.float32)
+        self._check(self._lib.ev2g_tqc_get_ent_coef(self._h, t, out.ctypes.data))
+        return out
+
+    def tqc_set_rate(self, t, lr):
+        self._check(self._lib.ev2g_tqc_set_rate(self._h, t, float(lr)))
+
+    def tqc_seed(self, t, seed, first_draw=0):
+        self._check(self._lib.ev2g_tqc_seed(self._h, t, int(seed) & (2 ** 64 - 1), int(first_draw)))
+
+    def tqc_act_seed(self, t, seed, first_launch=0):
+        self._check(self._lib.ev2g_tqc_act_seed(self._h, t, int(seed) & (2 ** 64 - 1), int(first_launch)))
+
+    def tqc_counters(self, t):
+        """(updates applied, Polyak steps among them, the learner's next draw base, the collection stream's launch counter)."""
+        n, tu, d, a = C.c_int64(0), C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.ev2g_tqc_counters(self._h, t, C.byref(n), C.byref(tu), C.byref(d), C.byref(a)))
+        return int(n.value), int(tu.value), int(d.value), int(a.value)
+
+    def tqc_truncate(self, tq, log_pi_next, reward, done, B, n_critics, n_quantiles, drop, gamma, log_ent_coef, z_out):
+        """The sort-and-truncate kernel alone on DEVICE arrays (ev2g_tqc_truncate): tq [n_critics][B, n_quantiles] -> z_out [B, K]."""
+        self._check(self._lib.ev2g_tqc_truncate(self._h, _ptr(tq), _ptr(log_pi_next), _ptr(reward), _ptr(done), int(B), int(n_critics), int(n_quantiles), int(drop),
+                                                float(gamma), _ptr(log_ent_coef), _ptr(z_out)))
+
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
         if out is not None:
@@ -1295,3 +1420,32 @@ def host_sac_y(tq, log_pi_next, reward, done, gamma, log_ent_coef):
     _host_call(load_library().ev2g_host_sac_y(tq.ctypes.data, lp.ctypes.data, reward.ctypes.data, done.ctypes.data, tq.shape[1], tq.shape[0], float(gamma),
                                               float(log_ent_coef), y.ctypes.data))
     return y
+
+
+def tqc_default_config():
+    """sb3_contrib's defaults of TQC as an _abi.TqcConfigC (ev2g_tqc_default_config)."""
+    cfg = _abi.TqcConfigC()
+    _host_call(load_library().ev2g_tqc_default_config(C.byref(cfg)))
+    return cfg
+
+
+def host_tqc_target(tq, log_pi_next, reward, done, drop, gamma, log_ent_coef):
+    """Host twin of the sort-and-truncate kernel (ev2g_host_tqc_target): z [B, K] float32 from the target critics' atoms tq [n_critics, B,
+    n_quantiles] and log pi' [B]."""
+    tq, lp, reward = (np.ascontiguousarray(a, np.float32) for a in (tq, log_pi_next, reward))
+    done = np.ascontiguousarray(done, np.uint8)
+    nc, B, nq = tq.shape
+    z = np.empty((B, max(nc * (nq - int(drop)), 0)), np.float32)
+    _host_call(load_library().ev2g_host_tqc_target(tq.ctypes.data, lp.ctypes.data, reward.ctypes.data, done.ctypes.data, B, nc, nq, int(drop), float(gamma),
+                                                   float(log_ent_coef), z.ctypes.data))
+    return z
+
+
+def host_tqc_critic_head(z, q, drop):
+    """Host twin of the quantile Huber head (ev2g_host_tqc_critic_head): (dq [n_critics, B, n_quantiles], critic_loss) float32 from z [B, K] and
+    the critics' outputs q [n_critics, B, n_quantiles]."""
+    z, q = np.ascontiguousarray(z, np.float32), np.ascontiguousarray(q, np.float32)
+    nc, B, nq = q.shape
+    dq, loss = np.empty_like(q), np.zeros(1, np.float32)
+    _host_call(load_library().ev2g_host_tqc_critic_head(z.ctypes.data, q.ctypes.data, B, nc, nq, int(drop), dq.ctypes.data, loss.ctypes.data))
+    return dq, float(loss[0])

@@ -22,7 +22,8 @@ The Gaussian term is the reduced form of `Normal(mu, sigma).log_prob(mu + sigma 
 
 `sac_update_numpy` (with `sac_critic_numpy` / `sac_actor_numpy`) is the float64 restatement with analytic backprop, no torch: the numerics
 reference the tests hold the kernels to.  Refused with a message: `use_sde`, `action_noise`, a `learning_starts` warm-up, schedule objects (drive
-one with `set_rate()`), `optimize_memory_usage`, TQC, `ent_coef` strings other than `auto` / `auto_<float>`.
+one with `set_rate()`), `optimize_memory_usage`, TQC's arguments (TQC is `ev2gym_amd.tqc`, over this module's actor and learner class), `ent_coef`
+strings other than `auto` / `auto_<float>`.
 """
 from __future__ import annotations
 
@@ -218,15 +219,28 @@ class SACLearner:
     parameters back under SB3's keys; `close()` (or closing the collector or the engine, in any order) frees the device object."""
 
     PRESET = dict(n_critics=2, lr=3e-4, tau=0.005, gamma=0.99, batch_size=256, target_update_interval=1, ent_coef="auto", target_entropy="auto")
+    # what ev2gym_amd.tqc.TQCLearner overrides: the entries' prefix (engine.<ABI>_create, ...; the collector's attribute of that name), the collector's name, the keys refused as TQC's
+    ABI, COLLECTOR = "sac", "SACCollector"
+    QUANTILE_KEYS = ("top_quantiles_to_drop_per_net", "n_quantiles")
+    OUT_OF_SCOPE = ("state-dependent exploration, exploration noise, a random warm-up, the replay buffer's memory options and TQC's quantile critics are "
+                    "out of scope")
+
+    def _eng(self, entry):
+        return getattr(self.eng, f"{self.ABI}_{entry}")
+
+    def _init_critics(self, D, P, h1, h2, seed, cfg):
+        return [init_critic_weights(D, P, seed=int(seed) + 1 + j, h1=h1, h2=h2) for j in range(int(cfg["n_critics"]))]
+
+    def _shape(self, D, h1, h2, P, cfg):
+        return (D, h1, h2, P, int(cfg["n_critics"]))
 
     def __init__(self, collector, actor=None, critics=None, seed=0, sample_seed=None, **kw):
         name = type(self).__name__
         for k, bad in (("use_sde", lambda v: bool(v)), ("use_sde_at_warmup", lambda v: bool(v)), ("action_noise", lambda v: v is not None),
                        ("learning_starts", lambda v: int(v) != 0), ("optimize_memory_usage", lambda v: bool(v)), ("handle_timeout_termination", lambda v: bool(v)),
-                       ("top_quantiles_to_drop_per_net", lambda v: True), ("n_quantiles", lambda v: True)):
+                       *((k, lambda v: True) for k in self.QUANTILE_KEYS)):
             if k in kw and bad(kw.pop(k)):
-                raise ValueError(f"{name}: {k} is not supported (state-dependent exploration, exploration noise, a random warm-up, the replay buffer's "
-                                 "memory options and TQC's quantile critics are out of scope; see the module docstring)")
+                raise ValueError(f"{name}: {k} is not supported ({self.OUT_OF_SCOPE}; see the module docstring)")
         cfg = dict(self.PRESET, **{k: kw.pop(k) for k in list(kw) if k in self.PRESET or k in ("beta1", "beta2", "adam_eps")})
         if kw:
             raise ValueError(f"{name}: {sorted(kw)[0]} is not supported (see the module docstring)")
@@ -243,23 +257,22 @@ class SACLearner:
         self.collector, self.eng = collector, collector.eng
         if getattr(getattr(collector, "learner", None), "learner", None):
             raise ValueError(f"{name}: the collector already has a learner")
-        if not hasattr(collector, "sac"):
-            raise ValueError(f"{name}: the collector is not a SACCollector (a DeviceReplayCollector owns a deterministic policy object)")
+        if not hasattr(collector, self.ABI):
+            raise ValueError(f"{name}: the collector is not a {self.COLLECTOR} (a DeviceReplayCollector owns a deterministic policy object)")
         if collector.cap - 1 > MAX_BLOCKS:
             raise ValueError(f"{name}: the collector's ring holds up to {collector.cap - 1} complete episodes, the sampler's table {MAX_BLOCKS}: "
                              f"capacity_episodes must be at most {MAX_BLOCKS + 1}")
         actor = [np.ascontiguousarray(a, np.float32) for a in (actor if actor is not None else collector.weights)]
         (h1, D), h2, P = actor[0].shape, actor[2].shape[0], actor[4].shape[0]
-        n_critics = int(cfg["n_critics"])
+        self.shape = self._shape(D, h1, h2, P, cfg)
         if critics is None:
-            critics = [init_critic_weights(D, P, seed=int(seed) + 1 + j, h1=h1, h2=h2) for j in range(n_critics)]
-        self.shape = (D, h1, h2, P, n_critics)
+            critics = self._init_critics(D, P, h1, h2, seed, cfg)
         self.cfg, self.lr = cfg, float(cfg["lr"])
         self.sample_seed = int(seed if sample_seed is None else sample_seed)
         self.sample_counter = 0     # the draw counter of the next sampled batch (ev2g_replay_sample)
         self.num_timesteps = 0
         self.last_losses = None
-        self.learner = self.eng.sac_create(actor, critics, collector.lo, seed=seed, ent_coef=ent0, ent_coef_auto=int(self.ent_coef_auto),
+        self.learner = self._eng("create")(actor, critics, collector.lo, seed=seed, ent_coef=ent0, ent_coef_auto=int(self.ent_coef_auto),
                                            target_entropy_auto=int(te == "auto"), target_entropy=0.0 if te == "auto" else float(te), **cfg)
         collector.learner = self
 
@@ -268,11 +281,11 @@ class SACLearner:
     def set_rate(self, lr):
         """The learning rate of the following updates, of all three optimisers (how a schedule is driven from Python)."""
         self.lr = float(lr)
-        self.eng.sac_set_rate(self.learner, self.lr)
+        self._eng("set_rate")(self.learner, self.lr)
 
     def counters(self):
         """(updates, Polyak steps among them, the learner's next draw base, the collection actor's sampling launches)."""
-        return self.eng.sac_counters(self.learner)
+        return self._eng("counters")(self.learner)
 
     def complete_blocks(self):
         """The ring's complete blocks, newest first: the list the sampler draws from."""
@@ -299,13 +312,13 @@ class SACLearner:
         blocks = self.complete_blocks()
         if not blocks:
             raise RuntimeError("train: the replay ring holds no complete episode (collector.collect_episode() first)")
-        c, eng = self.collector, self.eng
+        c, eng, update = self.collector, self.eng, self._eng("update")
         obs, act, rew, nxt, done, losses = self._batch_buffers(B, steps)
         ring = [(c.obs[b], c.actions[b], c.reward[b], c.done[b]) for b in blocks]
         for k in range(steps):
             eng.replay_sample(ring, c.T, c.E, c.D, c.P, B, self.sample_seed, self.sample_counter, obs, act, rew, nxt, done)
             self.sample_counter += 1
-            eng.sac_update(self.learner, obs, act, rew, nxt, done, B, losses.at(4 * k))
+            update(self.learner, obs, act, rew, nxt, done, B, losses.at(4 * k))
         self.last_losses = losses.to_host()   # (synchronises)
         mean = self.last_losses.astype(np.float64).mean(axis=0)
         return dict(critic_loss=float(mean[0]), actor_loss=float(mean[1]), ent_coef_loss=float(mean[2]), ent_coef=float(mean[3]), n_updates=self.counters()[0])
@@ -323,18 +336,18 @@ class SACLearner:
 
     def ent_coef(self):
         """alpha = exp(log_ent_coef) as it stands."""
-        return float(np.exp(np.float64(self.eng.sac_get_ent_coef(self.learner)[0])))
+        return float(np.exp(np.float64(self._eng("get_ent_coef")(self.learner)[0])))
 
     def get_weights(self, target=False):
         """(actor eight arrays, [critic six arrays, ...]) read back from the device, or (target) (None, the target critics)."""
-        flat = self.eng.sac_get_weights(self.learner, self.shape, target)
+        flat = self._eng("get_weights")(self.learner, self.shape, target)
         if target:
             return None, [flat[6 * j:6 + 6 * j] for j in range(self.shape[4])]
         return flat[:8], [flat[8 + 6 * j:14 + 6 * j] for j in range(self.shape[4])]
 
     def get_grads(self):
         """(actor eight arrays, [critic six arrays, ...], the gradient of log_ent_coef) of the last gradient of each half."""
-        flat, g = self.eng.sac_get_grads(self.learner, self.shape)
+        flat, g = self._eng("get_grads")(self.learner, self.shape)
         return flat[:8], [flat[8 + 6 * j:14 + 6 * j] for j in range(self.shape[4])], g
 
     def state_dict(self):
@@ -345,12 +358,12 @@ class SACLearner:
         for prefix, cs in (("critic", critics), ("critic_target", self.get_weights(True)[1])):
             for j, c in enumerate(cs):
                 out.update({f"{prefix}.qf{j}.{k}": a for k, a in zip(CRITIC_KEYS, c)})
-        out["log_ent_coef"] = self.eng.sac_get_ent_coef(self.learner)[:1].copy()
+        out["log_ent_coef"] = self._eng("get_ent_coef")(self.learner)[:1].copy()
         return out
 
     def close(self):
         if self.learner:
-            self.eng.sac_destroy(self.learner)   # (nothing happens if the engine already took it along)
+            self._eng("destroy")(self.learner)   # (nothing happens if the engine already took it along)
         self.learner = None
         if getattr(self.collector, "learner", None) is self:
             self.collector.learner = None

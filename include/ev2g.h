@@ -847,8 +847,8 @@ int ev2g_host_a2c_head(const float *mean, const float *value, const float *actio
  * created with (every packing of csrc/ev2g_policy_host.h, padding untouched), so the collector reads the new actor without the weights leaving
  * the device.  A policy has at most one learner (EV2G_ERR_STATE for a second); the learner is owned by the handle and ends with it, with
  * ev2g_td3_destroy, or with ev2g_mlp_destroy of its policy.  Rollout graphs captured for the policy stay valid (the images keep their addresses).
- * Not reproduced: action_noise, learning_starts, schedule objects (ev2g_td3_set_rate between calls drives one), TQC.  SAC is not this learner's
- * either: it has its own object with a stochastic actor, ev2g_sac_* below. */
+ * Not reproduced: action_noise, learning_starts, schedule objects (ev2g_td3_set_rate between calls drives one).  SAC and TQC are not this
+ * learner's: each has its own object with a stochastic actor, ev2g_sac_* and ev2g_tqc_* below. */
 #define EV2G_TD3_MAX_BATCH 1024
 typedef struct ev2g_td3 ev2g_td3;
 typedef struct ev2g_td3_config {
@@ -935,7 +935,8 @@ int ev2g_host_polyak(float *target, const float *param, int64_t n, double tau);
  * LIMITS (a message per field otherwise): d_in <= 192, hidden widths 1 .. 256, d_out <= 64, 1 <= B <= EV2G_TD3_MAX_BATCH, n_critics 1 or 2.
  * actor: the 8 host arrays actor.latent_pi.{0,2}.{weight,bias}, actor.mu.{weight,bias}, actor.log_std.{weight,bias}; critics: 6 per critic; all
  * float32 in SB3's [out, in] layout.  The object belongs to the handle: freed by ev2g_sac_destroy or with ev2g_destroy.
- * Not reproduced: use_sde, action_noise, learning_starts, schedule objects (ev2g_sac_set_rate between calls drives one), TQC. */
+ * Not reproduced: use_sde, action_noise, learning_starts, schedule objects (ev2g_sac_set_rate between calls drives one).  TQC's quantile
+ * critics are not this object's: ev2g_tqc_* below. */
 typedef struct ev2g_sac ev2g_sac;
 typedef struct ev2g_sac_config {
     double lr, beta1, beta2, adam_eps, tau, gamma;         /* 3e-4 (all three optimisers), 0.9, 0.999, 1e-8, 0.005, 0.99 */
@@ -991,6 +992,72 @@ int ev2g_host_sac_head_back(const float *mu, const float *log_std, const float *
                             float *d_log_std);
 int ev2g_host_sac_y(const float *tq, const float *log_pi_next, const float *reward, const uint8_t *done, int B, int n_critics, double gamma,
                     float log_ent_coef, float *y);
+
+/* ---- TQC on the device: sb3_contrib's TQC.train() (Truncated Quantile Critics; MlpPolicy, Box actions, use_sde off) and its stochastic
+ * collection actor (csrc/ev2g_tqc.h over csrc/ev2g_sac.h) ----
+ *   actor: SAC's squashed Gaussian, bit for bit (the section above): the same head, draws, collection kernel and packed images.
+ *   critics: n_critics (1 .. 5) of (s, a) -> h1 -> h2 -> n_quantiles (1 .. 64) with ReLU, no output activation, and their targets.
+ *   nq = n_quantiles, nc = n_critics, d = top_quantiles_to_drop_per_net, M = nc nq <= 128 pooled atoms, K = M - d nc >= 1 kept target atoms,
+ *   tau_i = (i + 0.5) / nq.
+ * One update on the contiguous DEVICE batch (s, a~, r, s', done) of B rows, alpha = exp(log_ent_coef) as it stands before the update, the
+ * draws as in SAC (a_pi: d0 + b P + p; a': d0 + B P + b P + p; d0 += 2 B P):
+ *   per row the M atoms critic_target_j(s', a')[i] pooled j-major, sorted ascending under the key (value, pool index) -- equal values, +0 and
+ *   -0 among them, keep their pool order -- and the first K kept:  z_k = r + ((1 - done) gamma) (sorted_k - alpha log pi');
+ *   delta = z_k - critic_j(s, a~)[i];  critic_loss = mean over (b, j, i, k) of |tau_i - 1[delta < 0]| huber(delta), huber = |delta| - 0.5 where
+ *   |delta| > 1 else 0.5 delta^2 (one plain mean, sum_over_quantiles = False) -> Adam on all critics;
+ *   actor_loss = mean_b(alpha log pi_b - mean_{j,i} critic_j(s, a_pi)[i]) with the critics after their step, through every critic -> Adam on the actor;
+ *   ent_coef_loss, the Polyak step on the critics, and the rewrite of the collection actor's packed weights as in SAC.
+ * z, the critics' output deltas and the losses are float64 from float32 operands in one fixed order, each rounded once; no float atomics: the
+ * same call on the same state gives the same bits.
+ * LIMITS (a message per field otherwise): d_in <= 192, hidden widths 1 .. 256, d_out <= 64, n_critics 1 .. 5, n_quantiles 1 .. 64,
+ * n_critics * n_quantiles <= 128, 0 <= top_quantiles_to_drop_per_net <= n_quantiles - 1, 1 <= B <= EV2G_TD3_MAX_BATCH.
+ * actor: the 8 host arrays of ev2g_sac_create; critics: 6 per critic, the last layer's [n_quantiles, h2] and [n_quantiles]; float32, [out, in].
+ * The object belongs to the handle: freed by ev2g_tqc_destroy or with ev2g_destroy.
+ * Not reproduced: use_sde, action_noise, learning_starts, schedule objects (ev2g_tqc_set_rate between calls drives one). */
+typedef struct ev2g_tqc ev2g_tqc;
+typedef struct ev2g_tqc_config {
+    double lr, beta1, beta2, adam_eps, tau, gamma;         /* as ev2g_sac_config: 3e-4, 0.9, 0.999, 1e-8, 0.005, 0.99 */
+    double ent_coef;
+    double target_entropy;
+    int32_t n_critics, target_update_interval;             /* 2, 1 */
+    int32_t ent_coef_auto, target_entropy_auto;            /* 1, 1 */
+    int32_t n_quantiles, top_quantiles_to_drop_per_net;    /* 25, 2 */
+} ev2g_tqc_config;
+int ev2g_tqc_default_config(ev2g_tqc_config *cfg);
+int ev2g_tqc_create(ev2g_handle *h, const ev2g_tqc_config *cfg, int d_in, int h1, int h2, int d_out, float lo, const float *const *actor,
+                    const float *const *critics, uint64_t seed, ev2g_tqc **out);
+void ev2g_tqc_destroy(ev2g_handle *h, ev2g_tqc *t);
+/* The entries of the SAC section with the same meaning, arguments and staging rules (losses [4]: critic_loss, actor_loss, ent_coef_loss,
+ * ent_coef; ev2g_tqc_apply without a pending gradient: EV2G_ERR_STATE).  `out` of get_grads / get_weights: 8 + 6 n_critics arrays. */
+int ev2g_tqc_update(ev2g_handle *h, ev2g_tqc *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                    const uint8_t *done, int B, float *losses);
+int ev2g_tqc_critic_grad(ev2g_handle *h, ev2g_tqc *t, const float *obs, const float *actions, const float *reward, const float *next_obs,
+                         const uint8_t *done, int B, float *losses);
+int ev2g_tqc_actor_grad(ev2g_handle *h, ev2g_tqc *t, const float *obs, int B, float *losses);
+int ev2g_tqc_apply(ev2g_handle *h, ev2g_tqc *t);
+int ev2g_tqc_act(ev2g_handle *h, ev2g_tqc *t, const float *obs32, int n_rows, int deterministic, float *actions, float *mu, float *log_std,
+                 float *log_pi);
+int ev2g_tqc_collect(ev2g_handle *h, ev2g_tqc *t, int k_steps, int deterministic, const ev2g_transitions *tr);
+int ev2g_tqc_get_grads(ev2g_handle *h, ev2g_tqc *t, float *const *out, float *g_log_ent_coef);
+int ev2g_tqc_get_weights(ev2g_handle *h, ev2g_tqc *t, int target, float *const *out);
+/* z [B, K] and log pi' [B] (may be NULL) of the last critic gradient (B: its batch size), HOST arrays; synchronises */
+int ev2g_tqc_get_z(ev2g_handle *h, ev2g_tqc *t, float *z, float *log_pi_next, int B);
+int ev2g_tqc_get_log_pi(ev2g_handle *h, ev2g_tqc *t, float *log_pi, int B);
+int ev2g_tqc_get_ent_coef(ev2g_handle *h, ev2g_tqc *t, float *out3);
+int ev2g_tqc_set_rate(ev2g_handle *h, ev2g_tqc *t, double lr);
+int ev2g_tqc_seed(ev2g_handle *h, ev2g_tqc *t, uint64_t seed, uint64_t first_draw);
+int ev2g_tqc_act_seed(ev2g_handle *h, ev2g_tqc *t, uint64_t seed, uint64_t first_launch);
+int ev2g_tqc_counters(ev2g_handle *h, ev2g_tqc *t, int64_t *updates, int64_t *target_updates, uint64_t *next_draw, uint64_t *act_launches);
+/* The sort-and-truncate kernel alone on the caller's DEVICE arrays: tq [n_critics][B, n_quantiles], log_pi_next, reward [B] float32, done [B]
+ * uint8, log_ent_coef one float32; z_out [B, K].  The shape limits above hold.  Asynchronous; a read-only addition for tests, like ev2g_td3_get_y. */
+int ev2g_tqc_truncate(ev2g_handle *h, const float *tq, const float *log_pi_next, const float *reward, const uint8_t *done, int B, int n_critics,
+                      int n_quantiles, int top_quantiles_to_drop, double gamma, const float *log_ent_coef, float *z_out);
+/* Host twins (HOST arrays).  ev2g_host_tqc_target: z [B, K] as ev2g_tqc_truncate forms it (log_ent_coef by value).  ev2g_host_tqc_critic_head:
+ * dq [n_critics][B, n_quantiles] and *critic_loss from z [B, K] and q [n_critics][B, n_quantiles], the device's chains and joins. */
+int ev2g_host_tqc_target(const float *tq, const float *log_pi_next, const float *reward, const uint8_t *done, int B, int n_critics, int n_quantiles,
+                         int top_quantiles_to_drop, double gamma, float log_ent_coef, float *z);
+int ev2g_host_tqc_critic_head(const float *z, const float *q, int B, int n_critics, int n_quantiles, int top_quantiles_to_drop, float *dq,
+                              float *critic_loss);
 
 /* ---- plain device-memory helpers so a ctypes host needs no other HIP binding --------------- */
 void *ev2g_malloc(ev2g_handle *h, size_t bytes);
