@@ -35,6 +35,7 @@ obs, rew, done, mask = eng.empty((E, D)), eng.empty((E,)), eng.empty((E,), np.ui
 names = ["A home/charger", "barrier waits", "B battery maths", "C home", "D reduce", "E env-level", "prefetch issue", "loop top"]
 if OUTER: names[6], names[7] = "EPILOGUE (state write-back)", "PROLOGUE (state load)"
 if "-DEV2G_PT_BSPLIT" in defs: names[7], names[2], names[0] = "B operands (LDS + record wait)", "B battery maths proper", "A home/charger + loop top"
+if any(d.startswith("-DEV2G_PT_DRAIN") for d in defs): names[7], names[5] = "loop top: two marks (=1: + a wait for the step before's stores)", "E env-level + step-end bookkeeping"
 print(f"## {wname} {eng.kernel_name} defs={defs}")
 for persistent in (True, False):
     eng.reset(obs)
