@@ -21,6 +21,7 @@
 #include "ev2g_load_host.h"
 #include "ev2g_route_host.h"
 #include "ev2g_balance_host.h"
+#include "ev2g_timing_host.h"
 #include "ev2g_policy_host.h"
 #include "ev2g_step_v2.h"
 #include "ev2g_step_wave.h"
@@ -183,7 +184,7 @@ struct ev2g_tqc : SacCore {
     TqcPlan tq;
 };
 
-#define EV2G_EV_RING 32
+#define EV2G_EV_RING TIMING_RING
 struct ev2g_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -263,11 +264,15 @@ struct ev2g_handle {
     // callers -- ev2g_heuristic_run, ev2g_link_run / _rollout, ev2g_grid_run / _run_observed / _rollout; not ev2g_step): a caller that queues
     // several launches and reads their durations afterwards (bench.py's roofline pass) does not have to drain the stream after each one
     hipEvent_t ev0s[EV2G_EV_RING] = {}, ev1s[EV2G_EV_RING] = {};
-    int ev_slot = 0;
-    bool ev_valid[EV2G_EV_RING] = {};          // the slot's closing event was recorded (a call that failed half-way leaves it false: its duration reads -1)
+    // the ring's bookkeeping (ev2g_timing_host.h).  A persistent ev2g_step_n that is ONE launch of ev2g_step_wave is timed by the kernel's own clock
+    // stamps (the wide stride-0 instantiations: StepRoute::stamps) instead of an event pair -- slot i's pair is d_stamps[2 i], [2 i + 1] --, so that nothing but kernels stands on the stream between the
+    // launches of an episode loop; EV2G_LAUNCH_TIMING=events at load time keeps the event pair everywhere
+    TimingRing ring;
+    unsigned long long *d_stamps = nullptr;     // [EV2G_EV_RING][2], zeroed at creation, freed with the handle (life_allocs)
+    std::vector<void *> life_allocs;            // device blocks that live as long as the handle
+    int wall_khz = 0;                           // hipDeviceAttributeWallClockRate of the handle's device (0: unknown -- no stamps)
+    bool timing_events = false;                 // LoadSwitches::timing_events of the last load
     unsigned fused_attr_mask = 0;               // fused instantiations whose dynamic-LDS attribute was set for THIS handle's device (bit = FusedRoute::index)
-    long long ev_calls = 0;
-    bool timed = false;
     std::string err;
     CommState comm;                             // RCCL communicator of the statistics exchange (ev2g_comm_init), if any
     // ev2g_rollout segments captured as HIP graphs: a policy-in-the-loop step is two short dependent kernels, so the enqueue cost
@@ -351,14 +356,25 @@ static void free_pool(std::vector<void *> &pool) {
 
 // The bracket of a timed call: timed_open takes the next slot of the event ring once the arguments are accepted, timed_close records the end
 // on the success path only -- a call that returns an error in between leaves the slot invalid (its duration reads -1) and `timed` as it was.
-static int timed_open(ev2g_handle *h) {
-    h->ev_slot = (h->ev_slot + 1) % EV2G_EV_RING; h->ev_calls += 1; h->ev_valid[h->ev_slot] = false;
-    HIPCHK(h, hipEventRecord(h->ev0s[h->ev_slot], h->stream));
+// A call that knows only behind route_step what it launches (ev2g_step_n's single persistent launch) takes the slot first and lets launch_steps
+// decide between timed_events and timed_stamps; every other call is timed_open = slot + opening event.
+static int timed_events(ev2g_handle *h) {
+    h->ring.open(TIMING_EVENTS);
+    HIPCHK(h, hipEventRecord(h->ev0s[h->ring.slot], h->stream));
     return EV2G_OK;
 }
+static bool stamps_usable(const ev2g_handle *h) { return h->d_stamps != nullptr && h->wall_khz > 0 && !h->timing_events; }
+static unsigned long long *timed_stamps(ev2g_handle *h) {   // the slot's pair, for WaveArgs::stamp
+    h->ring.open(TIMING_STAMPS);
+    return h->d_stamps + 2 * (size_t)h->ring.slot;
+}
+static int timed_open(ev2g_handle *h) {
+    h->ring.take();
+    return timed_events(h);
+}
 static int timed_close(ev2g_handle *h) {
-    HIPCHK(h, hipEventRecord(h->ev1s[h->ev_slot], h->stream)); h->ev_valid[h->ev_slot] = true;
-    h->timed = true;
+    if (h->ring.kind[h->ring.slot] == TIMING_EVENTS) HIPCHK(h, hipEventRecord(h->ev1s[h->ring.slot], h->stream));
+    h->ring.close();
     return EV2G_OK;
 }
 
@@ -577,6 +593,13 @@ int ev2g_create(const ev2g_config *cfg, ev2g_handle **out) {
         h->own_stream = true;
     }
     for (int i = 0; i < EV2G_EV_RING; i++) { (void)hipEventCreate(&h->ev0s[i]); (void)hipEventCreate(&h->ev1s[i]); }
+    // the stamp pairs and the rate of the clock they hold (a device that reports none keeps the event pairs: stamps_usable)
+    if (hipDeviceGetAttribute(&h->wall_khz, hipDeviceAttributeWallClockRate, h->device) != hipSuccess) h->wall_khz = 0;
+    if (int rc = dalloc(h, h->life_allocs, (size_t)EV2G_EV_RING * 2, &h->d_stamps)) {
+        g_create_error = "ev2g_create: " + h->err;
+        ev2g_destroy(h);
+        return rc;
+    }
     *out = h;
     return EV2G_OK;
 }
@@ -594,6 +617,7 @@ void ev2g_destroy(ev2g_handle *h) {
     free_pool(h->scn_allocs);
     free_pool(h->st_allocs);
     free_pool(h->user_allocs);
+    free_pool(h->life_allocs);
     for (void *p : h->user_host_allocs) (void)hipHostFree(p);
     h->user_host_allocs.clear();
     if (h->peek_stage) (void)hipHostFree(h->peek_stage);
@@ -1078,6 +1102,7 @@ int ev2g_load_scenarios(ev2g_handle *h, const ev2g_scenario_batch *b) {
     free_pool(h->scn_allocs);
     free_pool(h->st_allocs);
     h->loaded = false;
+    h->timing_events = sw.timing_events;
     h->cls_map.clear();
 
     if ((rc = load_plan_layout(plan, b, h->cfg, sw, msg))) return fail(h, rc, msg);
@@ -1195,8 +1220,10 @@ static StepIO make_io(const ev2g_handle *h, const StepRows &r, long long step0, 
 }
 
 // One step launch: route_step (ev2g_route_host.h) decides from the loaded shape and from what this call passes, the decision is stored for the
-// reporters and for launch_stats, and its table entry is launched.
-static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int auto_reset) {
+// reporters and for launch_stats, and its table entry is launched.  `open_timing`: the launch is the whole of a timed call whose slot is taken
+// (ev2g_step_n's single persistent launch) -- an accepted launch of an ev2g_step_wave instantiation with the stamp sites (StepRoute::stamps) gets the
+// slot's stamp pair, any other one the opening event.
+static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int auto_reset, bool open_timing = false) {
     const DevScn &s = h->scn;
     const ev2g_step_extras &x = h->extras;
     h->state_epoch += 1;
@@ -1213,6 +1240,11 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
         return fail(h, EV2G_ERR_ARG, r.refusal);
     }
     h->last = r;
+    unsigned long long *stamp = nullptr;
+    if (open_timing) {
+        if (r.family == ROUTE_WAVE && r.stamps && stamps_usable(h)) stamp = timed_stamps(h);
+        else if (int rc = timed_events(h)) return rc;
+    }
     const V2P *pp = (const V2P *)h->d_v2p;
     const LaunchDims d{dim3(s.n_groups), h->lds_bytes, h->stream};
     switch (r.family) {
@@ -1221,7 +1253,7 @@ static int launch_steps(ev2g_handle *h, const StepIO &io, int t0, int k, int aut
         const int *grp_map = r.balance ? balance_get(h, h->scn_off) : nullptr;   // (the window's map: built at load, or here at a window's first launch)
         if (r.balance && !grp_map) { h->last.balance = false; h->last.balance_reason = "the window's map could not be copied to the device"; }
         const WaveArgs wa{s.P, s.T, s.E, s.D, s.M, st.slab_port, st.slab_port_slice, st.hist,
-                    st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->shape.epw, s.P, grp_map};
+                    st.env_acc, s.cs_pack, (char *)st.line, h->d_step_tab, (char *)st.port_dyn, s.dict, h->shape.epw, s.P, grp_map, stamp};
         const WaveLaunch launch = kWaveTable[route_wave_index(r.sk, r.rk, r.io32, r.fullk)];
         if (!launch) return fail(h, EV2G_ERR_ARG, "EV2G_ONLY_00 build: only the cfg2 specialisation exists");   // (every entry a route names exists in a full build: tests/host/route_check.cpp)
         if (r.ff && h->d_place) HIPCHK(h, hipMemsetAsync(h->d_place, 0, sizeof(unsigned) * (2 * (size_t)s.n_groups + 2048), h->stream));   // (EV2G_PLACEMENT=1 only)
@@ -1293,7 +1325,7 @@ int ev2g_step(ev2g_handle *h, const double *actions, double *obs, double *reward
     int rc = launch_steps(h, io, h->current_step, 1, 0);
     if (rc) return rc;
     h->current_step += 1;
-    h->timed = false;
+    h->ring.untimed();
     return EV2G_OK;
 }
 
@@ -1306,7 +1338,10 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
     int rc = EV2G_OK;
     const long long adv = (auto_reset == EV2G_AUTO_RESET_NEXT) ? h->E % h->M : 0;   // pool offset advance per in-run reset
     const StepRows rows{{actions, a_stride}, {obs, o_stride}, {reward, r_stride}, {done, d_stride}, {mask, m_stride}};
-    if ((rc = timed_open(h))) return rc;
+    // the call's slot of the timing ring; how it is timed is decided where the call knows what it launches: a persistent call that is ONE launch
+    // leaves it to launch_steps (stamps where the instantiation has them), everything else -- the per-step chain, the run cut at the episode ends, a call of no
+    // steps -- amortises one event pair over its launches
+    h->ring.take();
     if (mode == EV2G_STEPN_PERSISTENT) {
         int k = k_steps;
         if (!auto_reset) k = std::min(k, h->T - h->current_step);
@@ -1317,6 +1352,7 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
         int resets = 0;
         { int t = h->current_step; for (int i = 0; i < k; i++) { if (t >= h->T) { t = 0; resets++; } t++; } }
         if (adv != 0 && resets > 0 && (long long)(resets + 1) * h->E > h->M) {
+            if ((rc = timed_events(h))) return rc;
             for (int i0 = 0; i0 < k;) {
                 if (h->current_step >= h->T) {
                     int r2 = ev2g_reset_ex(h, nullptr, h->scn_off + adv);
@@ -1330,7 +1366,7 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
             }
             return timed_close(h);
         }
-        if (k > 0) rc = launch_steps(h, make_io(h, rows, 0, auto_reset), h->current_step, k, auto_reset);
+        rc = k > 0 ? launch_steps(h, make_io(h, rows, 0, auto_reset), h->current_step, k, auto_reset, true) : timed_events(h);
         if (rc) return rc;
         if (auto_reset) {
             // replay the step counter on the host: reset happens lazily before the step that follows a terminal one
@@ -1342,6 +1378,7 @@ int ev2g_step_n(ev2g_handle *h, int k_steps, int mode, const double *actions, in
         }
         if (k < k_steps) rc = fail(h, EV2G_ERR_DONE, "ev2g_step_n: episode finished before k_steps (auto_reset off)");
     } else {
+        if ((rc = timed_events(h))) return rc;
         StepChain c{"ev2g_step_n"};
         c.actions = {const_cast<double *>(actions), a_stride}; c.a_stride_to_kernel = true;   // (no agent: the rows are only read)
         c.obs = rows.obs; c.reward = rows.reward; c.done = rows.done; c.mask = rows.mask;
@@ -2194,14 +2231,23 @@ int ev2g_grid_get_stats(ev2g_handle *h, ev2g_grid *g, double *vv_sum, int32_t *v
     return EV2G_OK;
 }
 
+const char *ev2g_last_launch_timing(const ev2g_handle *h) { return h ? timing_kind_name(h->ring.last_kind()) : ""; }
+
 double ev2g_last_step_n_kernel_ms(ev2g_handle *h) {
     return ev2g_step_n_kernel_ms_back(h, 0);
 }
 
 double ev2g_step_n_kernel_ms_back(ev2g_handle *h, int back) {
-    if (!h || !h->timed || back < 0 || back >= EV2G_EV_RING || back >= h->ev_calls) return -1.0;
-    const int slot = ((h->ev_slot - back) % EV2G_EV_RING + EV2G_EV_RING) % EV2G_EV_RING;
-    if (!h->ev_valid[slot]) return -1.0;
+    if (!h) return -1.0;
+    const int slot = h->ring.slot_of(back);
+    if (slot < 0) return -1.0;
+    if (h->ring.kind[slot] == TIMING_STAMPS) {   // the kernel's own stamps: behind everything queued on the stream, the slot's two words
+        unsigned long long w[2] = {0, 0};
+        (void)hipSetDevice(h->device);
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return -1.0;
+        if (hipMemcpy(w, h->d_stamps + 2 * (size_t)slot, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
+        return timing_stamp_ms(w[0], w[1], h->wall_khz);
+    }
     if (hipEventSynchronize(h->ev1s[slot]) != hipSuccess) return -1.0;
     float ms = 0;
     if (hipEventElapsedTime(&ms, h->ev0s[slot], h->ev1s[slot]) != hipSuccess) return -1.0;

@@ -34,6 +34,7 @@ struct LoadSwitches {
     bool kernel_v2 = false;           // EV2G_KERNEL=v2: the general kernel on the common shape
     bool no_dict = false;             // EV2G_NO_DICT: one ClsRec per session
     bool no_big = false;              // EV2G_NO_BIG: ev2g_step_v2<1024> where ev2g_step_big would run
+    bool timing_events = false;       // EV2G_LAUNCH_TIMING=events: every timed call keeps its HIP-event pair (ev2g_timing_host.h), no launch stamps
 };
 inline LoadSwitches load_switches_from_env() {
     LoadSwitches sw;
@@ -49,6 +50,8 @@ inline LoadSwitches load_switches_from_env() {
     sw.kernel_v2 = kn && std::string(kn) == "v2";
     sw.no_dict = std::getenv("EV2G_NO_DICT") != nullptr;
     sw.no_big = std::getenv("EV2G_NO_BIG") != nullptr;
+    const char *lt = std::getenv("EV2G_LAUNCH_TIMING");
+    sw.timing_events = lt && std::string(lt) == "events";
     return sw;
 }
 

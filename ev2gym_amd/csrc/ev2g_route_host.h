@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "../../include/ev2g.h"
+#include "ev2g_timing_host.h"
 
 // the kernel a launch runs on
 enum RouteFamily {
@@ -63,6 +64,7 @@ struct StepRoute {
     bool balance = false;            // the launch gets a CU-balance map for the window it steps (ev2g_last_launch_balance) ...
     const char *balance_reason = ""; // ... why it keeps the kernel's own map
     bool inl_stats = false;          // the kernel computes get_statistics of every env in its tail
+    bool stamps = false;             // the instantiation has the two launch-stamp sites (timing_wave_stamped, ev2g_timing_host.h: the kernel's STAMPED is the same function)
     const char *general_reason = ""; // ev2g_last_launch_general_reason
     const char *inl_reason = "";     // why the in-launch statistics are not available (ev2g_last_stats_reason reports it)
     const char *refusal = nullptr;   // the launch is refused (EV2G_ERR_ARG) with this message: nothing above `ff` is decided then
@@ -111,6 +113,7 @@ inline StepRoute route_step(const RouteShape &s, const RouteCall &c) {
         r.fullk = full ? (str3 ? 3 : (wide ? 2 : 1)) : 0;
         r.io32 = full ? f32io : !c.actions;
         r.specialisation = r.fullk;
+        r.stamps = timing_wave_stamped(r.fullk);
         // (ev2g_step_wave.h's FFW is the kernel's half: a stride-0 float64 full instantiation of a head-table state, V2P::ff_count set -- one env per
         // wavefront --, k > 1)
         r.ff = full && !str3 && f64io && c.k > 1 && s.ff_count && s.state_kind != EV2G_STATE_PUBLIC_PST;

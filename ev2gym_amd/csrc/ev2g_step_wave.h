@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "ev2g_step_v2.h"
 #include "ev2g_mlp.h"
+#include "ev2g_timing_host.h"
 
 #define EV2G_WAVE_BLOCK 256
 // the shortest EV-free stretch ev2g_step_wave fast-forwards (FFW): a one-step pass costs a barrier and one memory round trip, like the step it replaces
@@ -136,7 +137,25 @@ struct WaveArgs {
     int dict;                // DevScn::dict: V2P::cls_rec is a dictionary (entry = bits 20..31 of the port's LDS word); 0: one ClsRec per session
     int epw, es;             // envs per wavefront (<= 64 / P) and the lane stride between them (>= P; P: packed, 64 / epw: aligned to lane rows)
     const int *grp_map = nullptr;   // [gridDim.x] the env group of every workgroup (a permutation, ev2g_balance_host.h); nullptr: the kernel's own map
+    // launch stamps (ev2g_timing_host.h): two words of the handle's ring -- [0] the constant-rate wall clock in workgroup 0's prologue, [1] the largest
+    // one a workgroup read at its exit (behind a barrier: one atomic maximum per workgroup); nullptr: the launch is timed by events around it, or not at all, and the kernel does what it always did
+    unsigned long long *stamp = nullptr;
 };
+// The kernel-argument segment of ev2g_step_wave as a struct: where the two stamp sites fetch WaveArgs::stamp from, each for itself -- taken from `wa` the
+// pointer would be a scalar register pair held (or parked in lanes) across the whole step loop, like the output pointers before the peeled step.
+// It MUST follow the kernel's parameter list up to and including `wa` (the trailing FusedArgs is left out): a parameter inserted in front of `wa`
+// without its twin here would make the sites read another word as the pointer.
+struct WaveKernArgs {
+    const void *params; StepIO io; int t0, k_steps, auto_reset; WaveArgs wa;
+};
+static_assert(offsetof(WaveKernArgs, io) == 8 && offsetof(WaveKernArgs, t0) == 8 + sizeof(StepIO) && alignof(WaveArgs) == 8 &&
+              offsetof(WaveKernArgs, wa) == ((8 + sizeof(StepIO) + 3 * sizeof(int) + 7) & ~(size_t)7),
+              "WaveKernArgs lays the parameters out the way the kernel-argument segment does: each at its natural alignment, in order");
+__device__ __forceinline__ unsigned long long *ev2g_wave_stamp_arg() {
+    const char __attribute__((address_space(4))) *kargs = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kargs));
+    return *(unsigned long long *const __attribute__((address_space(4))) *)(kargs + offsetof(WaveKernArgs, wa) + offsetof(WaveArgs, stamp));
+}
 
 // IO32: the actions are float32 (StepIO::act32) -- the policy-network interface; float32 observations (StepIO::obs32) are
 // written whenever that pointer is set, in either instantiation.
@@ -165,6 +184,7 @@ struct WaveArgs {
 // fragment feeds two MFMAs, the weight stream per env halves, and 8192 envs are one round of 256 workgroups instead of two rounds of 512.
 // NWF (round 6, last session; ACT with a head-table state, AE = 1): the FLOAT32 policy (EV2G_MLP_F32: two bf16 terms per weight, three per activation)
 // inside the launch -- ev2g_mlp3_inline_f32 (ev2g_mlp.h): the input rows stay float32 in LDS, the hidden activations' three copies fill the staging rows.
+// (the parameter list is mirrored by WaveKernArgs above, which the launch-stamp sites read `wa.stamp` through: change the two together)
 template <int SK, int RK, bool IO32, int FULLK = 0, int BLOCK = EV2G_WAVE_BLOCK, bool ACT = false, int AE = 1, int NWF = 1>
 __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict__ params, StepIO io, int t0,
                                                            int k_steps, int auto_reset, WaveArgs wa, FusedArgs fa) {
@@ -280,6 +300,15 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
             S->place[2u * blockIdx.x] = (xcc << 16) | (hw & 0xffffu);
             S->place[2u * blockIdx.x + 1u] = rank;
         }
+    }
+    // launch stamps: the wide stride-0 instantiations (FULLK 2: a whole-episode launch's) read the wall clock at both ends of the kernel when the host
+    // passes a pair (WaveArgs::stamp; timing_wave_stamped in ev2g_timing_host.h is the rule, which route_step applies as StepRoute::stamps on the host).  Only they: their peeled step keeps the kernel-argument
+    // pointer alive across the loop anyway, so the end site costs them nothing, while every other instantiation paid for it with scalar registers parked
+    // in lanes and the general one with 68 bytes of scratch (profiles/r28_launch_stamps.txt)
+    constexpr bool STAMPED = timing_wave_stamped(FULLK) && !ACT && BLOCK == EV2G_WAVE_BLOCK;
+    if (STAMPED && blockIdx.x == 0 && tid == 0) {
+        unsigned long long *stamp = ev2g_wave_stamp_arg();
+        if (stamp != nullptr) stamp[0] = wall_clock64();
     }
     // ---- home lane set-up ----
     const int elw = lane / ES;           // env inside the wavefront
@@ -496,6 +525,23 @@ __global__ void __launch_bounds__(BLOCK, 4) ev2g_step_wave(const V2P *__restrict
                         (const double *)S->sess_final_cap, (const double *)S->sess_abs_e, (const double *)S->soc_log, (const PortLine *)S->line};
             ev2g_env_stats<1, EV2G_INL_STATS_NK, EV2G_INL_STATS_LK>(v, es, true, scn_s, lane, T, stats_out,
                                                                   lds + (size_t)wv * EV2G_INL_STATS_LK * 64, lane);
+        }
+    }
+    // the launch's end stamp: every workgroup's exit time -- read behind a barrier, so it is its last wavefront's --, the largest one stays (relaxed,
+    // result unused: no round trip; the clock only grows, so a pair reused by a later launch needs no clearing).  ONE atomic per workgroup: an agent-scope
+    // atomic executes at the memory side, those on one word queue up there, and a balanced launch's workgroups end together -- one per wavefront (4096 at
+    // cfg2) made the cfg2 headline 3.2 % SLOWER than the parent, one per workgroup measures like none at all (profiles/r28_launch_stamps.txt)
+    // Which wavefront issues it: the first one behind the barrier to swap a marker into cnt[0] -- dead since the step loop, never negative (a count of
+    // ports), and beyond the statistics phase's LDS blocks.  (`tid == 0` instead kept the thread index alive to the end: two VGPRs more.)
+    static_assert(!STAMPED || (size_t)BLOCK * EV2G_INL_STATS_LK * sizeof(double) <=sizeof(double) * (EV2G_NQ * (size_t)RS + 7 * (size_t)NS + 4 * 64) + sizeof(int) * 6 * (size_t)NS, "the statistics phase's blocks end in front of cnt");
+    // A launch without a pair (the one-step launches of a chain) skips all of it behind one scalar load: the barrier and the swap cost such a 10 us
+    // launch 0.7 %, the load and its wait still cost it 0.3-0.4 % (profiles/r28_launch_stamps.txt section 3).
+    if (STAMPED) {
+        unsigned long long *stamp = ev2g_wave_stamp_arg();
+        if (stamp != nullptr) {   // (uniform: a kernel argument)
+            __syncthreads();
+            if (lane == 0 && __hip_atomic_exchange(cnt, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != -1)
+                __hip_atomic_fetch_max(stamp + 1, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }

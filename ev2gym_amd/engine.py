@@ -215,6 +215,7 @@ def load_library(path: Optional[str] = None):
         "ev2g_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int]),
         "ev2g_comm_destroy": (None, [vp]),
         "ev2g_step_n_kernel_ms_back": (dbl, [vp, C.c_int]),
+        "ev2g_last_launch_timing": (C.c_char_p, [vp]),
         "ev2g_comm_world_size": (C.c_int, [vp]),
         "ev2g_comm_gathers": (C.c_longlong, [vp]),
         "ev2g_gather_stats": (C.c_int, [vp, vp]),
@@ -243,7 +244,7 @@ EXPORTED_SYMBOLS = [
     "ev2g_scenario_offset", "ev2g_set_step_extras", "ev2g_kernel_name", "ev2g_last_launch_specialisation", "ev2g_last_launch_general_reason", "ev2g_last_stats_route", "ev2g_last_stats_reason", "ev2g_last_launch_fast_forwarded", "ev2g_last_launch_placement", "ev2g_last_launch_balance", "ev2g_fallback_reason", "ev2g_big_kernel_reason", "ev2g_step", "ev2g_step_n",
     "ev2g_check_faults", "ev2g_get_stats", "ev2g_get_stats_reset", "ev2g_get_stats_reset_f32", "ev2g_reset_f32", "ev2g_collect", "ev2g_stat_name", "ev2g_peek", "ev2g_malloc", "ev2g_free",
     "ev2g_memcpy_h2d", "ev2g_memcpy_d2h", "ev2g_host_malloc", "ev2g_host_free", "ev2g_synchronize", "ev2g_fill_uniform", "ev2g_host_uniform",
-    "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_mlp_kernel_name", "ev2g_rollout",
+    "ev2g_last_step_n_kernel_ms", "ev2g_step_n_kernel_ms_back", "ev2g_last_launch_timing", "ev2g_mlp_create", "ev2g_mlp_create_ex", "ev2g_mlp_destroy", "ev2g_mlp_forward", "ev2g_mlp_kernel_name", "ev2g_rollout",
     "ev2g_rollout_graph_launches", "ev2g_comm_get_unique_id", "ev2g_comm_init", "ev2g_comm_destroy", "ev2g_comm_world_size", "ev2g_comm_gathers", "ev2g_gather_stats",
     "ev2g_pool_refill", "ev2g_pool_refill_overflows", "ev2g_pool_session_capacity", "ev2g_gen_default_config", "ev2g_generate", "ev2g_gen_batch", "ev2g_gen_free", "ev2g_gen_table",
     "ev2g_heuristic_create", "ev2g_heuristic_destroy", "ev2g_heuristic_actions", "ev2g_heuristic_run",
@@ -385,6 +386,12 @@ class Engine:
         n, why = C.c_int64(0), C.c_char_p()
         on = self._lib.ev2g_last_launch_balance(self._h, C.byref(n), C.byref(why))
         return bool(on), int(n.value), (why.value or b"").decode()
+
+    @property
+    def last_launch_timing(self) -> str:
+        """How the last timed call was measured (include/ev2g.h): "stamps" -- the kernel's own clock readings, a persistent step_n that is one launch of
+        the fast-path kernel --, "events" -- a HIP-event pair around the call's launches --, or "" where last_step_n_kernel_ms reads -1."""
+        return (self._lib.ev2g_last_launch_timing(self._h) or b"").decode()
 
     def last_launch_placement(self):
         """Development (EV2G_PLACEMENT=1 at load time, include/ev2g.h): [n_workgroups, 2] uint32 -- hardware ids and arrival rank on its CU of every workgroup

@@ -1075,12 +1075,26 @@ int ev2g_synchronize(ev2g_handle *h);
  * GPU legs of a benchmark see identical action tensors (RandomAgent, heuristics.py:546-558). */
 int ev2g_fill_uniform(ev2g_handle *h, double *dst, int64_t n, uint64_t seed, double lo, double hi);
 void ev2g_host_uniform(double *dst, int64_t n, uint64_t seed, double lo, double hi);
-/* elapsed GPU time of the kernels enqueued by the last ev2g_step_n(), measured with HIP events on
- * the handle's stream; total over the K launches, in milliseconds. */
+/* elapsed GPU time of the kernels enqueued by the last ev2g_step_n(), in milliseconds; total over the K launches.  Measured in one of two ways
+ * (ev2g_last_launch_timing says which):
+ *   "events"  a pair of HIP events recorded on the handle's stream around the call's launches: the per-step chain, a persistent run cut at the
+ *             episode ends, the general kernels, and every other timed entry (ev2g_rollout, ev2g_collect, "timed like ev2g_step_n").
+ *   "stamps"  a persistent ev2g_step_n that is ONE launch of ev2g_step_wave's wide stride-0 instantiation (ev2g_last_launch_specialisation 2: the
+ *             whole-episode launch of an episode loop) reads the device's constant-rate wall clock (hipDeviceAttributeWallClockRate) itself: the
+ *             duration runs from the first workgroup's prologue to the last wavefront's exit.  It does not contain the dispatch ramp in front of
+ *             the kernel or the end-of-kernel cache write-back and completion signal behind it, which an event pair includes: a stamped duration
+ *             reads 5-6 us shorter than the event pair of the same launch (median 5.2 us at 4096 x 50, 6.0 us at 8192 x 20 PublicPST;
+ *             profiles/r28_launch_stamps.txt).  Nothing but the kernel is put on the stream, so the launches
+ *             of an episode loop run back to back with the episode-end kernels; an event record between two kernels drains the queue and costs
+ *             the loop about 6 us each (profiles/r28_launch_stamps.txt).  Reading a stamped duration waits for the handle's stream.
+ * EV2G_LAUNCH_TIMING=events in the environment at load time keeps the event pair on every path. */
 double ev2g_last_step_n_kernel_ms(ev2g_handle *h);
-/* the same for the timed call `back` calls before the last one (0 = the last; the handle keeps the event pairs of its last 32 ev2g_step_n /
- * ev2g_rollout / ev2g_collect calls): launches can be queued back to back and their durations read afterwards.  -1.0: out of range. */
+/* the same for the timed call `back` calls before the last one (0 = the last; the handle keeps the event pairs or stamp pairs of its last 32
+ * ev2g_step_n / ev2g_rollout / ev2g_collect calls): launches can be queued back to back and their durations read afterwards.  -1.0: out of range,
+ * a call that failed, or a plain ev2g_step since. */
 double ev2g_step_n_kernel_ms_back(ev2g_handle *h, int back);
+/* how the last timed call was measured: "stamps", "events", or "" where ev2g_last_step_n_kernel_ms reads -1 */
+const char *ev2g_last_launch_timing(const ev2g_handle *h);
 
 /* ---- scenario generator (host side, no GPU involved) ------------------------------------------------------------------
  * What EV2Gym.reset() draws for one episode -- EV sessions (EV_spawner utils.py:477-557, spawn_single_EV :177-345), prices
