@@ -149,6 +149,25 @@ class PpoInfoC(C.Structure):   # ev2g_ppo_info
     _fields_ = [("lds_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("grid_cap", C.c_int32), ("n_params", C.c_int32)]
 
 
+class TrpoConfigC(C.Structure):   # ev2g_trpo_config, in header order
+    _fields_ = [("lr", C.c_double), ("target_kl", C.c_double), ("cg_damping", C.c_double), ("line_search_shrinking_factor", C.c_double),
+                ("cg_max_steps", C.c_int32), ("line_search_max_iter", C.c_int32), ("normalize_advantage", C.c_int32)]
+
+
+class TrpoInfoC(C.Structure):   # ev2g_trpo_info
+    _fields_ = [("lds_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("grid_cap", C.c_int32), ("n_params", C.c_int32), ("n_actor", C.c_int32)]
+
+
+class TrpoReportC(C.Structure):   # ev2g_trpo_report
+    _fields_ = [("cg_iterations", C.c_int32), ("line_search_tries", C.c_int32), ("accepted", C.c_int32), ("failed", C.c_int32),
+                ("objective_before", C.c_double), ("objective_after", C.c_double), ("kl", C.c_double), ("beta", C.c_double), ("c", C.c_double),
+                ("xHx", C.c_double)]
+
+
+# the actor's seven arrays in the order of a flat TRPO vector (sb3_contrib: the parameters without "value" in their name), as indices of AC_PARAMS
+TRPO_ACTOR = (12, 0, 1, 2, 3, 8, 9)
+
+
 class Td3ConfigC(C.Structure):   # ev2g_td3_config, in header order
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double), ("tau", C.c_double), ("gamma", C.c_double),
                 ("target_policy_noise", C.c_double), ("target_noise_clip", C.c_double), ("n_critics", C.c_int32), ("policy_delay", C.c_int32)]

@@ -36,6 +36,7 @@
 #include "ev2g_ac.h"
 #include "ev2g_ppo.h"
 #include "ev2g_learner_host.h"
+#include "ev2g_trpo_host.h"
 #include "ev2g_td3_host.h"
 #include "ev2g_sac_host.h"
 #include "ev2g_tqc_host.h"
@@ -141,6 +142,17 @@ struct ev2g_ppo : DevOwner {
     int n_blocks = 0;          // blocks of the reduce / apply launches: ceil(n_params / 256)
     long long t = 0;           // the optimiser's step count
     bool have_grad = false;    // a gradient no apply has consumed yet
+    // a TRPO learner (ev2g_trpo_create, ev2g_trpo.h): its config, the solve's float64 vectors and theta0 [n_actor], the direction images, the
+    // step's state, the per-workgroup partials, and mu0 [B, P] (in swap_allocs: regrown when B * P grows)
+    TrpoSpec trpo;
+    TrpoPlan tplan;
+    TrpoMap tmap{};
+    double *tg = nullptr, *tx = nullptr, *tr = nullptr, *tp = nullptr, *thv = nullptr, *tpart = nullptr;
+    float *theta0 = nullptr, *mu0 = nullptr, *dimg[EV2G_TRPO_ACTOR_ARRAYS] = {};
+    TrpoState *tstate = nullptr;
+    size_t mu0_elems = 0;
+    int n_ablocks = 0;         // blocks of the launches over a flat actor vector
+    bool have_step = false;    // a policy step was queued: there is a report and a direction
 };
 
 // the TD3 / DDPG learner of a policy (ev2g_td3_create, ev2g_td3.h): float32 masters, targets, Adam's state and the last gradient in the plan's
@@ -298,7 +310,8 @@ struct ev2g_handle {
     std::vector<ev2g_sac *> sacs;               // the SAC learners created on this handle (freed with it)
     std::vector<ev2g_tqc *> tqcs;               // the TQC learners created on this handle (freed with it)
     unsigned sac_attr_mask = 0;                 // ev2g_sac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
-    unsigned ppo_attr_mask = 0;                 // ev2g_ppo_grad_kernel instantiations (bit relu + 2 head) whose dynamic-LDS attribute was set
+    unsigned trpo_attr_mask = 0;                // the TRPO kernels likewise (bit relu)
+    unsigned ppo_attr_mask = 0;               // ev2g_ppo_grad_kernel instantiations (bit relu + 2 head) whose dynamic-LDS attribute was set
     unsigned ac_attr_mask = 0;                  // ev2g_ac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
 };
 
@@ -2592,8 +2605,9 @@ static int ppo_check(ev2g_handle *h, ev2g_ppo *p, const char *who) { return owne
 static int learner_check(ev2g_handle *h, ev2g_ppo *p, const char *who, int kind) {
     if (int rc = ppo_check(h, p, who)) return rc;
     if (p->spec.kind != kind)
-        return fail(h, EV2G_ERR_STATE, std::string(who) + (p->spec.kind == LEARNER_A2C ? ": the learner is an A2C learner (the ev2g_a2c_* entries drive it)"
-                                                                                      : ": the learner is a PPO learner (the ev2g_ppo_* entries drive it)"));
+        return fail(h, EV2G_ERR_STATE, std::string(who) + (p->spec.kind == LEARNER_A2C    ? ": the learner is an A2C learner (the ev2g_a2c_* entries drive it)"
+                                                           : p->spec.kind == LEARNER_TRPO ? ": the learner is a TRPO learner (the ev2g_trpo_* entries drive it)"
+                                                                                          : ": the learner is a PPO learner (the ev2g_ppo_* entries drive it)"));
     return EV2G_OK;
 }
 
@@ -2660,7 +2674,7 @@ static int ppo_device_stage(ev2g_handle *h, ev2g_ppo *p, ev2g_acpolicy *ac, cons
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     const int relu = ac->relu ? 1 : 0, head = p->spec.head;
     const unsigned bit = 1u << (relu + 2 * head);
-    if (e == hipSuccess && pl.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & bit)) {   // (function attributes are per device: once per handle)
+    if (e == hipSuccess && p->spec.kind != LEARNER_TRPO && pl.lds.bytes > 48 * 1024 && !(h->ppo_attr_mask & bit)) {   // (function attributes are per device: once per handle)
         e = hipFuncSetAttribute(ppo_grad_kernel(relu, head).fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
         if (e == hipSuccess) h->ppo_attr_mask |= bit;
     }
@@ -2851,6 +2865,247 @@ int ev2g_host_a2c_head(const float *mean, const float *value, const float *actio
     const LearnerSpec spec = learner_spec(*cfg);
     if (spec.one_row_norm_refused && spec.hyper.normalize && B == 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_a2c_head: normalize_advantage needs B >= 2");
     learner_host_head(spec, mean, value, actions, log_std, nullptr, advantages, returns, B, P, d_mean, d_value, d_log_std, stats);
+    return EV2G_OK;
+}
+
+// ---- the TRPO learner (ev2g_trpo.h): a third kind of ev2g_ppo ----
+int ev2g_trpo_query(int d_in, int h1, int h2, int v1, int v2, int d_out, ev2g_trpo_info *info) {
+    if (!info) return fail(nullptr, EV2G_ERR_ARG, "ev2g_trpo_query: info is null");
+    const TrpoPlan p = plan_trpo(d_in, h1, h2, v1, v2, d_out);
+    if (p.err) return fail(nullptr, p.err, p.refusal);
+    info->lds_bytes = (int64_t)p.lds.bytes; info->workspace_bytes = (int64_t)(p.ppo.workspace_bytes + p.vector_bytes);
+    info->grid_cap = p.ppo.grid_cap; info->n_params = p.ppo.n_params; info->n_actor = p.n_actor;
+    return EV2G_OK;
+}
+
+// the kernels of one activation (ev2g_trpo_create sets their dynamic-LDS attribute)
+struct TrpoKernels { const void *fn[4]; };
+extern "C++" template <int ACT>
+static TrpoKernels trpo_kernels_of() {
+    return {{(const void *)ev2g_trpo_policy_kernel<ACT, EV2G_TRPO_GRAD>, (const void *)ev2g_trpo_policy_kernel<ACT, EV2G_TRPO_FVP>,
+             (const void *)ev2g_trpo_policy_kernel<ACT, EV2G_TRPO_EVAL>, (const void *)ev2g_trpo_value_kernel<ACT>}};
+}
+// mode: EV2G_TRPO_GRAD / _FVP / _EVAL, or 3: the critic's kernel
+static void trpo_launch_rows(ev2g_handle *h, ev2g_ppo *p, int mode, int n_wg, const TrpoArgs &a) {
+    const dim3 grid((unsigned)n_wg), block(EV2G_PPO_BLOCK);
+    const size_t lds = p->tplan.lds.bytes;
+    const AcDev &ac = p->ac->dev;
+    const TrpoLds &L = p->tplan.lds;
+#define EV2G_TRPO_LAUNCH(ACT) \
+    switch (mode) { \
+    case EV2G_TRPO_GRAD: hipLaunchKernelGGL((ev2g_trpo_policy_kernel<ACT, EV2G_TRPO_GRAD>), grid, block, lds, h->stream, ac, p->dev, L, a); break; \
+    case EV2G_TRPO_FVP: hipLaunchKernelGGL((ev2g_trpo_policy_kernel<ACT, EV2G_TRPO_FVP>), grid, block, lds, h->stream, ac, p->dev, L, a); break; \
+    case EV2G_TRPO_EVAL: hipLaunchKernelGGL((ev2g_trpo_policy_kernel<ACT, EV2G_TRPO_EVAL>), grid, block, lds, h->stream, ac, p->dev, L, a); break; \
+    default: hipLaunchKernelGGL((ev2g_trpo_value_kernel<ACT>), grid, block, lds, h->stream, ac, p->dev, L, a); break; \
+    }
+    if (p->ac->relu) { EV2G_TRPO_LAUNCH(EV2G_AC_RELU) } else { EV2G_TRPO_LAUNCH(EV2G_AC_TANH) }
+#undef EV2G_TRPO_LAUNCH
+}
+
+static int trpo_device_stage(ev2g_handle *h, ev2g_ppo *p, const char *who) {
+    const TrpoPlan &tp = p->tplan;
+    const size_t n = (size_t)tp.n_actor;
+    double **f64[] = {&p->tg, &p->tx, &p->tr, &p->tp, &p->thv};
+    for (double **d : f64)
+        if (int rc = dalloc(h, p->allocs, n, d)) return rc;
+    if (int rc = dalloc(h, p->allocs, (size_t)tp.ppo.grid_cap * 2, &p->tpart)) return rc;
+    if (int rc = dalloc(h, p->allocs, n, &p->theta0)) return rc;
+    if (int rc = dalloc(h, p->allocs, 1, &p->tstate)) return rc;
+    const auto tab = ac_params(tp.ppo.ac);
+    for (int k = 0; k < EV2G_TRPO_ACTOR_ARRAYS; k++)
+        if (tab[(size_t)tp.arr[k]].slot != AC_NO_IMAGE)
+            if (int rc = dalloc(h, p->allocs, tab[(size_t)tp.arr[k]].img_floats, &p->dimg[k])) return rc;
+    p->tmap = trpo_map(tp, p->dimg);
+    p->n_ablocks = (tp.n_actor + 255) / 256;
+    const int relu = p->ac->relu ? 1 : 0;
+    if (tp.lds.bytes > 48 * 1024 && !(h->trpo_attr_mask & (1u << relu))) {
+        const TrpoKernels k = relu ? trpo_kernels_of<EV2G_AC_RELU>() : trpo_kernels_of<EV2G_AC_TANH>();
+        for (const void *fn : k.fn) {
+            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV2G_PPO_LDS_LIMIT);
+            if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        }
+        h->trpo_attr_mask |= 1u << relu;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+int ev2g_trpo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_trpo_config *cfg, ev2g_ppo **out) {
+    if (int rc = learner_create(h, ac, "ev2g_trpo_create", cfg, out)) return rc;
+    ev2g_ppo *p = *out;
+    p->trpo = trpo_spec(*cfg);
+    p->tplan = plan_trpo(ac->plan.d_in, ac->plan.h1, ac->plan.h2, ac->plan.v1, ac->plan.v2, ac->plan.d_out);
+    if (int rc = trpo_device_stage(h, p, "ev2g_trpo_create")) {
+        owned_destroy(h, &ev2g_handle::ppos, p, ppo_free);
+        *out = nullptr;
+        return rc;
+    }
+    return EV2G_OK;
+}
+
+int ev2g_trpo_set_rate(ev2g_handle *h, ev2g_ppo *p, double lr) {
+    if (int rc = learner_check(h, p, "ev2g_trpo_set_rate", LEARNER_TRPO)) return rc;
+    if (int rc = fields_check(h, "ev2g_trpo_set_rate", trpo_rate_fields(lr))) return rc;
+    p->spec.lr = lr; p->trpo.lr = lr;
+    return EV2G_OK;
+}
+
+static int trpo_wgs(const ev2g_ppo *p, int B) {
+    const int chunks = (B + EV2G_PPO_ROWS - 1) / EV2G_PPO_ROWS;
+    return chunks < p->tplan.ppo.grid_cap ? chunks : p->tplan.ppo.grid_cap;
+}
+
+// mu0 [B, P]: regrown when B * P grows
+static int trpo_rows_block(ev2g_handle *h, ev2g_ppo *p, int B) {
+    const size_t need = (size_t)B * (size_t)p->ac->dev.d_out;
+    if (p->mu0_elems >= need) return EV2G_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    free_pool(p->swap_allocs); p->mu0 = nullptr; p->mu0_elems = 0;
+    if (int rc = dalloc(h, p->swap_allocs, need, &p->mu0)) return rc;
+    p->mu0_elems = need;
+    return EV2G_OK;
+}
+
+// the queue of g, J(theta0), mu0: the advantage statistics if asked for, the GRAD launch, the reduction
+static int trpo_queue_grad(ev2g_handle *h, ev2g_ppo *p, TrpoArgs &a) {
+    const int B = a.B, n_wg = trpo_wgs(p, B);
+    if (int rc = trpo_rows_block(h, p, B)) return rc;
+    if (a.normalize && B > 1) hipLaunchKernelGGL(ev2g_ppo_advstat_kernel, dim3(1), dim3(1024), 0, h->stream, a.adv, a.idx, B, p->advstat);
+    a.advstat = p->advstat; a.work = p->work; a.part = p->tpart; a.mu0 = p->mu0; a.st = p->tstate; a.gate = EV2G_TRPO_GATE_NONE;
+    trpo_launch_rows(h, p, EV2G_TRPO_GRAD, n_wg, a);
+    hipLaunchKernelGGL(ev2g_trpo_reduce_kernel<float>, dim3((unsigned)p->n_ablocks), dim3(256), 0, h->stream, p->map, p->tmap, (const float *)p->work, n_wg, 0,
+                       (const float *)nullptr, 0.0, p->tg, (float *)nullptr, p->grad, (const double *)p->tpart, B, p->tstate, EV2G_TRPO_GATE_NONE);
+    return EV2G_OK;
+}
+
+// H v for the float64 vector v -> p->thv (gate: the launches return at once when the solve has ended)
+static void trpo_queue_fvp(ev2g_handle *h, ev2g_ppo *p, TrpoArgs a, const double *v, int gate) {
+    const int n_wg = trpo_wgs(p, a.B);
+    hipLaunchKernelGGL(ev2g_trpo_dir_kernel<double>, dim3((unsigned)p->n_ablocks), dim3(256), 0, h->stream, p->tmap, v, (const TrpoState *)p->tstate, gate);
+    a.gate = gate;
+    trpo_launch_rows(h, p, EV2G_TRPO_FVP, n_wg, a);
+    hipLaunchKernelGGL(ev2g_trpo_reduce_kernel<double>, dim3((unsigned)p->n_ablocks), dim3(256), 0, h->stream, p->map, p->tmap, (const float *)p->work, n_wg, 1, v,
+                       p->trpo.cg_damping, p->thv, (float *)nullptr, (float *)nullptr, (const double *)p->tpart, a.B, p->tstate, gate);
+}
+
+static TrpoArgs trpo_args(const ev2g_ppo *p, const float *obs, const float *actions, const float *old_lp, const float *adv, const float *ret, const int32_t *idx,
+                          int B) {
+    TrpoArgs a{};
+    a.obs = obs; a.actions = actions; a.old_lp = old_lp; a.adv = adv; a.ret = ret; a.idx = (const int *)idx; a.B = B; a.normalize = p->trpo.normalize;
+    a.advstat = p->advstat; a.work = p->work; a.part = p->tpart; a.mu0 = p->mu0; a.ls0 = p->theta0;   // (log_std leads a flat actor vector)
+    a.dw1 = p->dimg[1]; a.db1 = p->dimg[2]; a.dw2 = p->dimg[3]; a.db2 = p->dimg[4]; a.dw3 = p->dimg[5]; a.db3 = p->dimg[6];
+    a.st = p->tstate; a.gate = EV2G_TRPO_GATE_NONE;
+    return a;
+}
+
+int ev2g_trpo_grad(ev2g_handle *h, ev2g_ppo *p, const float *obs, const float *actions, const float *old_lp, const float *adv, const int32_t *idx, int B,
+                   double *objective) {
+    if (int rc = learner_check(h, p, "ev2g_trpo_grad", LEARNER_TRPO)) return rc;
+    if (!obs || !actions || !old_lp || !adv || !idx) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_grad: null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_grad: B must be at least 1");
+    TrpoArgs a = trpo_args(p, obs, actions, old_lp, adv, nullptr, idx, B);
+    if (int rc = trpo_queue_grad(h, p, a)) return rc;
+    if (objective) HIPCHK(h, hipMemcpyAsync(objective, &p->tstate->J0, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_trpo_fvp(ev2g_handle *h, ev2g_ppo *p, const float *obs, const int32_t *idx, int B, const float *v, float *Hv) {
+    if (int rc = learner_check(h, p, "ev2g_trpo_fvp", LEARNER_TRPO)) return rc;
+    if (!obs || !idx || !v || !Hv) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_fvp: null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_fvp: B must be at least 1");
+    const TrpoArgs a = trpo_args(p, obs, nullptr, nullptr, nullptr, nullptr, idx, B);
+    const int n_wg = trpo_wgs(p, B);
+    hipLaunchKernelGGL(ev2g_trpo_dir_kernel<float>, dim3((unsigned)p->n_ablocks), dim3(256), 0, h->stream, p->tmap, v, (const TrpoState *)p->tstate,
+                       EV2G_TRPO_GATE_NONE);
+    trpo_launch_rows(h, p, EV2G_TRPO_FVP, n_wg, a);
+    hipLaunchKernelGGL(ev2g_trpo_reduce_kernel<float>, dim3((unsigned)p->n_ablocks), dim3(256), 0, h->stream, p->map, p->tmap, (const float *)p->work, n_wg, 1, v,
+                       p->trpo.cg_damping, (double *)nullptr, Hv, (float *)nullptr, (const double *)p->tpart, B, p->tstate, EV2G_TRPO_GATE_NONE);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_trpo_policy_step(ev2g_handle *h, ev2g_ppo *p, const float *obs, const float *actions, const float *old_lp, const float *adv, const int32_t *idx,
+                          int B) {
+    if (int rc = learner_check(h, p, "ev2g_trpo_policy_step", LEARNER_TRPO)) return rc;
+    if (!obs || !actions || !old_lp || !adv || !idx) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_policy_step: null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_policy_step: B must be at least 1");
+    const TrpoSpec &s = p->trpo;
+    TrpoArgs a = trpo_args(p, obs, actions, old_lp, adv, nullptr, idx, B);
+    if (int rc = trpo_queue_grad(h, p, a)) return rc;
+    const int n = p->tplan.n_actor, n_wg = trpo_wgs(p, B);
+    const dim3 one(1), cg(EV2G_TRPO_CG_BLOCK), ab((unsigned)p->n_ablocks);
+    hipLaunchKernelGGL(ev2g_trpo_cg_init_kernel, one, cg, 0, h->stream, n, (const double *)p->tg, p->tx, p->tr, p->tp, p->tstate);
+    for (int i = 0; i < s.cg_max_steps; i++) {
+        trpo_queue_fvp(h, p, a, p->tp, EV2G_TRPO_GATE_CG);
+        hipLaunchKernelGGL(ev2g_trpo_cg_step_kernel, one, cg, 0, h->stream, n, (const double *)p->thv, p->tx, p->tr, p->tp, p->tstate, i == s.cg_max_steps - 1 ? 1 : 0);
+    }
+    trpo_queue_fvp(h, p, a, p->tx, EV2G_TRPO_GATE_NONE);
+    hipLaunchKernelGGL(ev2g_trpo_stepsize_kernel, one, cg, 0, h->stream, p->map, p->tmap, (const double *)p->tx, (const double *)p->thv, s.target_kl,
+                       (const float *)p->theta, p->theta0, p->tstate);
+    a.gate = EV2G_TRPO_GATE_LS;
+    for (int k = 0; k < s.ls_max_iter; k++) {
+        hipLaunchKernelGGL(ev2g_trpo_candidate_kernel, ab, dim3(256), 0, h->stream, p->map, p->tmap, (const double *)p->tx, (const float *)p->theta0, p->theta,
+                           (const TrpoState *)p->tstate);
+        trpo_launch_rows(h, p, EV2G_TRPO_EVAL, n_wg, a);
+        hipLaunchKernelGGL(ev2g_trpo_decide_kernel, one, cg, 0, h->stream, p->map, p->tmap, (const double *)p->tpart, n_wg, B, s.target_kl, s.shrink,
+                           k == s.ls_max_iter - 1 ? 1 : 0, (const float *)p->theta0, p->theta, p->tstate);
+    }
+    HIPCHK(h, hipGetLastError());
+    p->have_step = true;
+    return EV2G_OK;
+}
+
+int ev2g_trpo_critic_minibatch(ev2g_handle *h, ev2g_ppo *p, const float *obs, const float *returns, const int32_t *idx, int B, float *value_loss) {
+    if (int rc = learner_check(h, p, "ev2g_trpo_critic_minibatch", LEARNER_TRPO)) return rc;
+    if (!obs || !returns || !idx) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_critic_minibatch: null argument");
+    if (B < 1) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_critic_minibatch: B must be at least 1");
+    const TrpoArgs a = trpo_args(p, obs, nullptr, nullptr, nullptr, returns, idx, B);
+    const int n_wg = trpo_wgs(p, B);
+    trpo_launch_rows(h, p, 3, n_wg, a);
+    hipLaunchKernelGGL(ev2g_trpo_vreduce_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->work, (const double *)p->tpart, n_wg,
+                       B, p->grad, value_loss);
+    p->t += 1;
+    hipLaunchKernelGGL(ev2g_trpo_vapply_kernel, dim3((unsigned)p->n_blocks), dim3(256), 0, h->stream, p->map, (const float *)p->grad,
+                       adam_step(p->spec.lr, p->spec.beta1, p->spec.beta2, p->spec.eps, p->t), p->theta, p->m, p->v);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_trpo_get_report(ev2g_handle *h, ev2g_ppo *p, ev2g_trpo_report *report) {
+    if (int rc = learner_check(h, p, "ev2g_trpo_get_report", LEARNER_TRPO)) return rc;
+    if (!report) return fail(h, EV2G_ERR_ARG, "ev2g_trpo_get_report: report is null");
+    if (!p->have_step) return fail(h, EV2G_ERR_STATE, "ev2g_trpo_get_report: no policy step yet (ev2g_trpo_policy_step first)");
+    TrpoState st;
+    HIPCHK(h, hipMemcpyAsync(&st, p->tstate, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    report->cg_iterations = st.cg_iters; report->line_search_tries = st.ls_tries; report->accepted = st.accepted; report->failed = st.failed;
+    report->objective_before = st.J0; report->objective_after = st.J1; report->kl = st.kl; report->beta = st.beta; report->c = st.c; report->xHx = st.xHx;
+    return EV2G_OK;
+}
+
+int ev2g_trpo_get_direction(ev2g_handle *h, ev2g_ppo *p, double *x, double *g) {
+    if (int rc = learner_check(h, p, "ev2g_trpo_get_direction", LEARNER_TRPO)) return rc;
+    if (!p->have_step) return fail(h, EV2G_ERR_STATE, "ev2g_trpo_get_direction: no policy step yet (ev2g_trpo_policy_step first)");
+    const size_t bytes = (size_t)p->tplan.n_actor * sizeof(double);
+    if (x) HIPCHK(h, hipMemcpyAsync(x, p->tx, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (g) HIPCHK(h, hipMemcpyAsync(g, p->tg, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+int ev2g_host_trpo_cg_step(double *x, double *r, double *p, const double *Hp, int64_t n, double *rho, int last, int32_t *done) {
+    if (!x || !r || !p || !Hp || !rho || !done || n < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_trpo_cg_step: null argument or n < 1");
+    *done = trpo_host_cg_step(x, r, p, Hp, (int)n, rho, last);
+    return EV2G_OK;
+}
+
+int ev2g_host_trpo_rows(const float *mean, const float *mean0, const float *actions, const float *log_std, const float *log_std0, const float *old_log_prob,
+                        const float *advantages, int B, int P, int normalize_advantage, double *j, double *kl) {
+    if (!mean || !mean0 || !actions || !log_std || !log_std0 || !old_log_prob || !advantages || !j || !kl)
+        return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_trpo_rows: null argument");
+    if (B < 1 || P < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_trpo_rows: B and P must be positive");
+    trpo_host_rows(mean, mean0, actions, log_std, log_std0, old_log_prob, advantages, B, P, normalize_advantage, j, kl);
     return EV2G_OK;
 }
 

@@ -14,7 +14,7 @@
 #include "../../include/ev2g.h"
 #include "ev2g_ppo.h"
 
-enum LearnerKind { LEARNER_PPO = 0, LEARNER_A2C = 1 };   // which entries drive the learner (ev2g_ppo_* / ev2g_a2c_*)
+enum LearnerKind { LEARNER_PPO = 0, LEARNER_A2C = 1, LEARNER_TRPO = 2 };   // which entries drive the learner (ev2g_ppo_* / ev2g_a2c_* / ev2g_trpo_*)
 enum LearnerHead { LEARNER_HEAD_PPO = 0, LEARNER_HEAD_A2C = 1 };   // ev2g_ppo_grad_kernel's HEAD (EV2G_HEAD_*: ev2g_host.hip asserts they agree)
 enum LearnerOptimiser { LEARNER_ADAM = 0, LEARNER_RMSPROP = 1 };   // ev2g_ppo_apply_kernel / ev2g_a2c_apply_kernel
 

@@ -133,6 +133,17 @@ def load_library(path: Optional[str] = None):
         "ev2g_a2c_update": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
         "ev2g_host_rmsprop": (C.c_int, [vp, vp, vp, i64, dbl, dbl, dbl]),
         "ev2g_host_a2c_head": (C.c_int, [vp] * 6 + [C.c_int, C.c_int, C.POINTER(_abi.A2cConfigC), vp, vp, vp, vp]),
+        "ev2g_trpo_query": (C.c_int, [C.c_int] * 6 + [C.POINTER(_abi.TrpoInfoC)]),
+        "ev2g_trpo_create": (C.c_int, [vp, vp, C.POINTER(_abi.TrpoConfigC), C.POINTER(vp)]),
+        "ev2g_trpo_set_rate": (C.c_int, [vp, vp, dbl]),
+        "ev2g_trpo_grad": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int, vp]),
+        "ev2g_trpo_fvp": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp]),
+        "ev2g_trpo_policy_step": (C.c_int, [vp, vp] + [vp] * 5 + [C.c_int]),
+        "ev2g_trpo_critic_minibatch": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
+        "ev2g_trpo_get_report": (C.c_int, [vp, vp, C.POINTER(_abi.TrpoReportC)]),
+        "ev2g_trpo_get_direction": (C.c_int, [vp, vp, vp, vp]),
+        "ev2g_host_trpo_cg_step": (C.c_int, [vp, vp, vp, vp, i64, vp, C.c_int, vp]),
+        "ev2g_host_trpo_rows": (C.c_int, [vp] * 7 + [C.c_int, C.c_int, C.c_int, vp, vp]),
         "ev2g_td3_default_config": (C.c_int, [C.c_int, C.POINTER(_abi.Td3ConfigC)]),
         "ev2g_td3_create": (C.c_int, [vp, vp, C.POINTER(_abi.Td3ConfigC)] + [C.c_int] * 4 + [vp, vp, C.c_uint64, C.POINTER(vp)]),
         "ev2g_td3_destroy": (None, [vp, vp]),
@@ -258,6 +269,8 @@ EXPORTED_SYMBOLS = [
     "ev2g_ppo_query", "ev2g_ppo_create", "ev2g_ppo_destroy", "ev2g_ppo_set_rates", "ev2g_ppo_grad", "ev2g_ppo_apply", "ev2g_ppo_minibatch",
     "ev2g_ppo_get_grads", "ev2g_ppo_sync", "ev2g_ac_get_weights", "ev2g_host_adam", "ev2g_host_ppo_head",
     "ev2g_a2c_create", "ev2g_a2c_set_rate", "ev2g_a2c_grad", "ev2g_a2c_apply", "ev2g_a2c_update", "ev2g_host_rmsprop", "ev2g_host_a2c_head",
+    "ev2g_trpo_query", "ev2g_trpo_create", "ev2g_trpo_set_rate", "ev2g_trpo_grad", "ev2g_trpo_fvp", "ev2g_trpo_policy_step", "ev2g_trpo_critic_minibatch",
+    "ev2g_trpo_get_report", "ev2g_trpo_get_direction", "ev2g_host_trpo_cg_step", "ev2g_host_trpo_rows",
     "ev2g_td3_default_config", "ev2g_td3_create", "ev2g_td3_destroy", "ev2g_td3_update", "ev2g_td3_critic_grad", "ev2g_td3_actor_grad", "ev2g_td3_apply",
     "ev2g_td3_get_grads", "ev2g_td3_get_weights", "ev2g_td3_get_y", "ev2g_td3_set_rate", "ev2g_td3_seed", "ev2g_td3_counters", "ev2g_replay_sample",
     "ev2g_host_replay_indices", "ev2g_host_td3_target", "ev2g_host_polyak",
@@ -864,6 +877,48 @@ class Engine:
     def a2c_update(self, learner, obs, actions, advantages, returns, idx, B, stats=None):
         self._learner_rows("ev2g_a2c_update", learner, (obs, actions, advantages, returns), idx, B, stats)
 
+    # ---- the TRPO learner (include/ev2g.h: ev2g_trpo_*); ppo_destroy / ppo_get_grads / ppo_sync serve it too -----------------------------
+    def trpo_create(self, ac, lr=1e-3, target_kl=0.01, cg_damping=0.1, line_search_shrinking_factor=0.8, cg_max_steps=15, line_search_max_iter=10,
+                    normalize_advantage=True):
+        """A TRPO learner bound to the device policy `ac` (ev2g_trpo_create), freed by ppo_destroy, with its policy or with the engine."""
+        cfg = _abi.TrpoConfigC(float(lr), float(target_kl), float(cg_damping), float(line_search_shrinking_factor), int(cg_max_steps),
+                               int(line_search_max_iter), int(bool(normalize_advantage)))
+        out = C.c_void_p()
+        self._check(self._lib.ev2g_trpo_create(self._h, ac, C.byref(cfg), C.byref(out)))
+        return out.value
+
+    def trpo_set_rate(self, learner, lr):
+        self._check(self._lib.ev2g_trpo_set_rate(self._h, learner, float(lr)))
+
+    def trpo_grad(self, learner, obs, actions, old_log_prob, advantages, idx, B, objective=None):
+        """g, J(theta0) and mu0 over rows idx [B] (int32) of the DEVICE float32 arrays; g goes into the actor's arrays of ppo_get_grads.
+        objective: float64 [1] DEVICE or None."""
+        self._learner_rows("ev2g_trpo_grad", learner, (obs, actions, old_log_prob, advantages), idx, B, objective)
+
+    def trpo_fvp(self, learner, obs, idx, B, v, Hv):
+        """One Fisher-vector product, damping included: v, Hv float32 [n_actor] DEVICE, flat in the actor's order."""
+        self._check(self._lib.ev2g_trpo_fvp(self._h, learner, _ptr(obs), _ptr(idx), int(B), _ptr(v), _ptr(Hv)))
+
+    def trpo_policy_step(self, learner, obs, actions, old_log_prob, advantages, idx, B):
+        """The whole natural-gradient step over rows idx [B]: asynchronous (trpo_get_report or ppo_sync waits for it)."""
+        self._check(self._lib.ev2g_trpo_policy_step(self._h, learner, _ptr(obs), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(idx), int(B)))
+
+    def trpo_critic_minibatch(self, learner, obs, returns, idx, B, value_loss=None):
+        """One Adam step of the value function over rows idx [B]; value_loss: float32 [1] DEVICE or None."""
+        self._check(self._lib.ev2g_trpo_critic_minibatch(self._h, learner, _ptr(obs), _ptr(returns), _ptr(idx), int(B), _ptr(value_loss)))
+
+    def trpo_get_report(self, learner) -> dict:
+        """What the last policy step did (ev2g_trpo_report's fields).  Synchronises."""
+        rep = _abi.TrpoReportC()
+        self._check(self._lib.ev2g_trpo_get_report(self._h, learner, C.byref(rep)))
+        return {k: getattr(rep, k) for k, _ in _abi.TrpoReportC._fields_}
+
+    def trpo_get_direction(self, learner, n_actor):
+        """(x, g) of the last policy step as host float64 arrays [n_actor], flat in the actor's order.  Synchronises."""
+        x, g = np.empty(n_actor, np.float64), np.empty(n_actor, np.float64)
+        self._check(self._lib.ev2g_trpo_get_direction(self._h, learner, x.ctypes.data, g.ctypes.data))
+        return x, g
+
     # ---- the TD3 / DDPG learner and the replay ring's sampler (include/ev2g.h: ev2g_td3_*, ev2g_replay_sample) ------------------------------
     def td3_create(self, mlp, actor, critics, seed=0, ddpg=False, **config):
         """A TD3 (or, ddpg=True, DDPG) learner bound to the policy `mlp` (ev2g_td3_create): actor six host arrays, critics a list of six-array
@@ -1299,6 +1354,45 @@ def ppo_query(d_in, h1, h2, v1, v2, d_out) -> dict:
     if rc != 0:
         raise EngineError(rc, L.ev2g_last_error(None).decode())
     return {k: int(getattr(info, k)) for k, _ in _abi.PpoInfoC._fields_}
+
+
+def trpo_query(d_in, h1, h2, v1, v2, d_out) -> dict:
+    """The TRPO learner's plan of a network (ev2g_trpo_query; host-only): lds_bytes, workspace_bytes, grid_cap, n_params, n_actor."""
+    L = load_library()
+    info = _abi.TrpoInfoC()
+    rc = L.ev2g_trpo_query(int(d_in), int(h1), int(h2), int(v1), int(v2), int(d_out), C.byref(info))
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+    return {k: int(getattr(info, k)) for k, _ in _abi.TrpoInfoC._fields_}
+
+
+def host_trpo_cg_step(x, r, p, Hp, rho, last=False):
+    """Host twin of one conjugate-gradient iteration (ev2g_host_trpo_cg_step): float64 arrays x / r / p are updated IN PLACE from the given Hp.
+    Returns (the new rho, whether the solve has ended)."""
+    for a in (x, r, p):
+        assert a.dtype == np.float64 and a.flags.c_contiguous
+    Hp = np.ascontiguousarray(Hp, np.float64)
+    L = load_library()
+    rho_c, done = C.c_double(float(rho)), C.c_int32(0)
+    rc = L.ev2g_host_trpo_cg_step(x.ctypes.data, r.ctypes.data, p.ctypes.data, Hp.ctypes.data, x.size, C.addressof(rho_c), int(bool(last)),
+                                  C.addressof(done))
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+    return rho_c.value, bool(done.value)
+
+
+def host_trpo_rows(mean, mean0, actions, log_std, log_std0, old_log_prob, advantages, normalize_advantage=True):
+    """Host twin of the line search's row terms (ev2g_host_trpo_rows): (j [B], kl [B]) float64."""
+    mean, mean0, actions, log_std, log_std0, old, adv = (np.ascontiguousarray(a, np.float32) for a in
+                                                         (mean, mean0, actions, log_std, log_std0, old_log_prob, advantages))
+    B, P = mean.shape
+    j, kl = np.empty(B, np.float64), np.empty(B, np.float64)
+    L = load_library()
+    rc = L.ev2g_host_trpo_rows(mean.ctypes.data, mean0.ctypes.data, actions.ctypes.data, log_std.ctypes.data, log_std0.ctypes.data, old.ctypes.data,
+                               adv.ctypes.data, B, P, int(bool(normalize_advantage)), j.ctypes.data, kl.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, L.ev2g_last_error(None).decode())
+    return j, kl
 
 
 def host_adam(theta, m, v, g, t, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-5):

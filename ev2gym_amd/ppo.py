@@ -14,7 +14,7 @@ Box action space:
     loss = -mean(min(A^ r, A^ clip(r, 1 - c, 1 + c))) + ent_coef * (-entropy) + vf_coef * mean((R - v)^2)
     g <- g * min(1, max_grad_norm / (|g| + 1e-6));  torch.optim.Adam(eps=1e-5), no amsgrad, no weight decay
 
-A2C is `ev2gym_amd.a2c.A2CLearner`.  Out of scope, refused where a caller could ask for them: `clip_range_vf`, `target_kl`, TRPO, learning-rate
+A2C is `ev2gym_amd.a2c.A2CLearner`, TRPO `ev2gym_amd.trpo.TRPOLearner`.  Out of scope, refused where a caller could ask for them: `clip_range_vf`, `target_kl`, learning-rate
 schedules as objects (the rate is settable between calls: `set_rates`), action masks, orthogonal initialisation (weights arrive from the
 caller).
 """

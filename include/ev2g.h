@@ -737,7 +737,7 @@ int ev2g_host_gae(const double *reward, const float *values, const uint8_t *epis
  *   A^ = (A - mean(A)) / (std(A) + 1e-8) with the unbiased std, when normalize_advantage is set and B > 1, else A
  *   loss = -mean(min(A^ r, A^ clip(r, 1 - c, 1 + c))) + ent_coef * (-entropy) + vf_coef * mean((R - v)^2)
  *   statistics [6]: policy_loss, value_loss, entropy_loss, loss, approx_kl = mean((r - 1) - log r), clip_fraction = mean(|r - 1| > c)
- * Not reproduced (there is nothing to ask them with): clip_range_vf, target_kl, TRPO, schedule objects (ev2g_ppo_set_rates between calls
+ * Not reproduced (there is nothing to ask them with): clip_range_vf, target_kl, schedule objects (ev2g_ppo_set_rates between calls
  * drives one), action masks, orthogonal initialisation.
  * LIMITS: every network with d_in <= 192, d_out <= 64 and hidden widths <= 64 is accepted, wider ones as far as the gradient kernel's LDS plan
  * fits the CU's 160 KiB (ev2g_ppo_query tells); anything else is EV2G_ERR_ARG at create with a message naming the width. */
@@ -798,7 +798,7 @@ int ev2g_host_ppo_head(const float *mean, const float *value, const float *actio
  *   RMSprop(lr, alpha, eps, no weight decay, no momentum, not centered): sq <- alpha sq + (1 - alpha) g g;  theta <- theta - lr g / (sqrt(sq) + eps)
  *   statistics [6] in ev2g_ppo_grad's order; approx_kl and clip_fraction are exactly 0.
  * use_rms_prop = 0 selects torch.optim.Adam(betas 0.9 / 0.999, eps 1e-5), what SB3's policy builds when RMSprop is switched off.
- * Not reproduced: RMSpropTFLike, schedule objects (ev2g_a2c_set_rate between calls drives one), action masks, TRPO.
+ * Not reproduced: RMSpropTFLike, schedule objects (ev2g_a2c_set_rate between calls drives one), action masks.  (TRPO is the third kind, below.)
  * ev2g_ppo_destroy, ev2g_ppo_get_grads, ev2g_ppo_sync, ev2g_ppo_query and ev2g_ac_get_weights serve both kinds, and ev2g_ac_set_weights /
  * ev2g_ac_set_log_std reset the masters of both (the optimiser's state is kept).  ev2g_ppo_grad / _apply / _minibatch / _set_rates on an A2C
  * learner, and the ev2g_a2c_* entries on a PPO learner, are EV2G_ERR_STATE. */
@@ -826,6 +826,68 @@ int ev2g_a2c_update(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const f
 int ev2g_host_rmsprop(float *theta, float *sq, const float *g, int64_t n, double lr, double alpha, double eps);
 int ev2g_host_a2c_head(const float *mean, const float *value, const float *actions, const float *log_std, const float *advantages,
                        const float *returns, int B, int P, const ev2g_a2c_config *cfg, float *d_mean, float *d_value, float *d_log_std, float *stats);
+
+/* ---- the TRPO learner (csrc/ev2g_trpo.h): sb3_contrib's TRPO.train() with default settings ----
+ * A third kind of the same learner object.  The POLICY STEP, over the rows it is given, entirely on the handle's stream (no host round trip):
+ *   A^ as above (normalised when normalize_advantage is set and B > 1);  J(theta) = mean(A^ exp(lp - old_lp));  g = grad J over the ACTOR's
+ *   parameters, flat in sb3_contrib's order: log_std | pi_W1 | pi_b1 | pi_W2 | pi_b2 | action_W | action_b
+ *   KL(theta) = mean_i sum_p [ ls0_p - ls_p + (e^{2 ls_p} + (mu_ip - mu0_ip)^2) / (2 e^{2 ls0_p}) - 1/2 ]  (new || old; mu0, ls0 at theta0)
+ *   H v = grad(grad KL . v) + cg_damping v, computed as the Fisher product J_mu^T diag(e^{-2 ls0}) J_mu v / B + 2 v_log_std + cg_damping v
+ *   (exact at theta0: one forward-mode tangent pass, then the reverse pass)
+ *   conjugate gradient on H x = g: x = 0, r = p = g, rho = r . r; nothing if rho < 1e-10; at most cg_max_steps times alpha = rho / (p . Hp),
+ *   x += alpha p, and unless it was the last: r -= alpha Hp, rho' = r . r, stop if rho' < 1e-10, p = r + (rho' / rho) p
+ *   beta = sqrt(2 target_kl / (x . Hx));  line search: theta = theta0 + c beta x for c = 1, s, s^2, ... (at most line_search_max_iter tries),
+ *   accepted when KL < target_kl and J > J(theta0); theta0 is put back bit for bit when no try is.
+ * DEVIATION: a non-finite or non-positive x . Hx (x = 0 from a vanishing gradient included) fails the step and leaves theta0; sb3_contrib
+ * would write NaN parameters.
+ * The CRITIC: value_loss = mean((R - v)^2) over a minibatch, torch.optim.Adam(lr, 0.9, 0.999, eps 1e-5) on the six value arrays alone, no
+ * gradient clipping; the actor's arrays, their images and their optimiser slots are not touched.
+ * Not reproduced: use_sde, shared trunks, schedule objects (ev2g_trpo_set_rate between calls drives one), action masks.
+ * ev2g_ppo_destroy, ev2g_ppo_sync, ev2g_ppo_get_grads and ev2g_ac_get_weights serve this kind too; the other ev2g_ppo_* and the ev2g_a2c_*
+ * entries on a TRPO learner, and the ev2g_trpo_* entries on another kind, are EV2G_ERR_STATE. */
+typedef struct ev2g_trpo_config {
+    double lr;                                 /* 1e-3: the value function's Adam.  lr >= 0 */
+    double target_kl, cg_damping;              /* 0.01, 0.1.  target_kl > 0, cg_damping >= 0 */
+    double line_search_shrinking_factor;       /* 0.8, in (0, 1) */
+    int32_t cg_max_steps, line_search_max_iter;   /* 15, 10.  both >= 1 */
+    int32_t normalize_advantage;               /* 1 */
+} ev2g_trpo_config;
+typedef struct ev2g_trpo_info {
+    int64_t lds_bytes, workspace_bytes;        /* the kernels' dynamic LDS (never more than ev2g_ppo_query's); slabs + the solve's vectors */
+    int32_t grid_cap, n_params, n_actor;       /* as ev2g_ppo_info; elements of a flat actor vector */
+} ev2g_trpo_info;
+typedef struct ev2g_trpo_report {
+    int32_t cg_iterations, line_search_tries, accepted, failed;   /* failed: no try was made (x . Hx not positive) */
+    double objective_before, objective_after;  /* J(theta0); J of the last try evaluated (0 when none was) */
+    double kl, beta, c, xHx;                   /* KL of the last try evaluated; the full step; the last coefficient; x . Hx, damping included */
+} ev2g_trpo_report;
+/* Host-only: the plan of a network's TRPO learner.  Accepts exactly what ev2g_ppo_query accepts. */
+int ev2g_trpo_query(int d_in, int h1, int h2, int v1, int v2, int d_out, ev2g_trpo_info *info);
+/* As ev2g_ppo_create: one learner per policy of any kind (EV2G_ERR_STATE for a second), EV2G_ERR_ARG naming the field for an out-of-range value. */
+int ev2g_trpo_create(ev2g_handle *h, ev2g_acpolicy *ac, const ev2g_trpo_config *cfg, ev2g_ppo **out);
+int ev2g_trpo_set_rate(ev2g_handle *h, ev2g_ppo *learner, double lr);
+/* g, J(theta0) and mu0 over rows idx[0 .. B) of the DEVICE float32 arrays (as ev2g_ppo_grad, without returns).  g goes into the actor's seven
+ * arrays of the gradient ev2g_ppo_get_grads reads; the six value arrays of it are untouched.  objective: float64 [1] DEVICE, may be NULL. */
+int ev2g_trpo_grad(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *old_log_prob, const float *advantages,
+                   const int32_t *idx, int B, double *objective);
+/* One product: v [n_actor] -> H v [n_actor], both DEVICE float32, flat in the actor's order, at the current parameters, cg_damping included. */
+int ev2g_trpo_fvp(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const int32_t *idx, int B, const float *v, float *Hv);
+/* The whole policy step.  Asynchronous: ev2g_trpo_get_report (or ev2g_ppo_sync) waits for it. */
+int ev2g_trpo_policy_step(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *actions, const float *old_log_prob,
+                          const float *advantages, const int32_t *idx, int B);
+/* One critic minibatch: the value gradient over rows idx[0 .. B), then Adam.  value_loss: float32 [1] DEVICE, may be NULL. */
+int ev2g_trpo_critic_minibatch(ev2g_handle *h, ev2g_ppo *learner, const float *obs, const float *returns, const int32_t *idx, int B, float *value_loss);
+/* What the last ev2g_trpo_policy_step did (EV2G_ERR_STATE before the first).  Synchronises. */
+int ev2g_trpo_get_report(ev2g_handle *h, ev2g_ppo *learner, ev2g_trpo_report *report);
+/* The last step's x and g, flat in the actor's order, into HOST float64 arrays [n_actor] (either may be NULL).  EV2G_ERR_STATE before the first
+ * step.  Synchronises. */
+int ev2g_trpo_get_direction(ev2g_handle *h, ev2g_ppo *learner, double *x, double *g);
+/* Host twins.  ev2g_host_trpo_cg_step: one iteration of the solve's vector algebra from a given Hp, x / r / p [n] float64 updated in place,
+ * *rho in and out; returns through *done whether the solve has ended (the last iteration, or rho' < 1e-10).  ev2g_host_trpo_rows: the row terms
+ * of J and KL, j / kl [B] float64, from mean / mean0 / actions [B, P], log_std / log_std0 [P], old_log_prob / advantages [B]. */
+int ev2g_host_trpo_cg_step(double *x, double *r, double *p, const double *Hp, int64_t n, double *rho, int last, int32_t *done);
+int ev2g_host_trpo_rows(const float *mean, const float *mean0, const float *actions, const float *log_std, const float *log_std0,
+                        const float *old_log_prob, const float *advantages, int B, int P, int normalize_advantage, double *j, double *kl);
 
 /* ---- the off-policy learner of the device replay ring: SB3's TD3.train() for TD3Policy, with DDPG as a preset (csrc/ev2g_td3.h) ----
  * One gradient step per call on a batch (s, a, r, s', done) of B rows, the update counter n incremented first:
