@@ -613,6 +613,7 @@ __global__ void __launch_bounds__(EV2G_BLOCK) ev2g_step_kernel(DevScn s, DevStat
             }
             for (int idx = tid; idx < ne * 8; idx += EV2G_BLOCK) st.env_acc[(long long)e0 * 8 + idx] = 0.0;
             for (int idx = tid; idx < ne; idx += EV2G_BLOCK) st.hist[EV2G_HIST(e0 + idx, 0, T, s.R) + 1] = 0.0;
+            for (int idx = tid; idx < ne; idx += EV2G_BLOCK) st.env_fault[e0 + idx] = 0;   // as ev2g_reset_kernel and ev2g_env_reset: faults are those since the last reset
             t = 0;
             __syncthreads();
         }

@@ -56,7 +56,17 @@ def _yaml_variant(base, overrides, name):
     return p
 
 
-def _topology_file(name, transformers):
+def threshold_cases():
+    """tests/threshold_cases.py (the policies on the reference's decision thresholds), loaded by path: the reference tree comes first on sys.path."""
+    import importlib.util
+    if "threshold_cases" not in sys.modules:
+        spec = importlib.util.spec_from_file_location("threshold_cases", os.path.join(REPO, "tests", "threshold_cases.py"))
+        sys.modules["threshold_cases"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(sys.modules["threshold_cases"])
+    return sys.modules["threshold_cases"]
+
+
+def _topology_file(name, transformers, min_charge_current=6, min_discharge_current=0):
     """Write a charging_network_topology JSON in the layout of example_config_files/charging_topology_10.json:
     transformers = [(max_power, [(n_ports, max_charge_current, max_discharge_current, voltage, phases), ...]), ...]."""
     import json
@@ -64,7 +74,8 @@ def _topology_file(name, transformers):
     for i, (max_power, chargers) in enumerate(transformers):
         chs = {}
         for n_ports, imax, dmax, volt, ph in chargers:
-            chs[f"charger_{k + 1}"] = dict(id=k, min_charge_current=6, max_charge_current=imax, min_discharge_current=0,
+            lo_c, lo_d = [m[k] if isinstance(m, (list, tuple)) else m for m in (min_charge_current, min_discharge_current)]   # one value, or one per charger
+            chs[f"charger_{k + 1}"] = dict(id=k, min_charge_current=lo_c, max_charge_current=imax, min_discharge_current=lo_d,
                                            max_discharge_current=dmax, voltage=volt, n_ports=n_ports, charger_type="AC", phases=ph)
             k += 1
         topo[f"transformer_{i + 1}"] = dict(id=i + 1, max_power=max_power, charging_stations=chs)
@@ -187,6 +198,9 @@ def run_case(name, config, state_fn, reward_fn, seed, policy, steps=None, env=No
     elif policy == "mixed":     # many exact zeros and sign flips (cycle counter, a==0 branch)
         act = rng.uniform(lo, 1.0, (T, P)) * (rng.random((T, P)) < 0.7)
         act[rng.random((T, P)) < 0.1] = 1.0
+    elif policy in threshold_cases().POLICIES:   # on the decision thresholds (tests/threshold_cases.py): edge_*.npz
+        from ev2gym_amd.scenario import ScenarioBatch
+        act = threshold_cases().policy(policy, lo, (T, 1, P), seed, ScenarioBatch.from_single(scn))[:, 0]
     elif policy.startswith("agent:"):
         # actions chosen, step by step, by one of the reference's env-reading heuristics (baselines/heuristics.py:7-267); the
         # fixture records what the agent chose.  The restated agent of ev2gym_amd (same name) is driven on the SAME reference env
@@ -407,6 +421,24 @@ def main():
     tp2 = _topology_file("het_b", [(100, [(4, 32, 0, 400, 3), (2, 16, 0, 230, 1), (2, 32, 0, 400, 3), (1, 16, 0, 400, 3), (1, 32, 0, 400, 3), (1, 32, 0, 230, 3)])])
     t2 = _yaml_variant(pst, {"charging_network_topology": tp2, "spawn_multiplier": 10}, "pst_topo_het_b")
     cases.append(("topo_pst_het_mixed_s43", t2, *PST, 43, "mixed", None))
+    # actions ON the reference's decision thresholds (tests/threshold_cases.py says which classes each case is built for): edge_*.npz.
+    # The two topology files are 230 V single-phase 16 A / 32 A chargers (the site's configured voltage and phases with them: the transformers
+    # take theirs from the config, transformer.py:39-40) whose `min - 0.01` edges are +-4 A or +-8 A: below and above the gate of the
+    # homogeneous EVs, 1.38 kW = 6 A exactly, so that neither decision always hides the other (heterogeneous specs have tables and no minimum power).
+    tp3 = _topology_file("edge", [(60, [(2, 32, -32, 230, 1), (2, 16, -16, 230, 1), (1, 16, -16, 230, 1)]),
+                                  (40, [(1, 32, -32, 230, 1), (1, 16, -16, 230, 1), (1, 16, -16, 230, 1)])],
+                          [4.01, 8.01, 4.01, 8.01, 4.01, 8.01], [-3.99, -7.99, -7.99, -3.99, -3.99, -7.99])
+    site = {"voltage": 230, "phases": 1}
+    t3 = _yaml_variant(ppl, {"charging_network_topology": tp3, "spawn_multiplier": 10, "heterogeneous_ev_specs": False, "charging_station": site,
+                             "ev": {"min_ac_charge_power": 1.38, "min_discharge_power": -1.38, "ev_phases": 1}}, "v2gppl_topo_edge_gate")
+    tp4 = _topology_file("edge16", [(60, [(2, 16, -16, 230, 1), (2, 16, -16, 230, 1), (1, 16, -16, 230, 1)]),
+                                    (40, [(1, 16, -16, 230, 1), (1, 16, -16, 230, 1), (1, 16, -16, 230, 1)])], 4.01, -3.99)
+    t4 = _yaml_variant(ppl, {"charging_network_topology": tp4, "spawn_multiplier": 10, "charging_station": site}, "v2gppl_topo_edge_lut")
+    for name, cfg, fns in [("edge_v2gppl_lat64_s91", ppl, PPL), ("edge_pst_lat64_s92", pst, PST), ("edge_v2gmax_dec_s93", vmax, VMX),
+                           ("edge_v2gppl_gates_lat64_s94", gates, PPL), ("edge_v2gppl_p2_latwild_s95", p2, PPL), ("edge_pst_p3_latwild_s96", p3, PST),
+                           ("edge_v2gppl_c10r3_lat64_s97", r3, PPL), ("edge_topo_v2gppl_het_gate_s98", t3, PPL),
+                           ("edge_topo_v2gppl_het_lat32_s99", t4, PPL), ("edge_v2gppl_ts5_dec_s100", ts5, PPL)]:
+        cases.append((name, cfg, *fns, int(name.rsplit("_s", 1)[1]), threshold_cases().EDGE_FIXTURES[name][0], None))
     for c in cases:
         if only and c[0] not in only:
             continue

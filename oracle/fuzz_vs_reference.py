@@ -28,6 +28,7 @@ def main(n_cases):
     from ev2gym_amd import _abi
     from ev2gym_amd.scenario import ScenarioBatch
     from oracle import Oracle
+    tc = cg.threshold_cases()
     base = "ev2gym/example_config_files/"
     rng = np.random.default_rng(int(os.environ.get("EV2G_FUZZ_SEED", "2026")))
     worst = 0.0
@@ -59,12 +60,21 @@ def main(n_cases):
         err = np.abs(o[0] - obs0).max()
         T, P = env.simulation_length, env.number_of_ports
         lo = -1.0 if env.config["v2g_enabled"] else 0.0
-        pol = rng.choice(["rand", "wild", "mixed"])
+        # three continuous policies and the five on the decision thresholds: of n cases about 3 n / 8 are continuous ones (all of them before
+        # the threshold policies were added) -- raise n_cases accordingly when it is the continuous ones that matter
+        pol = str(rng.choice(["rand", "wild", "mixed"] + list(tc.POLICIES)))
+        edge = tc.policy(pol, lo, (T, 1, P), seed, batch)[:, 0] if pol in tc.POLICIES else None   # on the decision thresholds (tests/threshold_cases.py)
         info = None
         faulted = False
         for t in range(T):
-            a = rng.uniform(lo, 1.0, P) if pol == "rand" else (rng.uniform(-1.6 if lo < 0 else 0, 1.6, P) if pol == "wild"
-                                                                 else rng.uniform(lo, 1.0, P) * (rng.random(P) < 0.7))
+            if edge is not None:
+                a = edge[t]
+            elif pol == "rand":
+                a = rng.uniform(lo, 1.0, P)
+            elif pol == "wild":
+                a = rng.uniform(-1.6 if lo < 0 else 0, 1.6, P)
+            else:
+                a = rng.uniform(lo, 1.0, P) * (rng.random(P) < 0.7)
             try:
                 ro, rr, rd, _, info = env.step(a.copy())
             except Exception as ex:   # the reference's over-current exception (ev_charger.py:203-205): the oracle must flag the same step
@@ -86,7 +96,7 @@ def main(n_cases):
         ora.close()
         worst = max(worst, err)
         print(f"case {case:3d} {sf:22s} {rf:40s} {'topology ' + str([c.n_ports for c in env.charging_stations]) if topo else ''} C={len(env.charging_stations):2d} npc={over['number_of_ports_per_cs']} R={len(env.transformers)} "
-              f"dt={over['timescale']:2d} het={int(over['heterogeneous_ev_specs'])} {pol:5s} max rel err {err:.2e}" + (" (over-current fault at the same step)" if faulted else ""), flush=True)
+              f"dt={over['timescale']:2d} het={int(over['heterogeneous_ev_specs'])} {pol:7s} max rel err {err:.2e}" + (" (over-current fault at the same step)" if faulted else ""), flush=True)
         assert err < 1e-9, "oracle and reference disagree"
     print(f"{n_cases} cases, worst relative error {worst:.2e}")
 

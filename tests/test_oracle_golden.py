@@ -82,3 +82,35 @@ def test_step_after_done_is_an_error(golden):
     *_, rc = o.step(z["act"][0:1].copy())
     assert rc == _abi.ERR_DONE  # `assert not self.done` (ev2gym_env.py:343)
     o.close()
+
+
+def test_fixtures_keep_the_site_voltage_on_charger_zero(golden):
+    """A KNOWN LIMITATION, pinned.  The reference's transformers take their voltage from the site's configuration, `charging_station.voltage *
+    sqrt(phases)` (transformer.py:39-40); the capture records it as `scn_tr_voltage`, but the scenario batch has no field for it, and the oracle
+    (ev2g_oracle.c: `tr->voltage`) and the facade (ev2gym_amd/env.py: Transformer.voltage / max_current) take charger 0's instead.  Only the
+    inspection values `tr_amps` / `max_current` depend on it -- no observation, reward, statistic or decision does.  Every committed fixture
+    therefore has charger 0 at the site's voltage: the two edge_topo_* ones, whose chargers are all 230 V single-phase, set the site to that.  A
+    fixture that breaks this fails here first, with the reason, rather than in the trajectory test's `tr_amps`."""
+    z, batch, _, _ = golden
+    site = batch.arrays["cs_voltage"][0] * np.sqrt(float(batch.arrays["cs_phases"][0]))
+    assert np.array_equal(np.asarray(z["scn_tr_voltage"], float), np.full(batch.n_transformers, site)), (z["scn_tr_voltage"], site)
+
+
+def test_oracle_transformer_current_uses_charger_zeros_voltage():
+    """The other half of the limitation above, as the oracle behaves today: on a topology whose first charger is 230 V single-phase at a 400 V
+    three-phase site, `tr_amps` before any EV draws current is the transformer's power over charger 0's 230 V, where the reference divides by
+    400 * sqrt(3).  When the batch learns the site's voltage, this test changes with it."""
+    from ev2gym_amd.scenario_gen import GenConfig, generate
+    topo = dict(n_ports=np.array([2, 1, 1]), transformer=np.array([0, 0, 1]), min_charge_current=np.zeros(3), max_charge_current=np.array([16.0, 32.0, 32.0]),
+                min_discharge_current=np.zeros(3), max_discharge_current=-np.array([16.0, 32.0, 32.0]), voltage=np.array([230.0, 400.0, 400.0]),
+                phases=np.array([1, 3, 3]), tr_max_power=np.array([60.0, 40.0]))
+    pool = generate(GenConfig(n_envs=2, topology=topo, seed=3))
+    o = Oracle(pool, 0, 0)
+    o.reset()
+    o.step(np.zeros((pool.n_envs, pool.n_ports)))
+    for e in range(pool.n_envs):
+        pk = o.peek(e)
+        assert np.abs(pk["tr_power"]).max() > 0
+        _close(pk["tr_amps"], pk["tr_power"] * 1000.0 / 230.0, f"env {e}: tr_amps over charger 0's voltage")
+        assert np.abs(pk["tr_amps"] - pk["tr_power"] * 1000.0 / (400.0 * np.sqrt(3.0))).max() > 1.0
+    o.close()

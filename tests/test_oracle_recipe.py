@@ -35,8 +35,9 @@ def test_differential_fuzz_against_the_live_reference_starts_and_agrees():
 
 @needs_reference
 def test_capture_script_regenerates_committed_fixtures(tmp_path):
-    """One `agent_*` and one `b2b_*` case: the two families that import ev2gym_amd after the reference (the ones that broke)."""
-    names = ["agent_roundrobin_pst_s61", "b2b_pst_rand_s53"]
+    """One `agent_*` and one `b2b_*` case: the two families that import ev2gym_amd after the reference (the ones that broke); two `edge_*`
+    cases: their actions come from tests/threshold_cases.py, one of them through the scenario the reference drew (the `gate` policy)."""
+    names = ["agent_roundrobin_pst_s61", "b2b_pst_rand_s53", "edge_topo_v2gppl_het_gate_s98", "edge_v2gppl_p2_latwild_s95"]
     _run([os.path.join(ROOT, "oracle", "capture_golden.py")] + names, env={"EV2G_GOLDEN_OUT": str(tmp_path)})
     for n in names:
         new, old = np.load(tmp_path / (n + ".npz"), allow_pickle=False), np.load(os.path.join(ROOT, "tests", "golden", n + ".npz"), allow_pickle=False)
