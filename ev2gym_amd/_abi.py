@@ -188,6 +188,30 @@ class TqcConfigC(C.Structure):   # ev2g_tqc_config, in header order: ev2g_sac_co
     _fields_ = SacConfigC._fields_ + [("n_quantiles", C.c_int32), ("top_quantiles_to_drop_per_net", C.c_int32)]
 
 
+class ArsConfigC(C.Structure):   # ev2g_ars_config, in header order
+    _fields_ = [("learning_rate", C.c_double), ("delta_std", C.c_double), ("alive_bonus_offset", C.c_double), ("n_delta", C.c_int32), ("n_top", C.c_int32)]
+
+
+class ArsInfoC(C.Structure):   # ev2g_ars_info
+    _fields_ = [("max_in", C.c_int32), ("max_hidden", C.c_int32), ("max_out", C.c_int32), ("max_delta", C.c_int32), ("n_params", C.c_int32),
+                ("candidate_floats", C.c_int64), ("image_bytes", C.c_int64), ("delta_bytes", C.c_int64), ("total_bytes", C.c_int64), ("lds_bytes", C.c_int64)]
+
+
+class ArsReportC(C.Structure):   # ev2g_ars_report
+    _fields_ = [("sigma_r", C.c_double), ("step", C.c_double), ("iteration", C.c_int64), ("refused", C.c_int32), ("first_bad", C.c_int32), ("n_top", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+ARS_KINDS = {"MlpPolicy": 0, "LinearPolicy": 1}   # EV2G_ARS_MLP, EV2G_ARS_LINEAR
+
+
+def ars_param_shapes(kind, d_in, h1, h2, d_out):
+    """theta's arrays in parameters_to_vector order: the MLP policy's six, the linear policy's one."""
+    if kind == "LinearPolicy":
+        return [(d_out, d_in)]
+    return [(h1, d_in), (h1,), (h2, h1), (h2,), (d_out, h2), (d_out,)]
+
+
 TD3_MAX_BATCH = 1024   # EV2G_TD3_MAX_BATCH
 
 

@@ -40,6 +40,7 @@
 #include "ev2g_td3_host.h"
 #include "ev2g_sac_host.h"
 #include "ev2g_tqc_host.h"
+#include "ev2g_ars.h"
 #include <cstdlib>
 
 static thread_local std::string g_create_error;
@@ -196,6 +197,26 @@ struct ev2g_tqc : SacCore {
     TqcPlan tq;
 };
 
+// an ARS learner (ev2g_ars_create, ev2g_ars.h): theta, the centre image and the 2 n_delta candidate images, the directions of the last perturb,
+// the envs' returns (regrown with E, in swap_allocs, with the object's observation, action, reward, done and mask rows), the candidates' returns, the ranks
+// and the report; what the host knows of an iteration's progress
+struct ev2g_ars : DevOwner {
+    ev2g_ars_config cfg{};
+    ArsPlan plan;
+    ArsDev dev{};
+    float *theta = nullptr, *centre = nullptr, *cand = nullptr, *delta = nullptr;
+    double *ret = nullptr, *env_return = nullptr, *reward = nullptr;
+    int32_t *rank = nullptr, *order = nullptr;
+    ev2g_ars_report *report = nullptr;
+    float *obs32 = nullptr, *act32 = nullptr;
+    uint8_t *done = nullptr, *mask = nullptr;   // [E], [E, P]: every step's, overwritten (the full step instantiation writes all its outputs)
+    long long rows_E = 0, rows_D = 0, rows_P = 0, rows_T = 0;   // what the swap blocks were sized for
+    unsigned long long seed = 0, iter = 0;   // the next perturb's iteration
+    long long updates = 0, steps = 0;        // updates queued; env steps since the last perturb
+    int roll_E = 0;                          // the envs of the rollouts since the last perturb (0: none)
+    bool have_dirs = false, returns_set = false;
+};
+
 #define EV2G_EV_RING TIMING_RING
 struct ev2g_handle {
     int device = 0;
@@ -309,6 +330,8 @@ struct ev2g_handle {
     std::vector<ev2g_td3 *> td3s;               // the TD3 / DDPG learners created on this handle (freed with it, or with their policy)
     std::vector<ev2g_sac *> sacs;               // the SAC learners created on this handle (freed with it)
     std::vector<ev2g_tqc *> tqcs;               // the TQC learners created on this handle (freed with it)
+    std::vector<ev2g_ars *> arss;               // the ARS learners created on this handle (freed with it)
+    unsigned ars_attr_mask = 0;                 // ev2g_ars_act_kernel instantiations (bit kind) whose dynamic-LDS attribute was set for this handle's device
     unsigned sac_attr_mask = 0;                 // ev2g_sac_act_kernel instantiations whose dynamic-LDS attribute was set for this handle's device
     unsigned trpo_attr_mask = 0;                // the TRPO kernels likewise (bit relu)
     unsigned ppo_attr_mask = 0;               // ev2g_ppo_grad_kernel instantiations (bit relu + 2 head) whose dynamic-LDS attribute was set
@@ -644,6 +667,7 @@ void ev2g_destroy(ev2g_handle *h) {
     release_all(h->td3s, td3_free);
     release_all(h->sacs);
     release_all(h->tqcs);
+    release_all(h->arss);
     release_all(h->acs);
     ev2g_comm_destroy(h);
     drop_rollout_graphs(h);
@@ -1316,6 +1340,11 @@ struct StepChain {
     ev2g_acpolicy *ac = nullptr;
     bool ac_deterministic = false, ac_direct = false;
     Rows<float> ac_obs, ac_actions, ac_values, ac_log_probs;
+    // an ARS learner (not with a link, a grid or a wrapper): its population (or centre) launch reads the object's float32 observation row and
+    // writes its action row; the step reads that row and writes the next observation over the first -- per launch on the fast path (ars_direct),
+    // through the registered hand-over pair with device-to-device copies elsewhere, as the actor-critic's stage
+    ev2g_ars *ars = nullptr;
+    bool ars_population = false, ars_direct = false;
     Rows<double> obs, reward;   // every step's outputs
     Rows<uint8_t> done, mask;
     int auto_reset = 0;                // an episode end inside the segment (chain_steps; run_chain refuses it up front): 0 ends the call with EV2G_ERR_DONE
@@ -1327,6 +1356,7 @@ static int run_chain(ev2g_handle *h, StepChain c, int k);
 static int wrap_launch(ev2g_handle *h, ev2g_wrap *w, const void *in, bool in32, double *out);
 static int ac_launch(ev2g_handle *h, ev2g_acpolicy *ac, const float *x, int n_rows, bool sample, float *mean, float *actions, float *clipped,
                      float *value, float *log_prob);
+static int ars_launch(ev2g_handle *h, ev2g_ars *a, const float *x, int n_rows, bool population, float *actions);
 
 int ev2g_step(ev2g_handle *h, const double *actions, double *obs, double *reward, uint8_t *done, uint8_t *action_mask) {
     if (!h || !h->loaded) return fail(h, EV2G_ERR_STATE, "ev2g_step: no scenarios loaded");
@@ -2094,16 +2124,27 @@ static int chain_steps(ev2g_handle *h, const StepChain &c, int k) {
             if (!c.ac_direct)
                 HIPCHK(h, hipMemcpyAsync((void *)h->extras.actions_f32, c.ac->clipped, EP * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         }
+        if (c.ars) {
+            if (c.ars_direct) {
+                if ((rc = ars_launch(h, c.ars, c.ars->obs32, h->E, c.ars_population, c.ars->act32))) return rc;
+            } else {
+                if (i == 0) HIPCHK(h, hipMemcpyAsync(h->extras.obs_f32, c.ars->obs32, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+                if ((rc = ars_launch(h, c.ars, (const float *)h->extras.obs_f32, h->E, c.ars_population, (float *)h->extras.actions_f32))) return rc;
+            }
+        }
         StepIO io = make_io(h, StepRows{{act_i, c.a_stride_to_kernel ? c.actions.stride : 0}, {c.obs.at(i)}, {c.reward.at(i)}, {c.done.at(i)}, {c.mask.at(i)}},
                             c.count_steps ? i : 0, 0);
         if (c.ac && c.ac_direct) { io.act32 = c.ac->clipped; io.obs32 = c.ac_obs.at(i + 1); }
+        if (c.ars && c.ars_direct) { io.act32 = c.ars->act32; io.obs32 = c.ars->obs32; }
         if ((rc = launch_steps(h, io, h->current_step, 1, 0))) return rc;
+        if (c.ars && !c.ars_direct)
+            HIPCHK(h, hipMemcpyAsync(c.ars->obs32, h->extras.obs_f32, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         if (c.ac && !c.ac_direct)
             HIPCHK(h, hipMemcpyAsync(c.ac_obs.at(i + 1), h->extras.obs_f32, ED * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         if (g && (rc = grid_launch_step(h, g, c.vm.at(i), c.reward.at(i), c.base_weight, c.voltage_weight))) return rc;
         h->current_step += 1;
         // (collect_direct promises the full instantiation; were it ever wrong the step has run and is counted, the rows of this step are not to be trusted)
-        if (c.ac && c.ac_direct && h->last.specialisation <= 0) return fail(h, EV2G_ERR_STATE, std::string(c.who) + ": internal: the direct path needs the full instantiation");
+        if (((c.ac && c.ac_direct) || (c.ars && c.ars_direct)) && h->last.specialisation <= 0) return fail(h, EV2G_ERR_STATE, std::string(c.who) + ": internal: the direct path needs the full instantiation");
         if (l && l->p_delay > 0.0) {
             if ((rc = link_launch_obs(h, l, h->current_step, c.obs.at(i), c.actor ? l->obs32 : nullptr))) return rc;
         } else if (l && c.actor) {
@@ -2126,7 +2167,9 @@ static int run_chain(ev2g_handle *h, StepChain c, int k) {
         return fail(h, EV2G_ERR_ARG, who + ": negative step count or stride");
     if (c.ac && (l || g || c.wrap))
         return fail(h, EV2G_ERR_ARG, who + ": a Gaussian actor-critic does not stack with a link, a grid or an action wrapper");
-    if (!c.agent && !c.actor && !c.ac && !c.actions.p) return fail(h, EV2G_ERR_ARG, who + ": without an agent the " + (l ? "raw " : "") + "actions are read from `actions`");
+    if (c.ars && (l || g || c.wrap || c.ac || c.agent || c.actor))
+        return fail(h, EV2G_ERR_ARG, who + ": an ARS learner does not stack with a link, a grid, an action wrapper or another action source");
+    if (!c.agent && !c.actor && !c.ac && !c.ars && !c.actions.p) return fail(h, EV2G_ERR_ARG, who + ": without an agent the " + (l ? "raw " : "") + "actions are read from `actions`");
     // the engine resets lazily inside the step launch after an episode end, so an agent's launch for the new episode's first step would
     // read the finished episode's ports: segments stay inside one episode, the caller resets in between
     if (h->current_step + k > h->T) return fail(h, EV2G_ERR_DONE, who + ": the segment would run past the episode end");
@@ -4078,6 +4121,304 @@ static int stats_reset_impl(ev2g_handle *h, double *stats, double *obs, float *o
 }
 int ev2g_get_stats_reset(ev2g_handle *h, double *stats, double *obs, int64_t scenario_offset) { return stats_reset_impl(h, stats, obs, nullptr, scenario_offset); }
 int ev2g_get_stats_reset_f32(ev2g_handle *h, double *stats, float *obs32, int64_t scenario_offset) { return stats_reset_impl(h, stats, nullptr, obs32, scenario_offset); }
+
+// ---- the ARS learner and its population actor (ev2g_ars.h) ----
+static int ars_check(ev2g_handle *h, ev2g_ars *a, const char *who) { return owned_check(h, &ev2g_handle::arss, a, "ARS learner", who, false); }
+
+struct ArsActEntry {
+    const void *fn;
+    void (*launch)(const LaunchDims &, const ArsDev &, const float *images, const float *x, int R, float *act);
+};
+extern "C++" template <int KIND>
+static void launch_ars_act(const LaunchDims &d, const ArsDev &dev, const float *images, const float *x, int R, float *act) {
+    hipLaunchKernelGGL(ev2g_ars_act_kernel<KIND>, d.grid, dim3(EV2G_AC_BLOCK), d.lds, d.stream, dev, images, x, R, act);
+}
+static const ArsActEntry &ars_act_kernel(int kind) {
+    static const ArsActEntry tab[2] = {{(const void *)ev2g_ars_act_kernel<EV2G_ARS_MLP>, &launch_ars_act<EV2G_ARS_MLP>},
+                                       {(const void *)ev2g_ars_act_kernel<EV2G_ARS_LINEAR>, &launch_ars_act<EV2G_ARS_LINEAR>}};
+    return tab[kind == EV2G_ARS_LINEAR ? 1 : 0];
+}
+static unsigned ars_blocks(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 1 << 16); }
+
+// one launch of ev2g_ars_act_kernel over n_rows rows: C = 2 n_delta candidates of n_rows / C rows over the candidate images, or the centre image
+static int ars_launch(ev2g_handle *h, ev2g_ars *a, const float *x, int n_rows, bool population, float *actions) {
+    const int C = population ? 2 * a->plan.n_delta : 1, R = n_rows / C;
+    const LaunchDims dims{dim3((unsigned)(C * ars_tiles_per_candidate(R))), a->plan.lds, h->stream};
+    ars_act_kernel(a->plan.kind).launch(dims, a->dev, population ? a->cand : a->centre, x, R, actions);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+int ev2g_ars_default_config(ev2g_ars_config *cfg) {
+    if (!cfg) return fail(nullptr, EV2G_ERR_ARG, "ev2g_ars_default_config: cfg is null");
+    ars_default_config(cfg);
+    return EV2G_OK;
+}
+
+int ev2g_ars_query(const ev2g_ars_config *cfg, int kind, int d_in, int h1, int h2, int d_out, ev2g_ars_info *out) {
+    if (!cfg || !out) return fail(nullptr, EV2G_ERR_ARG, "ev2g_ars_query: null argument");
+    const std::string refusal = ars_config_refusal("ev2g_ars_query", *cfg);
+    if (!refusal.empty()) return fail(nullptr, EV2G_ERR_ARG, refusal);
+    const ArsPlan p = plan_ars(kind, d_in, h1, h2, d_out, cfg->n_delta, cfg->n_top);
+    if (p.err) return fail(nullptr, p.err, p.refusal);
+    *out = ev2g_ars_info{EV2G_AC_MAX_IN, EV2G_AC_MAX_HIDDEN, EV2G_AC_MAX_OUT, EV2G_ARS_MAX_DELTA, p.lay.n_params, (int64_t)p.dev.stride,
+                         (int64_t)p.image_bytes, (int64_t)p.delta_bytes, (int64_t)p.total_bytes, (int64_t)p.lds};
+    return EV2G_OK;
+}
+
+static int ars_launch_repack(ev2g_handle *h, ev2g_ars *a) {
+    hipLaunchKernelGGL(ev2g_ars_repack_kernel, dim3(ars_blocks(a->plan.lay.n_params)), dim3(256), 0, h->stream, a->plan.lay, (const float *)a->theta, a->centre);
+    HIPCHK(h, hipGetLastError());
+    return EV2G_OK;
+}
+
+static int ars_device_stage(ev2g_handle *h, ev2g_ars *a, const float *theta) {
+    const ArsPlan &p = a->plan;
+    const size_t n = (size_t)p.lay.n_params, nd = (size_t)p.n_delta, stride = (size_t)p.dev.stride;
+    if (int rc = dalloc(h, a->allocs, n, &a->theta)) return rc;
+    if (int rc = dalloc(h, a->allocs, stride, &a->centre)) return rc;          // (zeros: the padding nothing writes afterwards)
+    if (int rc = dalloc(h, a->allocs, 2 * nd * stride, &a->cand)) return rc;
+    if (int rc = dalloc(h, a->allocs, nd * n, &a->delta)) return rc;
+    if (int rc = dalloc(h, a->allocs, 2 * nd, &a->ret)) return rc;
+    if (int rc = dalloc(h, a->allocs, nd, &a->rank)) return rc;
+    if (int rc = dalloc(h, a->allocs, nd, &a->order)) return rc;
+    if (int rc = dalloc(h, a->allocs, 1, &a->report)) return rc;
+    if (theta) HIPCHK(h, hipMemcpyAsync(a->theta, theta, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (int rc = ars_launch_repack(h, a)) return rc;
+    const unsigned bit = 1u << (p.kind == EV2G_ARS_LINEAR ? 1 : 0);
+    if (p.lds > 48 * 1024 && !(h->ars_attr_mask & bit)) {   // (function attributes are per device: once per handle, for the largest network)
+        const hipError_t e = hipFuncSetAttribute(ars_act_kernel(p.kind).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev2g_sac_lds_max());
+        if (e != hipSuccess) return fail(h, EV2G_ERR_HIP, std::string("ev2g_ars_create: hipFuncSetAttribute: ") + hipGetErrorString(e));
+        h->ars_attr_mask |= bit;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // theta is the caller's
+    return EV2G_OK;
+}
+
+int ev2g_ars_create(ev2g_handle *h, const ev2g_ars_config *cfg, int kind, int d_in, int h1, int h2, int d_out, float lo, const float *theta, uint64_t seed,
+                    ev2g_ars **out) {
+    const char *who = "ev2g_ars_create";
+    if (!h || !out) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    *out = nullptr;
+    if (!cfg) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    const std::string refusal = ars_config_refusal(who, *cfg);
+    if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+    const ArsPlan plan = plan_ars(kind, d_in, h1, h2, d_out, cfg->n_delta, cfg->n_top);
+    if (plan.err) return fail(h, plan.err, plan.refusal);
+    if (lo != -1.0f && lo != 0.0f) return fail(h, EV2G_ERR_ARG, std::string(who) + ": lo must be -1 or 0");
+    if (theta)
+        for (int i = 0; i < plan.lay.n_params; i++)
+            if (!std::isfinite(theta[i])) return fail(h, EV2G_ERR_ARG, std::string(who) + ": theta[" + std::to_string(i) + "] is not finite");
+    (void)hipSetDevice(h->device);
+    ev2g_ars *a = new ev2g_ars();
+    a->cfg = *cfg; a->plan = plan; a->dev = plan.dev; a->dev.lo = lo; a->seed = seed;
+    return owned_created(h, &ev2g_handle::arss, a, ars_device_stage(h, a, theta), out);
+}
+
+void ev2g_ars_destroy(ev2g_handle *h, ev2g_ars *a) { owned_destroy(h, &ev2g_handle::arss, a); }
+
+int ev2g_ars_perturb(ev2g_handle *h, ev2g_ars *a) {
+    if (int rc = ars_check(h, a, "ev2g_ars_perturb")) return rc;
+    const ArsPlan &p = a->plan;
+    hipLaunchKernelGGL(ev2g_ars_perturb_kernel, dim3(ars_blocks((long long)p.n_delta * p.lay.n_params)), dim3(256), 0, h->stream, p.lay, (const float *)a->theta,
+                       p.n_delta, (float)a->cfg.delta_std, (uint64_t)a->seed, (uint64_t)a->iter, (long long)p.dev.stride, a->delta, a->cand);
+    HIPCHK(h, hipGetLastError());
+    if (a->env_return) HIPCHK(h, hipMemsetAsync(a->env_return, 0, (size_t)a->rows_E * sizeof(double), h->stream));
+    a->iter += 1; a->steps = 0; a->roll_E = 0; a->have_dirs = true; a->returns_set = false;
+    return EV2G_OK;
+}
+
+int ev2g_ars_act(ev2g_handle *h, ev2g_ars *a, const float *obs32, int n_rows, int population, float *actions) {
+    const char *who = "ev2g_ars_act";
+    if (int rc = ars_check(h, a, who)) return rc;
+    if (!obs32 || !actions || n_rows <= 0) return fail(h, EV2G_ERR_ARG, std::string(who) + ": obs32 or actions is null, or n_rows is not positive");
+    if (population) {
+        const std::string refusal = ars_rows_refusal(who, "n_rows", n_rows, a->plan.n_delta);
+        if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+        if (!a->have_dirs) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no candidates yet (ev2g_ars_perturb first)");
+    }
+    return ars_launch(h, a, obs32, n_rows, population != 0, actions);
+}
+
+// the object's rows for the loaded shape: the observation and action rows, the envs' returns and the reward rows of one episode
+static int ars_rows(ev2g_handle *h, ev2g_ars *a, const char *who) {
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (a->obs32 && a->rows_E == h->E && a->rows_D == h->D && a->rows_P == h->P && a->rows_T == h->T) return EV2G_OK;
+    if (a->roll_E) return fail(h, EV2G_ERR_STATE, std::string(who) + ": the loaded shape changed inside an iteration (ev2g_ars_perturb starts the next one)");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    free_pool(a->swap_allocs);
+    a->obs32 = a->act32 = nullptr; a->env_return = a->reward = nullptr; a->done = a->mask = nullptr;
+    a->rows_E = h->E; a->rows_D = h->D; a->rows_P = h->P; a->rows_T = h->T;
+    if (int rc = dalloc(h, a->swap_allocs, (size_t)h->E * h->D, &a->obs32)) return rc;
+    if (int rc = dalloc(h, a->swap_allocs, (size_t)h->E * h->P, &a->act32)) return rc;
+    if (int rc = dalloc(h, a->swap_allocs, (size_t)h->E, &a->env_return)) return rc;
+    if (int rc = dalloc(h, a->swap_allocs, (size_t)h->E, &a->done)) return rc;
+    if (int rc = dalloc(h, a->swap_allocs, (size_t)h->E * h->P, &a->mask)) return rc;
+    return dalloc(h, a->swap_allocs, (size_t)h->E * h->T, &a->reward);
+}
+
+float *ev2g_ars_obs_f32(ev2g_handle *h, ev2g_ars *a) {
+    if (ars_check(h, a, "ev2g_ars_obs_f32") || ars_rows(h, a, "ev2g_ars_obs_f32")) return nullptr;
+    return a->obs32;
+}
+float *ev2g_ars_actions_f32(ev2g_handle *h, ev2g_ars *a) {
+    if (ars_check(h, a, "ev2g_ars_actions_f32") || ars_rows(h, a, "ev2g_ars_actions_f32")) return nullptr;
+    return a->act32;
+}
+
+int ev2g_ars_rollout(ev2g_handle *h, ev2g_ars *a, int k_steps, int population, double *reward, int64_t r_stride) {
+    const char *who = "ev2g_ars_rollout";
+    if (int rc = ars_check(h, a, who)) return rc;
+    if (!h->loaded) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no scenarios loaded");
+    if (k_steps < 0 || (reward && r_stride < h->E)) return fail(h, EV2G_ERR_ARG, std::string(who) + ": negative step count, or a reward stride below the env count");
+    if (a->dev.d_in != h->D) return fail(h, EV2G_ERR_ARG, std::string(who) + ": d_in " + std::to_string(a->dev.d_in) + " != the observation width " + std::to_string(h->D));
+    if (a->dev.d_out != h->P) return fail(h, EV2G_ERR_ARG, std::string(who) + ": d_out " + std::to_string(a->dev.d_out) + " != the ports " + std::to_string(h->P));
+    if (population) {
+        const std::string refusal = ars_rows_refusal(who, "the env count", h->E, a->plan.n_delta);
+        if (!refusal.empty()) return fail(h, EV2G_ERR_ARG, refusal);
+        if (!a->have_dirs) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no candidates yet (ev2g_ars_perturb first)");
+    }
+    const ev2g_step_extras &x = h->extras;
+    const bool direct = collect_direct(h);   // the two routes of ev2g_ac_collect
+    if (!direct && !(x.obs_f32 && x.actions_f32 && x.obs_f32_step_stride == 0))
+        return fail(h, EV2G_ERR_ARG, std::string(who) + ": this configuration steps through the registered float32 hand-over buffers: register them with "
+                                                        "ev2g_set_step_extras (observation step stride 0) first");
+    if (int rc = ars_rows(h, a, who)) return rc;
+    StepChain c{who};
+    c.ars = a; c.ars_population = population != 0; c.ars_direct = direct;
+    c.reward = reward ? Rows<double>{reward, (long long)r_stride} : Rows<double>{a->reward, h->E};
+    c.done = {a->done}; c.mask = {a->mask};   // (stride 0: the per-launch float32 rows need the full instantiation, which writes every output)
+    c.count_steps = false;   // (as ev2g_ac_collect: the registered buffers do not advance)
+    if (int rc = run_chain(h, c, k_steps)) return rc;
+    if (k_steps > 0) {
+        hipLaunchKernelGGL(ev2g_ars_returns_kernel, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, h->stream, a->env_return, (const double *)c.reward.p, k_steps,
+                           c.reward.stride, h->E);
+        HIPCHK(h, hipGetLastError());
+        if (population) { a->steps += k_steps; a->roll_E = h->E; }
+    }
+    return EV2G_OK;
+}
+
+int ev2g_ars_update(ev2g_handle *h, ev2g_ars *a) {
+    const char *who = "ev2g_ars_update";
+    if (int rc = ars_check(h, a, who)) return rc;
+    const ArsPlan &p = a->plan;
+    if (!a->have_dirs) return fail(h, EV2G_ERR_STATE, std::string(who) + ": no directions yet (ev2g_ars_perturb first)");
+    if (!a->returns_set && !a->roll_E)
+        return fail(h, EV2G_ERR_STATE, std::string(who) + ": no returns yet (ev2g_ars_rollout in population mode, or ev2g_ars_set_returns, first)");
+    if (!a->returns_set) {
+        const int C = 2 * p.n_delta;
+        hipLaunchKernelGGL(ev2g_ars_candidates_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, h->stream, (const double *)a->env_return, a->roll_E / C, C,
+                           a->cfg.alive_bonus_offset, a->steps, a->ret);
+    }
+    hipLaunchKernelGGL(ev2g_ars_rank_kernel, dim3(1), dim3(256), 0, h->stream, (const double *)a->ret, p.n_delta, p.n_top, a->cfg.learning_rate,
+                       (long long)a->iter - 1, a->rank, a->order, a->report);
+    hipLaunchKernelGGL(ev2g_ars_step_kernel, dim3(ars_blocks(p.lay.n_params)), dim3(256), 0, h->stream, p.lay, a->theta, (const float *)a->delta,
+                       (const double *)a->ret, (const int32_t *)a->order, (const ev2g_ars_report *)a->report, p.n_delta, p.n_top, a->centre);
+    HIPCHK(h, hipGetLastError());
+    a->updates += 1; a->returns_set = false; a->roll_E = 0;
+    return EV2G_OK;
+}
+
+int ev2g_ars_get_report(ev2g_handle *h, ev2g_ars *a, ev2g_ars_report *report, double *returns, int32_t *ranks) {
+    if (int rc = ars_check(h, a, "ev2g_ars_get_report")) return rc;
+    if (report) HIPCHK(h, hipMemcpyAsync(report, a->report, sizeof *report, hipMemcpyDeviceToHost, h->stream));
+    if (returns) HIPCHK(h, hipMemcpyAsync(returns, a->ret, (size_t)2 * a->plan.n_delta * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (ranks) HIPCHK(h, hipMemcpyAsync(ranks, a->rank, (size_t)a->plan.n_delta * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+
+static int ars_read(ev2g_handle *h, const char *who, void *dst, const void *src, size_t bytes) {
+    if (!dst) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EV2G_OK;
+}
+int ev2g_ars_get_weights(ev2g_handle *h, ev2g_ars *a, float *theta) {
+    if (int rc = ars_check(h, a, "ev2g_ars_get_weights")) return rc;
+    return ars_read(h, "ev2g_ars_get_weights", theta, a->theta, (size_t)a->plan.lay.n_params * sizeof(float));
+}
+int ev2g_ars_set_weights(ev2g_handle *h, ev2g_ars *a, const float *theta) {
+    const char *who = "ev2g_ars_set_weights";
+    if (int rc = ars_check(h, a, who)) return rc;
+    if (!theta) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    for (int i = 0; i < a->plan.lay.n_params; i++)
+        if (!std::isfinite(theta[i])) return fail(h, EV2G_ERR_ARG, std::string(who) + ": theta[" + std::to_string(i) + "] is not finite");
+    HIPCHK(h, hipMemcpyAsync(a->theta, theta, (size_t)a->plan.lay.n_params * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (int rc = ars_launch_repack(h, a)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // theta is the caller's
+    return EV2G_OK;
+}
+int ev2g_ars_get_candidate(ev2g_handle *h, ev2g_ars *a, int c, float *theta) {
+    const char *who = "ev2g_ars_get_candidate";
+    if (int rc = ars_check(h, a, who)) return rc;
+    if (c < 0 || c >= 2 * a->plan.n_delta) return fail(h, EV2G_ERR_ARG, std::string(who) + ": candidate " + std::to_string(c) + " is outside 0 .. " + std::to_string(2 * a->plan.n_delta - 1));
+    std::vector<float> image((size_t)a->plan.dev.stride);
+    if (int rc = ars_read(h, who, theta ? image.data() : nullptr, a->cand + (size_t)c * (size_t)a->plan.dev.stride, image.size() * sizeof(float))) return rc;
+    ars_unpack(a->plan.lay, image.data(), theta);
+    return EV2G_OK;
+}
+int ev2g_ars_get_deltas(ev2g_handle *h, ev2g_ars *a, float *delta) {
+    if (int rc = ars_check(h, a, "ev2g_ars_get_deltas")) return rc;
+    return ars_read(h, "ev2g_ars_get_deltas", delta, a->delta, (size_t)a->plan.n_delta * a->plan.lay.n_params * sizeof(float));
+}
+int ev2g_ars_get_env_returns(ev2g_handle *h, ev2g_ars *a, double *env_return, int n_envs) {
+    const char *who = "ev2g_ars_get_env_returns";
+    if (int rc = ars_check(h, a, who)) return rc;
+    if (!a->env_return || n_envs != a->rows_E) return fail(h, EV2G_ERR_ARG, std::string(who) + ": n_envs is not the env count of the object's rollouts");
+    return ars_read(h, who, env_return, a->env_return, (size_t)n_envs * sizeof(double));
+}
+int ev2g_ars_set_returns(ev2g_handle *h, ev2g_ars *a, const double *returns) {
+    const char *who = "ev2g_ars_set_returns";
+    if (int rc = ars_check(h, a, who)) return rc;
+    if (!returns) return fail(h, EV2G_ERR_ARG, std::string(who) + ": null argument");
+    HIPCHK(h, hipMemcpyAsync(a->ret, returns, (size_t)2 * a->plan.n_delta * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // returns is the caller's
+    a->returns_set = true;
+    return EV2G_OK;
+}
+int ev2g_ars_set_rates(ev2g_handle *h, ev2g_ars *a, double learning_rate, double delta_std) {
+    if (int rc = ars_check(h, a, "ev2g_ars_set_rates")) return rc;
+    if (int rc = fields_check(h, "ev2g_ars_set_rates", ars_rate_fields(learning_rate, delta_std))) return rc;
+    a->cfg.learning_rate = learning_rate; a->cfg.delta_std = delta_std;
+    return EV2G_OK;
+}
+int ev2g_ars_seed(ev2g_handle *h, ev2g_ars *a, uint64_t seed, uint64_t first_iteration) {
+    if (int rc = ars_check(h, a, "ev2g_ars_seed")) return rc;
+    a->seed = seed; a->iter = first_iteration;
+    return EV2G_OK;
+}
+int ev2g_ars_counters(ev2g_handle *h, ev2g_ars *a, uint64_t *next_iteration, int64_t *updates, int64_t *steps) {
+    if (int rc = ars_check(h, a, "ev2g_ars_counters")) return rc;
+    if (next_iteration) *next_iteration = a->iter;
+    if (updates) *updates = a->updates;
+    if (steps) *steps = a->steps;
+    return EV2G_OK;
+}
+
+int ev2g_host_ars_perturb(const float *theta, int n_delta, int n_params, double delta_std, uint64_t seed, uint64_t iteration, float *delta, float *cand) {
+    if (!theta || !delta) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ars_perturb: null argument");
+    if (n_delta < 1 || n_params < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ars_perturb: n_delta and n_params must be positive");
+    ars_host_perturb(theta, n_delta, n_params, delta_std, seed, iteration, delta, cand, [](uint64_t s, uint64_t j) { return ev2g_ac_normal(s, j); });
+    return EV2G_OK;
+}
+int ev2g_host_ars_returns(double *env_return, const double *reward, int k, int64_t r_stride, int n_envs, int n_candidates, double alive_bonus_offset,
+                          int64_t steps, double *returns) {
+    if (!env_return) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ars_returns: null argument");
+    if (k < 0 || n_envs < 1 || (reward && r_stride < n_envs) || (returns && (n_candidates < 1 || n_envs % n_candidates != 0)))
+        return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ars_returns: k < 0, a stride below n_envs, or n_envs is no multiple of n_candidates");
+    ars_host_returns(env_return, reward, k, (long long)r_stride, n_envs, n_candidates, alive_bonus_offset, (long long)steps, returns);
+    return EV2G_OK;
+}
+int ev2g_host_ars_update(float *theta, const float *delta, const double *returns, int n_delta, int n_top, int n_params, double learning_rate, int32_t *ranks,
+                         ev2g_ars_report *report) {
+    if (!theta || !delta || !returns || !ranks || !report) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ars_update: null argument");
+    if (n_delta < 1 || n_top < 1 || n_top > n_delta || n_params < 1) return fail(nullptr, EV2G_ERR_ARG, "ev2g_host_ars_update: 1 <= n_top <= n_delta and n_params >= 1 are needed");
+    report->iteration = 0; report->reserved = 0;
+    ars_host_update(theta, delta, returns, n_delta, n_top, n_params, learning_rate, ranks, report);
+    return EV2G_OK;
+}
 
 // ---- multi-GPU statistics exchange (RCCL) --------------------------------------------------------------------------------
 int ev2g_comm_get_unique_id(void *id) {

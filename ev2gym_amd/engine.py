@@ -203,6 +203,29 @@ def load_library(path: Optional[str] = None):
         "ev2g_tqc_truncate": (C.c_int, [vp] * 5 + [C.c_int] * 4 + [dbl, vp, vp]),
         "ev2g_host_tqc_target": (C.c_int, [vp] * 4 + [C.c_int] * 4 + [dbl, C.c_float, vp]),
         "ev2g_host_tqc_critic_head": (C.c_int, [vp, vp] + [C.c_int] * 4 + [vp, vp]),
+        "ev2g_ars_default_config": (C.c_int, [C.POINTER(_abi.ArsConfigC)]),
+        "ev2g_ars_query": (C.c_int, [C.POINTER(_abi.ArsConfigC)] + [C.c_int] * 5 + [C.POINTER(_abi.ArsInfoC)]),
+        "ev2g_ars_create": (C.c_int, [vp, C.POINTER(_abi.ArsConfigC)] + [C.c_int] * 5 + [C.c_float, vp, C.c_uint64, C.POINTER(vp)]),
+        "ev2g_ars_destroy": (None, [vp, vp]),
+        "ev2g_ars_perturb": (C.c_int, [vp, vp]),
+        "ev2g_ars_act": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+        "ev2g_ars_obs_f32": (vp, [vp, vp]),
+        "ev2g_ars_actions_f32": (vp, [vp, vp]),
+        "ev2g_ars_rollout": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, i64]),
+        "ev2g_ars_update": (C.c_int, [vp, vp]),
+        "ev2g_ars_get_report": (C.c_int, [vp, vp, C.POINTER(_abi.ArsReportC), vp, vp]),
+        "ev2g_ars_get_weights": (C.c_int, [vp, vp, vp]),
+        "ev2g_ars_set_weights": (C.c_int, [vp, vp, vp]),
+        "ev2g_ars_get_candidate": (C.c_int, [vp, vp, C.c_int, vp]),
+        "ev2g_ars_get_deltas": (C.c_int, [vp, vp, vp]),
+        "ev2g_ars_get_env_returns": (C.c_int, [vp, vp, vp, C.c_int]),
+        "ev2g_ars_set_returns": (C.c_int, [vp, vp, vp]),
+        "ev2g_ars_set_rates": (C.c_int, [vp, vp, dbl, dbl]),
+        "ev2g_ars_seed": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ev2g_ars_counters": (C.c_int, [vp, vp, C.POINTER(C.c_uint64), C.POINTER(i64), C.POINTER(i64)]),
+        "ev2g_host_ars_perturb": (C.c_int, [vp, C.c_int, C.c_int, dbl, C.c_uint64, C.c_uint64, vp, vp]),
+        "ev2g_host_ars_returns": (C.c_int, [vp, vp, C.c_int, i64, C.c_int, C.c_int, dbl, i64, vp]),
+        "ev2g_host_ars_update": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, dbl, vp, C.POINTER(_abi.ArsReportC)]),
         "ev2g_stat_name": (C.c_char_p, [C.c_int]),
         "ev2g_peek": (C.c_int, [vp, C.c_int, C.POINTER(_abi.EnvViewC)]),
         "ev2g_malloc": (vp, [vp, C.c_size_t]),
@@ -279,7 +302,11 @@ EXPORTED_SYMBOLS = [
     "ev2g_sac_set_rate", "ev2g_sac_seed", "ev2g_sac_act_seed", "ev2g_sac_counters", "ev2g_host_sac_head", "ev2g_host_sac_head_back", "ev2g_host_sac_y",
     "ev2g_tqc_default_config", "ev2g_tqc_create", "ev2g_tqc_destroy", "ev2g_tqc_update", "ev2g_tqc_critic_grad", "ev2g_tqc_actor_grad", "ev2g_tqc_apply",
     "ev2g_tqc_act", "ev2g_tqc_collect", "ev2g_tqc_get_grads", "ev2g_tqc_get_weights", "ev2g_tqc_get_z", "ev2g_tqc_get_log_pi", "ev2g_tqc_get_ent_coef",
-    "ev2g_tqc_set_rate", "ev2g_tqc_seed", "ev2g_tqc_act_seed", "ev2g_tqc_counters", "ev2g_tqc_truncate", "ev2g_host_tqc_target", "ev2g_host_tqc_critic_head"]
+    "ev2g_tqc_set_rate", "ev2g_tqc_seed", "ev2g_tqc_act_seed", "ev2g_tqc_counters", "ev2g_tqc_truncate", "ev2g_host_tqc_target", "ev2g_host_tqc_critic_head",
+    "ev2g_ars_default_config", "ev2g_ars_query", "ev2g_ars_create", "ev2g_ars_destroy", "ev2g_ars_perturb", "ev2g_ars_act", "ev2g_ars_obs_f32",
+    "ev2g_ars_actions_f32", "ev2g_ars_rollout", "ev2g_ars_update", "ev2g_ars_get_report", "ev2g_ars_get_weights", "ev2g_ars_set_weights",
+    "ev2g_ars_get_candidate", "ev2g_ars_get_deltas", "ev2g_ars_get_env_returns", "ev2g_ars_set_returns", "ev2g_ars_set_rates", "ev2g_ars_seed",
+    "ev2g_ars_counters", "ev2g_host_ars_perturb", "ev2g_host_ars_returns", "ev2g_host_ars_update"]
 
 
 def _ptr(x):
@@ -1191,6 +1218,96 @@ class Engine:
         self._check(self._lib.ev2g_tqc_truncate(self._h, _ptr(tq), _ptr(log_pi_next), _ptr(reward), _ptr(done), int(B), int(n_critics), int(n_quantiles), int(drop),
                                                 float(gamma), _ptr(log_ent_coef), _ptr(z_out)))
 
+    # ---- the ARS learner and its population actor (include/ev2g.h: ev2g_ars_*) ------------------------------------------------------------------
+    def ars_create(self, kind, d_in, h1, h2, d_out, lo, theta=None, seed=0, **config):
+        """An ARS learner (ev2g_ars_create): kind "MlpPolicy" or "LinearPolicy"; theta float32 [n_params] or None for zeros; config overrides
+        fields of sb3_contrib's defaults (ev2g_ars_config).  Freed by ars_destroy or with the engine."""
+        cfg = ars_config(**config)
+        th = None if theta is None else np.ascontiguousarray(theta, np.float32)
+        n = ars_query(kind, d_in, h1, h2, d_out, cfg)["n_params"]
+        if th is not None and th.shape != (n,):
+            raise ValueError(f"ars_create: theta has shape {th.shape}, expected {(n,)}")
+        out = C.c_void_p()
+        self._check(self._lib.ev2g_ars_create(self._h, C.byref(cfg), _abi.ARS_KINDS[kind], int(d_in), int(h1), int(h2), int(d_out), float(lo),
+                                              None if th is None else th.ctypes.data, int(seed) & (2 ** 64 - 1), C.byref(out)))
+        return out
+
+    def ars_destroy(self, a):
+        if a and self._h:
+            self._lib.ev2g_ars_destroy(self._h, a)
+
+    def ars_perturb(self, a):
+        self._check(self._lib.ev2g_ars_perturb(self._h, a))
+
+    def ars_act(self, a, obs32, n_rows, actions, population=False):
+        """DEVICE obs32 [n_rows, D] -> actions [n_rows, P] (ev2g_ars_act): under theta, or rows [c R, (c + 1) R) under candidate c."""
+        self._check(self._lib.ev2g_ars_act(self._h, a, _ptr(obs32), int(n_rows), int(bool(population)), _ptr(actions)))
+
+    def ars_obs_f32(self, a) -> int:
+        p = self._lib.ev2g_ars_obs_f32(self._h, a)
+        if not p:
+            self._check(_abi.ERR_STATE)
+        return p
+
+    def ars_actions_f32(self, a) -> int:
+        p = self._lib.ev2g_ars_actions_f32(self._h, a)
+        if not p:
+            self._check(_abi.ERR_STATE)
+        return p
+
+    def ars_rollout(self, a, k, population=True, reward=None, r_stride=0):
+        """k x (population or centre actor -> env step) from the object's observation row (ev2g_ars_rollout)."""
+        self._check(self._lib.ev2g_ars_rollout(self._h, a, int(k), int(bool(population)), _ptr(reward), int(r_stride)))
+
+    def ars_update(self, a):
+        self._check(self._lib.ev2g_ars_update(self._h, a))
+
+    def ars_get_report(self, a, n_delta) -> dict:
+        rep, ret, ranks = _abi.ArsReportC(), np.empty(2 * int(n_delta), np.float64), np.empty(int(n_delta), np.int32)
+        self._check(self._lib.ev2g_ars_get_report(self._h, a, C.byref(rep), ret.ctypes.data, ranks.ctypes.data))
+        return dict(returns=ret, ranks=ranks, sigma_r=rep.sigma_r, step=rep.step, refused=bool(rep.refused), first_bad=rep.first_bad, n_top=rep.n_top,
+                    iteration=rep.iteration)
+
+    def ars_get_weights(self, a, n_params):
+        th = np.empty(int(n_params), np.float32)
+        self._check(self._lib.ev2g_ars_get_weights(self._h, a, th.ctypes.data))
+        return th
+
+    def ars_set_weights(self, a, theta):
+        th = np.ascontiguousarray(theta, np.float32)
+        self._check(self._lib.ev2g_ars_set_weights(self._h, a, th.ctypes.data))
+
+    def ars_get_candidate(self, a, c, n_params):
+        th = np.empty(int(n_params), np.float32)
+        self._check(self._lib.ev2g_ars_get_candidate(self._h, a, int(c), th.ctypes.data))
+        return th
+
+    def ars_get_deltas(self, a, n_delta, n_params):
+        d = np.empty((int(n_delta), int(n_params)), np.float32)
+        self._check(self._lib.ev2g_ars_get_deltas(self._h, a, d.ctypes.data))
+        return d
+
+    def ars_get_env_returns(self, a):
+        r = np.empty(self.E, np.float64)
+        self._check(self._lib.ev2g_ars_get_env_returns(self._h, a, r.ctypes.data, self.E))
+        return r
+
+    def ars_set_returns(self, a, returns):
+        r = np.ascontiguousarray(returns, np.float64)
+        self._check(self._lib.ev2g_ars_set_returns(self._h, a, r.ctypes.data))
+
+    def ars_set_rates(self, a, learning_rate, delta_std):
+        self._check(self._lib.ev2g_ars_set_rates(self._h, a, float(learning_rate), float(delta_std)))
+
+    def ars_seed(self, a, seed, first_iteration=0):
+        self._check(self._lib.ev2g_ars_seed(self._h, a, int(seed) & (2 ** 64 - 1), int(first_iteration)))
+
+    def ars_counters(self, a):
+        """(the next perturb's iteration, updates queued, env steps since the last perturb)"""
+        n, u, st = C.c_uint64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.ev2g_ars_counters(self._h, a, C.byref(n), C.byref(u), C.byref(st)))
+        return n.value, u.value, st.value
+
     def stats(self, out=None) -> np.ndarray:
         """[E,17] get_statistics() scalars (utils.py:84-101) as a host array (or into a device `out`)."""
         if out is not None:
@@ -1550,3 +1667,54 @@ def host_tqc_critic_head(z, q, drop):
     dq, loss = np.empty_like(q), np.zeros(1, np.float32)
     _host_call(load_library().ev2g_host_tqc_critic_head(z.ctypes.data, q.ctypes.data, B, nc, nq, int(drop), dq.ctypes.data, loss.ctypes.data))
     return dq, float(loss[0])
+
+
+def ars_config(**config):
+    """sb3_contrib's defaults of ARS as an _abi.ArsConfigC (ev2g_ars_default_config), with `config`'s fields over them."""
+    cfg = _abi.ArsConfigC()
+    _host_call(load_library().ev2g_ars_default_config(C.byref(cfg)))
+    for k, v in config.items():
+        if not hasattr(cfg, k):
+            raise TypeError(f"ars_config: unknown config field {k}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def ars_query(kind, d_in, h1, h2, d_out, cfg=None) -> dict:
+    """Limits, n_params, bytes and LDS of an ARS learner of this shape (ev2g_ars_query); a refused shape or config raises EngineError."""
+    info = _abi.ArsInfoC()
+    _host_call(load_library().ev2g_ars_query(C.byref(cfg if cfg is not None else ars_config()), _abi.ARS_KINDS[kind], int(d_in), int(h1), int(h2), int(d_out),
+                                             C.byref(info)))
+    return {f[0]: getattr(info, f[0]) for f in _abi.ArsInfoC._fields_}
+
+
+def host_ars_perturb(theta, n_delta, delta_std, seed, iteration):
+    """Host twin of ev2g_ars_perturb (ev2g_host_ars_perturb): (delta [n_delta, n_params], cand [2 n_delta, n_params]) float32."""
+    theta = np.ascontiguousarray(theta, np.float32)
+    delta, cand = np.empty((int(n_delta), theta.size), np.float32), np.empty((2 * int(n_delta), theta.size), np.float32)
+    _host_call(load_library().ev2g_host_ars_perturb(theta.ctypes.data, int(n_delta), theta.size, float(delta_std), int(seed) & (2 ** 64 - 1), int(iteration),
+                                                    delta.ctypes.data, cand.ctypes.data))
+    return delta, cand
+
+
+def host_ars_returns(env_return, reward, n_candidates=0, alive_bonus_offset=0.0, steps=0):
+    """Host twin of the returns launches (ev2g_host_ars_returns): float64 `env_return` [E] += the rows reward [k, E] (None: nothing) IN PLACE;
+    returns the candidates' returns [n_candidates] (None for 0)."""
+    assert env_return.dtype == np.float64 and env_return.flags.c_contiguous
+    rw = None if reward is None else np.ascontiguousarray(reward, np.float64)
+    out = np.empty(int(n_candidates), np.float64) if n_candidates else None
+    _host_call(load_library().ev2g_host_ars_returns(env_return.ctypes.data, None if rw is None else rw.ctypes.data, 0 if rw is None else rw.shape[0],
+                                                    env_return.size if rw is None else rw.shape[1], env_return.size, int(n_candidates), float(alive_bonus_offset),
+                                                    int(steps), None if out is None else out.ctypes.data))
+    return out
+
+
+def host_ars_update(theta, delta, returns, n_top, learning_rate):
+    """Host twin of ev2g_ars_update (ev2g_host_ars_update): (new theta float32, report dict as Engine.ars_get_report's)."""
+    theta = np.array(theta, np.float32)
+    delta, returns = np.ascontiguousarray(delta, np.float32), np.ascontiguousarray(returns, np.float64)
+    n_delta = delta.shape[0]
+    ranks, rep = np.empty(n_delta, np.int32), _abi.ArsReportC()
+    _host_call(load_library().ev2g_host_ars_update(theta.ctypes.data, delta.ctypes.data, returns.ctypes.data, n_delta, int(n_top), theta.size, float(learning_rate),
+                                                   ranks.ctypes.data, C.byref(rep)))
+    return theta, dict(returns=returns.copy(), ranks=ranks, sigma_r=rep.sigma_r, step=rep.step, refused=bool(rep.refused), first_bad=rep.first_bad, n_top=rep.n_top)

@@ -1233,6 +1233,88 @@ int ev2g_pool_session_capacity(const ev2g_handle *h);
  * which = 3 / 4: the V2G / EV+PHEV fleet as rows of (share, battery kWh, max AC kW); returns the number of values written */
 int ev2g_gen_table(int which, int kind, double *out, int n_max);
 
+/* ---- ARS on the device: sb3_contrib's ARS (Augmented Random Search) with per-candidate weights (csrc/ev2g_ars.h, ev2g_ars_host.h) ----
+ *   MlpPolicy (EV2G_ARS_MLP):       obs -> ReLU(h1) -> ReLU(h2) -> linear(d_out) -> tanh, unscaled into the env's box [lo, 1]; theta = W1 | b1 | W2 | b2 | W3 | b3
+ *   LinearPolicy (EV2G_ARS_LINEAR): obs -> linear(d_out), no bias, clipped to [lo, 1] (h1, h2 are not read);                   theta = W
+ * every matrix [out, in] row-major (parameters_to_vector).  One iteration: ev2g_ars_perturb draws delta [n_delta, n_params] ~ N(0, 1) -- direction
+ * k's element i of iteration n is draw (n n_delta + k) n_params + i of ev2g_ac_host_normal's generator under the object's seed -- and writes the
+ * 2 n_delta candidates' packed weights (k: theta + delta_std delta_k, n_delta + k: theta - delta_std delta_k, float32, each operation rounded
+ * once); the population actor evaluates n_rows = C R rows as C = 2 n_delta candidates of R consecutive rows, each under ITS OWN weights, in one
+ * launch; ev2g_ars_rollout steps the engine's envs under it and sums every env's rewards (float64, steps ascending); ev2g_ars_update forms
+ * return[c] = sum of candidate c's envs ascending + alive_bonus_offset x the steps they took, ranks score_k = max(r+_k, r-_k) descending (ties to
+ * the lower k), keeps n_top directions, sigma_R = their 2 n_top returns' unbiased standard deviation (r+ in rank order, then r-),
+ * step = learning_rate / (n_top sigma_R + 1e-6), theta_i <- (float)(theta_i + step sum_j (r+_j - r-_j) delta_j,i) in float64, j in rank order.
+ * A return that is not finite refuses the update inside the launch: theta keeps its bits and the report says which candidate.  Everything is
+ * queued on the handle's stream with device-resident state; sums run in one fixed order, no atomics: the same calls give the same bits, and
+ * the host twins below give the device's bits.  A row's action depends on its candidate's weights alone, not on R, C or the row's place.
+ * LIMITS (a message per field otherwise): d_in <= 192, hidden widths 1 .. 256, d_out <= 64, 1 <= n_top <= n_delta <= 4096.
+ * The object belongs to the handle: freed by ev2g_ars_destroy or with ev2g_destroy. */
+#define EV2G_ARS_MLP 0
+#define EV2G_ARS_LINEAR 1
+typedef struct ev2g_ars ev2g_ars;
+typedef struct ev2g_ars_config {
+    double learning_rate, delta_std, alive_bonus_offset;   /* 0.02, 0.05, 0 */
+    int32_t n_delta, n_top;                                /* 8, 8 */
+} ev2g_ars_config;
+typedef struct ev2g_ars_info {
+    int32_t max_in, max_hidden, max_out, max_delta;        /* the limits */
+    int32_t n_params;
+    int64_t candidate_floats;                              /* one candidate's packed image */
+    int64_t image_bytes, delta_bytes, total_bytes;         /* 1 + 2 n_delta images; the directions; everything the object allocates at create */
+    int64_t lds_bytes;                                     /* of the population actor's workgroup */
+} ev2g_ars_info;
+typedef struct ev2g_ars_report {
+    double sigma_r, step;
+    int64_t iteration;                                     /* the iteration whose directions the update used */
+    int32_t refused, first_bad, n_top;                     /* refused != 0: first_bad is the first candidate whose return was not finite (else -1) */
+    int32_t reserved;
+} ev2g_ars_report;
+int ev2g_ars_default_config(ev2g_ars_config *cfg);
+/* what an object of this shape takes; a refused shape or config returns the code, ev2g_last_error(NULL) the message */
+int ev2g_ars_query(const ev2g_ars_config *cfg, int kind, int d_in, int h1, int h2, int d_out, ev2g_ars_info *out);
+/* theta: HOST float32 [n_params], or NULL for zeros (sb3_contrib's zero_policy) */
+int ev2g_ars_create(ev2g_handle *h, const ev2g_ars_config *cfg, int kind, int d_in, int h1, int h2, int d_out, float lo, const float *theta,
+                    uint64_t seed, ev2g_ars **out);
+void ev2g_ars_destroy(ev2g_handle *h, ev2g_ars *a);
+/* the next iteration's directions and candidate weights; zeroes the envs' returns and the step count; the iteration counter advances */
+int ev2g_ars_perturb(ev2g_handle *h, ev2g_ars *a);
+/* DEVICE obs32 [n_rows, d_in] -> actions [n_rows, d_out] in [lo, 1].  population == 0: every row under theta; else n_rows must be a positive
+ * multiple of 2 n_delta and rows [c R, (c + 1) R) run under candidate c (after an ev2g_ars_perturb). */
+int ev2g_ars_act(ev2g_handle *h, ev2g_ars *a, const float *obs32, int n_rows, int population, float *actions);
+/* The object's own float32 observation row [E, D] and action row [E, P] (allocated on first use): ev2g_reset_f32 into the first one starts an
+ * episode for ev2g_ars_rollout, which keeps it current. */
+float *ev2g_ars_obs_f32(ev2g_handle *h, ev2g_ars *a);
+float *ev2g_ars_actions_f32(ev2g_handle *h, ev2g_ars *a);
+/* k_steps x (population or centre actor on the object's observation row -> one-step launch), a segment inside one episode, then every env's
+ * rewards added to its return (the rows reward [k_steps, r_stride >= E] DEVICE float64 are kept when given).  On the fast path the step reads
+ * and writes the object's rows per launch; elsewhere through the registered float32 hand-over buffers (ev2g_set_step_extras, observation
+ * stride 0), as ev2g_ac_collect.  population != 0: E must be a positive multiple of 2 n_delta.  No link, grid or wrapper is applied. */
+int ev2g_ars_rollout(ev2g_handle *h, ev2g_ars *a, int k_steps, int population, double *reward, int64_t r_stride);
+/* the step from the envs' returns of the rollouts since the last perturb, or from ev2g_ars_set_returns' */
+int ev2g_ars_update(ev2g_handle *h, ev2g_ars *a);
+/* HOST read-backs; all synchronise; each out may be NULL.  returns [2 n_delta] float64, ranks [n_delta] (direction k's rank, 0 the best) */
+int ev2g_ars_get_report(ev2g_handle *h, ev2g_ars *a, ev2g_ars_report *report, double *returns, int32_t *ranks);
+int ev2g_ars_get_weights(ev2g_handle *h, ev2g_ars *a, float *theta);
+int ev2g_ars_set_weights(ev2g_handle *h, ev2g_ars *a, const float *theta);
+/* candidate c's parameter vector [n_params], unpacked from its image */
+int ev2g_ars_get_candidate(ev2g_handle *h, ev2g_ars *a, int c, float *theta);
+int ev2g_ars_get_deltas(ev2g_handle *h, ev2g_ars *a, float *delta);
+int ev2g_ars_get_env_returns(ev2g_handle *h, ev2g_ars *a, double *env_return, int n_envs);
+/* 2 n_delta HOST returns in front of the next update, in place of the envs' */
+int ev2g_ars_set_returns(ev2g_handle *h, ev2g_ars *a, const double *returns);
+int ev2g_ars_set_rates(ev2g_handle *h, ev2g_ars *a, double learning_rate, double delta_std);
+int ev2g_ars_seed(ev2g_handle *h, ev2g_ars *a, uint64_t seed, uint64_t first_iteration);
+/* the next perturb's iteration, updates queued, env steps since the last perturb (each may be NULL) */
+int ev2g_ars_counters(ev2g_handle *h, ev2g_ars *a, uint64_t *next_iteration, int64_t *updates, int64_t *steps);
+/* Host twins (HOST arrays), bit for bit what the launches compute.  perturb: delta [n_delta, n_params] and cand [2 n_delta, n_params] (may be
+ * NULL) of iteration n.  returns: env_return [n_envs] += the rows reward [k, r_stride] (NULL: nothing), then returns [n_candidates] (may be NULL)
+ * of n_envs / n_candidates consecutive envs each.  update: theta [n_params] in place, ranks [n_delta], the report. */
+int ev2g_host_ars_perturb(const float *theta, int n_delta, int n_params, double delta_std, uint64_t seed, uint64_t iteration, float *delta, float *cand);
+int ev2g_host_ars_returns(double *env_return, const double *reward, int k, int64_t r_stride, int n_envs, int n_candidates, double alive_bonus_offset,
+                          int64_t steps, double *returns);
+int ev2g_host_ars_update(float *theta, const float *delta, const double *returns, int n_delta, int n_top, int n_params, double learning_rate,
+                         int32_t *ranks, ev2g_ars_report *report);
+
 #ifdef __cplusplus
 }
 #endif
