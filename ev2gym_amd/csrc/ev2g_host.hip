@@ -4290,11 +4290,11 @@ int ev2g_ars_rollout(ev2g_handle *h, ev2g_ars *a, int k_steps, int population, d
     c.done = {a->done}; c.mask = {a->mask};   // (stride 0: the per-launch float32 rows need the full instantiation, which writes every output)
     c.count_steps = false;   // (as ev2g_ac_collect: the registered buffers do not advance)
     if (int rc = run_chain(h, c, k_steps)) return rc;
-    if (k_steps > 0) {
+    if (k_steps > 0 && population) {   // (a centre rollout is no part of the iteration: the envs' returns, the step count and roll_E stay as they are)
         hipLaunchKernelGGL(ev2g_ars_returns_kernel, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, h->stream, a->env_return, (const double *)c.reward.p, k_steps,
                            c.reward.stride, h->E);
         HIPCHK(h, hipGetLastError());
-        if (population) { a->steps += k_steps; a->roll_E = h->E; }
+        a->steps += k_steps; a->roll_E = h->E;
     }
     return EV2G_OK;
 }

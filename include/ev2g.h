@@ -1240,7 +1240,7 @@ int ev2g_gen_table(int which, int kind, double *out, int n_max);
  * k's element i of iteration n is draw (n n_delta + k) n_params + i of ev2g_ac_host_normal's generator under the object's seed -- and writes the
  * 2 n_delta candidates' packed weights (k: theta + delta_std delta_k, n_delta + k: theta - delta_std delta_k, float32, each operation rounded
  * once); the population actor evaluates n_rows = C R rows as C = 2 n_delta candidates of R consecutive rows, each under ITS OWN weights, in one
- * launch; ev2g_ars_rollout steps the engine's envs under it and sums every env's rewards (float64, steps ascending); ev2g_ars_update forms
+ * launch; ev2g_ars_rollout in population mode steps the engine's envs under it and sums every env's rewards (float64, steps ascending); ev2g_ars_update forms
  * return[c] = sum of candidate c's envs ascending + alive_bonus_offset x the steps they took, ranks score_k = max(r+_k, r-_k) descending (ties to
  * the lower k), keeps n_top directions, sigma_R = their 2 n_top returns' unbiased standard deviation (r+ in rank order, then r-),
  * step = learning_rate / (n_top sigma_R + 1e-6), theta_i <- (float)(theta_i + step sum_j (r+_j - r-_j) delta_j,i) in float64, j in rank order.
@@ -1285,8 +1285,10 @@ int ev2g_ars_act(ev2g_handle *h, ev2g_ars *a, const float *obs32, int n_rows, in
  * episode for ev2g_ars_rollout, which keeps it current. */
 float *ev2g_ars_obs_f32(ev2g_handle *h, ev2g_ars *a);
 float *ev2g_ars_actions_f32(ev2g_handle *h, ev2g_ars *a);
-/* k_steps x (population or centre actor on the object's observation row -> one-step launch), a segment inside one episode, then every env's
- * rewards added to its return (the rows reward [k_steps, r_stride >= E] DEVICE float64 are kept when given).  On the fast path the step reads
+/* k_steps x (population or centre actor on the object's observation row -> one-step launch), a segment inside one episode; the rows reward
+ * [k_steps, r_stride >= E] DEVICE float64 are kept when given, in both modes.  population != 0: then every env's rewards are added to its return
+ * and the steps counted.  population == 0 (an evaluation of theta) is no part of the iteration: it changes neither the envs' returns nor the step
+ * count, so it may stand anywhere between ev2g_ars_perturb and ev2g_ars_update.  On the fast path the step reads
  * and writes the object's rows per launch; elsewhere through the registered float32 hand-over buffers (ev2g_set_step_extras, observation
  * stride 0), as ev2g_ac_collect.  population != 0: E must be a positive multiple of 2 n_delta.  No link, grid or wrapper is applied. */
 int ev2g_ars_rollout(ev2g_handle *h, ev2g_ars *a, int k_steps, int population, double *reward, int64_t r_stride);

@@ -6,6 +6,12 @@
   * the host twins through the library: perturb bit for bit theta +- float32(delta * float32(delta_std)) with delta from ev2g_ac_host_normal at
     the stated indices (iteration n + 1 continues the range); update within one float32 rounding of `ars_update_numpy`; the crafted updates
     (ties to the lower index, equal returns, NaN, infinity); the returns in the stated order against a numpy loop, bit for bit;
+  * the cases of tests/test_ars_range_gpu.py, pinned on the float64 reference alone before the device is asked: on every ars_cases.EDGE_NETS
+    network (both boxes, and the saturated one) the candidates' actions pairwise more than 1e-3 apart at every C and R, fewer than 10 % of the
+    tanh pre-activations beyond 9, the linear policies' actions at both bounds and strictly inside, the shifted ports' pre-activations beyond
+    10 (a seed that misses one is passed over among ten fixed seeds; the count is printed); the large updates' returns -- pairwise distinct
+    scores; integer returns of eight values with equal scores on both sides of the n_top cut and directions k and k + 256 tied; one NaN at the
+    last candidate; one +inf above candidate 256 -- and the twin within one float32 rounding of the float64 update at n_delta up to 4096;
   * tests/host/ars_check.cpp, a stand-alone C++17 program, plain and under -fsanitize=address,undefined;
   * the Python-side refusals, the policies' state-dict names and the pack -> unpack round trip;
   * the compiler's resource report of every ev2g_ars_* kernel: no spills, no scratch, the population actor within 128 VGPRs."""
@@ -70,11 +76,14 @@ def test_host_perturb_is_two_float32_roundings_of_the_stated_draws():
     assert float(np.float32(std)) != std and (cand[:n_delta] != theta).any()
 
 
-@pytest.mark.parametrize("n_delta,n_top", ac.UPDATE_CASES)
+@pytest.mark.parametrize("n_delta,n_top", ac.UPDATE_CASES + ac.LARGE_UPDATES)
 def test_host_update_is_one_float32_rounding_from_the_float64_update(n_delta, n_top):
     from ev2gym_amd.ars import ars_update_numpy
     from ev2gym_amd.engine import host_ars_update
-    case = ac.update_case(n_delta, n_top)
+    if (n_delta, n_top) in ac.LARGE_UPDATES:   # the device's large updates (tests/test_ars_range_gpu.py): the bound holds for the twin before the device is asked
+        case = dict(ac.large_update(n_delta), returns=ac.large_returns(n_delta, n_top, "distinct"))
+    else:
+        case = ac.update_case(n_delta, n_top)
     ref, info = ars_update_numpy(case["theta"], case["delta"], case["returns"], n_top, case["lr"])
     new, rep = host_ars_update(case["theta"], case["delta"], case["returns"], n_top, case["lr"])
     tol = EPS32 * np.maximum(np.abs(ref), TINY32)
@@ -125,6 +134,78 @@ def test_host_returns_run_in_the_stated_order():
     assert np.array_equal(_bits(ret), _bits(want))
     with pytest.raises(EngineError):
         host_ars_returns(env, None, 5)   # 24 envs are no multiple of 5 candidates
+
+
+EDGE_PINS = [(tag, lo, False) for tag in sorted(ac.EDGE_NETS) for lo in (-1.0, 0.0)] + [("eighth", -1.0, True), ("eighth", 0.0, True)]
+
+
+@pytest.mark.parametrize("tag,lo,saturate", EDGE_PINS)
+def test_edge_cases_keep_their_pins_on_the_float64_reference(tag, lo, saturate):
+    """What tests/test_ars_range_gpu.py's forward cases rely on, on the float64 reference alone (ars_cases.edge_case): candidates more than 1e-3
+    apart at every C and R, tanh mostly unsaturated, the linear policies' actions at both bounds and inside, the shifted ports saturated."""
+    from ev2gym_amd.ars import ars_forward_numpy, split_theta
+    case = ac.edge_case(tag, lo, saturate)
+    kind, D, h1, h2, P = ac.net_of(tag)
+    print(f"ARS EDGE CASE {tag} lo {lo:g}{' saturated' if saturate else ''}: seeds skipped {case['seeds_skipped']}  " +
+          "  ".join(f"C {C}: " + " ".join(f"{k} {v:.3g}" for k, v in fig.items()) for C, fig in case["figures"].items()))
+    assert case["misses"] == [] and case["seeds_skipped"] < 10
+    assert case["theta"].size == ac.n_params_of(tag) and sorted(case["cands"]) == list(ac.EDGE_C)
+    for C in ac.EDGE_C:
+        assert case["cands"][C].shape == (C, case["theta"].size)
+        for R in ac.EDGE_R:
+            ref = case["refs"][C, R]
+            assert ref.shape == (C, R, P) and ref.min() >= lo and ref.max() <= 1.0
+    if saturate:
+        # |v| >= 10 (pinned by edge_case): tanh(v) is within 4.2e-9 of +-1 and rounds to exactly +-1 in float32, whose unscaled action is exactly
+        # 1 or lo; the float64 action stays 1 - O(1e-10) (and, at lo = 0, a 1e-11 that float32 could hold: the device's tanhf cannot)
+        assert np.float32(np.tanh(10.0)) == np.float32(1.0) and np.float32(np.tanh(-10.0)) == np.float32(-1.0) and 1.0 - np.tanh(10.0) < 4.2e-9
+        ref = case["refs"][6, 33]
+        for p, shift in case["sat"].items():
+            want = 1.0 if shift > 0 else lo
+            assert 0.0 < np.abs(ref[..., p] - want).max() < 5e-9, p
+        assert len(case["sat"]) == 29 and sum(s > 0 for s in case["sat"].values()) == 15
+    if kind == "LinearPolicy":   # (the reference clips: an element beyond a bound IS the bound)
+        w = split_theta(case["cands"][2][0], kind, D, h1, h2, P)
+        raw = case["rows"].astype(np.float64) @ w[0].astype(np.float64).T
+        assert np.array_equal(ars_forward_numpy(case["rows"], w, kind, lo), np.clip(raw, lo, 1.0))
+
+
+@pytest.mark.parametrize("n_delta,n_top", ac.LARGE_UPDATES)
+def test_large_returns_are_distinct_tied_and_bad_as_stated(n_delta, n_top):
+    distinct = ac.large_returns(n_delta, n_top, "distinct")
+    assert distinct.shape == (2 * n_delta,) and len(set(ac.scores(distinct).tolist())) == n_delta and np.isfinite(distinct).all()
+    ties = ac.large_returns(n_delta, n_top, "ties")
+    s = ac.scores(ties)
+    assert np.array_equal(ties, np.round(ties)) and len(set(ties.tolist())) == 8
+    ranked = np.sort(s)[::-1]
+    if n_top < n_delta:
+        assert ranked[n_top - 1] == ranked[n_top], "equal scores must stand on both sides of the n_top cut"
+    else:
+        assert len(set(s.tolist())) < n_delta
+    if n_delta > 256:
+        assert any(s[k] == s[k + 256] for k in range(n_delta - 256)), "directions k and k + 256 must tie for some k"
+        assert s[0] == s[256] and ac.stable_ranks(ties)[0] < ac.stable_ranks(ties)[256]
+    rank = ac.stable_ranks(ties)
+    assert sorted(rank.tolist()) == list(range(n_delta)) and all(s[a] >= s[b] for a, b in zip(np.argsort(rank)[:-1], np.argsort(rank)[1:]))
+    nan, inf = ac.large_returns(n_delta, n_top, "nan"), ac.large_returns(n_delta, n_top, "inf")
+    assert np.flatnonzero(~np.isfinite(nan)).tolist() == [2 * n_delta - 1] and np.isnan(nan[-1])
+    assert np.flatnonzero(~np.isfinite(inf)).tolist() == [ac.LARGE_INF_AT] and inf[ac.LARGE_INF_AT] == np.inf and 256 < ac.LARGE_INF_AT < 2 * n_delta
+    for bad in (nan, inf):
+        keep = np.isfinite(bad)
+        assert np.array_equal(bad[keep], distinct[keep])
+
+
+def test_large_update_twin_on_ties_and_bad_returns():
+    """host_ars_update at n_delta 257: ranks by "ties to the lower index" as numpy's stable argsort states it, and the refusals' first_bad"""
+    from ev2gym_amd.engine import host_ars_update
+    n_delta, n_top = 257, 1
+    case = ac.large_update(n_delta)
+    ties = ac.large_returns(n_delta, n_top, "ties")
+    new, rep = host_ars_update(case["theta"], case["delta"], ties, n_top, case["lr"])
+    assert np.array_equal(rep["ranks"], ac.stable_ranks(ties)) and not rep["refused"] and (new != case["theta"]).any()
+    for kind, at in (("nan", 2 * n_delta - 1), ("inf", ac.LARGE_INF_AT)):
+        new, rep = host_ars_update(case["theta"], case["delta"], ac.large_returns(n_delta, n_top, kind), n_top, case["lr"])
+        assert rep["refused"] and rep["first_bad"] == at and np.array_equal(_bits(new), _bits(case["theta"])), kind
 
 
 def test_ars_check_host_program(tmp_path):

@@ -1,6 +1,7 @@
 """The ARS learner on the device (csrc/ev2g_ars.h; ev2g_ars_*; ev2gym_amd/ars.py): the population actor against a float64 numpy forward on every
 row's OWN candidate, candidate indexing bit for bit, perturb and update against their host twins bit for bit, a whole episode in population mode
 against a twin engine and the returns' host twin, three train() iterations against the twin loop, the refusals and the teardown.
+These are the workload's own shapes; tests/test_ars_range_gpu.py runs the same kernels over the rest of the range the plan accepts.
 
 Engines: the PublicPST fixture tests/golden/pst_rand_s2 tiled to pools of 12 envs (and 8) x 20 ports, 112-step episodes (ev2g_step_wave; both
 collector routes) -- a short generated pool sees its first EV only around step 11, so its rewards are all zero and its returns check nothing.  Forward tolerance, per
